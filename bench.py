@@ -9,17 +9,23 @@ when the timed region starts (the PyTorch use-case); inputs follow the reference
 generator (uniform [-5, 5) emissions, uniform targets in [1, C-1], blank 0),
 seeded.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver under torch.distributed.run, one rank per GPU;
 utterances are independent, so each rank owns B utterances (weak scaling) and the
 only collective is an all_gather of the B scalar losses over RCCL.
 
-Prints ONE JSON line (see the contract in the task statement), including
+A plain run sets up, warms up, times the K steps and prints ONE JSON line: metric,
+value (losses/s), unit, higher_is_better, dtype, ms_per_step (one timed step).
+--dump-outputs DIR writes what the timed path computed in its last step (the losses and
+a fixed, seeded sample of the emission gradients) as DIR/<name>.npy.
+--full adds every side record to the line and to bench_out/last_full.json, among them
   roofline     -- forwardScore kernel: algorithmic bytes (8A + 8N per graph) /
                   hipEvent-timed launch duration vs the 8 TB/s HBM3E peak
   cpu_baseline -- the unmodified reference's parallelMap CTC pattern on all host
-                  cores (oracle/_ref) on a bounded sample of the same workload.
+                  cores (oracle/_ref) on a bounded sample of the same workload
+and the cold pass, the built-lattice step, the reference's API forms and programs,
+BASELINE's other configurations and the in-run parity check against the reference.
 """
 import argparse
 import ctypes as C
@@ -302,12 +308,12 @@ def parity_in_run(em, tg, losses, grads, T, Cn, U, n):
 
 def unmodified_caller(B):
     """The reference's own benchmark program, benchmarks/ctc.cpp:136-168, compiled UNMODIFIED against
-    include/gtn and linked to libgtn_amd.so (tests/dropin/Makefile): per-utterance graph functions called
+    include/gtn and linked to libgtn_amd.so (oracle/dropin.mk): per-utterance graph functions called
     from parallelMap threads, which the engine gathers into batched launches (gtnx_parallel_enter).  Its
     own configuration (T=1000, U=100, alphabet 28), its own timing loop (5 + 100 iterations)."""
     import re
     import subprocess
-    exe = os.path.join(ROOT, "tests", "dropin", "_bin", "bm_ctc")
+    exe = os.path.join(ROOT, "oracle", "_ref", "dropin", "bm_ctc")
     if not os.path.exists(exe):
         return None
     try:
@@ -326,7 +332,7 @@ def unmodified_caller(B):
                                          "source": "BASELINE.md (measured in the build container, other hardware)"}}
         # benchmarks/functions.cpp, unmodified too: compose of two explicit graphs (100 x 20 arcs against
         # 50 x (500 + 500 self loops)), unsorted and sorted -- the reference on one core: 98.6 / 6.6 ms
-        fexe = os.path.join(ROOT, "tests", "dropin", "_bin", "bm_functions")
+        fexe = os.path.join(ROOT, "oracle", "_ref", "dropin", "bm_functions")
         if os.path.exists(fexe):
             rf = subprocess.run([fexe], capture_output=True, text=True, timeout=240)
             ft = {k: float(v) for k, v in re.findall(r"Timing (\w+) \.\.\.\s+([0-9.e+-]+) msec", rf.stdout)}
@@ -385,7 +391,7 @@ def other_configs(args):
     out["C2"] = run_json([py, os.path.join(ROOT, "tools", "bench_configs.py"), "c2"], 300)
     out["C3_viterbi"] = run_json([py, os.path.join(ROOT, "tools", "bench_configs.py"), "c3v"], 600)
     out["C4"] = run_json([py, os.path.join(ROOT, "tools", "bench_c4.py"), "--steps", "4"], 600)
-    c5 = run_json([py, os.path.join(ROOT, "bench.py"), "--config", "c5", "--steps", "10", "--warmup", "2", "--no-configs",
+    c5 = run_json([py, os.path.join(ROOT, "bench.py"), "--full", "--config", "c5", "--steps", "10", "--warmup", "2", "--no-configs",
                    "--no-reference-api", "--no-unmodified-caller", "--no-built-lattice", "--cpu-baseline-seconds", "20"], 600,
                   env={"GTN_BENCH_OUT": os.path.join(OUT_DIR, "c5")})
     try:  # (the child's stdout line is the compact one; its full record is in its own side file)
@@ -556,6 +562,66 @@ def dry_run(args, dist, torch, world, rank, dev):
         leave_quietly()
 
 
+def headline(args, world, world_dist, forced, native, B, T, Cn, U, dt, priming_steps):
+    """the record of the timed loop: what a plain run prints, and what --full adds its side records to"""
+    return {
+        "metric": "CTC forward+backward losses/sec (T=1000, C=256)" if (T, Cn) == (1000, 256)
+        else f"CTC forward+backward losses/sec (T={T}, C={Cn})",
+        "value": world * B * args.steps / dt,
+        "unit": "losses/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup, "priming_steps": priming_steps,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": f"{'BASELINE config C3' if (B, T, Cn, U) == (512, 1000, 256, 100) else 'CTC'}: compose(ctc_target, emissions)+forwardScore CTC loss "
+                               f"fwd+bwd, T={T}, C={Cn}, U={U}, batch={B} per GPU",
+                   "global_batch": world * B,
+                   "parallelism": f"dp{world} (utterance sharding, all_gather of losses)",
+                   # (in `config` so that the driver's parsed record keeps it:) ranks in the RCCL process group
+                   # of THIS run (0: no process group)
+                   "rccl_ranks": world if world_dist else 0,
+                   "host": "python (gtn_amd/api.py)" if native is None else "C++ (include/gtn/, bench_native/ctc_step.cpp)"},
+        "collectives": ("RCCL (nccl backend): all_gather of the losses per step (asynchronous, overlapping the next step), "
+                        "barrier + all_reduce(MAX) around the timed region" + (" -- forced at world size 1 (GTN_BENCH_FORCE_DIST=1)" if forced and world == 1 else ""))
+        if world_dist else None,
+    }
+
+
+DUMP_GRAD_FLOATS = 8 << 20  # emission-gradient elements --dump-outputs writes at most (32 MB of float32)
+
+
+def dump_outputs(d, lg, grad_dev, keep, stream, B, T, Cn):
+    """--dump-outputs: what the timed path computed in its last step, as float32 .npy files in `d` -- the losses a
+    caller receives (this rank's; every rank's too when the step gathers them) and the emission gradients of a fixed,
+    seeded choice of utterances (all of them when they fit in DUMP_GRAD_FLOATS), in utterance order.  The inputs are
+    seeded (graphgen.ctc_inputs): the same arguments give the same inputs on every run."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    k = max(1, min(B, DUMP_GRAD_FLOATS // max(T * Cn, 1)))
+    pick = np.arange(B) if k == B else np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+    rows = max(1, min(T, DUMP_GRAD_FLOATS // (k * Cn)))  # (one utterance larger than the budget: its first frames)
+    with torch.cuda.stream(stream):
+        losses = lg.last_losses().cpu()
+        gathered = lg.last_gathered()
+        gathered = gathered.cpu() if gathered is not None else None
+        if grad_dev is not None:  # the C++ host: the step's gradients land in this [B, T, C] tensor
+            grads = grad_dev[torch.from_numpy(pick).to(grad_dev.device), :rows].cpu().numpy()
+        else:  # the Python host: the step returned its emission graphs
+            ems = keep[0]
+            grads = np.stack([np.asarray(ems[int(b)].grad().weights_to_numpy(), np.float32).reshape(T, Cn)[:rows]
+                              for b in pick])
+    stream.synchronize()
+    np.save(os.path.join(d, "losses.npy"), losses.numpy().astype(np.float32))
+    if gathered is not None:
+        np.save(os.path.join(d, "losses_all_ranks.npy"), gathered.numpy().astype(np.float32))
+    np.save(os.path.join(d, "emission_grads.npy"), np.ascontiguousarray(grads, np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -586,6 +652,15 @@ def main():
                     help="utterances of the timed batch checked against the reference in this run (default 64; 16 at C5)")
     ap.add_argument("--python-host", action="store_true",
                     help="drive the step through the Python interface instead of the C++ one")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step: losses.npy "
+                         "(float32 [B]; losses_all_ranks.npy [N*B] when N > 1) and emission_grads.npy (float32, a fixed "
+                         "seeded sample of the utterances' [T, C] gradients, at most 32 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every side record (cold pass, per-kernel rooflines from a profiled pass, built-lattice "
+                         "step, reference API forms and programs, BASELINE's other configurations, CPU baseline, in-run "
+                         "parity against the reference) and the full record bench_out/last_full.json; the --no-* "
+                         "options above select among them")
     args = ap.parse_args()
     if args.config == "c5":
         args.T, args.C, args.U = 2000, 1024, 200
@@ -688,17 +763,19 @@ def main():
     for _ in range(3):
         step()
     fence()
-    # ---- COLD pass: W warm-up + K timed steps exactly as the flags ask, on a GPU that has been busy for a few
-    # milliseconds only (its clocks are still on their way up): reported as ms_per_step_cold / value_cold
-    for _ in range(args.warmup):
-        step()
-    fence()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    fence()
     from gtn_amd.distributed import max_over_ranks
-    dt_cold = max_over_ranks(time.perf_counter() - t0, dev)
+    dt_cold = None
+    if args.full:
+        # ---- COLD pass: W warm-up + K timed steps exactly as the flags ask, on a GPU that has been busy for a few
+        # milliseconds only (its clocks are still on their way up): reported as ms_per_step_cold / value_cold
+        for _ in range(args.warmup):
+            step()
+        fence()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence()
+        dt_cold = max_over_ranks(time.perf_counter() - t0, dev)
     # ---- PRIMED pass (`value`): the GPU leaves its idle clocks some tens of milliseconds after work arrives; with
     # W = 5 and K = 20 the whole measurement is 17 ms long and would be taken on the way up (0.668 ms per step
     # against 0.630 over 300 steps).  PRIME_STEPS more untimed steps (about 0.2 s at C3; the same count on every
@@ -714,18 +791,31 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    gtn.prof_reset()
-    gtn.prof_enable(True)
     t0 = time.perf_counter()
     keep = None
     for _ in range(args.steps):
         keep = step()
     fence()
     dt = dt_local = time.perf_counter() - t0
-    gtn.prof_enable(False)
     dt = max_over_ranks(dt, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, lg, grad_dev if native is not None else None, keep, stream, B, T, Cn)
+    if not args.full:
+        # a plain run: the headline figure only -- no side records, no side file
+        line = compact_line(headline(args, world, world_dist, forced, native, B, T, Cn, U, dt, priming_steps)) \
+            if rank == 0 else None
+        del keep
+        gtn.set_stream(None)
+        gtn.synchronize()
+        gtn.empty_cache()
+        if world_dist:
+            dist.destroy_process_group()
+        if line is not None:
+            say_last(line, world)
+        elif world_dist:
+            leave_quietly()
+        return
 
-    prof = {n: gtn.prof_get(n) for n in gtn.prof_names()}
     host_ms = None
     if native is not None:
         try:  # host phases of the timed loop's last step (bench_native/ctc_step.cpp)
@@ -735,8 +825,7 @@ def main():
                                [round(float(x), 3) for x in buf]))
         except Exception:
             host_ms = None
-    loss_dev = lg.last_losses()  # (what the side legs below write into and read from)
-    losses_timed = loss_dev.cpu().numpy().copy()  # of the timed loop's last step
+    losses_timed = lg.last_losses().cpu().numpy().copy()  # of the timed loop's last step
     grad_timed = None
     if native is not None:
         try:
@@ -745,6 +834,16 @@ def main():
             stream.synchronize()
         except Exception:
             grad_timed = None
+    # ---- PROFILED pass: K more steps with the engine's hipEvent pairs around each kernel family, for the per-kernel
+    # figures below (kernel_ms_per_step, roofline); the timed loop above runs without them
+    gtn.prof_reset()
+    gtn.prof_enable(True)
+    for _ in range(args.steps):
+        keep = step()
+    fence()
+    gtn.prof_enable(False)
+    prof = {n: gtn.prof_get(n) for n in gtn.prof_names()}
+    loss_dev = lg.last_losses()  # (what the side legs below write into and read from)
     # composed-lattice size of utterance 0 (one extra untimed intersect)
     e0 = gtn.linear_graph_n(1, T, Cn, em_dev)
     comp = gtn.intersect(build_ctc_graphs(gtn, tg[:1]), e0)
@@ -906,32 +1005,14 @@ def main():
             parity = {"error": str(e)[:300], "ok": False}
     if rank == 0:
         losses = losses_timed
-        out = {
-            "metric": "CTC forward+backward losses/sec (T=1000, C=256)" if (T, Cn) == (1000, 256)
-            else f"CTC forward+backward losses/sec (T={T}, C={Cn})",
-            "value": world * B * args.steps / dt,
-            "unit": "losses/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup, "priming_steps": priming_steps,
-            "ms_per_step": dt / args.steps * 1e3,
-            # the same K steps after the same W warm-up steps WITHOUT the priming steps in front (clocks rising)
-            "ms_per_step_cold": dt_cold / args.steps * 1e3, "value_cold": world * B * args.steps / dt_cold,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": f"{'BASELINE config C3' if (B, T, Cn, U) == (512, 1000, 256, 100) else 'CTC'}: compose(ctc_target, emissions)+forwardScore CTC loss "
-                                   f"fwd+bwd, T={T}, C={Cn}, U={U}, batch={B} per GPU",
-                       "global_batch": world * B, "composed_nodes": n_nodes, "composed_arcs": n_arcs,
-                       "parallelism": f"dp{world} (utterance sharding, all_gather of losses)",
-                       # (in `config` so that the driver's parsed record keeps them:) ranks in the RCCL process group
-                       # of THIS run (0: no process group), and the same step through the reference's own API
-                       # (parallelMap over per-utterance lambdas, tests/native/bm_ctc_c256.cpp) beside `value`
-                       "rccl_ranks": world if world_dist else 0,
-                       "value_reference_api": ((reference_api or {}).get("reference_loop") or {}).get("losses_per_s"),
-                       "host": "python (gtn_amd/api.py)" if native is None else "C++ (include/gtn/, bench_native/ctc_step.cpp)"},
+        out = headline(args, world, world_dist, forced, native, B, T, Cn, U, dt, priming_steps)
+        # the same K steps after the same W warm-up steps WITHOUT the priming steps in front (clocks rising)
+        out["ms_per_step_cold"], out["value_cold"] = dt_cold / args.steps * 1e3, world * B * args.steps / dt_cold
+        out["config"]["composed_nodes"], out["config"]["composed_arcs"] = n_nodes, n_arcs
+        # the same step through the reference's own API (parallelMap over per-utterance lambdas,
+        # tests/native/bm_ctc_c256.cpp) beside `value`
+        out["config"]["value_reference_api"] = ((reference_api or {}).get("reference_loop") or {}).get("losses_per_s")
+        out.update({
             "roofline": roof,
             # every other kernel family of the timed loop against the same 8 TB/s
             "roofline_other": {k: v for k, v in roofs.items() if k != dominant},
@@ -944,13 +1025,10 @@ def main():
             # one entry per rank: its own wall time, host phases and host-thread budget (NUMA-pinned when N > 1)
             "per_rank": ranks,
             "numa": numa,
-            "collectives": ("RCCL (nccl backend): all_gather of the losses per step (asynchronous, overlapping the next step), "
-                            "barrier + all_reduce(MAX) around the timed region" + (" -- forced at world size 1 (GTN_BENCH_FORCE_DIST=1)" if forced and world == 1 else ""))
-            if world_dist else None,
             "loss_mean": float(np.mean(losses)),
             # the first utterances of the timed batch, losses and emission gradients, against the reference in this run
             "parity_in_run": parity,
-        }
+        })
         if world == 1 and not args.no_unmodified_caller:
             out["unmodified_caller"] = unmodified_caller(B)
         if world == 1 and native is not None and not args.no_reference_api:

@@ -1,13 +1,16 @@
 # The reference's OWN pybind11 binding (bindings/python/gtn/_*.cpp, seven modules + __init__.py), compiled UNMODIFIED
 # from where it lies under /root/reference against include/gtn (the header-only C++ mirror) and linked to
 # libgtn_amd.so: `import gtn` then IS the reference's Python package over the MI355X engine (SURVEY.md section 8(b):
-# "callers recompile against the new headers").  Outputs only into tests/pydropin/_ext/gtn/ (git-ignored, travels to
-# the GPU box like tests/dropin/_bin); the package's __init__.py goes there as bytecode -- no reference source is
-# copied into the repository.  tests/test_pydropin_gpu.py runs the reference's 47 Python tests and
-# examples/pytorch_loss.py through it.
-REF ?= /root/reference
-ROOT := $(abspath ../..)
-OUT := _ext/gtn
+# "callers recompile against the new headers").  Outputs only into oracle/_ref/py_ext/gtn/ (git-ignored, kept with the
+# rest of _ref/ where the reference is absent); the package's __init__.py goes there as bytecode -- no reference
+# source is copied into the repository.  tests/test_pydropin_gpu.py runs the reference's 47 Python tests and
+# examples/pytorch_loss.py through it.  Run by __graft_entry__.build():  make -C oracle pydropin
+ifndef REF
+$(error REF: the reference checkout -- run as `make -C oracle pydropin`)
+endif
+HERE := $(dir $(abspath $(lastword $(MAKEFILE_LIST))))
+ROOT := $(abspath $(HERE)..)
+OUT := $(HERE)_ref/py_ext/gtn
 PY ?= python3
 SUF := $(shell $(PY)-config --extension-suffix 2>/dev/null || $(PY) -c "import sysconfig; print(sysconfig.get_config_var('EXT_SUFFIX'))")
 PYINC := $(shell $(PY) -m pybind11 --includes)
@@ -27,4 +30,5 @@ $(OUT)/__init__.pyc: $(REF)/bindings/python/gtn/__init__.py
 	$(PY) -c "import py_compile; py_compile.compile('$<', cfile='$@', dfile='reference:bindings/python/gtn/__init__.py', doraise=True)"
 
 clean:
-	rm -rf _ext
+	rm -rf $(HERE)_ref/py_ext
+.PHONY: all clean

@@ -62,7 +62,7 @@ def test_bench_multi_rank_branch_over_rccl():
     import tempfile
     env = dict(os.environ, GTN_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(31500 + os.getpid() % 2000),
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", GTN_BENCH_OUT=tempfile.mkdtemp(prefix="gtn_bench_"))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "5", "--warmup", "2",
                         "--batch", "64", "--no-cpu-baseline", "--no-unmodified-caller", "--no-configs", "--no-reference-api",
                         "--no-built-lattice"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]

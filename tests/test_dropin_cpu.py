@@ -1,6 +1,6 @@
 """The host-only part of the drop-in proof, runnable without a GPU: the reference's
 graph_test / creations_test / utils_test (test/*.cpp, compiled unmodified against
-include/gtn by tests/dropin/Makefile) only build, inspect, copy, sort, print, save and
+include/gtn by oracle/dropin.mk) only build, inspect, copy, sort, print, save and
 load graphs -- no device op -- so they must pass on the CPU-only host as well."""
 import os
 import subprocess
@@ -8,13 +8,20 @@ import subprocess
 import pytest
 
 BIN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dropin", "_bin")
+REF_BIN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "dropin")
+OWN = ("gather_test", "region_test", "adjacency_refs_test")
+
+
+def _exe(name):
+    """own programs (tests/native) in tests/dropin/_bin, the reference's in oracle/_ref/dropin"""
+    return os.path.join(BIN if name in OWN else REF_BIN, name)
 
 
 @pytest.mark.parametrize("name", ["graph_test", "creations_test", "utils_test"])
 def test_reference_host_test_program(name):
-    exe = os.path.join(BIN, name)
+    exe = _exe(name)
     if not os.path.exists(exe):
-        pytest.skip("tests/dropin/_bin not built (needs /root/reference: __graft_entry__.build())")
+        pytest.skip("oracle/_ref/dropin not built (needs the reference at build time: __graft_entry__.build())")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert "All tests passed" in r.stdout
@@ -32,10 +39,10 @@ def test_headers_and_abi_over_the_unmodified_reference(name, tmp_path):
     and the ABI's semantics (aliasing, exceptions, grad functions, formats) are the reference's.
     (tests/test_dropin_gpu.py runs the same binaries on the HIP engine.)"""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(BIN, name)
+    exe = _exe(name)
     ref = os.path.join(root, "oracle", "_ref", "libgtn_ref.so")
     if not os.path.exists(exe) or not os.path.exists(ref):
-        pytest.skip("needs tests/dropin/_bin and oracle/_ref (built from /root/reference by __graft_entry__.build())")
+        pytest.skip("needs oracle/_ref (built from the reference by __graft_entry__.build())")
     os.symlink(ref, tmp_path / "libgtn_amd.so")  # the binaries ask for this name; LD_LIBRARY_PATH precedes RUNPATH
     env = dict(os.environ, LD_LIBRARY_PATH=str(tmp_path) + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
@@ -52,12 +59,12 @@ def test_reference_examples_build_and_run_over_the_reference(name, tmp_path):
     headers the reference pulls in transitively (<iostream>, <cassert>) -- and the examples run to completion,
     their own asserts included, on the reference backend behind the C ABI."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(BIN, "ex_" + name)
+    exe = _exe("ex_" + name)
     ref = os.path.join(root, "oracle", "_ref", "libgtn_ref.so")
     if not os.path.exists(exe) or not os.path.exists(ref):
-        pytest.skip("needs tests/dropin/_bin and oracle/_ref (built from /root/reference by __graft_entry__.build())")
+        pytest.skip("needs oracle/_ref (built from the reference by __graft_entry__.build())")
     for b in ("ctc", "functions"):
-        assert os.path.exists(os.path.join(BIN, "bm_" + b)), "benchmarks/%s.cpp did not build" % b
+        assert os.path.exists(_exe("bm_" + b)), "benchmarks/%s.cpp did not build" % b
     os.symlink(ref, tmp_path / "libgtn_amd.so")
     env = dict(os.environ, LD_LIBRARY_PATH=str(tmp_path) + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))

@@ -1,14 +1,24 @@
 """Drop-in proof: the reference's own Catch2 test programs (test/*.cpp), compiled
-UNMODIFIED against include/gtn and linked to libgtn_amd.so by tests/dropin/Makefile
-(run from __graft_entry__.build() where /root/reference exists), executed here on
-the GPU.  Nothing is read from /root/reference at run time: the binaries are
-prebuilt and travel with the snapshot."""
+UNMODIFIED against include/gtn and linked to libgtn_amd.so by oracle/dropin.mk
+into oracle/_ref/dropin (run from __graft_entry__.build() where the reference exists),
+and the repository's own programs (tests/native, built by tests/dropin/Makefile into
+tests/dropin/_bin), executed here on the GPU.  Nothing is read from the reference at
+run time: the reference's binaries are prebuilt and kept with oracle/_ref."""
 import os
 import subprocess
 
 import pytest
 
 BIN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dropin", "_bin")
+REF_BIN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "dropin")
+OWN = ("gather_test", "region_test", "adjacency_refs_test", "bm_ctc_c256")
+
+
+def _exe(name):
+    """own programs (tests/native) in tests/dropin/_bin, the reference's in oracle/_ref/dropin"""
+    return os.path.join(BIN if name in OWN else REF_BIN, name)
+
+
 PROGRAMS = [
     "graph_test",
     "functions_test",
@@ -27,7 +37,7 @@ PROGRAMS = [
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", PROGRAMS)
 def test_reference_test_program(name):
-    exe = os.path.join(BIN, name)
+    exe = _exe(name)
     if not os.path.exists(exe):
         pytest.fail(f"{exe} missing: run __graft_entry__.build() where /root/reference is available")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
@@ -45,7 +55,7 @@ def test_reference_example_program(name):
     """the reference's CTC / ASG criteria (examples/ctc.cpp, examples/asg.cpp), unmodified, on the engine:
     same output as built against the reference itself (tests/golden/make_examples_expected.py)"""
     import json
-    exe = os.path.join(BIN, name)
+    exe = _exe(name)
     if not os.path.exists(exe):
         pytest.fail(f"{exe} missing: run __graft_entry__.build() where /root/reference is available")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
@@ -58,7 +68,7 @@ def test_reference_ctc_benchmark_runs():
     """benchmarks/ctc.cpp, unmodified (per-utterance calls from parallelMap threads, gathered by the
     engine into batched launches): all five timings come out"""
     import re
-    exe = os.path.join(BIN, "bm_ctc")
+    exe = _exe("bm_ctc")
     if not os.path.exists(exe):
         pytest.fail(f"{exe} missing: run __graft_entry__.build() where /root/reference is available")
     r = subprocess.run([exe, "16"], capture_output=True, text=True, timeout=600)
@@ -80,7 +90,7 @@ def test_reference_loop_at_c3_matches_one_call_at_a_time(alphabet):
     caller's emission buffer WIPED between the two maps -- setWeights copies (graph.cpp:179-181), and the engine
     makes that copy inside the region's forward sweep"""
     import json
-    exe = os.path.join(BIN, "bm_ctc_c256")
+    exe = _exe("bm_ctc_c256")
     if not os.path.exists(exe):
         pytest.fail(f"{exe} missing: run __graft_entry__.build() where /root/reference is available")
     r = subprocess.run([exe, "64", str(alphabet), "3", "device", "check"], capture_output=True, text=True, timeout=600)

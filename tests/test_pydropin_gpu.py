@@ -3,12 +3,12 @@
 autograd, criteria, parallel forms) and its PyTorch CTC loss example (examples/pytorch_loss.py:19-102), unmodified,
 with `import gtn` resolving to gtn_amd over libgtn_amd.so -- the MI355X engine, not the reference library
 (tests/test_pydropin_cpu.py runs the same sources on the reference backend).  The GPU box has no /root/reference:
-the tests are run from their bytecode (tests/pydropin/_pyc, compiled where the sources lie by
-tests/pydropin/build_pyc.py: the compiled form of the reference's tests travels like tests/dropin/_bin).
+the tests are run from their bytecode (oracle/_ref/pyc, compiled where the sources lie by
+oracle/build_pyc.py: the compiled form of the reference's tests is kept with the rest of oracle/_ref).
 
 Two bindings, the same tests: `ctypes` = gtn_amd/api.py (this repository's Python mirror over the C ABI), and `pybind11` =
 the REFERENCE'S OWN binding (bindings/python/gtn/_*.cpp + __init__.py), compiled unmodified against include/gtn and
-linked to libgtn_amd.so by tests/pydropin/Makefile -- the caller SURVEY.md section 8(b) names, recompiled, not rewritten."""
+linked to libgtn_amd.so by oracle/pydropin.mk -- the caller SURVEY.md section 8(b) names, recompiled, not rewritten."""
 import glob
 import os
 import subprocess
@@ -19,7 +19,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PYC = os.path.join(ROOT, "tests", "pydropin", "_pyc")
+PYC = os.path.join(ROOT, "oracle", "_ref", "pyc")
 
 RUNNER = r'''
 import importlib.machinery, importlib.util, sys, unittest
@@ -36,13 +36,13 @@ sys.exit(0 if res.wasSuccessful() else 1)
 '''
 
 
-EXT = os.path.join(ROOT, "tests", "pydropin", "_ext")
+EXT = os.path.join(ROOT, "oracle", "_ref", "py_ext")
 
 
 def _env(tmp_path, binding="ctypes"):
     if binding == "pybind11":
         if not glob.glob(os.path.join(EXT, "gtn", "_graph*.so")):
-            pytest.skip("tests/pydropin/_ext not built (needs /root/reference: __graft_entry__.build())")
+            pytest.skip("oracle/_ref/py_ext not built (needs the reference at build time: __graft_entry__.build())")
         pkgroot = EXT
     else:
         pkg = tmp_path / "gtn"
@@ -67,7 +67,7 @@ MODULES = ["test_autograd", "test_bindings", "test_creations", "test_criterions"
 def test_reference_python_binding_tests_run_on_the_engine(name, binding, tmp_path):
     path = os.path.join(PYC, name + ".pyc")
     if not os.path.exists(path):
-        pytest.skip("tests/pydropin/_pyc not built (needs /root/reference: __graft_entry__.build())")
+        pytest.skip("oracle/_ref/pyc not built (needs the reference at build time: __graft_entry__.build())")
     runner = tmp_path / "run_module.py"
     runner.write_text(RUNNER)
     r = subprocess.run([sys.executable, str(runner), name, path], capture_output=True, text=True, timeout=900,
@@ -81,7 +81,7 @@ def test_reference_python_binding_tests_run_on_the_engine(name, binding, tmp_pat
 def test_reference_pytorch_loss_example_runs_on_the_engine(binding, tmp_path):
     path = os.path.join(PYC, "pytorch_loss.pyc")
     if not os.path.exists(path):
-        pytest.skip("tests/pydropin/_pyc not built (needs /root/reference: __graft_entry__.build())")
+        pytest.skip("oracle/_ref/pyc not built (needs the reference at build time: __graft_entry__.build())")
     r = subprocess.run([sys.executable, path], capture_output=True, text=True, timeout=900, env=_env(tmp_path, binding),
                        cwd=str(tmp_path))
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]

@@ -5,7 +5,7 @@ tag=${1:-quick}
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-q="--gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-built-lattice --no-configs --no-reference-api --no-unmodified-caller"
+q="--full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-built-lattice --no-configs --no-reference-api --no-unmodified-caller"
 for rep in 1 2; do
   timeout 200 python bench.py $q 2>$out/b_$rep.err | tail -n 1 > $out/b_$rep.json
   python -c "import json; d=json.load(open('$out/b_$rep.json')); print('rep $rep: value', round(d['value']), 'ms_per_step', round(d['ms_per_step'],4), 'priming', d.get('priming_steps'), 'frac', round(d['roofline']['frac'],3), 'parity', d['parity_in_run']['ok'])"

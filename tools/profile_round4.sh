@@ -30,7 +30,7 @@ pmc() {  # name, counters, command...
   local s=$(find $OUT/tmp_$name -name "*counter_collection.csv" | head -1); [ -n "$s" ] && cp $s $OUT/${name}.csv
   rm -rf $OUT/tmp_$name
 }
-B="python $REPO/bench.py --no-cpu-baseline --no-unmodified-caller --no-configs --no-reference-api"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-unmodified-caller --no-configs --no-reference-api"
 stats bm_ctc_c256 $REPO/tests/dropin/_bin/bm_ctc_c256 512 256 10 device
 stats c5 $B --no-built-lattice --config c5 --steps 3 --warmup 1
 pmc c5_pmc_FETCH_SIZE FETCH_SIZE $B --no-built-lattice --config c5 --steps 2 --warmup 1
