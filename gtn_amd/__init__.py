@@ -65,6 +65,7 @@ prof_names = _api.prof_names
 debug_symbolic_route = _api.debug_symbolic_route
 debug_viterbi_ties = _api.debug_viterbi_ties
 debug_tie_ranks = _api.debug_tie_ranks
+debug_align_stats = getattr(_api, "debug_align_stats", None)  # (Batch.viterbi_align: which route aligned how many)
 
 
 def load_txt(text):

@@ -719,6 +719,33 @@ def make_api(lib):
             off = np.ascontiguousarray(offsets, dtype=np.int64)
             check(lib.gtnx_batch_grads_device(self._h, _as_dev_ptr(device_out), off.ctypes.data))
 
+        def viterbi_align(self, labels_out, tokens_out=None, scores_out=None, frames=None, row_stride=None):
+            """forced alignment with the results left on the device (gtnx_batch_viterbi_align): row b of `labels_out`
+            (int32 CUDA tensor [B, >= T], or a device address with `row_stride` entries between rows) gets the label of every frame of
+            element b's best path, -1 past the path and everywhere when no path exists; `tokens_out` the index into
+            the label sequence (-1 on blank frames), `scores_out` (float32 [B]) the path scores; `frames`: per-element
+            frame counts.  A composition of Batch.ctc_targets with Batch.linear is one launch with no copy back and no
+            wait; other batches go through viterbi_path (tokens_out and frames are errors there)."""
+            n = len(self)
+            stride = row_stride
+            for t in (labels_out, tokens_out):
+                if t is None or not hasattr(t, "data_ptr"):
+                    continue
+                if t.element_size() != 4 or t.dim() != 2 or t.shape[0] < n or (t.shape[1] > 1 and t.stride(1) != 1):
+                    raise ValueError("viterbi_align: outputs must be int32 tensors [B, T] with contiguous rows")
+                if stride is not None and t.stride(0) != stride:
+                    raise ValueError("viterbi_align: labels_out and tokens_out must have the same row stride")
+                stride = t.stride(0)
+            if stride is None:
+                raise ValueError("viterbi_align: a device address needs row_stride")
+            fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32)
+            if fr is not None and fr.shape != (n,):
+                raise ValueError("viterbi_align: one frame count per element")
+            check(lib.gtnx_batch_viterbi_align(self._h, fr.ctypes.data if fr is not None else None,
+                                               _as_dev_ptr(labels_out), int(stride),
+                                               _as_dev_ptr(tokens_out) if tokens_out is not None else None,
+                                               _as_dev_ptr(scores_out) if scores_out is not None else None))
+
     ns.Batch = Batch
 
     def _batch_fn(cfn, *args):
@@ -834,6 +861,15 @@ def make_api(lib):
         check(lib.gtnx_debug_viterbi_ties(C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def debug_align_stats():
+        """(fast, fallback): utterances Batch.viterbi_align has aligned so far by its one launch / through the path
+        graphs of viterbi_path (include/gtn_amd.h: gtnx_batch_align_stats)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(lib.gtnx_batch_align_stats(C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    if hasattr(lib, "gtnx_batch_align_stats"):
+        ns.debug_align_stats = debug_align_stats
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties
 

@@ -31,6 +31,22 @@ extern "C" __attribute__((visibility("default"))) int gtn_ctc_loss_n(const void*
   }
 }
 
+// CTC forced alignment.  emissions: DEVICE float [B][T][C]; targets / lengths: host int32 (concatenated / [B]);
+// frames: host int32 [B] or null; labels: DEVICE int32 [B][T]; tokens: DEVICE int32 [B][T] or null; scores: DEVICE
+// float [B] or null.  Returns 0, or -1 with the message in gtn_criteria_last_error().
+extern "C" __attribute__((visibility("default"))) int gtn_ctc_align_n(const void* emissions, const int* targets,
+                                                                      const int* lengths, int B, int T, int C,
+                                                                      int blank, const int* frames, void* labels,
+                                                                      void* tokens, void* scores) {
+  try {
+    gtn::criteria::ctcAlignBatch(emissions, targets, lengths, B, T, C, blank, frames, labels, tokens, scores);
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
 // The same, as benchmarks/ctc.cpp:150-165 runs it: target graphs with calcGrad = true, and THEIR gradients too.
 // target_grad: DEVICE float, utterance b's arc gradients (arc ids of benchmarks/ctc.cpp:40-58's addArc order) at
 // target_grad + target_grad_offsets[b]; grad must be non-null.

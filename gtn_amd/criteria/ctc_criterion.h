@@ -108,5 +108,28 @@ inline void ctcLossBatch(
   ctcLossBatch(emissions, flat.data(), len.data(), (int)targets.size(), T, C, blank, lossDev, gradDev, targetGrad, times);
 }
 
+/** CTC forced alignment of a batch, results on the device: per utterance the best path of target_b ∩ emissions_b
+ *  (viterbiPath, shortest.cpp:190-272) as the label of every frame (`labels`, device int32 [B][T]), the index of the
+ *  frame's token in the target, -1 on blank frames (`tokens`, device int32 [B][T] or null) and the path score
+ *  (`scores`, device float [B] or null).  `frames`: host [B] or null -- how many of the T rows of each utterance
+ *  count; entries past them are -1.  `emissions`: device [B][T][C], read in place.  Nothing is copied back. */
+inline void ctcAlignBatch(
+    const void* emissions,
+    const int* targets,  // target sequences back to back
+    const int* lengths,  // [B]
+    int B,
+    int T,
+    int C,
+    int blank,
+    const int* frames,
+    void* labels,
+    void* tokens,
+    void* scores) {
+  Batch ctcs = Batch::ctcTargets(targets, lengths, B, blank, /*calcGrad=*/false);
+  Batch ems = Batch::linear(B, T, C, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  Batch comp = batched::intersect(ctcs, ems);
+  batched::viterbiAlign(comp, static_cast<int*>(labels), T, static_cast<int*>(tokens), static_cast<float*>(scores), frames);
+}
+
 } // namespace criteria
 } // namespace gtn

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <limits>
 #include <unordered_map>
 #include <unordered_set>
 
@@ -953,6 +954,124 @@ BatchP batch_shortest_distance(const BatchP& x, bool tropical) {
 BatchP batch_viterbi_path(const BatchP& x) {
   batch_materialise(*x);
   return batch_from_graphs(op_viterbi_path(x->graphs));
+}
+
+// ---- forced alignment with device-resident output (align.hip) ------------------------------------------------
+namespace {
+std::atomic<int64_t> g_align_fast{0}, g_align_fallback{0};
+
+// every other batch: the path graphs of batch_viterbi_path, their labels read on the host, one upload
+void align_fallback(const BatchP& x, const int* frames, int* labels_dev, int64_t row_stride, int* tokens_dev,
+                    float* scores_dev) {
+  if (tokens_dev)
+    throw_invalid("[gtnx_batch_viterbi_align] token indices are defined for device-built CTC targets composed with a "
+                  "linear batch only (this batch takes the path-graph route)");
+  if (frames)
+    throw_invalid("[gtnx_batch_viterbi_align] per-utterance frame counts need device-built CTC targets composed with a "
+                  "linear batch (this batch takes the path-graph route)");
+  GTNX_HOST_T("batch.viterbi_align.fallback");
+  Runtime& rt = Runtime::get();
+  const int n = x->n;
+  // (a PRODUCT's rows are as long as its chains; other batches: as long as the longest path)
+  int64_t width = (x->kind == Batch::PRODUCT && x->chain && x->chain->kind == Batch::LINEAR) ? x->chain->M : 0;
+  BatchP paths = batch_viterbi_path(x);
+  for (int b = 0; b < n; ++b) width = std::max<int64_t>(width, paths->graphs[size_t(b)].num_arcs());
+  if (width > row_stride) throw_invalid("[gtnx_batch_viterbi_align] row_stride is shorter than the longest path");
+  PinnedMemP hl = rt.alloc_pinned(sizeof(int) * size_t(n) * size_t(width ? width : 1));
+  PinnedMemP hs = rt.alloc_pinned(sizeof(float) * size_t(n));
+  std::fill(hl->as<int>(), hl->as<int>() + size_t(n) * size_t(width), -1);
+  for (int b = 0; b < n; ++b) {
+    Graph& g = paths->graphs[size_t(b)];
+    const int64_t len = g.num_arcs();
+    float score = g.num_nodes() > 0 ? 0.0f : -std::numeric_limits<float>::infinity();
+    if (len > 0) {
+      g.s->ensure_host();
+      std::copy(g.s->il.begin(), g.s->il.begin() + len, hl->as<int>() + size_t(b) * size_t(width));
+      const float* w = g.weights_host(false);
+      for (int64_t t = 0; t < len; ++t) score += w[t];  // (in path order, as the recursion accumulates it)
+    }
+    hs->as<float>()[b] = score;
+  }
+  if (width > 0)
+    HIP_CHECK(hipMemcpy2DAsync(labels_dev, sizeof(int) * size_t(row_stride), hl->ptr, sizeof(int) * size_t(width),
+                               sizeof(int) * size_t(width), size_t(n), hipMemcpyHostToDevice, rt.stream()));
+  if (scores_dev) rt.h2d_pinned(scores_dev, hs->ptr, sizeof(float) * size_t(n));
+  g_align_fallback.fetch_add(n);
+}
+}  // namespace
+
+void batch_align_stats(int64_t* fast, int64_t* fallback) {
+  if (fast) *fast = g_align_fast.load();
+  if (fallback) *fallback = g_align_fallback.load();
+}
+
+void batch_viterbi_align(const BatchP& x, const int* frames, int* labels_dev, int64_t row_stride, int* tokens_dev,
+                         float* scores_dev) {
+  GTNX_HOST_T("batch.viterbi_align");
+  Runtime& rt = Runtime::get();  // (first: without a device this is a device error, whatever the arguments)
+  if (!labels_dev) throw_invalid("[gtnx_batch_viterbi_align] null labels pointer");
+  if (row_stride < 0) throw_invalid("[gtnx_batch_viterbi_align] negative row stride");
+  const int n = x->n;
+  if (n <= 0) return;
+  // a kernel of this device writes the results: memory of another GPU of the process is refused, not written
+  if (!ptr_local_to(labels_dev, rt.device()) || (tokens_dev && !ptr_local_to(tokens_dev, rt.device())) ||
+      (scores_dev && !ptr_local_to(scores_dev, rt.device())))
+    throw_invalid("[gtnx_batch_viterbi_align] an output pointer is not memory of the engine's current device");
+  bool fast = x->kind == Batch::PRODUCT && x->fixed && x->chain && x->fixed->kind == Batch::CTC_TARGETS && !x->fixed->fal &&
+              x->chain->kind == Batch::LINEAR && x->fixed->rec_mem && x->fixed->n == n && x->chain->n == n;
+  if (fast) {
+    const Batch& fx = *x->fixed;
+    const Batch& ch = *x->chain;
+    const int vec = ch.C % 4 == 0 && (reinterpret_cast<uintptr_t>(ch.w_dev) & 15) == 0;
+    fast = band_align_ok(fx.max_nodes, ch.C, vec) && fx.max_label < ch.C;
+    // the closed form of the queue ranks (ops_band.cpp tie_ranks) holds with the blank below every label
+    for (size_t i = 0; i < fx.labels.size() && fast; ++i) fast = fx.labels[i] > fx.blank;
+  }
+  if (!fast) {
+    align_fallback(x, frames, labels_dev, row_stride, tokens_dev, scores_dev);
+    return;
+  }
+  Batch& fx = *x->fixed;
+  Batch& ch = *x->chain;
+  const int T = ch.M, C = ch.C;
+  if (row_stride < T) throw_invalid("[gtnx_batch_viterbi_align] row_stride is shorter than the chains");
+  if (frames)
+    for (int b = 0; b < n; ++b)
+      if (frames[b] < 0 || frames[b] > T) throw_invalid("[gtnx_batch_viterbi_align] a frame count outside 0 .. T");
+  if (ch.w_pend) ch.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  // back-pointer planes: 2 bits per (time, node), one 256-byte row of words per 16 / NPL steps (align.hip)
+  const int npl = align_npl(fx.max_nodes);
+  const size_t plane = align_up((size_t(T) * size_t(npl) + 15) / 16 * 256 + 256, 256);
+  DevMemP work = rt.alloc(plane * size_t(n));
+  std::vector<AlignArgs> tab(static_cast<size_t>(n));
+  double abytes = 0;
+  for (int b = 0; b < n; ++b) {
+    AlignArgs& a = tab[size_t(b)];
+    a = AlignArgs{};
+    const int* t = fx.labels.data() + fx.lab_off[size_t(b)];
+    const int U = fx.lab_off[size_t(b) + 1] - fx.lab_off[size_t(b)];
+    const size_t N = size_t(2 * U + 1);
+    char* base = fx.rec_mem->as<char>(fx.rec_off[size_t(b)]);
+    a.nodes = reinterpret_cast<BandNode*>(base);
+    a.nflags = reinterpret_cast<uint8_t*>(base + align_up(sizeof(BandNode) * N, 64));
+    a.em = ch.w_dev + size_t(b) * size_t(T) * size_t(C);
+    a.bp = work->as<unsigned>(plane * size_t(b));
+    a.labels = labels_dev + int64_t(b) * row_stride;
+    a.tokens = tokens_dev ? tokens_dev + int64_t(b) * row_stride : nullptr;
+    a.score = scores_dev ? scores_dev + b : nullptr;
+    a.N = int(N);
+    a.T = frames ? frames[b] : T;
+    a.T_full = T;
+    a.C = C;
+    int p = 0;
+    while (p + 1 < U && t[p] < t[p + 1]) ++p;
+    a.p = p;
+    abytes += 4.0 * a.T * C + 0.5 * double(a.T) * double(N) + 8.0 * a.T;
+  }
+  DevMemP d = upload_vec(tab);
+  GTNX_PROF("band_viterbi_align", abytes);
+  launch_band_align(d->as<AlignArgs>(), n, fx.max_nodes, rt.stream());
+  g_align_fast.fetch_add(n);
 }
 
 

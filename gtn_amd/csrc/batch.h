@@ -110,6 +110,15 @@ BatchP batch_linear(int n, int M, int C, bool calc_grad, const void* dev, bool b
 BatchP batch_compose(const BatchP& a, const BatchP& b, bool intersect);
 BatchP batch_shortest_distance(const BatchP& x, bool tropical);
 BatchP batch_viterbi_path(const BatchP& x);
+// Forced alignment with device-resident output: labels_dev[b * row_stride + t] = the label of frame t on utterance b's
+// best path (-1 from the path's end on, everywhere when there is no path), tokens_dev likewise the index into the label
+// sequence (-1 on blank frames), scores_dev[b] the path's score.  A PRODUCT of device-built CTC targets (blank below
+// every label) with a LINEAR batch is aligned by one launch on the engine's stream (align.hip): no graphs, no copy
+// back, no synchronisation; frames (host, [n], or null): rows of each utterance to align.  Every other batch goes
+// through batch_viterbi_path and one upload; tokens_dev and frames are invalid arguments there.
+void batch_viterbi_align(const BatchP& x, const int* frames, int* labels_dev, int64_t row_stride, int* tokens_dev,
+                         float* scores_dev);
+void batch_align_stats(int64_t* fast, int64_t* fallback);  // utterances aligned by the launch / by the path graphs
 // items_dev (optional): device memory of the CALLER's that the n result values are written into directly (borrowed: it
 // must outlive the result); a later batch_items_device to the same address copies nothing
 BatchP batch_scalar(ScalarKind k, const BatchP& a, const BatchP& b, void* items_dev = nullptr);

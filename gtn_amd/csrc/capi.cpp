@@ -858,6 +858,16 @@ GTNX_API gtnx_status_t gtnx_batch_viterbi_score(gtnx_batch_t a, gtnx_batch_t* ou
 GTNX_API gtnx_status_t gtnx_batch_viterbi_path(gtnx_batch_t a, gtnx_batch_t* out) {
   return guard([&] { *out = HB(batch_viterbi_path(BH(a))); });
 }
+GTNX_API gtnx_status_t gtnx_batch_viterbi_align(gtnx_batch_t a, const int* frames, void* labels_device, int64_t row_stride,
+                                                void* tokens_device, void* scores_device) {
+  return guard([&] {
+    batch_viterbi_align(BH(a), frames, static_cast<int*>(labels_device), row_stride, static_cast<int*>(tokens_device),
+                        static_cast<float*>(scores_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_align_stats(int64_t* fast, int64_t* fallback) {
+  return guard([&] { batch_align_stats(fast, fallback); });
+}
 GTNX_API gtnx_status_t gtnx_batch_backward(gtnx_batch_t a, int retain) {
   return guard([&] { batch_backward(BH(a), retain != 0); });
 }

@@ -547,6 +547,25 @@ struct BandDecode {
 void launch_band_viterbi(const BandDecode* d_pairs, int n, int stage_floats, int max_nodes, int max_labels, int vec,
                          hipStream_t st, int ranked = 0);
 bool band_viterbi_wave_ok(int max_nodes, int max_labels, int vec);
+// Forced alignment of chain o (CTC target acceptor), one wave per utterance (align.hip): the tropical recursion of
+// band_viterbi_wave_kernel<NPL, RANKED = true> over the first T of the utterance's T_full emission rows, ties decided
+// by the closed-form node ranks of ops_band.cpp (tie_ranks: blank below every label; p = leading strict ascents of the
+// label sequence), and the frame labels / token indices written from the pointer chase straight into the caller's rows.
+struct AlignArgs {
+  const GTNX_G BandNode* nodes;  // [N] the target's band records (batch_ctc_targets)
+  const GTNX_G uint8_t* nflags;  // [N]
+  const GTNX_G float* em;        // [T_full][C], 16-byte aligned, C % 4 == 0
+  GTNX_G unsigned* bp;           // back-pointer words: ceil(T * NPL / 16) rows of 64
+  GTNX_G int* labels;            // [T_full] label of every frame, -1 from T on (and everywhere without a path)
+  GTNX_G int* tokens;            // [T_full] index into the label sequence, -1 on blank frames; or null
+  GTNX_G float* score;           // [1] or null
+  int N, T, T_full, C;
+  int p, pad;
+};
+int align_npl(int max_nodes);  // nodes per lane of a launch (1, 2, 4, 8)
+// max_nodes <= 512, C <= 2048 and a multiple of 4, every em 16-byte aligned: band_align_ok
+bool band_align_ok(int max_nodes, int max_labels, int vec);
+void launch_band_align(const AlignArgs* d_args, int n, int max_nodes, hipStream_t st);
 // ---------------------------------------------------------------------------
 // rational.hip: clone / concat / closure / union_ (functions.cpp:66-223) built on the device
 // ---------------------------------------------------------------------------

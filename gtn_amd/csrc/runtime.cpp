@@ -649,6 +649,7 @@ bool local_to(const void* p, int dev) {
   return a.type == hipMemoryTypeHost || (a.type == hipMemoryTypeDevice && a.device == dev);
 }
 }  // namespace
+bool ptr_local_to(const void* p, int dev) { return local_to(p, dev); }
 // (up to a megabyte by a kernel of ours -- kernels.h: launch_copy_small; the runtime's copy costs the host about twice
 // a launch, and the copies of this size are the ones at the head of a latency chain: setWeights of one utterance)
 void Runtime::d2d(void* dst, const void* src, size_t bytes) {

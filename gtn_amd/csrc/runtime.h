@@ -196,6 +196,10 @@ class Runtime {
   friend struct Scope;
 };
 
+// may a kernel running on device `dev` touch p?  (Host memory and that device's own: yes; another GPU's: no.  With one
+// GPU in the process there is nothing to ask.)
+bool ptr_local_to(const void* p, int dev);
+
 #define GTNX_PROF(name, bytes) ::gtnx::Runtime::Scope _prof_scope(&::gtnx::Runtime::get(), name, bytes)
 
 // host wall-clock phases (GTNX_HOST_TIMING=1 prints the table at exit); diagnostics only

@@ -1,4 +1,4 @@
-"""PyTorch entry points of the hot path: `ctc_loss` and `asg_loss`.
+"""PyTorch entry points of the hot path: `ctc_loss`, `asg_loss` and `ctc_forced_align`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -31,6 +31,10 @@ def _native():
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             lib.gtn_asg_loss_n.restype = C.c_int
             lib.gtn_criteria_last_error.restype = C.c_char_p
+            if hasattr(lib, "gtn_ctc_align_n"):
+                lib.gtn_ctc_align_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+                lib.gtn_ctc_align_n.restype = C.c_int
             _NATIVE = lib
         else:
             _NATIVE = False
@@ -130,6 +134,48 @@ def _flat_targets(targets):
     flat = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int32).reshape(-1) for t in targets])
                                 if len(targets) else np.zeros(0, np.int32), dtype=np.int32)
     return flat, np.ascontiguousarray([len(t) for t in targets], dtype=np.int32)
+
+
+def ctc_forced_align(log_probs, targets, blank=0, input_lengths=None):
+    """CTC forced alignment of a batch, device-resident: the best path of target_b ∩ emissions_b (the reference's
+    viterbiPath) for every utterance in one launch, nothing copied back.
+    log_probs: float32 CUDA tensor [B, T, C] (any scores), read in place and left untouched; targets: B label
+    sequences; input_lengths: per-utterance frame counts (<= T) or None.
+    Returns (labels int32 [B, T], tokens int32 [B, T], scores float32 [B]) on log_probs.device: the label of every
+    frame, the index of the frame's token in its target (-1 on blank frames), the path score.  Entries past an
+    utterance's length are -1; an utterance no path fits has score -inf and rows of -1.  No autograd."""
+    assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 3
+    B, T, C = log_probs.shape
+    if len(targets) != B:
+        raise ValueError(f"ctc_forced_align: {len(targets)} target sequences for a batch of {B}")
+    x = log_probs.detach().contiguous()
+    frames = None
+    if input_lengths is not None:
+        frames = np.ascontiguousarray([int(v) for v in input_lengths], dtype=np.int32)
+        if frames.shape != (B,):
+            raise ValueError(f"ctc_forced_align: {frames.size} input lengths for a batch of {B}")
+    stream = torch.cuda.current_stream(x.device)
+    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
+    if not stream.cuda_stream:
+        torch.cuda.current_stream(x.device).synchronize()  # engine runs on its own stream
+    labels = torch.empty(B, T, dtype=torch.int32, device=x.device)
+    tokens = torch.empty(B, T, dtype=torch.int32, device=x.device)
+    scores = torch.empty(B, dtype=torch.float32, device=x.device)
+    lib = _native()
+    if lib and hasattr(lib, "gtn_ctc_align_n"):
+        flat, lens = _flat_targets(targets)
+        rc = lib.gtn_ctc_align_n(x.data_ptr(), flat.ctypes.data, lens.ctypes.data, B, T, C, int(blank),
+                                 frames.ctypes.data if frames is not None else None, labels.data_ptr(),
+                                 tokens.data_ptr(), scores.data_ptr())
+        if rc != 0:
+            raise RuntimeError(lib.gtn_criteria_last_error().decode())
+    else:
+        ctcs = gtn.Batch.ctc_targets([list(t) for t in targets], blank, calc_grad=False)
+        ems = gtn.Batch.linear(B, T, C, x, calc_grad=False, borrow=True)
+        gtn.intersect(ctcs, ems).viterbi_align(labels, tokens, scores, frames)
+    if not stream.cuda_stream:
+        gtn.synchronize()
+    return labels, tokens, scores
 
 
 class _ASGLoss(torch.autograd.Function):

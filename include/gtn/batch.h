@@ -139,6 +139,15 @@ inline Batch intersect(const Batch& a, const Batch& b) { return detail::batchBin
 inline Batch forwardScore(const Batch& a) { return detail::batchUnary(&gtnx_batch_forward_score, a); }
 inline Batch viterbiScore(const Batch& a) { return detail::batchUnary(&gtnx_batch_viterbi_score, a); }
 inline Batch viterbiPath(const Batch& a) { return detail::batchUnary(&gtnx_batch_viterbi_path, a); }
+/** Forced alignment with the results left on the device: row b of labelsDevice (int32, rowStride entries apart) gets
+ *  the label of every frame of utterance b's best path, -1 past the path; tokensDevice the index into the label
+ *  sequence (-1 on blank frames), scoresDevice the path scores; frames (host, [n]): emission rows to align per
+ *  utterance.  One launch, no copy back and no wait for a product of Batch::ctcTargets with Batch::linear; other
+ *  batches go through viterbiPath (tokensDevice and frames must be null there) -- gtnx_batch_viterbi_align */
+inline void viterbiAlign(const Batch& product, int* labelsDevice, int64_t rowStride, int* tokensDevice = nullptr,
+                         float* scoresDevice = nullptr, const int* frames = nullptr) {
+  detail::check(gtnx_batch_viterbi_align(product.handle(), frames, labelsDevice, rowStride, tokensDevice, scoresDevice));
+}
 inline void backward(const Batch& a, bool retainGraph = false) { detail::check(gtnx_batch_backward(a.handle(), retainGraph)); }
 } // namespace batched
 

@@ -286,6 +286,21 @@ gtnx_status_t gtnx_batch_intersect(gtnx_batch_t a, gtnx_batch_t b, gtnx_batch_t*
 gtnx_status_t gtnx_batch_forward_score(gtnx_batch_t a, gtnx_batch_t* out);            /* functions.cpp:320-322 */
 gtnx_status_t gtnx_batch_viterbi_score(gtnx_batch_t a, gtnx_batch_t* out);            /* functions.cpp:324-326 */
 gtnx_status_t gtnx_batch_viterbi_path(gtnx_batch_t a, gtnx_batch_t* out);             /* functions.cpp:328-330 */
+/* Forced alignment with device-resident output: what a caller of the reference gets from viterbiPath
+ * (shortest.cpp:190-272) plus the per-utterance host loop written around it (read every path graph's arc labels, pad,
+ * upload), as one call that leaves the results in the caller's device memory.  Row b of labels_device
+ * (int32, row_stride entries apart) receives the label of every frame on utterance b's best path and -1 from the
+ * path's end on (everywhere when no accepting path exists); tokens_device (or null) likewise the index into the
+ * utterance's label sequence, -1 on blank frames; scores_device (float32 [n], or null) the path's score, -inf without
+ * a path.  frames (host, [n], or null): how many of the T emission rows of each utterance are aligned.
+ * A composition of gtnx_batch_ctc_targets (blank below every label) with gtnx_batch_linear (alphabet a multiple of 4,
+ * at most 2048; at most 512 nodes) is aligned by ONE launch on the engine's stream: nothing is copied back and the
+ * call does not wait for the device.  Any other batch goes through gtnx_batch_viterbi_path and one upload; tokens_device
+ * and frames are GTNX_INVALID_ARGUMENT there.  Output pointers must be memory the engine's current device may write. */
+gtnx_status_t gtnx_batch_viterbi_align(gtnx_batch_t a, const int* frames, void* labels_device, int64_t row_stride,
+                                       void* tokens_device, void* scores_device);
+/* utterances aligned so far (process-wide) by the launch / by the path-graph route */
+gtnx_status_t gtnx_batch_align_stats(int64_t* fast, int64_t* fallback);
 gtnx_status_t gtnx_batch_backward(gtnx_batch_t a, int retain_graph);                  /* autograd.cpp:17-67 */
 gtnx_status_t gtnx_batch_items(gtnx_batch_t a, float* out);                           /* graph.h:143, n floats */
 gtnx_status_t gtnx_batch_items_device(gtnx_batch_t a, void* device_out);
