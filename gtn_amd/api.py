@@ -677,9 +677,18 @@ def make_api(lib):
             return cls._from_handle(h.value)
 
         @classmethod
-        def linear(cls, B, M, N, device_weights, calc_grad=True, borrow=False):
-            """B linear graphs over one device tensor [B, M, N]; borrow: read in place"""
+        def linear(cls, B, M, N, device_weights, calc_grad=True, borrow=False, rows=None):
+            """B linear graphs over one device tensor [B, M, N]; borrow: read in place; rows: per-element row counts
+            of a padded tensor (1 .. M) -- element b is linear_graph(rows[b], N) over the first rows[b] rows of its
+            slab, and its gradient keeps the [M, N] layout with zeros in the pad rows"""
             h = C.c_void_p()
+            if rows is not None:
+                r = np.ascontiguousarray([int(v) for v in rows], dtype=np.int32)
+                if r.shape != (int(B),):
+                    raise ValueError(f"Batch.linear: {r.size} row counts for a batch of {int(B)}")
+                check(lib.gtnx_batch_linear_rows(int(B), int(M), int(N), r.ctypes.data, int(bool(calc_grad)),
+                                                 _as_dev_ptr(device_weights), int(bool(borrow)), C.byref(h)))
+                return cls._from_handle(h.value)
             check(lib.gtnx_batch_linear(int(B), int(M), int(N), int(bool(calc_grad)), _as_dev_ptr(device_weights),
                                         int(bool(borrow)), C.byref(h)))
             return cls._from_handle(h.value)

@@ -31,6 +31,22 @@ extern "C" __attribute__((visibility("default"))) int gtn_ctc_loss_n(const void*
   }
 }
 
+// The same over a PADDED batch: frames: host int32 [B], utterance b's frame count (1 .. T) -- its loss is that of
+// emissions[b][:frames[b]], the pad rows are never read and rows [frames[b], T) of grad are 0.
+extern "C" __attribute__((visibility("default"))) int gtn_ctc_loss_frames_n(const void* emissions, const int* targets,
+                                                                            const int* lengths, int B, int T, int C,
+                                                                            int blank, const int* frames, void* loss,
+                                                                            void* grad) {
+  try {
+    gtn::criteria::ctcLossBatch(emissions, targets, lengths, B, T, C, blank, loss, grad, /*targetGrad=*/false, nullptr,
+                                nullptr, frames);
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
 // CTC forced alignment.  emissions: DEVICE float [B][T][C]; targets / lengths: host int32 (concatenated / [B]);
 // frames: host int32 [B] or null; labels: DEVICE int32 [B][T]; tokens: DEVICE int32 [B][T] or null; scores: DEVICE
 // float [B] or null.  Returns 0, or -1 with the message in gtn_criteria_last_error().

@@ -8,6 +8,7 @@
 
 #include <chrono>
 #include <cstdint>
+#include <stdexcept>
 #include <vector>
 
 #include "gtn/gtn.h"
@@ -49,7 +50,8 @@ struct CtcStepTimes {
  *  for a batch -- benchmarks/ctc.cpp:150-165 with one Batch per call instead of parallelMap over
  *  per-utterance graphs.  `emissions`: device [B][T][C], read in place; `lossDev`: device [B];
  *  `gradDev`: device [B][T][C] (d loss / d emissions, written in place) or null.  Targets may have
- *  different lengths. */
+ *  different lengths.  `frames` (host [B], or null): a padded batch -- utterance b has frames[b] <= T frames, the
+ *  loss is that of emissions_b[:frames[b]], rows past them are never read and their gradient is 0. */
 inline void ctcLossBatch(
     const void* emissions,
     const int* labels,   // target sequences back to back
@@ -62,13 +64,17 @@ inline void ctcLossBatch(
     void* gradDev,
     bool targetGrad = true,  // benchmarks/ctc.cpp builds its targets with calcGrad = true
     CtcStepTimes* times = nullptr,
-    Batch* targetsOut = nullptr) {  // the target acceptors (their gradients populated when targetGrad) handed back
+    Batch* targetsOut = nullptr,  // the target acceptors (their gradients populated when targetGrad) handed back
+    const int* frames = nullptr) {
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  if (frames)  // (before anything is launched)
+    for (int b = 0; b < B; ++b)
+      if (frames[b] < 1 || frames[b] > T) throw std::invalid_argument("[ctcLossBatch] a frame count outside 1 .. T");
   auto t0 = now();
   Batch ctcs = Batch::ctcTargets(labels, lengths, B, blank, targetGrad);
   auto t1 = now();
-  Batch ems = Batch::linear(B, T, C, emissions, gradDev != nullptr, /*borrow=*/true);
+  Batch ems = Batch::linear(B, T, C, emissions, gradDev != nullptr, /*borrow=*/true, frames);
   std::vector<int64_t> off(B);
   for (int b = 0; b < B; ++b) off[b] = (int64_t)b * T * C;
   if (gradDev) ems.bindGrads(gradDev, off.data());

@@ -40,7 +40,39 @@ BatchP result(Batch::Kind k, int n, std::shared_ptr<BatchOp> op) {
 
 bool native(const Batch& b, Batch::Kind k) { return b.kind == k; }
 
+// ---- ragged LINEAR batches: zeros for rows [rows[b], M) of every [M][C] slab at base + offs[b] floats (offs null:
+// slabs back to back) -- one launch, only the pad is written (padfill.hip)
+void pad_fill(Batch& b, float* base, const int64_t* offs = nullptr) {
+  if (b.kind != Batch::LINEAR || b.pad_floats <= 0) return;
+  Runtime& rt = Runtime::get();
+  const size_t n = size_t(b.n);
+  const size_t rows_bytes = align_up(sizeof(int) * n, 256);
+  if (!b.pad_mem) {
+    std::vector<int64_t> tab(rows_bytes / 8 + n + 1);
+    std::memcpy(tab.data(), b.rows.data(), sizeof(int) * n);
+    int64_t* prefix = tab.data() + rows_bytes / 8;
+    prefix[0] = 0;
+    for (size_t i = 0; i < n; ++i) prefix[i + 1] = prefix[i] + int64_t(b.M - b.rows[i]) * b.C;
+    b.pad_mem = upload_vec(tab);
+  }
+  PadFillArgs a{};
+  a.base = base;
+  a.rows = b.pad_mem->as<int>();
+  a.prefix = reinterpret_cast<const int64_t*>(b.pad_mem->as<char>(rows_bytes));
+  a.stride = int64_t(b.M) * b.C;
+  a.n = b.n;
+  a.C = b.C;
+  DevMemP d_offs;
+  if (offs) {
+    d_offs = upload_vec(std::vector<int64_t>(offs, offs + n));
+    a.offs = d_offs->as<int64_t>();
+  }
+  GTNX_PROF("linear_pad_fill", 4.0 * double(b.pad_floats));
+  launch_pad_fill(a, b.pad_floats, rt.stream());
+}
+
 // ---- the gradient array of a batch: bound destination, else a fresh block
+// (a ragged LINEAR batch's block leaves here with its pad rows zero: whoever writes it next writes rows < rows[b] only)
 void alloc_grad(Batch& b, bool zero) {
   Runtime& rt = Runtime::get();
   b.g_off.resize(size_t(b.n) + 1);
@@ -56,6 +88,7 @@ void alloc_grad(Batch& b, bool zero) {
     b.g_mem = zero ? rt.alloc_zero(bytes ? bytes : 4) : rt.alloc(bytes ? bytes : 4);
     b.g_dev = b.g_mem->as<float>();
   }
+  if (!zero) pad_fill(b, b.g_dev);
 }
 
 // a block the kernels may overwrite: the batch's own gradient when it has none yet, else a scratch
@@ -75,6 +108,7 @@ GradTarget grad_target(Batch& b, bool zero) {
   const size_t bytes = sizeof(float) * size_t(b.g_off[size_t(b.n)]);
   t.scratch = zero ? rt.alloc_zero(bytes ? bytes : 4) : rt.alloc(bytes ? bytes : 4);
   t.ptr = t.scratch->as<float>();
+  if (!zero) pad_fill(b, t.ptr);  // (add_scratch folds the whole block in: the pad rows must not carry what was there)
   return t;
 }
 void add_scratch(Batch& b, const GradTarget& t) {
@@ -129,7 +163,7 @@ struct BFsLinearOp : BatchOp {
     for (int b = 0; b < e.n; ++b) {
       LinArgs& a = args[size_t(b)];
       a.w = e.w_dev + size_t(b) * A;
-      a.M = e.M;
+      a.M = e.rows_of(b);
       a.C = e.C;
       a.out_score = nullptr;
       a.partial = nullptr;
@@ -506,8 +540,14 @@ BatchP batch_asg_force_align(const int* labels, const int* lengths, int n, Graph
   return b;
 }
 
-BatchP batch_linear(int n, int M, int C, bool calc_grad, const void* dev, bool borrow) {
+BatchP batch_linear(int n, int M, int C, bool calc_grad, const void* dev, bool borrow, const int* rows) {
   if (n < 0 || M < 0 || C < 0) throw_invalid("[gtnx_batch_linear] negative size");
+  int64_t pad_rows = 0;
+  if (rows)
+    for (int i = 0; i < n; ++i) {
+      if (rows[i] < 1 || rows[i] > M) throw_invalid("[gtnx_batch_linear_rows] a row count outside 1 .. M");
+      pad_rows += M - rows[i];
+    }
   Runtime& rt = Runtime::get();
   BatchP b = make_batch(Batch::LINEAR, n, calc_grad);
   b->M = M;
@@ -523,6 +563,10 @@ BatchP batch_linear(int n, int M, int C, bool calc_grad, const void* dev, bool b
     if (dev && bytes) rt.d2d(b->w_mem->ptr, dev, bytes);
   }
   b->w_dev = b->w_mem->as<float>();
+  if (pad_rows > 0) {  // (row counts that are all M: the plain batch, in every respect)
+    b->rows.assign(rows, rows + n);
+    b->pad_floats = pad_rows * C;
+  }
   return b;
 }
 
@@ -687,21 +731,23 @@ void batch_materialise(Batch& x) {
       break;
     case Batch::LINEAR: {
       gs.reserve(size_t(x.n));
-      const int64_t A = int64_t(x.M) * x.C;
+      const int64_t stride = int64_t(x.M) * x.C;
       for (int i = 0; i < x.n; ++i) {
         Graph g = Graph::make_result(x.calc_grad);  // (out of the scope's slab: an element refers to nothing)
         Structure& s = *g.s;
+        const int rows = x.rows_of(i);  // (ragged: the first rows of the slab, linearGraph(rows, C))
+        const int64_t A = int64_t(rows) * x.C;
         s.kind = KIND_LINEAR;
-        s.M = x.M;
+        s.M = rows;
         s.C = x.C;
-        s.N = int64_t(x.M) + 1;
+        s.N = int64_t(rows) + 1;
         s.A = A;
         s.ilabel_sorted = s.olabel_sorted = true;
         Weights& w = *g.w;
         w.n = A;
         if (x.w_pend) x.w_pend->settle();  // (the element graphs' weights are looked at by whoever gets them)
         w.dev_mem = x.w_mem;
-        w.dev = x.w_dev + size_t(i) * size_t(A);
+        w.dev = x.w_dev + size_t(i) * size_t(stride);
         w.dev_valid = true;
         w.host_valid = false;
         w.version++;
@@ -862,7 +908,7 @@ BatchP batch_shortest_distance(const BatchP& x, bool tropical) {
       p.w = fx.fal ? fx.rec_mem->as<float>(fx.w_off[size_t(b)]) : nullptr;  // CTC targets: all-zero weights
       p.em = ch.w_dev + size_t(b) * size_t(T) * size_t(C);
       p.N = int(N);
-      p.T = T;
+      p.T = ch.rows_of(b);  // (the arena, the rowlse stride and p.em stay on T: the chain's slab)
       p.C = C;
       p.NS = band_row_stride(p.N, band_npl(p.N));
       p.alpha = op->arena->as<float>(ao[size_t(b)]);
@@ -886,7 +932,7 @@ BatchP batch_shortest_distance(const BatchP& x, bool tropical) {
         q.em_copy = const_cast<float*>(p.em);
       }
       tab.push_back({BandLaunchKey{C, band_npl(q.N), fx.fal ? 0 : 1, 0, band_vec_ok(q)}, q});
-      abytes += 4.0 * T * C + 4.0 * double(T + 1) * p.NS + (fuse_copy ? 4.0 * T * C : 0.0);
+      abytes += 4.0 * p.T * C + 4.0 * double(p.T + 1) * p.NS + (fuse_copy ? 4.0 * T * C : 0.0);
     }
     // (a launch that also makes the region's copy reads the caller's buffer: its table is not the backward sweep's)
     band_launch(tab, false, "band_forward_score", abytes, fuse_copy ? nullptr : &op->fwd_table);
@@ -928,7 +974,7 @@ BatchP batch_shortest_distance(const BatchP& x, bool tropical) {
     for (int b = 0; b < n; ++b) {
       LinArgs& a = args[size_t(b)];
       a.w = x->w_dev + size_t(b) * A;
-      a.M = x->M;
+      a.M = x->rows_of(b);
       a.C = x->C;
       a.out_score = scal + b;
       a.partial = partial + size_t(b) * 8;
@@ -1036,8 +1082,11 @@ void batch_viterbi_align(const BatchP& x, const int* frames, int* labels_dev, in
   const int T = ch.M, C = ch.C;
   if (row_stride < T) throw_invalid("[gtnx_batch_viterbi_align] row_stride is shorter than the chains");
   if (frames)
-    for (int b = 0; b < n; ++b)
+    for (int b = 0; b < n; ++b) {
       if (frames[b] < 0 || frames[b] > T) throw_invalid("[gtnx_batch_viterbi_align] a frame count outside 0 .. T");
+      if (frames[b] > ch.rows_of(b))
+        throw_invalid("[gtnx_batch_viterbi_align] a frame count beyond the rows the chain carries");
+    }
   if (ch.w_pend) ch.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
   // back-pointer planes: 2 bits per (time, node), one 256-byte row of words per 16 / NPL steps (align.hip)
   const int npl = align_npl(fx.max_nodes);
@@ -1060,7 +1109,7 @@ void batch_viterbi_align(const BatchP& x, const int* frames, int* labels_dev, in
     a.tokens = tokens_dev ? tokens_dev + int64_t(b) * row_stride : nullptr;
     a.score = scores_dev ? scores_dev + b : nullptr;
     a.N = int(N);
-    a.T = frames ? frames[b] : T;
+    a.T = frames ? frames[b] : ch.rows_of(b);
     a.T_full = T;
     a.C = C;
     int p = 0;
@@ -1285,7 +1334,7 @@ void batch_items_host(const BatchP& x, float* out) {
 }
 void batch_grads_bind(const BatchP& x, void* dev_out, const int64_t* offsets) {
   if (x->materialised) {
-    grads_bind_device(x->graphs, dev_out, offsets);
+    grads_bind_device(x->graphs, dev_out, offsets);  // (ragged: the pad rows are filled by batch_grads_device)
     return;
   }
   if (x->kind != Batch::LINEAR && x->kind != Batch::SCALAR) return;  // a hint
@@ -1304,6 +1353,8 @@ void batch_grads_device(const BatchP& x, void* dev_out, const int64_t* offsets) 
   if (x->kind == Batch::CTC_TARGETS) batch_materialise(*x);  // exact arc counts live with the element graphs
   if (x->materialised) {
     grads_device(x->graphs, dev_out, offsets);
+    // ragged: the element graphs hold rows[b] * C floats each, the caller's layout is [M][C] per element
+    pad_fill(*x, static_cast<float*>(dev_out), offsets);
     return;
   }
   if (!x->g_dev) throw_logic("[gtn::Graph::grad] Gradient not calculated yet.");  // graph.cpp:131-140

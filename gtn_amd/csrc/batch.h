@@ -83,6 +83,14 @@ struct Batch {
   DevMemP nc_mem;                    // forwardScore of every chain + per-row log-sum-exps, left behind by a sweep
   float* nc_norm = nullptr;
   float* nc_rowlse = nullptr;
+  // ... ragged: element b is linearGraph(rows[b], C) over the first rows[b] rows of its [M][C] slab (1 <= rows[b] <= M;
+  // the slab stride, the gradient layout and every arena stay on M).  Empty: every element has M rows.  The gradient's
+  // rows [rows[b], M) are zero: the sweeps write rows < rows[b] and ONE launch of padfill.hip stores the rest
+  // (pad_floats of them; its table -- rows [n] and the prefix sums of the pads [n + 1] -- is uploaded on first use)
+  std::vector<int> rows;
+  int64_t pad_floats = 0;
+  DevMemP pad_mem;
+  int rows_of(int b) const { return rows.empty() ? M : rows[size_t(b)]; }
   // ---- PRODUCT: compose(fixed, chain) / compose(chain, fixed), never built
   BatchP fixed, chain;
   bool chain_first = false, intersect = false;
@@ -106,7 +114,8 @@ struct Batch {
 BatchP batch_from_graphs(std::vector<Graph> gs);
 BatchP batch_ctc_targets(const int* labels, const int* lengths, int n, int blank, bool calc_grad);
 BatchP batch_asg_force_align(const int* labels, const int* lengths, int n, Graph& transitions, int n_labels);
-BatchP batch_linear(int n, int M, int C, bool calc_grad, const void* dev, bool borrow);
+// rows (host, [n], or null): the rows of each element that count (Batch::rows); outside 1 .. M: invalid argument
+BatchP batch_linear(int n, int M, int C, bool calc_grad, const void* dev, bool borrow, const int* rows = nullptr);
 BatchP batch_compose(const BatchP& a, const BatchP& b, bool intersect);
 BatchP batch_shortest_distance(const BatchP& x, bool tropical);
 BatchP batch_viterbi_path(const BatchP& x);
@@ -114,7 +123,8 @@ BatchP batch_viterbi_path(const BatchP& x);
 // best path (-1 from the path's end on, everywhere when there is no path), tokens_dev likewise the index into the label
 // sequence (-1 on blank frames), scores_dev[b] the path's score.  A PRODUCT of device-built CTC targets (blank below
 // every label) with a LINEAR batch is aligned by one launch on the engine's stream (align.hip): no graphs, no copy
-// back, no synchronisation; frames (host, [n], or null): rows of each utterance to align.  Every other batch goes
+// back, no synchronisation; frames (host, [n], or null): rows of each utterance to align (null: the chain's own row
+// counts; more than those: invalid argument).  Every other batch goes
 // through batch_viterbi_path and one upload; tokens_dev and frames are invalid arguments there.
 void batch_viterbi_align(const BatchP& x, const int* frames, int* labels_dev, int64_t row_stride, int* tokens_dev,
                          float* scores_dev);

@@ -812,6 +812,10 @@ GTNX_API gtnx_status_t gtnx_batch_asg_force_align(const int* labels, const int* 
 GTNX_API gtnx_status_t gtnx_batch_linear(int n, int M, int N, int cg, const void* dev, int borrow, gtnx_batch_t* out) {
   return guard([&] { *out = HB(batch_linear(n, M, N, cg != 0, dev, borrow != 0)); });
 }
+GTNX_API gtnx_status_t gtnx_batch_linear_rows(int n, int M, int N, const int* rows, int cg, const void* dev, int borrow,
+                                             gtnx_batch_t* out) {
+  return guard([&] { *out = HB(batch_linear(n, M, N, cg != 0, dev, borrow != 0, rows)); });
+}
 GTNX_API gtnx_status_t gtnx_batch_destroy(gtnx_batch_t b) {
   return guard([&] {
     auto* p = reinterpret_cast<BatchP*>(b);

@@ -740,6 +740,17 @@ struct ScatterArgs {
   int n;
 };
 void launch_scatter_add(const ScatterArgs* d_args, int n, int maxn, hipStream_t st);
+// zeros for the pad rows of a ragged [n][M][C] tensor (padfill.hip): element b's floats [rows[b] * C, M * C) at
+// base + (offs ? offs[b] : b * stride); prefix[b] = sum over b' < b of (M - rows[b']) * C, prefix[n] the total
+struct PadFillArgs {
+  GTNX_G float* base;
+  const GTNX_G int64_t* offs;    // [n] float offsets of the elements, or nullptr: b * stride
+  const GTNX_G int* rows;        // [n]
+  const GTNX_G int64_t* prefix;  // [n + 1]
+  int64_t stride;
+  int n, C;
+};
+void launch_pad_fill(const PadFillArgs& a, int64_t total_floats, hipStream_t st);
 // materialise a KIND_LINEAR graph's arc arrays
 void launch_linear_materialize(int M, int C, int* src, int* dst, int* il, int* ol, hipStream_t st);
 

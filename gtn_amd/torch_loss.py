@@ -27,6 +27,10 @@ def _native():
             lib.gtn_ctc_loss_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p]
             lib.gtn_ctc_loss_n.restype = C.c_int
+            if hasattr(lib, "gtn_ctc_loss_frames_n"):
+                lib.gtn_ctc_loss_frames_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+                lib.gtn_ctc_loss_frames_n.restype = C.c_int
             lib.gtn_asg_loss_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             lib.gtn_asg_loss_n.restype = C.c_int
@@ -60,11 +64,14 @@ def ctc_target_graph(target, blank=0):
 
 class _CTCLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, log_probs, targets, blank, reduction):
+    def forward(ctx, log_probs, targets, blank, reduction, frames=None):
         assert log_probs.is_cuda and log_probs.dtype == torch.float32 and log_probs.dim() == 3
         B, T, C = log_probs.shape
         if len(targets) != B:
             raise ValueError(f"ctc_loss: {len(targets)} target sequences for a batch of {B}")
+        ctx.ragged = frames is not None
+        if frames is not None:
+            return _CTCLoss._forward_frames(ctx, log_probs, targets, blank, reduction, frames)
         x = log_probs.contiguous()
         stream = torch.cuda.current_stream(x.device)
         gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
@@ -103,10 +110,55 @@ class _CTCLoss(torch.autograd.Function):
         return out
 
     @staticmethod
+    def _forward_frames(ctx, log_probs, targets, blank, reduction, frames):
+        """a padded batch: utterance b has frames[b] <= T frames (the pad rows are never read, their gradient is 0)"""
+        B, T, C = log_probs.shape
+        x = log_probs.contiguous()
+        stream = torch.cuda.current_stream(x.device)
+        gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
+        if not stream.cuda_stream:
+            torch.cuda.current_stream(x.device).synchronize()  # engine runs on its own stream
+        out = torch.empty(B, dtype=torch.float32, device=x.device)
+        lib = _native()
+        ctx.shape = (B, T, C)
+        ctx.reduction = reduction
+        if lib:
+            if not hasattr(lib, "gtn_ctc_loss_frames_n"):
+                raise RuntimeError("ctc_loss(input_lengths=...) needs gtn_ctc_loss_frames_n in "
+                                   "gtn_amd/lib/libgtn_criteria.so (run __graft_entry__.build())")
+            flat, lens = _flat_targets(targets)
+            grad = torch.empty(B, T, C, dtype=torch.float32, device=x.device) if log_probs.requires_grad else None
+            rc = lib.gtn_ctc_loss_frames_n(x.data_ptr(), flat.ctypes.data, lens.ctypes.data, B, T, C, int(blank),
+                                           frames.ctypes.data, out.data_ptr(),
+                                           grad.data_ptr() if grad is not None else None)
+            if rc != 0:
+                raise RuntimeError(lib.gtn_criteria_last_error().decode())
+            ctx.graphs = None
+            ctx.grad = grad
+        else:
+            ctcs = gtn.Batch.ctc_targets([list(t) for t in targets], blank, calc_grad=False)
+            ems = gtn.Batch.linear(B, T, C, x, calc_grad=log_probs.requires_grad, borrow=True, rows=frames)
+            # (this order lets the sweep over target o emissions leave forwardScore(emissions) behind)
+            score = gtn.forward_score(gtn.intersect(ctcs, ems))
+            losses = gtn.subtract(gtn.forward_score(ems), score)
+            losses.items_to_device(out)
+            ctx.graphs = (losses, ems)
+            ctx.keep = x  # (borrowed by `ems` until the backward pass)
+        if not stream.cuda_stream:
+            gtn.synchronize()
+        return out.mean() if reduction == "mean" else (out.sum() if reduction == "sum" else out)
+
+    @staticmethod
     def backward(ctx, grad_out):
         B, T, C = ctx.shape
         if ctx.graphs is None:
             grad = ctx.grad  # computed with the forward pass by the native criterion
+        elif isinstance(ctx.graphs[1], gtn.Batch):
+            losses, ems = ctx.graphs
+            gtn.backward(losses)
+            grad = torch.empty(B, T, C, dtype=torch.float32, device=grad_out.device)
+            ems.grads_to_device(grad, [b * T * C for b in range(B)])
+            gtn.synchronize()
         else:
             losses, ems = ctx.graphs
             gtn.backward(losses)
@@ -119,15 +171,32 @@ class _CTCLoss(torch.autograd.Function):
             scale = grad_out.reshape(1, 1, 1)
         else:
             scale = grad_out.reshape(B, 1, 1)
-        return grad * scale, None, None, None
+        return (grad * scale, None, None, None) + ((None,) if ctx.ragged else ())
 
 
-def ctc_loss(log_probs, targets, blank=0, reduction="none"):
+def _frame_counts(name, input_lengths, B, T, low):
+    """per-utterance frame counts as a host int32 array [B], each in low .. T"""
+    vals = input_lengths.tolist() if hasattr(input_lengths, "tolist") else list(input_lengths)
+    frames = np.ascontiguousarray([int(v) for v in vals], dtype=np.int32)
+    if frames.shape != (B,):
+        raise ValueError(f"{name}: {frames.size} input lengths for a batch of {B}")
+    if B and (int(frames.min()) < low or int(frames.max()) > T):
+        raise ValueError(f"{name}: an input length outside {low} .. {T}")
+    return frames
+
+
+def ctc_loss(log_probs, targets, blank=0, reduction="none", input_lengths=None):
     """log_probs: float32 CUDA tensor [B, T, C] (any scores; the loss carries its own
     normaliser forwardScore(emissions), as in benchmarks/ctc.cpp:150-158).
-    targets: sequence of B label sequences.  Returns per-utterance losses (or their
-    mean / sum); differentiable w.r.t. log_probs."""
-    return _CTCLoss.apply(log_probs, targets, blank, reduction)
+    targets: sequence of B label sequences.  input_lengths: a sequence or int tensor of B frame
+    counts (1 .. T) for a padded batch, or None: utterance b's loss is that of log_probs[b, :T_b]
+    (+inf when its target does not fit into T_b frames), rows past T_b are never read and their
+    gradient is 0.  Returns per-utterance losses (or their mean / sum over B); differentiable
+    w.r.t. log_probs."""
+    if input_lengths is None:
+        return _CTCLoss.apply(log_probs, targets, blank, reduction)
+    frames = _frame_counts("ctc_loss", input_lengths, log_probs.shape[0], log_probs.shape[1], 1)
+    return _CTCLoss.apply(log_probs, targets, blank, reduction, frames)
 
 
 def _flat_targets(targets):

@@ -61,10 +61,16 @@ class Batch {
     detail::check(gtnx_batch_asg_force_align(labels, lengths, n, transitions.handle(), numLabels, &b.h_));
     return b;
   }
-  /** n linear graphs over one device tensor [n][M][N] (see linearGraphs) */
-  static Batch linear(int n, int M, int N, const void* deviceWeights, bool calcGrad = true, bool borrow = false) {
+  /** n linear graphs over one device tensor [n][M][N] (see linearGraphs); rows (host, [n]): a padded tensor --
+   *  element b is linearGraph(rows[b], N) over the first rows[b] rows of its slab, its gradient keeps the [M][N]
+   *  layout with zeros in the pad rows (gtnx_batch_linear_rows) */
+  static Batch linear(int n, int M, int N, const void* deviceWeights, bool calcGrad = true, bool borrow = false,
+                      const int* rows = nullptr) {
     Batch b;
-    detail::check(gtnx_batch_linear(n, M, N, calcGrad, deviceWeights, borrow, &b.h_));
+    if (rows)
+      detail::check(gtnx_batch_linear_rows(n, M, N, rows, calcGrad, deviceWeights, borrow, &b.h_));
+    else
+      detail::check(gtnx_batch_linear(n, M, N, calcGrad, deviceWeights, borrow, &b.h_));
     return b;
   }
 

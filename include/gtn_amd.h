@@ -271,6 +271,13 @@ gtnx_status_t gtnx_batch_asg_force_align(const int* labels, const int* lengths, 
  * place (see gtnx_linear_graph_borrow_n) */
 gtnx_status_t gtnx_batch_linear(int n, int M, int N, int calc_grad, const void* device_weights, int borrow,
                                 gtnx_batch_t* out);
+/* ... over a PADDED tensor: element b is linearGraph(rows[b], N) over the first rows[b] rows of its [M][N] slab (rows:
+ * host [n], 1 <= rows[b] <= M, else GTNX_INVALID_ARGUMENT; null: gtnx_batch_linear).  The slab stride stays M*N, and so
+ * does the layout of the gradients (gtnx_batch_grads_device / _bind_device): rows [rows[b], M) of element b's gradient
+ * are 0, and the values of the pad rows are never read.  gtnx_batch_viterbi_align with frames == NULL aligns rows[b]
+ * frames; frames[b] > rows[b] is GTNX_INVALID_ARGUMENT. */
+gtnx_status_t gtnx_batch_linear_rows(int n, int M, int N, const int* rows, int calc_grad, const void* device_weights,
+                                     int borrow, gtnx_batch_t* out);
 gtnx_status_t gtnx_batch_destroy(gtnx_batch_t b);
 gtnx_status_t gtnx_batch_size(gtnx_batch_t b, int* out);
 gtnx_status_t gtnx_batch_get(gtnx_batch_t b, int i, gtnx_graph_t* out);               /* new handle */
