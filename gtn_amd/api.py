@@ -734,7 +734,9 @@ def make_api(lib):
             element b's best path, -1 past the path and everywhere when no path exists; `tokens_out` the index into
             the label sequence (-1 on blank frames), `scores_out` (float32 [B]) the path scores; `frames`: per-element
             frame counts.  A composition of Batch.ctc_targets with Batch.linear is one launch with no copy back and no
-            wait; other batches go through viterbi_path (tokens_out and frames are errors there)."""
+            wait, and so is a composition of Batch.asg_force_align with Batch.linear over the same alphabet, in either
+            argument order (there `tokens_out` = index into the label sequence, never -1 inside a path: ASG has no
+            blanks); other batches go through viterbi_path (tokens_out and frames are errors there)."""
             n = len(self)
             stride = row_stride
             for t in (labels_out, tokens_out):

@@ -90,5 +90,51 @@ inline void asgLossBatch(
   asgLossBatch(emissions, flat.data(), len.data(), (int)targets.size(), T, N, transitions, lossDev, gradDev);
 }
 
+/** ASG forced alignment of a batch, results on the device: per utterance the best path of
+ *  emissions_b o (forceAlign_b o transitions) (viterbiPath, shortest.cpp:190-272) as the label of every frame
+ *  (`labelsDev`, device int32 [B][T]), the index of that label in the target (`tokensDev`, device int32 [B][T] or
+ *  null; never -1 inside a path) and the path score (`scoresDev`, device float [B] or null).  `frames`: host [B] or
+ *  null -- how many of the T rows of each utterance count; entries past them are -1, and an utterance with fewer
+ *  frames than labels has score -inf and rows of -1.  `emissions`: device [B][T][N], read in place; `transitions`: the
+ *  graph of asgTransitions(N) with the caller's weights.  One launch, nothing is copied back (N a multiple of 4, at
+ *  most 2048; targets of at most 511 labels -- other shapes take the path-graph route, which has no tokens/frames). */
+inline void asgAlignBatch(
+    const void* emissions,
+    const int* labels,
+    const int* lengths,
+    int B,
+    int T,
+    int N,
+    Graph& transitions,
+    const int* frames,
+    void* labelsDev,
+    void* tokensDev,
+    void* scoresDev) {
+  Batch ems = Batch::linear(B, T, N, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  Batch fals = Batch::asgForceAlign(labels, lengths, B, transitions, N);
+  Batch comp = batched::compose(ems, fals);
+  batched::viterbiAlign(comp, static_cast<int*>(labelsDev), T, static_cast<int*>(tokensDev),
+                        static_cast<float*>(scoresDev), frames);
+}
+
+inline void asgAlignBatch(
+    const void* emissions,
+    const std::vector<std::vector<int>>& targets,
+    int T,
+    int N,
+    Graph& transitions,
+    const int* frames,
+    void* labelsDev,
+    void* tokensDev,
+    void* scoresDev) {
+  std::vector<int> flat, len;
+  for (auto& t : targets) {
+    flat.insert(flat.end(), t.begin(), t.end());
+    len.push_back((int)t.size());
+  }
+  asgAlignBatch(emissions, flat.data(), len.data(), (int)targets.size(), T, N, transitions, frames, labelsDev, tokensDev,
+                scoresDev);
+}
+
 } // namespace criteria
 } // namespace gtn

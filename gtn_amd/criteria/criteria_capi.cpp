@@ -111,3 +111,30 @@ extern "C" __attribute__((visibility("default"))) int gtn_asg_loss_n(const void*
     return -1;
   }
 }
+
+// ASG forced alignment.  emissions / targets / lengths / trans_w as for gtn_asg_loss_n; frames: host int32 [B] or null;
+// labels: DEVICE int32 [B][T]; tokens: DEVICE int32 [B][T] or null; scores: DEVICE float [B] or null.
+// Returns 0, or -1 with the message in gtn_criteria_last_error().
+extern "C" __attribute__((visibility("default"))) int gtn_asg_align_n(const void* emissions, const int* targets,
+                                                                      const int* lengths, int B, int T, int N,
+                                                                      const void* trans_w, const int* frames,
+                                                                      void* labels, void* tokens, void* scores) {
+  try {
+    // (a structure of its own: the loss's cached graph carries gradient state between calls)
+    static std::mutex mu;
+    static auto* cache = new std::map<int, gtn::Graph>();  // never destroyed: outlives the engine's teardown
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache->find(N);
+    if (it == cache->end()) {
+      it = cache->emplace(N, gtn::criteria::asgTransitions(N)).first;
+      it->second.setCalcGrad(false);
+    }
+    gtn::Graph& trans = it->second;
+    trans.setWeightsDevice(trans_w);  // arc ids are creation order: arcSort permutes lists, not ids
+    gtn::criteria::asgAlignBatch(emissions, targets, lengths, B, T, N, trans, frames, labels, tokens, scores);
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}

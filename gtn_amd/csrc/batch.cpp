@@ -758,7 +758,8 @@ void batch_materialise(Batch& x) {
     case Batch::PRODUCT: {
       batch_materialise(*x.fixed);
       batch_materialise(*x.chain);
-      CompMode symbolic;
+      std::unique_ptr<CompMode> symbolic;
+      if (!x.wide) symbolic.reset(new CompMode);  // (a wide product: what batch_compose's per-graph branch would have made)
       gs = x.chain_first ? op_compose(x.chain->graphs, x.fixed->graphs, x.intersect)
                          : op_compose(x.fixed->graphs, x.chain->graphs, x.intersect);
       break;
@@ -822,7 +823,11 @@ BatchP batch_compose(const BatchP& a, const BatchP& b, bool intersect) {
   bool chain_first = false;
   if (native(*a, Batch::CTC_TARGETS) && native(*b, Batch::LINEAR)) fx = a.get(), ch = b.get();
   if (native(*a, Batch::LINEAR) && native(*b, Batch::CTC_TARGETS)) fx = b.get(), ch = a.get(), chain_first = true;
-  if (fx && a->n == b->n && ch->C >= band_min_labels() && ch->C <= band_max_labels() && fx->max_label < ch->C && ch->M <= (1 << 20)) {
+  // (force-alignment acceptors over an alphabet past the band sweeps' limit still form a product, for the alignment
+  // launch alone -- Batch::wide: every other consumer composes the elements, as before)
+  const bool wide = fx && fx->fal && ch->C > band_max_labels() && ch->C <= asg_align_max_labels();
+  if (fx && a->n == b->n && ch->C >= band_min_labels() && (ch->C <= band_max_labels() || wide) && fx->max_label < ch->C &&
+      ch->M <= (1 << 20)) {
     struct Op : BatchOp {
       void backward(Batch&) override {}  // a symbolic product has no gradient of its own
     };
@@ -833,6 +838,7 @@ BatchP batch_compose(const BatchP& a, const BatchP& b, bool intersect) {
     r->chain = chain_first ? a : b;
     r->chain_first = chain_first;
     r->intersect = intersect;
+    r->wide = wide;
     return r;
   }
   batch_materialise(*a);
@@ -843,7 +849,7 @@ BatchP batch_compose(const BatchP& a, const BatchP& b, bool intersect) {
 BatchP batch_shortest_distance(const BatchP& x, bool tropical) {
   GTNX_HOST_T("batch.shortest_distance");
   Runtime& rt = Runtime::get();
-  if (!tropical && native(*x, Batch::PRODUCT) && !x->materialised) {
+  if (!tropical && native(*x, Batch::PRODUCT) && !x->materialised && !x->wide) {
     Batch& fx = *x->fixed;
     Batch& ch = *x->chain;
     const int n = x->n, T = ch.M, C = ch.C;
@@ -1010,11 +1016,11 @@ std::atomic<int64_t> g_align_fast{0}, g_align_fallback{0};
 void align_fallback(const BatchP& x, const int* frames, int* labels_dev, int64_t row_stride, int* tokens_dev,
                     float* scores_dev) {
   if (tokens_dev)
-    throw_invalid("[gtnx_batch_viterbi_align] token indices are defined for device-built CTC targets composed with a "
-                  "linear batch only (this batch takes the path-graph route)");
+    throw_invalid("[gtnx_batch_viterbi_align] token indices are defined for device-built CTC targets or ASG force-alignment "
+                  "acceptors composed with a linear batch only (this batch takes the path-graph route)");
   if (frames)
-    throw_invalid("[gtnx_batch_viterbi_align] per-utterance frame counts need device-built CTC targets composed with a "
-                  "linear batch (this batch takes the path-graph route)");
+    throw_invalid("[gtnx_batch_viterbi_align] per-utterance frame counts need device-built CTC targets or ASG "
+                  "force-alignment acceptors composed with a linear batch (this batch takes the path-graph route)");
   GTNX_HOST_T("batch.viterbi_align.fallback");
   Runtime& rt = Runtime::get();
   const int n = x->n;
@@ -1073,7 +1079,16 @@ void batch_viterbi_align(const BatchP& x, const int* frames, int* labels_dev, in
     // the closed form of the queue ranks (ops_band.cpp tie_ranks) holds with the blank below every label
     for (size_t i = 0; i < fx.labels.size() && fast; ++i) fast = fx.labels[i] > fx.blank;
   }
-  if (!fast) {
+  // ... or of device-built force-alignment acceptors o ASG transitions (asg_align.hip), either argument order
+  bool asg = x->kind == Batch::PRODUCT && x->fixed && x->chain && x->fixed->kind == Batch::CTC_TARGETS && x->fixed->fal &&
+             x->chain->kind == Batch::LINEAR && x->fixed->rec_mem && x->fixed->n == n && x->chain->n == n;
+  if (asg) {
+    const Batch& fx = *x->fixed;
+    const Batch& ch = *x->chain;
+    const int vec = ch.C % 4 == 0 && (reinterpret_cast<uintptr_t>(ch.w_dev) & 15) == 0;
+    asg = asg_align_ok(fx.max_nodes, ch.C, vec) && fx.trans_labels == ch.C && fx.max_label < ch.C;
+  }
+  if (!fast && !asg) {
     align_fallback(x, frames, labels_dev, row_stride, tokens_dev, scores_dev);
     return;
   }
@@ -1088,6 +1103,39 @@ void batch_viterbi_align(const BatchP& x, const int* frames, int* labels_dev, in
         throw_invalid("[gtnx_batch_viterbi_align] a frame count beyond the rows the chain carries");
     }
   if (ch.w_pend) ch.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  if (asg) {
+    // back-pointer planes: 1 bit per (time, node), one 256-byte row of words per 32 / NPL steps, NPL the LAUNCH's
+    const int npl = asg_align_npl(fx.max_nodes);
+    const size_t plane = asg_align_plane_bytes(T, npl);
+    DevMemP work = rt.alloc(plane * size_t(n));
+    std::vector<AsgAlignArgs> tab(static_cast<size_t>(n));
+    double abytes = 0;
+    for (int b = 0; b < n; ++b) {
+      AsgAlignArgs& a = tab[size_t(b)];
+      a = AsgAlignArgs{};
+      const int U = fx.lab_off[size_t(b) + 1] - fx.lab_off[size_t(b)];
+      const size_t N = size_t(U) + 1;
+      char* base = fx.rec_mem->as<char>(fx.rec_off[size_t(b)]);
+      a.nodes = reinterpret_cast<BandNode*>(base);
+      a.nflags = reinterpret_cast<uint8_t*>(base + align_up(sizeof(BandNode) * N, 64));
+      a.w = fx.rec_mem->as<float>(fx.w_off[size_t(b)]);
+      a.em = ch.w_dev + size_t(b) * size_t(T) * size_t(C);
+      a.bp = work->as<unsigned>(plane * size_t(b));
+      a.labels = labels_dev + int64_t(b) * row_stride;
+      a.tokens = tokens_dev ? tokens_dev + int64_t(b) * row_stride : nullptr;
+      a.score = scores_dev ? scores_dev + b : nullptr;
+      a.N = int(N);
+      a.T = frames ? frames[b] : ch.rows_of(b);
+      a.T_full = T;
+      a.C = C;
+      abytes += 4.0 * a.T * C + 0.25 * double(a.T) * double(N) + 8.0 * a.T;
+    }
+    DevMemP d = upload_vec(tab);
+    GTNX_PROF("asg_viterbi_align", abytes);
+    launch_asg_align(d->as<AsgAlignArgs>(), n, fx.max_nodes, rt.stream());
+    g_align_fast.fetch_add(n);
+    return;
+  }
   // back-pointer planes: 2 bits per (time, node), one 256-byte row of words per 16 / NPL steps (align.hip)
   const int npl = align_npl(fx.max_nodes);
   const size_t plane = align_up((size_t(T) * size_t(npl) + 15) / 16 * 256 + 256, 256);

@@ -94,6 +94,8 @@ struct Batch {
   // ---- PRODUCT: compose(fixed, chain) / compose(chain, fixed), never built
   BatchP fixed, chain;
   bool chain_first = false, intersect = false;
+  bool wide = false;  // force-alignment acceptors x an alphabet of 1025 .. 2048 labels: past the band sweeps, kept for
+                      // batch_viterbi_align's launch (asg_align.hip) -- everything else composes the element graphs
   // ---- SCALAR: one float per element
   DevMemP v_mem;
   float* v_dev = nullptr;
@@ -124,7 +126,9 @@ BatchP batch_viterbi_path(const BatchP& x);
 // sequence (-1 on blank frames), scores_dev[b] the path's score.  A PRODUCT of device-built CTC targets (blank below
 // every label) with a LINEAR batch is aligned by one launch on the engine's stream (align.hip): no graphs, no copy
 // back, no synchronisation; frames (host, [n], or null): rows of each utterance to align (null: the chain's own row
-// counts; more than those: invalid argument).  Every other batch goes
+// counts; more than those: invalid argument).  A PRODUCT of device-built force-alignment acceptors o ASG transitions
+// (batch_asg_force_align) with a LINEAR batch over the same alphabet likewise, either argument order (asg_align.hip;
+// tokens = index into the label sequence, never -1 inside a path; exact ties: the step wins).  Every other batch goes
 // through batch_viterbi_path and one upload; tokens_dev and frames are invalid arguments there.
 void batch_viterbi_align(const BatchP& x, const int* frames, int* labels_dev, int64_t row_stride, int* tokens_dev,
                          float* scores_dev);

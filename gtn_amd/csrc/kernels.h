@@ -566,6 +566,28 @@ int align_npl(int max_nodes);  // nodes per lane of a launch (1, 2, 4, 8)
 // max_nodes <= 512, C <= 2048 and a multiple of 4, every em 16-byte aligned: band_align_ok
 bool band_align_ok(int max_nodes, int max_labels, int vec);
 void launch_band_align(const AlignArgs* d_args, int n, int max_nodes, hipStream_t st);
+// Forced alignment of chain o (force-alignment acceptor o ASG transitions), one wave per utterance (asg_align.hip):
+// the tropical recursion over the U + 1 nodes of batch_asg_force_align's band records -- two candidates per node, the
+// self-loop (aid[0]) and the step from node n - 1 (aid[1]), weights from the batch's gathered `w` -- over the first T of
+// the utterance's T_full emission rows; of two equal candidates the step wins (the reference's queue order); the frame
+// labels / token indices (node - 1, never -1 inside a path) written from the pointer chase into the caller's rows.
+struct AsgAlignArgs {
+  const GTNX_G BandNode* nodes;  // [N = U + 1] the target's band records (batch_asg_force_align)
+  const GTNX_G uint8_t* nflags;  // [N]
+  const GTNX_G float* w;         // [2U] arc weights, arc-id order (BandNode.aid indexes it)
+  const GTNX_G float* em;        // [T_full][C], 16-byte aligned, C % 4 == 0
+  GTNX_G unsigned* bp;           // back-pointer words, 1 bit per (time, node): ceil(T * NPL / 32) rows of 64
+  GTNX_G int* labels;            // [T_full] label of every frame, -1 from T on (and everywhere without a path)
+  GTNX_G int* tokens;            // [T_full] index into the label sequence; or null
+  GTNX_G float* score;           // [1] or null
+  int N, T, T_full, C;
+};
+int asg_align_npl(int max_nodes);  // nodes per lane of a launch (1, 2, 4, 8)
+int asg_align_max_labels();        // 2048
+// max_nodes <= 512, C <= 2048 and a multiple of 4, every em 16-byte aligned: asg_align_ok
+bool asg_align_ok(int max_nodes, int max_labels, int vec);
+size_t asg_align_plane_bytes(int T, int npl);  // one utterance's back-pointer plane, sized by the LAUNCH's npl
+void launch_asg_align(const AsgAlignArgs* d_args, int n, int max_nodes, hipStream_t st);
 // ---------------------------------------------------------------------------
 // rational.hip: clone / concat / closure / union_ (functions.cpp:66-223) built on the device
 // ---------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-"""PyTorch entry points of the hot path: `ctc_loss`, `asg_loss` and `ctc_forced_align`.
+"""PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align` and
+`asg_forced_align`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -39,6 +40,10 @@ def _native():
                 lib.gtn_ctc_align_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
                 lib.gtn_ctc_align_n.restype = C.c_int
+            if hasattr(lib, "gtn_asg_align_n"):
+                lib.gtn_asg_align_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+                lib.gtn_asg_align_n.restype = C.c_int
             _NATIVE = lib
         else:
             _NATIVE = False
@@ -315,3 +320,71 @@ def asg_loss(emissions, transitions, targets, start=None, reduction="none"):
     if start is None:
         start = torch.zeros(emissions.shape[-1], dtype=torch.float32, device=emissions.device)
     return _ASGLoss.apply(emissions, transitions, start, targets, reduction)
+
+
+def _asg_transitions_graph(N, w):
+    """gtn::criteria::asgTransitions(N) over the device weights `w` ([N + N*N]: N start arcs, then arc N + i*N + j =
+    j -> i)"""
+    g = gtn.Graph(False)
+    g.add_nodes(np.array([1] + [0] * N, np.uint8), np.array([0] + [1] * N, np.uint8))
+    n = np.arange(N)
+    src = np.concatenate([np.zeros(N, np.int32), np.tile(n + 1, N).astype(np.int32)])
+    dst = np.concatenate([n + 1, np.repeat(n + 1, N)]).astype(np.int32)
+    lab = np.concatenate([n, np.repeat(n, N)]).astype(np.int32)
+    g.add_arcs(src, dst, lab, lab, np.zeros(N + N * N, np.float32))
+    g.arc_sort()
+    g.set_weights_device(w)
+    return g
+
+
+def asg_forced_align(emissions, transitions, targets, start=None, input_lengths=None):
+    """ASG forced alignment of a batch, device-resident: the best path of emissions_b o (forceAlign(target_b) o
+    transitions) (the reference's viterbiPath over examples/asg.cpp:50-68) for every utterance in one launch, nothing
+    copied back.
+    emissions: float32 CUDA tensor [B, T, N] (any scores), read in place and left untouched; transitions: [N, N] with
+    transitions[i, j] the score of label j followed by label i; start: [N] scores of the first label (zeros when
+    omitted); targets: B label sequences over 0 .. N-1; input_lengths: per-utterance frame counts (0 .. T) or None.
+    Returns (labels int32 [B, T], tokens int32 [B, T], scores float32 [B]) on emissions.device: the label of every
+    frame, the index of that label in its target (which of two equal neighbours a frame belongs to; never -1 inside
+    a path), the path score.  Entries past an utterance's length are -1; an utterance with fewer frames than labels
+    (or with no labels) has score -inf and rows of -1.  Of two exactly equal candidates the step to the next label
+    wins, as in the reference.  No autograd.
+    The launch takes N a multiple of 4 with 4 <= N <= 2048 and targets of at most 511 labels; any other shape raises
+    the engine's error (token indices and frame counts do not exist on the path-graph route)."""
+    assert emissions.is_cuda and emissions.dtype == torch.float32 and emissions.dim() == 3
+    B, T, N = emissions.shape
+    if start is None:
+        start = torch.zeros(N, dtype=torch.float32, device=emissions.device)
+    assert transitions.shape == (N, N) and start.shape == (N,)
+    if len(targets) != B:
+        raise ValueError(f"asg_forced_align: {len(targets)} target sequences for a batch of {B}")
+    frames = None if input_lengths is None else _frame_counts("asg_forced_align", input_lengths, B, T, 0)
+    x = emissions.detach().contiguous()
+    # arc order of gtn::criteria::asgTransitions: N start arcs, then arc N + i*N + j = j -> i
+    w = torch.cat([start.detach().reshape(-1), transitions.detach().reshape(-1)]).to(torch.float32).contiguous()
+    stream = torch.cuda.current_stream(x.device)
+    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
+    if not stream.cuda_stream:
+        stream.synchronize()  # engine runs on its own stream
+    labels = torch.empty(B, T, dtype=torch.int32, device=x.device)
+    tokens = torch.empty(B, T, dtype=torch.int32, device=x.device)
+    scores = torch.empty(B, dtype=torch.float32, device=x.device)
+    lib = _native()
+    if lib:
+        if not hasattr(lib, "gtn_asg_align_n"):
+            raise RuntimeError("asg_forced_align needs gtn_asg_align_n in gtn_amd/lib/libgtn_criteria.so "
+                               "(run __graft_entry__.build())")
+        flat, lens = _flat_targets(targets)
+        rc = lib.gtn_asg_align_n(x.data_ptr(), flat.ctypes.data, lens.ctypes.data, B, T, N, w.data_ptr(),
+                                 frames.ctypes.data if frames is not None else None, labels.data_ptr(),
+                                 tokens.data_ptr(), scores.data_ptr())
+        if rc != 0:
+            raise RuntimeError(lib.gtn_criteria_last_error().decode())
+    else:
+        trans = _asg_transitions_graph(N, w)
+        ems = gtn.Batch.linear(B, T, N, x, calc_grad=False, borrow=True)
+        fals = gtn.Batch.asg_force_align([list(t) for t in targets], trans, N)
+        gtn.compose(ems, fals).viterbi_align(labels, tokens, scores, frames)
+    if not stream.cuda_stream:
+        gtn.synchronize()
+    return labels, tokens, scores

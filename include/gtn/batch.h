@@ -148,8 +148,10 @@ inline Batch viterbiPath(const Batch& a) { return detail::batchUnary(&gtnx_batch
 /** Forced alignment with the results left on the device: row b of labelsDevice (int32, rowStride entries apart) gets
  *  the label of every frame of utterance b's best path, -1 past the path; tokensDevice the index into the label
  *  sequence (-1 on blank frames), scoresDevice the path scores; frames (host, [n]): emission rows to align per
- *  utterance.  One launch, no copy back and no wait for a product of Batch::ctcTargets with Batch::linear; other
- *  batches go through viterbiPath (tokensDevice and frames must be null there) -- gtnx_batch_viterbi_align */
+ *  utterance.  One launch, no copy back and no wait for a product of Batch::ctcTargets with Batch::linear, and for a
+ *  product of Batch::asgForceAlign with Batch::linear over the same alphabet (either argument order; tokens = index
+ *  into the label sequence, never -1 inside an ASG path); other batches go through viterbiPath (tokensDevice and
+ *  frames must be null there) -- gtnx_batch_viterbi_align */
 inline void viterbiAlign(const Batch& product, int* labelsDevice, int64_t rowStride, int* tokensDevice = nullptr,
                          float* scoresDevice = nullptr, const int* frames = nullptr) {
   detail::check(gtnx_batch_viterbi_align(product.handle(), frames, labelsDevice, rowStride, tokensDevice, scoresDevice));

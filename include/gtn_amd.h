@@ -302,8 +302,12 @@ gtnx_status_t gtnx_batch_viterbi_path(gtnx_batch_t a, gtnx_batch_t* out);       
  * a path.  frames (host, [n], or null): how many of the T emission rows of each utterance are aligned.
  * A composition of gtnx_batch_ctc_targets (blank below every label) with gtnx_batch_linear (alphabet a multiple of 4,
  * at most 2048; at most 512 nodes) is aligned by ONE launch on the engine's stream: nothing is copied back and the
- * call does not wait for the device.  Any other batch goes through gtnx_batch_viterbi_path and one upload; tokens_device
- * and frames are GTNX_INVALID_ARGUMENT there.  Output pointers must be memory the engine's current device may write. */
+ * call does not wait for the device.  So is a composition, in either argument order, of gtnx_batch_asg_force_align
+ * over n_labels labels with gtnx_batch_linear over the same alphabet (a multiple of 4, at most 2048; targets of at most
+ * 511 labels): there tokens_device is the index into the label sequence of the label the frame carries -- never -1
+ * inside a path, ASG has no blanks -- and of two equal candidates the step from the previous label wins, as in the
+ * reference's viterbiPath on the built lattice.  Any other batch goes through gtnx_batch_viterbi_path and one upload;
+ * tokens_device and frames are GTNX_INVALID_ARGUMENT there.  Output pointers must be memory the engine's current device may write. */
 gtnx_status_t gtnx_batch_viterbi_align(gtnx_batch_t a, const int* frames, void* labels_device, int64_t row_stride,
                                        void* tokens_device, void* scores_device);
 /* utterances aligned so far (process-wide) by the launch / by the path-graph route */
