@@ -66,6 +66,7 @@ debug_symbolic_route = _api.debug_symbolic_route
 debug_viterbi_ties = _api.debug_viterbi_ties
 debug_tie_ranks = _api.debug_tie_ranks
 debug_align_stats = getattr(_api, "debug_align_stats", None)  # (Batch.viterbi_align: which route aligned how many)
+debug_decode_stats = _api.debug_decode_stats  # (Batch.viterbi_decode: which route decoded how many)
 
 
 def load_txt(text):

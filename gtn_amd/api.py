@@ -757,6 +757,42 @@ def make_api(lib):
                                                _as_dev_ptr(tokens_out) if tokens_out is not None else None,
                                                _as_dev_ptr(scores_out) if scores_out is not None else None))
 
+        def viterbi_decode(self, transitions, labels_out, scores_out=None, frames=None, collapsed_out=None,
+                           lengths_out=None, row_stride=None):
+            """viterbi_path(compose(element b, transitions)) of the whole batch against ONE shared graph, results left
+            on the device (gtnx_batch_viterbi_decode): row b of `labels_out` (int32 CUDA tensor [B, >= M], or a device
+            address with `row_stride` entries between rows) gets the label of every frame t < T_b and -1 from T_b to
+            the row's width M; `scores_out` (float32 [B]) the path scores; `collapsed_out` (int32, rows like
+            labels_out) the labels with runs of equal consecutive frames merged, then -1; `lengths_out` (int32 [B],
+            needs collapsed_out) how many; `frames`: T_b per element (0 .. M, at most the rows the batch carries;
+            None: those rows).  Without an accepting path (T_b = 0 included): entries -1, score -inf, length 0.
+            A Batch.linear against an asg-transitions-shaped graph of 8 .. 1024 nodes (7 .. 1023 labels) is ONE sweep
+            of the padded batch and one launch, with no copy back and no wait; the pad rows never change a bit of any
+            output; exact ties: first accept node, then the smallest source node.  Other graphs / batches go through
+            viterbi_path and one upload (`frames` is an error there)."""
+            n = len(self)
+            stride = row_stride
+            for t in (labels_out, collapsed_out):
+                if t is None or not hasattr(t, "data_ptr"):
+                    continue
+                if t.element_size() != 4 or t.dim() != 2 or t.shape[0] < n or (t.shape[1] > 1 and t.stride(1) != 1):
+                    raise ValueError("viterbi_decode: outputs must be int32 tensors [B, M] with contiguous rows")
+                if stride is not None and t.stride(0) != stride:
+                    raise ValueError("viterbi_decode: labels_out and collapsed_out must have the same row stride")
+                stride = t.stride(0)
+            if stride is None:
+                raise ValueError("viterbi_decode: a device address needs row_stride")
+            if lengths_out is not None and collapsed_out is None:
+                raise ValueError("viterbi_decode: lengths_out needs collapsed_out")
+            fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32)
+            if fr is not None and fr.shape != (n,):
+                raise ValueError("viterbi_decode: one frame count per element")
+            check(lib.gtnx_batch_viterbi_decode(self._h, transitions._h, fr.ctypes.data if fr is not None else None,
+                                                _as_dev_ptr(labels_out), int(stride),
+                                                _as_dev_ptr(scores_out) if scores_out is not None else None,
+                                                _as_dev_ptr(collapsed_out) if collapsed_out is not None else None,
+                                                _as_dev_ptr(lengths_out) if lengths_out is not None else None))
+
     ns.Batch = Batch
 
     def _batch_fn(cfn, *args):
@@ -879,8 +915,16 @@ def make_api(lib):
         check(lib.gtnx_batch_align_stats(C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def debug_decode_stats():
+        """(fast, fallback): utterances Batch.viterbi_decode has decoded so far by its one launch / through the path
+        graphs of viterbi_path (include/gtn_amd.h: gtnx_batch_decode_stats)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(lib.gtnx_batch_decode_stats(C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     if hasattr(lib, "gtnx_batch_align_stats"):
         ns.debug_align_stats = debug_align_stats
+    ns.debug_decode_stats = debug_decode_stats
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties
 

@@ -136,5 +136,30 @@ inline void asgAlignBatch(
                 scoresDev);
 }
 
+/** ASG decode of a batch, results on the device: per utterance the best path of emissions_b o transitions
+ *  (viterbiPath, shortest.cpp:190-272) as the label of every frame (`labelsDev`, device int32 [B][T]), the path score
+ *  (`scoresDev`, device float [B] or null), the labels with runs of equal consecutive frames merged (`collapsedDev`,
+ *  device int32 [B][T] or null) and how many of them (`lengthsDev`, device int32 [B] or null; needs collapsedDev).
+ *  `frames`: host [B] or null -- how many of the T rows of each utterance count (0 .. T); entries past them are -1, and
+ *  an utterance without frames has score -inf and length 0.  `emissions`: device [B][T][N], read in place, pad rows
+ *  included (what they hold never changes a bit of any output); `transitions`: the graph of asgTransitions(N) with the
+ *  caller's weights.  7 <= N <= 1023: one sweep of the padded batch and one launch, nothing is copied back; exact ties
+ *  go to the smallest label.  Other N take the path-graph route, which has no frame counts. */
+inline void asgDecodeBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int N,
+    Graph& transitions,
+    const int* frames,
+    void* labelsDev,
+    void* scoresDev,
+    void* collapsedDev,
+    void* lengthsDev) {
+  Batch ems = Batch::linear(B, T, N, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  batched::viterbiDecode(ems, transitions, static_cast<int*>(labelsDev), T, static_cast<float*>(scoresDev), frames,
+                         static_cast<int*>(collapsedDev), static_cast<int*>(lengthsDev));
+}
+
 } // namespace criteria
 } // namespace gtn

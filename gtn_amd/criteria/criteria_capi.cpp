@@ -138,3 +138,30 @@ extern "C" __attribute__((visibility("default"))) int gtn_asg_align_n(const void
     return -1;
   }
 }
+
+// ASG decode.  emissions: DEVICE [B][T][N]; trans_w: DEVICE [N + N*N] as for gtn_asg_loss_n; frames: host int32 [B] or
+// null; labels: DEVICE int32 [B][T]; scores: DEVICE float [B] or null; collapsed: DEVICE int32 [B][T] or null; lengths:
+// DEVICE int32 [B] or null (needs collapsed).  Returns 0, or -1 with the message in gtn_criteria_last_error().
+extern "C" __attribute__((visibility("default"))) int gtn_asg_decode_n(const void* emissions, int B, int T, int N,
+                                                                       const void* trans_w, const int* frames,
+                                                                       void* labels, void* scores, void* collapsed,
+                                                                       void* lengths) {
+  try {
+    // (a structure of its own per N, as gtn_asg_align_n keeps: the loss's cached graph carries gradient state)
+    static std::mutex mu;
+    static auto* cache = new std::map<int, gtn::Graph>();  // never destroyed: outlives the engine's teardown
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache->find(N);
+    if (it == cache->end()) {
+      it = cache->emplace(N, gtn::criteria::asgTransitions(N)).first;
+      it->second.setCalcGrad(false);
+    }
+    gtn::Graph& trans = it->second;
+    trans.setWeightsDevice(trans_w);  // arc ids are creation order: arcSort permutes lists, not ids
+    gtn::criteria::asgDecodeBatch(emissions, B, T, N, trans, frames, labels, scores, collapsed, lengths);
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}

@@ -1171,6 +1171,136 @@ void batch_viterbi_align(const BatchP& x, const int* frames, int* labels_dev, in
   g_align_fast.fetch_add(n);
 }
 
+// ---- decode against one shared transitions graph with device-resident output (asg_decode.hip) ----------------
+namespace {
+std::atomic<int64_t> g_decode_fast{0}, g_decode_fallback{0};
+
+// every other graph or batch: viterbiPath over the composed elements, labels read and collapsed on the host, one upload
+void decode_fallback(const BatchP& ems, Graph& transitions, const int* frames, int* labels_dev, int64_t row_stride,
+                     float* scores_dev, int* collapsed_dev, int* lengths_dev) {
+  if (frames)
+    throw_invalid("[gtnx_batch_viterbi_decode] per-utterance frame counts need a linear batch and a dense transitions "
+                  "graph of 8 .. 1024 nodes whose ties go by node order (this batch takes the path-graph route, which "
+                  "decodes the rows the elements carry: pass frames = null)");
+  GTNX_HOST_T("batch.viterbi_decode.fallback");
+  Runtime& rt = Runtime::get();
+  const int n = ems->n;
+  batch_materialise(*ems);
+  std::vector<Graph> tr{transitions};
+  std::vector<Graph> comp = op_compose(ems->graphs, tr, false);
+  std::vector<Graph> paths = op_viterbi_path(comp);
+  int64_t width = ems->kind == Batch::LINEAR ? ems->M : 0;
+  for (int b = 0; b < n; ++b) width = std::max<int64_t>(width, paths[size_t(b)].num_arcs());
+  if (width > row_stride) throw_invalid("[gtnx_batch_viterbi_decode] row_stride is shorter than the longest path");
+  const size_t cells = size_t(n) * size_t(width ? width : 1);
+  PinnedMemP hl = rt.alloc_pinned(sizeof(int) * cells * 2);
+  PinnedMemP hs = rt.alloc_pinned((sizeof(float) + sizeof(int)) * size_t(n));
+  int* lab = hl->as<int>();
+  int* col = lab + cells;
+  float* sc = hs->as<float>();
+  int* len_out = reinterpret_cast<int*>(sc + n);
+  std::fill(lab, lab + 2 * cells, -1);
+  for (int b = 0; b < n; ++b) {
+    Graph& g = paths[size_t(b)];
+    const int64_t len = g.num_arcs();
+    float score = (g.num_nodes() > 0 && len > 0) ? 0.0f : -std::numeric_limits<float>::infinity();
+    int k = 0;
+    if (len > 0) {
+      g.s->ensure_host();
+      int* row = lab + size_t(b) * size_t(width);
+      int* crow = col + size_t(b) * size_t(width);
+      std::copy(g.s->il.begin(), g.s->il.begin() + len, row);
+      const float* w = g.weights_host(false);
+      for (int64_t t = 0; t < len; ++t) {
+        score += w[t];  // (in path order, as the recursion accumulates it)
+        if (t == 0 || row[t] != row[t - 1]) crow[k++] = row[t];
+      }
+    }
+    sc[b] = score;
+    len_out[b] = k;
+  }
+  if (width > 0) {
+    HIP_CHECK(hipMemcpy2DAsync(labels_dev, sizeof(int) * size_t(row_stride), lab, sizeof(int) * size_t(width),
+                               sizeof(int) * size_t(width), size_t(n), hipMemcpyHostToDevice, rt.stream()));
+    if (collapsed_dev)
+      HIP_CHECK(hipMemcpy2DAsync(collapsed_dev, sizeof(int) * size_t(row_stride), col, sizeof(int) * size_t(width),
+                                 sizeof(int) * size_t(width), size_t(n), hipMemcpyHostToDevice, rt.stream()));
+  }
+  if (scores_dev) rt.h2d_pinned(scores_dev, sc, sizeof(float) * size_t(n));
+  if (lengths_dev) rt.h2d_pinned(lengths_dev, len_out, sizeof(int) * size_t(n));
+  g_decode_fallback.fetch_add(n);
+}
+}  // namespace
+
+void batch_decode_stats(int64_t* fast, int64_t* fallback) {
+  if (fast) *fast = g_decode_fast.load();
+  if (fallback) *fallback = g_decode_fallback.load();
+}
+
+void batch_viterbi_decode(const BatchP& ems, Graph& transitions, const int* frames, int* labels_dev, int64_t row_stride,
+                          float* scores_dev, int* collapsed_dev, int* lengths_dev) {
+  GTNX_HOST_T("batch.viterbi_decode");
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) throw_invalid("[gtnx_batch_viterbi_decode] null batch");
+  if (!labels_dev) throw_invalid("[gtnx_batch_viterbi_decode] null labels pointer");
+  if (row_stride < 0) throw_invalid("[gtnx_batch_viterbi_decode] negative row stride");
+  if (lengths_dev && !collapsed_dev)
+    throw_invalid("[gtnx_batch_viterbi_decode] lengths are those of the collapsed sequences: pass collapsed_device too");
+  const int n = ems->n;
+  const bool linear = ems->kind == Batch::LINEAR && !ems->leaf;
+  if (frames && linear)
+    for (int b = 0; b < n; ++b) {
+      if (frames[b] < 0 || frames[b] > ems->M) throw_invalid("[gtnx_batch_viterbi_decode] a frame count outside 0 .. M");
+      if (frames[b] > ems->rows_of(b))
+        throw_invalid("[gtnx_batch_viterbi_decode] a frame count beyond the rows the batch carries");
+    }
+  if (linear && n > 0 && row_stride < ems->M)
+    throw_invalid("[gtnx_batch_viterbi_decode] row_stride is shorter than the rows of the batch");
+  Runtime& rt = Runtime::get();
+  if (n <= 0) return;
+  // a kernel of this device writes the results: memory of another GPU of the process is refused, not written
+  if (!ptr_local_to(labels_dev, rt.device()) || (scores_dev && !ptr_local_to(scores_dev, rt.device())) ||
+      (collapsed_dev && !ptr_local_to(collapsed_dev, rt.device())) ||
+      (lengths_dev && !ptr_local_to(lengths_dev, rt.device())))
+    throw_invalid("[gtnx_batch_viterbi_decode] an output pointer is not memory of the engine's current device");
+  if (!linear || !ems->w_dev || !lazy_decode_ok(transitions, ems->M, ems->C)) {
+    decode_fallback(ems, transitions, frames, labels_dev, row_stride, scores_dev, collapsed_dev, lengths_dev);
+    return;
+  }
+  Batch& x = *ems;
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  // full-length views of the slabs (batch_materialise's elements with M rows whatever `rows` says): one shape, one
+  // group, one sweep -- the sweep reads the pad rows, the back-trace never looks at what it made of them
+  std::vector<Graph> chains;
+  chains.reserve(size_t(n));
+  std::vector<int> fr(static_cast<size_t>(n));
+  {
+    GraphSlabScope slab_scope(size_t(n));
+    const int64_t stride = int64_t(x.M) * x.C;
+    for (int i = 0; i < n; ++i) {
+      Graph g = Graph::make_result(false);
+      Structure& s = *g.s;
+      s.kind = KIND_LINEAR;
+      s.M = x.M;
+      s.C = x.C;
+      s.N = int64_t(x.M) + 1;
+      s.A = stride;
+      s.ilabel_sorted = s.olabel_sorted = true;
+      Weights& w = *g.w;
+      w.n = stride;
+      w.dev_mem = x.w_mem;
+      w.dev = x.w_dev + size_t(i) * size_t(stride);
+      w.dev_valid = true;
+      w.host_valid = false;
+      w.version++;
+      chains.push_back(std::move(g));
+      fr[size_t(i)] = frames ? frames[i] : x.rows_of(i);
+    }
+  }
+  lazy_viterbi_decode(chains, transitions, fr, labels_dev, row_stride, scores_dev, collapsed_dev, lengths_dev);
+  g_decode_fast.fetch_add(n);
+}
+
 
 namespace {
 // a GRAPHS batch of one-arc graphs as a native SCALAR batch (values gathered; backward continues on the graphs' tape)

@@ -133,6 +133,20 @@ BatchP batch_viterbi_path(const BatchP& x);
 void batch_viterbi_align(const BatchP& x, const int* frames, int* labels_dev, int64_t row_stride, int* tokens_dev,
                          float* scores_dev);
 void batch_align_stats(int64_t* fast, int64_t* fallback);  // utterances aligned by the launch / by the path graphs
+// viterbiPath(ems_b o transitions) of a whole batch against ONE shared graph, results on the device: labels_dev[b *
+// row_stride + t] = the label of frame t of utterance b's best path for t < T_b, -1 from T_b to the row's width M (and
+// everywhere without an accepting path: score -inf, length 0); scores_dev[b] (or null) the path score; collapsed_dev[b *
+// row_stride + ..] (or null) the labels with runs of equal consecutive frames merged, -1 up to M; lengths_dev[b] (or
+// null; needs collapsed_dev) how many.  frames (host, [n], or null): T_b, null = rows_of(b); outside 0 .. M or above
+// rows_of(b): invalid argument, before anything is launched.  A native LINEAR batch against a graph in the dense regime
+// whose ties go by node order (lazy_decode_ok: asgTransitions-shaped, 8 .. 1024 nodes) with outputs local to the
+// device: full-length views of the slabs form ONE max-plus group (the sweep reads the pad rows; what they hold never
+// changes a bit of any output), asg_decode.hip is launched once, no download, no path graphs, no wait.  Ties: first
+// accept node in accept-list order, then the smallest source node.  Everything else: op_viterbi_path over the composed
+// elements, labels read and collapsed on the host, one upload; frames must be null there.
+void batch_viterbi_decode(const BatchP& ems, Graph& transitions, const int* frames, int* labels_dev, int64_t row_stride,
+                          float* scores_dev, int* collapsed_dev, int* lengths_dev);
+void batch_decode_stats(int64_t* fast, int64_t* fallback);  // utterances decoded by the launch / by the path graphs
 // items_dev (optional): device memory of the CALLER's that the n result values are written into directly (borrowed: it
 // must outlive the result); a later batch_items_device to the same address copies nothing
 BatchP batch_scalar(ScalarKind k, const BatchP& a, const BatchP& b, void* items_dev = nullptr);

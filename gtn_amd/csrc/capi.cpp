@@ -872,6 +872,18 @@ GTNX_API gtnx_status_t gtnx_batch_viterbi_align(gtnx_batch_t a, const int* frame
 GTNX_API gtnx_status_t gtnx_batch_align_stats(int64_t* fast, int64_t* fallback) {
   return guard([&] { batch_align_stats(fast, fallback); });
 }
+GTNX_API gtnx_status_t gtnx_batch_viterbi_decode(gtnx_batch_t ems, gtnx_graph_t transitions, const int* frames,
+                                                 void* labels_device, int64_t row_stride, void* scores_device,
+                                                 void* collapsed_device, void* lengths_device) {
+  return guard([&] {
+    batch_viterbi_decode(BH(ems), G(transitions), frames, static_cast<int*>(labels_device), row_stride,
+                         static_cast<float*>(scores_device), static_cast<int*>(collapsed_device),
+                         static_cast<int*>(lengths_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_decode_stats(int64_t* fast, int64_t* fallback) {
+  return guard([&] { batch_decode_stats(fast, fallback); });
+}
 GTNX_API gtnx_status_t gtnx_batch_backward(gtnx_batch_t a, int retain) {
   return guard([&] { batch_backward(BH(a), retain != 0); });
 }

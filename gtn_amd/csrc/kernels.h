@@ -695,6 +695,14 @@ void launch_maxplus_prep(const LazyGroup& g, hipStream_t st);                  /
 void launch_maxplus_step(const LazyGroup& g, int t, hipStream_t st);           // alpha[t] -> alpha[t+1]
 void launch_maxplus_path(const LazyGroup& g, int* path_arc, int* path_il, int* path_ol, float* path_w, int* path_len,
                          hipStream_t st);
+// asg_decode.hip: the decode of every utterance of a max-plus group at its own length, results on the device -- one
+// wave per utterance walks back from row d_frames[b] (device, [nb], 0 .. g.T) of the alpha planes the sweeps above
+// filled for t = 0 .. g.T: labels[b * row_stride + t] the label of frame t (-1 from d_frames[b] to g.T), scores[b] the
+// best accept score of that row (or null), collapsed[b * row_stride + ..] the labels with runs merged, -1 up to g.T
+// (or null), lengths[b] how many (or null).  Ties: first accept node in accept_list order, smallest source node.
+// No accepting path: entries -1, score -inf, length 0.  Nothing past row d_frames[b] is read.
+void launch_asg_decode(const LazyGroup& g, const int* d_frames, int* labels, int64_t row_stride, float* scores,
+                       int* collapsed, int* lengths, hipStream_t st);
 void launch_lazy_mfma_prep(const LazyGroup& g, hipStream_t st);                // Ep / ETp from E
 void launch_lazy_mfma_init(const LazyGroup& g, int which, hipStream_t st);     // keys, first input (0 forward, 1 backward)
 void launch_lazy_mfma_step(const LazyGroup& g, int t, int backward, hipStream_t st);

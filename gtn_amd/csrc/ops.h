@@ -74,6 +74,14 @@ std::vector<Graph> op_scalar(ScalarKind k, std::vector<Graph>& a, std::vector<Gr
 std::vector<Graph> op_shortest_distance(std::vector<Graph>& gs, bool tropical);
 std::vector<Graph> op_viterbi_path(std::vector<Graph>& gs);
 std::vector<Graph> op_compose(std::vector<Graph>& a, std::vector<Graph>& b, bool intersect);
+// viterbiPath(chain_b o fixed) for chains of ONE length M that share `fixed`, each decoded at its own frame count, the
+// results left on the device (ops_lazy.cpp, asg_decode.hip): one group through the max-plus sweeps, one launch of the
+// back-trace, no download, no path graphs, no wait.  lazy_decode_ok: `fixed` is an explicit graph in the dense regime
+// whose ties go by node order (an asgTransitions-shaped graph of 8 .. 1024 nodes) and chains of M rows over C labels
+// qualify.  frames: [chains.size()], each 0 .. M (checked by the caller).  collapsed_dev / lengths_dev / scores_dev may be null.
+bool lazy_decode_ok(Graph& fixed, int M, int C);
+void lazy_viterbi_decode(std::vector<Graph>& chains, Graph& fixed, const std::vector<int>& frames, int* labels_dev,
+                         int64_t row_stride, float* scores_dev, int* collapsed_dev, int* lengths_dev);
 // rational operations built on the device (rational.hip): clone / projections, concat, closure, union_
 enum RationalKind { RAT_CLONE = 0, RAT_CONCAT = 1, RAT_CLOSURE = 2, RAT_UNION = 3 };
 Graph op_rational(int kind, std::vector<Graph>& inputs, int projection);

@@ -752,6 +752,55 @@ std::vector<Graph> lazy_pair_forward_score(std::vector<Graph>& gs) {
   return outs;
 }
 
+// ---- decode of a padded batch against one shared G, results on the device (asg_decode.hip) -------------------
+// The group key (LazyKey) carries T, so chains of distinct lengths fall into one group -- one chain of T_b launches --
+// each.  Here every chain is a full-length view of its slab (M rows), so the batch is ONE group and one sweep, and the
+// back-trace of utterance b starts from row frames[b] of the planes that sweep stored.
+bool lazy_decode_ok(Graph& fixed, int M, int C) {
+  if (!fixed.s || fixed.s->lazy || fixed.s->deferred || fixed.s->kind != KIND_EXPLICIT || M < 1 || C < 1) return false;
+  Structure& fs = *fixed.s;
+  std::shared_ptr<Structure::DenseInfo> di;
+  if (!lazy_dense_ok(fs, /*chain_first=*/true, C, &di) || !di->ties_by_node_order || di->ncol <= 0) return false;
+  // (what compose asks of a product it keeps symbolic: ops_compose.cpp)
+  return size_t(lazy_tile_batch()) * size_t((fs.N | 1) + (int64_t(C) | 1)) * 4 <= size_t(lazy_lds_limit());
+}
+
+void lazy_viterbi_decode(std::vector<Graph>& chains, Graph& fixed, const std::vector<int>& frames, int* labels_dev,
+                         int64_t row_stride, float* scores_dev, int* collapsed_dev, int* lengths_dev) {
+  Runtime& rt = Runtime::get();
+  const size_t n = chains.size();
+  if (n == 0) return;
+  // the symbolic products compose(chain_b, fixed), as op_compose leaves them (never built, never handed out)
+  std::vector<Graph> prods;
+  prods.reserve(n);
+  {
+    GraphSlabScope slab_scope(n);
+    auto lop = make_lazy_compose_op();
+    for (size_t i = 0; i < n; ++i) {
+      Graph out = make_output(lop, int(i), {chains[i], fixed});
+      out.s->host_valid = false;
+      out.s->lazy = std::make_shared<LazyProduct>(LazyProduct{chains[i], fixed, 1, false});
+      prods.push_back(std::move(out));
+    }
+  }
+  std::vector<std::pair<int, int>> slot;
+  std::vector<std::shared_ptr<LazyGroupState>> groups = lazy_forward(prods, SD_TROPICAL, slot);
+  if (groups.size() != 1 || !groups[0]->maxplus || groups[0]->view.nb != int(n))
+    throw_logic("[gtnx_batch_viterbi_decode] internal: the batch did not form one max-plus group");
+  LazyGroup v = groups[0]->view;
+  v.tie_by_node = 1;
+  DevMemP d_frames = upload_vec(frames);
+  // algorithmic bytes of the back-trace: per frame one alpha row, one emission row (staged) and the visited node's
+  // in-row (16 B per record, max_in_deg at most); the label rows out, the collapsed pass over them
+  double bytes = 0;
+  for (size_t b = 0; b < n; ++b)
+    bytes += double(frames[b]) * (4.0 * v.N + 4.0 * v.C + 16.0 * groups[0]->max_in_deg) + 4.0 * v.T +
+             (collapsed_dev ? 4.0 * frames[b] + 4.0 * v.T : 0.0);
+  GTNX_PROF("asg_viterbi_decode", bytes);
+  launch_asg_decode(v, d_frames->as<int>(), labels_dev, row_stride, scores_dev, collapsed_dev, lengths_dev, rt.stream());
+  // (the planes and the table go back to the stream-ordered pool behind the launch)
+}
+
 std::atomic<int64_t> g_viterbi_ties_seen{0}, g_viterbi_ties_unresolved{0};
 
 void LazyPathOp::backward(std::vector<Member>& ms) {

@@ -1,5 +1,5 @@
-"""PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align` and
-`asg_forced_align`.
+"""PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
+`asg_forced_align` and `asg_decode`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -44,6 +44,10 @@ def _native():
                 lib.gtn_asg_align_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
                 lib.gtn_asg_align_n.restype = C.c_int
+            if hasattr(lib, "gtn_asg_decode_n"):
+                lib.gtn_asg_decode_n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+                lib.gtn_asg_decode_n.restype = C.c_int
             _NATIVE = lib
         else:
             _NATIVE = False
@@ -388,3 +392,61 @@ def asg_forced_align(emissions, transitions, targets, start=None, input_lengths=
     if not stream.cuda_stream:
         gtn.synchronize()
     return labels, tokens, scores
+
+
+def asg_decode(emissions, transitions, start=None, input_lengths=None, collapse=False):
+    """ASG Viterbi decode of a batch, device-resident: the best path of emissions_b o transitions (the reference's
+    viterbiPath over the full-connect product of examples/asg.cpp:36-47) for every utterance -- one sweep of the padded
+    batch and one launch whatever the lengths, nothing copied back.
+    emissions: float32 CUDA tensor [B, T, N] (any scores), read in place and left untouched, pad rows included (what
+    they hold, NaN included, never changes a bit of any output); transitions: [N, N] with transitions[i, j] the score
+    of label j followed by label i; start: [N] scores of the first label (zeros when omitted); input_lengths:
+    per-utterance frame counts (0 .. T) or None.
+    Returns (labels int32 [B, T], scores float32 [B]) on emissions.device -- the label of every frame, -1 from the
+    utterance's length on, and the path score -- and with collapse=True also (collapsed int32 [B, T], lengths int32
+    [B]): the labels with runs of equal consecutive frames merged, -1 from the length on.  An utterance without frames
+    has rows of -1, score -inf and length 0.  Of exactly equal candidates the smallest label wins, as in the reference.
+    Runs on the caller's stream; no autograd.
+    The launch takes 7 <= N <= 1023; any other N goes through viterbi_path and one upload, where input_lengths raises
+    the engine's error."""
+    if emissions.dim() != 3 or emissions.dtype != torch.float32:
+        raise ValueError("asg_decode: emissions must be a float32 tensor [B, T, N]")
+    B, T, N = emissions.shape
+    if tuple(transitions.shape) != (N, N):
+        raise ValueError(f"asg_decode: transitions must be [{N}, {N}]")
+    if start is not None and tuple(start.shape) != (N,):
+        raise ValueError(f"asg_decode: start must be [{N}]")
+    frames = None if input_lengths is None else _frame_counts("asg_decode", input_lengths, B, T, 0)
+    if not emissions.is_cuda:
+        raise RuntimeError("asg_decode: emissions must be a CUDA tensor (the decode runs on the device)")
+    if start is None:
+        start = torch.zeros(N, dtype=torch.float32, device=emissions.device)
+    x = emissions.detach().contiguous()
+    # arc order of gtn::criteria::asgTransitions: N start arcs, then arc N + i*N + j = j -> i
+    w = torch.cat([start.detach().reshape(-1), transitions.detach().reshape(-1)]).to(torch.float32).contiguous()
+    stream = torch.cuda.current_stream(x.device)
+    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
+    if not stream.cuda_stream:
+        stream.synchronize()  # engine runs on its own stream
+    labels = torch.empty(B, T, dtype=torch.int32, device=x.device)
+    scores = torch.empty(B, dtype=torch.float32, device=x.device)
+    collapsed = torch.empty(B, T, dtype=torch.int32, device=x.device) if collapse else None
+    lengths = torch.empty(B, dtype=torch.int32, device=x.device) if collapse else None
+    lib = _native()
+    if lib:
+        if not hasattr(lib, "gtn_asg_decode_n"):
+            raise RuntimeError("asg_decode needs gtn_asg_decode_n in gtn_amd/lib/libgtn_criteria.so "
+                               "(run __graft_entry__.build())")
+        rc = lib.gtn_asg_decode_n(x.data_ptr(), B, T, N, w.data_ptr(),
+                                  frames.ctypes.data if frames is not None else None, labels.data_ptr(),
+                                  scores.data_ptr(), collapsed.data_ptr() if collapse else None,
+                                  lengths.data_ptr() if collapse else None)
+        if rc != 0:
+            raise RuntimeError(lib.gtn_criteria_last_error().decode())
+    else:
+        trans = _asg_transitions_graph(N, w)
+        ems = gtn.Batch.linear(B, T, N, x, calc_grad=False, borrow=True)
+        ems.viterbi_decode(trans, labels, scores, frames, collapsed, lengths, row_stride=T)
+    if not stream.cuda_stream:
+        gtn.synchronize()
+    return (labels, scores, collapsed, lengths) if collapse else (labels, scores)

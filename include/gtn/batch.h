@@ -156,6 +156,21 @@ inline void viterbiAlign(const Batch& product, int* labelsDevice, int64_t rowStr
                          float* scoresDevice = nullptr, const int* frames = nullptr) {
   detail::check(gtnx_batch_viterbi_align(product.handle(), frames, labelsDevice, rowStride, tokensDevice, scoresDevice));
 }
+/** viterbiPath(compose(ems[b], transitions)) of the whole batch against ONE shared graph, results left on the device:
+ *  row b of labelsDevice (int32, rowStride >= M entries apart) gets the label of every frame t < T_b and -1 from T_b
+ *  to the row's width M; scoresDevice the path scores; collapsedDevice (rows like labelsDevice) the labels with runs of
+ *  equal consecutive frames merged, then -1; lengthsDevice (needs collapsedDevice) how many; frames (host, [n]): T_b,
+ *  null = the rows the batch carries.  No accepting path (T_b = 0 included): entries -1, score -inf, length 0.  A
+ *  Batch::linear against an asgTransitions-shaped graph of 8 .. 1024 nodes: ONE sweep of the padded batch and one
+ *  launch, no copy back, no wait; the pad rows never change a bit of any output; exact ties: first accept node, then
+ *  the smallest source node.  Other graphs / batches go through viterbiPath and one upload (frames must be null
+ *  there) -- gtnx_batch_viterbi_decode */
+inline void viterbiDecode(const Batch& ems, const Graph& transitions, int* labelsDevice, int64_t rowStride,
+                          float* scoresDevice = nullptr, const int* frames = nullptr, int* collapsedDevice = nullptr,
+                          int* lengthsDevice = nullptr) {
+  detail::check(gtnx_batch_viterbi_decode(ems.handle(), transitions.handle(), frames, labelsDevice, rowStride,
+                                          scoresDevice, collapsedDevice, lengthsDevice));
+}
 inline void backward(const Batch& a, bool retainGraph = false) { detail::check(gtnx_batch_backward(a.handle(), retainGraph)); }
 } // namespace batched
 

@@ -312,6 +312,30 @@ gtnx_status_t gtnx_batch_viterbi_align(gtnx_batch_t a, const int* frames, void* 
                                        void* tokens_device, void* scores_device);
 /* utterances aligned so far (process-wide) by the launch / by the path-graph route */
 gtnx_status_t gtnx_batch_align_stats(int64_t* fast, int64_t* fallback);
+/* Decode of a whole batch against ONE shared graph with device-resident output: viterbiPath(ems_b o transitions)
+ * (shortest.cpp:190-272 over compose.cpp:377-522), the call an ASG model makes at inference, without the path graphs.
+ * Row b of labels_device (int32, row_stride entries apart, row_stride >= M) receives the label of every frame t < T_b of
+ * utterance b's best path and -1 from T_b to the row's width M; scores_device (float32 [n], or null) the path's score;
+ * collapsed_device (int32 rows like labels_device, or null) the labels with runs of equal consecutive frames merged,
+ * then -1 up to M; lengths_device (int32 [n], or null; needs collapsed_device) how many.  Without an accepting path
+ * (T_b = 0 included): every entry -1, score -inf, length 0.  frames (host, [n], or null): T_b; null means the rows the
+ * batch carries (gtnx_batch_linear_rows; M otherwise); a count outside 0 .. M or above those rows is
+ * GTNX_INVALID_ARGUMENT, raised before anything is launched.
+ * ems = gtnx_batch_linear / _rows and a transitions graph of 8 .. 1024 nodes whose every node's in-arcs share one
+ * label and whose nodes all reach all nodes with in-arcs, lists in node order (gtn::criteria::asgTransitions over 7 ..
+ * 1023 labels, arc-sorted or not): the whole padded batch is swept ONCE at full length M -- whatever the frame counts;
+ * the pad rows are read by that sweep, and what they hold (NaN included) never changes a bit of any output -- and ONE
+ * launch on the engine's stream walks every utterance back from its own row T_b: nothing is copied back, no graph is
+ * built and the call does not wait for the device.  Exact ties: the first accept node in the graph's accept order,
+ * then the arc from the smallest source node -- the reference's choice on the built lattice of such a graph.
+ * Any other graph or batch (fewer than 7 or more than 1023 labels, another shape, GTNX_NO_DENSE=1) goes through
+ * gtnx_viterbi_path_n over the composed elements, the labels read and collapsed on the host, one upload; frames must be
+ * null there (GTNX_INVALID_ARGUMENT otherwise).  Output pointers must be memory the engine's current device may write. */
+gtnx_status_t gtnx_batch_viterbi_decode(gtnx_batch_t ems, gtnx_graph_t transitions, const int* frames,
+                                        void* labels_device, int64_t row_stride, void* scores_device,
+                                        void* collapsed_device, void* lengths_device);
+/* utterances decoded so far (process-wide) by the launch / by the path-graph route */
+gtnx_status_t gtnx_batch_decode_stats(int64_t* fast, int64_t* fallback);
 gtnx_status_t gtnx_batch_backward(gtnx_batch_t a, int retain_graph);                  /* autograd.cpp:17-67 */
 gtnx_status_t gtnx_batch_items(gtnx_batch_t a, float* out);                           /* graph.h:143, n floats */
 gtnx_status_t gtnx_batch_items_device(gtnx_batch_t a, void* device_out);
