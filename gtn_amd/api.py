@@ -793,6 +793,45 @@ def make_api(lib):
                                                 _as_dev_ptr(collapsed_out) if collapsed_out is not None else None,
                                                 _as_dev_ptr(lengths_out) if lengths_out is not None else None))
 
+        def linear_decode(self, labels_out, scores_out=None, frames=None, blank=-1, collapsed_out=None,
+                          starts_out=None, lengths_out=None, row_stride=None):
+            """viterbi_path(element b) of a batch of chains plus the CTC collapse, results left on the device
+            (gtnx_batch_linear_decode): row b of `labels_out` (int32 CUDA tensor [B, >= M], or a device address with
+            `row_stride` entries between rows) gets the first label holding the maximum of every frame t < T_b (the
+            smallest label among equal maxima; NaN and -inf are never taken) and -1 from T_b to the row's width M;
+            `scores_out` (float32 [B]) the path scores, the float32 sum of the maxima in frame order; `collapsed_out`
+            (int32, rows like labels_out) the labels with repeats merged and `blank` dropped (blank < 0: nothing is
+            dropped), then -1; `starts_out` (rows alike, needs collapsed_out) the first frame of each; `lengths_out`
+            (int32 [B], needs collapsed_out) how many; `frames`: T_b per element (0 .. M, at most the rows the batch
+            carries; None: those rows).  A frame with nothing above -inf leaves no path: entries -1, score -inf,
+            length 0; T_b = 0 likewise (a chain without frames has no accepting node).
+            A Batch.linear is two launches with no copy back and no wait; rows from T_b on are never read.  Other
+            batches go through viterbi_path and one upload (`frames` is an error there)."""
+            n = len(self)
+            stride = row_stride
+            for t in (labels_out, collapsed_out, starts_out):
+                if t is None or not hasattr(t, "data_ptr"):
+                    continue
+                if t.element_size() != 4 or t.dim() != 2 or t.shape[0] < n or (t.shape[1] > 1 and t.stride(1) != 1):
+                    raise ValueError("linear_decode: outputs must be int32 tensors [B, M] with contiguous rows")
+                if stride is not None and t.stride(0) != stride:
+                    raise ValueError("linear_decode: labels_out, collapsed_out and starts_out must have the same "
+                                     "row stride")
+                stride = t.stride(0)
+            if stride is None:
+                raise ValueError("linear_decode: a device address needs row_stride")
+            if (lengths_out is not None or starts_out is not None) and collapsed_out is None:
+                raise ValueError("linear_decode: lengths_out and starts_out need collapsed_out")
+            fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32)
+            if fr is not None and fr.shape != (n,):
+                raise ValueError("linear_decode: one frame count per element")
+            check(lib.gtnx_batch_linear_decode(self._h, fr.ctypes.data if fr is not None else None, int(blank),
+                                               _as_dev_ptr(labels_out), int(stride),
+                                               _as_dev_ptr(scores_out) if scores_out is not None else None,
+                                               _as_dev_ptr(collapsed_out) if collapsed_out is not None else None,
+                                               _as_dev_ptr(starts_out) if starts_out is not None else None,
+                                               _as_dev_ptr(lengths_out) if lengths_out is not None else None))
+
     ns.Batch = Batch
 
     def _batch_fn(cfn, *args):
@@ -922,9 +961,17 @@ def make_api(lib):
         check(lib.gtnx_batch_decode_stats(C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def debug_linear_decode_stats():
+        """(fast, fallback): utterances Batch.linear_decode has decoded so far by its two launches / through the path
+        graphs of viterbi_path (include/gtn_amd.h: gtnx_batch_linear_decode_stats)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(lib.gtnx_batch_linear_decode_stats(C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     if hasattr(lib, "gtnx_batch_align_stats"):
         ns.debug_align_stats = debug_align_stats
     ns.debug_decode_stats = debug_decode_stats
+    ns.debug_linear_decode_stats = debug_linear_decode_stats
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties
 

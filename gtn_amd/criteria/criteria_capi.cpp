@@ -63,6 +63,23 @@ extern "C" __attribute__((visibility("default"))) int gtn_ctc_align_n(const void
   }
 }
 
+// CTC best-path decode.  emissions: DEVICE float [B][T][C]; blank: the label the collapse drops (< 0: none); frames: host
+// int32 [B] or null; labels: DEVICE int32 [B][T]; scores: DEVICE float [B] or null; collapsed / starts: DEVICE int32
+// [B][T] or null; lengths: DEVICE int32 [B] or null (starts and lengths need collapsed).  Returns 0, or -1 with the
+// message in gtn_criteria_last_error().
+extern "C" __attribute__((visibility("default"))) int gtn_ctc_decode_n(const void* emissions, int B, int T, int C,
+                                                                       int blank, const int* frames, void* labels,
+                                                                       void* scores, void* collapsed, void* starts,
+                                                                       void* lengths) {
+  try {
+    gtn::criteria::ctcDecodeBatch(emissions, B, T, C, blank, frames, labels, scores, collapsed, starts, lengths);
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
 // The same, as benchmarks/ctc.cpp:150-165 runs it: target graphs with calcGrad = true, and THEIR gradients too.
 // target_grad: DEVICE float, utterance b's arc gradients (arc ids of benchmarks/ctc.cpp:40-58's addArc order) at
 // target_grad + target_grad_offsets[b]; grad must be non-null.

@@ -137,5 +137,31 @@ inline void ctcAlignBatch(
   batched::viterbiAlign(comp, static_cast<int*>(labels), T, static_cast<int*>(tokens), static_cast<float*>(scores), frames);
 }
 
+/** CTC best-path decode of a batch, results on the device: per utterance viterbiPath(emissions_b) (shortest.cpp:190-272
+ *  on linearGraph(T, C)) as the label of every frame (`labelsDev`, device int32 [B][T]: the smallest label among equal
+ *  maxima), the path score (`scoresDev`, device float [B] or null: the float32 sum of the row maxima in frame order),
+ *  the labels with repeats merged and `blank` dropped (`collapsedDev`, device int32 [B][T] or null; blank < 0 drops
+ *  nothing), the first frame of each (`startsDev`, device int32 [B][T] or null; needs collapsedDev) and how many
+ *  (`lengthsDev`, device int32 [B] or null; needs collapsedDev).  `frames`: host [B] or null -- how many of the T rows of
+ *  each utterance count (0 .. T); entries past them are -1, rows past them are never read, and an utterance without
+ *  frames has no path.  No path (a frame with nothing above -inf, or no frames): entries -1, score -inf, length 0.
+ *  `emissions`: device [B][T][C], read in place.  Two launches; nothing is copied back. */
+inline void ctcDecodeBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int C,
+    int blank,
+    const int* frames,
+    void* labelsDev,
+    void* scoresDev,
+    void* collapsedDev,
+    void* startsDev,
+    void* lengthsDev) {
+  Batch ems = Batch::linear(B, T, C, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  batched::linearDecode(ems, static_cast<int*>(labelsDev), T, static_cast<float*>(scoresDev), frames, blank,
+                        static_cast<int*>(collapsedDev), static_cast<int*>(startsDev), static_cast<int*>(lengthsDev));
+}
+
 } // namespace criteria
 } // namespace gtn

@@ -1301,6 +1301,148 @@ void batch_viterbi_decode(const BatchP& ems, Graph& transitions, const int* fram
   g_decode_fast.fetch_add(n);
 }
 
+// ---- best path of the chains themselves plus the CTC collapse, device-resident output (linear_decode.hip) ----
+namespace {
+std::atomic<int64_t> g_linear_decode_fast{0}, g_linear_decode_fallback{0};
+
+// every other batch: the path graphs of batch_viterbi_path, labels read and collapsed on the host, one upload
+void linear_decode_fallback(const BatchP& ems, int blank, int* labels_dev, int64_t row_stride,
+                            float* scores_dev, int* collapsed_dev, int* starts_dev, int* lengths_dev) {
+  GTNX_HOST_T("batch.linear_decode.fallback");
+  Runtime& rt = Runtime::get();
+  const int n = ems->n;
+  BatchP paths = batch_viterbi_path(ems);
+  int64_t width = ems->kind == Batch::LINEAR ? ems->M : 0;
+  for (int b = 0; b < n; ++b) width = std::max<int64_t>(width, paths->graphs[size_t(b)].num_arcs());
+  if (width > row_stride) throw_invalid("[gtnx_batch_linear_decode] row_stride is shorter than the longest path");
+  const size_t cells = size_t(n) * size_t(width ? width : 1);
+  PinnedMemP hl = rt.alloc_pinned(sizeof(int) * cells * 3);
+  PinnedMemP hs = rt.alloc_pinned((sizeof(float) + sizeof(int)) * size_t(n));
+  int* lab = hl->as<int>();
+  int* col = lab + cells;
+  int* sta = col + cells;
+  float* sc = hs->as<float>();
+  int* len_out = reinterpret_cast<int*>(sc + n);
+  std::fill(lab, lab + 3 * cells, -1);
+  for (int b = 0; b < n; ++b) {
+    Graph& g = paths->graphs[size_t(b)];
+    const int64_t len = g.num_arcs();
+    // (no path, zero frames included: the empty graph)
+    float score = g.num_nodes() > 0 ? 0.0f : -std::numeric_limits<float>::infinity();
+    int k = 0;
+    if (len > 0) {
+      g.s->ensure_host();
+      int* row = lab + size_t(b) * size_t(width);
+      int* crow = col + size_t(b) * size_t(width);
+      int* srow = sta + size_t(b) * size_t(width);
+      std::copy(g.s->il.begin(), g.s->il.begin() + len, row);
+      const float* w = g.weights_host(false);
+      for (int64_t t = 0; t < len; ++t) {
+        score += w[t];  // (in path order, as the recursion accumulates it)
+        if ((t == 0 || row[t] != row[t - 1]) && row[t] != blank) {
+          crow[k] = row[t];
+          srow[k++] = int(t);
+        }
+      }
+    }
+    sc[b] = score;
+    len_out[b] = k;
+  }
+  if (width > 0) {
+    int* src[3] = {lab, col, sta};
+    int* dst[3] = {labels_dev, collapsed_dev, starts_dev};
+    for (int i = 0; i < 3; ++i)
+      if (dst[i])
+        HIP_CHECK(hipMemcpy2DAsync(dst[i], sizeof(int) * size_t(row_stride), src[i], sizeof(int) * size_t(width),
+                                   sizeof(int) * size_t(width), size_t(n), hipMemcpyHostToDevice, rt.stream()));
+  }
+  if (scores_dev) rt.h2d_pinned(scores_dev, sc, sizeof(float) * size_t(n));
+  if (lengths_dev) rt.h2d_pinned(lengths_dev, len_out, sizeof(int) * size_t(n));
+  g_linear_decode_fallback.fetch_add(n);
+}
+}  // namespace
+
+void batch_linear_decode_stats(int64_t* fast, int64_t* fallback) {
+  if (fast) *fast = g_linear_decode_fast.load();
+  if (fallback) *fallback = g_linear_decode_fallback.load();
+}
+
+void batch_linear_decode(const BatchP& ems, const int* frames, int blank, int* labels_dev, int64_t row_stride,
+                         float* scores_dev, int* collapsed_dev, int* starts_dev, int* lengths_dev) {
+  GTNX_HOST_T("batch.linear_decode");
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) throw_invalid("[gtnx_batch_linear_decode] null batch");
+  if (!labels_dev) throw_invalid("[gtnx_batch_linear_decode] null labels pointer");
+  if (row_stride < 0) throw_invalid("[gtnx_batch_linear_decode] negative row stride");
+  if ((lengths_dev || starts_dev) && !collapsed_dev)
+    throw_invalid("[gtnx_batch_linear_decode] lengths and starts are those of the collapsed sequences: pass "
+                  "collapsed_device too");
+  const int n = ems->n;
+  const bool linear = ems->kind == Batch::LINEAR && !ems->leaf && ems->w_dev;
+  if (frames && !linear)
+    throw_invalid("[gtnx_batch_linear_decode] per-utterance frame counts need a native linear batch (this batch takes "
+                  "the path-graph route, which decodes the rows the elements carry: pass frames = null)");
+  if (frames)
+    for (int b = 0; b < n; ++b) {
+      if (frames[b] < 0 || frames[b] > ems->M) throw_invalid("[gtnx_batch_linear_decode] a frame count outside 0 .. M");
+      if (frames[b] > ems->rows_of(b))
+        throw_invalid("[gtnx_batch_linear_decode] a frame count beyond the rows the batch carries");
+    }
+  if (linear && n > 0 && row_stride < ems->M)
+    throw_invalid("[gtnx_batch_linear_decode] row_stride is shorter than the rows of the batch");
+  if (linear && blank >= ems->C) throw_invalid("[gtnx_batch_linear_decode] blank is not below the number of labels");
+  Runtime& rt = Runtime::get();
+  if (n <= 0) return;
+  // a kernel of this device writes the results: memory of another GPU of the process is refused, not written
+  if (!ptr_local_to(labels_dev, rt.device()) || (scores_dev && !ptr_local_to(scores_dev, rt.device())) ||
+      (collapsed_dev && !ptr_local_to(collapsed_dev, rt.device())) ||
+      (starts_dev && !ptr_local_to(starts_dev, rt.device())) ||
+      (lengths_dev && !ptr_local_to(lengths_dev, rt.device())))
+    throw_invalid("[gtnx_batch_linear_decode] an output pointer is not memory of the engine's current device");
+  Batch& x = *ems;
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  if (!linear) {
+    linear_decode_fallback(ems, blank, labels_dev, row_stride, scores_dev, collapsed_dev, starts_dev,
+                           lengths_dev);
+    return;
+  }
+  std::vector<int> fr(static_cast<size_t>(n));
+  // algorithmic bytes: every emission of the rows that count once, label and maximum out / back in, the pad of the
+  // label rows, the collapsed rows
+  double row_bytes = 0, col_bytes = 0;
+  for (int b = 0; b < n; ++b) {
+    const int t = fr[size_t(b)] = frames ? frames[b] : x.rows_of(b);
+    row_bytes += 4.0 * x.C * t + 8.0 * t;
+    col_bytes += 8.0 * t + 4.0 * (x.M - t) + (collapsed_dev ? 8.0 * x.M : 0.0);
+  }
+  DevMemP d_frames = upload_vec(fr);
+  DevMemP rowmax = rt.alloc(sizeof(float) * std::max<size_t>(size_t(n) * size_t(x.M), 1));
+  LinearDecodeArgs a{};
+  a.em = x.w_dev;
+  a.frames = d_frames->as<int>();
+  a.labels = labels_dev;
+  a.rowmax = rowmax->as<float>();
+  a.scores = scores_dev;
+  a.collapsed = collapsed_dev;
+  a.starts = starts_dev;
+  a.lengths = lengths_dev;
+  a.row_stride = row_stride;
+  a.n = n;
+  a.M = x.M;
+  a.C = x.C;
+  a.blank = blank;
+  {
+    GTNX_PROF("linear_decode_rows", row_bytes);
+    launch_linear_decode(a, 0, rt.stream());
+  }
+  {
+    GTNX_PROF("linear_decode_collapse", col_bytes);
+    launch_linear_decode(a, 1, rt.stream());
+  }
+  // (the scratch and the table go back to the stream-ordered pool behind the launches)
+  g_linear_decode_fast.fetch_add(n);
+}
+
 
 namespace {
 // a GRAPHS batch of one-arc graphs as a native SCALAR batch (values gathered; backward continues on the graphs' tape)

@@ -147,6 +147,21 @@ void batch_align_stats(int64_t* fast, int64_t* fallback);  // utterances aligned
 void batch_viterbi_decode(const BatchP& ems, Graph& transitions, const int* frames, int* labels_dev, int64_t row_stride,
                           float* scores_dev, int* collapsed_dev, int* lengths_dev);
 void batch_decode_stats(int64_t* fast, int64_t* fallback);  // utterances decoded by the launch / by the path graphs
+// viterbiPath(ems_b) of a whole batch of chains plus the CTC collapse, results on the device (the decode a CTC model
+// runs at inference).  labels_dev[b * row_stride + t] = the first label holding the maximum of frame t for t < T_b
+// (shortest.cpp:190-272: `>` from -inf, so the smallest label among equal maxima; NaN and -inf are never taken), -1
+// from T_b to the row's width M; scores_dev[b] (or null) = ((0 + m_0) + m_1) + ... in float32 in frame order;
+// collapsed_dev[b * row_stride + k] (or null) the labels with repeats merged and `blank` dropped (blank < 0: nothing is
+// dropped), starts_dev (or null; needs collapsed_dev) the first frame of each, both -1 from the length to M;
+// lengths_dev[b] (or null; needs collapsed_dev) how many.  A frame without an entry above -inf: no path -- every entry
+// of every row -1, score -inf, length 0; T_b = 0 likewise (creations.cpp:22: the start node does not accept).  frames (host, [n], or null): T_b,
+// null = rows_of(b); outside 0 .. M or above rows_of(b), row_stride < M, blank >= C: invalid argument, before a device
+// is asked for.  A native LINEAR batch: two launches of linear_decode.hip on the engine's stream, rows from T_b on are
+// never read, no download, no path graphs, no wait.  Everything else: batch_viterbi_path, labels read and collapsed
+// on the host by the same rules, one upload; frames must be null there.
+void batch_linear_decode(const BatchP& ems, const int* frames, int blank, int* labels_dev, int64_t row_stride,
+                         float* scores_dev, int* collapsed_dev, int* starts_dev, int* lengths_dev);
+void batch_linear_decode_stats(int64_t* fast, int64_t* fallback);  // utterances decoded by the launches / the path graphs
 // items_dev (optional): device memory of the CALLER's that the n result values are written into directly (borrowed: it
 // must outlive the result); a later batch_items_device to the same address copies nothing
 BatchP batch_scalar(ScalarKind k, const BatchP& a, const BatchP& b, void* items_dev = nullptr);

@@ -884,6 +884,18 @@ GTNX_API gtnx_status_t gtnx_batch_viterbi_decode(gtnx_batch_t ems, gtnx_graph_t 
 GTNX_API gtnx_status_t gtnx_batch_decode_stats(int64_t* fast, int64_t* fallback) {
   return guard([&] { batch_decode_stats(fast, fallback); });
 }
+GTNX_API gtnx_status_t gtnx_batch_linear_decode(gtnx_batch_t ems, const int* frames, int blank, void* labels_device,
+                                                int64_t row_stride, void* scores_device, void* collapsed_device,
+                                                void* starts_device, void* lengths_device) {
+  return guard([&] {
+    batch_linear_decode(BH(ems), frames, blank, static_cast<int*>(labels_device), row_stride,
+                        static_cast<float*>(scores_device), static_cast<int*>(collapsed_device),
+                        static_cast<int*>(starts_device), static_cast<int*>(lengths_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_linear_decode_stats(int64_t* fast, int64_t* fallback) {
+  return guard([&] { batch_linear_decode_stats(fast, fallback); });
+}
 GTNX_API gtnx_status_t gtnx_batch_backward(gtnx_batch_t a, int retain) {
   return guard([&] { batch_backward(BH(a), retain != 0); });
 }

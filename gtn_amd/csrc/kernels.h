@@ -781,6 +781,27 @@ struct PadFillArgs {
   int n, C;
 };
 void launch_pad_fill(const PadFillArgs& a, int64_t total_floats, hipStream_t st);
+// linear_decode.hip: viterbiPath of every chain of an [n][M][C] tensor at its own length frames[b] (device, 0 .. M),
+// then the CTC collapse, results on the device.  labels[b * row_stride + t] = the first label holding the maximum of
+// row t (-1 from frames[b] to M); scores[b] (or null) = ((0 + m_0) + m_1) + ... in frame order; collapsed[b *
+// row_stride + k] (or null) the labels with repeats merged and `blank` dropped (blank < 0: nothing dropped), starts
+// likewise (or null; needs collapsed) the first frame of each, both -1 from lengths[b] (or null) to M.  A row without
+// an entry above -inf, or frames[b] = 0: no path -- every entry of every row -1, score -inf, length 0.  rowmax: [n][M] floats of
+// scratch.  Nothing from row frames[b] on is read.  Two launches: which = 0 the rows (label and maximum of every
+// row), which = 1 one wave per utterance (score, collapse, the -1 entries).
+struct LinearDecodeArgs {
+  const GTNX_G float* em;
+  const GTNX_G int* frames;  // [n]
+  GTNX_G int* labels;
+  GTNX_G float* rowmax;      // [n][M]
+  GTNX_G float* scores;
+  GTNX_G int* collapsed;
+  GTNX_G int* starts;
+  GTNX_G int* lengths;
+  int64_t row_stride;
+  int n, M, C, blank;
+};
+void launch_linear_decode(const LinearDecodeArgs& a, int which, hipStream_t st);
 // materialise a KIND_LINEAR graph's arc arrays
 void launch_linear_materialize(int M, int C, int* src, int* dst, int* il, int* ol, hipStream_t st);
 

@@ -1,5 +1,5 @@
 """PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
-`asg_forced_align` and `asg_decode`.
+`asg_forced_align`, `asg_decode` and `ctc_decode`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -48,6 +48,10 @@ def _native():
                 lib.gtn_asg_decode_n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
                 lib.gtn_asg_decode_n.restype = C.c_int
+            if hasattr(lib, "gtn_ctc_decode_n"):
+                lib.gtn_ctc_decode_n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+                lib.gtn_ctc_decode_n.restype = C.c_int
             _NATIVE = lib
         else:
             _NATIVE = False
@@ -450,3 +454,54 @@ def asg_decode(emissions, transitions, start=None, input_lengths=None, collapse=
     if not stream.cuda_stream:
         gtn.synchronize()
     return (labels, scores, collapsed, lengths) if collapse else (labels, scores)
+
+
+def ctc_decode(log_probs, blank=0, input_lengths=None, collapse=True):
+    """CTC best-path (greedy) decode of a batch, device-resident: the reference's viterbiPath(emissions_b) for every
+    utterance of a padded batch, then the CTC collapse (merge repeats, drop blanks) -- two launches whatever the
+    lengths, nothing copied back.
+    log_probs: float32 CUDA tensor [B, T, C] (any scores), read in place and left untouched; rows past an utterance's
+    length are never read; blank: the label the collapse drops (negative: none, repeats are merged only);
+    input_lengths: per-utterance frame counts (0 .. T) or None.
+    Returns (labels int32 [B, T], scores float32 [B]) on log_probs.device -- the label of every frame, -1 from the
+    utterance's length on, and the path score, the float32 sum of the frame maxima in frame order -- and with
+    collapse=True also (tokens int32 [B, T], starts int32 [B, T], lengths int32 [B]): the collapsed labels, the first
+    frame of each, both -1 from the length on.  Of exactly equal maxima the smallest label wins, as in the reference;
+    NaN and -inf are never chosen, and a frame with nothing above -inf leaves the utterance without a path: rows of
+    -1, score -inf, length 0.  So does an utterance without frames (linearGraph(0, C) has no accepting node).
+    Runs on the caller's stream; no autograd."""
+    if log_probs.dim() != 3 or log_probs.dtype != torch.float32:
+        raise ValueError("ctc_decode: log_probs must be a float32 tensor [B, T, C]")
+    B, T, N = log_probs.shape
+    blank = int(blank)
+    if blank >= N:
+        raise ValueError(f"ctc_decode: blank must be below the {N} labels (negative: no blank)")
+    frames = None if input_lengths is None else _frame_counts("ctc_decode", input_lengths, B, T, 0)
+    if not log_probs.is_cuda:
+        raise RuntimeError("ctc_decode: log_probs must be a CUDA tensor (the decode runs on the device)")
+    x = log_probs.detach().contiguous()
+    stream = torch.cuda.current_stream(x.device)
+    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
+    if not stream.cuda_stream:
+        stream.synchronize()  # engine runs on its own stream
+    labels = torch.empty(B, T, dtype=torch.int32, device=x.device)
+    scores = torch.empty(B, dtype=torch.float32, device=x.device)
+    tokens = torch.empty(B, T, dtype=torch.int32, device=x.device) if collapse else None
+    starts = torch.empty(B, T, dtype=torch.int32, device=x.device) if collapse else None
+    lengths = torch.empty(B, dtype=torch.int32, device=x.device) if collapse else None
+    lib = _native()
+    if lib:
+        if not hasattr(lib, "gtn_ctc_decode_n"):
+            raise RuntimeError("ctc_decode needs gtn_ctc_decode_n in gtn_amd/lib/libgtn_criteria.so "
+                               "(run __graft_entry__.build())")
+        rc = lib.gtn_ctc_decode_n(x.data_ptr(), B, T, N, blank, frames.ctypes.data if frames is not None else None,
+                                  labels.data_ptr(), scores.data_ptr(), tokens.data_ptr() if collapse else None,
+                                  starts.data_ptr() if collapse else None, lengths.data_ptr() if collapse else None)
+        if rc != 0:
+            raise RuntimeError(lib.gtn_criteria_last_error().decode())
+    else:
+        ems = gtn.Batch.linear(B, T, N, x, calc_grad=False, borrow=True)
+        ems.linear_decode(labels, scores, frames, blank, tokens, starts, lengths, row_stride=T)
+    if not stream.cuda_stream:
+        gtn.synchronize()
+    return (labels, scores, tokens, starts, lengths) if collapse else (labels, scores)

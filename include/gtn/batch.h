@@ -171,6 +171,21 @@ inline void viterbiDecode(const Batch& ems, const Graph& transitions, int* label
   detail::check(gtnx_batch_viterbi_decode(ems.handle(), transitions.handle(), frames, labelsDevice, rowStride,
                                           scoresDevice, collapsedDevice, lengthsDevice));
 }
+/** viterbiPath(ems[b]) of a whole batch of chains plus the CTC collapse, results left on the device: row b of
+ *  labelsDevice (int32, rowStride >= M entries apart) gets the first label holding the maximum of every frame t < T_b
+ *  and -1 from T_b to the row's width M; scoresDevice the path scores (float32 sum in frame order); collapsedDevice
+ *  (rows like labelsDevice) the labels with repeats merged and `blank` dropped (blank < 0: nothing dropped), then -1;
+ *  startsDevice (rows alike; needs collapsedDevice) the first frame of each; lengthsDevice (needs collapsedDevice) how
+ *  many; frames (host, [n]): T_b, null = the rows the batch carries.  A frame with nothing above -inf: no path --
+ *  entries -1, score -inf, length 0; T_b = 0 likewise.  A Batch::linear: two launches, no copy
+ *  back, no wait, rows from T_b on are never read.  Other batches go through viterbiPath and one upload (frames must
+ *  be null there) -- gtnx_batch_linear_decode */
+inline void linearDecode(const Batch& ems, int* labelsDevice, int64_t rowStride, float* scoresDevice = nullptr,
+                         const int* frames = nullptr, int blank = -1, int* collapsedDevice = nullptr,
+                         int* startsDevice = nullptr, int* lengthsDevice = nullptr) {
+  detail::check(gtnx_batch_linear_decode(ems.handle(), frames, blank, labelsDevice, rowStride, scoresDevice,
+                                         collapsedDevice, startsDevice, lengthsDevice));
+}
 inline void backward(const Batch& a, bool retainGraph = false) { detail::check(gtnx_batch_backward(a.handle(), retainGraph)); }
 } // namespace batched
 

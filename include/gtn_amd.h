@@ -336,6 +336,32 @@ gtnx_status_t gtnx_batch_viterbi_decode(gtnx_batch_t ems, gtnx_graph_t transitio
                                         void* collapsed_device, void* lengths_device);
 /* utterances decoded so far (process-wide) by the launch / by the path-graph route */
 gtnx_status_t gtnx_batch_decode_stats(int64_t* fast, int64_t* fallback);
+/* Best-path decode of a whole batch of chains with device-resident output: viterbiPath(ems_b) (shortest.cpp:190-272
+ * on creations.cpp:20-33) followed by the CTC collapse (merge repeats, then drop blanks), the call a CTC model makes at
+ * inference, without the path graphs.  Row b of labels_device (int32, row_stride entries apart, row_stride >= M)
+ * receives for every frame t < T_b the FIRST label holding the row's maximum (the reference compares with `>` from
+ * -inf: the smallest label among equal maxima; NaN and -inf are never taken) and -1 from T_b to the row's width M;
+ * scores_device (float32 [n], or null) ((0 + m_0) + m_1) + ... + m_{T_b - 1} in float32 in frame order;
+ * collapsed_device (int32 rows like labels_device, or null) the labels with runs of equal consecutive frames merged and
+ * `blank` dropped (blank < 0: nothing is dropped -- viterbiPath of a linear graph, nothing CTC about it), then -1 up to
+ * M; starts_device (rows alike, or null; needs collapsed_device) the first frame of each kept label, then -1;
+ * lengths_device (int32 [n], or null; needs collapsed_device) how many.  A frame without an entry above -inf leaves
+ * no path: every entry of every row -1, score -inf, length 0.  T_b = 0 likewise: linearGraph(0, C) is a start node that
+ * does not accept (creations.cpp:22).
+ * frames (host, [n], or null): T_b; null means the rows the batch carries (gtnx_batch_linear_rows; M otherwise).
+ * GTNX_INVALID_ARGUMENT, raised before a device is asked for: a null batch or labels pointer, a negative stride,
+ * lengths or starts without collapsed, a count outside 0 .. M or above the rows the batch carries, row_stride < M,
+ * blank >= C.
+ * ems = gtnx_batch_linear / _rows: two launches on the engine's stream (every emission of the rows that count is read
+ * once; rows from T_b on are never read), nothing is copied back, no graph is built and the call does not wait for
+ * the device.  Any other batch goes through gtnx_batch_viterbi_path, the labels read and collapsed on the host by the
+ * same rules, one upload; frames must be null there (GTNX_INVALID_ARGUMENT otherwise).  Output pointers must be memory
+ * the engine's current device may write. */
+gtnx_status_t gtnx_batch_linear_decode(gtnx_batch_t ems, const int* frames, int blank, void* labels_device,
+                                       int64_t row_stride, void* scores_device, void* collapsed_device,
+                                       void* starts_device, void* lengths_device);
+/* utterances decoded so far (process-wide) by the launches / by the path-graph route */
+gtnx_status_t gtnx_batch_linear_decode_stats(int64_t* fast, int64_t* fallback);
 gtnx_status_t gtnx_batch_backward(gtnx_batch_t a, int retain_graph);                  /* autograd.cpp:17-67 */
 gtnx_status_t gtnx_batch_items(gtnx_batch_t a, float* out);                           /* graph.h:143, n floats */
 gtnx_status_t gtnx_batch_items_device(gtnx_batch_t a, void* device_out);
