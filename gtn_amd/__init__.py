@@ -67,6 +67,7 @@ debug_viterbi_ties = _api.debug_viterbi_ties
 debug_tie_ranks = _api.debug_tie_ranks
 debug_align_stats = getattr(_api, "debug_align_stats", None)  # (Batch.viterbi_align: which route aligned how many)
 debug_decode_stats = _api.debug_decode_stats  # (Batch.viterbi_decode: which route decoded how many)
+debug_full_connect_stats = _api.debug_full_connect_stats  # (forward_score of a padded batch o ASG transitions: which route)
 debug_linear_decode_stats = _api.debug_linear_decode_stats  # (Batch.linear_decode: which route decoded how many)
 
 

@@ -129,6 +129,7 @@ _SIGS = {
     "gtnx_batch_viterbi_decode": [c_graph, c_graph, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                   C.c_void_p],
     "gtnx_batch_decode_stats": [c_i64_p, c_i64_p],
+    "gtnx_batch_full_connect_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_linear_decode": [c_graph, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p],
     "gtnx_batch_linear_decode_stats": [c_i64_p, c_i64_p],

@@ -968,8 +968,17 @@ def make_api(lib):
         check(lib.gtnx_batch_linear_decode_stats(C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def debug_full_connect_stats():
+        """(fast, fallback): utterances whose ASG full-connect score forward_score(compose(Batch.linear(rows=...),
+        transitions)) came from the one launch of asg_full.hip / utterances of such a padded batch that took the composed
+        elements instead (include/gtn_amd.h: gtnx_batch_full_connect_stats)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(lib.gtnx_batch_full_connect_stats(C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     if hasattr(lib, "gtnx_batch_align_stats"):
         ns.debug_align_stats = debug_align_stats
+    ns.debug_full_connect_stats = debug_full_connect_stats
     ns.debug_decode_stats = debug_decode_stats
     ns.debug_linear_decode_stats = debug_linear_decode_stats
     ns.debug_symbolic_route = debug_symbolic_route

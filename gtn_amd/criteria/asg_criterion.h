@@ -9,6 +9,7 @@
 #pragma once
 
 #include <cstdint>
+#include <stdexcept>
 #include <vector>
 
 #include "gtn/gtn.h"
@@ -49,7 +50,13 @@ inline Graph asgForceAlign(const std::vector<int>& target) {
  *  criterion_test.cpp:289-305); `lossDev`: device [B]; `gradDev`: device [B][T][N] or null.
  *  Written on batch records (gtn/batch.h): the force-alignment acceptors composed with the transitions are
  *  built on the device from the label sequences (what took 137 of 154 ms per batch of 512 through the
- *  ordinary compose), the full-connect term runs through the per-graph functions on the batch's elements. */
+ *  ordinary compose), the full-connect term runs through the per-graph functions on the batch's elements.
+ *  `frames` (host [B], or null): a padded batch -- utterance b has frames[b] <= T frames, its loss is that of
+ *  emissions_b[:frames[b]], rows past them are never read and their gradient is 0.  With frame counts and N <= 128
+ *  the full-connect term is one launch that walks every utterance's own rows (gtnx_batch_full_connect_stats); larger
+ *  alphabets compose the elements, one group of launches per distinct length.  An utterance with fewer frames than
+ *  labels has no alignment: its loss is +inf, its gradient rows hold the full-connect term's posteriors alone (the
+ *  force-align term of a score of -inf is 0), and the transitions gradient likewise receives only that term of it. */
 inline void asgLossBatch(
     const void* emissions,
     const int* labels,
@@ -59,8 +66,12 @@ inline void asgLossBatch(
     int N,
     Graph& transitions,
     void* lossDev,
-    void* gradDev) {
-  Batch ems = Batch::linear(B, T, N, emissions, gradDev != nullptr, /*borrow=*/true);
+    void* gradDev,
+    const int* frames = nullptr) {
+  if (frames)  // (before anything is launched)
+    for (int b = 0; b < B; ++b)
+      if (frames[b] < 1 || frames[b] > T) throw std::invalid_argument("[asgLossBatch] a frame count outside 1 .. T");
+  Batch ems = Batch::linear(B, T, N, emissions, gradDev != nullptr, /*borrow=*/true, frames);
   std::vector<int64_t> off(B);
   for (int b = 0; b < B; ++b) off[b] = (int64_t)b * T * N;
   Batch trans(std::vector<Graph>{transitions});
@@ -81,13 +92,14 @@ inline void asgLossBatch(
     int N,
     Graph& transitions,
     void* lossDev,
-    void* gradDev) {
+    void* gradDev,
+    const int* frames = nullptr) {
   std::vector<int> flat, len;
   for (auto& t : targets) {
     flat.insert(flat.end(), t.begin(), t.end());
     len.push_back((int)t.size());
   }
-  asgLossBatch(emissions, flat.data(), len.data(), (int)targets.size(), T, N, transitions, lossDev, gradDev);
+  asgLossBatch(emissions, flat.data(), len.data(), (int)targets.size(), T, N, transitions, lossDev, gradDev, frames);
 }
 
 /** ASG forced alignment of a batch, results on the device: per utterance the best path of

@@ -101,11 +101,13 @@ extern "C" __attribute__((visibility("default"))) int gtn_ctc_loss_target_grads_
 // host int32 (concatenated / [B]); trans_w: DEVICE float [N + N*N] in the arc order of
 // gtn::criteria::asgTransitions BEFORE its arcSort (arc i: <s> -> i; arc N + i*N + j: j -> i);
 // loss: DEVICE float [B]; grad_em: DEVICE [B][T][N] or null; grad_trans: DEVICE [N + N*N] or null.
-extern "C" __attribute__((visibility("default"))) int gtn_asg_loss_n(const void* emissions, const int* targets,
-                                                                     const int* lengths, int B, int T, int N,
-                                                                     const void* trans_w, void* loss, void* grad_em,
-                                                                     void* grad_trans) {
+namespace {
+int asg_loss_impl(const void* emissions, const int* targets, const int* lengths, int B, int T, int N, const void* trans_w,
+                  const int* frames, void* loss, void* grad_em, void* grad_trans) {
   try {
+    if (frames)  // (before the weights are handed to the engine: no device is asked for an invalid call)
+      for (int b = 0; b < B; ++b)
+        if (frames[b] < 1 || frames[b] > T) throw std::invalid_argument("[gtn_asg_loss_frames_n] a frame count outside 1 .. T");
     // the transitions STRUCTURE is kept across calls (a trainer only changes the weights)
     static std::mutex mu;
     static auto* cache = new std::map<int, gtn::Graph>();  // never destroyed: outlives the engine's teardown
@@ -116,7 +118,7 @@ extern "C" __attribute__((visibility("default"))) int gtn_asg_loss_n(const void*
     trans.setCalcGrad(grad_trans != nullptr);
     trans.zeroGrad();
     trans.setWeightsDevice(trans_w);  // arc ids are creation order: arcSort permutes lists, not ids
-    gtn::criteria::asgLossBatch(emissions, targets, lengths, B, T, N, trans, loss, grad_em);
+    gtn::criteria::asgLossBatch(emissions, targets, lengths, B, T, N, trans, loss, grad_em, frames);
     if (grad_trans) {
       gtnx_graph_t h = trans.handle();
       int64_t off = 0;
@@ -127,6 +129,28 @@ extern "C" __attribute__((visibility("default"))) int gtn_asg_loss_n(const void*
     g_err = e.what();
     return -1;
   }
+}
+}  // namespace
+
+extern "C" __attribute__((visibility("default"))) int gtn_asg_loss_n(const void* emissions, const int* targets,
+                                                                     const int* lengths, int B, int T, int N,
+                                                                     const void* trans_w, void* loss, void* grad_em,
+                                                                     void* grad_trans) {
+  return asg_loss_impl(emissions, targets, lengths, B, T, N, trans_w, nullptr, loss, grad_em, grad_trans);
+}
+
+// The same over a PADDED batch: frames: host int32 [B], utterance b's frame count (1 .. T) -- its loss is that of
+// emissions[b][:frames[b]], the pad rows are never read and rows [frames[b], T) of grad_em are 0.
+extern "C" __attribute__((visibility("default"))) int gtn_asg_loss_frames_n(const void* emissions, const int* targets,
+                                                                            const int* lengths, int B, int T, int N,
+                                                                            const void* trans_w, const int* frames,
+                                                                            void* loss, void* grad_em,
+                                                                            void* grad_trans) {
+  if (!frames) {
+    g_err = "[gtn_asg_loss_frames_n] null frame counts";
+    return -1;
+  }
+  return asg_loss_impl(emissions, targets, lengths, B, T, N, trans_w, frames, loss, grad_em, grad_trans);
 }
 
 // ASG forced alignment.  emissions / targets / lengths / trans_w as for gtn_asg_loss_n; frames: host int32 [B] or null;

@@ -5,6 +5,8 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <unordered_map>
 #include <unordered_set>
@@ -281,6 +283,57 @@ struct BFalOp : BatchOp {
     DevMemP dt = upload_vec(tab);
     launch_asg_fal_scatter(out.g_dev, out.rec_mem->as<int>(), dt->as<int64_t>(), out.n, longest, gm->as<float>(), rt.stream());
     tr.add_grad_device(gm, gm->as<float>(), /*adopt=*/true);  // (accumulates when the graph holds a gradient already)
+  }
+};
+
+// forwardScore of a padded batch against ONE asgTransitions graph (Batch::full; asg_full.hip): one launch writes the
+// emission gradient's rows < rows[b], a second adds the utterances' shares of the transitions gradient in utterance
+// order, and the sum goes into the transitions graph the way BFalOp's does
+std::atomic<int64_t> g_full_fast{0}, g_full_fallback{0};
+struct BFullOp : BatchOp {  // inputs[0]: the PRODUCT
+  AsgFullArgs args{};  // as launched forward
+  DevMemP arena;       // scores [n] | scores in float64 [n] | per-step scales [n][M] | scaled alpha rows [n][M][N]
+  DevMemP rows_mem;
+  DevMemP w_mem;       // the transitions weights the forward launch read
+  DevMemP through_acc;  // as BFsBandOp's
+  void backward(Batch& out) override {
+    Batch& prod = *inputs[0];
+    Batch& ch = *prod.chain;
+    Graph& tr = prod.fixed->graphs[0];
+    Runtime& rt = Runtime::get();
+    const float* delta = out.g_dev;
+    if (through_acc || t_batch_retain) {
+      const size_t n = size_t(prod.n);
+      if (!through_acc) through_acc = rt.alloc_zero(sizeof(float) * (n ? n : 1));
+      launch_vec_axpby(through_acc->as<float>(), out.g_dev, nullptr, n, 1.0f, 0.0f, /*accumulate=*/1, rt.stream());
+      delta = through_acc->as<float>();
+    }
+    const bool want_tr = tr.calc_grad();
+    if (!ch.calc_grad && !want_tr) return;
+    GradTarget ge;
+    if (ch.calc_grad) ge = grad_target(ch, false);  // rows < rows[b] are written by the kernel, the rest by pad_fill
+    AsgFullArgs a = args;
+    a.delta = delta;
+    a.grad_em = ge.ptr;
+    const size_t A = size_t(a.N) + size_t(a.N) * size_t(a.N);
+    DevMemP part;
+    if (want_tr) {
+      part = rt.alloc(sizeof(float) * A * size_t(a.n));
+      a.partial = part->as<float>();
+    }
+    {
+      GTNX_PROF("asg_full_backward", 4.0 * double(a.n) * a.M * a.N * (ge.ptr ? 3 : 2) + (want_tr ? 4.0 * double(A) * a.n : 0.0));
+      launch_asg_full_backward(a, rt.stream());
+    }
+    if (ch.calc_grad) add_scratch(ch, ge);
+    if (want_tr) {
+      DevMemP gm = rt.alloc(sizeof(float) * A);
+      {
+        GTNX_PROF("asg_full_reduce", 4.0 * double(A) * (a.n + 1));
+        launch_asg_full_reduce(part->as<float>(), a.n, a.N, gm->as<float>(), rt.stream());
+      }
+      tr.add_grad_device(gm, gm->as<float>(), /*adopt=*/true);  // (accumulates when the graph holds a gradient already)
+    }
   }
 };
 
@@ -759,7 +812,9 @@ void batch_materialise(Batch& x) {
       batch_materialise(*x.fixed);
       batch_materialise(*x.chain);
       std::unique_ptr<CompMode> symbolic;
-      if (!x.wide) symbolic.reset(new CompMode);  // (a wide product: what batch_compose's per-graph branch would have made)
+      // (a wide or full-connect product: what batch_compose's per-graph branch would have made)
+      if (!x.wide && !x.full) symbolic.reset(new CompMode);
+      if (x.full) g_full_fallback.fetch_add(x.n);
       gs = x.chain_first ? op_compose(x.chain->graphs, x.fixed->graphs, x.intersect)
                          : op_compose(x.fixed->graphs, x.chain->graphs, x.intersect);
       break;
@@ -818,7 +873,68 @@ Graph batch_get(const BatchP& x, int i) {
 }
 
 // ---- functions -------------------------------------------------------------------------------
+namespace {
+// exactly gtn::criteria::asgTransitions(N) in arc-id order (examples/asg.cpp:36-47): node 0 starts, nodes 1 .. N accept,
+// arc i: 0 -> i + 1, arc N + i * N + j: j + 1 -> i + 1, both labels i -- what asg_full.hip takes the weights to mean
+bool asg_transitions_layout(Graph& g, int N) {
+  if (!g.s || g.s->lazy || g.s->deferred || g.s->kind != KIND_EXPLICIT || N < 1) return false;
+  if (g.num_nodes() != int64_t(N) + 1 || g.num_arcs() != int64_t(N) * (N + 1)) return false;
+  Structure& s = *g.s;
+  s.ensure_host();
+  const size_t A = size_t(N) * size_t(N + 1);
+  if (s.src.size() != A || s.dst.size() != A || s.il.size() != A || s.ol.size() != A || s.nflags.size() != size_t(N) + 1)
+    return false;
+  if (s.nflags[0] != NF_START) return false;
+  for (int i = 0; i < N; ++i) {
+    if (s.nflags[size_t(i) + 1] != NF_ACCEPT) return false;
+    if (s.src[size_t(i)] != 0 || s.dst[size_t(i)] != i + 1 || s.il[size_t(i)] != i || s.ol[size_t(i)] != i) return false;
+    for (int j = 0; j < N; ++j) {
+      const size_t k = size_t(N) + size_t(i) * size_t(N) + size_t(j);
+      if (s.src[k] != j + 1 || s.dst[k] != i + 1 || s.il[k] != i || s.ol[k] != i) return false;
+    }
+  }
+  return true;
+}
+}  // namespace
+
+void batch_full_connect_stats(int64_t* fast, int64_t* fallback) {
+  if (fast) *fast = g_full_fast.load();
+  if (fallback) *fallback = g_full_fallback.load();
+}
+
 BatchP batch_compose(const BatchP& a, const BatchP& b, bool intersect) {
+  // a padded LINEAR batch against ONE asgTransitions graph over the same alphabet stays symbolic for forwardScore's
+  // launch (Batch::full, asg_full.hip); without row counts only under GTNX_FULL_CONNECT=1 (the two routes on the same work)
+  {
+    const bool a_lin = native(*a, Batch::LINEAR) && b->kind == Batch::GRAPHS && !b->fal && b->n == 1 && b->graphs.size() == 1;
+    const bool b_lin = native(*b, Batch::LINEAR) && a->kind == Batch::GRAPHS && !a->fal && a->n == 1 && a->graphs.size() == 1;
+    if (a_lin || b_lin) {
+      const BatchP& lin = a_lin ? a : b;
+      const BatchP& one = a_lin ? b : a;
+      static const bool all = [] {
+        const char* e = std::getenv("GTNX_FULL_CONNECT");
+        return e && *e && std::strcmp(e, "0") != 0;
+      }();
+      if (!lin->leaf && !lin->materialised && lin->n > 0 && lin->M >= 1 && lin->w_dev && (!lin->rows.empty() || all) &&
+          asg_transitions_layout(one->graphs[0], lin->C)) {
+        if (lin->C <= asg_full_max_labels()) {
+          struct Op : BatchOp {
+            void backward(Batch&) override {}  // a symbolic product has no gradient of its own
+          };
+          auto op = std::make_shared<Op>();
+          op->inputs = {a, b};
+          BatchP r = result(Batch::PRODUCT, lin->n, op);
+          r->fixed = one;
+          r->chain = lin;
+          r->chain_first = a_lin;
+          r->intersect = intersect;
+          r->full = true;
+          return r;
+        }
+        g_full_fallback.fetch_add(lin->n);  // (the per-length groups of the dense regime: correct, one chain of launches each)
+      }
+    }
+  }
   const Batch *fx = nullptr, *ch = nullptr;
   bool chain_first = false;
   if (native(*a, Batch::CTC_TARGETS) && native(*b, Batch::LINEAR)) fx = a.get(), ch = b.get();
@@ -849,7 +965,51 @@ BatchP batch_compose(const BatchP& a, const BatchP& b, bool intersect) {
 BatchP batch_shortest_distance(const BatchP& x, bool tropical) {
   GTNX_HOST_T("batch.shortest_distance");
   Runtime& rt = Runtime::get();
-  if (!tropical && native(*x, Batch::PRODUCT) && !x->materialised && !x->wide) {
+  if (!tropical && native(*x, Batch::PRODUCT) && !x->materialised && x->full) {
+    Batch& ch = *x->chain;
+    Graph& tr = x->fixed->graphs[0];
+    if (ch.w_pend) ch.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+    std::vector<Weights*> ws{tr.w.get()};
+    ensure_weights_device_batch(ws);
+    const int n = x->n, M = ch.M, N = ch.C;
+    const bool keep = x->calc_grad;  // (nothing is stored for a gradient nobody can ask for)
+    auto op = std::make_shared<BFullOp>();
+    op->inputs = {x};
+    size_t bytes = align_up(4 * size_t(n), 256);
+    const size_t o_zd = bytes;
+    bytes = align_up(bytes + 8 * size_t(n), 256);
+    const size_t o_L = bytes;
+    if (keep) bytes = align_up(bytes + 8 * size_t(n) * size_t(M), 256);
+    const size_t o_la = bytes;
+    if (keep) bytes += 4 * size_t(n) * size_t(M) * size_t(N);
+    op->arena = rt.alloc(bytes);
+    if (!ch.rows.empty()) op->rows_mem = upload_vec(ch.rows);
+    op->w_mem = tr.w->dev_mem;
+    AsgFullArgs& a = op->args;
+    a.em = ch.w_dev;
+    a.rows = op->rows_mem ? op->rows_mem->as<int>() : nullptr;
+    a.w = tr.w->dev;
+    a.score = op->arena->as<float>();
+    a.zd = op->arena->as<double>(o_zd);
+    a.L = keep ? op->arena->as<double>(o_L) : nullptr;
+    a.la = keep ? op->arena->as<float>(o_la) : nullptr;
+    a.n = n;
+    a.M = M;
+    a.N = N;
+    int64_t frames = 0;
+    for (int b = 0; b < n; ++b) frames += ch.rows_of(b);
+    {
+      GTNX_PROF("asg_full_forward", 4.0 * double(frames) * N * (keep ? 2 : 1));
+      launch_asg_full_forward(a, rt.stream());
+    }
+    g_full_fast.fetch_add(n);
+    DevMemP arena = op->arena;
+    BatchP r = result(Batch::SCALAR, n, op);
+    r->v_mem = arena;
+    r->v_dev = arena->as<float>();
+    return r;
+  }
+  if (!tropical && native(*x, Batch::PRODUCT) && !x->materialised && !x->wide && !x->full) {
     Batch& fx = *x->fixed;
     Batch& ch = *x->chain;
     const int n = x->n, T = ch.M, C = ch.C;

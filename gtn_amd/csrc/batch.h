@@ -96,6 +96,9 @@ struct Batch {
   bool chain_first = false, intersect = false;
   bool wide = false;  // force-alignment acceptors x an alphabet of 1025 .. 2048 labels: past the band sweeps, kept for
                       // batch_viterbi_align's launch (asg_align.hip) -- everything else composes the element graphs
+  bool full = false;  // `fixed` is a GRAPHS batch of ONE asgTransitions(C) graph, C <= asg_full_max_labels(), and `chain`
+                      // carries row counts (or GTNX_FULL_CONNECT=1): kept for forwardScore's launch (asg_full.hip) --
+                      // everything else composes the element graphs
   // ---- SCALAR: one float per element
   DevMemP v_mem;
   float* v_dev = nullptr;
@@ -120,6 +123,10 @@ BatchP batch_asg_force_align(const int* labels, const int* lengths, int n, Graph
 BatchP batch_linear(int n, int M, int C, bool calc_grad, const void* dev, bool borrow, const int* rows = nullptr);
 BatchP batch_compose(const BatchP& a, const BatchP& b, bool intersect);
 BatchP batch_shortest_distance(const BatchP& x, bool tropical);
+// utterances whose full-connect score forwardScore(chain_b o asgTransitions) came from the one launch of asg_full.hip /
+// utterances of a padded batch against such a graph that took the composed elements instead (an alphabet above
+// asg_full_max_labels(), or a consumer other than forwardScore)
+void batch_full_connect_stats(int64_t* fast, int64_t* fallback);
 BatchP batch_viterbi_path(const BatchP& x);
 // Forced alignment with device-resident output: labels_dev[b * row_stride + t] = the label of frame t on utterance b's
 // best path (-1 from the path's end on, everywhere when there is no path), tokens_dev likewise the index into the label

@@ -859,6 +859,9 @@ GTNX_API gtnx_status_t gtnx_batch_forward_score(gtnx_batch_t a, gtnx_batch_t* ou
 GTNX_API gtnx_status_t gtnx_batch_viterbi_score(gtnx_batch_t a, gtnx_batch_t* out) {
   return guard([&] { *out = HB(batch_shortest_distance(BH(a), true)); });
 }
+GTNX_API gtnx_status_t gtnx_batch_full_connect_stats(int64_t* fast, int64_t* fallback) {
+  return guard([&] { batch_full_connect_stats(fast, fallback); });
+}
 GTNX_API gtnx_status_t gtnx_batch_viterbi_path(gtnx_batch_t a, gtnx_batch_t* out) {
   return guard([&] { *out = HB(batch_viterbi_path(BH(a))); });
 }

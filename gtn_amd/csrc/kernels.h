@@ -781,6 +781,32 @@ struct PadFillArgs {
   int n, C;
 };
 void launch_pad_fill(const PadFillArgs& a, int64_t total_floats, hipStream_t st);
+// asg_full.hip: forwardScore(linearGraph(T_b, N) o asgTransitions(N)) of every utterance of a padded [n][M][N] tensor at
+// its own length and the gradient of those scores, one workgroup per utterance, one launch each way.  w: the transitions
+// weights in arc-id order (w[0 .. N) the start scores, w[N + i * N + j] the score of j -> i).  Forward: score[b]; with
+// la / L / zd set it also stores what the backward launch re-reads (la [n][M][N]: alpha_t[i] minus the step's running
+// scale, L [n][M]: that scale, zd [n]: the score in float64).  Backward (seed delta[b]): rows < rows[b] of grad_em
+// (or null) are OVERWRITTEN with delta * gamma, and partial (or null) [n][N + N * N] receives every utterance's
+// share of the transitions gradient, arc-id order; launch_asg_full_reduce adds the shares in utterance order (no
+// atomics).  Rows >= rows[b] of em, la and grad_em are never addressed.  A score of -inf: zeros.  1 <= N <=
+// asg_full_max_labels().
+struct AsgFullArgs {
+  const GTNX_G float* em;     // [n][M][N]
+  const GTNX_G int* rows;     // [n], 1 .. M, or nullptr: M
+  const GTNX_G float* w;      // [N + N * N]
+  GTNX_G float* score;        // [n]
+  GTNX_G float* la;           // [n][M][N] or nullptr (forward only: nothing kept for a gradient)
+  GTNX_G double* L;           // [n][M]
+  GTNX_G double* zd;          // [n]
+  const GTNX_G float* delta;  // [n] (backward)
+  GTNX_G float* grad_em;      // [n][M][N] or nullptr
+  GTNX_G float* partial;      // [n][N + N * N] or nullptr
+  int n, M, N;
+};
+int asg_full_max_labels();  // 128
+void launch_asg_full_forward(const AsgFullArgs& a, hipStream_t st);
+void launch_asg_full_backward(const AsgFullArgs& a, hipStream_t st);
+void launch_asg_full_reduce(const float* partial, int n, int N, float* out, hipStream_t st);
 // linear_decode.hip: viterbiPath of every chain of an [n][M][C] tensor at its own length frames[b] (device, 0 .. M),
 // then the CTC collapse, results on the device.  labels[b * row_stride + t] = the first label holding the maximum of
 // row t (-1 from frames[b] to M); scores[b] (or null) = ((0 + m_0) + m_1) + ... in frame order; collapsed[b *

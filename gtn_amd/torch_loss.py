@@ -35,6 +35,10 @@ def _native():
             lib.gtn_asg_loss_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             lib.gtn_asg_loss_n.restype = C.c_int
+            if hasattr(lib, "gtn_asg_loss_frames_n"):
+                lib.gtn_asg_loss_frames_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+                lib.gtn_asg_loss_frames_n.restype = C.c_int
             lib.gtn_criteria_last_error.restype = C.c_char_p
             if hasattr(lib, "gtn_ctc_align_n"):
                 lib.gtn_ctc_align_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -262,7 +266,7 @@ def ctc_forced_align(log_probs, targets, blank=0, input_lengths=None):
 
 class _ASGLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, emissions, transitions, start, targets, reduction):
+    def forward(ctx, emissions, transitions, start, targets, reduction, frames=None):
         assert emissions.is_cuda and emissions.dtype == torch.float32 and emissions.dim() == 3
         B, T, N = emissions.shape
         assert transitions.shape == (N, N) and start.shape == (N,)
@@ -283,9 +287,19 @@ class _ASGLoss(torch.autograd.Function):
         gem = torch.empty(B, T, N, dtype=torch.float32, device=x.device) if emissions.requires_grad else None
         need_tr = transitions.requires_grad or start.requires_grad
         gtr = torch.empty(N + N * N, dtype=torch.float32, device=x.device) if need_tr else None
-        rc = lib.gtn_asg_loss_n(x.data_ptr(), flat.ctypes.data, lens.ctypes.data, B, T, N, w.data_ptr(),
-                                out.data_ptr(), gem.data_ptr() if gem is not None else None,
-                                gtr.data_ptr() if gtr is not None else None)
+        ctx.ragged = frames is not None
+        if frames is None:
+            rc = lib.gtn_asg_loss_n(x.data_ptr(), flat.ctypes.data, lens.ctypes.data, B, T, N, w.data_ptr(),
+                                    out.data_ptr(), gem.data_ptr() if gem is not None else None,
+                                    gtr.data_ptr() if gtr is not None else None)
+        else:
+            if not hasattr(lib, "gtn_asg_loss_frames_n"):
+                raise RuntimeError("asg_loss(input_lengths=...) needs gtn_asg_loss_frames_n in "
+                                   "gtn_amd/lib/libgtn_criteria.so (run __graft_entry__.build())")
+            rc = lib.gtn_asg_loss_frames_n(x.data_ptr(), flat.ctypes.data, lens.ctypes.data, B, T, N, w.data_ptr(),
+                                           frames.ctypes.data, out.data_ptr(),
+                                           gem.data_ptr() if gem is not None else None,
+                                           gtr.data_ptr() if gtr is not None else None)
         if rc != 0:
             raise RuntimeError(lib.gtn_criteria_last_error().decode())
         if not stream.cuda_stream:
@@ -316,18 +330,26 @@ class _ASGLoss(torch.autograd.Function):
         if gtr is not None:
             g_st = gtr[:N] * scale_tr
             g_tr = gtr[N:].reshape(N, N) * scale_tr
-        return g_em, g_tr, g_st, None, None
+        return (g_em, g_tr, g_st, None, None) + ((None,) if ctx.ragged else ())
 
 
-def asg_loss(emissions, transitions, targets, start=None, reduction="none"):
+def asg_loss(emissions, transitions, targets, start=None, reduction="none", input_lengths=None):
     """The ASG criterion of examples/asg.cpp:30-68 / criterion_test.cpp:182-306 for a batch.
     emissions: float32 CUDA [B, T, N]; transitions: [N, N] with transitions[i, j] the score of
     label j followed by label i; start: [N] scores of the first label (zeros when omitted);
     targets: B label sequences.  Differentiable w.r.t. emissions, transitions and start; the
-    full-connect term runs on the symbolic composition (nothing of size T*N*N is stored)."""
+    full-connect term runs on the symbolic composition (nothing of size T*N*N is stored).
+    input_lengths: a sequence or int tensor of B frame counts (1 .. T) for a padded batch, or None: utterance
+    b's loss is that of emissions[b, :T_b], rows past T_b are never read and their gradient is 0.  With N <= 128
+    the full-connect term of a padded batch is one launch (one workgroup per utterance walks its own frames);
+    larger alphabets run one group of launches per distinct length.  An utterance with T_b < len(target_b) has
+    no alignment: its loss is +inf and its gradient rows hold the full-connect posteriors alone."""
     if start is None:
         start = torch.zeros(emissions.shape[-1], dtype=torch.float32, device=emissions.device)
-    return _ASGLoss.apply(emissions, transitions, start, targets, reduction)
+    if input_lengths is None:
+        return _ASGLoss.apply(emissions, transitions, start, targets, reduction)
+    frames = _frame_counts("asg_loss", input_lengths, emissions.shape[0], emissions.shape[1], 1)
+    return _ASGLoss.apply(emissions, transitions, start, targets, reduction, frames)
 
 
 def _asg_transitions_graph(N, w):

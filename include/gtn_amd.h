@@ -336,6 +336,14 @@ gtnx_status_t gtnx_batch_viterbi_decode(gtnx_batch_t ems, gtnx_graph_t transitio
                                         void* collapsed_device, void* lengths_device);
 /* utterances decoded so far (process-wide) by the launch / by the path-graph route */
 gtnx_status_t gtnx_batch_decode_stats(int64_t* fast, int64_t* fallback);
+/* gtnx_batch_compose / _intersect of a gtnx_batch_linear_rows batch with a one-element batch holding an ASG transitions
+ * graph over the same alphabet (N + 1 nodes, N (N + 1) arcs in the order of examples/asg.cpp:36-47), in either argument
+ * order, stays symbolic for N <= 128: gtnx_batch_forward_score of it is ONE launch that walks every utterance's own
+ * rows (pad rows are never read), its backward two more, and the transitions graph receives one gradient summed in
+ * utterance order (bit-repeatable).  Batches without row counts take that launch only under GTNX_FULL_CONNECT=1.
+ * Utterances scored so far (process-wide) by the launch / padded utterances that took the composed elements instead
+ * (a larger alphabet, or a consumer other than forwardScore). */
+gtnx_status_t gtnx_batch_full_connect_stats(int64_t* fast, int64_t* fallback);
 /* Best-path decode of a whole batch of chains with device-resident output: viterbiPath(ems_b) (shortest.cpp:190-272
  * on creations.cpp:20-33) followed by the CTC collapse (merge repeats, then drop blanks), the call a CTC model makes at
  * inference, without the path graphs.  Row b of labels_device (int32, row_stride entries apart, row_stride >= M)
