@@ -13,9 +13,42 @@ import numpy as np
 from ctc_fp64 import asg_fp64
 
 # (B, T, N, Umax): the shapes of tests/test_asg_frames_gpu.py -- one label, tiny N, N not a multiple of 4, letters,
-# across a wave (64 / 65), the limit of the launch (127 / 128)
+# the launcher's switch from 32 to 64 entries per lane (64 / 65), the limit of the launch (127 / 128)
 GPU_SHAPES = [(2, 9, 1, 3), (3, 7, 2, 3), (4, 12, 5, 4), (5, 40, 27, 9), (3, 33, 64, 10), (3, 33, 65, 10),
               (2, 20, 127, 6), (2, 20, 128, 6)]
+# the other edges of asg_full.hip's layout (N <= 2 * JH labels, JH = 16 / 32 / 64 entries per lane at N <= 32 / <= 64 /
+# else, read from LDS four at a time): a float4 with three live entries and with exactly four (3 / 4), the first label
+# owned by the second half's lanes at JH = 16 (16 / 17), the switch from JH = 16 to 32 (31 / 32 / 33)
+EDGE_SHAPES = [(3, 9, 3, 3), (3, 9, 4, 3), (4, 11, 16, 5), (4, 11, 17, 5), (4, 11, 31, 5), (4, 11, 32, 5),
+               (4, 11, 33, 5)]
+# utterances of production length (T = 1000): frames [1200, 30, 1, 234] and [600, 20, 1]
+LONG_SHAPES = [(4, 1200, 27, 30), (3, 600, 128, 20)]
+# seeded_case arguments: more utterances than the card has compute units, every length 1 .. 6 among them
+MANY_CASE = (5, 300, 6, 5, 3)
+# seeded_case arguments of the batch that kill_emissions turns into the -inf case: frames [12, 4, 1, 5]
+DEAD_CASE = (91, 4, 12, 9, 4)
+# upstream gradients of reduction="none" on (5, 40, 27, 9): a zero and a negative one among them
+SEEDS = [0.0, -1.5, 2.0, 0.5, 1.0]
+# the seed of a second (4, 12, 5, 4) batch run against the transitions graph of the first (gradient accumulation)
+SECOND_SEED = 4242
+
+
+def shape_seed(shape):
+    """the seed under which tests/test_asg_frames_*.py draw the batch of a (B, T, N, Umax)"""
+    _, T, N, _ = shape
+    return 1000 + 7 * N + T
+
+
+def kill_emissions(em):
+    """a copy of DEAD_CASE's emissions with -inf in them: label 4 everywhere, labels 0 .. 6 of one frame of utterance 0,
+    every label but 0 in the first frame of utterance 3 -- utterances 0, 2 and 3 keep finite scores -- and the whole of
+    frame 1 of utterance 1, which leaves that utterance without a path"""
+    em = np.array(em, copy=True)
+    em[:, :, 4] = -np.inf
+    em[0, 3, :7] = -np.inf
+    em[3, 0, 1:] = -np.inf
+    em[1, 1, :] = -np.inf
+    return em
 
 
 def fal_fp64(em, trans, start, target):

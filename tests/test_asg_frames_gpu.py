@@ -15,7 +15,8 @@ import sys
 import numpy as np
 import pytest
 
-from asg_loss_fp import GPU_SHAPES, batch_fp64, seeded_case
+from asg_loss_fp import (DEAD_CASE, EDGE_SHAPES, GPU_SHAPES, LONG_SHAPES, MANY_CASE, SECOND_SEED, SEEDS, batch_fp64,
+                         kill_emissions, seeded_case, shape_seed)
 from ctc_fp64 import asg_fp64
 
 pytestmark = pytest.mark.gpu
@@ -35,7 +36,7 @@ def _dev(x):
 def _case(shape, em_scale=1.0):
     """(em, em with NaN in every pad row, trans, start, targets, frames, the float64 yardstick over the batch)"""
     B, T, N, Umax = shape
-    em, trans, start, targets, frames = seeded_case(1000 + 7 * N + T, B, T, N, Umax, em_scale)
+    em, trans, start, targets, frames = seeded_case(shape_seed(shape), B, T, N, Umax, em_scale)
     assert frames[0] == T and 1 in frames.tolist() and any(f == len(t) for f, t in zip(frames, targets))
     em_nan = em.copy()
     for b, f in enumerate(frames):
@@ -47,13 +48,15 @@ def _case(shape, em_scale=1.0):
     return em, em_nan, trans, start, targets, frames, ref
 
 
-def _torch_step(em, trans, start, targets, frames, reduction="sum", weights=None, grad=True):
+def _torch_step(em, trans, start, targets, frames, reduction="sum", weights=None, grad=True, tr_grad=None):
     """asg_loss + backward -> (losses [B] or the reduced value, d em, d trans [N, N], d start [N]) as numpy (None where
-    not asked for); weights: upstream gradient of reduction='none' (then only the emissions require a gradient)"""
+    not asked for); weights: upstream gradient of reduction='none' (then only the emissions require a gradient, unless
+    tr_grad=True asks for the transitions and start gradients beside them)"""
     import gtn_amd.torch_loss as tl
+    tr_grad = weights is None if tr_grad is None else tr_grad
     e = _dev(em).requires_grad_(grad)
-    t = _dev(trans).requires_grad_(grad and weights is None)
-    s = _dev(start).requires_grad_(grad and weights is None)
+    t = _dev(trans).requires_grad_(grad and tr_grad)
+    s = _dev(start).requires_grad_(grad and tr_grad)
     loss = tl.asg_loss(e, t, targets, start=s, reduction=reduction, input_lengths=frames)
     if grad:
         if weights is not None:
@@ -123,24 +126,34 @@ def _transitions_graph(gtn, trans, start):
     return g
 
 
-def _batch_step(gtn, em_dev, trans, start, frames, chain_first):
+def _batch_step(gtn, em_dev, trans, start, frames, chain_first, em_grad=True, tr=None, root=None):
     """forward_score(compose(chains, transitions)) and backward through the Batch API; the emission gradient is bound
-    into a tensor with one slab more than the batch, which must come back untouched"""
+    into a tensor with one slab more than the batch, which must come back untouched.  em_grad=False: the chains ask
+    for no gradient and must hold none afterwards (None is returned for it); tr: a transitions graph to run against
+    (its calc_grad as the caller set it: None is returned for a gradient it does not ask for) instead of a fresh one;
+    root: what backward starts from, as a function of the scores (gtn.negate: every utterance is seeded with -1)"""
     import torch
     B, T, N = em_dev.shape
-    tr = _transitions_graph(gtn, trans, start)
-    ems = gtn.Batch.linear(B, T, N, em_dev, True, True, rows=frames)
+    tr = _transitions_graph(gtn, trans, start) if tr is None else tr
+    ems = gtn.Batch.linear(B, T, N, em_dev, em_grad, True, rows=frames)
     one = gtn.Batch([tr])
     grad = torch.full((B + 1, T, N), SENTINEL, device="cuda:0")
     off = np.arange(B, dtype=np.int64) * T * N
-    ems.bind_grads(grad, off)
+    if em_grad:
+        ems.bind_grads(grad, off)
     score = gtn.forward_score(gtn.compose(ems, one) if chain_first else gtn.compose(one, ems))
-    gtn.backward(score)
-    ems.grads_to_device(grad, off)
+    gtn.backward(score if root is None else root(score))
+    if em_grad:
+        ems.grads_to_device(grad, off)
+    else:
+        with pytest.raises(RuntimeError, match="Gradient not calculated"):
+            ems.grads_to_device(grad, off)
     gtn.synchronize()
     g = grad.cpu().numpy()
     assert (g[B] == SENTINEL).all(), "the slab behind the bound gradient was written"
-    return np.asarray(score.items()), g[:B], tr.grad().weights_to_numpy()
+    assert em_grad or (g == SENTINEL).all(), "an emission gradient nobody asked for was written"
+    return (np.asarray(score.items()), g[:B] if em_grad else None,
+            tr.grad().weights_to_numpy() if tr.calc_grad else None)
 
 
 @pytest.mark.parametrize("chain_first", [True, False], ids=["chain_first", "transitions_first"])
@@ -326,6 +339,221 @@ def test_alphabet_above_the_limit_takes_the_composed_elements(gtn):
         assert abs(loss[b] - ref["loss"][b]) <= _loss_tol(ref, b), b
     _check_em(f"N={N}", g_em, ref["g_em"], frames, 1.0)
     _check_tr(f"N={N}", g_tr, g_st, ref["g_tr"].sum(0), N)
+
+
+# ---- 11. the edges of the launch's layout: N = 3 / 4, 16 / 17, 31 / 32 / 33 ------------------------------------------
+def _full_connect_fp64(em, trans, start, frames, skip=()):
+    """asg_fp64 per utterance on em[b, :T_b]: (scores [B], d em [B, T, N] with zeros in the pad rows, d transitions
+    [B, N + N * N]); utterances in `skip` are not asked (zeros, score nan)"""
+    B, T, N = em.shape
+    tw = np.concatenate([start, trans.reshape(-1)])
+    z, g_em, g_tr = np.full(B, np.nan), np.zeros((B, T, N)), np.zeros((B, N + N * N))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for b, f in enumerate(frames):
+            if b not in skip:
+                z[b], g_em[b, :f], g_tr[b] = asg_fp64(em[b, :f], tw)[:3]
+    return z, g_em, g_tr
+
+
+def _check_scores(tag, score, want, frames, skip=()):
+    for b, f in enumerate(frames):
+        if b in skip:
+            continue
+        print(f"{tag} b={b} T_b={f} score {score[b]:.6f} want {want[b]:.6f}")
+        assert abs(score[b] - want[b]) <= 1e-4 * max(1.0, abs(want[b])), (tag, b)
+
+
+@pytest.mark.parametrize("shape", EDGE_SHAPES, ids=str)
+def test_layout_edges_through_both_entries(gtn, shape):
+    em, em_nan, trans, start, targets, frames, ref = _case(shape)
+    B, T, N, _ = shape
+    f0 = gtn.debug_full_connect_stats()
+    loss, g_em, g_tr, g_st = _torch_step(em, trans, start, targets, frames, "sum")
+    f1 = gtn.debug_full_connect_stats()
+    assert (f1[0] - f0[0], f1[1] - f0[1]) == (B, 0), "the launch of asg_full.hip did not take every utterance"
+    want = ref["loss"].sum()
+    tol = sum(_loss_tol(ref, b) for b in range(B))
+    print(f"{shape} sum loss {float(loss):.6f} want {want:.6f} tol {tol:.2e}")
+    assert abs(float(loss) - want) <= tol
+    _check_em(f"{shape} sum", g_em, ref["g_em"], frames, 1.0)
+    _check_tr(f"{shape} sum", g_tr, g_st, ref["g_tr"].sum(0), N)
+    out = []
+    for e in (em, em_nan):
+        f0 = gtn.debug_full_connect_stats()
+        out.append(_batch_step(gtn, _dev(e), trans, start, frames, True))
+        f1 = gtn.debug_full_connect_stats()
+        assert (f1[0] - f0[0], f1[1] - f0[1]) == (B, 0), "the launch of asg_full.hip did not take every utterance"
+    z, w_em, w_tr = _full_connect_fp64(em, trans, start, frames)
+    score, g_em, g_tr = out[0]
+    _check_scores(str(shape), score, z, frames)
+    _check_em(str(shape), g_em, w_em, frames, 1.0)
+    _check_tr(str(shape), g_tr[N:], g_tr[:N], w_tr.sum(0), N)
+    for x, y in zip(out[0], out[1]):
+        assert np.array_equal(x, y), "NaN in the pad rows of the emissions changed an output"
+
+
+# ---- 12. utterances of production length ------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", LONG_SHAPES, ids=str)
+def test_long_utterances_through_asg_loss(gtn, shape):
+    """the scaled recursion over 1200 and 600 frames beside utterances of 30 / 20 frames and of one: per-utterance
+    losses, emission gradients utterance by utterance (pad rows == 0), transitions and start gradients"""
+    em, _, trans, start, targets, frames, ref = _case(shape)
+    B, T, N, _ = shape
+    f0, _ = gtn.debug_full_connect_stats()
+    loss, g_em, g_tr, g_st = _torch_step(em, trans, start, targets, frames, "none")
+    assert gtn.debug_full_connect_stats()[0] - f0 == B
+    for b in range(B):
+        print(f"{shape} b={b} T_b={frames[b]} loss {loss[b]:.6f} want {ref['loss'][b]:.6f} tol {_loss_tol(ref, b):.2e}")
+        assert abs(loss[b] - ref["loss"][b]) <= _loss_tol(ref, b), (shape, b)
+    _check_em(f"{shape} long", g_em, ref["g_em"], frames, 1.0)
+    _check_tr(f"{shape} long", g_tr, g_st, ref["g_tr"].sum(0), N)
+
+
+@pytest.mark.parametrize("shape", LONG_SHAPES, ids=str)
+def test_long_utterances_full_connect_term_alone(gtn, shape):
+    em, _, trans, start, _, frames, _ = _case(shape)
+    N = shape[2]
+    z, w_em, w_tr = _full_connect_fp64(em, trans, start, frames)
+    score, g_em, g_tr = _batch_step(gtn, _dev(em), trans, start, frames, True)
+    _check_scores(f"{shape} long batch", score, z, frames)
+    _check_em(f"{shape} long batch", g_em, w_em, frames, 1.0)
+    _check_tr(f"{shape} long batch", g_tr[N:], g_tr[:N], w_tr.sum(0), N)
+
+
+# ---- 13. more utterances than compute units -----------------------------------------------------------------------------
+def test_more_utterances_than_compute_units(gtn):
+    """300 workgroups, 300 slices for asg_full_reduce_kernel to add in utterance order: scores, emission gradients and
+    the transitions gradient against the yardstick's sum, the same bits twice, the guard slab untouched (_batch_step)"""
+    em, trans, start, _, frames = seeded_case(*MANY_CASE)
+    B, T, N = em.shape
+    assert B == 300 and set(frames.tolist()) == set(range(1, T + 1))
+    z, w_em, w_tr = _full_connect_fp64(em, trans, start, frames)
+    assert np.isfinite(z).all()
+    f0 = gtn.debug_full_connect_stats()
+    x = [_batch_step(gtn, _dev(em), trans, start, frames, True) for _ in range(2)]
+    f1 = gtn.debug_full_connect_stats()
+    assert (f1[0] - f0[0], f1[1] - f0[1]) == (2 * B, 0)
+    score, g_em, g_tr = x[0]
+    err = np.abs(score - z) / np.maximum(1.0, np.abs(z))
+    print(f"many: score rel {err.max():.2e}")
+    assert (err <= 1e-4).all(), int(err.argmax())
+    err = np.abs(g_em - w_em).reshape(B, -1).max(1)
+    print(f"many: em grad abs {err.max():.2e}")
+    assert np.isfinite(g_em).all() and (err <= 1e-4).all(), int(err.argmax())
+    for b, f in enumerate(frames):
+        assert not g_em[b, f:].any(), (b, "pad rows of the gradient are not 0")
+    _check_tr("many", g_tr[N:], g_tr[:N], w_tr.sum(0), N)
+    for u, v in zip(x[0], x[1]):
+        assert np.array_equal(u, v)
+
+
+# ---- 14. -inf emissions and an utterance without a path ---------------------------------------------------------------
+def test_dead_emissions_and_an_utterance_without_a_path(gtn):
+    """-inf in the emissions is probability 0; an utterance whose every path is -inf has score -inf
+    and a gradient of zeros that the backward kernel STORES (its early return), never 0 * inf.  The values asked of
+    utterance 1 are stated, not computed: the float64 yardstick is NaN there.  Full-connect term only -- the
+    force-align term of such a batch is -inf and the loss +inf."""
+    em, trans, start, _, frames = seeded_case(*DEAD_CASE)
+    assert frames.tolist() == [12, 4, 1, 5]
+    B, T, N = em.shape
+    em = kill_emissions(em)
+    em_nan = em.copy()
+    for b, f in enumerate(frames):
+        em_nan[b, f:] = np.nan
+    z, w_em, w_tr = _full_connect_fp64(em, trans, start, frames, skip=(1,))
+    assert np.isfinite(np.delete(z, 1)).all() and np.isfinite(w_em).all() and np.isfinite(w_tr).all()
+    out = [_batch_step(gtn, _dev(e), trans, start, frames, True) for e in (em, em_nan)]
+    score, g_em, g_tr = out[0]
+    assert score[1] == -np.inf
+    assert not np.isnan(score).any() and not np.isnan(g_em).any() and not np.isnan(g_tr).any()
+    assert not g_em[1].any(), "the utterance without a path has a gradient"
+    assert not g_em[np.isneginf(em)].any(), "an emission of probability 0 has a gradient"
+    _check_scores("dead", score, z, frames, skip=(1,))
+    _check_em("dead", g_em, w_em, frames, 1.0)  # (utterance 1: zeros against the zeros stated above)
+    _check_tr("dead", g_tr[N:], g_tr[:N], w_tr[[0, 2, 3]].sum(0), N)
+    for x, y in zip(out[0], out[1]):
+        assert np.array_equal(x, y), "NaN in the pad rows of the emissions changed an output"
+
+
+# ---- 15. which gradients are asked for ----------------------------------------------------------------------------------
+def test_only_the_gradients_asked_for(gtn):
+    """transitions only (the xi kernel with no emission gradient to store), emissions only (the kernel without xi),
+    neither (nothing kept by the forward launch; backward does nothing and raises nothing).  The scores are the
+    both-wanted run's bit for bit: one forward kernel, and keeping la / L only adds stores."""
+    em, _, trans, start, _, frames, _ = _case(LETTERS)
+    N = LETTERS[2]
+    z, w_em, w_tr = _full_connect_fp64(em, trans, start, frames)
+    both = _batch_step(gtn, _dev(em), trans, start, frames, True)
+    _check_scores("both", both[0], z, frames)
+
+    def step(em_grad, tr_grad):
+        tr = _transitions_graph(gtn, trans, start)
+        tr.calc_grad = tr_grad
+        score, g_em, g_tr = _batch_step(gtn, _dev(em), trans, start, frames, True, em_grad=em_grad, tr=tr)
+        assert np.array_equal(score, both[0]), (em_grad, tr_grad, "the scores depend on which gradients are wanted")
+        assert tr_grad or not tr.is_grad_available()
+        return g_em, g_tr
+
+    g_em, g_tr = step(False, True)
+    assert g_em is None
+    _check_tr("transitions only", g_tr[N:], g_tr[:N], w_tr.sum(0), N)
+    assert np.array_equal(g_tr, both[2]), "the transitions gradient depends on whether the emissions want one"
+    g_em, g_tr = step(True, False)
+    assert g_tr is None
+    _check_em("emissions only", g_em, w_em, frames, 1.0)
+    assert step(False, False) == (None, None)
+
+
+# ---- 16. upstream gradients: zero, negative ---------------------------------------------------------------------------
+def test_upstream_seeds_zero_and_negative(gtn):
+    """reduction='none' with seeds [0, -1.5, 2, 0.5, 1]: the zero-seed utterance's emission rows are exactly 0, the
+    others w_b times the yardstick.  asg_loss REFUSES a transitions gradient under per-utterance seeds that differ
+    (torch_loss.py: the criterion sums it over the batch with unit seeds; RuntimeError) -- a documented limit, pinned
+    here; inside the contract the transitions gradient is held to the yardstick under a uniform negative seed.
+    asg_loss hands the launch unit seeds and scales afterwards, so the kernel's own `delta` is reached through the
+    Batch API: negate(score) seeds every utterance with -1, subtract(score, score) with 0."""
+    em, _, trans, start, targets, frames, ref = _case(LETTERS)
+    B, T, N, _ = LETTERS
+    w = np.asarray(SEEDS, np.float64)
+    loss, g_em, _, _ = _torch_step(em, trans, start, targets, frames, "none", weights=SEEDS)
+    for b in range(B):
+        assert abs(loss[b] - ref["loss"][b]) <= _loss_tol(ref, b), b
+    assert not g_em[0].any(), "a seed of 0 left a gradient"
+    _check_em("seeds", g_em, ref["g_em"], frames, w)
+    with pytest.raises(RuntimeError, match="uniform upstream"):
+        _torch_step(em, trans, start, targets, frames, "none", weights=SEEDS, tr_grad=True)
+    _, g_em, g_tr, g_st = _torch_step(em, trans, start, targets, frames, "none", weights=[-1.5] * B, tr_grad=True)
+    _check_em("seed -1.5", g_em, ref["g_em"], frames, -1.5)
+    _check_tr("seed -1.5", g_tr, g_st, -1.5 * ref["g_tr"].sum(0), N)
+    # the kernel's delta
+    z, w_em, w_tr = _full_connect_fp64(em, trans, start, frames)
+    score, g_em, g_tr = _batch_step(gtn, _dev(em), trans, start, frames, True, root=gtn.negate)
+    _check_scores("negate", score, z, frames)
+    _check_em("negate", g_em, w_em, frames, -1.0)
+    _check_tr("negate", g_tr[N:], g_tr[:N], -w_tr.sum(0), N)
+    score, g_em, g_tr = _batch_step(gtn, _dev(em), trans, start, frames, True, root=lambda s: gtn.subtract(s, s))
+    _check_scores("x - x", score, z, frames)
+    assert not g_em.any() and not g_tr.any(), "a seed of 0 left a gradient"
+
+
+# ---- 17. a transitions graph that already holds a gradient ----------------------------------------------------------------
+def test_transitions_gradient_accumulates_until_zero_grad(gtn):
+    """two different padded batches against the SAME transitions graph, backward on each without zero_grad: the
+    graph holds the sum (BFullOp: add_grad_device); after zero_grad and one more step, the single one"""
+    shape = (4, 12, 5, 4)
+    em1, _, trans, start, _, fr1, _ = _case(shape)
+    em2, _, _, _, fr2 = seeded_case(SECOND_SEED, *shape)
+    N = shape[2]
+    w1 = _full_connect_fp64(em1, trans, start, fr1)[2].sum(0)
+    w2 = _full_connect_fp64(em2, trans, start, fr2)[2].sum(0)
+    tr = _transitions_graph(gtn, trans, start)
+    _, _, g = _batch_step(gtn, _dev(em1), trans, start, fr1, True, tr=tr)
+    _check_tr("first", g[N:], g[:N], w1, N)
+    _, _, g = _batch_step(gtn, _dev(em2), trans, start, fr2, True, tr=tr)
+    _check_tr("first + second", g[N:], g[:N], w1 + w2, N)
+    tr.zero_grad()
+    _, _, g = _batch_step(gtn, _dev(em2), trans, start, fr2, True, tr=tr)
+    _check_tr("second after zero_grad", g[N:], g[:N], w2, N)
 
 
 if __name__ == "__main__" and len(sys.argv) == 4 and sys.argv[1] == _CHILD:
