@@ -69,6 +69,7 @@ debug_align_stats = getattr(_api, "debug_align_stats", None)  # (Batch.viterbi_a
 debug_decode_stats = _api.debug_decode_stats  # (Batch.viterbi_decode: which route decoded how many)
 debug_full_connect_stats = _api.debug_full_connect_stats  # (forward_score of a padded batch o ASG transitions: which route)
 debug_linear_decode_stats = _api.debug_linear_decode_stats  # (Batch.linear_decode: which route decoded how many)
+debug_ctc_beam_stats = _api.debug_ctc_beam_stats  # (Batch.ctc_beam_decode: calls that launched, utterances decoded)
 
 
 def load_txt(text):

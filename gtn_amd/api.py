@@ -832,6 +832,51 @@ def make_api(lib):
                                                _as_dev_ptr(starts_out) if starts_out is not None else None,
                                                _as_dev_ptr(lengths_out) if lengths_out is not None else None))
 
+        def ctc_beam_decode(self, tokens_out, lengths_out, scores_out, frames=None, blank=0, beam_size=16,
+                            cutoff_top_n=16, nbest=1, row_stride=None):
+            """CTC prefix beam search with N-best output over a Batch.linear, results left on the device
+            (gtnx_batch_ctc_beam_decode; DESIGN section 20 holds the contract): `tokens_out` (int32 CUDA tensor
+            [B, nbest, >= M] with contiguous rows, or a device address of [B][nbest][row_stride]) gets the labels of
+            the `nbest` best label sequences of every utterance, best first, -1 from each one's length to the row's
+            width M; `lengths_out` (int32 [B, nbest]) their lengths; `scores_out` (float32 [B, nbest]) their log
+            scores, summed over the alignments the beam kept.  Slots without a hypothesis (fewer than nbest prefixes, a
+            frame with nothing above -inf, T_b = 0): -1, 0, -inf.  `beam_size` 1 .. 64 prefixes are kept, a frame
+            offers its `cutoff_top_n` (1 .. 32) best labels plus `blank`; `frames`: T_b per element (0 .. M, at most
+            the rows the batch carries; None: those rows).  Two launches with no copy back and no wait; rows from T_b
+            on are never read.  Any batch but a Batch.linear is an error: there is no other route."""
+            n = len(self)
+            stride = row_stride
+            t = tokens_out
+            if t is not None and hasattr(t, "data_ptr"):
+                if (str(t.dtype) != "torch.int32" or t.dim() != 3 or t.shape[0] < n or t.shape[1] != int(nbest)
+                        or (t.shape[2] > 1 and t.stride(2) != 1) or (n > 1 and t.stride(0) != t.shape[1] * t.stride(1))):
+                    raise ValueError("ctc_beam_decode: tokens_out must be an int32 tensor [B, nbest, M] with contiguous "
+                                     "rows, equally spaced")
+                if stride is not None and t.stride(1) != stride:
+                    raise ValueError("ctc_beam_decode: row_stride is not the row stride of tokens_out")
+                stride = t.stride(1)
+                m, c = C.c_int(-1), C.c_int(-1)
+                check(lib.gtnx_batch_linear_shape(self._h, C.byref(m), C.byref(c)))
+                if t.shape[2] < m.value:  # (the kernel writes M entries of every row, whatever lies behind a view)
+                    raise ValueError(f"ctc_beam_decode: tokens_out has rows of {t.shape[2]} entries, the batch has "
+                                     f"{m.value} rows")
+            if stride is None:
+                raise ValueError("ctc_beam_decode: a device address needs row_stride")
+            for o, dt, what in ((lengths_out, "torch.int32", "lengths_out must be an int32"),
+                                (scores_out, "torch.float32", "scores_out must be a float32")):
+                if o is not None and hasattr(o, "data_ptr") and (str(o.dtype) != dt or not o.is_contiguous()
+                                                                 or o.numel() < n * int(nbest)):
+                    raise ValueError(f"ctc_beam_decode: {what} contiguous tensor [B, nbest]")
+            fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32)
+            if fr is not None and fr.shape != (n,):
+                raise ValueError("ctc_beam_decode: one frame count per element")
+            check(lib.gtnx_batch_ctc_beam_decode(self._h, fr.ctypes.data if fr is not None else None, int(blank),
+                                                 int(beam_size), int(cutoff_top_n), int(nbest),
+                                                 _as_dev_ptr(tokens_out) if tokens_out is not None else None,
+                                                 int(stride),
+                                                 _as_dev_ptr(lengths_out) if lengths_out is not None else None,
+                                                 _as_dev_ptr(scores_out) if scores_out is not None else None))
+
     ns.Batch = Batch
 
     def _batch_fn(cfn, *args):
@@ -968,6 +1013,13 @@ def make_api(lib):
         check(lib.gtnx_batch_linear_decode_stats(C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def debug_ctc_beam_stats():
+        """(calls, utterances): calls of Batch.ctc_beam_decode that have launched so far and the utterances they
+        decoded (include/gtn_amd.h: gtnx_batch_ctc_beam_stats)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(lib.gtnx_batch_ctc_beam_stats(C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def debug_full_connect_stats():
         """(fast, fallback): utterances whose ASG full-connect score forward_score(compose(Batch.linear(rows=...),
         transitions)) came from the one launch of asg_full.hip / utterances of such a padded batch that took the composed
@@ -981,6 +1033,7 @@ def make_api(lib):
     ns.debug_full_connect_stats = debug_full_connect_stats
     ns.debug_decode_stats = debug_decode_stats
     ns.debug_linear_decode_stats = debug_linear_decode_stats
+    ns.debug_ctc_beam_stats = debug_ctc_beam_stats
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties
 

@@ -80,6 +80,23 @@ extern "C" __attribute__((visibility("default"))) int gtn_ctc_decode_n(const voi
   }
 }
 
+// CTC prefix beam search with N-best output.  emissions: DEVICE float [B][T][C]; frames: host int32 [B] or null; tokens:
+// DEVICE int32 [B][nbest][T]; lengths: DEVICE int32 [B][nbest]; scores: DEVICE float [B][nbest].  Returns 0, or -1 with
+// the message in gtn_criteria_last_error().
+extern "C" __attribute__((visibility("default"))) int gtn_ctc_beam_decode_n(const void* emissions, int B, int T, int C,
+                                                                            int blank, const int* frames, int beam_size,
+                                                                            int cutoff_top_n, int nbest, void* tokens,
+                                                                            void* lengths, void* scores) {
+  try {
+    gtn::criteria::ctcBeamDecodeBatch(emissions, B, T, C, blank, frames, beam_size, cutoff_top_n, nbest, tokens, lengths,
+                                      scores);
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
 // The same, as benchmarks/ctc.cpp:150-165 runs it: target graphs with calcGrad = true, and THEIR gradients too.
 // target_grad: DEVICE float, utterance b's arc gradients (arc ids of benchmarks/ctc.cpp:40-58's addArc order) at
 // target_grad + target_grad_offsets[b]; grad must be non-null.

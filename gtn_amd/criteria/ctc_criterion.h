@@ -163,5 +163,29 @@ inline void ctcDecodeBatch(
                         static_cast<int*>(collapsedDev), static_cast<int*>(startsDev), static_cast<int*>(lengthsDev));
 }
 
+/** CTC prefix beam search of a batch with N-best output, results on the device: per utterance the `nbest` best label
+ *  sequences, summed over the alignments the beam kept (gtnx_batch_ctc_beam_decode has the contract).  `tokensDev`:
+ *  device int32 [B][nbest][T], -1 from a hypothesis's length on; `lengthsDev`: device int32 [B][nbest]; `scoresDev`:
+ *  device float [B][nbest]; slots without a hypothesis -1, 0, -inf.  `frames`: host [B] or null -- how many of the T
+ *  rows of each utterance count (0 .. T); rows past them are never read.  `emissions`: device [B][T][C], read in
+ *  place.  Two launches; nothing is copied back. */
+inline void ctcBeamDecodeBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int C,
+    int blank,
+    const int* frames,
+    int beamSize,
+    int cutoffTopN,
+    int nbest,
+    void* tokensDev,
+    void* lengthsDev,
+    void* scoresDev) {
+  Batch ems = Batch::linear(B, T, C, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  batched::ctcBeamDecode(ems, static_cast<int*>(tokensDev), T, static_cast<int*>(lengthsDev),
+                         static_cast<float*>(scoresDev), blank, beamSize, cutoffTopN, nbest, frames);
+}
+
 } // namespace criteria
 } // namespace gtn

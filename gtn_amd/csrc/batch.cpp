@@ -1603,6 +1603,98 @@ void batch_linear_decode(const BatchP& ems, const int* frames, int blank, int* l
   g_linear_decode_fast.fetch_add(n);
 }
 
+// ---- CTC prefix beam search with N-best output, device-resident (ctc_beam.hip) ----
+namespace {
+std::atomic<int64_t> g_ctc_beam_calls{0}, g_ctc_beam_utts{0};
+}  // namespace
+
+void batch_ctc_beam_stats(int64_t* calls, int64_t* utterances) {
+  if (calls) *calls = g_ctc_beam_calls.load();
+  if (utterances) *utterances = g_ctc_beam_utts.load();
+}
+
+void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int beam, int topn, int nbest,
+                           int* tokens_dev, int64_t row_stride, int* lengths_dev, float* scores_dev) {
+  GTNX_HOST_T("batch.ctc_beam_decode");
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) throw_invalid("[gtnx_batch_ctc_beam_decode] null batch");
+  if (!tokens_dev || !lengths_dev || !scores_dev)
+    throw_invalid("[gtnx_batch_ctc_beam_decode] null output pointer (tokens, lengths and scores are all written)");
+  if (row_stride < 0) throw_invalid("[gtnx_batch_ctc_beam_decode] negative row stride");
+  if (beam < 1 || beam > 64) throw_invalid("[gtnx_batch_ctc_beam_decode] beam_size outside 1 .. 64");
+  if (topn < 1 || topn > 32) throw_invalid("[gtnx_batch_ctc_beam_decode] cutoff_top_n outside 1 .. 32");
+  if (nbest < 1) throw_invalid("[gtnx_batch_ctc_beam_decode] nbest below 1");
+  if (nbest > beam) throw_invalid("[gtnx_batch_ctc_beam_decode] nbest above beam_size");
+  if (blank < 0) throw_invalid("[gtnx_batch_ctc_beam_decode] negative blank");
+  Runtime& rt = Runtime::get();
+  const int n = ems->n;
+  // there is no other route: the search runs on the slabs of a native linear batch
+  if (!(ems->kind == Batch::LINEAR && !ems->leaf && ems->w_dev))
+    throw_invalid("[gtnx_batch_ctc_beam_decode] not a native linear batch (gtnx_batch_linear / _rows)");
+  Batch& x = *ems;
+  if (frames)
+    for (int b = 0; b < n; ++b) {
+      if (frames[b] < 0 || frames[b] > x.M) throw_invalid("[gtnx_batch_ctc_beam_decode] a frame count outside 0 .. M");
+      if (frames[b] > x.rows_of(b))
+        throw_invalid("[gtnx_batch_ctc_beam_decode] a frame count beyond the rows the batch carries");
+    }
+  if (n > 0 && row_stride < x.M)
+    throw_invalid("[gtnx_batch_ctc_beam_decode] row_stride is shorter than the rows of the batch");
+  if (blank >= x.C) throw_invalid("[gtnx_batch_ctc_beam_decode] blank is not below the number of labels");
+  // (a candidate's key keeps its label in 25 bits; trie nodes are numbered 1 + t * beam + slot in an int)
+  if (x.C > (1 << 25)) throw_invalid("[gtnx_batch_ctc_beam_decode] more than 2^25 labels");
+  if (int64_t(x.M) * beam + 1 > std::numeric_limits<int>::max())
+    throw_invalid("[gtnx_batch_ctc_beam_decode] rows times beam_size does not fit an int");
+  if (n <= 0) return;
+  // a kernel of this device writes the results: memory of another GPU of the process is refused, not written
+  if (!ptr_local_to(tokens_dev, rt.device()) || !ptr_local_to(lengths_dev, rt.device()) ||
+      !ptr_local_to(scores_dev, rt.device()))
+    throw_invalid("[gtnx_batch_ctc_beam_decode] an output pointer is not memory of the engine's current device");
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  std::vector<int> fr(static_cast<size_t>(n));
+  // algorithmic bytes.  rows: every emission of the rows that count once, topn + 1 entries and a count out.  search:
+  // those back in, a trie node per kept extension (at most beam per frame), the output rows.
+  double row_bytes = 0, search_bytes = 0;
+  for (int b = 0; b < n; ++b) {
+    const int t = fr[size_t(b)] = frames ? frames[b] : x.rows_of(b);
+    row_bytes += (4.0 * x.C + 8.0 * (topn + 1) + 4.0) * t;
+    search_bytes += (8.0 * (topn + 1) + 4.0 + 8.0 * beam) * t + nbest * (4.0 * x.M + 8.0);
+  }
+  DevMemP d_frames = upload_vec(fr);
+  const size_t rows = std::max<size_t>(size_t(n) * size_t(x.M), 1);
+  DevMemP entries = rt.alloc(8 * rows * size_t(topn + 1));
+  DevMemP counts = rt.alloc(sizeof(int) * rows);
+  DevMemP trie = rt.alloc(8 * size_t(n) * (size_t(x.M) * size_t(beam) + 1));
+  CtcBeamArgs a{};
+  a.em = x.w_dev;
+  a.frames = d_frames->as<int>();
+  a.ent_val = entries->as<float>();
+  a.ent_cnt = counts->as<int>();
+  a.trie = trie->as<int>();
+  a.tokens = tokens_dev;
+  a.lengths = lengths_dev;
+  a.scores = scores_dev;
+  a.row_stride = row_stride;
+  a.n = n;
+  a.M = x.M;
+  a.C = x.C;
+  a.blank = blank;
+  a.beam = beam;
+  a.topn = topn;
+  a.nbest = nbest;
+  {
+    GTNX_PROF("ctc_beam_rows", row_bytes);
+    launch_ctc_beam(a, 0, rt.stream());
+  }
+  {
+    GTNX_PROF("ctc_beam_search", search_bytes);
+    launch_ctc_beam(a, 1, rt.stream());
+  }
+  // (the scratch and the table go back to the stream-ordered pool behind the launches)
+  g_ctc_beam_calls.fetch_add(1);
+  g_ctc_beam_utts.fetch_add(n);
+}
+
 
 namespace {
 // a GRAPHS batch of one-arc graphs as a native SCALAR batch (values gathered; backward continues on the graphs' tape)

@@ -169,6 +169,20 @@ void batch_decode_stats(int64_t* fast, int64_t* fallback);  // utterances decode
 void batch_linear_decode(const BatchP& ems, const int* frames, int blank, int* labels_dev, int64_t row_stride,
                          float* scores_dev, int* collapsed_dev, int* starts_dev, int* lengths_dev);
 void batch_linear_decode_stats(int64_t* fast, int64_t* fallback);  // utterances decoded by the launches / the path graphs
+// CTC prefix beam search with N-best output over a native LINEAR batch, results on the device (DESIGN section 20 holds
+// the contract: token set of a frame = its topn best labels plus blank, at most `beam` distinct prefixes with (pb, pnb),
+// exact prefix merging, the total order of the candidates).  tokens_dev[(b * nbest + r) * row_stride + k]: the labels of
+// hypothesis r of utterance b, -1 from its length to the row's width M; lengths_dev[b * nbest + r]; scores_dev[b * nbest
+// + r] = logadd(pb, pnb); slots without a hypothesis (fewer than nbest prefixes, a frame with an empty token set,
+// T_b = 0): -1, 0, -inf.  frames (host, [n], or null): T_b, null = rows_of(b).  Invalid argument before a device is
+// asked for: null outputs, a negative stride, beam outside 1 .. 64, topn outside 1 .. 32, nbest outside 1 .. beam, a
+// negative blank.  With the device: a batch that is not a native LINEAR one (there is no other route), a count outside
+// 0 .. M or above rows_of(b), row_stride < M, blank >= C, outputs that are not memory of the current device.  Two
+// launches of ctc_beam.hip on the engine's stream, scratch from the stream-ordered pool; rows from T_b on are never
+// read, no download, no wait.
+void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int beam, int topn, int nbest,
+                           int* tokens_dev, int64_t row_stride, int* lengths_dev, float* scores_dev);
+void batch_ctc_beam_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they decoded
 // items_dev (optional): device memory of the CALLER's that the n result values are written into directly (borrowed: it
 // must outlive the result); a later batch_items_device to the same address copies nothing
 BatchP batch_scalar(ScalarKind k, const BatchP& a, const BatchP& b, void* items_dev = nullptr);

@@ -899,6 +899,25 @@ GTNX_API gtnx_status_t gtnx_batch_linear_decode(gtnx_batch_t ems, const int* fra
 GTNX_API gtnx_status_t gtnx_batch_linear_decode_stats(int64_t* fast, int64_t* fallback) {
   return guard([&] { batch_linear_decode_stats(fast, fallback); });
 }
+GTNX_API gtnx_status_t gtnx_batch_ctc_beam_decode(gtnx_batch_t ems, const int* frames, int blank, int beam_size,
+                                                  int cutoff_top_n, int nbest, void* tokens_device, int64_t row_stride,
+                                                  void* lengths_device, void* scores_device) {
+  return guard([&] {
+    batch_ctc_beam_decode(BH(ems), frames, blank, beam_size, cutoff_top_n, nbest, static_cast<int*>(tokens_device),
+                          row_stride, static_cast<int*>(lengths_device), static_cast<float*>(scores_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_ctc_beam_stats(int64_t* calls, int64_t* utterances) {
+  return guard([&] { batch_ctc_beam_stats(calls, utterances); });
+}
+GTNX_API gtnx_status_t gtnx_batch_linear_shape(gtnx_batch_t ems, int* rows, int* labels) {
+  return guard([&] {
+    const BatchP& b = BH(ems);
+    const bool linear = b->kind == Batch::LINEAR;
+    if (rows) *rows = linear ? b->M : -1;
+    if (labels) *labels = linear ? b->C : -1;
+  });
+}
 GTNX_API gtnx_status_t gtnx_batch_backward(gtnx_batch_t a, int retain) {
   return guard([&] { batch_backward(BH(a), retain != 0); });
 }

@@ -828,6 +828,27 @@ struct LinearDecodeArgs {
   int n, M, C, blank;
 };
 void launch_linear_decode(const LinearDecodeArgs& a, int which, hipStream_t st);
+// ctc_beam.hip: CTC prefix beam search with N-best output over every chain of an [n][M][C] tensor at its own length
+// frames[b] (device, 0 .. M), results on the device (the contract: DESIGN section 20).  which = 0: the rows -- the
+// token set S_t of every row that counts, (value, label) entries [n][M][topn + 1] and their counts [n][M] in scratch.
+// which = 1: one workgroup per utterance, sequential over the frames -- at most `beam` prefixes with (pb, pnb), exact
+// prefix identity through the trie in scratch (node 1 + t * beam + slot = (parent node, label), node 0 the empty
+// prefix), then tokens[(b * nbest + r) * row_stride + k] (-1 from the length to M), lengths[b * nbest + r],
+// scores[b * nbest + r]; slots without a hypothesis: -1, 0, -inf.  Nothing from row frames[b] on is read.
+// beam 1 .. 64, topn 1 .. 32, nbest 1 .. beam, C <= 2^25, M * beam < 2^31 (the engine has refused the rest).
+struct CtcBeamArgs {
+  const GTNX_G float* em;
+  const GTNX_G int* frames;  // [n]
+  GTNX_G float* ent_val;     // [n][M][topn + 1], interleaved with ent_lab as 8-byte entries: see ctc_beam.hip
+  GTNX_G int* ent_cnt;       // [n][M]
+  GTNX_G int* trie;          // [n][M * beam + 1][2]
+  GTNX_G int* tokens;
+  GTNX_G int* lengths;
+  GTNX_G float* scores;
+  int64_t row_stride;
+  int n, M, C, blank, beam, topn, nbest;
+};
+void launch_ctc_beam(const CtcBeamArgs& a, int which, hipStream_t st);
 // materialise a KIND_LINEAR graph's arc arrays
 void launch_linear_materialize(int M, int C, int* src, int* dst, int* il, int* ol, hipStream_t st);
 

@@ -1,5 +1,5 @@
 """PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
-`asg_forced_align`, `asg_decode` and `ctc_decode`.
+`asg_forced_align`, `asg_decode`, `ctc_decode` and `ctc_beam_decode`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -56,6 +56,10 @@ def _native():
                 lib.gtn_ctc_decode_n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
                 lib.gtn_ctc_decode_n.restype = C.c_int
+            if hasattr(lib, "gtn_ctc_beam_decode_n"):
+                lib.gtn_ctc_beam_decode_n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                      C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+                lib.gtn_ctc_beam_decode_n.restype = C.c_int
             _NATIVE = lib
         else:
             _NATIVE = False
@@ -527,3 +531,59 @@ def ctc_decode(log_probs, blank=0, input_lengths=None, collapse=True):
     if not stream.cuda_stream:
         gtn.synchronize()
     return (labels, scores, tokens, starts, lengths) if collapse else (labels, scores)
+
+
+def ctc_beam_decode(log_probs, blank=0, input_lengths=None, beam_size=16, cutoff_top_n=16, nbest=1):
+    """CTC prefix beam search of a batch with N-best output, device-resident: the best label sequences, summed over
+    their alignments, where `ctc_decode` gives the best alignment -- two launches whatever the lengths, nothing copied
+    back.
+    log_probs: float32 CUDA tensor [B, T, C] (any scores), read in place and left untouched; rows past an utterance's
+    length are never read; blank: the blank label (0 .. C - 1); input_lengths: per-utterance frame counts (0 .. T) or
+    None; beam_size: prefixes kept per frame (1 .. 64); cutoff_top_n: the best labels of a frame that may extend a
+    prefix (1 .. 32; blank is always offered where its score is above -inf); nbest: hypotheses returned (1 ..
+    beam_size).
+    Returns (tokens int32 [B, nbest, T], lengths int32 [B, nbest], scores float32 [B, nbest]) on log_probs.device, best
+    first: the labels of each hypothesis, -1 from its length on, and its log score summed over the alignments the beam
+    kept (float32 log-add; unpruned it is -ctc_loss of that sequence).  Of exactly equal scores the order is: a prefix
+    that stayed before one that grew, then the parent's rank, then the label; NaN and -inf are never chosen.  Slots
+    without a hypothesis -- fewer than nbest prefixes, a frame with nothing above -inf, an utterance without frames --
+    get -1, length 0 and score -inf.  Runs on the caller's stream; no autograd."""
+    if log_probs.dim() != 3 or log_probs.dtype != torch.float32:
+        raise ValueError("ctc_beam_decode: log_probs must be a float32 tensor [B, T, C]")
+    B, T, N = log_probs.shape
+    blank, beam_size, cutoff_top_n, nbest = int(blank), int(beam_size), int(cutoff_top_n), int(nbest)
+    if not 0 <= blank < N:
+        raise ValueError(f"ctc_beam_decode: blank must be one of the {N} labels")
+    if not 1 <= beam_size <= 64:
+        raise ValueError("ctc_beam_decode: beam_size outside 1 .. 64")
+    if not 1 <= cutoff_top_n <= 32:
+        raise ValueError("ctc_beam_decode: cutoff_top_n outside 1 .. 32")
+    if not 1 <= nbest <= beam_size:
+        raise ValueError("ctc_beam_decode: nbest outside 1 .. beam_size")
+    frames = None if input_lengths is None else _frame_counts("ctc_beam_decode", input_lengths, B, T, 0)
+    if not log_probs.is_cuda:
+        raise RuntimeError("ctc_beam_decode: log_probs must be a CUDA tensor (the search runs on the device)")
+    x = log_probs.detach().contiguous()
+    stream = torch.cuda.current_stream(x.device)
+    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
+    if not stream.cuda_stream:
+        stream.synchronize()  # engine runs on its own stream
+    tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=x.device)
+    lengths = torch.empty(B, nbest, dtype=torch.int32, device=x.device)
+    scores = torch.empty(B, nbest, dtype=torch.float32, device=x.device)
+    lib = _native()
+    if lib:
+        if not hasattr(lib, "gtn_ctc_beam_decode_n"):
+            raise RuntimeError("ctc_beam_decode needs gtn_ctc_beam_decode_n in gtn_amd/lib/libgtn_criteria.so "
+                               "(run __graft_entry__.build())")
+        rc = lib.gtn_ctc_beam_decode_n(x.data_ptr(), B, T, N, blank, frames.ctypes.data if frames is not None else None,
+                                       beam_size, cutoff_top_n, nbest, tokens.data_ptr(), lengths.data_ptr(),
+                                       scores.data_ptr())
+        if rc != 0:
+            raise RuntimeError(lib.gtn_criteria_last_error().decode())
+    else:
+        ems = gtn.Batch.linear(B, T, N, x, calc_grad=False, borrow=True)
+        ems.ctc_beam_decode(tokens, lengths, scores, frames, blank, beam_size, cutoff_top_n, nbest, row_stride=T)
+    if not stream.cuda_stream:
+        gtn.synchronize()
+    return tokens, lengths, scores

@@ -186,6 +186,18 @@ inline void linearDecode(const Batch& ems, int* labelsDevice, int64_t rowStride,
   detail::check(gtnx_batch_linear_decode(ems.handle(), frames, blank, labelsDevice, rowStride, scoresDevice,
                                          collapsedDevice, startsDevice, lengthsDevice));
 }
+/** CTC prefix beam search with N-best output over a Batch::linear, results left on the device: tokensDevice int32
+ *  [n][nbest][rowStride] (the labels of hypothesis r, then -1 up to the row's width M), lengthsDevice int32 [n][nbest],
+ *  scoresDevice float32 [n][nbest] (the log score summed over the alignments the beam kept); slots without a hypothesis:
+ *  -1, 0, -inf.  beamSize 1 .. 64 prefixes, the cutoffTopN (1 .. 32) best labels of a frame plus blank, nbest <=
+ *  beamSize; frames (host, [n]): T_b, null = the rows the batch carries.  Two launches, no copy back, no wait, rows from
+ *  T_b on are never read -- gtnx_batch_ctc_beam_decode */
+inline void ctcBeamDecode(const Batch& ems, int* tokensDevice, int64_t rowStride, int* lengthsDevice, float* scoresDevice,
+                          int blank = 0, int beamSize = 16, int cutoffTopN = 16, int nbest = 1,
+                          const int* frames = nullptr) {
+  detail::check(gtnx_batch_ctc_beam_decode(ems.handle(), frames, blank, beamSize, cutoffTopN, nbest, tokensDevice,
+                                           rowStride, lengthsDevice, scoresDevice));
+}
 inline void backward(const Batch& a, bool retainGraph = false) { detail::check(gtnx_batch_backward(a.handle(), retainGraph)); }
 } // namespace batched
 

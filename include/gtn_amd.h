@@ -370,6 +370,33 @@ gtnx_status_t gtnx_batch_linear_decode(gtnx_batch_t ems, const int* frames, int 
                                        void* starts_device, void* lengths_device);
 /* utterances decoded so far (process-wide) by the launches / by the path-graph route */
 gtnx_status_t gtnx_batch_linear_decode_stats(int64_t* fast, int64_t* fallback);
+/* CTC prefix beam search with N-best output over a whole batch of chains, results left on the device: the best LABEL
+ * SEQUENCES, summed over their alignments, where gtnx_batch_linear_decode gives the best alignment.  Per frame the
+ * token set is the cutoff_top_n best labels of the row (value descending, of equal values the smaller label; NaN and
+ * -inf are never chosen) plus `blank` where its entry is above -inf; the state is at most beam_size distinct prefixes
+ * with the log scores (pb, pnb) of their alignments that end / do not end in blank, starting from the empty prefix with
+ * (0, -inf); a frame gives every prefix a stay candidate and one extension per non-blank member of the set, an
+ * extension that is a prefix of the list already is added into that prefix (exact prefix identity, not hashed), and
+ * the first beam_size candidates by (total descending, stay before extension, parent's rank, label) are the new list.
+ * log-add is m + log1p(exp(n - m)) in float32 (DESIGN section 20 has the whole contract; unpruned, a hypothesis's score
+ * is forwardScore(ctcTarget(y) intersected with emissions_b)).
+ * tokens_device: int32 [n][nbest][row_stride], row_stride >= M: the labels of hypothesis r, -1 from its length to M;
+ * lengths_device: int32 [n][nbest]; scores_device: float32 [n][nbest].  Slots without a hypothesis -- fewer than nbest
+ * prefixes, a frame without anything above -inf, T_b = 0 (linearGraph(0, C) does not accept) -- get -1, 0 and -inf.
+ * frames (host, [n], or null): T_b; null means the rows the batch carries.  Rows from T_b on are never read.
+ * GTNX_INVALID_ARGUMENT before a device is asked for: a null batch or output pointer, a negative stride, beam_size
+ * outside 1 .. 64, cutoff_top_n outside 1 .. 32, nbest outside 1 .. beam_size, a negative blank.  With the device: ems is
+ * not a gtnx_batch_linear / _rows batch (there is no other route), a count outside 0 .. M or above the rows the batch
+ * carries, row_stride < M, blank >= C, more than 2^25 labels, outputs the engine's current device may not write.
+ * Two launches on the engine's stream (ctc_beam.hip), scratch from the stream-ordered pool, nothing is copied back
+ * and the call does not wait for the device. */
+gtnx_status_t gtnx_batch_ctc_beam_decode(gtnx_batch_t ems, const int* frames, int blank, int beam_size,
+                                         int cutoff_top_n, int nbest, void* tokens_device, int64_t row_stride,
+                                         void* lengths_device, void* scores_device);
+/* calls that have launched so far (process-wide) / utterances they decoded */
+gtnx_status_t gtnx_batch_ctc_beam_stats(int64_t* calls, int64_t* utterances);
+/* rows M and labels C of the slabs of a gtnx_batch_linear / _rows batch; -1, -1 for any other batch */
+gtnx_status_t gtnx_batch_linear_shape(gtnx_batch_t ems, int* rows, int* labels);
 gtnx_status_t gtnx_batch_backward(gtnx_batch_t a, int retain_graph);                  /* autograd.cpp:17-67 */
 gtnx_status_t gtnx_batch_items(gtnx_batch_t a, float* out);                           /* graph.h:143, n floats */
 gtnx_status_t gtnx_batch_items_device(gtnx_batch_t a, void* device_out);

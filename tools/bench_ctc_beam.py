@@ -1,0 +1,211 @@
+"""CTC prefix beam search with N-best output on the device at BASELINE config C3's shape (B = 512, T = 1000, C = 256),
+beam_size 16, cutoff_top_n 16, nbest 1, beside the greedy decode of the same tensor.
+
+  beam    Batch.ctc_beam_decode: two launches (ctc_beam_rows_kernel, ctc_beam_search_kernel), tokens / lengths /
+          scores written into the caller's tensors, no copy back
+  greedy  Batch.linear_decode on the same tensor in the same process: its row kernel is the pure stream the beam
+          search's row kernel adds the top-K rounds to
+
+There is no route for this call on the previous commit, so there is nothing to alternate with and no speed-up to
+claim.
+
+    python tools/bench_ctc_beam.py [--out profiles/ctc_beam_c3.json]
+        three samples, every sample a process of its own that warms its shapes up and then times windows of at least
+        half a second with a host clock around a closing synchronise, for `beam` and for `greedy`
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_ctc_beam.py --worker trace
+        a few calls of both, for the mean times of the kernels (a run of its own: no counters, no other tracing);
+        with --beam W --topn K the trace runs at another beam_size / cutoff_top_n (the search kernel's time against
+        the number of candidates per frame: what a frame costs when there is next to nothing to rank);
+    python tools/bench_ctc_beam.py --merge-stats DIR/.../kernel_stats.csv [--beam W --topn K] [--out ...]
+        adds those means to the record: the row kernel beside linear_decode_rows_kernel and as a fraction of its own
+        byte model (4 C in, 8 (K + 1) + 4 out per row) at the stream rate, the search kernel per batch and per frame.
+
+Needs a GPU; a measurement path that finds none fails.
+"""
+import argparse
+import csv
+import json
+import os
+import subprocess
+import sys
+import time
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+STREAM_GBS = 6300.0  # the achievable HBM stream rate the floor is derived from
+B, T, C = 512, 1000, 256
+BLANK, BEAM, TOPN, NBEST = 0, 16, 16, 1
+WINDOW_S = 0.5
+
+
+def inputs(torch):
+    """log-softmax of seeded normals with a blank that wins about half of the frames, in runs"""
+    g = torch.Generator(device="cuda")
+    g.manual_seed(1234)
+    em = torch.randn((B, T, C), generator=g, device="cuda", dtype=torch.float32) * 3.0
+    em[:, :, BLANK] += (torch.rand((B, T // 8 + 1, 1), generator=g, device="cuda") < 0.5).repeat_interleave(
+        8, dim=1)[:, :T, 0] * 12.0
+    return torch.log_softmax(em, dim=2).contiguous()
+
+
+def byte_model():
+    """(rows kernel, search kernel): 4 C in and 8 (K + 1) + 4 out per row; those back in, at most a trie node per beam
+    and frame, the output rows"""
+    rows = float(B) * T * (4.0 * C + 8.0 * (TOPN + 1) + 4.0)
+    search = float(B) * (T * (8.0 * (TOPN + 1) + 4.0 + 8.0 * BEAM) + NBEST * (4.0 * T + 8.0))
+    return rows, search
+
+
+def worker(kind, beam=BEAM, topn=TOPN):
+    sys.path.insert(0, HERE)
+    import torch
+    import gtn_amd as gtn
+    assert torch.cuda.is_available() and gtn.device_count() > 0, "bench_ctc_beam needs a GPU"
+    em = inputs(torch)
+    tokens = torch.empty((B, NBEST, T), dtype=torch.int32, device="cuda")
+    lengths = torch.empty((B, NBEST), dtype=torch.int32, device="cuda")
+    scores = torch.empty((B, NBEST), dtype=torch.float32, device="cuda")
+    labels = torch.empty((B, T), dtype=torch.int32, device="cuda")
+    gtok = torch.empty((B, T), dtype=torch.int32, device="cuda")
+    gsta = torch.empty((B, T), dtype=torch.int32, device="cuda")
+    gsc = torch.empty((B,), dtype=torch.float32, device="cuda")
+    glen = torch.empty((B,), dtype=torch.int32, device="cuda")
+
+    def beam_step():
+        ems = gtn.Batch.linear(B, T, C, em, False, True)
+        ems.ctc_beam_decode(tokens, lengths, scores, None, BLANK, beam, topn, NBEST)
+
+    def greedy_step():
+        ems = gtn.Batch.linear(B, T, C, em, False, True)
+        ems.linear_decode(labels, gsc, None, BLANK, gtok, gsta, glen)
+
+    def sync():
+        gtn.synchronize()
+        torch.cuda.synchronize()
+
+    def timed(step):
+        for _ in range(3):
+            step()
+        sync()
+        n, t0 = 0, time.perf_counter()
+        while True:
+            step()
+            sync()
+            n += 1
+            dt = time.perf_counter() - t0
+            if dt >= WINDOW_S:
+                return dt / n * 1e3, n
+
+    if kind == "trace":
+        for _ in range(5):
+            beam_step()
+            greedy_step()
+            sync()
+        print(json.dumps({"trace": "done"}))
+        return
+    c0 = gtn.debug_ctc_beam_stats()
+    ms, n = timed(beam_step if kind == "beam" else greedy_step)
+    sync()
+    c1 = gtn.debug_ctc_beam_stats()
+    rec = {"kind": kind, "utterances": B, "ms_per_batch": ms, "iters": n, "beam_utterances": c1[1] - c0[1]}
+    if kind == "beam":
+        rec["mean_length"] = float(lengths.float().mean().item())
+        rec["mean_score"] = float(scores.mean().item())
+        beam_step()
+        greedy_step()
+        sync()
+        # the summed score of the best label sequence is at least the score of the best alignment (up to rounding)
+        rec["beam_score_minus_greedy_score_min"] = float((scores[:, 0] - gsc).min().item())
+    print(json.dumps(rec))
+
+
+def run_worker(kind):
+    env = dict(os.environ)
+    env.pop("PYTHONPATH", None)
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", kind], env=env,
+                         stdout=subprocess.PIPE, timeout=500, check=True).stdout.decode()
+    rec = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+    print(f"[bench_ctc_beam] {kind}: {rec['ms_per_batch']:.3f} ms per batch of {rec['utterances']}", file=sys.stderr,
+          flush=True)
+    return rec
+
+
+def spread(v):
+    return {"samples": v, "min": min(v), "max": max(v), "median": sorted(v)[len(v) // 2]}
+
+
+KERNELS = ("ctc_beam_rows_kernel", "ctc_beam_search_kernel", "linear_decode_rows_kernel",
+           "linear_decode_collapse_kernel")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--worker", choices=["beam", "greedy", "trace"])
+    ap.add_argument("--merge-stats")
+    ap.add_argument("--beam", type=int, default=BEAM)
+    ap.add_argument("--topn", type=int, default=TOPN)
+    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "ctc_beam_c3.json"))
+    a = ap.parse_args()
+    if a.worker:
+        worker(a.worker, a.beam, a.topn)
+        return
+    rec = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            rec = json.load(f)
+    rows_bytes, search_bytes = byte_model()
+    if a.merge_stats and (a.beam, a.topn) != (BEAM, TOPN):
+        with open(a.merge_stats) as f:
+            for row in csv.DictReader(f):
+                if "ctc_beam_search_kernel" in row["Name"]:
+                    ms = float(row["AverageNs"]) * 1e-6
+                    rec.setdefault("search_kernel_by_setting", {})[f"beam_size {a.beam}, cutoff_top_n {a.topn}"] = {
+                        "ms_per_batch": ms, "us_per_frame_of_the_batch": ms * 1e3 / T,
+                        "candidates_per_frame_at_most": a.beam + a.beam * a.topn}
+                if "ctc_beam_rows_kernel" in row["Name"]:
+                    rec.setdefault("rows_kernel_by_setting", {})[f"cutoff_top_n {a.topn}"] = float(row["AverageNs"]) * 1e-6
+    elif a.merge_stats:
+        means = {}
+        with open(a.merge_stats) as f:
+            for row in csv.DictReader(f):
+                for key in KERNELS:
+                    if key in row["Name"]:
+                        means[key] = {"calls": int(row["Calls"]), "mean_ms": float(row["AverageNs"]) * 1e-6,
+                                      "min_ms": float(row["MinNs"]) * 1e-6, "max_ms": float(row["MaxNs"]) * 1e-6}
+        rec["kernels"] = means
+        k, sib = means.get("ctc_beam_rows_kernel"), means.get("linear_decode_rows_kernel")
+        if k:
+            gbs = rows_bytes / (k["mean_ms"] * 1e-3) / 1e9
+            rec["rows_kernel_on_its_byte_model"] = {
+                "achieved_GBs": gbs, "stream_rate_GBs": STREAM_GBS, "frac": gbs / STREAM_GBS,
+                "floor_ms": rows_bytes / (STREAM_GBS * 1e9) * 1e3, "bytes": "(4 C + 8 (K + 1) + 4) per row"}
+            if sib:
+                rec["rows_kernel_over_linear_decode_rows_kernel"] = k["mean_ms"] / sib["mean_ms"]
+        k = means.get("ctc_beam_search_kernel")
+        if k:
+            rec["search_kernel"] = {"ms_per_batch": k["mean_ms"], "us_per_frame_of_the_batch": k["mean_ms"] * 1e3 / T,
+                                    "workgroups": B, "achieved_GBs": search_bytes / (k["mean_ms"] * 1e-3) / 1e9}
+    else:
+        be, gr, last = [], [], None
+        for _ in range(3):
+            last = run_worker("beam")
+            assert last["beam_utterances"] > 0, last
+            be.append(last["ms_per_batch"])
+            gr.append(run_worker("greedy")["ms_per_batch"])
+        rec.update({"shape": {"B": B, "T": T, "C": C, "blank": BLANK, "beam_size": BEAM, "cutoff_top_n": TOPN,
+                              "nbest": NBEST},
+                    "unit": "ms per batch, host clock around a closing synchronise, windows >= 0.5 s",
+                    "beam": dict(spread(be), what="Batch.ctc_beam_decode (tokens, lengths, scores)", utterances=B),
+                    "greedy": dict(spread(gr), what="Batch.linear_decode on the same tensor (all five outputs)",
+                                   utterances=B),
+                    "rows_bytes": rows_bytes, "search_bytes": search_bytes,
+                    "mean_length": last["mean_length"], "mean_score": last["mean_score"],
+                    "beam_score_minus_greedy_score_min": last["beam_score_minus_greedy_score_min"]})
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+
+
+if __name__ == "__main__":
+    main()
