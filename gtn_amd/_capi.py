@@ -137,6 +137,9 @@ _SIGS = {
                                    C.c_void_p, C.c_void_p],
     "gtnx_batch_ctc_beam_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_linear_shape": [c_graph, c_i32_p, c_i32_p],
+    "gtnx_batch_edit_distance": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int,
+                                 C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "gtnx_batch_edit_distance_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_backward": [c_graph, C.c_int],
     "gtnx_batch_items": [c_graph, C.c_void_p],
     "gtnx_batch_items_device": [c_graph, C.c_void_p],

@@ -1020,6 +1020,84 @@ def make_api(lib):
         check(lib.gtnx_batch_ctc_beam_stats(C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def debug_edit_distance_stats():
+        """(calls, pairs): calls of edit_distance that have launched so far and the pairs they computed
+        (include/gtn_amd.h: gtnx_batch_edit_distance_stats)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(lib.gtnx_batch_edit_distance_stats(C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def edit_distance(hyp, hyp_lengths, ref, ref_lengths, dist_out, ops_out=None, B=None, N=None, L=None, U=None,
+                      hyp_stride=None, ref_stride=None):
+        """Levenshtein distance (unit costs) of all B * N pairs (hyp[b, k], ref[b]) of token rows on the device, results
+        left on the device (gtnx_batch_edit_distance; DESIGN section 21 holds the contract).  `hyp`: int32 CUDA tensor
+        [B, N, L] or [B, L] (then N = 1) with contiguous, equally spaced rows, or a device address with B, N, L and
+        hyp_stride (elements between rows, >= L); `hyp_lengths`: int32 [B, N], contiguous; `ref`: int32 [B, U] with
+        contiguous rows, or an address with U and ref_stride; `ref_lengths`: int32 [B].  The lengths stay on the device:
+        the kernel clamps them to 0 .. L / 0 .. U and reads nothing at or past them; tokens are compared with == only.
+        `dist_out`: int32 [B, N]; `ops_out`: int32 [B, N, 3] = (substitutions, deletions, insertions) of the walk back
+        that prefers the diagonal, then up (a deletion: a reference token without counterpart), then left (an
+        insertion), or None: then nothing is kept for the walk and the call is one launch.  L <= 65536, U <= 4096.  No
+        copy back and no wait."""
+        dims = {"B": B, "N": N, "L": L, "U": U}
+
+        def settle(name, value):
+            if dims[name] is not None and int(dims[name]) != int(value):
+                raise ValueError(f"edit_distance: {name} = {dims[name]} is not what the tensors say ({value})")
+            dims[name] = int(value)
+
+        tensors = []
+        if hasattr(hyp, "data_ptr"):
+            if str(hyp.dtype) != "torch.int32" or hyp.dim() not in (2, 3):
+                raise ValueError("edit_distance: hyp must be an int32 tensor [B, N, L] or [B, L]")
+            h = hyp if hyp.dim() == 3 else hyp.unsqueeze(1)
+            settle("B", h.shape[0]), settle("N", h.shape[1]), settle("L", h.shape[2])
+            rows = h.stride(1) if h.shape[1] > 1 else (h.stride(0) if h.shape[0] > 1 else max(h.shape[2], 1))
+            if ((h.shape[2] > 1 and h.stride(2) != 1)
+                    or (h.shape[0] > 1 and h.shape[1] > 1 and h.stride(0) != h.shape[1] * h.stride(1))):
+                raise ValueError("edit_distance: hyp must have contiguous rows, equally spaced")
+            if hyp_stride is not None and int(hyp_stride) != rows:
+                raise ValueError("edit_distance: hyp_stride is not the row stride of hyp")
+            hyp_stride = rows
+            tensors.append(("hyp", hyp))
+        if hasattr(ref, "data_ptr"):
+            if str(ref.dtype) != "torch.int32" or ref.dim() != 2:
+                raise ValueError("edit_distance: ref must be an int32 tensor [B, U]")
+            settle("B", ref.shape[0]), settle("U", ref.shape[1])
+            rows = ref.stride(0) if ref.shape[0] > 1 else max(ref.shape[1], 1)
+            if ref.shape[1] > 1 and ref.stride(1) != 1:
+                raise ValueError("edit_distance: ref must have contiguous rows")
+            if ref_stride is not None and int(ref_stride) != rows:
+                raise ValueError("edit_distance: ref_stride is not the row stride of ref")
+            ref_stride = rows
+            tensors.append(("ref", ref))
+        for name in ("B", "N", "L", "U"):
+            if dims[name] is None:
+                raise ValueError(f"edit_distance: a device address needs {name}")
+        if hyp_stride is None or ref_stride is None:
+            raise ValueError("edit_distance: a device address needs hyp_stride / ref_stride")
+        b, n, l, u = (dims[k] for k in ("B", "N", "L", "U"))
+        for o, count, what in ((hyp_lengths, b * n, "hyp_lengths must be an int32 contiguous tensor [B, N]"),
+                               (ref_lengths, b, "ref_lengths must be an int32 contiguous tensor [B]"),
+                               (dist_out, b * n, "dist_out must be an int32 contiguous tensor [B, N]"),
+                               (ops_out, 3 * b * n, "ops_out must be an int32 contiguous tensor [B, N, 3]")):
+            if o is not None and hasattr(o, "data_ptr"):
+                if str(o.dtype) != "torch.int32" or not o.is_contiguous() or o.numel() != count:
+                    raise ValueError(f"edit_distance: {what}")
+                tensors.append((what.split()[0], o))
+        for name, t in tensors:  # (a host tensor's address means nothing to the kernel)
+            if hasattr(t, "is_cuda") and not t.is_cuda:
+                raise ValueError(f"edit_distance: {name} must be a CUDA tensor")
+
+        if b * n == 0 and tensors:
+            return  # (no pair, nothing to launch -- and an empty tensor has no address to hand to the engine)
+
+        def addr(x):
+            return _as_dev_ptr(x) if x is not None else None
+
+        check(lib.gtnx_batch_edit_distance(addr(hyp), int(hyp_stride), addr(hyp_lengths), addr(ref), int(ref_stride),
+                                           addr(ref_lengths), b, n, l, u, addr(dist_out), addr(ops_out)))
+
     def debug_full_connect_stats():
         """(fast, fallback): utterances whose ASG full-connect score forward_score(compose(Batch.linear(rows=...),
         transitions)) came from the one launch of asg_full.hip / utterances of such a padded batch that took the composed
@@ -1034,6 +1112,8 @@ def make_api(lib):
     ns.debug_decode_stats = debug_decode_stats
     ns.debug_linear_decode_stats = debug_linear_decode_stats
     ns.debug_ctc_beam_stats = debug_ctc_beam_stats
+    ns.debug_edit_distance_stats = debug_edit_distance_stats
+    ns.edit_distance = edit_distance
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties
 

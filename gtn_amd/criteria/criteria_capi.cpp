@@ -9,6 +9,7 @@
 
 #include "asg_criterion.h"
 #include "ctc_criterion.h"
+#include "edit_distance.h"
 
 namespace {
 thread_local std::string g_err;
@@ -90,6 +91,22 @@ extern "C" __attribute__((visibility("default"))) int gtn_ctc_beam_decode_n(cons
   try {
     gtn::criteria::ctcBeamDecodeBatch(emissions, B, T, C, blank, frames, beam_size, cutoff_top_n, nbest, tokens, lengths,
                                       scores);
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
+// Edit distance of all B * N pairs (hyp[b][k], ref[b]).  hyp: DEVICE int32 [B][N][L]; hyp_lengths: DEVICE int32 [B][N];
+// ref: DEVICE int32 [B][U]; ref_lengths: DEVICE int32 [B]; dist: DEVICE int32 [B][N]; ops: DEVICE int32 [B][N][3] or
+// null.  Returns 0, or -1 with the message in gtn_criteria_last_error().
+extern "C" __attribute__((visibility("default"))) int gtn_edit_distance_n(const void* hyp, const void* hyp_lengths,
+                                                                          const void* ref, const void* ref_lengths,
+                                                                          int B, int N, int L, int U, void* dist,
+                                                                          void* ops) {
+  try {
+    gtn::criteria::editDistanceBatch(hyp, hyp_lengths, ref, ref_lengths, B, N, L, U, dist, ops);
     return 0;
   } catch (const std::exception& e) {
     g_err = e.what();

@@ -1696,6 +1696,91 @@ void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int 
 }
 
 
+// ---- batched edit distance of device-resident token rows (edit_distance.hip) ----
+namespace {
+std::atomic<int64_t> g_edit_distance_calls{0}, g_edit_distance_pairs{0};
+// what the walk's scratch of ONE launch may take; a call that needs more runs its pairs in slices of launches.  A pair
+// at the largest widths takes 64 MiB, so a slice always holds at least one pair.
+constexpr int64_t kEditDistanceScratchCap = int64_t(256) << 20;
+int64_t edit_distance_scratch_cap() {
+  // (debug switch, read per call: tests lower the cap to see a sliced call without allocating gigabytes)
+  const char* e = std::getenv("GTNX_EDIT_DISTANCE_SCRATCH_BYTES");
+  if (e && *e) {
+    const long long v = std::atoll(e);
+    if (v > 0) return std::min<int64_t>(v, kEditDistanceScratchCap);
+  }
+  return kEditDistanceScratchCap;
+}
+}  // namespace
+
+void batch_edit_distance_stats(int64_t* calls, int64_t* pairs) {
+  if (calls) *calls = g_edit_distance_calls.load();
+  if (pairs) *pairs = g_edit_distance_pairs.load();
+}
+
+void batch_edit_distance(const int* hyp_dev, int64_t hyp_stride, const int* hyp_len_dev, const int* ref_dev,
+                         int64_t ref_stride, const int* ref_len_dev, int B, int N, int L, int U, int* dist_dev,
+                         int* ops_dev) {
+  GTNX_HOST_T("batch.edit_distance");
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!hyp_dev || !hyp_len_dev || !ref_dev || !ref_len_dev)
+    throw_invalid("[gtnx_batch_edit_distance] null input pointer (hyp, hyp_lengths, ref and ref_lengths are all read)");
+  if (!dist_dev) throw_invalid("[gtnx_batch_edit_distance] null dist pointer");
+  if (B < 0 || N < 0 || L < 0 || U < 0) throw_invalid("[gtnx_batch_edit_distance] negative B, N, L or U");
+  if (hyp_stride < 0 || ref_stride < 0) throw_invalid("[gtnx_batch_edit_distance] negative row stride");
+  if (hyp_stride < L) throw_invalid("[gtnx_batch_edit_distance] hyp_stride is shorter than the rows' width L");
+  if (ref_stride < U) throw_invalid("[gtnx_batch_edit_distance] ref_stride is shorter than the rows' width U");
+  // (the carries of a row of columns and the reference live in LDS; a lane of the wave owns one block of 64 rows)
+  if (L > kEditDistanceMaxL) throw_invalid("[gtnx_batch_edit_distance] L above 65536");
+  if (U > kEditDistanceMaxU) throw_invalid("[gtnx_batch_edit_distance] U above 4096");
+  const int64_t pairs = int64_t(B) * N;
+  if (pairs > std::numeric_limits<int>::max()) throw_invalid("[gtnx_batch_edit_distance] B times N does not fit an int");
+  if (pairs == 0) return;
+  Runtime& rt = Runtime::get();
+  // a kernel of this device writes the results: memory of another GPU of the process is refused, not written
+  if (!ptr_local_to(dist_dev, rt.device()) || (ops_dev && !ptr_local_to(ops_dev, rt.device())))
+    throw_invalid("[gtnx_batch_edit_distance] an output pointer is not memory of the engine's current device");
+  const int nbU = (U + 63) / 64;
+  EditDistanceArgs a{};
+  a.hyp = hyp_dev;
+  a.hyp_len = hyp_len_dev;
+  a.ref = ref_dev;
+  a.ref_len = ref_len_dev;
+  a.dist = dist_dev;
+  a.ops = ops_dev;
+  a.hyp_stride = hyp_stride;
+  a.ref_stride = ref_stride;
+  a.N = N;
+  a.L = L;
+  a.U = U;
+  a.nbU = nbU;
+  // algorithmic bytes, by the widths (the lengths are device memory: an upper bound): every token and length once, the
+  // distance out; with ops the (Pv, Mv) words of every (column, block) out and back in, and the three counts
+  const double io_bytes = double(pairs) * (4.0 * L + 8.0) + double(B) * (4.0 * U + 4.0);
+  if (!ops_dev) {
+    a.pair0 = 0;
+    a.count = int(pairs);
+    GTNX_PROF("edit_distance", io_bytes);
+    launch_edit_distance(a, rt.stream());
+  } else {
+    const int64_t per_pair = int64_t(16) * L * nbU;
+    const int64_t slice = per_pair > 0 ? std::max<int64_t>(1, edit_distance_scratch_cap() / per_pair) : pairs;
+    for (int64_t p0 = 0; p0 < pairs; p0 += slice) {
+      const int64_t cnt = std::min(slice, pairs - p0);
+      DevMemP words = rt.alloc(size_t(std::max<int64_t>(per_pair * cnt, 16)));
+      a.scratch = words->as<gtnx_ul2>();
+      a.pair0 = p0;
+      a.count = int(cnt);
+      GTNX_PROF("edit_distance_ops", (io_bytes / double(pairs) + 2.0 * double(per_pair) + 12.0) * double(cnt));
+      launch_edit_distance(a, rt.stream());
+      // (the words go back to the stream-ordered pool behind the launch)
+    }
+  }
+  g_edit_distance_calls.fetch_add(1);
+  g_edit_distance_pairs.fetch_add(pairs);
+}
+
+
 namespace {
 // a GRAPHS batch of one-arc graphs as a native SCALAR batch (values gathered; backward continues on the graphs' tape)
 BatchP scalars_from_graphs(const BatchP& gsb) {

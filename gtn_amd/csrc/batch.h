@@ -183,6 +183,22 @@ void batch_linear_decode_stats(int64_t* fast, int64_t* fallback);  // utterances
 void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int beam, int topn, int nbest,
                            int* tokens_dev, int64_t row_stride, int* lengths_dev, float* scores_dev);
 void batch_ctc_beam_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they decoded
+// Levenshtein distance (unit costs) of all B * N pairs (hyp[b, k], ref[b]) of device-resident token rows, results on the
+// device (DESIGN section 21 holds the contract).  hyp_dev: int32 [B][N] rows of width L, hyp_stride elements apart;
+// hyp_len_dev: int32 [B][N]; ref_dev: int32 [B] rows of width U, ref_stride apart; ref_len_dev: int32 [B] -- lengths
+// are DEVICE memory, clamped to 0 .. L / 0 .. U by the kernel, and nothing at or past a clamped length is read.  Tokens
+// are compared with == only.  dist_dev[b * N + k]; ops_dev (or null) [b * N + k][3] = (substitutions, deletions,
+// insertions) of the walk back from (len_ref, len_hyp) that takes the first move attaining D[i][j] of diagonal, up
+// (deletion), left (insertion).  Invalid argument before a device is asked for: a null input or dist pointer, negative
+// B, N, L, U or stride, a stride below its width, L > 65536, U > 4096, B * N beyond an int; B * N == 0 returns without
+// a device.  With the device: an output that is not memory of the current device.  Without ops one launch; with ops
+// the walk's scratch (16 bytes * L * ceil(U / 64) per pair, from the stream-ordered pool) is capped at 256 MiB per
+// launch (GTNX_EDIT_DISTANCE_SCRATCH_BYTES lowers the cap: a debug switch) and the pairs run in slices of launches.
+// No download, no wait.
+void batch_edit_distance(const int* hyp_dev, int64_t hyp_stride, const int* hyp_len_dev, const int* ref_dev,
+                         int64_t ref_stride, const int* ref_len_dev, int B, int N, int L, int U, int* dist_dev,
+                         int* ops_dev);
+void batch_edit_distance_stats(int64_t* calls, int64_t* pairs);  // calls that launched / pairs they computed
 // items_dev (optional): device memory of the CALLER's that the n result values are written into directly (borrowed: it
 // must outlive the result); a later batch_items_device to the same address copies nothing
 BatchP batch_scalar(ScalarKind k, const BatchP& a, const BatchP& b, void* items_dev = nullptr);

@@ -910,6 +910,19 @@ GTNX_API gtnx_status_t gtnx_batch_ctc_beam_decode(gtnx_batch_t ems, const int* f
 GTNX_API gtnx_status_t gtnx_batch_ctc_beam_stats(int64_t* calls, int64_t* utterances) {
   return guard([&] { batch_ctc_beam_stats(calls, utterances); });
 }
+GTNX_API gtnx_status_t gtnx_batch_edit_distance(const void* hyp_device, int64_t hyp_stride,
+                                                const void* hyp_lengths_device, const void* ref_device,
+                                                int64_t ref_stride, const void* ref_lengths_device, int B, int N, int L,
+                                                int U, void* dist_device, void* ops_device) {
+  return guard([&] {
+    batch_edit_distance(static_cast<const int*>(hyp_device), hyp_stride, static_cast<const int*>(hyp_lengths_device),
+                        static_cast<const int*>(ref_device), ref_stride, static_cast<const int*>(ref_lengths_device), B,
+                        N, L, U, static_cast<int*>(dist_device), static_cast<int*>(ops_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_edit_distance_stats(int64_t* calls, int64_t* pairs) {
+  return guard([&] { batch_edit_distance_stats(calls, pairs); });
+}
 GTNX_API gtnx_status_t gtnx_batch_linear_shape(gtnx_batch_t ems, int* rows, int* labels) {
   return guard([&] {
     const BatchP& b = BH(ems);

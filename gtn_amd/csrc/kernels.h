@@ -849,6 +849,29 @@ struct CtcBeamArgs {
   int n, M, C, blank, beam, topn, nbest;
 };
 void launch_ctc_beam(const CtcBeamArgs& a, int which, hipStream_t st);
+// edit_distance.hip: Levenshtein distance (unit costs) of the pairs pair0 .. pair0 + count - 1, pair p = b * N + k being
+// (hyp + p * hyp_stride, hyp_len[p]) against (ref + b * ref_stride, ref_len[b]) -- one launch, one wave per pair, Myers'
+// bit-vector recurrence in Hyyro's block form with the wave as the 64-bit word (the contract: DESIGN section 21).
+// Lengths are device memory, clamped to 0 .. L / 0 .. U by the kernel; nothing at or past a clamped length is read.
+// dist[p]; with ops non-null also ops[3 p ..] = (substitutions, deletions, insertions) of the walk back that prefers
+// diagonal, then up, then left, from (Pv, Mv) of every (column, block) kept in scratch: 16 bytes * count * L * nbU.
+// L <= kEditDistanceMaxL, U <= kEditDistanceMaxU (one block per lane; the engine has refused the rest).
+constexpr int kEditDistanceMaxL = 65536;
+constexpr int kEditDistanceMaxU = 4096;
+typedef unsigned long long gtnx_ul2 __attribute__((ext_vector_type(2)));
+struct EditDistanceArgs {
+  const GTNX_G int* hyp;
+  const GTNX_G int* hyp_len;  // [pairs]
+  const GTNX_G int* ref;
+  const GTNX_G int* ref_len;  // [pairs / N]
+  GTNX_G int* dist;           // [pairs]
+  GTNX_G int* ops;            // [pairs][3] or null
+  GTNX_G gtnx_ul2* scratch;   // [count][L][nbU], with ops only
+  int64_t hyp_stride, ref_stride;
+  int64_t pair0;
+  int count, N, L, U, nbU;
+};
+void launch_edit_distance(const EditDistanceArgs& a, hipStream_t st);
 // materialise a KIND_LINEAR graph's arc arrays
 void launch_linear_materialize(int M, int C, int* src, int* dst, int* il, int* ol, hipStream_t st);
 

@@ -1,5 +1,5 @@
 """PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
-`asg_forced_align`, `asg_decode`, `ctc_decode` and `ctc_beam_decode`.
+`asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_beam_decode` and `edit_distance`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -60,6 +60,10 @@ def _native():
                 lib.gtn_ctc_beam_decode_n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                       C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
                 lib.gtn_ctc_beam_decode_n.restype = C.c_int
+            if hasattr(lib, "gtn_edit_distance_n"):
+                lib.gtn_edit_distance_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+                lib.gtn_edit_distance_n.restype = C.c_int
             _NATIVE = lib
         else:
             _NATIVE = False
@@ -587,3 +591,66 @@ def ctc_beam_decode(log_probs, blank=0, input_lengths=None, beam_size=16, cutoff
     if not stream.cuda_stream:
         gtn.synchronize()
     return tokens, lengths, scores
+
+
+def edit_distance(hyp, hyp_lengths, ref, ref_lengths, return_ops=False):
+    """Levenshtein distance of hypotheses against references, device-resident: one launch (with `return_ops`, one per
+    slice of pairs), nothing copied back -- `edit_distance(*ctc_beam_decode(...)[:2], ref, ref_lengths)` has no host
+    round trip, and a `min` over the nbest axis of the result is the oracle error count.
+    hyp: int32 CUDA tensor [B, N, L] (the `ctc_beam_decode` form) or [B, L] (the `ctc_decode` form); hyp_lengths: int32
+    or int64 CUDA tensor [B, N] / [B]; ref: int32 CUDA tensor [B, U]; ref_lengths: int32 or int64 CUDA tensor [B].
+    Lengths are read on the device and clamped to 0 .. L / 0 .. U there (a negative one counts as 0); elements at or
+    past a length are never read, so a slot without a hypothesis (length 0, tokens -1) scores the reference's length.
+    Tokens are compared with == only: any int32 is a token.  L <= 65536, U <= 4096.
+    Returns dist, int32 [B, N] (or [B] for a [B, L] hyp), on hyp.device: unit costs for substitution, insertion and
+    deletion.  With return_ops also ops, int32 [B, N, 3] (or [B, 3]) = (substitutions, deletions, insertions) of the
+    walk back from the last cell that takes the diagonal where it attains the distance, else up (a deletion: a
+    reference token without counterpart), else left (an insertion); they sum to dist.  Runs on the caller's stream;
+    no autograd."""
+    if not (torch.is_tensor(hyp) and hyp.dtype == torch.int32 and hyp.dim() in (2, 3)):
+        raise ValueError("edit_distance: hyp must be an int32 tensor [B, N, L] or [B, L]")
+    flat = hyp.dim() == 2
+    B, N, L = (hyp.shape[0], 1, hyp.shape[1]) if flat else hyp.shape
+    if not (torch.is_tensor(ref) and ref.dtype == torch.int32 and ref.dim() == 2 and ref.shape[0] == B):
+        raise ValueError(f"edit_distance: ref must be an int32 tensor [B, U] for a batch of {B}")
+    U = ref.shape[1]
+    for t, shape, what in ((hyp_lengths, (B,) if flat else (B, N), "hyp_lengths"), (ref_lengths, (B,), "ref_lengths")):
+        if not (torch.is_tensor(t) and t.dtype in (torch.int32, torch.int64) and tuple(t.shape) == tuple(shape)):
+            raise ValueError(f"edit_distance: {what} must be an int32 or int64 tensor {list(shape)}")
+    if L > 65536 or U > 4096:
+        raise ValueError("edit_distance: rows wider than the kernel takes (L <= 65536, U <= 4096)")
+    for t, what in ((hyp, "hyp"), (hyp_lengths, "hyp_lengths"), (ref, "ref"), (ref_lengths, "ref_lengths")):
+        if not t.is_cuda:
+            raise RuntimeError(f"edit_distance: {what} must be a CUDA tensor (the distances are computed on the device)")
+        if t.device != hyp.device:
+            raise ValueError("edit_distance: all tensors must be on one device")
+    h, r = hyp.detach().contiguous(), ref.detach().contiguous()
+    if B * N and h.numel() == 0:
+        h = h.new_empty(1)  # (rows without an element are never read, but an empty tensor has no address)
+    if B * N and r.numel() == 0:
+        r = r.new_empty(1)
+    hl = hyp_lengths.detach().to(torch.int32).contiguous()  # (int64 lengths are converted on the device)
+    rl = ref_lengths.detach().to(torch.int32).contiguous()
+    stream = torch.cuda.current_stream(h.device)
+    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
+    if not stream.cuda_stream:
+        stream.synchronize()  # engine runs on its own stream
+    dist = torch.empty(B, N, dtype=torch.int32, device=h.device)
+    ops = torch.empty(B, N, 3, dtype=torch.int32, device=h.device) if return_ops else None
+    lib = _native()
+    if B * N == 0:
+        pass  # (no pair: nothing to launch, and an empty tensor has no address to hand over)
+    elif lib and hasattr(lib, "gtn_edit_distance_n"):
+        rc = lib.gtn_edit_distance_n(h.data_ptr(), hl.data_ptr(), r.data_ptr(), rl.data_ptr(), B, N, L, U,
+                                     dist.data_ptr(), ops.data_ptr() if return_ops else None)
+        if rc != 0:
+            raise RuntimeError(lib.gtn_criteria_last_error().decode())
+    else:
+        gtn.edit_distance(h.data_ptr(), hl.data_ptr(), r.data_ptr(), rl.data_ptr(), dist.data_ptr(),
+                          ops.data_ptr() if return_ops else None, B=B, N=N, L=L, U=U, hyp_stride=L, ref_stride=U)
+    if not stream.cuda_stream:
+        gtn.synchronize()
+    if flat:
+        dist = dist.reshape(B)
+        ops = ops.reshape(B, 3) if return_ops else None
+    return (dist, ops) if return_ops else dist

@@ -198,6 +198,19 @@ inline void ctcBeamDecode(const Batch& ems, int* tokensDevice, int64_t rowStride
   detail::check(gtnx_batch_ctc_beam_decode(ems.handle(), frames, blank, beamSize, cutoffTopN, nbest, tokensDevice,
                                            rowStride, lengthsDevice, scoresDevice));
 }
+/** Levenshtein distance (unit costs) of all B * N pairs (hyp[b, k], ref[b]) of device-resident token rows, results left
+ *  on the device: hypDevice int32 B * N rows of width L, hypStride (>= L) apart, hypLengthsDevice int32 [B][N];
+ *  refDevice int32 B rows of width U, refStride (>= U) apart, refLengthsDevice int32 [B] -- the lengths are device
+ *  memory, clamped to the widths by the kernel, and nothing at or past a length is read; distDevice int32 [B][N];
+ *  opsDevice int32 [B][N][3] = (substitutions, deletions, insertions) of the walk back that prefers diagonal, then up,
+ *  then left, or null to skip it.  L <= 65536, U <= 4096.  One launch without ops; no copy back, no wait --
+ *  gtnx_batch_edit_distance */
+inline void editDistance(const int* hypDevice, int64_t hypStride, const int* hypLengthsDevice, const int* refDevice,
+                         int64_t refStride, const int* refLengthsDevice, int B, int N, int L, int U, int* distDevice,
+                         int* opsDevice = nullptr) {
+  detail::check(gtnx_batch_edit_distance(hypDevice, hypStride, hypLengthsDevice, refDevice, refStride, refLengthsDevice,
+                                         B, N, L, U, distDevice, opsDevice));
+}
 inline void backward(const Batch& a, bool retainGraph = false) { detail::check(gtnx_batch_backward(a.handle(), retainGraph)); }
 } // namespace batched
 

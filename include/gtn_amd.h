@@ -395,6 +395,33 @@ gtnx_status_t gtnx_batch_ctc_beam_decode(gtnx_batch_t ems, const int* frames, in
                                          void* lengths_device, void* scores_device);
 /* calls that have launched so far (process-wide) / utterances they decoded */
 gtnx_status_t gtnx_batch_ctc_beam_stats(int64_t* calls, int64_t* utterances);
+/* Levenshtein distance of all B * N pairs (hyp[b, k], ref[b]) of token rows that live on the device, results left on
+ * the device: what examples/edit_distance.cpp computes as -viterbiScore(compose(hyp, compose(edits, ref))), without the
+ * edits graph of alphabet^2 arcs.  Unit costs for substitution, insertion and deletion; tokens are compared with ==
+ * only, any int32 is a token and there is no alphabet size.
+ * hyp_device: int32, B * N rows of width L, hyp_stride (>= L) elements apart; hyp_lengths_device: int32 [B][N], dense;
+ * ref_device: int32, B rows of width U, ref_stride (>= U) apart; ref_lengths_device: int32 [B], dense.  The lengths are
+ * DEVICE memory (what gtnx_batch_linear_decode / gtnx_batch_ctc_beam_decode wrote): the host never sees them.  The
+ * kernel clamps a length to 0 .. L (0 .. U), a negative one counts as 0, and elements at or past the clamped length
+ * are never read -- a beam-search slot without a hypothesis (length 0, tokens -1) scores ref's length.
+ * dist_device: int32 [B][N].  ops_device: int32 [B][N][3] = (substitutions, deletions, insertions), or null to skip
+ * it; a deletion is a reference token without a hypothesis counterpart, an insertion the converse.  The counts are
+ * those of ONE alignment: with D[i][j] the distance of ref[:i] and hyp[:j], walk back from (len_ref, len_hyp) and take
+ * at every cell the first move that attains D[i][j] of: diagonal (a match where the tokens are equal, else a
+ * substitution), up (a deletion), left (an insertion).  S + D + I == dist.  With ops null nothing is stored for the walk.
+ * GTNX_INVALID_ARGUMENT before a device is asked for: a null input or dist pointer, negative B, N, L or U, a negative
+ * stride or one shorter than its width, L > 65536, U > 4096 (the limits of the implementation: the carries of a row of
+ * columns and the reference live in LDS, a lane owns one block of 64 reference tokens), B * N beyond an int.  B * N == 0
+ * returns without touching a device.  With the device: an output the engine's current device may not write.
+ * One launch on the engine's stream without ops (edit_distance.hip).  With ops the walk keeps 16 bytes * L *
+ * ceil(U / 64) per pair in scratch from the stream-ordered pool, at most 256 MiB per launch: beyond that the pairs run
+ * in slices of launches (the environment variable GTNX_EDIT_DISTANCE_SCRATCH_BYTES, read per call, lowers the cap: a
+ * debug switch for tests).  Nothing is copied back, the call does not wait, nothing but dist and ops is written. */
+gtnx_status_t gtnx_batch_edit_distance(const void* hyp_device, int64_t hyp_stride, const void* hyp_lengths_device,
+                                       const void* ref_device, int64_t ref_stride, const void* ref_lengths_device,
+                                       int B, int N, int L, int U, void* dist_device, void* ops_device);
+/* calls that have launched so far (process-wide) / pairs they computed */
+gtnx_status_t gtnx_batch_edit_distance_stats(int64_t* calls, int64_t* pairs);
 /* rows M and labels C of the slabs of a gtnx_batch_linear / _rows batch; -1, -1 for any other batch */
 gtnx_status_t gtnx_batch_linear_shape(gtnx_batch_t ems, int* rows, int* labels);
 gtnx_status_t gtnx_batch_backward(gtnx_batch_t a, int retain_graph);                  /* autograd.cpp:17-67 */
