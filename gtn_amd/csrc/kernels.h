@@ -592,7 +592,7 @@ void launch_asg_align(const AsgAlignArgs* d_args, int n, int max_nodes, hipStrea
 // rational.hip: clone / concat / closure / union_ (functions.cpp:66-223) built on the device
 // ---------------------------------------------------------------------------
 struct RationalSeg {      // one input graph's place in the output
-  DGraph g;               // its device view, weights included (implicit chains: n_start = n_accept = 1)
+  DGraph g;               // its device view, weights included (implicit chains: as ensure_device_batch fills it in)
   int node_off, arc_off;  // where its nodes / arcs start
   int conn_off;           // where the epsilon connectors INTO it (concat) / around it (closure) start
   int keep_start, keep_accept;

@@ -65,7 +65,7 @@ Graph op_rational(int kind, std::vector<Graph>& ins, int projection) {
   std::vector<Weights*> ws;
   for (auto& g : ins) {
     g.s->resolve_sizes();
-    if (g.s->kind != KIND_LINEAR) ss.push_back(g.s.get());
+    ss.push_back(g.s.get());  // (implicit chains too: that is where their device view -- kind, M, C -- is filled in)
     ws.push_back(g.w.get());
   }
   ensure_device_batch(ss);
@@ -80,24 +80,11 @@ Graph op_rational(int kind, std::vector<Graph>& ins, int projection) {
   for (int i = 0; i < k; ++i) {
     RationalSeg& s = segs[size_t(i)];
     s = RationalSeg{};
-    s.g = device_view(ins[size_t(i)]);
-    if (s.g.kind == KIND_LINEAR) {
-      s.g.N = int(ins[size_t(i)].s->N);
-      s.g.A = int(ins[size_t(i)].s->A);
-      s.g.M = ins[size_t(i)].s->M;
-      s.g.C = ins[size_t(i)].s->C;
-      s.g.n_start = s.g.n_accept = 1;
-    } else if (!(s.g.flags & 4)) {
-      eps_free = false;
-    }
+    s.g = device_view(ins[size_t(i)]);  // (implicit chains: kind, N, A, M, C and the counts come from ensure_device_batch)
+    if (!(s.g.flags & 4)) eps_free = false;
     s.node_off = int(N);
-    if (concat && i > 0) {  // the connectors into graph i come right after graph i's own arcs (functions.cpp:139-149)
-      s.arc_off = int(A);
-      s.conn_off = int(A) + s.g.A;
-    } else {
-      s.arc_off = int(A);
-      s.conn_off = int(A) + s.g.A;
-    }
+    s.arc_off = int(A);
+    s.conn_off = int(A) + s.g.A;  // the connectors into graph i come right after graph i's own arcs (functions.cpp:139-149)
     offs.push_back(A);
     int conn = 0;
     if (concat && i > 0) conn = segs[size_t(i) - 1].g.n_accept * s.g.n_start;
@@ -212,12 +199,13 @@ Graph op_remove(Graph& gin, int ilabel, int olabel) {
   const int N = g.N;
   if (N == 0) return out;
   const size_t scan_b = scan_temp_bytes(N + 1);
-  // keep flags -> ids of the kept nodes
-  DevMemP ids = rt.alloc(4 * (3 * size_t(N) + 8) + scan_b);
+  // keep flags -> ids of the kept nodes; rocprim's scratch sits on a 256-byte boundary behind them
+  const size_t ids_ints = align_up(4 * (3 * size_t(N) + 8), 256);
+  DevMemP ids = rt.alloc(ids_ints + scan_b);
   int* keep = ids->as<int>();
   int* new_id = keep + (N + 1);
   int* roots = new_id + (N + 1);
-  void* scan_tmp = roots + N + 2;
+  void* scan_tmp = ids->as<char>(ids_ints);
   HIP_CHECK(hipMemsetAsync(keep, 0, 4 * size_t(N + 1), rt.stream()));
   launch_remove_keep(g, ilabel, olabel, keep, rt.stream());
   launch_exclusive_scan(keep, new_id, N + 1, scan_tmp, scan_b, rt.stream());
@@ -228,7 +216,8 @@ Graph op_remove(Graph& gin, int ilabel, int olabel) {
   // walks: batches of `rows` kept nodes share 2 x rows x N ints of scratch (at most ~256 MB)
   const int rows = int(std::max<int64_t>(1, std::min<int64_t>(K, (int64_t(32) << 20) / std::max(N, 1))));
   DevMemP scratch = rt.alloc_zero(8 * size_t(rows) * size_t(N));
-  DevMemP counts = rt.alloc(4 * (2 * size_t(K) + 4) + scan_temp_bytes(K + 1));
+  const size_t counts_ints = align_up(4 * (2 * size_t(K) + 4), 256);
+  DevMemP counts = rt.alloc(counts_ints + scan_temp_bytes(K + 1));
   RemoveArgs ra{};
   ra.g = g;
   ra.ilabel = ilabel;
@@ -246,7 +235,7 @@ Graph op_remove(Graph& gin, int ilabel, int olabel) {
     ra.root0 = r0;
     launch_remove_walk(ra, false, rt.stream());
   }
-  launch_exclusive_scan(ra.arc_cnt, arc_off, K + 1, arc_off + K + 2, scan_temp_bytes(K + 1), rt.stream());
+  launch_exclusive_scan(ra.arc_cnt, arc_off, K + 1, counts->as<char>(counts_ints), scan_temp_bytes(K + 1), rt.stream());
   int A = 0;
   rt.d2h_sync(&A, arc_off + K, sizeof(int));
   // the result's arena (as op_rational lays it out)

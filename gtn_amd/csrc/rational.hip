@@ -13,13 +13,15 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "common.h"
 #include "kernels.h"
 
 namespace gtnx {
 namespace {
 
-__global__ void rat_arcs_kernel(const RationalSeg* __restrict__ segs, RationalOut out, int projection) {
-  const RationalSeg s = segs[blockIdx.y];
+// (seg0: the first segment of this launch -- the segment dimension runs in slices, see launch_rational_build)
+__global__ void rat_arcs_kernel(const RationalSeg* __restrict__ segs, int seg0, RationalOut out, int projection) {
+  const RationalSeg s = segs[seg0 + blockIdx.y];
   for (int a = blockIdx.x * blockDim.x + threadIdx.x; a < s.g.A; a += gridDim.x * blockDim.x) {
     const int o = s.arc_off + a;
     int sn, dn, il, ol;
@@ -43,12 +45,13 @@ __global__ void rat_arcs_kernel(const RationalSeg* __restrict__ segs, RationalOu
 
 // node flags: keep_start / keep_accept say whether the segment's own flags survive (concat keeps the
 // first graph's starts and the last graph's accepts only; closure none)
-__global__ void rat_nodes_kernel(const RationalSeg* __restrict__ segs, RationalOut out, int closure) {
-  const RationalSeg s = segs[blockIdx.y];
-  if (closure && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) out.nflags[0] = NF_START | NF_ACCEPT;
+__global__ void rat_nodes_kernel(const RationalSeg* __restrict__ segs, int seg0, RationalOut out, int closure) {
+  const RationalSeg s = segs[seg0 + blockIdx.y];
+  if (closure && blockIdx.x == 0 && seg0 + blockIdx.y == 0 && threadIdx.x == 0) out.nflags[0] = NF_START | NF_ACCEPT;
   for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < s.g.N; n += gridDim.x * blockDim.x) {
     uint8_t f;
-    if (s.g.kind == KIND_LINEAR) f = uint8_t((n == 0 ? NF_START : 0) | (n == s.g.M ? NF_ACCEPT : 0));
+    // (linearGraph(0, C) is one start node that does NOT accept: creations.cpp:20-33)
+    if (s.g.kind == KIND_LINEAR) f = uint8_t((n == 0 ? NF_START : 0) | (n == s.g.M && s.g.M > 0 ? NF_ACCEPT : 0));
     else f = s.g.nflags[n];
     uint8_t o = 0;
     if (s.keep_start && (f & NF_START)) o |= NF_START;
@@ -64,8 +67,9 @@ __device__ __forceinline__ int seg_accept(const RationalSeg& s, int i) { return 
 // epsilon connectors.  concat (functions.cpp:139-149): for every accept p of the previous graph and every start
 // q of this one, arc conn_off + p * n_start + q.  closure (functions.cpp:179-186): new start -> every old start,
 // then every old accept -> new start.
-__global__ void rat_conn_kernel(const RationalSeg* __restrict__ segs, RationalOut out, int closure) {
-  const RationalSeg s = segs[blockIdx.y];
+__global__ void rat_conn_kernel(const RationalSeg* __restrict__ segs, int seg0, RationalOut out, int closure) {
+  const int seg = seg0 + blockIdx.y;
+  const RationalSeg s = segs[seg];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (closure) {
     const int ns = s.g.n_start, na = s.g.n_accept;
@@ -82,8 +86,8 @@ __global__ void rat_conn_kernel(const RationalSeg* __restrict__ segs, RationalOu
     out.w[o] = 0.0f;
     return;
   }
-  if (blockIdx.y == 0) return;
-  const RationalSeg p = segs[blockIdx.y - 1];
+  if (seg == 0) return;
+  const RationalSeg p = segs[seg - 1];  // (the previous segment of the whole list, also across a slice edge)
   const int ns = s.g.n_start, na = p.g.n_accept;
   if (i >= ns * na) return;
   const int o = s.conn_off + i;
@@ -252,19 +256,24 @@ size_t rational_csr_temp_bytes(int N, int A) {
   (void)rocprim::radix_sort_pairs(nullptr, sort_b, (const unsigned*)nullptr, (unsigned*)nullptr, (const int*)nullptr,
                                   (int*)nullptr, size_t(A > 0 ? A : 1), 0, 32);
   (void)rocprim::exclusive_scan(nullptr, scan_b, (const int*)nullptr, (int*)nullptr, 0, size_t(N + 1), rocprim::plus<int>());
-  // keys out + iota + counts, then the primitives' own scratch
-  return 256 + 4 * size_t(A > 0 ? A : 1) * 2 + 4 * size_t(N + 2) + std::max(sort_b, scan_b) + 256;
+  // keys out + iota + counts, then the primitives' own scratch, which rocprim wants on a 256-byte boundary
+  return align_up(4 * size_t(A > 0 ? A : 1) * 2 + 4 * size_t(N + 2), 256) + std::max(sort_b, scan_b) + 256;
 }
 
 void launch_rational_build(const RationalSeg* d_segs, int nseg, int max_A, int max_N, int max_conn, const RationalOut& out,
                            int projection, int closure, void* temp, hipStream_t st) {
-  const int N = out.N, A = out.A;
-  if (max_A > 0)
-    hipLaunchKernelGGL(rat_arcs_kernel, dim3(std::min((max_A + 255) / 256, 4096), nseg), dim3(256), 0, st, d_segs, out, projection);
-  hipLaunchKernelGGL(rat_nodes_kernel, dim3(std::max(1, std::min((max_N + 255) / 256, 4096)), nseg), dim3(256), 0, st, d_segs,
-                     out, closure);
-  if (max_conn > 0)
-    hipLaunchKernelGGL(rat_conn_kernel, dim3((max_conn + 255) / 256, nseg), dim3(256), 0, st, d_segs, out, closure);
+  // the segment dimension is the grid's y, which the hardware limits to 65535: slices of at most kSegSlice inputs
+  constexpr int kSegSlice = 32768;
+  for (int seg0 = 0; seg0 < nseg; seg0 += kSegSlice) {
+    const int ny = std::min(kSegSlice, nseg - seg0);
+    if (max_A > 0)
+      hipLaunchKernelGGL(rat_arcs_kernel, dim3(std::min((max_A + 255) / 256, 4096), ny), dim3(256), 0, st, d_segs, seg0, out,
+                         projection);
+    hipLaunchKernelGGL(rat_nodes_kernel, dim3(std::max(1, std::min((max_N + 255) / 256, 4096)), ny), dim3(256), 0, st, d_segs,
+                       seg0, out, closure);
+    if (max_conn > 0)
+      hipLaunchKernelGGL(rat_conn_kernel, dim3((max_conn + 255) / 256, ny), dim3(256), 0, st, d_segs, seg0, out, closure);
+  }
   launch_rational_adjacency(out, temp, st);
 }
 
@@ -276,7 +285,7 @@ void launch_rational_adjacency(const RationalOut& out, void* temp, hipStream_t s
   unsigned* keys_out = reinterpret_cast<unsigned*>(t);
   int* iota = reinterpret_cast<int*>(t + 4 * size_t(A > 0 ? A : 1));
   int* cnt = iota + (A > 0 ? A : 1);
-  void* scratch = reinterpret_cast<char*>(cnt + N + 2);
+  void* scratch = t + align_up(4 * size_t(A > 0 ? A : 1) * 2 + 4 * size_t(N + 2), 256);  // (rational_csr_temp_bytes)
   size_t sort_b = 0, scan_b = 0;
   (void)rocprim::radix_sort_pairs(nullptr, sort_b, (const unsigned*)nullptr, (unsigned*)nullptr, (const int*)nullptr,
                                   (int*)nullptr, size_t(A > 0 ? A : 1), 0, 32);
