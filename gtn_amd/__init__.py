@@ -72,6 +72,7 @@ debug_linear_decode_stats = _api.debug_linear_decode_stats  # (Batch.linear_deco
 debug_ctc_beam_stats = _api.debug_ctc_beam_stats  # (Batch.ctc_beam_decode: calls that launched, utterances decoded)
 edit_distance = _api.edit_distance  # (batched Levenshtein distance of device-resident token rows)
 debug_edit_distance_stats = _api.debug_edit_distance_stats  # (edit_distance: calls that launched, pairs computed)
+debug_ctc_score_stats = _api.debug_ctc_score_stats  # (Batch.ctc_score / ctc_score_grad: calls that launched, pairs taken)
 
 
 def load_txt(text):

@@ -877,6 +877,94 @@ def make_api(lib):
                                                  _as_dev_ptr(lengths_out) if lengths_out is not None else None,
                                                  _as_dev_ptr(scores_out) if scores_out is not None else None))
 
+        def _ctc_score_args(self, who, tokens, lengths, frames, N, L, row_stride, max_length):
+            """(frames array or None, tokens address, row stride, lengths address, N, L, max_length) of a ctc_score call"""
+            n = len(self)
+            if tokens is not None and hasattr(tokens, "data_ptr"):
+                t = tokens
+                if str(t.dtype) != "torch.int32" or t.dim() != 3 or t.shape[0] != n:
+                    raise ValueError(f"{who}: tokens must be an int32 tensor [B, N, L]")
+                if ((t.shape[2] > 1 and t.stride(2) != 1)
+                        or (t.shape[0] > 1 and t.shape[1] > 1 and t.stride(0) != t.shape[1] * t.stride(1))):
+                    raise ValueError(f"{who}: tokens must have contiguous rows, equally spaced")
+                rows = t.stride(1) if t.shape[1] > 1 else (t.stride(0) if t.shape[0] > 1 else max(t.shape[2], 1))
+                for name, given, have in (("N", N, t.shape[1]), ("L", L, t.shape[2]), ("row_stride", row_stride, rows)):
+                    if given is not None and int(given) != int(have):
+                        raise ValueError(f"{who}: {name} = {given} is not what tokens says ({have})")
+                N, L, row_stride = t.shape[1], t.shape[2], rows
+                if hasattr(t, "is_cuda") and not t.is_cuda:
+                    raise ValueError(f"{who}: tokens must be a CUDA tensor")
+            if N is None or L is None or row_stride is None:
+                raise ValueError(f"{who}: a device address needs N, L and row_stride")
+            N, L = int(N), int(L)
+            if lengths is not None and hasattr(lengths, "data_ptr"):
+                if str(lengths.dtype) != "torch.int32" or not lengths.is_contiguous() or lengths.numel() != n * N:
+                    raise ValueError(f"{who}: lengths must be an int32 contiguous tensor [B, N]")
+                if hasattr(lengths, "is_cuda") and not lengths.is_cuda:
+                    raise ValueError(f"{who}: lengths must be a CUDA tensor")
+            fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32)
+            if fr is not None and fr.shape != (n,):
+                raise ValueError(f"{who}: one frame count per element")
+            if max_length is None:
+                m, c = C.c_int(-1), C.c_int(-1)
+                check(lib.gtnx_batch_linear_shape(self._h, C.byref(m), C.byref(c)))
+                max_length = max(1, min(L, m.value if m.value >= 0 else L, 4096))
+            return fr, tokens, int(row_stride), lengths, N, L, int(max_length)
+
+        def ctc_score(self, tokens, lengths, scores_out, frames=None, blank=0, max_length=None, N=None, L=None,
+                      row_stride=None):
+            """The exact log score of all B * N device-resident hypotheses under the slabs of a Batch.linear, results
+            left on the device (gtnx_batch_ctc_score; DESIGN section 22 holds the contract): scores_out[b, k] =
+            forwardScore(ctcGraph(tokens[b, k, :len], blank) o emissions_b[:T_b]) with len = clamp(lengths[b, k], 0, L),
+            nothing subtracted.  `tokens`: int32 CUDA tensor [B, N, L] with contiguous, equally spaced rows, or a device
+            address with N, L and row_stride (elements between rows, >= L); `lengths`: int32 [B, N], contiguous -- they
+            stay on the device; `scores_out`: float32 [B, N]; `frames`: T_b per element (0 .. M) or None; `max_length`
+            (1 .. 4096, default min(L, M, 4096)): the bound on len that sizes LDS -- longer hypotheses score -inf, as do
+            ones that do not fit, tokens outside 0 .. C - 1 inside a length, and T_b == 0.  A slot without a hypothesis
+            (length 0, tokens -1) scores as the empty sequence.  One launch, no copy back and no wait."""
+            fr, tok, stride, ln, N, L, U = self._ctc_score_args("ctc_score", tokens, lengths, frames, N, L, row_stride,
+                                                                max_length)
+            if scores_out is not None and hasattr(scores_out, "data_ptr"):
+                if (str(scores_out.dtype) != "torch.float32" or not scores_out.is_contiguous()
+                        or scores_out.numel() != len(self) * N):
+                    raise ValueError("ctc_score: scores_out must be a float32 contiguous tensor [B, N]")
+                if len(self) * N == 0:
+                    return
+            check(lib.gtnx_batch_ctc_score(self._h, fr.ctypes.data if fr is not None else None, int(blank),
+                                           _as_dev_ptr(tok) if tok is not None else None, stride,
+                                           _as_dev_ptr(ln) if ln is not None else None, N, L, U,
+                                           _as_dev_ptr(scores_out) if scores_out is not None else None))
+
+        def ctc_score_grad(self, tokens, lengths, weights, grad_out, frames=None, blank=0, max_length=None, N=None,
+                           L=None, row_stride=None):
+            """grad_out[b, t, c] = sum over k of weights[b, k] * d score[b, k] / d emissions[b, t, c] for the scores of
+            `ctc_score` (gtnx_batch_ctc_score_grad): `weights` float32 [B, N] on the device, `grad_out` float32
+            [B, M, C], every element written (zeros where nothing lands, rows from T_b on included) -- except that a call
+            without pairs (B * N == 0) writes nothing.  Pairs with a -inf score or a weight of exactly 0 add nothing.
+            Stateless: the alpha rows are recomputed into pooled scratch (sliced beyond 256 MiB, same bits); the sums are
+            taken in a fixed order without atomics, so the result has the same bits run to run."""
+            fr, tok, stride, ln, N, L, U = self._ctc_score_args("ctc_score_grad", tokens, lengths, frames, N, L,
+                                                                row_stride, max_length)
+            for o, what in ((weights, "weights must be a float32 contiguous tensor [B, N]"),
+                            (grad_out, "grad_out must be a float32 contiguous tensor [B, M, C]")):
+                if o is not None and hasattr(o, "data_ptr"):
+                    if str(o.dtype) != "torch.float32" or not o.is_contiguous():
+                        raise ValueError(f"ctc_score_grad: {what}")
+            if weights is not None and hasattr(weights, "data_ptr") and weights.numel() != len(self) * N:
+                raise ValueError("ctc_score_grad: weights must be a float32 contiguous tensor [B, N]")
+            if grad_out is not None and hasattr(grad_out, "data_ptr"):
+                m, c = C.c_int(-1), C.c_int(-1)
+                check(lib.gtnx_batch_linear_shape(self._h, C.byref(m), C.byref(c)))
+                if m.value >= 0 and grad_out.numel() != len(self) * m.value * c.value:
+                    raise ValueError("ctc_score_grad: grad_out must be a float32 contiguous tensor [B, M, C]")
+                if len(self) * N == 0:
+                    return
+            check(lib.gtnx_batch_ctc_score_grad(self._h, fr.ctypes.data if fr is not None else None, int(blank),
+                                                _as_dev_ptr(tok) if tok is not None else None, stride,
+                                                _as_dev_ptr(ln) if ln is not None else None, N, L, U,
+                                                _as_dev_ptr(weights) if weights is not None else None,
+                                                _as_dev_ptr(grad_out) if grad_out is not None else None))
+
     ns.Batch = Batch
 
     def _batch_fn(cfn, *args):
@@ -1020,6 +1108,13 @@ def make_api(lib):
         check(lib.gtnx_batch_ctc_beam_stats(C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def debug_ctc_score_stats():
+        """(calls, pairs): calls of Batch.ctc_score / Batch.ctc_score_grad that have launched so far and the pairs they
+        took (include/gtn_amd.h: gtnx_batch_ctc_score_stats)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(lib.gtnx_batch_ctc_score_stats(C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def debug_edit_distance_stats():
         """(calls, pairs): calls of edit_distance that have launched so far and the pairs they computed
         (include/gtn_amd.h: gtnx_batch_edit_distance_stats)"""
@@ -1113,6 +1208,7 @@ def make_api(lib):
     ns.debug_linear_decode_stats = debug_linear_decode_stats
     ns.debug_ctc_beam_stats = debug_ctc_beam_stats
     ns.debug_edit_distance_stats = debug_edit_distance_stats
+    ns.debug_ctc_score_stats = debug_ctc_score_stats
     ns.edit_distance = edit_distance
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties

@@ -98,6 +98,41 @@ extern "C" __attribute__((visibility("default"))) int gtn_ctc_beam_decode_n(cons
   }
 }
 
+// Exact CTC log scores of B * N device-resident hypotheses.  emissions: DEVICE float32 [B][T][C]; frames: HOST int [B] or
+// null; tokens: DEVICE int32 [B][N][L]; lengths: DEVICE int32 [B][N]; scores: DEVICE float32 [B][N].  Returns 0, or -1
+// with the message in gtn_criteria_last_error().
+extern "C" __attribute__((visibility("default"))) int gtn_ctc_score_n(const void* emissions, int B, int T, int C,
+                                                                      int blank, const int* frames, const void* tokens,
+                                                                      const void* lengths, int N, int L, int max_length,
+                                                                      void* scores) {
+  try {
+    if (!scores) throw std::invalid_argument("gtn_ctc_score_n: null scores");
+    gtn::criteria::ctcScoreBatch(emissions, B, T, C, blank, frames, tokens, lengths, N, L, max_length, scores);
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
+// ... and their gradient: grad (DEVICE float32 [B][T][C], every element written) = sum_k weights[b][k] * d score[b][k] /
+// d emissions_b for weights: DEVICE float32 [B][N].
+extern "C" __attribute__((visibility("default"))) int gtn_ctc_score_grad_n(const void* emissions, int B, int T, int C,
+                                                                           int blank, const int* frames,
+                                                                           const void* tokens, const void* lengths,
+                                                                           int N, int L, int max_length,
+                                                                           const void* weights, void* grad) {
+  try {
+    if (!weights || !grad) throw std::invalid_argument("gtn_ctc_score_grad_n: null weights or grad");
+    gtn::criteria::ctcScoreBatch(emissions, B, T, C, blank, frames, tokens, lengths, N, L, max_length, nullptr, weights,
+                                 grad);
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
 // Edit distance of all B * N pairs (hyp[b][k], ref[b]).  hyp: DEVICE int32 [B][N][L]; hyp_lengths: DEVICE int32 [B][N];
 // ref: DEVICE int32 [B][U]; ref_lengths: DEVICE int32 [B]; dist: DEVICE int32 [B][N]; ops: DEVICE int32 [B][N][3] or
 // null.  Returns 0, or -1 with the message in gtn_criteria_last_error().

@@ -187,5 +187,42 @@ inline void ctcBeamDecodeBatch(
                          static_cast<float*>(scoresDev), blank, beamSize, cutoffTopN, nbest, frames);
 }
 
+/** The exact log scores of B * N device-resident hypotheses under the B emission slabs, and (with weightsDev and gradDev)
+ *  the gradient sum_k weights[b][k] * d score[b][k] / d emissions_b: `emissions` device float32 [B][T][C], read in
+ *  place; `tokensDev` device int32 [B][N][L] (dense rows); `lengthsDev` device int32 [B][N]; `frames` host [B] or null;
+ *  `scoresDev` device float32 [B][N] or null; `weightsDev` device float32 [B][N] and `gradDev` device float32 [B][T][C],
+ *  both or neither.  gtnx_batch_ctc_score / _grad have the contract.  Nothing is copied back. */
+inline void ctcScoreBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int C,
+    int blank,
+    const int* frames,
+    const void* tokensDev,
+    const void* lengthsDev,
+    int N,
+    int L,
+    int maxLength,
+    void* scoresDev,
+    const void* weightsDev = nullptr,
+    void* gradDev = nullptr) {
+  if ((weightsDev == nullptr) != (gradDev == nullptr)) {
+    throw std::invalid_argument("ctcScoreBatch: weights and grad come together");
+  }
+  if (!scoresDev && !gradDev) {
+    throw std::invalid_argument("ctcScoreBatch: neither scores nor grad asked for");
+  }
+  Batch ems = Batch::linear(B, T, C, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  if (scoresDev) {
+    batched::ctcScore(ems, static_cast<const int*>(tokensDev), L, static_cast<const int*>(lengthsDev), N, L, maxLength,
+                      static_cast<float*>(scoresDev), blank, frames);
+  }
+  if (gradDev) {
+    batched::ctcScoreGrad(ems, static_cast<const int*>(tokensDev), L, static_cast<const int*>(lengthsDev), N, L,
+                          maxLength, static_cast<const float*>(weightsDev), static_cast<float*>(gradDev), blank, frames);
+  }
+}
+
 } // namespace criteria
 } // namespace gtn

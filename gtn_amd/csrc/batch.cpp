@@ -1781,6 +1781,145 @@ void batch_edit_distance(const int* hyp_dev, int64_t hyp_stride, const int* hyp_
 }
 
 
+// ---- batched CTC score of device-resident hypotheses, and its gradient (ctc_score.hip) ----
+namespace {
+std::atomic<int64_t> g_ctc_score_calls{0}, g_ctc_score_pairs{0};
+// what the alpha rows of ONE launch may take; a gradient call that needs more runs its pairs in slices of launches.  A
+// pair that is above the cap by itself runs alone with scratch of its own size.
+constexpr int64_t kCtcScoreScratchCap = int64_t(256) << 20;
+int64_t ctc_score_scratch_cap() {
+  // (debug switch, read per call: tests lower the cap to see a sliced call without allocating gigabytes)
+  const char* e = std::getenv("GTNX_CTC_SCORE_SCRATCH_BYTES");
+  if (e && *e) {
+    const long long v = std::atoll(e);
+    if (v > 0) return std::min<int64_t>(v, kCtcScoreScratchCap);
+  }
+  return kCtcScoreScratchCap;
+}
+
+// both entry points: scores_dev for the score, weights_dev and grad_dev for the gradient
+void ctc_score_impl(const char* who, const BatchP& ems, const int* frames, int blank, const int* tokens_dev,
+                    int64_t row_stride, const int* lengths_dev, int N, int L, int max_length, float* scores_dev,
+                    const float* weights_dev, float* grad_dev) {
+  const std::string tag = std::string("[") + who + "] ";
+  const bool want_grad = scores_dev == nullptr;
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) throw_invalid(tag + "null batch");
+  if (!tokens_dev || !lengths_dev) throw_invalid(tag + "null input pointer (tokens and lengths are both read)");
+  if (want_grad ? (!weights_dev || !grad_dev) : false) throw_invalid(tag + "null weights or grad pointer");
+  if (N < 0 || L < 0) throw_invalid(tag + "negative N or L");
+  if (row_stride < 0) throw_invalid(tag + "negative row stride");
+  if (blank < 0) throw_invalid(tag + "negative blank");
+  if (row_stride < L) throw_invalid(tag + "row_stride is shorter than the rows' width L");
+  if (max_length < 1 || max_length > kCtcScoreMaxU) throw_invalid(tag + "max_length outside 1 .. 4096");
+  const int n = ems->n;
+  const int64_t pairs = int64_t(n) * N;
+  if (pairs > std::numeric_limits<int>::max()) throw_invalid(tag + "n times N does not fit an int");
+  if (pairs <= 0) return;
+  Runtime& rt = Runtime::get();
+  // there is no other route: the scores are those of the slabs of a native linear batch
+  if (!(ems->kind == Batch::LINEAR && !ems->leaf && ems->w_dev))
+    throw_invalid(tag + "not a native linear batch (gtnx_batch_linear / _rows)");
+  Batch& x = *ems;
+  if (frames)
+    for (int b = 0; b < n; ++b) {
+      if (frames[b] < 0 || frames[b] > x.M) throw_invalid(tag + "a frame count outside 0 .. M");
+      if (frames[b] > x.rows_of(b)) throw_invalid(tag + "a frame count beyond the rows the batch carries");
+    }
+  if (blank >= x.C) throw_invalid(tag + "blank is not below the number of labels");
+  // a kernel of this device writes the results: memory of another GPU of the process is refused, not written
+  if (want_grad ? !ptr_local_to(grad_dev, rt.device()) : !ptr_local_to(scores_dev, rt.device()))
+    throw_invalid(tag + "an output pointer is not memory of the engine's current device");
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  std::vector<int> fr(static_cast<size_t>(n));
+  int maxT = 0;
+  double frame_sum = 0;
+  for (int b = 0; b < n; ++b) {
+    fr[size_t(b)] = frames ? frames[b] : x.rows_of(b);
+    maxT = std::max(maxT, fr[size_t(b)]);
+    frame_sum += fr[size_t(b)];
+  }
+  DevMemP d_frames = upload_vec(fr);
+  const int U = max_length;
+  const int64_t SM = 2 * int64_t(U) + 1;
+  CtcScoreArgs a{};
+  a.em = x.w_dev;
+  a.frames = d_frames->as<int>();
+  a.tokens = tokens_dev;
+  a.lengths = lengths_dev;
+  a.weights = weights_dev;
+  a.grad = grad_dev;
+  a.row_stride = row_stride;
+  a.N = N;
+  a.L = L;
+  a.U = U;
+  a.M = x.M;
+  a.C = x.C;
+  a.blank = blank;
+  // algorithmic bytes, by the widths (the lengths are device memory: an upper bound).  forward: per pair and frame one
+  // emission per state, the tokens and the length once, the score out.  With the rows kept: every alpha out as well.
+  // backward: the alphas and the emissions back in, one load and one store of a gradient element per state and frame
+  // at most, the tokens and the length, and the utterance's slab zeroed once.
+  const double per_pair_frames = frame_sum / double(n);  // (the mean: every utterance has N pairs)
+  const double fwd_pair = 4.0 * double(SM) * per_pair_frames + 4.0 * std::min(L, U) + 8.0;
+  if (!want_grad) {
+    a.scores = scores_dev;
+    a.pair0 = 0;
+    a.score0 = 0;
+    a.count = int(pairs);
+    GTNX_PROF("ctc_score", fwd_pair * double(pairs));
+    launch_ctc_score_forward(a, rt.stream());
+  } else {
+    const int64_t per_pair = std::max<int64_t>(int64_t(maxT), 1) * SM;  // floats
+    const int64_t slice = std::max<int64_t>(1, ctc_score_scratch_cap() / (4 * per_pair));
+    a.pair_stride = per_pair;
+    for (int64_t p0 = 0; p0 < pairs; p0 += slice) {
+      const int64_t cnt = std::min(slice, pairs - p0);
+      DevMemP rows = rt.alloc(size_t(4 * per_pair * cnt));
+      DevMemP sc = rt.alloc(size_t(4 * cnt));
+      a.alpha = rows->as<float>();
+      a.scores = sc->as<float>();
+      a.pair0 = p0;
+      a.score0 = p0;
+      a.count = int(cnt);
+      {
+        GTNX_PROF("ctc_score_alpha", 2.0 * fwd_pair * double(cnt));
+        launch_ctc_score_forward(a, rt.stream());
+      }
+      {
+        GTNX_PROF("ctc_score_grad", (4.0 * fwd_pair + 4.0 * double(x.M) * x.C / double(N)) * double(cnt));
+        launch_ctc_score_backward(a, rt.stream());
+      }
+      // (the rows go back to the stream-ordered pool behind the launches)
+    }
+  }
+  g_ctc_score_calls.fetch_add(1);
+  g_ctc_score_pairs.fetch_add(pairs);
+}
+}  // namespace
+
+void batch_ctc_score_stats(int64_t* calls, int64_t* pairs) {
+  if (calls) *calls = g_ctc_score_calls.load();
+  if (pairs) *pairs = g_ctc_score_pairs.load();
+}
+
+void batch_ctc_score(const BatchP& ems, const int* frames, int blank, const int* tokens_dev, int64_t row_stride,
+                     const int* lengths_dev, int N, int L, int max_length, float* scores_dev) {
+  GTNX_HOST_T("batch.ctc_score");
+  if (!scores_dev) throw_invalid("[gtnx_batch_ctc_score] null scores pointer");
+  ctc_score_impl("gtnx_batch_ctc_score", ems, frames, blank, tokens_dev, row_stride, lengths_dev, N, L, max_length,
+                 scores_dev, nullptr, nullptr);
+}
+
+void batch_ctc_score_grad(const BatchP& ems, const int* frames, int blank, const int* tokens_dev, int64_t row_stride,
+                          const int* lengths_dev, int N, int L, int max_length, const float* weights_dev,
+                          float* grad_dev) {
+  GTNX_HOST_T("batch.ctc_score_grad");
+  ctc_score_impl("gtnx_batch_ctc_score_grad", ems, frames, blank, tokens_dev, row_stride, lengths_dev, N, L,
+                 max_length, nullptr, weights_dev, grad_dev);
+}
+
+
 namespace {
 // a GRAPHS batch of one-arc graphs as a native SCALAR batch (values gathered; backward continues on the graphs' tape)
 BatchP scalars_from_graphs(const BatchP& gsb) {

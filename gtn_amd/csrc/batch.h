@@ -199,6 +199,25 @@ void batch_edit_distance(const int* hyp_dev, int64_t hyp_stride, const int* hyp_
                          int64_t ref_stride, const int* ref_len_dev, int B, int N, int L, int U, int* dist_dev,
                          int* ops_dev);
 void batch_edit_distance_stats(int64_t* calls, int64_t* pairs);  // calls that launched / pairs they computed
+// The exact log score of all n * N device-resident hypotheses under the n emission slabs of a native linear batch,
+// score[b * N + k] = forwardScore(ctcGraph(tokens[b, k, :len], blank) o emissions_b[:T_b]) with len = clamp(lengths[b, k],
+// 0, L), nothing subtracted, results on the device (DESIGN section 22 holds the contract).  tokens_dev: int32 n * N rows
+// of width L, row_stride elements apart; lengths_dev: int32 [n][N], DEVICE memory; frames: HOST, T_b per element or null.
+// -inf (never NaN): no alignment fits, len > max_length, a token inside the length outside 0 .. C - 1, T_b == 0.
+// Invalid argument before a device is asked for: a null pointer, negative N, L, stride or blank, row_stride < L,
+// max_length outside 1 .. 4096; n * N == 0 returns without a device.  With the device: not a native linear batch, a
+// frame count outside 0 .. M, blank >= C, an output that is not memory of the current device.  One launch, no scratch.
+void batch_ctc_score(const BatchP& ems, const int* frames, int blank, const int* tokens_dev, int64_t row_stride,
+                     const int* lengths_dev, int N, int L, int max_length, float* scores_dev);
+// grad_dev[b][t][c] = sum over k of weights_dev[b * N + k] * d score[b, k] / d emissions[b][t][c], every element of
+// [n][M][C] written (zeros where nothing lands, pad rows included); a pair whose score is -inf or whose weight is
+// exactly 0 adds nothing.  The alpha rows are recomputed into scratch from the stream-ordered pool (max T_b * (2 *
+// max_length + 1) floats per pair), at most 256 MiB per launch pair (GTNX_CTC_SCORE_SCRATCH_BYTES lowers the cap: a
+// debug switch); beyond it the pairs run in slices with the same bits.  No floating-point atomics: bit-repeatable.
+void batch_ctc_score_grad(const BatchP& ems, const int* frames, int blank, const int* tokens_dev, int64_t row_stride,
+                          const int* lengths_dev, int N, int L, int max_length, const float* weights_dev,
+                          float* grad_dev);
+void batch_ctc_score_stats(int64_t* calls, int64_t* pairs);  // calls that launched (either kind) / pairs they took
 // items_dev (optional): device memory of the CALLER's that the n result values are written into directly (borrowed: it
 // must outlive the result); a later batch_items_device to the same address copies nothing
 BatchP batch_scalar(ScalarKind k, const BatchP& a, const BatchP& b, void* items_dev = nullptr);

@@ -923,6 +923,27 @@ GTNX_API gtnx_status_t gtnx_batch_edit_distance(const void* hyp_device, int64_t 
 GTNX_API gtnx_status_t gtnx_batch_edit_distance_stats(int64_t* calls, int64_t* pairs) {
   return guard([&] { batch_edit_distance_stats(calls, pairs); });
 }
+GTNX_API gtnx_status_t gtnx_batch_ctc_score(gtnx_batch_t ems, const int* frames, int blank, const void* tokens_device,
+                                            int64_t row_stride, const void* lengths_device, int N, int L,
+                                            int max_length, void* scores_device) {
+  return guard([&] {
+    batch_ctc_score(BH(ems), frames, blank, static_cast<const int*>(tokens_device), row_stride,
+                    static_cast<const int*>(lengths_device), N, L, max_length, static_cast<float*>(scores_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_ctc_score_grad(gtnx_batch_t ems, const int* frames, int blank,
+                                                 const void* tokens_device, int64_t row_stride,
+                                                 const void* lengths_device, int N, int L, int max_length,
+                                                 const void* weights_device, void* grad_device) {
+  return guard([&] {
+    batch_ctc_score_grad(BH(ems), frames, blank, static_cast<const int*>(tokens_device), row_stride,
+                         static_cast<const int*>(lengths_device), N, L, max_length,
+                         static_cast<const float*>(weights_device), static_cast<float*>(grad_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_ctc_score_stats(int64_t* calls, int64_t* pairs) {
+  return guard([&] { batch_ctc_score_stats(calls, pairs); });
+}
 GTNX_API gtnx_status_t gtnx_batch_linear_shape(gtnx_batch_t ems, int* rows, int* labels) {
   return guard([&] {
     const BatchP& b = BH(ems);

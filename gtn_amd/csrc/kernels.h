@@ -872,6 +872,32 @@ struct EditDistanceArgs {
   int count, N, L, U, nbU;
 };
 void launch_edit_distance(const EditDistanceArgs& a, hipStream_t st);
+// ctc_score.hip: the log score forwardScore(ctcGraph(y) o emissions_b[:T_b]) of the pairs pair0 .. pair0 + count - 1,
+// pair p = b * N + k being the hypothesis y = tokens[p * row_stride .. + clamp(lengths[p], 0, L)) of utterance b, and
+// the gradient sum_k weights[p] * d score[p] / d emissions_b (the contract: DESIGN section 22).
+//   forward:  one workgroup per pair; scores[p - score0] = the score (-inf: no path, length > U, a token outside
+//             0 .. C - 1, T_b == 0).  With `alpha` non-null the alpha row of every frame also goes to
+//             alpha[(p - pair0) * pair_stride + t * (2 U + 1) + s].
+//   backward: one workgroup per utterance of the range walks its pairs of the range in k order: beta in LDS, the
+//             occupancies exp(alpha + beta - score) summed per label in a fixed order and added into grad[b][t][label]
+//             by plain loads and stores (no atomics).  The workgroup that holds k == 0 zeroes grad[b] first.
+// The workgroup's width and the states per lane are chosen from 2 U + 1 alone (ctc_score_config).
+constexpr int kCtcScoreMaxU = 4096;
+struct CtcScoreArgs {
+  const GTNX_G float* em;       // [n][M][C]
+  const GTNX_G int* frames;     // [n]
+  const GTNX_G int* tokens;     // pair p's row at tokens + p * row_stride
+  const GTNX_G int* lengths;    // [pairs]
+  GTNX_G float* scores;         // [.. - score0]
+  GTNX_G float* alpha;          // [count][pair_stride] or null (forward); read by backward
+  const GTNX_G float* weights;  // [pairs] (backward)
+  GTNX_G float* grad;           // [n][M][C] (backward)
+  int64_t row_stride, pair0, score0, pair_stride;
+  int count, N, L, U, M, C, blank;
+};
+void ctc_score_config(int U, int* width, int* per_lane);  // the workgroup's width and the states a lane owns
+void launch_ctc_score_forward(const CtcScoreArgs& a, hipStream_t st);
+void launch_ctc_score_backward(const CtcScoreArgs& a, hipStream_t st);
 // materialise a KIND_LINEAR graph's arc arrays
 void launch_linear_materialize(int M, int C, int* src, int* dst, int* il, int* ol, hipStream_t st);
 

@@ -1,5 +1,5 @@
 """PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
-`asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_beam_decode` and `edit_distance`.
+`asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_beam_decode`, `edit_distance` and `ctc_score`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -64,6 +64,14 @@ def _native():
                 lib.gtn_edit_distance_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p]
                 lib.gtn_edit_distance_n.restype = C.c_int
+            if hasattr(lib, "gtn_ctc_score_n"):
+                lib.gtn_ctc_score_n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+                lib.gtn_ctc_score_n.restype = C.c_int
+                lib.gtn_ctc_score_grad_n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                     C.c_void_p]
+                lib.gtn_ctc_score_grad_n.restype = C.c_int
             _NATIVE = lib
         else:
             _NATIVE = False
@@ -654,3 +662,124 @@ def edit_distance(hyp, hyp_lengths, ref, ref_lengths, return_ops=False):
         dist = dist.reshape(B)
         ops = ops.reshape(B, 3) if return_ops else None
     return (dist, ops) if return_ops else dist
+
+
+def _engine_stream(device):
+    """point the engine at the caller's stream; returns the stream"""
+    stream = torch.cuda.current_stream(device)
+    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
+    if not stream.cuda_stream:
+        stream.synchronize()  # engine runs on its own stream
+    return stream
+
+
+class _CTCScore(torch.autograd.Function):
+    """forward: one launch that stores nothing but the scores; backward: the one gradient call with grad_out as the
+    weights.  The node keeps tensors only: the backward recomputes what it needs."""
+
+    @staticmethod
+    def forward(ctx, log_probs, tokens, lengths, blank, frames, max_length):
+        B, T, C_ = log_probs.shape
+        N, L = tokens.shape[1], tokens.shape[2]
+        x = log_probs.detach().contiguous()
+        stream = _engine_stream(x.device)
+        scores = torch.empty(B, N, dtype=torch.float32, device=x.device)
+        lib = _native()
+        fr = frames.ctypes.data if frames is not None else None
+        if B * N == 0:
+            pass  # (no pair: nothing to launch, and an empty tensor has no address to hand over)
+        elif lib:
+            if not hasattr(lib, "gtn_ctc_score_n"):
+                raise RuntimeError("ctc_score needs gtn_ctc_score_n in gtn_amd/lib/libgtn_criteria.so "
+                                   "(run __graft_entry__.build())")
+            rc = lib.gtn_ctc_score_n(x.data_ptr(), B, T, C_, blank, fr, tokens.data_ptr(), lengths.data_ptr(), N, L,
+                                     max_length, scores.data_ptr())
+            if rc != 0:
+                raise RuntimeError(lib.gtn_criteria_last_error().decode())
+        else:
+            ems = gtn.Batch.linear(B, T, C_, x, calc_grad=False, borrow=True)
+            ems.ctc_score(tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr(), frames, blank, max_length, N=N, L=L,
+                          row_stride=L)
+        if not stream.cuda_stream:
+            gtn.synchronize()
+        ctx.save_for_backward(x, tokens, lengths)
+        ctx.args = (blank, frames, max_length)
+        return scores
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, tokens, lengths = ctx.saved_tensors
+        blank, frames, max_length = ctx.args
+        B, T, C_ = x.shape
+        N, L = tokens.shape[1], tokens.shape[2]
+        if B * N == 0 or x.numel() == 0:
+            return torch.zeros_like(x), None, None, None, None, None
+        w = grad_out.detach().to(torch.float32).contiguous()
+        stream = _engine_stream(x.device)
+        grad = torch.empty(B, T, C_, dtype=torch.float32, device=x.device)
+        lib = _native()
+        fr = frames.ctypes.data if frames is not None else None
+        if lib:
+            rc = lib.gtn_ctc_score_grad_n(x.data_ptr(), B, T, C_, blank, fr, tokens.data_ptr(), lengths.data_ptr(), N, L,
+                                          max_length, w.data_ptr(), grad.data_ptr())
+            if rc != 0:
+                raise RuntimeError(lib.gtn_criteria_last_error().decode())
+        else:
+            ems = gtn.Batch.linear(B, T, C_, x, calc_grad=False, borrow=True)
+            ems.ctc_score_grad(tokens.data_ptr(), lengths.data_ptr(), w.data_ptr(), grad.data_ptr(), frames, blank,
+                               max_length, N=N, L=L, row_stride=L)
+        if not stream.cuda_stream:
+            gtn.synchronize()
+        return grad, None, None, None, None, None
+
+
+def ctc_score(log_probs, tokens, lengths, blank=0, input_lengths=None, max_length=None):
+    """The exact log score of device-resident hypotheses under the emissions, differentiable: score[b, k] =
+    forwardScore(ctcGraph(tokens[b, k, :len], blank) o log_probs[b, :T_b]), the log-sum over all alignments of the summed
+    emissions, for all B * N hypotheses in one launch against the B shared slabs -- no download of the tokens, no wait, no
+    repeated emissions.  No normaliser is subtracted: `ctc_loss(x, [y]) == forwardScore(x) - ctc_score(x, y)`, and an
+    unpruned `ctc_beam_decode` gives the same number as its score.  It is the middle term of N-best objectives
+    (`ctc_beam_decode` -> `ctc_score` -> `edit_distance` -> softmax-weighted risk).
+    log_probs: float32 CUDA tensor [B, T, C] (any scores), read in place; tokens: int32 CUDA tensor [B, N, L] (the
+    `ctc_beam_decode` form) or [B, L]; lengths: int32 or int64 CUDA tensor [B, N] / [B], read on the device and clamped to
+    0 .. L there (a negative one counts as 0) -- elements at or past a length are never read; blank: 0 .. C - 1 (a token
+    equal to blank is a label like any other); input_lengths: per-utterance frame counts (0 .. T) or None -- rows past
+    T_b are never read and their gradient is exactly 0; max_length (1 .. 4096, default min(L, T, 4096)): the caller's
+    bound on the hypotheses' lengths, which sizes the kernel's LDS and the backward's scratch.
+    Returns float32 [B, N] (or [B]).  A score is -inf, with zero gradient and never NaN, when no alignment fits (length
+    + repeats > T_b), every path crosses a -inf emission, the length is above max_length, a token inside the length lies
+    outside 0 .. C - 1, or T_b == 0.  A beam slot WITHOUT a hypothesis (length 0, tokens -1) scores as the empty
+    sequence, all blanks, which is a finite number: mask such slots with the -inf of the beam's own scores
+    (`torch.where(beam_scores == -inf, beam_scores, score)`).
+    The backward is one call that returns sum_k grad_out[b, k] * d score[b, k] / d log_probs; it recomputes what it
+    needs (the node keeps tensors only), skips pairs whose score is -inf or whose incoming gradient is exactly 0, and
+    sums in a fixed order without atomics, so it has the same bits run to run.  Without requires_grad it never launches.
+    Runs on the caller's stream."""
+    if not (torch.is_tensor(log_probs) and log_probs.dim() == 3 and log_probs.dtype == torch.float32):
+        raise ValueError("ctc_score: log_probs must be a float32 tensor [B, T, C]")
+    B, T, C_ = log_probs.shape
+    if not (torch.is_tensor(tokens) and tokens.dtype == torch.int32 and tokens.dim() in (2, 3) and tokens.shape[0] == B):
+        raise ValueError(f"ctc_score: tokens must be an int32 tensor [B, N, L] or [B, L] for a batch of {B}")
+    flat = tokens.dim() == 2
+    N, L = (1, tokens.shape[1]) if flat else tokens.shape[1:]
+    shape = (B,) if flat else (B, N)
+    if not (torch.is_tensor(lengths) and lengths.dtype in (torch.int32, torch.int64) and tuple(lengths.shape) == shape):
+        raise ValueError(f"ctc_score: lengths must be an int32 or int64 tensor {list(shape)}")
+    blank = int(blank)
+    if not 0 <= blank < C_:
+        raise ValueError(f"ctc_score: blank must be one of the {C_} labels")
+    max_length = max(1, min(L, T, 4096)) if max_length is None else int(max_length)
+    if not 1 <= max_length <= 4096:
+        raise ValueError("ctc_score: max_length outside 1 .. 4096")
+    frames = None if input_lengths is None else _frame_counts("ctc_score", input_lengths, B, T, 0)
+    for t, what in ((log_probs, "log_probs"), (tokens, "tokens"), (lengths, "lengths")):
+        if not t.is_cuda:
+            raise RuntimeError(f"ctc_score: {what} must be a CUDA tensor (the scores are computed on the device)")
+        if t.device != log_probs.device:
+            raise ValueError("ctc_score: all tensors must be on one device")
+    tok = tokens.detach().reshape(B, N, L).contiguous()
+    if B * N and tok.numel() == 0:
+        tok = tok.new_empty(B, N, 1)[:, :, :0]  # (rows without an element are never read, but they need an address)
+    ln = lengths.detach().to(torch.int32).reshape(B, N).contiguous()  # (int64 lengths are converted on the device)
+    out = _CTCScore.apply(log_probs, tok, ln, blank, frames, max_length)
+    return out.reshape(B) if flat else out

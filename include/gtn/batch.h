@@ -211,6 +211,27 @@ inline void editDistance(const int* hypDevice, int64_t hypStride, const int* hyp
   detail::check(gtnx_batch_edit_distance(hypDevice, hypStride, hypLengthsDevice, refDevice, refStride, refLengthsDevice,
                                          B, N, L, U, distDevice, opsDevice));
 }
+/** The exact log score of all n * N device-resident hypotheses under the slabs of a Batch::linear, results left on the
+ *  device: scoresDevice[b][k] = forwardScore(ctcGraph(tokens[b][k][0 .. len), blank) o emissions_b[0 .. T_b)), len =
+ *  clamp(lengthsDevice[b][k], 0, L), nothing subtracted.  tokensDevice int32 n * N rows of width L, rowStride (>= L)
+ *  apart; lengthsDevice int32 [n][N] (device memory); maxLength 1 .. 4096 bounds len (longer ones score -inf, as do
+ *  hypotheses that do not fit, tokens outside 0 .. C - 1 and T_b == 0); frames (host, [n]): T_b, null = the rows the
+ *  batch carries.  One launch, no copy back, no wait -- gtnx_batch_ctc_score */
+inline void ctcScore(const Batch& ems, const int* tokensDevice, int64_t rowStride, const int* lengthsDevice, int N, int L,
+                     int maxLength, float* scoresDevice, int blank = 0, const int* frames = nullptr) {
+  detail::check(gtnx_batch_ctc_score(ems.handle(), frames, blank, tokensDevice, rowStride, lengthsDevice, N, L, maxLength,
+                                     scoresDevice));
+}
+/** gradDevice[b][t][c] = sum over k of weightsDevice[b][k] * d score[b][k] / d emissions[b][t][c] for the scores of
+ *  ctcScore, every element of float32 [n][M][C] written (zeros where nothing lands, rows from T_b on included); pairs
+ *  with a -inf score or a weight of exactly 0 add nothing.  Stateless (the alpha rows are recomputed into pooled
+ *  scratch, sliced beyond 256 MiB) and bit-repeatable (fixed summation order, no atomics) -- gtnx_batch_ctc_score_grad */
+inline void ctcScoreGrad(const Batch& ems, const int* tokensDevice, int64_t rowStride, const int* lengthsDevice, int N,
+                         int L, int maxLength, const float* weightsDevice, float* gradDevice, int blank = 0,
+                         const int* frames = nullptr) {
+  detail::check(gtnx_batch_ctc_score_grad(ems.handle(), frames, blank, tokensDevice, rowStride, lengthsDevice, N, L,
+                                          maxLength, weightsDevice, gradDevice));
+}
 inline void backward(const Batch& a, bool retainGraph = false) { detail::check(gtnx_batch_backward(a.handle(), retainGraph)); }
 } // namespace batched
 

@@ -422,6 +422,50 @@ gtnx_status_t gtnx_batch_edit_distance(const void* hyp_device, int64_t hyp_strid
                                        int B, int N, int L, int U, void* dist_device, void* ops_device);
 /* calls that have launched so far (process-wide) / pairs they computed */
 gtnx_status_t gtnx_batch_edit_distance_stats(int64_t* calls, int64_t* pairs);
+/* The exact log score of all n * N hypotheses that live on the device under the n emission slabs of `ems` (a
+ * gtnx_batch_linear / _rows batch, [n][M][C]), results left on the device: for pair (b, k)
+ *   len = clamp(lengths[b][k], 0, L) (a negative length counts as 0), y = tokens[b][k][0 .. len), T_b = frames[b],
+ *   scores[b][k] = forwardScore(ctcGraph(y, blank) o linearGraph(emissions_b[0 .. T_b)))
+ * the log-sum over all alignments of the summed emissions; no normaliser is subtracted, so the CTC loss of y is
+ * forwardScore(emissions_b) - scores[b][k], and an unpruned gtnx_batch_ctc_beam_decode gives the same number.  ctcGraph
+ * is the acceptor of benchmarks/ctc.cpp:40-58: 2 len + 1 nodes, a skip arc only between different neighbouring labels,
+ * the last two nodes accept; a token equal to `blank` is a label like any other.
+ * tokens_device: int32, n * N rows of width L, row_stride (>= L) elements apart; lengths_device: int32 [n][N], dense --
+ * DEVICE memory, what gtnx_batch_ctc_beam_decode wrote: the host never sees them.  frames: HOST, [n], T_b in 0 .. M, or
+ * null (the rows the batch carries).  max_length (1 .. 4096) is the caller's bound on len; it, not L, sizes LDS and
+ * scratch.  scores_device: float32 [n][N].
+ * The score is -inf -- never NaN, and without a gradient -- when no alignment fits (len + repeats > T_b), every path
+ * crosses a -inf emission, len > max_length, a token inside the length lies outside 0 .. C - 1 (checked by the kernel:
+ * such an element never becomes an address), or T_b == 0.  Elements at or past a length and emission rows at or past
+ * T_b are never read.  A beam-search slot without a hypothesis (length 0, tokens -1) scores as the empty sequence,
+ * all blanks: a finite number -- mask such slots with the beam's own -inf.
+ * GTNX_INVALID_ARGUMENT before a device is asked for: a null batch, tokens, lengths or scores pointer, negative N, L,
+ * row_stride or blank, row_stride < L, max_length outside 1 .. 4096.  n * N == 0 returns without touching a device.
+ * With the device: not a gtnx_batch_linear / _rows batch, a frame count outside 0 .. M, blank >= C, an output the
+ * engine's current device may not write.
+ * One launch on the engine's stream (ctc_score.hip), one workgroup per pair, no scratch; nothing is copied back, the
+ * call does not wait, nothing but scores is written. */
+gtnx_status_t gtnx_batch_ctc_score(gtnx_batch_t ems, const int* frames, int blank, const void* tokens_device,
+                                   int64_t row_stride, const void* lengths_device, int N, int L, int max_length,
+                                   void* scores_device);
+/* The gradient of those scores: grad[b][t][c] = sum over k of weights[b][k] * d scores[b][k] / d emissions[b][t][c], for
+ * caller-supplied weights_device (float32 [n][N], device memory) -- what the backward of any N-best objective needs,
+ * the hypotheses weighted separately.  The inputs are those of gtnx_batch_ctc_score, with the same meaning and the same
+ * refusals (weights and grad in the place of scores).  grad_device: float32 [n][M][C]; EVERY element is written: zeros
+ * where nothing lands, rows at or past T_b included.  A pair whose score is -inf or whose weight is exactly 0 adds
+ * nothing (0 * NaN never appears); a non-finite weight on a finite score is the caller's.
+ * The call is stateless: it recomputes the alpha rows into scratch from the stream-ordered pool, max_b T_b * (2 *
+ * max_length + 1) floats per pair, at most 256 MiB per pair of launches; beyond that the pairs run in slices, bit-equal
+ * to the unsliced run (the environment variable GTNX_CTC_SCORE_SCRATCH_BYTES, read per call, lowers the cap: a debug
+ * switch for tests); a single pair above the cap runs alone with scratch of its own size.  The sums are taken in one
+ * fixed order by plain loads and stores -- within a pair and frame the states of one label ascending, the pairs of an
+ * utterance in k order by one workgroup -- so the gradient has the same bits run to run; there are no floating-point
+ * atomics.  n * N == 0 returns without touching a device AND WITHOUT WRITING grad. */
+gtnx_status_t gtnx_batch_ctc_score_grad(gtnx_batch_t ems, const int* frames, int blank, const void* tokens_device,
+                                        int64_t row_stride, const void* lengths_device, int N, int L, int max_length,
+                                        const void* weights_device, void* grad_device);
+/* calls of either kind that have launched so far (process-wide) / pairs they took */
+gtnx_status_t gtnx_batch_ctc_score_stats(int64_t* calls, int64_t* pairs);
 /* rows M and labels C of the slabs of a gtnx_batch_linear / _rows batch; -1, -1 for any other batch */
 gtnx_status_t gtnx_batch_linear_shape(gtnx_batch_t ems, int* rows, int* labels);
 gtnx_status_t gtnx_batch_backward(gtnx_batch_t a, int retain_graph);                  /* autograd.cpp:17-67 */
