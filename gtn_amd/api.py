@@ -62,6 +62,41 @@ def make_api(lib):
             return int(x.data_ptr())
         return int(x)
 
+    def _opt_ptr(x):
+        """_as_dev_ptr of an argument that may be None"""
+        return _as_dev_ptr(x) if x is not None else None
+
+    def _row_tensors(who, names, tensors, n, row_stride, width_name):
+        """the one row stride of the int32 [B, width] outputs among `tensors` (None and device addresses are passed
+        over: those go by `row_stride`)"""
+        stride = row_stride
+        for t in tensors:
+            if t is None or not hasattr(t, "data_ptr"):
+                continue
+            if t.element_size() != 4 or t.dim() != 2 or t.shape[0] < n or (t.shape[1] > 1 and t.stride(1) != 1):
+                raise ValueError(f"{who}: outputs must be int32 tensors [B, {width_name}] with contiguous rows")
+            if stride is not None and t.stride(0) != stride:
+                raise ValueError(f"{who}: {names} must have the same row stride")
+            stride = t.stride(0)
+        if stride is None:
+            raise ValueError(f"{who}: a device address needs row_stride")
+        return int(stride)
+
+    def _frames_arg(who, frames, n):
+        """(host int32 array [n] or None, its address or None) of per-element frame counts; the caller keeps the array"""
+        if frames is None:
+            return None, None
+        fr = np.ascontiguousarray(frames, dtype=np.int32)
+        if fr.shape != (n,):
+            raise ValueError(f"{who}: one frame count per element")
+        return fr, fr.ctypes.data
+
+    def _stats2(cfn):
+        """the two counters of a gtnx_*_stats getter"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(cfn(C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     class Graph:
         """gtn.Graph (bindings/python/gtn/_graph.cpp:23-108)."""
 
@@ -738,24 +773,11 @@ def make_api(lib):
             argument order (there `tokens_out` = index into the label sequence, never -1 inside a path: ASG has no
             blanks); other batches go through viterbi_path (tokens_out and frames are errors there)."""
             n = len(self)
-            stride = row_stride
-            for t in (labels_out, tokens_out):
-                if t is None or not hasattr(t, "data_ptr"):
-                    continue
-                if t.element_size() != 4 or t.dim() != 2 or t.shape[0] < n or (t.shape[1] > 1 and t.stride(1) != 1):
-                    raise ValueError("viterbi_align: outputs must be int32 tensors [B, T] with contiguous rows")
-                if stride is not None and t.stride(0) != stride:
-                    raise ValueError("viterbi_align: labels_out and tokens_out must have the same row stride")
-                stride = t.stride(0)
-            if stride is None:
-                raise ValueError("viterbi_align: a device address needs row_stride")
-            fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32)
-            if fr is not None and fr.shape != (n,):
-                raise ValueError("viterbi_align: one frame count per element")
-            check(lib.gtnx_batch_viterbi_align(self._h, fr.ctypes.data if fr is not None else None,
-                                               _as_dev_ptr(labels_out), int(stride),
-                                               _as_dev_ptr(tokens_out) if tokens_out is not None else None,
-                                               _as_dev_ptr(scores_out) if scores_out is not None else None))
+            stride = _row_tensors("viterbi_align", "labels_out and tokens_out", (labels_out, tokens_out), n, row_stride,
+                                  "T")
+            fr, fr_ptr = _frames_arg("viterbi_align", frames, n)
+            check(lib.gtnx_batch_viterbi_align(self._h, fr_ptr, _as_dev_ptr(labels_out), stride, _opt_ptr(tokens_out),
+                                               _opt_ptr(scores_out)))
 
         def viterbi_decode(self, transitions, labels_out, scores_out=None, frames=None, collapsed_out=None,
                            lengths_out=None, row_stride=None):
@@ -771,27 +793,13 @@ def make_api(lib):
             output; exact ties: first accept node, then the smallest source node.  Other graphs / batches go through
             viterbi_path and one upload (`frames` is an error there)."""
             n = len(self)
-            stride = row_stride
-            for t in (labels_out, collapsed_out):
-                if t is None or not hasattr(t, "data_ptr"):
-                    continue
-                if t.element_size() != 4 or t.dim() != 2 or t.shape[0] < n or (t.shape[1] > 1 and t.stride(1) != 1):
-                    raise ValueError("viterbi_decode: outputs must be int32 tensors [B, M] with contiguous rows")
-                if stride is not None and t.stride(0) != stride:
-                    raise ValueError("viterbi_decode: labels_out and collapsed_out must have the same row stride")
-                stride = t.stride(0)
-            if stride is None:
-                raise ValueError("viterbi_decode: a device address needs row_stride")
+            stride = _row_tensors("viterbi_decode", "labels_out and collapsed_out", (labels_out, collapsed_out), n,
+                                  row_stride, "M")
             if lengths_out is not None and collapsed_out is None:
                 raise ValueError("viterbi_decode: lengths_out needs collapsed_out")
-            fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32)
-            if fr is not None and fr.shape != (n,):
-                raise ValueError("viterbi_decode: one frame count per element")
-            check(lib.gtnx_batch_viterbi_decode(self._h, transitions._h, fr.ctypes.data if fr is not None else None,
-                                                _as_dev_ptr(labels_out), int(stride),
-                                                _as_dev_ptr(scores_out) if scores_out is not None else None,
-                                                _as_dev_ptr(collapsed_out) if collapsed_out is not None else None,
-                                                _as_dev_ptr(lengths_out) if lengths_out is not None else None))
+            fr, fr_ptr = _frames_arg("viterbi_decode", frames, n)
+            check(lib.gtnx_batch_viterbi_decode(self._h, transitions._h, fr_ptr, _as_dev_ptr(labels_out), stride,
+                                                _opt_ptr(scores_out), _opt_ptr(collapsed_out), _opt_ptr(lengths_out)))
 
         def linear_decode(self, labels_out, scores_out=None, frames=None, blank=-1, collapsed_out=None,
                           starts_out=None, lengths_out=None, row_stride=None):
@@ -808,29 +816,14 @@ def make_api(lib):
             A Batch.linear is two launches with no copy back and no wait; rows from T_b on are never read.  Other
             batches go through viterbi_path and one upload (`frames` is an error there)."""
             n = len(self)
-            stride = row_stride
-            for t in (labels_out, collapsed_out, starts_out):
-                if t is None or not hasattr(t, "data_ptr"):
-                    continue
-                if t.element_size() != 4 or t.dim() != 2 or t.shape[0] < n or (t.shape[1] > 1 and t.stride(1) != 1):
-                    raise ValueError("linear_decode: outputs must be int32 tensors [B, M] with contiguous rows")
-                if stride is not None and t.stride(0) != stride:
-                    raise ValueError("linear_decode: labels_out, collapsed_out and starts_out must have the same "
-                                     "row stride")
-                stride = t.stride(0)
-            if stride is None:
-                raise ValueError("linear_decode: a device address needs row_stride")
+            stride = _row_tensors("linear_decode", "labels_out, collapsed_out and starts_out",
+                                  (labels_out, collapsed_out, starts_out), n, row_stride, "M")
             if (lengths_out is not None or starts_out is not None) and collapsed_out is None:
                 raise ValueError("linear_decode: lengths_out and starts_out need collapsed_out")
-            fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32)
-            if fr is not None and fr.shape != (n,):
-                raise ValueError("linear_decode: one frame count per element")
-            check(lib.gtnx_batch_linear_decode(self._h, fr.ctypes.data if fr is not None else None, int(blank),
-                                               _as_dev_ptr(labels_out), int(stride),
-                                               _as_dev_ptr(scores_out) if scores_out is not None else None,
-                                               _as_dev_ptr(collapsed_out) if collapsed_out is not None else None,
-                                               _as_dev_ptr(starts_out) if starts_out is not None else None,
-                                               _as_dev_ptr(lengths_out) if lengths_out is not None else None))
+            fr, fr_ptr = _frames_arg("linear_decode", frames, n)
+            check(lib.gtnx_batch_linear_decode(self._h, fr_ptr, int(blank), _as_dev_ptr(labels_out), stride,
+                                               _opt_ptr(scores_out), _opt_ptr(collapsed_out), _opt_ptr(starts_out),
+                                               _opt_ptr(lengths_out)))
 
         def ctc_beam_decode(self, tokens_out, lengths_out, scores_out, frames=None, blank=0, beam_size=16,
                             cutoff_top_n=16, nbest=1, row_stride=None):
@@ -867,15 +860,10 @@ def make_api(lib):
                 if o is not None and hasattr(o, "data_ptr") and (str(o.dtype) != dt or not o.is_contiguous()
                                                                  or o.numel() < n * int(nbest)):
                     raise ValueError(f"ctc_beam_decode: {what} contiguous tensor [B, nbest]")
-            fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32)
-            if fr is not None and fr.shape != (n,):
-                raise ValueError("ctc_beam_decode: one frame count per element")
-            check(lib.gtnx_batch_ctc_beam_decode(self._h, fr.ctypes.data if fr is not None else None, int(blank),
-                                                 int(beam_size), int(cutoff_top_n), int(nbest),
-                                                 _as_dev_ptr(tokens_out) if tokens_out is not None else None,
-                                                 int(stride),
-                                                 _as_dev_ptr(lengths_out) if lengths_out is not None else None,
-                                                 _as_dev_ptr(scores_out) if scores_out is not None else None))
+            fr, fr_ptr = _frames_arg("ctc_beam_decode", frames, n)
+            check(lib.gtnx_batch_ctc_beam_decode(self._h, fr_ptr, int(blank), int(beam_size), int(cutoff_top_n),
+                                                 int(nbest), _opt_ptr(tokens_out), int(stride), _opt_ptr(lengths_out),
+                                                 _opt_ptr(scores_out)))
 
         def _ctc_score_args(self, who, tokens, lengths, frames, N, L, row_stride, max_length):
             """(frames array or None, tokens address, row stride, lengths address, N, L, max_length) of a ctc_score call"""
@@ -902,9 +890,7 @@ def make_api(lib):
                     raise ValueError(f"{who}: lengths must be an int32 contiguous tensor [B, N]")
                 if hasattr(lengths, "is_cuda") and not lengths.is_cuda:
                     raise ValueError(f"{who}: lengths must be a CUDA tensor")
-            fr = None if frames is None else np.ascontiguousarray(frames, dtype=np.int32)
-            if fr is not None and fr.shape != (n,):
-                raise ValueError(f"{who}: one frame count per element")
+            fr, _ = _frames_arg(who, frames, n)
             if max_length is None:
                 m, c = C.c_int(-1), C.c_int(-1)
                 check(lib.gtnx_batch_linear_shape(self._h, C.byref(m), C.byref(c)))
@@ -930,10 +916,8 @@ def make_api(lib):
                     raise ValueError("ctc_score: scores_out must be a float32 contiguous tensor [B, N]")
                 if len(self) * N == 0:
                     return
-            check(lib.gtnx_batch_ctc_score(self._h, fr.ctypes.data if fr is not None else None, int(blank),
-                                           _as_dev_ptr(tok) if tok is not None else None, stride,
-                                           _as_dev_ptr(ln) if ln is not None else None, N, L, U,
-                                           _as_dev_ptr(scores_out) if scores_out is not None else None))
+            check(lib.gtnx_batch_ctc_score(self._h, fr.ctypes.data if fr is not None else None, int(blank), _opt_ptr(tok),
+                                           stride, _opt_ptr(ln), N, L, U, _opt_ptr(scores_out)))
 
         def ctc_score_grad(self, tokens, lengths, weights, grad_out, frames=None, blank=0, max_length=None, N=None,
                            L=None, row_stride=None):
@@ -960,10 +944,8 @@ def make_api(lib):
                 if len(self) * N == 0:
                     return
             check(lib.gtnx_batch_ctc_score_grad(self._h, fr.ctypes.data if fr is not None else None, int(blank),
-                                                _as_dev_ptr(tok) if tok is not None else None, stride,
-                                                _as_dev_ptr(ln) if ln is not None else None, N, L, U,
-                                                _as_dev_ptr(weights) if weights is not None else None,
-                                                _as_dev_ptr(grad_out) if grad_out is not None else None))
+                                                _opt_ptr(tok), stride, _opt_ptr(ln), N, L, U, _opt_ptr(weights),
+                                                _opt_ptr(grad_out)))
 
     ns.Batch = Batch
 
@@ -1076,51 +1058,37 @@ def make_api(lib):
     def debug_viterbi_ties():
         """(seen, unresolved): best paths of symbolic dense-partner products that ran through an exact tie / of those,
         the ones whose product was too large to rebuild and replay the reference's queue on (include/gtn_amd.h)"""
-        a, b = C.c_int64(0), C.c_int64(0)
-        check(lib.gtnx_debug_viterbi_ties(C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value)
+        return _stats2(lib.gtnx_debug_viterbi_ties)
 
     def debug_align_stats():
         """(fast, fallback): utterances Batch.viterbi_align has aligned so far by its one launch / through the path
         graphs of viterbi_path (include/gtn_amd.h: gtnx_batch_align_stats)"""
-        a, b = C.c_int64(0), C.c_int64(0)
-        check(lib.gtnx_batch_align_stats(C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value)
+        return _stats2(lib.gtnx_batch_align_stats)
 
     def debug_decode_stats():
         """(fast, fallback): utterances Batch.viterbi_decode has decoded so far by its one launch / through the path
         graphs of viterbi_path (include/gtn_amd.h: gtnx_batch_decode_stats)"""
-        a, b = C.c_int64(0), C.c_int64(0)
-        check(lib.gtnx_batch_decode_stats(C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value)
+        return _stats2(lib.gtnx_batch_decode_stats)
 
     def debug_linear_decode_stats():
         """(fast, fallback): utterances Batch.linear_decode has decoded so far by its two launches / through the path
         graphs of viterbi_path (include/gtn_amd.h: gtnx_batch_linear_decode_stats)"""
-        a, b = C.c_int64(0), C.c_int64(0)
-        check(lib.gtnx_batch_linear_decode_stats(C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value)
+        return _stats2(lib.gtnx_batch_linear_decode_stats)
 
     def debug_ctc_beam_stats():
         """(calls, utterances): calls of Batch.ctc_beam_decode that have launched so far and the utterances they
         decoded (include/gtn_amd.h: gtnx_batch_ctc_beam_stats)"""
-        a, b = C.c_int64(0), C.c_int64(0)
-        check(lib.gtnx_batch_ctc_beam_stats(C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value)
+        return _stats2(lib.gtnx_batch_ctc_beam_stats)
 
     def debug_ctc_score_stats():
         """(calls, pairs): calls of Batch.ctc_score / Batch.ctc_score_grad that have launched so far and the pairs they
         took (include/gtn_amd.h: gtnx_batch_ctc_score_stats)"""
-        a, b = C.c_int64(0), C.c_int64(0)
-        check(lib.gtnx_batch_ctc_score_stats(C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value)
+        return _stats2(lib.gtnx_batch_ctc_score_stats)
 
     def debug_edit_distance_stats():
         """(calls, pairs): calls of edit_distance that have launched so far and the pairs they computed
         (include/gtn_amd.h: gtnx_batch_edit_distance_stats)"""
-        a, b = C.c_int64(0), C.c_int64(0)
-        check(lib.gtnx_batch_edit_distance_stats(C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value)
+        return _stats2(lib.gtnx_batch_edit_distance_stats)
 
     def edit_distance(hyp, hyp_lengths, ref, ref_lengths, dist_out, ops_out=None, B=None, N=None, L=None, U=None,
                       hyp_stride=None, ref_stride=None):
@@ -1187,19 +1155,15 @@ def make_api(lib):
         if b * n == 0 and tensors:
             return  # (no pair, nothing to launch -- and an empty tensor has no address to hand to the engine)
 
-        def addr(x):
-            return _as_dev_ptr(x) if x is not None else None
-
-        check(lib.gtnx_batch_edit_distance(addr(hyp), int(hyp_stride), addr(hyp_lengths), addr(ref), int(ref_stride),
-                                           addr(ref_lengths), b, n, l, u, addr(dist_out), addr(ops_out)))
+        check(lib.gtnx_batch_edit_distance(_opt_ptr(hyp), int(hyp_stride), _opt_ptr(hyp_lengths), _opt_ptr(ref),
+                                           int(ref_stride), _opt_ptr(ref_lengths), b, n, l, u, _opt_ptr(dist_out),
+                                           _opt_ptr(ops_out)))
 
     def debug_full_connect_stats():
         """(fast, fallback): utterances whose ASG full-connect score forward_score(compose(Batch.linear(rows=...),
         transitions)) came from the one launch of asg_full.hip / utterances of such a padded batch that took the composed
         elements instead (include/gtn_amd.h: gtnx_batch_full_connect_stats)"""
-        a, b = C.c_int64(0), C.c_int64(0)
-        check(lib.gtnx_batch_full_connect_stats(C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value)
+        return _stats2(lib.gtnx_batch_full_connect_stats)
 
     if hasattr(lib, "gtnx_batch_align_stats"):
         ns.debug_align_stats = debug_align_stats

@@ -1168,758 +1168,6 @@ BatchP batch_viterbi_path(const BatchP& x) {
   return batch_from_graphs(op_viterbi_path(x->graphs));
 }
 
-// ---- forced alignment with device-resident output (align.hip) ------------------------------------------------
-namespace {
-std::atomic<int64_t> g_align_fast{0}, g_align_fallback{0};
-
-// every other batch: the path graphs of batch_viterbi_path, their labels read on the host, one upload
-void align_fallback(const BatchP& x, const int* frames, int* labels_dev, int64_t row_stride, int* tokens_dev,
-                    float* scores_dev) {
-  if (tokens_dev)
-    throw_invalid("[gtnx_batch_viterbi_align] token indices are defined for device-built CTC targets or ASG force-alignment "
-                  "acceptors composed with a linear batch only (this batch takes the path-graph route)");
-  if (frames)
-    throw_invalid("[gtnx_batch_viterbi_align] per-utterance frame counts need device-built CTC targets or ASG "
-                  "force-alignment acceptors composed with a linear batch (this batch takes the path-graph route)");
-  GTNX_HOST_T("batch.viterbi_align.fallback");
-  Runtime& rt = Runtime::get();
-  const int n = x->n;
-  // (a PRODUCT's rows are as long as its chains; other batches: as long as the longest path)
-  int64_t width = (x->kind == Batch::PRODUCT && x->chain && x->chain->kind == Batch::LINEAR) ? x->chain->M : 0;
-  BatchP paths = batch_viterbi_path(x);
-  for (int b = 0; b < n; ++b) width = std::max<int64_t>(width, paths->graphs[size_t(b)].num_arcs());
-  if (width > row_stride) throw_invalid("[gtnx_batch_viterbi_align] row_stride is shorter than the longest path");
-  PinnedMemP hl = rt.alloc_pinned(sizeof(int) * size_t(n) * size_t(width ? width : 1));
-  PinnedMemP hs = rt.alloc_pinned(sizeof(float) * size_t(n));
-  std::fill(hl->as<int>(), hl->as<int>() + size_t(n) * size_t(width), -1);
-  for (int b = 0; b < n; ++b) {
-    Graph& g = paths->graphs[size_t(b)];
-    const int64_t len = g.num_arcs();
-    float score = g.num_nodes() > 0 ? 0.0f : -std::numeric_limits<float>::infinity();
-    if (len > 0) {
-      g.s->ensure_host();
-      std::copy(g.s->il.begin(), g.s->il.begin() + len, hl->as<int>() + size_t(b) * size_t(width));
-      const float* w = g.weights_host(false);
-      for (int64_t t = 0; t < len; ++t) score += w[t];  // (in path order, as the recursion accumulates it)
-    }
-    hs->as<float>()[b] = score;
-  }
-  if (width > 0)
-    HIP_CHECK(hipMemcpy2DAsync(labels_dev, sizeof(int) * size_t(row_stride), hl->ptr, sizeof(int) * size_t(width),
-                               sizeof(int) * size_t(width), size_t(n), hipMemcpyHostToDevice, rt.stream()));
-  if (scores_dev) rt.h2d_pinned(scores_dev, hs->ptr, sizeof(float) * size_t(n));
-  g_align_fallback.fetch_add(n);
-}
-}  // namespace
-
-void batch_align_stats(int64_t* fast, int64_t* fallback) {
-  if (fast) *fast = g_align_fast.load();
-  if (fallback) *fallback = g_align_fallback.load();
-}
-
-void batch_viterbi_align(const BatchP& x, const int* frames, int* labels_dev, int64_t row_stride, int* tokens_dev,
-                         float* scores_dev) {
-  GTNX_HOST_T("batch.viterbi_align");
-  Runtime& rt = Runtime::get();  // (first: without a device this is a device error, whatever the arguments)
-  if (!labels_dev) throw_invalid("[gtnx_batch_viterbi_align] null labels pointer");
-  if (row_stride < 0) throw_invalid("[gtnx_batch_viterbi_align] negative row stride");
-  const int n = x->n;
-  if (n <= 0) return;
-  // a kernel of this device writes the results: memory of another GPU of the process is refused, not written
-  if (!ptr_local_to(labels_dev, rt.device()) || (tokens_dev && !ptr_local_to(tokens_dev, rt.device())) ||
-      (scores_dev && !ptr_local_to(scores_dev, rt.device())))
-    throw_invalid("[gtnx_batch_viterbi_align] an output pointer is not memory of the engine's current device");
-  bool fast = x->kind == Batch::PRODUCT && x->fixed && x->chain && x->fixed->kind == Batch::CTC_TARGETS && !x->fixed->fal &&
-              x->chain->kind == Batch::LINEAR && x->fixed->rec_mem && x->fixed->n == n && x->chain->n == n;
-  if (fast) {
-    const Batch& fx = *x->fixed;
-    const Batch& ch = *x->chain;
-    const int vec = ch.C % 4 == 0 && (reinterpret_cast<uintptr_t>(ch.w_dev) & 15) == 0;
-    fast = band_align_ok(fx.max_nodes, ch.C, vec) && fx.max_label < ch.C;
-    // the closed form of the queue ranks (ops_band.cpp tie_ranks) holds with the blank below every label
-    for (size_t i = 0; i < fx.labels.size() && fast; ++i) fast = fx.labels[i] > fx.blank;
-  }
-  // ... or of device-built force-alignment acceptors o ASG transitions (asg_align.hip), either argument order
-  bool asg = x->kind == Batch::PRODUCT && x->fixed && x->chain && x->fixed->kind == Batch::CTC_TARGETS && x->fixed->fal &&
-             x->chain->kind == Batch::LINEAR && x->fixed->rec_mem && x->fixed->n == n && x->chain->n == n;
-  if (asg) {
-    const Batch& fx = *x->fixed;
-    const Batch& ch = *x->chain;
-    const int vec = ch.C % 4 == 0 && (reinterpret_cast<uintptr_t>(ch.w_dev) & 15) == 0;
-    asg = asg_align_ok(fx.max_nodes, ch.C, vec) && fx.trans_labels == ch.C && fx.max_label < ch.C;
-  }
-  if (!fast && !asg) {
-    align_fallback(x, frames, labels_dev, row_stride, tokens_dev, scores_dev);
-    return;
-  }
-  Batch& fx = *x->fixed;
-  Batch& ch = *x->chain;
-  const int T = ch.M, C = ch.C;
-  if (row_stride < T) throw_invalid("[gtnx_batch_viterbi_align] row_stride is shorter than the chains");
-  if (frames)
-    for (int b = 0; b < n; ++b) {
-      if (frames[b] < 0 || frames[b] > T) throw_invalid("[gtnx_batch_viterbi_align] a frame count outside 0 .. T");
-      if (frames[b] > ch.rows_of(b))
-        throw_invalid("[gtnx_batch_viterbi_align] a frame count beyond the rows the chain carries");
-    }
-  if (ch.w_pend) ch.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
-  if (asg) {
-    // back-pointer planes: 1 bit per (time, node), one 256-byte row of words per 32 / NPL steps, NPL the LAUNCH's
-    const int npl = asg_align_npl(fx.max_nodes);
-    const size_t plane = asg_align_plane_bytes(T, npl);
-    DevMemP work = rt.alloc(plane * size_t(n));
-    std::vector<AsgAlignArgs> tab(static_cast<size_t>(n));
-    double abytes = 0;
-    for (int b = 0; b < n; ++b) {
-      AsgAlignArgs& a = tab[size_t(b)];
-      a = AsgAlignArgs{};
-      const int U = fx.lab_off[size_t(b) + 1] - fx.lab_off[size_t(b)];
-      const size_t N = size_t(U) + 1;
-      char* base = fx.rec_mem->as<char>(fx.rec_off[size_t(b)]);
-      a.nodes = reinterpret_cast<BandNode*>(base);
-      a.nflags = reinterpret_cast<uint8_t*>(base + align_up(sizeof(BandNode) * N, 64));
-      a.w = fx.rec_mem->as<float>(fx.w_off[size_t(b)]);
-      a.em = ch.w_dev + size_t(b) * size_t(T) * size_t(C);
-      a.bp = work->as<unsigned>(plane * size_t(b));
-      a.labels = labels_dev + int64_t(b) * row_stride;
-      a.tokens = tokens_dev ? tokens_dev + int64_t(b) * row_stride : nullptr;
-      a.score = scores_dev ? scores_dev + b : nullptr;
-      a.N = int(N);
-      a.T = frames ? frames[b] : ch.rows_of(b);
-      a.T_full = T;
-      a.C = C;
-      abytes += 4.0 * a.T * C + 0.25 * double(a.T) * double(N) + 8.0 * a.T;
-    }
-    DevMemP d = upload_vec(tab);
-    GTNX_PROF("asg_viterbi_align", abytes);
-    launch_asg_align(d->as<AsgAlignArgs>(), n, fx.max_nodes, rt.stream());
-    g_align_fast.fetch_add(n);
-    return;
-  }
-  // back-pointer planes: 2 bits per (time, node), one 256-byte row of words per 16 / NPL steps (align.hip)
-  const int npl = align_npl(fx.max_nodes);
-  const size_t plane = align_up((size_t(T) * size_t(npl) + 15) / 16 * 256 + 256, 256);
-  DevMemP work = rt.alloc(plane * size_t(n));
-  std::vector<AlignArgs> tab(static_cast<size_t>(n));
-  double abytes = 0;
-  for (int b = 0; b < n; ++b) {
-    AlignArgs& a = tab[size_t(b)];
-    a = AlignArgs{};
-    const int* t = fx.labels.data() + fx.lab_off[size_t(b)];
-    const int U = fx.lab_off[size_t(b) + 1] - fx.lab_off[size_t(b)];
-    const size_t N = size_t(2 * U + 1);
-    char* base = fx.rec_mem->as<char>(fx.rec_off[size_t(b)]);
-    a.nodes = reinterpret_cast<BandNode*>(base);
-    a.nflags = reinterpret_cast<uint8_t*>(base + align_up(sizeof(BandNode) * N, 64));
-    a.em = ch.w_dev + size_t(b) * size_t(T) * size_t(C);
-    a.bp = work->as<unsigned>(plane * size_t(b));
-    a.labels = labels_dev + int64_t(b) * row_stride;
-    a.tokens = tokens_dev ? tokens_dev + int64_t(b) * row_stride : nullptr;
-    a.score = scores_dev ? scores_dev + b : nullptr;
-    a.N = int(N);
-    a.T = frames ? frames[b] : ch.rows_of(b);
-    a.T_full = T;
-    a.C = C;
-    int p = 0;
-    while (p + 1 < U && t[p] < t[p + 1]) ++p;
-    a.p = p;
-    abytes += 4.0 * a.T * C + 0.5 * double(a.T) * double(N) + 8.0 * a.T;
-  }
-  DevMemP d = upload_vec(tab);
-  GTNX_PROF("band_viterbi_align", abytes);
-  launch_band_align(d->as<AlignArgs>(), n, fx.max_nodes, rt.stream());
-  g_align_fast.fetch_add(n);
-}
-
-// ---- decode against one shared transitions graph with device-resident output (asg_decode.hip) ----------------
-namespace {
-std::atomic<int64_t> g_decode_fast{0}, g_decode_fallback{0};
-
-// every other graph or batch: viterbiPath over the composed elements, labels read and collapsed on the host, one upload
-void decode_fallback(const BatchP& ems, Graph& transitions, const int* frames, int* labels_dev, int64_t row_stride,
-                     float* scores_dev, int* collapsed_dev, int* lengths_dev) {
-  if (frames)
-    throw_invalid("[gtnx_batch_viterbi_decode] per-utterance frame counts need a linear batch and a dense transitions "
-                  "graph of 8 .. 1024 nodes whose ties go by node order (this batch takes the path-graph route, which "
-                  "decodes the rows the elements carry: pass frames = null)");
-  GTNX_HOST_T("batch.viterbi_decode.fallback");
-  Runtime& rt = Runtime::get();
-  const int n = ems->n;
-  batch_materialise(*ems);
-  std::vector<Graph> tr{transitions};
-  std::vector<Graph> comp = op_compose(ems->graphs, tr, false);
-  std::vector<Graph> paths = op_viterbi_path(comp);
-  int64_t width = ems->kind == Batch::LINEAR ? ems->M : 0;
-  for (int b = 0; b < n; ++b) width = std::max<int64_t>(width, paths[size_t(b)].num_arcs());
-  if (width > row_stride) throw_invalid("[gtnx_batch_viterbi_decode] row_stride is shorter than the longest path");
-  const size_t cells = size_t(n) * size_t(width ? width : 1);
-  PinnedMemP hl = rt.alloc_pinned(sizeof(int) * cells * 2);
-  PinnedMemP hs = rt.alloc_pinned((sizeof(float) + sizeof(int)) * size_t(n));
-  int* lab = hl->as<int>();
-  int* col = lab + cells;
-  float* sc = hs->as<float>();
-  int* len_out = reinterpret_cast<int*>(sc + n);
-  std::fill(lab, lab + 2 * cells, -1);
-  for (int b = 0; b < n; ++b) {
-    Graph& g = paths[size_t(b)];
-    const int64_t len = g.num_arcs();
-    float score = (g.num_nodes() > 0 && len > 0) ? 0.0f : -std::numeric_limits<float>::infinity();
-    int k = 0;
-    if (len > 0) {
-      g.s->ensure_host();
-      int* row = lab + size_t(b) * size_t(width);
-      int* crow = col + size_t(b) * size_t(width);
-      std::copy(g.s->il.begin(), g.s->il.begin() + len, row);
-      const float* w = g.weights_host(false);
-      for (int64_t t = 0; t < len; ++t) {
-        score += w[t];  // (in path order, as the recursion accumulates it)
-        if (t == 0 || row[t] != row[t - 1]) crow[k++] = row[t];
-      }
-    }
-    sc[b] = score;
-    len_out[b] = k;
-  }
-  if (width > 0) {
-    HIP_CHECK(hipMemcpy2DAsync(labels_dev, sizeof(int) * size_t(row_stride), lab, sizeof(int) * size_t(width),
-                               sizeof(int) * size_t(width), size_t(n), hipMemcpyHostToDevice, rt.stream()));
-    if (collapsed_dev)
-      HIP_CHECK(hipMemcpy2DAsync(collapsed_dev, sizeof(int) * size_t(row_stride), col, sizeof(int) * size_t(width),
-                                 sizeof(int) * size_t(width), size_t(n), hipMemcpyHostToDevice, rt.stream()));
-  }
-  if (scores_dev) rt.h2d_pinned(scores_dev, sc, sizeof(float) * size_t(n));
-  if (lengths_dev) rt.h2d_pinned(lengths_dev, len_out, sizeof(int) * size_t(n));
-  g_decode_fallback.fetch_add(n);
-}
-}  // namespace
-
-void batch_decode_stats(int64_t* fast, int64_t* fallback) {
-  if (fast) *fast = g_decode_fast.load();
-  if (fallback) *fallback = g_decode_fallback.load();
-}
-
-void batch_viterbi_decode(const BatchP& ems, Graph& transitions, const int* frames, int* labels_dev, int64_t row_stride,
-                          float* scores_dev, int* collapsed_dev, int* lengths_dev) {
-  GTNX_HOST_T("batch.viterbi_decode");
-  // what the arguments alone decide comes first: no device is asked for an invalid call
-  if (!ems) throw_invalid("[gtnx_batch_viterbi_decode] null batch");
-  if (!labels_dev) throw_invalid("[gtnx_batch_viterbi_decode] null labels pointer");
-  if (row_stride < 0) throw_invalid("[gtnx_batch_viterbi_decode] negative row stride");
-  if (lengths_dev && !collapsed_dev)
-    throw_invalid("[gtnx_batch_viterbi_decode] lengths are those of the collapsed sequences: pass collapsed_device too");
-  const int n = ems->n;
-  const bool linear = ems->kind == Batch::LINEAR && !ems->leaf;
-  if (frames && linear)
-    for (int b = 0; b < n; ++b) {
-      if (frames[b] < 0 || frames[b] > ems->M) throw_invalid("[gtnx_batch_viterbi_decode] a frame count outside 0 .. M");
-      if (frames[b] > ems->rows_of(b))
-        throw_invalid("[gtnx_batch_viterbi_decode] a frame count beyond the rows the batch carries");
-    }
-  if (linear && n > 0 && row_stride < ems->M)
-    throw_invalid("[gtnx_batch_viterbi_decode] row_stride is shorter than the rows of the batch");
-  Runtime& rt = Runtime::get();
-  if (n <= 0) return;
-  // a kernel of this device writes the results: memory of another GPU of the process is refused, not written
-  if (!ptr_local_to(labels_dev, rt.device()) || (scores_dev && !ptr_local_to(scores_dev, rt.device())) ||
-      (collapsed_dev && !ptr_local_to(collapsed_dev, rt.device())) ||
-      (lengths_dev && !ptr_local_to(lengths_dev, rt.device())))
-    throw_invalid("[gtnx_batch_viterbi_decode] an output pointer is not memory of the engine's current device");
-  if (!linear || !ems->w_dev || !lazy_decode_ok(transitions, ems->M, ems->C)) {
-    decode_fallback(ems, transitions, frames, labels_dev, row_stride, scores_dev, collapsed_dev, lengths_dev);
-    return;
-  }
-  Batch& x = *ems;
-  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
-  // full-length views of the slabs (batch_materialise's elements with M rows whatever `rows` says): one shape, one
-  // group, one sweep -- the sweep reads the pad rows, the back-trace never looks at what it made of them
-  std::vector<Graph> chains;
-  chains.reserve(size_t(n));
-  std::vector<int> fr(static_cast<size_t>(n));
-  {
-    GraphSlabScope slab_scope(size_t(n));
-    const int64_t stride = int64_t(x.M) * x.C;
-    for (int i = 0; i < n; ++i) {
-      Graph g = Graph::make_result(false);
-      Structure& s = *g.s;
-      s.kind = KIND_LINEAR;
-      s.M = x.M;
-      s.C = x.C;
-      s.N = int64_t(x.M) + 1;
-      s.A = stride;
-      s.ilabel_sorted = s.olabel_sorted = true;
-      Weights& w = *g.w;
-      w.n = stride;
-      w.dev_mem = x.w_mem;
-      w.dev = x.w_dev + size_t(i) * size_t(stride);
-      w.dev_valid = true;
-      w.host_valid = false;
-      w.version++;
-      chains.push_back(std::move(g));
-      fr[size_t(i)] = frames ? frames[i] : x.rows_of(i);
-    }
-  }
-  lazy_viterbi_decode(chains, transitions, fr, labels_dev, row_stride, scores_dev, collapsed_dev, lengths_dev);
-  g_decode_fast.fetch_add(n);
-}
-
-// ---- best path of the chains themselves plus the CTC collapse, device-resident output (linear_decode.hip) ----
-namespace {
-std::atomic<int64_t> g_linear_decode_fast{0}, g_linear_decode_fallback{0};
-
-// every other batch: the path graphs of batch_viterbi_path, labels read and collapsed on the host, one upload
-void linear_decode_fallback(const BatchP& ems, int blank, int* labels_dev, int64_t row_stride,
-                            float* scores_dev, int* collapsed_dev, int* starts_dev, int* lengths_dev) {
-  GTNX_HOST_T("batch.linear_decode.fallback");
-  Runtime& rt = Runtime::get();
-  const int n = ems->n;
-  BatchP paths = batch_viterbi_path(ems);
-  int64_t width = ems->kind == Batch::LINEAR ? ems->M : 0;
-  for (int b = 0; b < n; ++b) width = std::max<int64_t>(width, paths->graphs[size_t(b)].num_arcs());
-  if (width > row_stride) throw_invalid("[gtnx_batch_linear_decode] row_stride is shorter than the longest path");
-  const size_t cells = size_t(n) * size_t(width ? width : 1);
-  PinnedMemP hl = rt.alloc_pinned(sizeof(int) * cells * 3);
-  PinnedMemP hs = rt.alloc_pinned((sizeof(float) + sizeof(int)) * size_t(n));
-  int* lab = hl->as<int>();
-  int* col = lab + cells;
-  int* sta = col + cells;
-  float* sc = hs->as<float>();
-  int* len_out = reinterpret_cast<int*>(sc + n);
-  std::fill(lab, lab + 3 * cells, -1);
-  for (int b = 0; b < n; ++b) {
-    Graph& g = paths->graphs[size_t(b)];
-    const int64_t len = g.num_arcs();
-    // (no path, zero frames included: the empty graph)
-    float score = g.num_nodes() > 0 ? 0.0f : -std::numeric_limits<float>::infinity();
-    int k = 0;
-    if (len > 0) {
-      g.s->ensure_host();
-      int* row = lab + size_t(b) * size_t(width);
-      int* crow = col + size_t(b) * size_t(width);
-      int* srow = sta + size_t(b) * size_t(width);
-      std::copy(g.s->il.begin(), g.s->il.begin() + len, row);
-      const float* w = g.weights_host(false);
-      for (int64_t t = 0; t < len; ++t) {
-        score += w[t];  // (in path order, as the recursion accumulates it)
-        if ((t == 0 || row[t] != row[t - 1]) && row[t] != blank) {
-          crow[k] = row[t];
-          srow[k++] = int(t);
-        }
-      }
-    }
-    sc[b] = score;
-    len_out[b] = k;
-  }
-  if (width > 0) {
-    int* src[3] = {lab, col, sta};
-    int* dst[3] = {labels_dev, collapsed_dev, starts_dev};
-    for (int i = 0; i < 3; ++i)
-      if (dst[i])
-        HIP_CHECK(hipMemcpy2DAsync(dst[i], sizeof(int) * size_t(row_stride), src[i], sizeof(int) * size_t(width),
-                                   sizeof(int) * size_t(width), size_t(n), hipMemcpyHostToDevice, rt.stream()));
-  }
-  if (scores_dev) rt.h2d_pinned(scores_dev, sc, sizeof(float) * size_t(n));
-  if (lengths_dev) rt.h2d_pinned(lengths_dev, len_out, sizeof(int) * size_t(n));
-  g_linear_decode_fallback.fetch_add(n);
-}
-}  // namespace
-
-void batch_linear_decode_stats(int64_t* fast, int64_t* fallback) {
-  if (fast) *fast = g_linear_decode_fast.load();
-  if (fallback) *fallback = g_linear_decode_fallback.load();
-}
-
-void batch_linear_decode(const BatchP& ems, const int* frames, int blank, int* labels_dev, int64_t row_stride,
-                         float* scores_dev, int* collapsed_dev, int* starts_dev, int* lengths_dev) {
-  GTNX_HOST_T("batch.linear_decode");
-  // what the arguments alone decide comes first: no device is asked for an invalid call
-  if (!ems) throw_invalid("[gtnx_batch_linear_decode] null batch");
-  if (!labels_dev) throw_invalid("[gtnx_batch_linear_decode] null labels pointer");
-  if (row_stride < 0) throw_invalid("[gtnx_batch_linear_decode] negative row stride");
-  if ((lengths_dev || starts_dev) && !collapsed_dev)
-    throw_invalid("[gtnx_batch_linear_decode] lengths and starts are those of the collapsed sequences: pass "
-                  "collapsed_device too");
-  const int n = ems->n;
-  const bool linear = ems->kind == Batch::LINEAR && !ems->leaf && ems->w_dev;
-  if (frames && !linear)
-    throw_invalid("[gtnx_batch_linear_decode] per-utterance frame counts need a native linear batch (this batch takes "
-                  "the path-graph route, which decodes the rows the elements carry: pass frames = null)");
-  if (frames)
-    for (int b = 0; b < n; ++b) {
-      if (frames[b] < 0 || frames[b] > ems->M) throw_invalid("[gtnx_batch_linear_decode] a frame count outside 0 .. M");
-      if (frames[b] > ems->rows_of(b))
-        throw_invalid("[gtnx_batch_linear_decode] a frame count beyond the rows the batch carries");
-    }
-  if (linear && n > 0 && row_stride < ems->M)
-    throw_invalid("[gtnx_batch_linear_decode] row_stride is shorter than the rows of the batch");
-  if (linear && blank >= ems->C) throw_invalid("[gtnx_batch_linear_decode] blank is not below the number of labels");
-  Runtime& rt = Runtime::get();
-  if (n <= 0) return;
-  // a kernel of this device writes the results: memory of another GPU of the process is refused, not written
-  if (!ptr_local_to(labels_dev, rt.device()) || (scores_dev && !ptr_local_to(scores_dev, rt.device())) ||
-      (collapsed_dev && !ptr_local_to(collapsed_dev, rt.device())) ||
-      (starts_dev && !ptr_local_to(starts_dev, rt.device())) ||
-      (lengths_dev && !ptr_local_to(lengths_dev, rt.device())))
-    throw_invalid("[gtnx_batch_linear_decode] an output pointer is not memory of the engine's current device");
-  Batch& x = *ems;
-  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
-  if (!linear) {
-    linear_decode_fallback(ems, blank, labels_dev, row_stride, scores_dev, collapsed_dev, starts_dev,
-                           lengths_dev);
-    return;
-  }
-  std::vector<int> fr(static_cast<size_t>(n));
-  // algorithmic bytes: every emission of the rows that count once, label and maximum out / back in, the pad of the
-  // label rows, the collapsed rows
-  double row_bytes = 0, col_bytes = 0;
-  for (int b = 0; b < n; ++b) {
-    const int t = fr[size_t(b)] = frames ? frames[b] : x.rows_of(b);
-    row_bytes += 4.0 * x.C * t + 8.0 * t;
-    col_bytes += 8.0 * t + 4.0 * (x.M - t) + (collapsed_dev ? 8.0 * x.M : 0.0);
-  }
-  DevMemP d_frames = upload_vec(fr);
-  DevMemP rowmax = rt.alloc(sizeof(float) * std::max<size_t>(size_t(n) * size_t(x.M), 1));
-  LinearDecodeArgs a{};
-  a.em = x.w_dev;
-  a.frames = d_frames->as<int>();
-  a.labels = labels_dev;
-  a.rowmax = rowmax->as<float>();
-  a.scores = scores_dev;
-  a.collapsed = collapsed_dev;
-  a.starts = starts_dev;
-  a.lengths = lengths_dev;
-  a.row_stride = row_stride;
-  a.n = n;
-  a.M = x.M;
-  a.C = x.C;
-  a.blank = blank;
-  {
-    GTNX_PROF("linear_decode_rows", row_bytes);
-    launch_linear_decode(a, 0, rt.stream());
-  }
-  {
-    GTNX_PROF("linear_decode_collapse", col_bytes);
-    launch_linear_decode(a, 1, rt.stream());
-  }
-  // (the scratch and the table go back to the stream-ordered pool behind the launches)
-  g_linear_decode_fast.fetch_add(n);
-}
-
-// ---- CTC prefix beam search with N-best output, device-resident (ctc_beam.hip) ----
-namespace {
-std::atomic<int64_t> g_ctc_beam_calls{0}, g_ctc_beam_utts{0};
-}  // namespace
-
-void batch_ctc_beam_stats(int64_t* calls, int64_t* utterances) {
-  if (calls) *calls = g_ctc_beam_calls.load();
-  if (utterances) *utterances = g_ctc_beam_utts.load();
-}
-
-void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int beam, int topn, int nbest,
-                           int* tokens_dev, int64_t row_stride, int* lengths_dev, float* scores_dev) {
-  GTNX_HOST_T("batch.ctc_beam_decode");
-  // what the arguments alone decide comes first: no device is asked for an invalid call
-  if (!ems) throw_invalid("[gtnx_batch_ctc_beam_decode] null batch");
-  if (!tokens_dev || !lengths_dev || !scores_dev)
-    throw_invalid("[gtnx_batch_ctc_beam_decode] null output pointer (tokens, lengths and scores are all written)");
-  if (row_stride < 0) throw_invalid("[gtnx_batch_ctc_beam_decode] negative row stride");
-  if (beam < 1 || beam > 64) throw_invalid("[gtnx_batch_ctc_beam_decode] beam_size outside 1 .. 64");
-  if (topn < 1 || topn > 32) throw_invalid("[gtnx_batch_ctc_beam_decode] cutoff_top_n outside 1 .. 32");
-  if (nbest < 1) throw_invalid("[gtnx_batch_ctc_beam_decode] nbest below 1");
-  if (nbest > beam) throw_invalid("[gtnx_batch_ctc_beam_decode] nbest above beam_size");
-  if (blank < 0) throw_invalid("[gtnx_batch_ctc_beam_decode] negative blank");
-  Runtime& rt = Runtime::get();
-  const int n = ems->n;
-  // there is no other route: the search runs on the slabs of a native linear batch
-  if (!(ems->kind == Batch::LINEAR && !ems->leaf && ems->w_dev))
-    throw_invalid("[gtnx_batch_ctc_beam_decode] not a native linear batch (gtnx_batch_linear / _rows)");
-  Batch& x = *ems;
-  if (frames)
-    for (int b = 0; b < n; ++b) {
-      if (frames[b] < 0 || frames[b] > x.M) throw_invalid("[gtnx_batch_ctc_beam_decode] a frame count outside 0 .. M");
-      if (frames[b] > x.rows_of(b))
-        throw_invalid("[gtnx_batch_ctc_beam_decode] a frame count beyond the rows the batch carries");
-    }
-  if (n > 0 && row_stride < x.M)
-    throw_invalid("[gtnx_batch_ctc_beam_decode] row_stride is shorter than the rows of the batch");
-  if (blank >= x.C) throw_invalid("[gtnx_batch_ctc_beam_decode] blank is not below the number of labels");
-  // (a candidate's key keeps its label in 25 bits; trie nodes are numbered 1 + t * beam + slot in an int)
-  if (x.C > (1 << 25)) throw_invalid("[gtnx_batch_ctc_beam_decode] more than 2^25 labels");
-  if (int64_t(x.M) * beam + 1 > std::numeric_limits<int>::max())
-    throw_invalid("[gtnx_batch_ctc_beam_decode] rows times beam_size does not fit an int");
-  if (n <= 0) return;
-  // a kernel of this device writes the results: memory of another GPU of the process is refused, not written
-  if (!ptr_local_to(tokens_dev, rt.device()) || !ptr_local_to(lengths_dev, rt.device()) ||
-      !ptr_local_to(scores_dev, rt.device()))
-    throw_invalid("[gtnx_batch_ctc_beam_decode] an output pointer is not memory of the engine's current device");
-  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
-  std::vector<int> fr(static_cast<size_t>(n));
-  // algorithmic bytes.  rows: every emission of the rows that count once, topn + 1 entries and a count out.  search:
-  // those back in, a trie node per kept extension (at most beam per frame), the output rows.
-  double row_bytes = 0, search_bytes = 0;
-  for (int b = 0; b < n; ++b) {
-    const int t = fr[size_t(b)] = frames ? frames[b] : x.rows_of(b);
-    row_bytes += (4.0 * x.C + 8.0 * (topn + 1) + 4.0) * t;
-    search_bytes += (8.0 * (topn + 1) + 4.0 + 8.0 * beam) * t + nbest * (4.0 * x.M + 8.0);
-  }
-  DevMemP d_frames = upload_vec(fr);
-  const size_t rows = std::max<size_t>(size_t(n) * size_t(x.M), 1);
-  DevMemP entries = rt.alloc(8 * rows * size_t(topn + 1));
-  DevMemP counts = rt.alloc(sizeof(int) * rows);
-  DevMemP trie = rt.alloc(8 * size_t(n) * (size_t(x.M) * size_t(beam) + 1));
-  CtcBeamArgs a{};
-  a.em = x.w_dev;
-  a.frames = d_frames->as<int>();
-  a.ent_val = entries->as<float>();
-  a.ent_cnt = counts->as<int>();
-  a.trie = trie->as<int>();
-  a.tokens = tokens_dev;
-  a.lengths = lengths_dev;
-  a.scores = scores_dev;
-  a.row_stride = row_stride;
-  a.n = n;
-  a.M = x.M;
-  a.C = x.C;
-  a.blank = blank;
-  a.beam = beam;
-  a.topn = topn;
-  a.nbest = nbest;
-  {
-    GTNX_PROF("ctc_beam_rows", row_bytes);
-    launch_ctc_beam(a, 0, rt.stream());
-  }
-  {
-    GTNX_PROF("ctc_beam_search", search_bytes);
-    launch_ctc_beam(a, 1, rt.stream());
-  }
-  // (the scratch and the table go back to the stream-ordered pool behind the launches)
-  g_ctc_beam_calls.fetch_add(1);
-  g_ctc_beam_utts.fetch_add(n);
-}
-
-
-// ---- batched edit distance of device-resident token rows (edit_distance.hip) ----
-namespace {
-std::atomic<int64_t> g_edit_distance_calls{0}, g_edit_distance_pairs{0};
-// what the walk's scratch of ONE launch may take; a call that needs more runs its pairs in slices of launches.  A pair
-// at the largest widths takes 64 MiB, so a slice always holds at least one pair.
-constexpr int64_t kEditDistanceScratchCap = int64_t(256) << 20;
-int64_t edit_distance_scratch_cap() {
-  // (debug switch, read per call: tests lower the cap to see a sliced call without allocating gigabytes)
-  const char* e = std::getenv("GTNX_EDIT_DISTANCE_SCRATCH_BYTES");
-  if (e && *e) {
-    const long long v = std::atoll(e);
-    if (v > 0) return std::min<int64_t>(v, kEditDistanceScratchCap);
-  }
-  return kEditDistanceScratchCap;
-}
-}  // namespace
-
-void batch_edit_distance_stats(int64_t* calls, int64_t* pairs) {
-  if (calls) *calls = g_edit_distance_calls.load();
-  if (pairs) *pairs = g_edit_distance_pairs.load();
-}
-
-void batch_edit_distance(const int* hyp_dev, int64_t hyp_stride, const int* hyp_len_dev, const int* ref_dev,
-                         int64_t ref_stride, const int* ref_len_dev, int B, int N, int L, int U, int* dist_dev,
-                         int* ops_dev) {
-  GTNX_HOST_T("batch.edit_distance");
-  // what the arguments alone decide comes first: no device is asked for an invalid call
-  if (!hyp_dev || !hyp_len_dev || !ref_dev || !ref_len_dev)
-    throw_invalid("[gtnx_batch_edit_distance] null input pointer (hyp, hyp_lengths, ref and ref_lengths are all read)");
-  if (!dist_dev) throw_invalid("[gtnx_batch_edit_distance] null dist pointer");
-  if (B < 0 || N < 0 || L < 0 || U < 0) throw_invalid("[gtnx_batch_edit_distance] negative B, N, L or U");
-  if (hyp_stride < 0 || ref_stride < 0) throw_invalid("[gtnx_batch_edit_distance] negative row stride");
-  if (hyp_stride < L) throw_invalid("[gtnx_batch_edit_distance] hyp_stride is shorter than the rows' width L");
-  if (ref_stride < U) throw_invalid("[gtnx_batch_edit_distance] ref_stride is shorter than the rows' width U");
-  // (the carries of a row of columns and the reference live in LDS; a lane of the wave owns one block of 64 rows)
-  if (L > kEditDistanceMaxL) throw_invalid("[gtnx_batch_edit_distance] L above 65536");
-  if (U > kEditDistanceMaxU) throw_invalid("[gtnx_batch_edit_distance] U above 4096");
-  const int64_t pairs = int64_t(B) * N;
-  if (pairs > std::numeric_limits<int>::max()) throw_invalid("[gtnx_batch_edit_distance] B times N does not fit an int");
-  if (pairs == 0) return;
-  Runtime& rt = Runtime::get();
-  // a kernel of this device writes the results: memory of another GPU of the process is refused, not written
-  if (!ptr_local_to(dist_dev, rt.device()) || (ops_dev && !ptr_local_to(ops_dev, rt.device())))
-    throw_invalid("[gtnx_batch_edit_distance] an output pointer is not memory of the engine's current device");
-  const int nbU = (U + 63) / 64;
-  EditDistanceArgs a{};
-  a.hyp = hyp_dev;
-  a.hyp_len = hyp_len_dev;
-  a.ref = ref_dev;
-  a.ref_len = ref_len_dev;
-  a.dist = dist_dev;
-  a.ops = ops_dev;
-  a.hyp_stride = hyp_stride;
-  a.ref_stride = ref_stride;
-  a.N = N;
-  a.L = L;
-  a.U = U;
-  a.nbU = nbU;
-  // algorithmic bytes, by the widths (the lengths are device memory: an upper bound): every token and length once, the
-  // distance out; with ops the (Pv, Mv) words of every (column, block) out and back in, and the three counts
-  const double io_bytes = double(pairs) * (4.0 * L + 8.0) + double(B) * (4.0 * U + 4.0);
-  if (!ops_dev) {
-    a.pair0 = 0;
-    a.count = int(pairs);
-    GTNX_PROF("edit_distance", io_bytes);
-    launch_edit_distance(a, rt.stream());
-  } else {
-    const int64_t per_pair = int64_t(16) * L * nbU;
-    const int64_t slice = per_pair > 0 ? std::max<int64_t>(1, edit_distance_scratch_cap() / per_pair) : pairs;
-    for (int64_t p0 = 0; p0 < pairs; p0 += slice) {
-      const int64_t cnt = std::min(slice, pairs - p0);
-      DevMemP words = rt.alloc(size_t(std::max<int64_t>(per_pair * cnt, 16)));
-      a.scratch = words->as<gtnx_ul2>();
-      a.pair0 = p0;
-      a.count = int(cnt);
-      GTNX_PROF("edit_distance_ops", (io_bytes / double(pairs) + 2.0 * double(per_pair) + 12.0) * double(cnt));
-      launch_edit_distance(a, rt.stream());
-      // (the words go back to the stream-ordered pool behind the launch)
-    }
-  }
-  g_edit_distance_calls.fetch_add(1);
-  g_edit_distance_pairs.fetch_add(pairs);
-}
-
-
-// ---- batched CTC score of device-resident hypotheses, and its gradient (ctc_score.hip) ----
-namespace {
-std::atomic<int64_t> g_ctc_score_calls{0}, g_ctc_score_pairs{0};
-// what the alpha rows of ONE launch may take; a gradient call that needs more runs its pairs in slices of launches.  A
-// pair that is above the cap by itself runs alone with scratch of its own size.
-constexpr int64_t kCtcScoreScratchCap = int64_t(256) << 20;
-int64_t ctc_score_scratch_cap() {
-  // (debug switch, read per call: tests lower the cap to see a sliced call without allocating gigabytes)
-  const char* e = std::getenv("GTNX_CTC_SCORE_SCRATCH_BYTES");
-  if (e && *e) {
-    const long long v = std::atoll(e);
-    if (v > 0) return std::min<int64_t>(v, kCtcScoreScratchCap);
-  }
-  return kCtcScoreScratchCap;
-}
-
-// both entry points: scores_dev for the score, weights_dev and grad_dev for the gradient
-void ctc_score_impl(const char* who, const BatchP& ems, const int* frames, int blank, const int* tokens_dev,
-                    int64_t row_stride, const int* lengths_dev, int N, int L, int max_length, float* scores_dev,
-                    const float* weights_dev, float* grad_dev) {
-  const std::string tag = std::string("[") + who + "] ";
-  const bool want_grad = scores_dev == nullptr;
-  // what the arguments alone decide comes first: no device is asked for an invalid call
-  if (!ems) throw_invalid(tag + "null batch");
-  if (!tokens_dev || !lengths_dev) throw_invalid(tag + "null input pointer (tokens and lengths are both read)");
-  if (want_grad ? (!weights_dev || !grad_dev) : false) throw_invalid(tag + "null weights or grad pointer");
-  if (N < 0 || L < 0) throw_invalid(tag + "negative N or L");
-  if (row_stride < 0) throw_invalid(tag + "negative row stride");
-  if (blank < 0) throw_invalid(tag + "negative blank");
-  if (row_stride < L) throw_invalid(tag + "row_stride is shorter than the rows' width L");
-  if (max_length < 1 || max_length > kCtcScoreMaxU) throw_invalid(tag + "max_length outside 1 .. 4096");
-  const int n = ems->n;
-  const int64_t pairs = int64_t(n) * N;
-  if (pairs > std::numeric_limits<int>::max()) throw_invalid(tag + "n times N does not fit an int");
-  if (pairs <= 0) return;
-  Runtime& rt = Runtime::get();
-  // there is no other route: the scores are those of the slabs of a native linear batch
-  if (!(ems->kind == Batch::LINEAR && !ems->leaf && ems->w_dev))
-    throw_invalid(tag + "not a native linear batch (gtnx_batch_linear / _rows)");
-  Batch& x = *ems;
-  if (frames)
-    for (int b = 0; b < n; ++b) {
-      if (frames[b] < 0 || frames[b] > x.M) throw_invalid(tag + "a frame count outside 0 .. M");
-      if (frames[b] > x.rows_of(b)) throw_invalid(tag + "a frame count beyond the rows the batch carries");
-    }
-  if (blank >= x.C) throw_invalid(tag + "blank is not below the number of labels");
-  // a kernel of this device writes the results: memory of another GPU of the process is refused, not written
-  if (want_grad ? !ptr_local_to(grad_dev, rt.device()) : !ptr_local_to(scores_dev, rt.device()))
-    throw_invalid(tag + "an output pointer is not memory of the engine's current device");
-  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
-  std::vector<int> fr(static_cast<size_t>(n));
-  int maxT = 0;
-  double frame_sum = 0;
-  for (int b = 0; b < n; ++b) {
-    fr[size_t(b)] = frames ? frames[b] : x.rows_of(b);
-    maxT = std::max(maxT, fr[size_t(b)]);
-    frame_sum += fr[size_t(b)];
-  }
-  DevMemP d_frames = upload_vec(fr);
-  const int U = max_length;
-  const int64_t SM = 2 * int64_t(U) + 1;
-  CtcScoreArgs a{};
-  a.em = x.w_dev;
-  a.frames = d_frames->as<int>();
-  a.tokens = tokens_dev;
-  a.lengths = lengths_dev;
-  a.weights = weights_dev;
-  a.grad = grad_dev;
-  a.row_stride = row_stride;
-  a.N = N;
-  a.L = L;
-  a.U = U;
-  a.M = x.M;
-  a.C = x.C;
-  a.blank = blank;
-  // algorithmic bytes, by the widths (the lengths are device memory: an upper bound).  forward: per pair and frame one
-  // emission per state, the tokens and the length once, the score out.  With the rows kept: every alpha out as well.
-  // backward: the alphas and the emissions back in, one load and one store of a gradient element per state and frame
-  // at most, the tokens and the length, and the utterance's slab zeroed once.
-  const double per_pair_frames = frame_sum / double(n);  // (the mean: every utterance has N pairs)
-  const double fwd_pair = 4.0 * double(SM) * per_pair_frames + 4.0 * std::min(L, U) + 8.0;
-  if (!want_grad) {
-    a.scores = scores_dev;
-    a.pair0 = 0;
-    a.score0 = 0;
-    a.count = int(pairs);
-    GTNX_PROF("ctc_score", fwd_pair * double(pairs));
-    launch_ctc_score_forward(a, rt.stream());
-  } else {
-    const int64_t per_pair = std::max<int64_t>(int64_t(maxT), 1) * SM;  // floats
-    const int64_t slice = std::max<int64_t>(1, ctc_score_scratch_cap() / (4 * per_pair));
-    a.pair_stride = per_pair;
-    for (int64_t p0 = 0; p0 < pairs; p0 += slice) {
-      const int64_t cnt = std::min(slice, pairs - p0);
-      DevMemP rows = rt.alloc(size_t(4 * per_pair * cnt));
-      DevMemP sc = rt.alloc(size_t(4 * cnt));
-      a.alpha = rows->as<float>();
-      a.scores = sc->as<float>();
-      a.pair0 = p0;
-      a.score0 = p0;
-      a.count = int(cnt);
-      {
-        GTNX_PROF("ctc_score_alpha", 2.0 * fwd_pair * double(cnt));
-        launch_ctc_score_forward(a, rt.stream());
-      }
-      {
-        GTNX_PROF("ctc_score_grad", (4.0 * fwd_pair + 4.0 * double(x.M) * x.C / double(N)) * double(cnt));
-        launch_ctc_score_backward(a, rt.stream());
-      }
-      // (the rows go back to the stream-ordered pool behind the launches)
-    }
-  }
-  g_ctc_score_calls.fetch_add(1);
-  g_ctc_score_pairs.fetch_add(pairs);
-}
-}  // namespace
-
-void batch_ctc_score_stats(int64_t* calls, int64_t* pairs) {
-  if (calls) *calls = g_ctc_score_calls.load();
-  if (pairs) *pairs = g_ctc_score_pairs.load();
-}
-
-void batch_ctc_score(const BatchP& ems, const int* frames, int blank, const int* tokens_dev, int64_t row_stride,
-                     const int* lengths_dev, int N, int L, int max_length, float* scores_dev) {
-  GTNX_HOST_T("batch.ctc_score");
-  if (!scores_dev) throw_invalid("[gtnx_batch_ctc_score] null scores pointer");
-  ctc_score_impl("gtnx_batch_ctc_score", ems, frames, blank, tokens_dev, row_stride, lengths_dev, N, L, max_length,
-                 scores_dev, nullptr, nullptr);
-}
-
-void batch_ctc_score_grad(const BatchP& ems, const int* frames, int blank, const int* tokens_dev, int64_t row_stride,
-                          const int* lengths_dev, int N, int L, int max_length, const float* weights_dev,
-                          float* grad_dev) {
-  GTNX_HOST_T("batch.ctc_score_grad");
-  ctc_score_impl("gtnx_batch_ctc_score_grad", ems, frames, blank, tokens_dev, row_stride, lengths_dev, N, L,
-                 max_length, nullptr, weights_dev, grad_dev);
-}
-
-
 namespace {
 // a GRAPHS batch of one-arc graphs as a native SCALAR batch (values gathered; backward continues on the graphs' tape)
 BatchP scalars_from_graphs(const BatchP& gsb) {

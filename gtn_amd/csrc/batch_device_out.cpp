@@ -1,0 +1,691 @@
+// batch_device_out.cpp -- the batch entry points that leave their results in the caller's device memory (declared and
+// specified in batch.h): forced alignment, decode against one shared graph, best path of the chains plus the CTC
+// collapse, CTC prefix beam search, edit distance, CTC score and its gradient.  The kernels differ; the host side around
+// them is the helpers below.
+//
+// Recipe for the next entry point, in this order:
+//   1. GTNX_HOST_T("batch.<name>"), then every check the arguments alone decide, each message "[gtnx_batch_<name>] ...":
+//      no device is asked for an invalid call.  native_linear(x) says whether x is slabs a kernel can read;
+//      check_frames(...) bounds the caller's frame counts.
+//   2. Runtime::get(), the early return of an empty call, check_outputs_local(...) over the output pointers.
+//   3. x.w_pend->settle() if the values are read, resolve_frames(...) (and upload_vec of it for a kernel that reads it),
+//      scratch from rt.alloc (scratch_cap(...) where a call is sliced), one argument struct of kernels.h, the launch
+//      under GTNX_PROF with its algorithmic bytes.
+//   4. the entry's Counters, and a *_stats getter that is its get().
+//   An entry with a route for every other batch computes the path graphs and hands them to paths_to_rows(...).
+#include "batch.h"
+
+#include <algorithm>
+#include <atomic>
+#include <cstdlib>
+#include <initializer_list>
+#include <limits>
+#include <string>
+
+namespace gtnx {
+
+namespace {
+
+[[noreturn]] void refuse(const char* entry, const char* text) { throw_invalid(std::string("[") + entry + "] " + text); }
+
+// the two totals behind a *_stats getter: (fast, fallback) utterances of an entry with a path-graph route, (calls,
+// items) of the others
+struct Counters {
+  std::atomic<int64_t> first{0}, second{0};
+  void add(int64_t a, int64_t b) {
+    if (a) first.fetch_add(a);
+    if (b) second.fetch_add(b);
+  }
+  void get(int64_t* a, int64_t* b) const {
+    if (a) *a = first.load();
+    if (b) *b = second.load();
+  }
+};
+
+// the caller's frame counts (null: none to check) lie in 0 .. limit and within the rows `x` carries
+struct FrameTexts {
+  const char *range, *rows;
+};
+constexpr FrameTexts kChainFrames{"a frame count outside 0 .. T", "a frame count beyond the rows the chain carries"};
+constexpr FrameTexts kBatchFrames{"a frame count outside 0 .. M", "a frame count beyond the rows the batch carries"};
+void check_frames(const char* entry, const int* frames, int n, int limit, const Batch& x,
+                  const FrameTexts& texts = kBatchFrames) {
+  if (!frames) return;
+  for (int b = 0; b < n; ++b) {
+    if (frames[b] < 0 || frames[b] > limit) refuse(entry, texts.range);
+    if (frames[b] > x.rows_of(b)) refuse(entry, texts.rows);
+  }
+}
+
+// a kernel of this device writes the results: memory of another GPU of the process is refused, not written
+void check_outputs_local(const char* entry, std::initializer_list<const void*> outs) {
+  const int dev = Runtime::get().device();
+  for (const void* p : outs)
+    if (p && !ptr_local_to(p, dev)) refuse(entry, "an output pointer is not memory of the engine's current device");
+}
+
+// slabs a kernel can read in place (gtnx_batch_linear / _rows)
+bool native_linear(const Batch& b) { return b.kind == Batch::LINEAR && !b.leaf && b.w_dev; }
+
+// T_b of every element: the caller's count, else the rows the batch carries
+std::vector<int> resolve_frames(const int* frames, const Batch& x) {
+  std::vector<int> fr(static_cast<size_t>(x.n));
+  for (int b = 0; b < x.n; ++b) fr[size_t(b)] = frames ? frames[b] : x.rows_of(b);
+  return fr;
+}
+
+// what the scratch of ONE launch may take; a call that needs more runs in slices of launches.  `env`: debug switch, read
+// per call: tests lower the cap to see a sliced call without allocating gigabytes
+int64_t scratch_cap(const char* env, int64_t cap) {
+  const char* e = std::getenv(env);
+  if (e && *e) {
+    const long long v = std::atoll(e);
+    if (v > 0) return std::min<int64_t>(v, cap);
+  }
+  return cap;
+}
+
+// The route of every batch no kernel takes: the labels of the path graphs read on the host, one upload.  Row b of
+// `labels` gets path b's labels and -1 up to the rows' width (`width_floor`, or the longest path if that is longer; a
+// width of 0 copies no label plane), `scores` the weights summed in path order, -inf without a path; with `collapsed`
+// the labels with repeats merged (and `blank` dropped if `drop_blank`), `starts` the first frame of each, `lengths` how
+// many.  All but `labels` may be null.
+struct PathRows {
+  int64_t width_floor;
+  bool arcless_scores_zero;  // a path with nodes and no arcs scores 0, not -inf
+  bool drop_blank;
+  int blank;
+  int* labels;
+  int64_t row_stride;
+  float* scores;
+  int *collapsed, *starts, *lengths;
+};
+void paths_to_rows(const char* entry, std::vector<Graph>& paths, const PathRows& o) {
+  Runtime& rt = Runtime::get();
+  const int n = int(paths.size());
+  int64_t width = o.width_floor;
+  for (Graph& g : paths) width = std::max<int64_t>(width, g.num_arcs());
+  if (width > o.row_stride) refuse(entry, "row_stride is shorter than the longest path");
+  const size_t cells = size_t(n) * size_t(width ? width : 1);
+  int* dst[3] = {o.labels, o.collapsed, o.starts};
+  PinnedMemP hl = rt.alloc_pinned(sizeof(int) * cells * 3);
+  PinnedMemP hs = rt.alloc_pinned((sizeof(float) + sizeof(int)) * size_t(n));
+  int* src[3] = {hl->as<int>(), hl->as<int>() + cells, hl->as<int>() + 2 * cells};
+  float* sc = hs->as<float>();
+  int* len_out = reinterpret_cast<int*>(sc + n);
+  std::fill(src[0], src[0] + 3 * cells, -1);
+  for (int b = 0; b < n; ++b) {
+    Graph& g = paths[size_t(b)];
+    const int64_t len = g.num_arcs();
+    // (no path, zero frames included: the empty graph)
+    float score = (g.num_nodes() > 0 && (o.arcless_scores_zero || len > 0)) ? 0.0f : -std::numeric_limits<float>::infinity();
+    int k = 0;
+    if (len > 0) {
+      g.s->ensure_host();
+      int* row = src[0] + size_t(b) * size_t(width);
+      int* crow = src[1] + size_t(b) * size_t(width);
+      int* srow = src[2] + size_t(b) * size_t(width);
+      std::copy(g.s->il.begin(), g.s->il.begin() + len, row);
+      const float* w = g.weights_host(false);
+      for (int64_t t = 0; t < len; ++t) {
+        score += w[t];  // (in path order, as the recursion accumulates it)
+        if ((t == 0 || row[t] != row[t - 1]) && !(o.drop_blank && row[t] == o.blank)) {
+          crow[k] = row[t];
+          srow[k++] = int(t);
+        }
+      }
+    }
+    sc[b] = score;
+    len_out[b] = k;
+  }
+  if (width > 0)
+    for (int i = 0; i < 3; ++i)
+      if (dst[i])
+        HIP_CHECK(hipMemcpy2DAsync(dst[i], sizeof(int) * size_t(o.row_stride), src[i], sizeof(int) * size_t(width),
+                                   sizeof(int) * size_t(width), size_t(n), hipMemcpyHostToDevice, rt.stream()));
+  if (o.scores) rt.h2d_pinned(o.scores, sc, sizeof(float) * size_t(n));
+  if (o.lengths) rt.h2d_pinned(o.lengths, len_out, sizeof(int) * size_t(n));
+}
+
+}  // namespace
+
+// ---- forced alignment with device-resident output (align.hip, asg_align.hip) ---------------------------------
+namespace {
+constexpr const char* kAlign = "gtnx_batch_viterbi_align";
+Counters g_align;  // (fast, fallback)
+
+// every other batch: the path graphs of batch_viterbi_path
+void align_fallback(const BatchP& x, const int* frames, int* labels_dev, int64_t row_stride, int* tokens_dev,
+                    float* scores_dev) {
+  if (tokens_dev)
+    throw_invalid("[gtnx_batch_viterbi_align] token indices are defined for device-built CTC targets or ASG force-alignment "
+                  "acceptors composed with a linear batch only (this batch takes the path-graph route)");
+  if (frames)
+    throw_invalid("[gtnx_batch_viterbi_align] per-utterance frame counts need device-built CTC targets or ASG "
+                  "force-alignment acceptors composed with a linear batch (this batch takes the path-graph route)");
+  GTNX_HOST_T("batch.viterbi_align.fallback");
+  // (a PRODUCT's rows are as long as its chains; other batches: as long as the longest path)
+  const int64_t floor = (x->kind == Batch::PRODUCT && x->chain && x->chain->kind == Batch::LINEAR) ? x->chain->M : 0;
+  BatchP paths = batch_viterbi_path(x);
+  paths_to_rows(kAlign, paths->graphs, {floor, true, false, 0, labels_dev, row_stride, scores_dev, nullptr, nullptr, nullptr});
+  g_align.add(0, x->n);
+}
+}  // namespace
+
+void batch_align_stats(int64_t* fast, int64_t* fallback) { g_align.get(fast, fallback); }
+
+void batch_viterbi_align(const BatchP& x, const int* frames, int* labels_dev, int64_t row_stride, int* tokens_dev,
+                         float* scores_dev) {
+  GTNX_HOST_T("batch.viterbi_align");
+  Runtime& rt = Runtime::get();  // (first: without a device this is a device error, whatever the arguments)
+  if (!labels_dev) throw_invalid("[gtnx_batch_viterbi_align] null labels pointer");
+  if (row_stride < 0) throw_invalid("[gtnx_batch_viterbi_align] negative row stride");
+  const int n = x->n;
+  if (n <= 0) return;
+  check_outputs_local(kAlign, {labels_dev, tokens_dev, scores_dev});
+  // device-built CTC targets (align.hip), or device-built force-alignment acceptors o ASG transitions (asg_align.hip),
+  // composed with a linear batch in either argument order
+  const bool built = x->kind == Batch::PRODUCT && x->fixed && x->chain && x->fixed->kind == Batch::CTC_TARGETS &&
+                     x->chain->kind == Batch::LINEAR && x->fixed->rec_mem && x->fixed->n == n && x->chain->n == n;
+  bool fast = built && !x->fixed->fal, asg = built && x->fixed->fal;
+  if (built) {
+    const Batch& fx = *x->fixed;
+    const Batch& ch = *x->chain;
+    const int vec = ch.C % 4 == 0 && (reinterpret_cast<uintptr_t>(ch.w_dev) & 15) == 0;
+    fast = fast && band_align_ok(fx.max_nodes, ch.C, vec) && fx.max_label < ch.C;
+    // the closed form of the queue ranks (ops_band.cpp tie_ranks) holds with the blank below every label
+    for (size_t i = 0; i < fx.labels.size() && fast; ++i) fast = fx.labels[i] > fx.blank;
+    asg = asg && asg_align_ok(fx.max_nodes, ch.C, vec) && fx.trans_labels == ch.C && fx.max_label < ch.C;
+  }
+  if (!fast && !asg) {
+    align_fallback(x, frames, labels_dev, row_stride, tokens_dev, scores_dev);
+    return;
+  }
+  Batch& fx = *x->fixed;
+  Batch& ch = *x->chain;
+  const int T = ch.M, C = ch.C;
+  if (row_stride < T) throw_invalid("[gtnx_batch_viterbi_align] row_stride is shorter than the chains");
+  check_frames(kAlign, frames, n, T, ch, kChainFrames);
+  if (ch.w_pend) ch.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  const std::vector<int> fr = resolve_frames(frames, ch);
+  // what AlignArgs and AsgAlignArgs share: element b's N band nodes, its emissions, its back-pointer plane, its rows
+  auto common = [&](auto& a, int b, size_t N, unsigned* bp) {
+    char* base = fx.rec_mem->as<char>(fx.rec_off[size_t(b)]);
+    a.nodes = reinterpret_cast<BandNode*>(base);
+    a.nflags = reinterpret_cast<uint8_t*>(base + align_up(sizeof(BandNode) * N, 64));
+    a.em = ch.w_dev + size_t(b) * size_t(T) * size_t(C);
+    a.bp = bp;
+    a.labels = labels_dev + int64_t(b) * row_stride;
+    a.tokens = tokens_dev ? tokens_dev + int64_t(b) * row_stride : nullptr;
+    a.score = scores_dev ? scores_dev + b : nullptr;
+    a.N = int(N);
+    a.T = fr[size_t(b)];
+    a.T_full = T;
+    a.C = C;
+  };
+  double abytes = 0;
+  if (asg) {
+    // back-pointer planes: 1 bit per (time, node), one 256-byte row of words per 32 / NPL steps, NPL the LAUNCH's
+    const int npl = asg_align_npl(fx.max_nodes);
+    const size_t plane = asg_align_plane_bytes(T, npl);
+    DevMemP work = rt.alloc(plane * size_t(n));
+    std::vector<AsgAlignArgs> tab(static_cast<size_t>(n));
+    for (int b = 0; b < n; ++b) {
+      AsgAlignArgs& a = tab[size_t(b)];
+      a = AsgAlignArgs{};
+      const size_t N = size_t(fx.lab_off[size_t(b) + 1] - fx.lab_off[size_t(b)]) + 1;
+      common(a, b, N, work->as<unsigned>(plane * size_t(b)));
+      a.w = fx.rec_mem->as<float>(fx.w_off[size_t(b)]);
+      abytes += 4.0 * a.T * C + 0.25 * double(a.T) * double(N) + 8.0 * a.T;
+    }
+    DevMemP d = upload_vec(tab);
+    GTNX_PROF("asg_viterbi_align", abytes);
+    launch_asg_align(d->as<AsgAlignArgs>(), n, fx.max_nodes, rt.stream());
+    g_align.add(n, 0);
+    return;
+  }
+  // back-pointer planes: 2 bits per (time, node), one 256-byte row of words per 16 / NPL steps (align.hip)
+  const int npl = align_npl(fx.max_nodes);
+  const size_t plane = align_up((size_t(T) * size_t(npl) + 15) / 16 * 256 + 256, 256);
+  DevMemP work = rt.alloc(plane * size_t(n));
+  std::vector<AlignArgs> tab(static_cast<size_t>(n));
+  for (int b = 0; b < n; ++b) {
+    AlignArgs& a = tab[size_t(b)];
+    a = AlignArgs{};
+    const int* t = fx.labels.data() + fx.lab_off[size_t(b)];
+    const int U = fx.lab_off[size_t(b) + 1] - fx.lab_off[size_t(b)];
+    const size_t N = size_t(2 * U + 1);
+    common(a, b, N, work->as<unsigned>(plane * size_t(b)));
+    int p = 0;
+    while (p + 1 < U && t[p] < t[p + 1]) ++p;
+    a.p = p;
+    abytes += 4.0 * a.T * C + 0.5 * double(a.T) * double(N) + 8.0 * a.T;
+  }
+  DevMemP d = upload_vec(tab);
+  GTNX_PROF("band_viterbi_align", abytes);
+  launch_band_align(d->as<AlignArgs>(), n, fx.max_nodes, rt.stream());
+  g_align.add(n, 0);
+}
+
+// ---- decode against one shared transitions graph with device-resident output (asg_decode.hip) ----------------
+namespace {
+constexpr const char* kDecode = "gtnx_batch_viterbi_decode";
+Counters g_decode;  // (fast, fallback)
+
+// every other graph or batch: viterbiPath over the composed elements
+void decode_fallback(const BatchP& ems, Graph& transitions, const int* frames, int* labels_dev, int64_t row_stride,
+                     float* scores_dev, int* collapsed_dev, int* lengths_dev) {
+  if (frames)
+    throw_invalid("[gtnx_batch_viterbi_decode] per-utterance frame counts need a linear batch and a dense transitions "
+                  "graph of 8 .. 1024 nodes whose ties go by node order (this batch takes the path-graph route, which "
+                  "decodes the rows the elements carry: pass frames = null)");
+  GTNX_HOST_T("batch.viterbi_decode.fallback");
+  batch_materialise(*ems);
+  std::vector<Graph> tr{transitions};
+  std::vector<Graph> comp = op_compose(ems->graphs, tr, false);
+  std::vector<Graph> paths = op_viterbi_path(comp);
+  paths_to_rows(kDecode, paths, {ems->kind == Batch::LINEAR ? ems->M : 0, false, false, 0, labels_dev, row_stride, scores_dev,
+                                 collapsed_dev, nullptr, lengths_dev});
+  g_decode.add(0, ems->n);
+}
+}  // namespace
+
+void batch_decode_stats(int64_t* fast, int64_t* fallback) { g_decode.get(fast, fallback); }
+
+void batch_viterbi_decode(const BatchP& ems, Graph& transitions, const int* frames, int* labels_dev, int64_t row_stride,
+                          float* scores_dev, int* collapsed_dev, int* lengths_dev) {
+  GTNX_HOST_T("batch.viterbi_decode");
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) throw_invalid("[gtnx_batch_viterbi_decode] null batch");
+  if (!labels_dev) throw_invalid("[gtnx_batch_viterbi_decode] null labels pointer");
+  if (row_stride < 0) throw_invalid("[gtnx_batch_viterbi_decode] negative row stride");
+  if (lengths_dev && !collapsed_dev)
+    throw_invalid("[gtnx_batch_viterbi_decode] lengths are those of the collapsed sequences: pass collapsed_device too");
+  const int n = ems->n;
+  // (a linear batch without values of its own is bounded like one with them, and refused by the route it takes)
+  const bool linear = ems->kind == Batch::LINEAR && !ems->leaf;
+  if (linear) check_frames(kDecode, frames, n, ems->M, *ems);
+  if (linear && n > 0 && row_stride < ems->M)
+    throw_invalid("[gtnx_batch_viterbi_decode] row_stride is shorter than the rows of the batch");
+  Runtime::get();
+  if (n <= 0) return;
+  check_outputs_local(kDecode, {labels_dev, scores_dev, collapsed_dev, lengths_dev});
+  if (!native_linear(*ems) || !lazy_decode_ok(transitions, ems->M, ems->C)) {
+    decode_fallback(ems, transitions, frames, labels_dev, row_stride, scores_dev, collapsed_dev, lengths_dev);
+    return;
+  }
+  Batch& x = *ems;
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  // full-length views of the slabs (batch_materialise's elements with M rows whatever `rows` says): one shape, one
+  // group, one sweep -- the sweep reads the pad rows, the back-trace never looks at what it made of them
+  std::vector<Graph> chains;
+  chains.reserve(size_t(n));
+  {
+    GraphSlabScope slab_scope(size_t(n));
+    const int64_t stride = int64_t(x.M) * x.C;
+    for (int i = 0; i < n; ++i) {
+      Graph g = Graph::make_result(false);
+      Structure& s = *g.s;
+      s.kind = KIND_LINEAR;
+      s.M = x.M;
+      s.C = x.C;
+      s.N = int64_t(x.M) + 1;
+      s.A = stride;
+      s.ilabel_sorted = s.olabel_sorted = true;
+      Weights& w = *g.w;
+      w.n = stride;
+      w.dev_mem = x.w_mem;
+      w.dev = x.w_dev + size_t(i) * size_t(stride);
+      w.dev_valid = true;
+      w.host_valid = false;
+      w.version++;
+      chains.push_back(std::move(g));
+    }
+  }
+  lazy_viterbi_decode(chains, transitions, resolve_frames(frames, x), labels_dev, row_stride, scores_dev, collapsed_dev,
+                      lengths_dev);
+  g_decode.add(n, 0);
+}
+
+// ---- best path of the chains themselves plus the CTC collapse, device-resident output (linear_decode.hip) ----
+namespace {
+constexpr const char* kLinearDecode = "gtnx_batch_linear_decode";
+Counters g_linear_decode;  // (fast, fallback)
+}  // namespace
+
+void batch_linear_decode_stats(int64_t* fast, int64_t* fallback) { g_linear_decode.get(fast, fallback); }
+
+void batch_linear_decode(const BatchP& ems, const int* frames, int blank, int* labels_dev, int64_t row_stride,
+                         float* scores_dev, int* collapsed_dev, int* starts_dev, int* lengths_dev) {
+  GTNX_HOST_T("batch.linear_decode");
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) throw_invalid("[gtnx_batch_linear_decode] null batch");
+  if (!labels_dev) throw_invalid("[gtnx_batch_linear_decode] null labels pointer");
+  if (row_stride < 0) throw_invalid("[gtnx_batch_linear_decode] negative row stride");
+  if ((lengths_dev || starts_dev) && !collapsed_dev)
+    throw_invalid("[gtnx_batch_linear_decode] lengths and starts are those of the collapsed sequences: pass "
+                  "collapsed_device too");
+  const int n = ems->n;
+  const bool linear = native_linear(*ems);
+  if (frames && !linear)
+    throw_invalid("[gtnx_batch_linear_decode] per-utterance frame counts need a native linear batch (this batch takes "
+                  "the path-graph route, which decodes the rows the elements carry: pass frames = null)");
+  check_frames(kLinearDecode, frames, n, ems->M, *ems);
+  if (linear && n > 0 && row_stride < ems->M)
+    throw_invalid("[gtnx_batch_linear_decode] row_stride is shorter than the rows of the batch");
+  if (linear && blank >= ems->C) throw_invalid("[gtnx_batch_linear_decode] blank is not below the number of labels");
+  Runtime& rt = Runtime::get();
+  if (n <= 0) return;
+  check_outputs_local(kLinearDecode, {labels_dev, scores_dev, collapsed_dev, starts_dev, lengths_dev});
+  Batch& x = *ems;
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  if (!linear) {
+    // every other batch: the path graphs of batch_viterbi_path
+    GTNX_HOST_T("batch.linear_decode.fallback");
+    BatchP paths = batch_viterbi_path(ems);
+    paths_to_rows(kLinearDecode, paths->graphs, {x.kind == Batch::LINEAR ? x.M : 0, true, true, blank, labels_dev, row_stride,
+                                                 scores_dev, collapsed_dev, starts_dev, lengths_dev});
+    g_linear_decode.add(0, n);
+    return;
+  }
+  const std::vector<int> fr = resolve_frames(frames, x);
+  // algorithmic bytes: every emission of the rows that count once, label and maximum out / back in, the pad of the
+  // label rows, the collapsed rows
+  double row_bytes = 0, col_bytes = 0;
+  for (int t : fr) {
+    row_bytes += 4.0 * x.C * t + 8.0 * t;
+    col_bytes += 8.0 * t + 4.0 * (x.M - t) + (collapsed_dev ? 8.0 * x.M : 0.0);
+  }
+  DevMemP d_frames = upload_vec(fr);
+  DevMemP rowmax = rt.alloc(sizeof(float) * std::max<size_t>(size_t(n) * size_t(x.M), 1));
+  LinearDecodeArgs a{};
+  a.em = x.w_dev;
+  a.frames = d_frames->as<int>();
+  a.labels = labels_dev;
+  a.rowmax = rowmax->as<float>();
+  a.scores = scores_dev;
+  a.collapsed = collapsed_dev;
+  a.starts = starts_dev;
+  a.lengths = lengths_dev;
+  a.row_stride = row_stride;
+  a.n = n;
+  a.M = x.M;
+  a.C = x.C;
+  a.blank = blank;
+  {
+    GTNX_PROF("linear_decode_rows", row_bytes);
+    launch_linear_decode(a, 0, rt.stream());
+  }
+  {
+    GTNX_PROF("linear_decode_collapse", col_bytes);
+    launch_linear_decode(a, 1, rt.stream());
+  }
+  // (the scratch and the table go back to the stream-ordered pool behind the launches)
+  g_linear_decode.add(n, 0);
+}
+
+// ---- CTC prefix beam search with N-best output, device-resident (ctc_beam.hip) ----
+namespace {
+constexpr const char* kCtcBeam = "gtnx_batch_ctc_beam_decode";
+Counters g_ctc_beam;  // (calls, utterances)
+}  // namespace
+
+void batch_ctc_beam_stats(int64_t* calls, int64_t* utterances) { g_ctc_beam.get(calls, utterances); }
+
+void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int beam, int topn, int nbest,
+                           int* tokens_dev, int64_t row_stride, int* lengths_dev, float* scores_dev) {
+  GTNX_HOST_T("batch.ctc_beam_decode");
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) throw_invalid("[gtnx_batch_ctc_beam_decode] null batch");
+  if (!tokens_dev || !lengths_dev || !scores_dev)
+    throw_invalid("[gtnx_batch_ctc_beam_decode] null output pointer (tokens, lengths and scores are all written)");
+  if (row_stride < 0) throw_invalid("[gtnx_batch_ctc_beam_decode] negative row stride");
+  if (beam < 1 || beam > 64) throw_invalid("[gtnx_batch_ctc_beam_decode] beam_size outside 1 .. 64");
+  if (topn < 1 || topn > 32) throw_invalid("[gtnx_batch_ctc_beam_decode] cutoff_top_n outside 1 .. 32");
+  if (nbest < 1) throw_invalid("[gtnx_batch_ctc_beam_decode] nbest below 1");
+  if (nbest > beam) throw_invalid("[gtnx_batch_ctc_beam_decode] nbest above beam_size");
+  if (blank < 0) throw_invalid("[gtnx_batch_ctc_beam_decode] negative blank");
+  Runtime& rt = Runtime::get();
+  const int n = ems->n;
+  // there is no other route: the search runs on the slabs of a native linear batch
+  if (!native_linear(*ems)) throw_invalid("[gtnx_batch_ctc_beam_decode] not a native linear batch (gtnx_batch_linear / _rows)");
+  Batch& x = *ems;
+  check_frames(kCtcBeam, frames, n, x.M, x);
+  if (n > 0 && row_stride < x.M)
+    throw_invalid("[gtnx_batch_ctc_beam_decode] row_stride is shorter than the rows of the batch");
+  if (blank >= x.C) throw_invalid("[gtnx_batch_ctc_beam_decode] blank is not below the number of labels");
+  // (a candidate's key keeps its label in 25 bits; trie nodes are numbered 1 + t * beam + slot in an int)
+  if (x.C > (1 << 25)) throw_invalid("[gtnx_batch_ctc_beam_decode] more than 2^25 labels");
+  if (int64_t(x.M) * beam + 1 > std::numeric_limits<int>::max())
+    throw_invalid("[gtnx_batch_ctc_beam_decode] rows times beam_size does not fit an int");
+  if (n <= 0) return;
+  check_outputs_local(kCtcBeam, {tokens_dev, lengths_dev, scores_dev});
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  const std::vector<int> fr = resolve_frames(frames, x);
+  // algorithmic bytes.  rows: every emission of the rows that count once, topn + 1 entries and a count out.  search:
+  // those back in, a trie node per kept extension (at most beam per frame), the output rows.
+  double row_bytes = 0, search_bytes = 0;
+  for (int t : fr) {
+    row_bytes += (4.0 * x.C + 8.0 * (topn + 1) + 4.0) * t;
+    search_bytes += (8.0 * (topn + 1) + 4.0 + 8.0 * beam) * t + nbest * (4.0 * x.M + 8.0);
+  }
+  DevMemP d_frames = upload_vec(fr);
+  const size_t rows = std::max<size_t>(size_t(n) * size_t(x.M), 1);
+  DevMemP entries = rt.alloc(8 * rows * size_t(topn + 1));
+  DevMemP counts = rt.alloc(sizeof(int) * rows);
+  DevMemP trie = rt.alloc(8 * size_t(n) * (size_t(x.M) * size_t(beam) + 1));
+  CtcBeamArgs a{};
+  a.em = x.w_dev;
+  a.frames = d_frames->as<int>();
+  a.ent_val = entries->as<float>();
+  a.ent_cnt = counts->as<int>();
+  a.trie = trie->as<int>();
+  a.tokens = tokens_dev;
+  a.lengths = lengths_dev;
+  a.scores = scores_dev;
+  a.row_stride = row_stride;
+  a.n = n;
+  a.M = x.M;
+  a.C = x.C;
+  a.blank = blank;
+  a.beam = beam;
+  a.topn = topn;
+  a.nbest = nbest;
+  {
+    GTNX_PROF("ctc_beam_rows", row_bytes);
+    launch_ctc_beam(a, 0, rt.stream());
+  }
+  {
+    GTNX_PROF("ctc_beam_search", search_bytes);
+    launch_ctc_beam(a, 1, rt.stream());
+  }
+  // (the scratch and the table go back to the stream-ordered pool behind the launches)
+  g_ctc_beam.add(1, n);
+}
+
+// ---- batched edit distance of device-resident token rows (edit_distance.hip) ----
+namespace {
+Counters g_edit_distance;  // (calls, pairs)
+// the walk's scratch: a pair at the largest widths takes 64 MiB, so a slice always holds at least one pair
+constexpr int64_t kEditDistanceScratchCap = int64_t(256) << 20;
+}  // namespace
+
+void batch_edit_distance_stats(int64_t* calls, int64_t* pairs) { g_edit_distance.get(calls, pairs); }
+
+void batch_edit_distance(const int* hyp_dev, int64_t hyp_stride, const int* hyp_len_dev, const int* ref_dev,
+                         int64_t ref_stride, const int* ref_len_dev, int B, int N, int L, int U, int* dist_dev,
+                         int* ops_dev) {
+  GTNX_HOST_T("batch.edit_distance");
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!hyp_dev || !hyp_len_dev || !ref_dev || !ref_len_dev)
+    throw_invalid("[gtnx_batch_edit_distance] null input pointer (hyp, hyp_lengths, ref and ref_lengths are all read)");
+  if (!dist_dev) throw_invalid("[gtnx_batch_edit_distance] null dist pointer");
+  if (B < 0 || N < 0 || L < 0 || U < 0) throw_invalid("[gtnx_batch_edit_distance] negative B, N, L or U");
+  if (hyp_stride < 0 || ref_stride < 0) throw_invalid("[gtnx_batch_edit_distance] negative row stride");
+  if (hyp_stride < L) throw_invalid("[gtnx_batch_edit_distance] hyp_stride is shorter than the rows' width L");
+  if (ref_stride < U) throw_invalid("[gtnx_batch_edit_distance] ref_stride is shorter than the rows' width U");
+  // (the carries of a row of columns and the reference live in LDS; a lane of the wave owns one block of 64 rows)
+  if (L > kEditDistanceMaxL) throw_invalid("[gtnx_batch_edit_distance] L above 65536");
+  if (U > kEditDistanceMaxU) throw_invalid("[gtnx_batch_edit_distance] U above 4096");
+  const int64_t pairs = int64_t(B) * N;
+  if (pairs > std::numeric_limits<int>::max()) throw_invalid("[gtnx_batch_edit_distance] B times N does not fit an int");
+  if (pairs == 0) return;
+  Runtime& rt = Runtime::get();
+  check_outputs_local("gtnx_batch_edit_distance", {dist_dev, ops_dev});
+  const int nbU = (U + 63) / 64;
+  EditDistanceArgs a{};
+  a.hyp = hyp_dev;
+  a.hyp_len = hyp_len_dev;
+  a.ref = ref_dev;
+  a.ref_len = ref_len_dev;
+  a.dist = dist_dev;
+  a.ops = ops_dev;
+  a.hyp_stride = hyp_stride;
+  a.ref_stride = ref_stride;
+  a.N = N;
+  a.L = L;
+  a.U = U;
+  a.nbU = nbU;
+  // algorithmic bytes, by the widths (the lengths are device memory: an upper bound): every token and length once, the
+  // distance out; with ops the (Pv, Mv) words of every (column, block) out and back in, and the three counts
+  const double io_bytes = double(pairs) * (4.0 * L + 8.0) + double(B) * (4.0 * U + 4.0);
+  if (!ops_dev) {
+    a.pair0 = 0;
+    a.count = int(pairs);
+    GTNX_PROF("edit_distance", io_bytes);
+    launch_edit_distance(a, rt.stream());
+  } else {
+    const int64_t per_pair = int64_t(16) * L * nbU;
+    const int64_t cap = scratch_cap("GTNX_EDIT_DISTANCE_SCRATCH_BYTES", kEditDistanceScratchCap);
+    const int64_t slice = per_pair > 0 ? std::max<int64_t>(1, cap / per_pair) : pairs;
+    for (int64_t p0 = 0; p0 < pairs; p0 += slice) {
+      const int64_t cnt = std::min(slice, pairs - p0);
+      DevMemP words = rt.alloc(size_t(std::max<int64_t>(per_pair * cnt, 16)));
+      a.scratch = words->as<gtnx_ul2>();
+      a.pair0 = p0;
+      a.count = int(cnt);
+      GTNX_PROF("edit_distance_ops", (io_bytes / double(pairs) + 2.0 * double(per_pair) + 12.0) * double(cnt));
+      launch_edit_distance(a, rt.stream());
+      // (the words go back to the stream-ordered pool behind the launch)
+    }
+  }
+  g_edit_distance.add(1, pairs);
+}
+
+// ---- batched CTC score of device-resident hypotheses, and its gradient (ctc_score.hip) ----
+namespace {
+Counters g_ctc_score;  // (calls, pairs)
+// the alpha rows of a gradient call: a pair that is above the cap by itself runs alone with scratch of its own size
+constexpr int64_t kCtcScoreScratchCap = int64_t(256) << 20;
+
+// both entry points: scores_dev for the score, weights_dev and grad_dev for the gradient
+void ctc_score_impl(const char* who, const BatchP& ems, const int* frames, int blank, const int* tokens_dev,
+                    int64_t row_stride, const int* lengths_dev, int N, int L, int max_length, float* scores_dev,
+                    const float* weights_dev, float* grad_dev) {
+  const bool want_grad = scores_dev == nullptr;
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) refuse(who, "null batch");
+  if (!tokens_dev || !lengths_dev) refuse(who, "null input pointer (tokens and lengths are both read)");
+  if (want_grad && (!weights_dev || !grad_dev)) refuse(who, "null weights or grad pointer");
+  if (N < 0 || L < 0) refuse(who, "negative N or L");
+  if (row_stride < 0) refuse(who, "negative row stride");
+  if (blank < 0) refuse(who, "negative blank");
+  if (row_stride < L) refuse(who, "row_stride is shorter than the rows' width L");
+  if (max_length < 1 || max_length > kCtcScoreMaxU) refuse(who, "max_length outside 1 .. 4096");
+  const int n = ems->n;
+  const int64_t pairs = int64_t(n) * N;
+  if (pairs > std::numeric_limits<int>::max()) refuse(who, "n times N does not fit an int");
+  if (pairs <= 0) return;
+  Runtime& rt = Runtime::get();
+  // there is no other route: the scores are those of the slabs of a native linear batch
+  if (!native_linear(*ems)) refuse(who, "not a native linear batch (gtnx_batch_linear / _rows)");
+  Batch& x = *ems;
+  check_frames(who, frames, n, x.M, x);
+  if (blank >= x.C) refuse(who, "blank is not below the number of labels");
+  check_outputs_local(who, {want_grad ? grad_dev : scores_dev});
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  const std::vector<int> fr = resolve_frames(frames, x);
+  int maxT = 0;
+  double frame_sum = 0;
+  for (int t : fr) {
+    maxT = std::max(maxT, t);
+    frame_sum += t;
+  }
+  DevMemP d_frames = upload_vec(fr);
+  const int U = max_length;
+  const int64_t SM = 2 * int64_t(U) + 1;
+  CtcScoreArgs a{};
+  a.em = x.w_dev;
+  a.frames = d_frames->as<int>();
+  a.tokens = tokens_dev;
+  a.lengths = lengths_dev;
+  a.weights = weights_dev;
+  a.grad = grad_dev;
+  a.row_stride = row_stride;
+  a.N = N;
+  a.L = L;
+  a.U = U;
+  a.M = x.M;
+  a.C = x.C;
+  a.blank = blank;
+  // algorithmic bytes, by the widths (the lengths are device memory: an upper bound).  forward: per pair and frame one
+  // emission per state, the tokens and the length once, the score out.  With the rows kept: every alpha out as well.
+  // backward: the alphas and the emissions back in, one load and one store of a gradient element per state and frame
+  // at most, the tokens and the length, and the utterance's slab zeroed once.
+  const double per_pair_frames = frame_sum / double(n);  // (the mean: every utterance has N pairs)
+  const double fwd_pair = 4.0 * double(SM) * per_pair_frames + 4.0 * std::min(L, U) + 8.0;
+  if (!want_grad) {
+    a.scores = scores_dev;
+    a.pair0 = 0;
+    a.score0 = 0;
+    a.count = int(pairs);
+    GTNX_PROF("ctc_score", fwd_pair * double(pairs));
+    launch_ctc_score_forward(a, rt.stream());
+  } else {
+    const int64_t per_pair = std::max<int64_t>(int64_t(maxT), 1) * SM;  // floats
+    const int64_t cap = scratch_cap("GTNX_CTC_SCORE_SCRATCH_BYTES", kCtcScoreScratchCap);
+    const int64_t slice = std::max<int64_t>(1, cap / (4 * per_pair));
+    a.pair_stride = per_pair;
+    for (int64_t p0 = 0; p0 < pairs; p0 += slice) {
+      const int64_t cnt = std::min(slice, pairs - p0);
+      DevMemP rows = rt.alloc(size_t(4 * per_pair * cnt));
+      DevMemP sc = rt.alloc(size_t(4 * cnt));
+      a.alpha = rows->as<float>();
+      a.scores = sc->as<float>();
+      a.pair0 = p0;
+      a.score0 = p0;
+      a.count = int(cnt);
+      {
+        GTNX_PROF("ctc_score_alpha", 2.0 * fwd_pair * double(cnt));
+        launch_ctc_score_forward(a, rt.stream());
+      }
+      {
+        GTNX_PROF("ctc_score_grad", (4.0 * fwd_pair + 4.0 * double(x.M) * x.C / double(N)) * double(cnt));
+        launch_ctc_score_backward(a, rt.stream());
+      }
+      // (the rows go back to the stream-ordered pool behind the launches)
+    }
+  }
+  g_ctc_score.add(1, pairs);
+}
+}  // namespace
+
+void batch_ctc_score_stats(int64_t* calls, int64_t* pairs) { g_ctc_score.get(calls, pairs); }
+
+void batch_ctc_score(const BatchP& ems, const int* frames, int blank, const int* tokens_dev, int64_t row_stride,
+                     const int* lengths_dev, int N, int L, int max_length, float* scores_dev) {
+  GTNX_HOST_T("batch.ctc_score");
+  if (!scores_dev) throw_invalid("[gtnx_batch_ctc_score] null scores pointer");
+  ctc_score_impl("gtnx_batch_ctc_score", ems, frames, blank, tokens_dev, row_stride, lengths_dev, N, L, max_length,
+                 scores_dev, nullptr, nullptr);
+}
+
+void batch_ctc_score_grad(const BatchP& ems, const int* frames, int blank, const int* tokens_dev, int64_t row_stride,
+                          const int* lengths_dev, int N, int L, int max_length, const float* weights_dev,
+                          float* grad_dev) {
+  GTNX_HOST_T("batch.ctc_score_grad");
+  ctc_score_impl("gtnx_batch_ctc_score_grad", ems, frames, blank, tokens_dev, row_stride, lengths_dev, N, L,
+                 max_length, nullptr, weights_dev, grad_dev);
+}
+
+}  // namespace gtnx

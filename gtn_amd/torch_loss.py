@@ -17,6 +17,25 @@ import gtn_amd as gtn
 _NATIVE = None
 
 
+_P, _I = C.c_void_p, C.c_int
+# the argument types of libgtn_criteria.so's entry points (gtn_amd/criteria/criteria_capi.cpp); all return an int.  A
+# library from before an entry point lacks its symbol
+_ARGTYPES = {
+    "gtn_ctc_loss_n": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "gtn_ctc_loss_frames_n": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "gtn_asg_loss_n": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "gtn_asg_loss_frames_n": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "gtn_ctc_align_n": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
+    "gtn_asg_align_n": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "gtn_asg_decode_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "gtn_ctc_decode_n": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "gtn_ctc_beam_decode_n": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P],
+    "gtn_edit_distance_n": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "gtn_ctc_score_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P],
+    "gtn_ctc_score_grad_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P],
+}
+
+
 def _native():
     """libgtn_criteria.so (gtn_amd/criteria/): the whole batch step in one native call --
     target graphs on host threads, batched graph functions, loss and gradient on the device"""
@@ -25,57 +44,61 @@ def _native():
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libgtn_criteria.so")
         if os.path.exists(path) and not os.environ.get("GTN_AMD_PYTHON_CRITERIA"):
             lib = C.CDLL(path)
-            lib.gtn_ctc_loss_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p]
-            lib.gtn_ctc_loss_n.restype = C.c_int
-            if hasattr(lib, "gtn_ctc_loss_frames_n"):
-                lib.gtn_ctc_loss_frames_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-                lib.gtn_ctc_loss_frames_n.restype = C.c_int
-            lib.gtn_asg_loss_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-            lib.gtn_asg_loss_n.restype = C.c_int
-            if hasattr(lib, "gtn_asg_loss_frames_n"):
-                lib.gtn_asg_loss_frames_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-                lib.gtn_asg_loss_frames_n.restype = C.c_int
             lib.gtn_criteria_last_error.restype = C.c_char_p
-            if hasattr(lib, "gtn_ctc_align_n"):
-                lib.gtn_ctc_align_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-                lib.gtn_ctc_align_n.restype = C.c_int
-            if hasattr(lib, "gtn_asg_align_n"):
-                lib.gtn_asg_align_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-                lib.gtn_asg_align_n.restype = C.c_int
-            if hasattr(lib, "gtn_asg_decode_n"):
-                lib.gtn_asg_decode_n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-                lib.gtn_asg_decode_n.restype = C.c_int
-            if hasattr(lib, "gtn_ctc_decode_n"):
-                lib.gtn_ctc_decode_n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-                lib.gtn_ctc_decode_n.restype = C.c_int
-            if hasattr(lib, "gtn_ctc_beam_decode_n"):
-                lib.gtn_ctc_beam_decode_n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                                      C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-                lib.gtn_ctc_beam_decode_n.restype = C.c_int
-            if hasattr(lib, "gtn_edit_distance_n"):
-                lib.gtn_edit_distance_n.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-                lib.gtn_edit_distance_n.restype = C.c_int
-            if hasattr(lib, "gtn_ctc_score_n"):
-                lib.gtn_ctc_score_n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-                lib.gtn_ctc_score_n.restype = C.c_int
-                lib.gtn_ctc_score_grad_n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                                     C.c_void_p]
-                lib.gtn_ctc_score_grad_n.restype = C.c_int
+            for name, argtypes in _ARGTYPES.items():
+                if hasattr(lib, name):
+                    getattr(lib, name).argtypes = argtypes
+                    getattr(lib, name).restype = C.c_int
             _NATIVE = lib
         else:
             _NATIVE = False
     return _NATIVE
+
+
+def _call(name, *args):
+    """one entry point of libgtn_criteria.so; its error as a RuntimeError"""
+    lib = _native()
+    if getattr(lib, name)(*args) != 0:
+        raise RuntimeError(lib.gtn_criteria_last_error().decode())
+
+
+def _has_native(who, symbol, python_route=False):
+    """whether `who` runs through `symbol` of libgtn_criteria.so.  Without the library it takes the Python route; so does
+    an entry with `python_route` when the library is from before the symbol, where the others raise"""
+    lib = _native()
+    if lib and not hasattr(lib, symbol) and not python_route:
+        raise RuntimeError(f"{who} needs {symbol} in gtn_amd/lib/libgtn_criteria.so (run __graft_entry__.build())")
+    return bool(lib) and hasattr(lib, symbol)
+
+
+def _ptr(t):
+    """device address of an optional tensor"""
+    return t.data_ptr() if t is not None else None
+
+
+def _host_ptr(a):
+    """host address of an optional numpy array"""
+    return a.ctypes.data if a is not None else None
+
+
+def _engine_stream(device):
+    """point the engine at the caller's stream; returns the stream"""
+    stream = torch.cuda.current_stream(device)
+    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
+    if not stream.cuda_stream:
+        stream.synchronize()  # engine runs on its own stream
+    return stream
+
+
+def _engine_done(stream):
+    """the tail of _engine_stream: on the null stream the caller's next kernel must wait for the engine's own stream"""
+    if not stream.cuda_stream:
+        gtn.synchronize()
+
+
+def _asg_weights(start, transitions):
+    """[N + N*N] in the arc order of gtn::criteria::asgTransitions: N start arcs, then arc N + i*N + j = j -> i"""
+    return torch.cat([start.detach().reshape(-1), transitions.detach().reshape(-1)]).to(torch.float32).contiguous()
 
 
 def ctc_target_graph(target, blank=0):
@@ -208,12 +231,12 @@ class _CTCLoss(torch.autograd.Function):
 
 
 def _frame_counts(name, input_lengths, B, T, low):
-    """per-utterance frame counts as a host int32 array [B], each in low .. T"""
+    """per-utterance frame counts as a host int32 array [B], each in low .. T (low None: the engine checks the range)"""
     vals = input_lengths.tolist() if hasattr(input_lengths, "tolist") else list(input_lengths)
     frames = np.ascontiguousarray([int(v) for v in vals], dtype=np.int32)
     if frames.shape != (B,):
         raise ValueError(f"{name}: {frames.size} input lengths for a batch of {B}")
-    if B and (int(frames.min()) < low or int(frames.max()) > T):
+    if B and low is not None and (int(frames.min()) < low or int(frames.max()) > T):
         raise ValueError(f"{name}: an input length outside {low} .. {T}")
     return frames
 
@@ -251,32 +274,20 @@ def ctc_forced_align(log_probs, targets, blank=0, input_lengths=None):
     if len(targets) != B:
         raise ValueError(f"ctc_forced_align: {len(targets)} target sequences for a batch of {B}")
     x = log_probs.detach().contiguous()
-    frames = None
-    if input_lengths is not None:
-        frames = np.ascontiguousarray([int(v) for v in input_lengths], dtype=np.int32)
-        if frames.shape != (B,):
-            raise ValueError(f"ctc_forced_align: {frames.size} input lengths for a batch of {B}")
-    stream = torch.cuda.current_stream(x.device)
-    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
-    if not stream.cuda_stream:
-        torch.cuda.current_stream(x.device).synchronize()  # engine runs on its own stream
+    frames = None if input_lengths is None else _frame_counts("ctc_forced_align", input_lengths, B, T, None)
+    stream = _engine_stream(x.device)
     labels = torch.empty(B, T, dtype=torch.int32, device=x.device)
     tokens = torch.empty(B, T, dtype=torch.int32, device=x.device)
     scores = torch.empty(B, dtype=torch.float32, device=x.device)
-    lib = _native()
-    if lib and hasattr(lib, "gtn_ctc_align_n"):
+    if _has_native("ctc_forced_align", "gtn_ctc_align_n", python_route=True):
         flat, lens = _flat_targets(targets)
-        rc = lib.gtn_ctc_align_n(x.data_ptr(), flat.ctypes.data, lens.ctypes.data, B, T, C, int(blank),
-                                 frames.ctypes.data if frames is not None else None, labels.data_ptr(),
-                                 tokens.data_ptr(), scores.data_ptr())
-        if rc != 0:
-            raise RuntimeError(lib.gtn_criteria_last_error().decode())
+        _call("gtn_ctc_align_n", x.data_ptr(), flat.ctypes.data, lens.ctypes.data, B, T, C, int(blank),
+              _host_ptr(frames), labels.data_ptr(), tokens.data_ptr(), scores.data_ptr())
     else:
         ctcs = gtn.Batch.ctc_targets([list(t) for t in targets], blank, calc_grad=False)
         ems = gtn.Batch.linear(B, T, C, x, calc_grad=False, borrow=True)
         gtn.intersect(ctcs, ems).viterbi_align(labels, tokens, scores, frames)
-    if not stream.cuda_stream:
-        gtn.synchronize()
+    _engine_done(stream)
     return labels, tokens, scores
 
 
@@ -406,33 +417,21 @@ def asg_forced_align(emissions, transitions, targets, start=None, input_lengths=
         raise ValueError(f"asg_forced_align: {len(targets)} target sequences for a batch of {B}")
     frames = None if input_lengths is None else _frame_counts("asg_forced_align", input_lengths, B, T, 0)
     x = emissions.detach().contiguous()
-    # arc order of gtn::criteria::asgTransitions: N start arcs, then arc N + i*N + j = j -> i
-    w = torch.cat([start.detach().reshape(-1), transitions.detach().reshape(-1)]).to(torch.float32).contiguous()
-    stream = torch.cuda.current_stream(x.device)
-    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
-    if not stream.cuda_stream:
-        stream.synchronize()  # engine runs on its own stream
+    w = _asg_weights(start, transitions)
+    stream = _engine_stream(x.device)
     labels = torch.empty(B, T, dtype=torch.int32, device=x.device)
     tokens = torch.empty(B, T, dtype=torch.int32, device=x.device)
     scores = torch.empty(B, dtype=torch.float32, device=x.device)
-    lib = _native()
-    if lib:
-        if not hasattr(lib, "gtn_asg_align_n"):
-            raise RuntimeError("asg_forced_align needs gtn_asg_align_n in gtn_amd/lib/libgtn_criteria.so "
-                               "(run __graft_entry__.build())")
+    if _has_native("asg_forced_align", "gtn_asg_align_n"):
         flat, lens = _flat_targets(targets)
-        rc = lib.gtn_asg_align_n(x.data_ptr(), flat.ctypes.data, lens.ctypes.data, B, T, N, w.data_ptr(),
-                                 frames.ctypes.data if frames is not None else None, labels.data_ptr(),
-                                 tokens.data_ptr(), scores.data_ptr())
-        if rc != 0:
-            raise RuntimeError(lib.gtn_criteria_last_error().decode())
+        _call("gtn_asg_align_n", x.data_ptr(), flat.ctypes.data, lens.ctypes.data, B, T, N, w.data_ptr(),
+              _host_ptr(frames), labels.data_ptr(), tokens.data_ptr(), scores.data_ptr())
     else:
         trans = _asg_transitions_graph(N, w)
         ems = gtn.Batch.linear(B, T, N, x, calc_grad=False, borrow=True)
         fals = gtn.Batch.asg_force_align([list(t) for t in targets], trans, N)
         gtn.compose(ems, fals).viterbi_align(labels, tokens, scores, frames)
-    if not stream.cuda_stream:
-        gtn.synchronize()
+    _engine_done(stream)
     return labels, tokens, scores
 
 
@@ -464,33 +463,20 @@ def asg_decode(emissions, transitions, start=None, input_lengths=None, collapse=
     if start is None:
         start = torch.zeros(N, dtype=torch.float32, device=emissions.device)
     x = emissions.detach().contiguous()
-    # arc order of gtn::criteria::asgTransitions: N start arcs, then arc N + i*N + j = j -> i
-    w = torch.cat([start.detach().reshape(-1), transitions.detach().reshape(-1)]).to(torch.float32).contiguous()
-    stream = torch.cuda.current_stream(x.device)
-    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
-    if not stream.cuda_stream:
-        stream.synchronize()  # engine runs on its own stream
+    w = _asg_weights(start, transitions)
+    stream = _engine_stream(x.device)
     labels = torch.empty(B, T, dtype=torch.int32, device=x.device)
     scores = torch.empty(B, dtype=torch.float32, device=x.device)
     collapsed = torch.empty(B, T, dtype=torch.int32, device=x.device) if collapse else None
     lengths = torch.empty(B, dtype=torch.int32, device=x.device) if collapse else None
-    lib = _native()
-    if lib:
-        if not hasattr(lib, "gtn_asg_decode_n"):
-            raise RuntimeError("asg_decode needs gtn_asg_decode_n in gtn_amd/lib/libgtn_criteria.so "
-                               "(run __graft_entry__.build())")
-        rc = lib.gtn_asg_decode_n(x.data_ptr(), B, T, N, w.data_ptr(),
-                                  frames.ctypes.data if frames is not None else None, labels.data_ptr(),
-                                  scores.data_ptr(), collapsed.data_ptr() if collapse else None,
-                                  lengths.data_ptr() if collapse else None)
-        if rc != 0:
-            raise RuntimeError(lib.gtn_criteria_last_error().decode())
+    if _has_native("asg_decode", "gtn_asg_decode_n"):
+        _call("gtn_asg_decode_n", x.data_ptr(), B, T, N, w.data_ptr(), _host_ptr(frames), labels.data_ptr(),
+              scores.data_ptr(), _ptr(collapsed), _ptr(lengths))
     else:
         trans = _asg_transitions_graph(N, w)
         ems = gtn.Batch.linear(B, T, N, x, calc_grad=False, borrow=True)
         ems.viterbi_decode(trans, labels, scores, frames, collapsed, lengths, row_stride=T)
-    if not stream.cuda_stream:
-        gtn.synchronize()
+    _engine_done(stream)
     return (labels, scores, collapsed, lengths) if collapse else (labels, scores)
 
 
@@ -518,30 +504,19 @@ def ctc_decode(log_probs, blank=0, input_lengths=None, collapse=True):
     if not log_probs.is_cuda:
         raise RuntimeError("ctc_decode: log_probs must be a CUDA tensor (the decode runs on the device)")
     x = log_probs.detach().contiguous()
-    stream = torch.cuda.current_stream(x.device)
-    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
-    if not stream.cuda_stream:
-        stream.synchronize()  # engine runs on its own stream
+    stream = _engine_stream(x.device)
     labels = torch.empty(B, T, dtype=torch.int32, device=x.device)
     scores = torch.empty(B, dtype=torch.float32, device=x.device)
     tokens = torch.empty(B, T, dtype=torch.int32, device=x.device) if collapse else None
     starts = torch.empty(B, T, dtype=torch.int32, device=x.device) if collapse else None
     lengths = torch.empty(B, dtype=torch.int32, device=x.device) if collapse else None
-    lib = _native()
-    if lib:
-        if not hasattr(lib, "gtn_ctc_decode_n"):
-            raise RuntimeError("ctc_decode needs gtn_ctc_decode_n in gtn_amd/lib/libgtn_criteria.so "
-                               "(run __graft_entry__.build())")
-        rc = lib.gtn_ctc_decode_n(x.data_ptr(), B, T, N, blank, frames.ctypes.data if frames is not None else None,
-                                  labels.data_ptr(), scores.data_ptr(), tokens.data_ptr() if collapse else None,
-                                  starts.data_ptr() if collapse else None, lengths.data_ptr() if collapse else None)
-        if rc != 0:
-            raise RuntimeError(lib.gtn_criteria_last_error().decode())
+    if _has_native("ctc_decode", "gtn_ctc_decode_n"):
+        _call("gtn_ctc_decode_n", x.data_ptr(), B, T, N, blank, _host_ptr(frames), labels.data_ptr(), scores.data_ptr(),
+              _ptr(tokens), _ptr(starts), _ptr(lengths))
     else:
         ems = gtn.Batch.linear(B, T, N, x, calc_grad=False, borrow=True)
         ems.linear_decode(labels, scores, frames, blank, tokens, starts, lengths, row_stride=T)
-    if not stream.cuda_stream:
-        gtn.synchronize()
+    _engine_done(stream)
     return (labels, scores, tokens, starts, lengths) if collapse else (labels, scores)
 
 
@@ -576,28 +551,17 @@ def ctc_beam_decode(log_probs, blank=0, input_lengths=None, beam_size=16, cutoff
     if not log_probs.is_cuda:
         raise RuntimeError("ctc_beam_decode: log_probs must be a CUDA tensor (the search runs on the device)")
     x = log_probs.detach().contiguous()
-    stream = torch.cuda.current_stream(x.device)
-    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
-    if not stream.cuda_stream:
-        stream.synchronize()  # engine runs on its own stream
+    stream = _engine_stream(x.device)
     tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=x.device)
     lengths = torch.empty(B, nbest, dtype=torch.int32, device=x.device)
     scores = torch.empty(B, nbest, dtype=torch.float32, device=x.device)
-    lib = _native()
-    if lib:
-        if not hasattr(lib, "gtn_ctc_beam_decode_n"):
-            raise RuntimeError("ctc_beam_decode needs gtn_ctc_beam_decode_n in gtn_amd/lib/libgtn_criteria.so "
-                               "(run __graft_entry__.build())")
-        rc = lib.gtn_ctc_beam_decode_n(x.data_ptr(), B, T, N, blank, frames.ctypes.data if frames is not None else None,
-                                       beam_size, cutoff_top_n, nbest, tokens.data_ptr(), lengths.data_ptr(),
-                                       scores.data_ptr())
-        if rc != 0:
-            raise RuntimeError(lib.gtn_criteria_last_error().decode())
+    if _has_native("ctc_beam_decode", "gtn_ctc_beam_decode_n"):
+        _call("gtn_ctc_beam_decode_n", x.data_ptr(), B, T, N, blank, _host_ptr(frames), beam_size, cutoff_top_n, nbest,
+              tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr())
     else:
         ems = gtn.Batch.linear(B, T, N, x, calc_grad=False, borrow=True)
         ems.ctc_beam_decode(tokens, lengths, scores, frames, blank, beam_size, cutoff_top_n, nbest, row_stride=T)
-    if not stream.cuda_stream:
-        gtn.synchronize()
+    _engine_done(stream)
     return tokens, lengths, scores
 
 
@@ -639,38 +603,22 @@ def edit_distance(hyp, hyp_lengths, ref, ref_lengths, return_ops=False):
         r = r.new_empty(1)
     hl = hyp_lengths.detach().to(torch.int32).contiguous()  # (int64 lengths are converted on the device)
     rl = ref_lengths.detach().to(torch.int32).contiguous()
-    stream = torch.cuda.current_stream(h.device)
-    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
-    if not stream.cuda_stream:
-        stream.synchronize()  # engine runs on its own stream
+    stream = _engine_stream(h.device)
     dist = torch.empty(B, N, dtype=torch.int32, device=h.device)
     ops = torch.empty(B, N, 3, dtype=torch.int32, device=h.device) if return_ops else None
-    lib = _native()
     if B * N == 0:
         pass  # (no pair: nothing to launch, and an empty tensor has no address to hand over)
-    elif lib and hasattr(lib, "gtn_edit_distance_n"):
-        rc = lib.gtn_edit_distance_n(h.data_ptr(), hl.data_ptr(), r.data_ptr(), rl.data_ptr(), B, N, L, U,
-                                     dist.data_ptr(), ops.data_ptr() if return_ops else None)
-        if rc != 0:
-            raise RuntimeError(lib.gtn_criteria_last_error().decode())
+    elif _has_native("edit_distance", "gtn_edit_distance_n", python_route=True):
+        _call("gtn_edit_distance_n", h.data_ptr(), hl.data_ptr(), r.data_ptr(), rl.data_ptr(), B, N, L, U,
+              dist.data_ptr(), _ptr(ops))
     else:
-        gtn.edit_distance(h.data_ptr(), hl.data_ptr(), r.data_ptr(), rl.data_ptr(), dist.data_ptr(),
-                          ops.data_ptr() if return_ops else None, B=B, N=N, L=L, U=U, hyp_stride=L, ref_stride=U)
-    if not stream.cuda_stream:
-        gtn.synchronize()
+        gtn.edit_distance(h.data_ptr(), hl.data_ptr(), r.data_ptr(), rl.data_ptr(), dist.data_ptr(), _ptr(ops),
+                          B=B, N=N, L=L, U=U, hyp_stride=L, ref_stride=U)
+    _engine_done(stream)
     if flat:
         dist = dist.reshape(B)
         ops = ops.reshape(B, 3) if return_ops else None
     return (dist, ops) if return_ops else dist
-
-
-def _engine_stream(device):
-    """point the engine at the caller's stream; returns the stream"""
-    stream = torch.cuda.current_stream(device)
-    gtn.set_stream(stream.cuda_stream if stream.cuda_stream else None)
-    if not stream.cuda_stream:
-        stream.synchronize()  # engine runs on its own stream
-    return stream
 
 
 class _CTCScore(torch.autograd.Function):
@@ -684,24 +632,16 @@ class _CTCScore(torch.autograd.Function):
         x = log_probs.detach().contiguous()
         stream = _engine_stream(x.device)
         scores = torch.empty(B, N, dtype=torch.float32, device=x.device)
-        lib = _native()
-        fr = frames.ctypes.data if frames is not None else None
         if B * N == 0:
             pass  # (no pair: nothing to launch, and an empty tensor has no address to hand over)
-        elif lib:
-            if not hasattr(lib, "gtn_ctc_score_n"):
-                raise RuntimeError("ctc_score needs gtn_ctc_score_n in gtn_amd/lib/libgtn_criteria.so "
-                                   "(run __graft_entry__.build())")
-            rc = lib.gtn_ctc_score_n(x.data_ptr(), B, T, C_, blank, fr, tokens.data_ptr(), lengths.data_ptr(), N, L,
-                                     max_length, scores.data_ptr())
-            if rc != 0:
-                raise RuntimeError(lib.gtn_criteria_last_error().decode())
+        elif _has_native("ctc_score", "gtn_ctc_score_n"):
+            _call("gtn_ctc_score_n", x.data_ptr(), B, T, C_, blank, _host_ptr(frames), tokens.data_ptr(),
+                  lengths.data_ptr(), N, L, max_length, scores.data_ptr())
         else:
             ems = gtn.Batch.linear(B, T, C_, x, calc_grad=False, borrow=True)
             ems.ctc_score(tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr(), frames, blank, max_length, N=N, L=L,
                           row_stride=L)
-        if not stream.cuda_stream:
-            gtn.synchronize()
+        _engine_done(stream)
         ctx.save_for_backward(x, tokens, lengths)
         ctx.args = (blank, frames, max_length)
         return scores
@@ -717,19 +657,14 @@ class _CTCScore(torch.autograd.Function):
         w = grad_out.detach().to(torch.float32).contiguous()
         stream = _engine_stream(x.device)
         grad = torch.empty(B, T, C_, dtype=torch.float32, device=x.device)
-        lib = _native()
-        fr = frames.ctypes.data if frames is not None else None
-        if lib:
-            rc = lib.gtn_ctc_score_grad_n(x.data_ptr(), B, T, C_, blank, fr, tokens.data_ptr(), lengths.data_ptr(), N, L,
-                                          max_length, w.data_ptr(), grad.data_ptr())
-            if rc != 0:
-                raise RuntimeError(lib.gtn_criteria_last_error().decode())
+        if _native():
+            _call("gtn_ctc_score_grad_n", x.data_ptr(), B, T, C_, blank, _host_ptr(frames), tokens.data_ptr(),
+                  lengths.data_ptr(), N, L, max_length, w.data_ptr(), grad.data_ptr())
         else:
             ems = gtn.Batch.linear(B, T, C_, x, calc_grad=False, borrow=True)
             ems.ctc_score_grad(tokens.data_ptr(), lengths.data_ptr(), w.data_ptr(), grad.data_ptr(), frames, blank,
                                max_length, N=N, L=L, row_stride=L)
-        if not stream.cuda_stream:
-            gtn.synchronize()
+        _engine_done(stream)
         return grad, None, None, None, None, None
 
 
