@@ -135,6 +135,8 @@ _SIGS = {
     "gtnx_batch_linear_decode_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_ctc_beam_decode": [c_graph, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64,
                                    C.c_void_p, C.c_void_p],
+    "gtnx_batch_ctc_beam_decode_lm": [c_graph, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float,
+                                      C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "gtnx_batch_ctc_beam_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_linear_shape": [c_graph, c_i32_p, c_i32_p],
     "gtnx_batch_edit_distance": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int,

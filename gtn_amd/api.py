@@ -826,7 +826,8 @@ def make_api(lib):
                                                _opt_ptr(lengths_out)))
 
         def ctc_beam_decode(self, tokens_out, lengths_out, scores_out, frames=None, blank=0, beam_size=16,
-                            cutoff_top_n=16, nbest=1, row_stride=None):
+                            cutoff_top_n=16, nbest=1, row_stride=None, lm=None, lm_weight=1.0, insertion_bonus=0.0,
+                            am_scores_out=None):
             """CTC prefix beam search with N-best output over a Batch.linear, results left on the device
             (gtnx_batch_ctc_beam_decode; DESIGN section 20 holds the contract): `tokens_out` (int32 CUDA tensor
             [B, nbest, >= M] with contiguous rows, or a device address of [B][nbest][row_stride]) gets the labels of
@@ -836,8 +837,25 @@ def make_api(lib):
             frame with nothing above -inf, T_b = 0): -1, 0, -inf.  `beam_size` 1 .. 64 prefixes are kept, a frame
             offers its `cutoff_top_n` (1 .. 32) best labels plus `blank`; `frames`: T_b per element (0 .. M, at most
             the rows the batch carries; None: those rows).  Two launches with no copy back and no wait; rows from T_b
-            on are never read.  Any batch but a Batch.linear is an error: there is no other route."""
+            on are never read.  Any batch but a Batch.linear is an error: there is no other route.
+            `lm` (float32 CUDA tensor [C + C * C] or a device address; None: no language model, the call above) fuses
+            a bigram over the labels into the ranking (gtnx_batch_ctc_beam_decode_lm): lm[c] scores
+            c as first label, lm[C + i * C + j] label j followed by label i -- `torch_loss._asg_weights(start,
+            transitions)`.  A prefix carries L = the sum over its labels of lm_weight * lm(...) + insertion_bonus;
+            candidates rank by acoustic total + L, a -inf entry forbids its bigram or first label, row pruning stays
+            acoustic.  `scores_out` then gets acoustic + L and `am_scores_out` (float32 [B, nbest], optional) the
+            acoustic total alone; slots without a hypothesis hold -inf in both."""
             n = len(self)
+            if lm is None and am_scores_out is not None:
+                raise ValueError("ctc_beam_decode: am_scores_out needs lm")
+            if lm is not None and hasattr(lm, "data_ptr"):
+                if str(lm.dtype) != "torch.float32" or lm.dim() != 1 or not lm.is_contiguous() or not lm.is_cuda:
+                    raise ValueError("ctc_beam_decode: lm must be a float32 contiguous CUDA tensor [C + C * C]")
+                m, c = C.c_int(-1), C.c_int(-1)
+                check(lib.gtnx_batch_linear_shape(self._h, C.byref(m), C.byref(c)))
+                if c.value >= 0 and lm.numel() != c.value + c.value * c.value:
+                    raise ValueError(f"ctc_beam_decode: lm has {lm.numel()} entries, {c.value} labels need "
+                                     f"{c.value + c.value * c.value}")
             stride = row_stride
             t = tokens_out
             if t is not None and hasattr(t, "data_ptr"):
@@ -856,11 +874,19 @@ def make_api(lib):
             if stride is None:
                 raise ValueError("ctc_beam_decode: a device address needs row_stride")
             for o, dt, what in ((lengths_out, "torch.int32", "lengths_out must be an int32"),
-                                (scores_out, "torch.float32", "scores_out must be a float32")):
+                                (scores_out, "torch.float32", "scores_out must be a float32"),
+                                (am_scores_out, "torch.float32", "am_scores_out must be a float32")):
                 if o is not None and hasattr(o, "data_ptr") and (str(o.dtype) != dt or not o.is_contiguous()
                                                                  or o.numel() < n * int(nbest)):
                     raise ValueError(f"ctc_beam_decode: {what} contiguous tensor [B, nbest]")
             fr, fr_ptr = _frames_arg("ctc_beam_decode", frames, n)
+            if lm is not None:
+                check(lib.gtnx_batch_ctc_beam_decode_lm(self._h, fr_ptr, int(blank), int(beam_size), int(cutoff_top_n),
+                                                        int(nbest), _opt_ptr(lm), float(lm_weight),
+                                                        float(insertion_bonus), _opt_ptr(tokens_out), int(stride),
+                                                        _opt_ptr(lengths_out), _opt_ptr(scores_out),
+                                                        _opt_ptr(am_scores_out)))
+                return
             check(lib.gtnx_batch_ctc_beam_decode(self._h, fr_ptr, int(blank), int(beam_size), int(cutoff_top_n),
                                                  int(nbest), _opt_ptr(tokens_out), int(stride), _opt_ptr(lengths_out),
                                                  _opt_ptr(scores_out)))

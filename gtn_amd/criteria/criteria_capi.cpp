@@ -99,6 +99,18 @@ GTN_EXPORT int gtn_ctc_beam_decode_n(const void* emissions, int B, int T, int C,
   });
 }
 
+// The same with a bigram table fused into the ranking.  lm: DEVICE float [C + C * C] (the arc order of asgTransitions);
+// scores: acoustic + language model; am_scores: DEVICE float [B][nbest] or null, the acoustic total alone.
+GTN_EXPORT int gtn_ctc_beam_decode_lm_n(const void* emissions, int B, int T, int C, int blank, const int* frames,
+                                        int beam_size, int cutoff_top_n, int nbest, const void* lm, float lm_weight,
+                                        float insertion_bonus, void* tokens, void* lengths, void* scores,
+                                        void* am_scores) {
+  return guarded([&] {
+    gtn::criteria::ctcBeamDecodeBatch(emissions, B, T, C, blank, frames, beam_size, cutoff_top_n, nbest, lm, lm_weight,
+                                      insertion_bonus, tokens, lengths, scores, am_scores);
+  });
+}
+
 // Exact CTC log scores of B * N device-resident hypotheses.  emissions: DEVICE float32 [B][T][C]; frames: HOST int [B] or
 // null; tokens: DEVICE int32 [B][N][L]; lengths: DEVICE int32 [B][N]; scores: DEVICE float32 [B][N].
 GTN_EXPORT int gtn_ctc_score_n(const void* emissions, int B, int T, int C, int blank, const int* frames,

@@ -187,6 +187,33 @@ inline void ctcBeamDecodeBatch(
                          static_cast<float*>(scoresDev), blank, beamSize, cutoffTopN, nbest, frames);
 }
 
+/** The same search with a bigram over the labels fused into the ranking (gtnx_batch_ctc_beam_decode_lm has the
+ *  contract): `lmDev` device float32 [C + C * C], the weights of asgTransitions(C) in its arc order -- what the ASG
+ *  criterion learns; `lmWeight`, `insertionBonus`: the scale of a table entry and what every label adds.  `scoresDev`
+ *  gets acoustic + language model, `amScoresDev` (device float [B][nbest], may be null) the acoustic total alone. */
+inline void ctcBeamDecodeBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int C,
+    int blank,
+    const int* frames,
+    int beamSize,
+    int cutoffTopN,
+    int nbest,
+    const void* lmDev,
+    float lmWeight,
+    float insertionBonus,
+    void* tokensDev,
+    void* lengthsDev,
+    void* scoresDev,
+    void* amScoresDev) {
+  Batch ems = Batch::linear(B, T, C, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  batched::ctcBeamDecode(ems, static_cast<const float*>(lmDev), lmWeight, insertionBonus, static_cast<int*>(tokensDev),
+                         T, static_cast<int*>(lengthsDev), static_cast<float*>(scoresDev),
+                         static_cast<float*>(amScoresDev), blank, beamSize, cutoffTopN, nbest, frames);
+}
+
 /** The exact log scores of B * N device-resident hypotheses under the B emission slabs, and (with weightsDev and gradDev)
  *  the gradient sum_k weights[b][k] * d score[b][k] / d emissions_b: `emissions` device float32 [B][T][C], read in
  *  place; `tokensDev` device int32 [B][N][L] (dense rows); `lengthsDev` device int32 [B][N]; `frames` host [B] or null;

@@ -182,6 +182,23 @@ void batch_linear_decode_stats(int64_t* fast, int64_t* fallback);  // utterances
 // read, no download, no wait.
 void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int beam, int topn, int nbest,
                            int* tokens_dev, int64_t row_stride, int* lengths_dev, float* scores_dev);
+// The same search with a bigram over the labels fused in (DESIGN section 23 holds the contract).  table_dev: device
+// float32 [C + C * C] in the arc order of criteria::asgTransitions -- table[c] scores c as first label, table[C + i * C
+// + j] label j followed by label i.  A prefix carries L = the sum over its labels of weight * table(...) + bonus,
+// float32, left to right; candidates rank by acoustic total + L, an extension whose term is not finite is dropped (-inf
+// in the table forbids it), row pruning and (pb, pnb) stay acoustic.  scores_dev gets acoustic + L, am_scores_dev (may
+// be null) the acoustic total, -inf in both for a slot without a hypothesis.  lm = null is the call above.  On top of
+// its refusals, before a device is asked for: a null table, a weight or bonus that is not finite; with the device: more
+// than 2^19 labels, a table that is not memory allocated on the current device (pageable, pinned or registered host
+// memory and managed memory are all refused: the kernel gathers from it), an am_scores_dev the device may not write.
+// Counted by batch_ctc_beam_stats like the call above.
+struct CtcBeamLm {
+  const float* table_dev;
+  float weight, bonus;
+  float* am_scores_dev;
+};
+void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int beam, int topn, int nbest,
+                           const CtcBeamLm* lm, int* tokens_dev, int64_t row_stride, int* lengths_dev, float* scores_dev);
 void batch_ctc_beam_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they decoded
 // Levenshtein distance (unit costs) of all B * N pairs (hyp[b, k], ref[b]) of device-resident token rows, results on the
 // device (DESIGN section 21 holds the contract).  hyp_dev: int32 [B][N] rows of width L, hyp_stride elements apart;

@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <initializer_list>
 #include <limits>
@@ -434,6 +435,12 @@ void batch_ctc_beam_stats(int64_t* calls, int64_t* utterances) { g_ctc_beam.get(
 
 void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int beam, int topn, int nbest,
                            int* tokens_dev, int64_t row_stride, int* lengths_dev, float* scores_dev) {
+  batch_ctc_beam_decode(ems, frames, blank, beam, topn, nbest, nullptr, tokens_dev, row_stride, lengths_dev, scores_dev);
+}
+
+void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int beam, int topn, int nbest,
+                           const CtcBeamLm* lm, int* tokens_dev, int64_t row_stride, int* lengths_dev,
+                           float* scores_dev) {
   GTNX_HOST_T("batch.ctc_beam_decode");
   // what the arguments alone decide comes first: no device is asked for an invalid call
   if (!ems) throw_invalid("[gtnx_batch_ctc_beam_decode] null batch");
@@ -445,6 +452,11 @@ void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int 
   if (nbest < 1) throw_invalid("[gtnx_batch_ctc_beam_decode] nbest below 1");
   if (nbest > beam) throw_invalid("[gtnx_batch_ctc_beam_decode] nbest above beam_size");
   if (blank < 0) throw_invalid("[gtnx_batch_ctc_beam_decode] negative blank");
+  if (lm) {
+    if (!lm->table_dev) throw_invalid("[gtnx_batch_ctc_beam_decode] null language model table");
+    if (!std::isfinite(lm->weight) || !std::isfinite(lm->bonus))
+      throw_invalid("[gtnx_batch_ctc_beam_decode] lm_weight and insertion_bonus must be finite");
+  }
   Runtime& rt = Runtime::get();
   const int n = ems->n;
   // there is no other route: the search runs on the slabs of a native linear batch
@@ -456,18 +468,29 @@ void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int 
   if (blank >= x.C) throw_invalid("[gtnx_batch_ctc_beam_decode] blank is not below the number of labels");
   // (a candidate's key keeps its label in 25 bits; trie nodes are numbered 1 + t * beam + slot in an int)
   if (x.C > (1 << 25)) throw_invalid("[gtnx_batch_ctc_beam_decode] more than 2^25 labels");
+  // (with a table the key also keeps the label's place in the token set, in 6 of those bits; a table of (2^19)^2
+  //  entries is four terabytes)
+  if (lm && x.C > (1 << 19)) throw_invalid("[gtnx_batch_ctc_beam_decode] more than 2^19 labels with a language model table");
   if (int64_t(x.M) * beam + 1 > std::numeric_limits<int>::max())
     throw_invalid("[gtnx_batch_ctc_beam_decode] rows times beam_size does not fit an int");
   if (n <= 0) return;
   check_outputs_local(kCtcBeam, {tokens_dev, lengths_dev, scores_dev});
+  if (lm) {
+    check_outputs_local(kCtcBeam, {lm->am_scores_dev});
+    // (the kernel gathers from it: host memory is refused too, with one GPU as well)
+    if (!ptr_device_memory_of(lm->table_dev, rt.device()))
+      refuse(kCtcBeam, "the language model table is not memory of the engine's current device");
+  }
   if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
   const std::vector<int> fr = resolve_frames(frames, x);
   // algorithmic bytes.  rows: every emission of the rows that count once, topn + 1 entries and a count out.  search:
-  // those back in, a trie node per kept extension (at most beam per frame), the output rows.
+  // those back in, a trie node per kept extension (at most beam per frame), the output rows; with a table one 4-byte
+  // gather per (beam, member of the set) and frame at the most, and the second score.
   double row_bytes = 0, search_bytes = 0;
   for (int t : fr) {
     row_bytes += (4.0 * x.C + 8.0 * (topn + 1) + 4.0) * t;
     search_bytes += (8.0 * (topn + 1) + 4.0 + 8.0 * beam) * t + nbest * (4.0 * x.M + 8.0);
+    if (lm) search_bytes += 4.0 * beam * (topn + 1) * t + (lm->am_scores_dev ? 4.0 * nbest : 0.0);
   }
   DevMemP d_frames = upload_vec(fr);
   const size_t rows = std::max<size_t>(size_t(n) * size_t(x.M), 1);
@@ -491,6 +514,12 @@ void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int 
   a.beam = beam;
   a.topn = topn;
   a.nbest = nbest;
+  if (lm) {
+    a.lm = lm->table_dev;
+    a.lm_weight = lm->weight;
+    a.lm_bonus = lm->bonus;
+    a.am_scores = lm->am_scores_dev;
+  }
   {
     GTNX_PROF("ctc_beam_rows", row_bytes);
     launch_ctc_beam(a, 0, rt.stream());

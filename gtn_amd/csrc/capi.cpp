@@ -907,6 +907,18 @@ GTNX_API gtnx_status_t gtnx_batch_ctc_beam_decode(gtnx_batch_t ems, const int* f
                           row_stride, static_cast<int*>(lengths_device), static_cast<float*>(scores_device));
   });
 }
+GTNX_API gtnx_status_t gtnx_batch_ctc_beam_decode_lm(gtnx_batch_t ems, const int* frames, int blank, int beam_size,
+                                                     int cutoff_top_n, int nbest, const void* lm_device, float lm_weight,
+                                                     float insertion_bonus, void* tokens_device, int64_t row_stride,
+                                                     void* lengths_device, void* scores_device,
+                                                     void* am_scores_device) {
+  return guard([&] {
+    const CtcBeamLm lm{static_cast<const float*>(lm_device), lm_weight, insertion_bonus,
+                       static_cast<float*>(am_scores_device)};
+    batch_ctc_beam_decode(BH(ems), frames, blank, beam_size, cutoff_top_n, nbest, &lm, static_cast<int*>(tokens_device),
+                          row_stride, static_cast<int*>(lengths_device), static_cast<float*>(scores_device));
+  });
+}
 GTNX_API gtnx_status_t gtnx_batch_ctc_beam_stats(int64_t* calls, int64_t* utterances) {
   return guard([&] { batch_ctc_beam_stats(calls, utterances); });
 }

@@ -31,6 +31,14 @@
 //                 1 + t * beam + r = (node of its parent, label)
 //            At the end thread r < nbest walks the parents of slot r and stores the tokens back to front; all threads
 //            fill the rest of the rows with -1.
+// With a bigram table (tests/ctc_beam_lm_fp.py) the search kernel is its LM = true instantiation:
+// every beam also carries L, the table's score of its prefix, candidates rank by acoustic total + L, and pb / pnb stay
+// acoustic.  The gathers inc(i, k) = lm_weight * w(last_i -> label_k) + lm_bonus go out after step 1, when S_t and the
+// last labels are known (wave v takes beams v, v + 4, ..., its lane k member k of the set), fly during step 2 and are
+// parked in LDS before its barrier; step 4 reads them from there.  A key then holds the combined total, so step 6
+// computes an extension's score again, by step 4's expression; for that the key keeps the member's place in the set in
+// its lowest 6 bits, below a label of 19 bits (the engine refuses more labels with a table: it would not fit a device).
+// LM = false is the code above, statement for statement: everything else sits under `if constexpr (LM)`.
 // No global atomics; nothing depends on the order in which waves arrive (keys are distinct, every slot has one writer).
 // Every store is a plain C++ store; there is no inline assembly.
 #include <hip/hip_runtime.h>
@@ -176,8 +184,32 @@ __device__ __forceinline__ bool same_prefix(const GTNX_G gtnx_i2* trie, int x, i
   return true;
 }
 
+// what the LM = true kernel keeps in LDS on top of the lists: L of every beam in both list copies, and inc(i, k) of the
+// frame at [i * kMaxSet + k]
+template <bool LM>
+struct LmLds {
+  float L[2][kMaxBeam];
+  float inc[kMaxBeam * kMaxSet];
+};
+template <>
+struct LmLds<false> {};
+constexpr int kSearchWaves = kSearchBlock / 64;
+constexpr int kIncTrips = kMaxBeam / kSearchWaves;  // gathers a thread holds at most: one per beam of its wave
+
+// lm_weight * w + lm_bonus: a product rounded, then a sum rounded -- never fused, the order of the host forms
+__device__ __forceinline__ float lm_term(float weight, float w, float bonus) {
+#pragma clang fp contract(off)
+  const float scaled = weight * w;
+  return scaled + bonus;
+}
+
+// finite: neither an infinity nor NaN
+__device__ __forceinline__ bool finite_bits(float f) { return (__float_as_uint(f) & 0x7f800000u) != 0x7f800000u; }
+
+template <bool LM>
 __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamArgs a) {
   __shared__ Beams beams[2];
+  __shared__ LmLds<LM> lmv;
   __shared__ unsigned long long key[kKeySlots];
   __shared__ float tot[kMaxBeam], spb[kMaxBeam], spnb[kMaxBeam];
   __shared__ int lastk[kMaxBeam];                  // where the beam's last label sits in S_t, or -1
@@ -206,6 +238,7 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
     beams[0].len[0] = 0;
     beams[0].hash[0] = 0ull;
     beams[0].phash[0] = 0ull;
+    if constexpr (LM) lmv.L[0][0] = 0.0f;
   }
   // the token set of the coming frame, one entry per thread, loaded a frame ahead
   gtnx_i2 nxt = entry(NEG_INF, -1);
@@ -239,6 +272,30 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
     const Beams& B = beams[cur];
     Beams& N = beams[cur ^ 1];
     const int bk = s_blank_k;
+    // the gathers of the frame go out: lane k of wave v holds inc(i, k) of the beams i = v, v + 4, ...  (the blank is
+    // no extension: its row and column are never read; a label of S_t is below C, a last label too)
+    [[maybe_unused]] float incr[kIncTrips];
+    if constexpr (LM) {
+      // (every LDS read first and unconditionally, so that they travel together: a slot past the list or the set
+      //  holds some int, and its gather is not issued)
+      const int lane = tid & 63, wave = tid >> 6;
+      const int cl = sl[lane < kMaxSet ? lane : 0];
+      int lastq[kIncTrips];
+#pragma unroll
+      for (int q = 0; q < kIncTrips; ++q) lastq[q] = B.last[wave + q * kSearchWaves];
+      const int c = (lane < cnt && lane != bk) ? cl : -1;
+#pragma unroll
+      for (int q = 0; q < kIncTrips; ++q) {
+        const int i = wave + q * kSearchWaves;
+        incr[q] = 0.0f;
+        if (q * kSearchWaves >= nb) continue;  // (the same in every thread: a trip without a beam)
+        if (i < nb && c >= 0) {
+          const int l = lastq[q];
+          const int64_t at = l < 0 ? int64_t(c) : int64_t(a.C) + int64_t(c) * a.C + l;
+          incr[q] = a.lm[at];
+        }
+      }
+    }
     // ---- 2. the stays
     if (tid < nb) {
       const float pb = B.pb[tid], pnb = B.pnb[tid];
@@ -251,6 +308,16 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
       spb[tid] = bk >= 0 ? tt + sv[bk] : NEG_INF;
       spnb[tid] = (lk >= 0 && pnb > NEG_INF) ? pnb + sv[lk] : NEG_INF;
       lastk[tid] = lk;
+    }
+    if constexpr (LM) {
+      // (slots that are no extension -- past the set, the blank -- get the term of 0: finite, and never used)
+      const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+      for (int q = 0; q < kIncTrips; ++q) {
+        const int i = wave + q * kSearchWaves;
+        if (q * kSearchWaves >= nb) continue;
+        if (i < nb && lane < kMaxSet) lmv.inc[i * kMaxSet + lane] = lm_term(a.lm_weight, incr[q], a.lm_bonus);
+      }
     }
     __syncthreads();
     // ---- 3. the extension that is a beam of the list joins it.  Beam i is the parent of beam j when it spells
@@ -285,15 +352,28 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
       unsigned long long kk = ~0ull;
       if (idx < nb) {
         const float total = logadd(spb[idx], spnb[idx]);
-        if (total > NEG_INF) kk = (static_cast<unsigned long long>(falling_bits(total)) << 32) | (uint32_t(idx) << 25);
+        if constexpr (LM) {
+          if (total > NEG_INF)
+            kk = (static_cast<unsigned long long>(falling_bits(total + lmv.L[cur][idx])) << 32) | (uint32_t(idx) << 25);
+        } else {
+          if (total > NEG_INF) kk = (static_cast<unsigned long long>(falling_bits(total)) << 32) | (uint32_t(idx) << 25);
+        }
       } else if (idx < ncand) {
         const int e = idx - nb, i = e / cnt, k = e - i * cnt;
         const int c = sl[k];
         const float base = c == B.last[i] ? B.pb[i] : tot[i];
         const float s = base + sv[k];
-        if (k != bk && !((struck[i] >> k) & 1ull) && base > NEG_INF && s > NEG_INF)
-          kk = (static_cast<unsigned long long>(falling_bits(s)) << 32) | 0x80000000u | (uint32_t(i) << 25) |
-               uint32_t(c);
+        if constexpr (LM) {
+          const float inc = lmv.inc[i * kMaxSet + k];  // (the blank's slot is finite, and the test on k drops it)
+          const float Li = lmv.L[cur][i];
+          if (k != bk && !((struck[i] >> k) & 1ull) && base > NEG_INF && s > NEG_INF && finite_bits(inc))
+            kk = (static_cast<unsigned long long>(falling_bits(s + (Li + inc))) << 32) | 0x80000000u |
+                 (uint32_t(i) << 25) | (uint32_t(c) << 6) | uint32_t(k);  // (C <= 2^19 with a table; k <= 32)
+        } else {
+          if (k != bk && !((struck[i] >> k) & 1ull) && base > NEG_INF && s > NEG_INF)
+            kk = (static_cast<unsigned long long>(falling_bits(s)) << 32) | 0x80000000u | (uint32_t(i) << 25) |
+                 uint32_t(c);
+        }
       }
       key[idx] = kk;
     }
@@ -333,11 +413,21 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
           N.len[place] = B.len[i];
           N.hash[place] = B.hash[i];
           N.phash[place] = B.phash[i];
+          if constexpr (LM) lmv.L[cur ^ 1][place] = lmv.L[cur][i];
         } else {
-          const int c = int(lo & 0x1ffffffu);
+          const int c = LM ? int((lo >> 6) & 0x7ffffu) : int(lo & 0x1ffffffu);
           const int nd = 1 + t * W + place;  // (M * beam < 2^31)
           N.pb[place] = NEG_INF;
-          N.pnb[place] = from_falling_bits(uint32_t(mine >> 32));
+          if constexpr (LM) {
+            // the key holds the combined total: the acoustic score again, by step 4's expression (the same bits; +0
+            // for -0, as the key's bits give it), and L of the new prefix, by step 4's too
+            const int k = int(lo & 63u);
+            const float s = (c == B.last[i] ? B.pb[i] : tot[i]) + sv[k];
+            N.pnb[place] = s + 0.0f;
+            lmv.L[cur ^ 1][place] = lmv.L[cur][i] + lmv.inc[i * kMaxSet + k];
+          } else {
+            N.pnb[place] = from_falling_bits(uint32_t(mine >> 32));
+          }
           N.node[place] = nd;
           N.last[place] = c;
           N.parent[place] = B.node[i];
@@ -370,9 +460,14 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
     GTNX_G int* row = a.tokens + (int64_t(b) * nbest + r) * a.row_stride;
     int len = 0;
     float score = NEG_INF;
+    [[maybe_unused]] float am = NEG_INF;
     if (r < nb) {
       len = F.len[r];  // (a prefix grows by at most one label per frame: len <= T <= M)
       score = logadd(F.pb[r], F.pnb[r]);
+      if constexpr (LM) {
+        am = score;
+        score = am + lmv.L[cur][r];
+      }
       int nd = F.node[r], lab = F.last[r], par = F.parent[r];
       for (int k = len - 1; k >= 0 && nd > 0; --k) {
         row[k] = lab;
@@ -386,6 +481,8 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
     }
     a.lengths[int64_t(b) * nbest + r] = len;
     a.scores[int64_t(b) * nbest + r] = score;
+    if constexpr (LM)
+      if (a.am_scores) a.am_scores[int64_t(b) * nbest + r] = am;
   }
 }
 
@@ -418,7 +515,10 @@ void launch_ctc_beam(const CtcBeamArgs& a, int which, hipStream_t st) {
     else launch_rows<64>(a, st);
     return;
   }
-  hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(static_cast<unsigned>(a.n)), dim3(kSearchBlock), 0, st, a);
+  if (a.lm)
+    hipLaunchKernelGGL(ctc_beam_search_kernel<true>, dim3(static_cast<unsigned>(a.n)), dim3(kSearchBlock), 0, st, a);
+  else
+    hipLaunchKernelGGL(ctc_beam_search_kernel<false>, dim3(static_cast<unsigned>(a.n)), dim3(kSearchBlock), 0, st, a);
 }
 
 }  // namespace gtnx

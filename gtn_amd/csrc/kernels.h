@@ -847,6 +847,13 @@ struct CtcBeamArgs {
   GTNX_G float* scores;
   int64_t row_stride;
   int n, M, C, blank, beam, topn, nbest;
+  // the bigram table, or null: [C + C * C], w[c] = c as first label, w[C + i * C + j] = j followed
+  // by i.  With it candidates rank by acoustic total + L, L(prefix) = sum of lm_weight * w + lm_bonus, an extension
+  // with a non-finite term is dropped, scores holds acoustic + L and am_scores (may be null) the acoustic total alone.
+  // C <= 2^19 with a table (the engine has refused the rest).
+  const GTNX_G float* lm;
+  float lm_weight, lm_bonus;
+  GTNX_G float* am_scores;
 };
 void launch_ctc_beam(const CtcBeamArgs& a, int which, hipStream_t st);
 // edit_distance.hip: Levenshtein distance (unit costs) of the pairs pair0 .. pair0 + count - 1, pair p = b * N + k being

@@ -650,6 +650,14 @@ bool local_to(const void* p, int dev) {
 }
 }  // namespace
 bool ptr_local_to(const void* p, int dev) { return local_to(p, dev); }
+bool ptr_device_memory_of(const void* p, int dev) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice && a.device == dev;
+}
 // (up to a megabyte by a kernel of ours -- kernels.h: launch_copy_small; the runtime's copy costs the host about twice
 // a launch, and the copies of this size are the ones at the head of a latency chain: setWeights of one utterance)
 void Runtime::d2d(void* dst, const void* src, size_t bytes) {

@@ -199,6 +199,10 @@ class Runtime {
 // may a kernel running on device `dev` touch p?  (Host memory and that device's own: yes; another GPU's: no.  With one
 // GPU in the process there is nothing to ask.)
 bool ptr_local_to(const void* p, int dev);
+// is p memory allocated on device `dev`?  Always asks the runtime: for an input a kernel gathers from, where pageable
+// host memory must be refused whatever the number of GPUs.  Pinned or registered host memory and managed memory are
+// refused too.
+bool ptr_device_memory_of(const void* p, int dev);
 
 #define GTNX_PROF(name, bytes) ::gtnx::Runtime::Scope _prof_scope(&::gtnx::Runtime::get(), name, bytes)
 

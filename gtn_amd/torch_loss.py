@@ -7,6 +7,7 @@ the GPU (no inputs.cpu(), no per-sample weights_to_numpy), the batch runs throug
 the batched graph functions, and the emission gradients come back as one tensor.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -17,7 +18,7 @@ import gtn_amd as gtn
 _NATIVE = None
 
 
-_P, _I = C.c_void_p, C.c_int
+_P, _I, _F = C.c_void_p, C.c_int, C.c_float
 # the argument types of libgtn_criteria.so's entry points (gtn_amd/criteria/criteria_capi.cpp); all return an int.  A
 # library from before an entry point lacks its symbol
 _ARGTYPES = {
@@ -30,6 +31,7 @@ _ARGTYPES = {
     "gtn_asg_decode_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "gtn_ctc_decode_n": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "gtn_ctc_beam_decode_n": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P],
+    "gtn_ctc_beam_decode_lm_n": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _F, _F, _P, _P, _P, _P],
     "gtn_edit_distance_n": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "gtn_ctc_score_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P],
     "gtn_ctc_score_grad_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P],
@@ -520,7 +522,8 @@ def ctc_decode(log_probs, blank=0, input_lengths=None, collapse=True):
     return (labels, scores, tokens, starts, lengths) if collapse else (labels, scores)
 
 
-def ctc_beam_decode(log_probs, blank=0, input_lengths=None, beam_size=16, cutoff_top_n=16, nbest=1):
+def ctc_beam_decode(log_probs, blank=0, input_lengths=None, beam_size=16, cutoff_top_n=16, nbest=1, transitions=None,
+                    start=None, lm_weight=1.0, insertion_bonus=0.0, return_am_scores=False):
     """CTC prefix beam search of a batch with N-best output, device-resident: the best label sequences, summed over
     their alignments, where `ctc_decode` gives the best alignment -- two launches whatever the lengths, nothing copied
     back.
@@ -534,7 +537,15 @@ def ctc_beam_decode(log_probs, blank=0, input_lengths=None, beam_size=16, cutoff
     kept (float32 log-add; unpruned it is -ctc_loss of that sequence).  Of exactly equal scores the order is: a prefix
     that stayed before one that grew, then the parent's rank, then the label; NaN and -inf are never chosen.  Slots
     without a hypothesis -- fewer than nbest prefixes, a frame with nothing above -inf, an utterance without frames --
-    get -1, length 0 and score -inf.  Runs on the caller's stream; no autograd."""
+    get -1, length 0 and score -inf.  Runs on the caller's stream; no autograd.
+    transitions [C, C] (and start [C], zeros if None): the bigram tables `asg_loss` learns, fused into the ranking --
+    transitions[i, j] scores label j followed by label i, start[c] label c as the first.  Every label of a prefix adds
+    lm_weight * (its table entry) + insertion_bonus to the prefix's language model score L (float32, left to right);
+    candidates rank by acoustic total + L, a -inf entry forbids its bigram or first label, the cutoff_top_n pruning
+    stays acoustic and rows and columns of `blank` are never read.  Both tables are detached and may be non-contiguous.
+    `scores` is then acoustic + L; with return_am_scores a fourth tensor, float32 [B, nbest], has the acoustic total
+    alone (unpruned, `ctc_score` of those tokens), -inf in empty slots.  transitions=None is the search without a
+    language model, whatever the other four say."""
     if log_probs.dim() != 3 or log_probs.dtype != torch.float32:
         raise ValueError("ctc_beam_decode: log_probs must be a float32 tensor [B, T, C]")
     B, T, N = log_probs.shape
@@ -548,13 +559,40 @@ def ctc_beam_decode(log_probs, blank=0, input_lengths=None, beam_size=16, cutoff
     if not 1 <= nbest <= beam_size:
         raise ValueError("ctc_beam_decode: nbest outside 1 .. beam_size")
     frames = None if input_lengths is None else _frame_counts("ctc_beam_decode", input_lengths, B, T, 0)
+    if transitions is not None:
+        if transitions.dim() != 2 or tuple(transitions.shape) != (N, N):
+            raise ValueError(f"ctc_beam_decode: transitions must be a tensor [{N}, {N}]")
+        if start is not None and tuple(start.shape) != (N,):
+            raise ValueError(f"ctc_beam_decode: start must be a tensor [{N}]")
+        lm_weight, insertion_bonus = float(lm_weight), float(insertion_bonus)
+        if not (math.isfinite(lm_weight) and math.isfinite(insertion_bonus)):
+            raise ValueError("ctc_beam_decode: lm_weight and insertion_bonus must be finite")
     if not log_probs.is_cuda:
         raise RuntimeError("ctc_beam_decode: log_probs must be a CUDA tensor (the search runs on the device)")
     x = log_probs.detach().contiguous()
+    table = None
+    if transitions is not None:
+        # (written on the caller's stream BEFORE the engine is pointed at it: on the null stream _engine_stream waits
+        #  once for what is queued so far, and the engine's own stream is ordered with nothing that comes after)
+        tr = transitions.detach().to(x.device)
+        st = torch.zeros(N, dtype=torch.float32, device=x.device) if start is None else start.detach().to(x.device)
+        table = _asg_weights(st, tr)
     stream = _engine_stream(x.device)
     tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=x.device)
     lengths = torch.empty(B, nbest, dtype=torch.int32, device=x.device)
     scores = torch.empty(B, nbest, dtype=torch.float32, device=x.device)
+    if table is not None:
+        am = torch.empty(B, nbest, dtype=torch.float32, device=x.device) if return_am_scores else None
+        if _has_native("ctc_beam_decode", "gtn_ctc_beam_decode_lm_n"):
+            _call("gtn_ctc_beam_decode_lm_n", x.data_ptr(), B, T, N, blank, _host_ptr(frames), beam_size, cutoff_top_n,
+                  nbest, table.data_ptr(), lm_weight, insertion_bonus, tokens.data_ptr(), lengths.data_ptr(),
+                  scores.data_ptr(), _ptr(am))
+        else:
+            ems = gtn.Batch.linear(B, T, N, x, calc_grad=False, borrow=True)
+            ems.ctc_beam_decode(tokens, lengths, scores, frames, blank, beam_size, cutoff_top_n, nbest, row_stride=T,
+                                lm=table, lm_weight=lm_weight, insertion_bonus=insertion_bonus, am_scores_out=am)
+        _engine_done(stream)
+        return (tokens, lengths, scores, am) if return_am_scores else (tokens, lengths, scores)
     if _has_native("ctc_beam_decode", "gtn_ctc_beam_decode_n"):
         _call("gtn_ctc_beam_decode_n", x.data_ptr(), B, T, N, blank, _host_ptr(frames), beam_size, cutoff_top_n, nbest,
               tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr())

@@ -198,6 +198,19 @@ inline void ctcBeamDecode(const Batch& ems, int* tokensDevice, int64_t rowStride
   detail::check(gtnx_batch_ctc_beam_decode(ems.handle(), frames, blank, beamSize, cutoffTopN, nbest, tokensDevice,
                                            rowStride, lengthsDevice, scoresDevice));
 }
+/** The same search with a bigram over the labels fused into the ranking: lmDevice float32 [C + C * C] in the arc order
+ *  of criteria::asgTransitions (lm[c]: c as first label; lm[C + i * C + j]: j followed by i); a prefix carries L = the
+ *  sum over its labels of lmWeight * lm(...) + insertionBonus, candidates rank by acoustic total + L, -inf in the table
+ *  forbids.  scoresDevice: acoustic + L; amScoresDevice (may be null): the acoustic total alone --
+ *  gtnx_batch_ctc_beam_decode_lm */
+inline void ctcBeamDecode(const Batch& ems, const float* lmDevice, float lmWeight, float insertionBonus,
+                          int* tokensDevice, int64_t rowStride, int* lengthsDevice, float* scoresDevice,
+                          float* amScoresDevice = nullptr, int blank = 0, int beamSize = 16, int cutoffTopN = 16,
+                          int nbest = 1, const int* frames = nullptr) {
+  detail::check(gtnx_batch_ctc_beam_decode_lm(ems.handle(), frames, blank, beamSize, cutoffTopN, nbest, lmDevice,
+                                              lmWeight, insertionBonus, tokensDevice, rowStride, lengthsDevice,
+                                              scoresDevice, amScoresDevice));
+}
 /** Levenshtein distance (unit costs) of all B * N pairs (hyp[b, k], ref[b]) of device-resident token rows, results left
  *  on the device: hypDevice int32 B * N rows of width L, hypStride (>= L) apart, hypLengthsDevice int32 [B][N];
  *  refDevice int32 B rows of width U, refStride (>= U) apart, refLengthsDevice int32 [B] -- the lengths are device

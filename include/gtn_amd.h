@@ -393,6 +393,32 @@ gtnx_status_t gtnx_batch_linear_decode_stats(int64_t* fast, int64_t* fallback);
 gtnx_status_t gtnx_batch_ctc_beam_decode(gtnx_batch_t ems, const int* frames, int blank, int beam_size,
                                          int cutoff_top_n, int nbest, void* tokens_device, int64_t row_stride,
                                          void* lengths_device, void* scores_device);
+/* gtnx_batch_ctc_beam_decode with a bigram over the labels fused into the ranking.
+ * lm_device: DEVICE float32 [C + C * C] in the arc order of gtn::criteria::asgTransitions: lm[c] is the score of c as
+ * first label, lm[C + i * C + j] the score of label j followed by label i -- the tables asg_loss learns. Every prefix
+ * y carries L(y) = sum_k (lm_weight * lm(y_{k-1} -> y_k) + insertion_bonus), float32, accumulated left to right;
+ * L(()) = 0.
+ * Everything above holds with these changes: a candidate ranks by its acoustic total plus L of its prefix (a stay by
+ * logadd(pb', pnb') + L(y), an extension of y by c by s + (L(y) + inc), s as above; the same order; a candidate whose
+ * acoustic total is -inf is dropped as above); an extension whose inc is -inf, +inf or NaN is dropped, so a -inf entry
+ * forbids a bigram or a first label; rows and columns of `blank` are never read; an extension that joins a prefix of
+ * the list adds acoustic mass only; the cutoff_top_n pruning of a row and (pb, pnb) stay acoustic; a prefix that
+ * leaves the list and is created again gets the same L bit for bit.
+ * scores_device: float32 [n][nbest], acoustic total + L; am_scores_device (may be null): float32 [n][nbest], the
+ * acoustic total alone -- unpruned, what gtnx_batch_ctc_score gives for those tokens. Slots without a hypothesis get
+ * -1, 0, -inf, -inf. With lm_weight = insertion_bonus = 0 and a finite table every output is byte-identical to
+ * gtnx_batch_ctc_beam_decode and am_scores to scores.
+ * GTNX_INVALID_ARGUMENT on top of gtnx_batch_ctc_beam_decode's, before a device is asked for: a null lm_device, an
+ * lm_weight or insertion_bonus that is not finite; with the device: more than 2^19 labels (such a table has no device
+ * to live on); lm_device is anything but memory allocated on the engine's current device -- the kernel gathers from
+ * it, so pageable host memory is refused with one GPU as well, and so are pinned or registered host memory and managed
+ * memory, which a kernel could read: copy such a table to the device first; am_scores_device is memory the device may
+ * not write. Nothing is written by a refused call. Counted by gtnx_batch_ctc_beam_stats. */
+gtnx_status_t gtnx_batch_ctc_beam_decode_lm(gtnx_batch_t ems, const int* frames, int blank, int beam_size,
+                                            int cutoff_top_n, int nbest, const void* lm_device, float lm_weight,
+                                            float insertion_bonus, void* tokens_device, int64_t row_stride,
+                                            void* lengths_device, void* scores_device,
+                                            void* am_scores_device /* may be null */);
 /* calls that have launched so far (process-wide) / utterances they decoded */
 gtnx_status_t gtnx_batch_ctc_beam_stats(int64_t* calls, int64_t* utterances);
 /* Levenshtein distance of all B * N pairs (hyp[b, k], ref[b]) of token rows that live on the device, results left on

@@ -20,6 +20,14 @@ claim.
         adds those means to the record: the row kernel beside linear_decode_rows_kernel and as a fraction of its own
         byte model (4 C in, 8 (K + 1) + 4 out per row) at the stream rate, the search kernel per batch and per frame.
 
+    python tools/bench_ctc_beam.py --lm [--out profiles/ctc_beam_lm_c3.json]
+        the same tensor with a seeded bigram table fused in (Batch.ctc_beam_decode(lm=...), lm_weight 0.8,
+        insertion_bonus 0.5, am_scores written too) beside the call without one: three samples of each, alternating,
+        every sample a process of its own.  `--worker trace --lm` and `--merge-stats CSV --lm` add the mean times of
+        the two instantiations of the search kernel (ms per batch, us per frame) and the cost of the table over the
+        call without it; with `--lm-weight 0 --lm-bonus 0` on both, the same at a weight and bonus of zero, where the
+        two searches keep the same prefixes and only the table's code differs.
+
 Needs a GPU; a measurement path that finds none fails.
 """
 import argparse
@@ -35,6 +43,7 @@ STREAM_GBS = 6300.0  # the achievable HBM stream rate the floor is derived from
 B, T, C = 512, 1000, 256
 BLANK, BEAM, TOPN, NBEST = 0, 16, 16, 1
 WINDOW_S = 0.5
+LM_WEIGHT, LM_BONUS = 0.8, 0.5
 
 
 def inputs(torch):
@@ -55,7 +64,14 @@ def byte_model():
     return rows, search
 
 
-def worker(kind, beam=BEAM, topn=TOPN):
+def lm_table(torch):
+    """a seeded bigram table [C + C * C]: normal(0, 2)"""
+    g = torch.Generator(device="cuda")
+    g.manual_seed(4321)
+    return (torch.randn((C + C * C,), generator=g, device="cuda", dtype=torch.float32) * 2.0).contiguous()
+
+
+def worker(kind, beam=BEAM, topn=TOPN, lm=False, lm_weight=LM_WEIGHT, lm_bonus=LM_BONUS):
     sys.path.insert(0, HERE)
     import torch
     import gtn_amd as gtn
@@ -69,6 +85,13 @@ def worker(kind, beam=BEAM, topn=TOPN):
     gsta = torch.empty((B, T), dtype=torch.int32, device="cuda")
     gsc = torch.empty((B,), dtype=torch.float32, device="cuda")
     glen = torch.empty((B,), dtype=torch.int32, device="cuda")
+    table = lm_table(torch) if lm or kind == "beam_lm" else None
+    am_scores = torch.empty((B, NBEST), dtype=torch.float32, device="cuda")
+
+    def beam_lm_step():
+        ems = gtn.Batch.linear(B, T, C, em, False, True)
+        ems.ctc_beam_decode(tokens, lengths, scores, None, BLANK, beam, topn, NBEST, lm=table, lm_weight=lm_weight,
+                            insertion_bonus=lm_bonus, am_scores_out=am_scores)
 
     def beam_step():
         ems = gtn.Batch.linear(B, T, C, em, False, True)
@@ -98,15 +121,27 @@ def worker(kind, beam=BEAM, topn=TOPN):
     if kind == "trace":
         for _ in range(5):
             beam_step()
-            greedy_step()
+            if lm:
+                beam_lm_step()
+            else:
+                greedy_step()
             sync()
         print(json.dumps({"trace": "done"}))
         return
     c0 = gtn.debug_ctc_beam_stats()
-    ms, n = timed(beam_step if kind == "beam" else greedy_step)
+    ms, n = timed({"beam": beam_step, "beam_lm": beam_lm_step, "greedy": greedy_step}[kind])
     sync()
     c1 = gtn.debug_ctc_beam_stats()
     rec = {"kind": kind, "utterances": B, "ms_per_batch": ms, "iters": n, "beam_utterances": c1[1] - c0[1]}
+    if kind == "beam_lm":
+        rec["mean_length"] = float(lengths.float().mean().item())
+        rec["mean_score"] = float(scores.mean().item())
+        rec["mean_am_score"] = float(am_scores.mean().item())
+        first = tokens.clone()
+        beam_step()
+        sync()
+        rec["utterances_whose_first_hypothesis_differs_from_the_call_without_a_table"] = int(
+            (first != tokens).any(dim=2).any(dim=1).sum().item())
     if kind == "beam":
         rec["mean_length"] = float(lengths.float().mean().item())
         rec["mean_score"] = float(scores.mean().item())
@@ -137,16 +172,76 @@ KERNELS = ("ctc_beam_rows_kernel", "ctc_beam_search_kernel", "linear_decode_rows
            "linear_decode_collapse_kernel")
 
 
+LM_KERNELS = {"without_table": ("ctc_beam_search_kernel<false>", "ctc_beam_search_kernelILb0E"),
+              "with_table": ("ctc_beam_search_kernel<true>", "ctc_beam_search_kernelILb1E")}
+
+
+def main_lm(a):
+    """the --lm record: end to end with and without the table, or (--merge-stats) the two search kernels' means"""
+    rec = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            rec = json.load(f)
+    if a.merge_stats:
+        means = {}
+        with open(a.merge_stats) as f:
+            for row in csv.DictReader(f):
+                for key, names in LM_KERNELS.items():
+                    if any(n in row["Name"] for n in names):
+                        ms = float(row["AverageNs"]) * 1e-6
+                        means[key] = {"calls": int(row["Calls"]), "ms_per_batch": ms, "us_per_frame_of_the_batch": ms * 1e3 / T,
+                                      "min_ms": float(row["MinNs"]) * 1e-6, "max_ms": float(row["MaxNs"]) * 1e-6}
+        assert len(means) == 2, means
+        # (at weight = bonus = 0 the search is the one without a table, step for step: what the table's code costs)
+        tag = "" if (a.lm_weight, a.lm_bonus) == (LM_WEIGHT, LM_BONUS) else f"_at_weight_{a.lm_weight:g}_bonus_{a.lm_bonus:g}"
+        rec["search_kernel" + tag] = means
+        rec["search_kernel_with_table_over_without" + tag] = (means["with_table"]["ms_per_batch"]
+                                                              / means["without_table"]["ms_per_batch"])
+    else:
+        plain, fused, last = [], [], None
+        for _ in range(3):
+            plain.append(run_worker("beam")["ms_per_batch"])
+            last = run_worker("beam_lm")
+            assert last["beam_utterances"] > 0, last
+            fused.append(last["ms_per_batch"])
+        rec.update({"shape": {"B": B, "T": T, "C": C, "blank": BLANK, "beam_size": BEAM, "cutoff_top_n": TOPN,
+                              "nbest": NBEST, "lm_weight": LM_WEIGHT, "insertion_bonus": LM_BONUS,
+                              "table": "normal(0, 2), seeded, C + C * C float32"},
+                    "unit": "ms per batch, host clock around a closing synchronise, windows >= 0.5 s",
+                    "beam": dict(spread(plain), what="Batch.ctc_beam_decode without a table", utterances=B),
+                    "beam_lm": dict(spread(fused), what="Batch.ctc_beam_decode(lm=...) with am_scores_out",
+                                    utterances=B),
+                    "beam_lm_over_beam": sorted(fused)[1] / sorted(plain)[1],
+                    "gathers_per_frame_at_most": BEAM * (TOPN + 1),
+                    "mean_length": last["mean_length"], "mean_score": last["mean_score"],
+                    "mean_am_score": last["mean_am_score"],
+                    "utterances_whose_first_hypothesis_differs_from_the_call_without_a_table":
+                        last["utterances_whose_first_hypothesis_differs_from_the_call_without_a_table"]})
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--worker", choices=["beam", "greedy", "trace"])
+    ap.add_argument("--worker", choices=["beam", "beam_lm", "greedy", "trace"])
+    ap.add_argument("--lm", action="store_true")
+    ap.add_argument("--lm-weight", type=float, default=LM_WEIGHT)
+    ap.add_argument("--lm-bonus", type=float, default=LM_BONUS)
     ap.add_argument("--merge-stats")
     ap.add_argument("--beam", type=int, default=BEAM)
     ap.add_argument("--topn", type=int, default=TOPN)
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "ctc_beam_c3.json"))
+    ap.add_argument("--out")
     a = ap.parse_args()
     if a.worker:
-        worker(a.worker, a.beam, a.topn)
+        worker(a.worker, a.beam, a.topn, a.lm, a.lm_weight, a.lm_bonus)
+        return
+    if not a.out:
+        a.out = os.path.join(HERE, "profiles", "ctc_beam_lm_c3.json" if a.lm else "ctc_beam_c3.json")
+    if a.lm:
+        main_lm(a)
         return
     rec = {}
     if os.path.exists(a.out):
