@@ -73,6 +73,7 @@ debug_ctc_beam_stats = _api.debug_ctc_beam_stats  # (Batch.ctc_beam_decode: call
 edit_distance = _api.edit_distance  # (batched Levenshtein distance of device-resident token rows)
 debug_edit_distance_stats = _api.debug_edit_distance_stats  # (edit_distance: calls that launched, pairs computed)
 debug_ctc_score_stats = _api.debug_ctc_score_stats  # (Batch.ctc_score / ctc_score_grad: calls that launched, pairs taken)
+debug_ctc_token_align_stats = _api.debug_ctc_token_align_stats  # (Batch.ctc_token_align: calls that launched, pairs aligned)
 
 
 def load_txt(text):

@@ -147,6 +147,10 @@ _SIGS = {
     "gtnx_batch_ctc_score_grad": [c_graph, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int,
                                   C.c_int, C.c_void_p, C.c_void_p],
     "gtnx_batch_ctc_score_stats": [c_i64_p, c_i64_p],
+    "gtnx_batch_ctc_token_align": [c_graph, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int,
+                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                   C.c_int64],
+    "gtnx_batch_ctc_token_align_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_backward": [c_graph, C.c_int],
     "gtnx_batch_items": [c_graph, C.c_void_p],
     "gtnx_batch_items_device": [c_graph, C.c_void_p],

@@ -973,6 +973,58 @@ def make_api(lib):
                                                 _opt_ptr(tok), stride, _opt_ptr(ln), N, L, U, _opt_ptr(weights),
                                                 _opt_ptr(grad_out)))
 
+        def ctc_token_align(self, tokens, lengths, scores_out, starts_out, ends_out, token_scores_out=None,
+                            frame_tokens_out=None, frames=None, blank=0, max_length=None, N=None, L=None,
+                            row_stride=None, out_stride=None, frame_stride=None):
+            """The best alignment of all B * N device-resident hypotheses under the slabs of a Batch.linear, results left
+            on the device (gtnx_batch_ctc_token_align; DESIGN section 24 holds the contract).  `tokens`, `lengths`,
+            `frames`, `blank`, `max_length`, N, L and row_stride are those of `ctc_score`.  `scores_out` float32 [B, N]:
+            the Viterbi score, -inf without a path; `starts_out` / `ends_out` int32 [B, N, L]: the first frame of token i
+            and one past its last, -1 for i >= len and without a path; `token_scores_out` float32 [B, N, L] or None: the
+            token's emissions summed in frame order; `frame_tokens_out` int32 [B, N, M] or None: the token index of every
+            frame, -1 on blank frames and from T_b on.  Tensors need contiguous, equally spaced rows (views of wider
+            tensors are fine: only the widths L and M are written); device addresses go with `out_stride` (>= L, default
+            L) and `frame_stride` (>= M, default M).  Float32 max-plus with the tie rule of `viterbi_align`: the same bits
+            every time.  No copy back and no wait."""
+            who = "ctc_token_align"
+            n = len(self)
+            fr, tok, stride, ln, N, L, U = self._ctc_score_args(who, tokens, lengths, frames, N, L, row_stride, max_length)
+
+            def rows_of(t, name, dtype, width, given):
+                """the row stride of an output: that of a tensor [B, N, width], else `given`"""
+                if t is None or not hasattr(t, "data_ptr"):
+                    return given
+                if str(t.dtype) != dtype or t.dim() != 3 or tuple(t.shape[:2]) != (n, N) or (width is not None
+                                                                                               and t.shape[2] != width):
+                    raise ValueError(f"{who}: {name} must be a {dtype[6:]} tensor [B, N, {'L' if name != 'frame_tokens_out' else 'M'}]")
+                if ((t.shape[2] > 1 and t.stride(2) != 1)
+                        or (t.shape[0] > 1 and t.shape[1] > 1 and t.stride(0) != t.shape[1] * t.stride(1))):
+                    raise ValueError(f"{who}: {name} must have contiguous rows, equally spaced")
+                rows = t.stride(1) if t.shape[1] > 1 else (t.stride(0) if t.shape[0] > 1 else max(t.shape[2], 1))
+                if given is not None and int(given) != int(rows):
+                    raise ValueError(f"{who}: the outputs must have one row stride ({name} has {rows}, not {given})")
+                return rows
+            for t, name, dtype in ((starts_out, "starts_out", "torch.int32"), (ends_out, "ends_out", "torch.int32"),
+                                   (token_scores_out, "token_scores_out", "torch.float32")):
+                out_stride = rows_of(t, name, dtype, L, out_stride)
+            frame_stride = rows_of(frame_tokens_out, "frame_tokens_out", "torch.int32", None, frame_stride)
+            if out_stride is None:
+                out_stride = L
+            if frame_stride is None:
+                m, c = C.c_int(-1), C.c_int(-1)
+                check(lib.gtnx_batch_linear_shape(self._h, C.byref(m), C.byref(c)))
+                frame_stride = max(m.value, 0)
+            if scores_out is not None and hasattr(scores_out, "data_ptr"):
+                if (str(scores_out.dtype) != "torch.float32" or not scores_out.is_contiguous()
+                        or scores_out.numel() != n * N):
+                    raise ValueError(f"{who}: scores_out must be a float32 contiguous tensor [B, N]")
+                if n * N == 0:
+                    return
+            check(lib.gtnx_batch_ctc_token_align(self._h, fr.ctypes.data if fr is not None else None, int(blank),
+                                                 _opt_ptr(tok), stride, _opt_ptr(ln), N, L, U, _opt_ptr(scores_out),
+                                                 _opt_ptr(starts_out), _opt_ptr(ends_out), _opt_ptr(token_scores_out),
+                                                 int(out_stride), _opt_ptr(frame_tokens_out), int(frame_stride)))
+
     ns.Batch = Batch
 
     def _batch_fn(cfn, *args):
@@ -1111,6 +1163,11 @@ def make_api(lib):
         took (include/gtn_amd.h: gtnx_batch_ctc_score_stats)"""
         return _stats2(lib.gtnx_batch_ctc_score_stats)
 
+    def debug_ctc_token_align_stats():
+        """(calls, pairs): calls of Batch.ctc_token_align that have launched so far and the pairs they aligned
+        (include/gtn_amd.h: gtnx_batch_ctc_token_align_stats)"""
+        return _stats2(lib.gtnx_batch_ctc_token_align_stats)
+
     def debug_edit_distance_stats():
         """(calls, pairs): calls of edit_distance that have launched so far and the pairs they computed
         (include/gtn_amd.h: gtnx_batch_edit_distance_stats)"""
@@ -1199,6 +1256,7 @@ def make_api(lib):
     ns.debug_ctc_beam_stats = debug_ctc_beam_stats
     ns.debug_edit_distance_stats = debug_edit_distance_stats
     ns.debug_ctc_score_stats = debug_ctc_score_stats
+    ns.debug_ctc_token_align_stats = debug_ctc_token_align_stats
     ns.edit_distance = edit_distance
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties

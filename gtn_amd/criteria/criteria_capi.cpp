@@ -133,6 +133,18 @@ GTN_EXPORT int gtn_ctc_score_grad_n(const void* emissions, int B, int T, int C, 
   });
 }
 
+// The best alignment of B * N device-resident hypotheses.  emissions: DEVICE float32 [B][T][C]; frames: HOST int [B] or
+// null; tokens: DEVICE int32 [B][N][L]; lengths: DEVICE int32 [B][N]; scores: DEVICE float32 [B][N]; starts / ends: DEVICE
+// int32 [B][N][L]; token_scores: DEVICE float32 [B][N][L] or null; frame_tokens: DEVICE int32 [B][N][T] or null.
+GTN_EXPORT int gtn_ctc_token_align_n(const void* emissions, int B, int T, int C, int blank, const int* frames,
+                                     const void* tokens, const void* lengths, int N, int L, int max_length,
+                                     void* scores, void* starts, void* ends, void* token_scores, void* frame_tokens) {
+  return guarded([&] {
+    gtn::criteria::ctcTokenAlignBatch(emissions, B, T, C, blank, frames, tokens, lengths, N, L, max_length, scores,
+                                      starts, ends, token_scores, frame_tokens);
+  });
+}
+
 // Edit distance of all B * N pairs (hyp[b][k], ref[b]).  hyp: DEVICE int32 [B][N][L]; hyp_lengths: DEVICE int32 [B][N];
 // ref: DEVICE int32 [B][U]; ref_lengths: DEVICE int32 [B]; dist: DEVICE int32 [B][N]; ops: DEVICE int32 [B][N][3] or
 // null.

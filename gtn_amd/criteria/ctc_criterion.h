@@ -251,5 +251,35 @@ inline void ctcScoreBatch(
   }
 }
 
+/** The best alignment of B * N device-resident hypotheses under the B emission slabs -- when each token was spoken and
+ *  how well the frames support it: `emissions` device float32 [B][T][C], read in place; `tokensDev` device int32
+ *  [B][N][L] and `lengthsDev` device int32 [B][N] (dense rows, what ctcBeamDecodeBatch wrote); `frames` host [B] or null;
+ *  `scoresDev` device float32 [B][N]; `startsDev` / `endsDev` device int32 [B][N][L]; `tokenScoresDev` device float32
+ *  [B][N][L] or null; `frameTokensDev` device int32 [B][N][T] or null.  gtnx_batch_ctc_token_align has the contract.
+ *  Nothing is copied back. */
+inline void ctcTokenAlignBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int C,
+    int blank,
+    const int* frames,
+    const void* tokensDev,
+    const void* lengthsDev,
+    int N,
+    int L,
+    int maxLength,
+    void* scoresDev,
+    void* startsDev,
+    void* endsDev,
+    void* tokenScoresDev = nullptr,
+    void* frameTokensDev = nullptr) {
+  Batch ems = Batch::linear(B, T, C, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  batched::ctcTokenAlign(ems, static_cast<const int*>(tokensDev), L, static_cast<const int*>(lengthsDev), N, L,
+                         maxLength, static_cast<float*>(scoresDev), static_cast<int*>(startsDev),
+                         static_cast<int*>(endsDev), static_cast<float*>(tokenScoresDev), L,
+                         static_cast<int*>(frameTokensDev), T, blank, frames);
+}
+
 } // namespace criteria
 } // namespace gtn

@@ -235,6 +235,24 @@ void batch_ctc_score_grad(const BatchP& ems, const int* frames, int blank, const
                           const int* lengths_dev, int N, int L, int max_length, const float* weights_dev,
                           float* grad_dev);
 void batch_ctc_score_stats(int64_t* calls, int64_t* pairs);  // calls that launched (either kind) / pairs they took
+// The best alignment of all n * N device-resident hypotheses (the pair form of batch_ctc_score) under the n emission
+// slabs of a native linear batch, results on the device (DESIGN section 24 holds the contract): scores_dev [n][N] the
+// Viterbi score, starts_dev / ends_dev (n * N rows of width L, out_stride apart) the first frame of token i and one past
+// its last, token_scores_dev (same layout, or null) the token's emissions summed in frame order, frame_tokens_dev (n * N
+// rows of width M, frame_stride apart, or null) the token index of every frame, -1 on blank frames.  Float32 max-plus
+// with the tie rule of align.hip: bit-reproducible.  -1 / -inf wherever no path covers an entry; a pair has no path
+// where batch_ctc_score gives -inf.  Every element of every row is written over its width, nothing beyond.
+// Invalid argument before a device is asked for: a null batch, input, scores, starts or ends pointer, negative N, L,
+// stride or blank, row_stride < L, out_stride < L, max_length outside 1 .. 4096; n * N == 0 returns without a device.
+// With the device: not a native linear batch, a frame count outside 0 .. M, blank >= C, frame_stride < M with frame
+// tokens, an output that is not memory of the current device.  The back-pointers (2 bits per state and frame, ceil(max
+// T_b / 16) * (2 max_length + 1) words per pair) come from the stream-ordered pool, at most 256 MiB per launch
+// (GTNX_CTC_TOKEN_ALIGN_SCRATCH_BYTES lowers the cap: a debug switch); beyond it the pairs run in slices, same bits.
+void batch_ctc_token_align(const BatchP& ems, const int* frames, int blank, const int* tokens_dev, int64_t row_stride,
+                           const int* lengths_dev, int N, int L, int max_length, float* scores_dev, int* starts_dev,
+                           int* ends_dev, float* token_scores_dev, int64_t out_stride, int* frame_tokens_dev,
+                           int64_t frame_stride);
+void batch_ctc_token_align_stats(int64_t* calls, int64_t* pairs);  // calls that launched / pairs they aligned
 // items_dev (optional): device memory of the CALLER's that the n result values are written into directly (borrowed: it
 // must outlive the result); a later batch_items_device to the same address copies nothing
 BatchP batch_scalar(ScalarKind k, const BatchP& a, const BatchP& b, void* items_dev = nullptr);

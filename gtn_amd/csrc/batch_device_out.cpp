@@ -717,4 +717,97 @@ void batch_ctc_score_grad(const BatchP& ems, const int* frames, int blank, const
                  max_length, nullptr, weights_dev, grad_dev);
 }
 
+// ---- batched CTC token alignment of device-resident hypotheses (ctc_token_align.hip) ----
+namespace {
+constexpr const char* kCtcTokenAlign = "gtnx_batch_ctc_token_align";
+Counters g_ctc_token_align;  // (calls, pairs)
+// the back-pointer words: a pair that is above the cap by itself runs alone with scratch of its own size
+constexpr int64_t kCtcTokenAlignScratchCap = int64_t(256) << 20;
+}  // namespace
+
+void batch_ctc_token_align_stats(int64_t* calls, int64_t* pairs) { g_ctc_token_align.get(calls, pairs); }
+
+void batch_ctc_token_align(const BatchP& ems, const int* frames, int blank, const int* tokens_dev, int64_t row_stride,
+                           const int* lengths_dev, int N, int L, int max_length, float* scores_dev, int* starts_dev,
+                           int* ends_dev, float* token_scores_dev, int64_t out_stride, int* frame_tokens_dev,
+                           int64_t frame_stride) {
+  GTNX_HOST_T("batch.ctc_token_align");
+  const char* who = kCtcTokenAlign;
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) refuse(who, "null batch");
+  if (!tokens_dev || !lengths_dev) refuse(who, "null input pointer (tokens and lengths are both read)");
+  if (!scores_dev || !starts_dev || !ends_dev) refuse(who, "null output pointer (scores, starts and ends are all written)");
+  if (N < 0 || L < 0) refuse(who, "negative N or L");
+  if (row_stride < 0 || out_stride < 0 || frame_stride < 0) refuse(who, "negative row stride");
+  if (blank < 0) refuse(who, "negative blank");
+  if (row_stride < L) refuse(who, "row_stride is shorter than the rows' width L");
+  if (out_stride < L) refuse(who, "out_stride is shorter than the rows' width L");
+  if (max_length < 1 || max_length > kCtcScoreMaxU) refuse(who, "max_length outside 1 .. 4096");
+  const int n = ems->n;
+  const int64_t pairs = int64_t(n) * N;
+  if (pairs > std::numeric_limits<int>::max()) refuse(who, "n times N does not fit an int");
+  if (pairs <= 0) return;
+  Runtime& rt = Runtime::get();
+  // there is no other route: the alignments are those of the slabs of a native linear batch
+  if (!native_linear(*ems)) refuse(who, "not a native linear batch (gtnx_batch_linear / _rows)");
+  Batch& x = *ems;
+  check_frames(who, frames, n, x.M, x);
+  if (blank >= x.C) refuse(who, "blank is not below the number of labels");
+  if (frame_tokens_dev && frame_stride < x.M) refuse(who, "frame_stride is shorter than the rows of the batch");
+  check_outputs_local(who, {scores_dev, starts_dev, ends_dev, token_scores_dev, frame_tokens_dev});
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  const std::vector<int> fr = resolve_frames(frames, x);
+  int maxT = 0;
+  double frame_sum = 0;
+  for (int t : fr) {
+    maxT = std::max(maxT, t);
+    frame_sum += t;
+  }
+  DevMemP d_frames = upload_vec(fr);
+  const int U = max_length;
+  const int64_t SM = 2 * int64_t(U) + 1;
+  CtcTokenAlignArgs a{};
+  a.em = x.w_dev;
+  a.frames = d_frames->as<int>();
+  a.tokens = tokens_dev;
+  a.lengths = lengths_dev;
+  a.scores = scores_dev;
+  a.starts = starts_dev;
+  a.ends = ends_dev;
+  a.token_scores = token_scores_dev;
+  a.frame_tokens = frame_tokens_dev;
+  a.row_stride = row_stride;
+  a.out_stride = out_stride;
+  a.frame_stride = frame_stride;
+  a.N = N;
+  a.L = L;
+  a.U = U;
+  a.M = x.M;
+  a.C = x.C;
+  a.blank = blank;
+  // algorithmic bytes, by the widths (the lengths are device memory: an upper bound).  Per pair and frame one emission
+  // per state and 2 bits per state out; the walk reads one window of 128 words per 16 frames; the tokens and the length
+  // once, the score and the two span rows out; with token scores one emission per frame at most and the row; with
+  // frame tokens the row.
+  const double per_pair_frames = frame_sum / double(n);  // (the mean: every utterance has N pairs)
+  const double pair_bytes = (4.0 + 0.25) * double(SM) * per_pair_frames + 32.0 * per_pair_frames + 4.0 * std::min(L, U) +
+                            8.0 + 8.0 * L + (token_scores_dev ? 4.0 * per_pair_frames + 4.0 * L : 0.0) +
+                            (frame_tokens_dev ? 4.0 * x.M : 0.0);
+  const int64_t per_pair = (std::max<int64_t>(int64_t(maxT), 1) + 15) / 16 * SM;  // words
+  const int64_t cap = scratch_cap("GTNX_CTC_TOKEN_ALIGN_SCRATCH_BYTES", kCtcTokenAlignScratchCap);
+  const int64_t slice = std::max<int64_t>(1, cap / (4 * per_pair));
+  a.pair_stride = per_pair;
+  for (int64_t p0 = 0; p0 < pairs; p0 += slice) {
+    const int64_t cnt = std::min(slice, pairs - p0);
+    DevMemP words = rt.alloc(size_t(4 * per_pair * cnt));
+    a.bp = words->as<unsigned>();
+    a.pair0 = p0;
+    a.count = int(cnt);
+    GTNX_PROF("ctc_token_align", pair_bytes * double(cnt));
+    launch_ctc_token_align(a, rt.stream());
+    // (the words go back to the stream-ordered pool behind the launch)
+  }
+  g_ctc_token_align.add(1, pairs);
+}
+
 }  // namespace gtnx

@@ -956,6 +956,23 @@ GTNX_API gtnx_status_t gtnx_batch_ctc_score_grad(gtnx_batch_t ems, const int* fr
 GTNX_API gtnx_status_t gtnx_batch_ctc_score_stats(int64_t* calls, int64_t* pairs) {
   return guard([&] { batch_ctc_score_stats(calls, pairs); });
 }
+GTNX_API gtnx_status_t gtnx_batch_ctc_token_align(gtnx_batch_t ems, const int* frames, int blank,
+                                                  const void* tokens_device, int64_t row_stride,
+                                                  const void* lengths_device, int N, int L, int max_length,
+                                                  void* scores_device, void* starts_device, void* ends_device,
+                                                  void* token_scores_device, int64_t out_stride,
+                                                  void* frame_tokens_device, int64_t frame_stride) {
+  return guard([&] {
+    batch_ctc_token_align(BH(ems), frames, blank, static_cast<const int*>(tokens_device), row_stride,
+                          static_cast<const int*>(lengths_device), N, L, max_length, static_cast<float*>(scores_device),
+                          static_cast<int*>(starts_device), static_cast<int*>(ends_device),
+                          static_cast<float*>(token_scores_device), out_stride, static_cast<int*>(frame_tokens_device),
+                          frame_stride);
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_ctc_token_align_stats(int64_t* calls, int64_t* pairs) {
+  return guard([&] { batch_ctc_token_align_stats(calls, pairs); });
+}
 GTNX_API gtnx_status_t gtnx_batch_linear_shape(gtnx_batch_t ems, int* rows, int* labels) {
   return guard([&] {
     const BatchP& b = BH(ems);

@@ -905,6 +905,28 @@ struct CtcScoreArgs {
 void ctc_score_config(int U, int* width, int* per_lane);  // the workgroup's width and the states a lane owns
 void launch_ctc_score_forward(const CtcScoreArgs& a, hipStream_t st);
 void launch_ctc_score_backward(const CtcScoreArgs& a, hipStream_t st);
+// ctc_token_align.hip: the best alignment (max-plus, the arithmetic and the tie rule of align.hip) of the pairs pair0 ..
+// pair0 + count - 1 of ctc_score.hip's hypothesis form (the contract: DESIGN section 24).  One workgroup per pair, width
+// and states per lane from ctc_score_config(U); row p of every output is written over its whole width: scores[p] the
+// path's score, starts / ends [p * out_stride + i] the first frame of token i and one past its last, token_scores (or
+// null) the token's emissions summed in frame order, frame_tokens[p * frame_stride + t] (or null) the token index of
+// frame t; -1 / -inf where no path covers an entry.  bp: the back-pointers of the launch, 2 bits per state and frame,
+// word (t / 16) * (2 U + 1) + s of the pair_stride words of workgroup blockIdx.x.
+struct CtcTokenAlignArgs {
+  const GTNX_G float* em;      // [n][M][C]
+  const GTNX_G int* frames;    // [n]
+  const GTNX_G int* tokens;    // pair p's row at tokens + p * row_stride
+  const GTNX_G int* lengths;   // [pairs]
+  GTNX_G float* scores;        // [pairs]
+  GTNX_G int* starts;          // pair p's row at starts + p * out_stride, width L
+  GTNX_G int* ends;            // the same
+  GTNX_G float* token_scores;  // the same, or null
+  GTNX_G int* frame_tokens;    // pair p's row at frame_tokens + p * frame_stride, width M, or null
+  GTNX_G unsigned* bp;         // [count][pair_stride]
+  int64_t row_stride, out_stride, frame_stride, pair0, pair_stride;
+  int count, N, L, U, M, C, blank;
+};
+void launch_ctc_token_align(const CtcTokenAlignArgs& a, hipStream_t st);
 // materialise a KIND_LINEAR graph's arc arrays
 void launch_linear_materialize(int M, int C, int* src, int* dst, int* il, int* ol, hipStream_t st);
 

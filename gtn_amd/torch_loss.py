@@ -1,5 +1,5 @@
 """PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
-`asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_beam_decode`, `edit_distance` and `ctc_score`.
+`asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_beam_decode`, `edit_distance`, `ctc_score` and `ctc_token_align`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -35,6 +35,7 @@ _ARGTYPES = {
     "gtn_edit_distance_n": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "gtn_ctc_score_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P],
     "gtn_ctc_score_grad_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P],
+    "gtn_ctc_token_align_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
 }
 
 
@@ -756,3 +757,82 @@ def ctc_score(log_probs, tokens, lengths, blank=0, input_lengths=None, max_lengt
     ln = lengths.detach().to(torch.int32).reshape(B, N).contiguous()  # (int64 lengths are converted on the device)
     out = _CTCScore.apply(log_probs, tok, ln, blank, frames, max_length)
     return out.reshape(B) if flat else out
+
+
+def ctc_token_align(log_probs, tokens, lengths, blank=0, input_lengths=None, max_length=None, return_token_scores=False,
+                    return_frames=False):
+    """When each token of each device-resident hypothesis was spoken, and how well the frames support it: the best
+    alignment (the reference's viterbiPath over ctcGraph(tokens[b, k, :len], blank) o log_probs[b, :T_b]) of all B * N
+    hypotheses in one call against the B shared slabs -- no download of the tokens, no wait, no host loop over frames.
+    It takes the tensors where `ctc_beam_decode` left them.
+    log_probs, tokens ([B, N, L] or [B, L]), lengths (int32 or int64, clamped to 0 .. L on the device), blank,
+    input_lengths and max_length (1 .. 4096, default min(L, T, 4096)) are those of `ctc_score`.
+    Returns (scores, starts, ends[, token_scores][, frame_tokens]) on log_probs.device:
+      scores        float32 [B, N] (or [B]): the score of the best path, -inf without one;
+      starts, ends  int32 [B, N, L] (or [B, L]): the first frame of token i and one past its last, so ends - starts is
+                    its duration (blank frames belong to no token); -1 for i >= len and for a pair without a path;
+      token_scores  float32, same shape (return_token_scores): the sum of log_probs[b, t, token] over the token's
+                    frames; -inf where starts is -1.  With normalised log_probs exp(token_scores / (ends - starts)) is
+                    the usual per-token confidence; nothing is subtracted here;
+      frame_tokens  int32 [B, N, T] (or [B, T]) (return_frames): the token index of every frame, -1 on blank frames and
+                    from T_b on -- the `tokens` plane of `ctc_forced_align`.
+    A pair has no path where `ctc_score` gives -inf: length + repeats > T_b, every path crosses a -inf emission, the
+    length is above max_length, a token inside the length is outside 0 .. C - 1, T_b == 0.  A beam slot without a
+    hypothesis (length 0) aligns as the empty sequence: a finite score and rows of -1.  Float32 max-plus arithmetic with
+    exact ties decided as `ctc_forced_align` decides them: the same bits every time.  No autograd.  Runs on the caller's
+    stream."""
+    who = "ctc_token_align"
+    if not (torch.is_tensor(log_probs) and log_probs.dim() == 3 and log_probs.dtype == torch.float32):
+        raise ValueError(f"{who}: log_probs must be a float32 tensor [B, T, C]")
+    B, T, C_ = log_probs.shape
+    if not (torch.is_tensor(tokens) and tokens.dtype == torch.int32 and tokens.dim() in (2, 3) and tokens.shape[0] == B):
+        raise ValueError(f"{who}: tokens must be an int32 tensor [B, N, L] or [B, L] for a batch of {B}")
+    flat = tokens.dim() == 2
+    N, L = (1, tokens.shape[1]) if flat else tokens.shape[1:]
+    shape = (B,) if flat else (B, N)
+    if not (torch.is_tensor(lengths) and lengths.dtype in (torch.int32, torch.int64) and tuple(lengths.shape) == shape):
+        raise ValueError(f"{who}: lengths must be an int32 or int64 tensor {list(shape)}")
+    blank = int(blank)
+    if not 0 <= blank < C_:
+        raise ValueError(f"{who}: blank must be one of the {C_} labels")
+    max_length = max(1, min(L, T, 4096)) if max_length is None else int(max_length)
+    if not 1 <= max_length <= 4096:
+        raise ValueError(f"{who}: max_length outside 1 .. 4096")
+    frames = None if input_lengths is None else _frame_counts(who, input_lengths, B, T, 0)
+    for t, what in ((log_probs, "log_probs"), (tokens, "tokens"), (lengths, "lengths")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {what} must be a CUDA tensor (the alignments are computed on the device)")
+        if t.device != log_probs.device:
+            raise ValueError(f"{who}: all tensors must be on one device")
+    x = log_probs.detach().contiguous()
+    tok = tokens.detach().reshape(B, N, L).contiguous()
+    ln = lengths.detach().to(torch.int32).reshape(B, N).contiguous()  # (int64 lengths are converted on the device)
+    stream = _engine_stream(x.device)
+    # (rows without an element are never written, but they need an address: a width of at least 1 behind the views)
+    W, F = max(L, 1), max(T, 1)
+    scores = torch.empty(B, N, dtype=torch.float32, device=x.device)
+    starts = torch.empty(B, N, W, dtype=torch.int32, device=x.device)
+    ends = torch.empty(B, N, W, dtype=torch.int32, device=x.device)
+    tsc = torch.empty(B, N, W, dtype=torch.float32, device=x.device) if return_token_scores else None
+    ftk = torch.empty(B, N, F, dtype=torch.int32, device=x.device) if return_frames else None
+    if tok.numel() == 0:
+        tok = tok.new_empty(B, N, 1)
+    if B * N == 0:
+        pass  # (no pair: nothing to launch, and an empty tensor has no address to hand over)
+    elif L == W and T == F and _has_native(who, "gtn_ctc_token_align_n", python_route=True):
+        _call("gtn_ctc_token_align_n", x.data_ptr(), B, T, C_, blank, _host_ptr(frames), tok.data_ptr(), ln.data_ptr(), N,
+              L, max_length, scores.data_ptr(), starts.data_ptr(), ends.data_ptr(), _ptr(tsc), _ptr(ftk))
+    else:
+        ems = gtn.Batch.linear(B, T, C_, x, calc_grad=False, borrow=True)
+        ems.ctc_token_align(tok.data_ptr(), ln.data_ptr(), scores.data_ptr(), starts.data_ptr(), ends.data_ptr(),
+                            _ptr(tsc), _ptr(ftk), frames, blank, max_length, N=N, L=L, row_stride=W, out_stride=W,
+                            frame_stride=F)
+    _engine_done(stream)
+    out = [scores, starts[:, :, :L], ends[:, :, :L]]
+    if return_token_scores:
+        out.append(tsc[:, :, :L])
+    if return_frames:
+        out.append(ftk[:, :, :T])
+    if flat:
+        out = [o.reshape(B, *o.shape[2:]) for o in out]
+    return tuple(out)

@@ -245,6 +245,21 @@ inline void ctcScoreGrad(const Batch& ems, const int* tokensDevice, int64_t rowS
   detail::check(gtnx_batch_ctc_score_grad(ems.handle(), frames, blank, tokensDevice, rowStride, lengthsDevice, N, L,
                                           maxLength, weightsDevice, gradDevice));
 }
+/** The best alignment of all n * N device-resident hypotheses (the form of ctcScore) under the slabs of a Batch::linear,
+ *  results left on the device: scoresDevice [n][N] the Viterbi score (-inf without a path); startsDevice / endsDevice
+ *  int32 n * N rows of width L, outStride (>= L) apart: the first frame of token i and one past its last, -1 for i >= len
+ *  and without a path; tokenScoresDevice (same layout, or null) the token's emissions summed in frame order;
+ *  frameTokensDevice (n * N rows of width M, frameStride >= M apart, or null) the token index of every frame, -1 on
+ *  blank frames and from T_b on.  Float32 max-plus with the tie rule of viterbiAlign: reproducible bit for bit.  No copy
+ *  back, no wait -- gtnx_batch_ctc_token_align */
+inline void ctcTokenAlign(const Batch& ems, const int* tokensDevice, int64_t rowStride, const int* lengthsDevice, int N,
+                          int L, int maxLength, float* scoresDevice, int* startsDevice, int* endsDevice,
+                          float* tokenScoresDevice, int64_t outStride, int* frameTokensDevice = nullptr,
+                          int64_t frameStride = 0, int blank = 0, const int* frames = nullptr) {
+  detail::check(gtnx_batch_ctc_token_align(ems.handle(), frames, blank, tokensDevice, rowStride, lengthsDevice, N, L,
+                                           maxLength, scoresDevice, startsDevice, endsDevice, tokenScoresDevice,
+                                           outStride, frameTokensDevice, frameStride));
+}
 inline void backward(const Batch& a, bool retainGraph = false) { detail::check(gtnx_batch_backward(a.handle(), retainGraph)); }
 } // namespace batched
 

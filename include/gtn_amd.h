@@ -492,6 +492,49 @@ gtnx_status_t gtnx_batch_ctc_score_grad(gtnx_batch_t ems, const int* frames, int
                                         const void* weights_device, void* grad_device);
 /* calls of either kind that have launched so far (process-wide) / pairs they took */
 gtnx_status_t gtnx_batch_ctc_score_stats(int64_t* calls, int64_t* pairs);
+/* The best alignment of those hypotheses: WHEN each token was spoken and how well the frames support it, for all n * N
+ * pairs in one call, results left on the device.  The inputs are those of gtnx_batch_ctc_score with the same meaning:
+ * pair (b, k) is y = tokens[b][k][0 .. len), len = clamp(lengths[b][k], 0, L), under emissions_b[0 .. T_b).  The states
+ * are those of ctcGraph(y, blank): s = 0 .. 2 len, even states carry `blank`, state 2 i + 1 carries y[i]; a frame enters
+ * s from s and s - 1, and from s - 2 for an odd s > 1 whose token differs from the one before; paths start in state 0
+ * before frame 0 and end in state 2 len or 2 len - 1 behind frame T_b - 1.  A token equal to `blank` is a label like
+ * any other.  Float32 max-plus: a candidate is alpha[source] + e(t, label(s)), one addition; the new value is the exact
+ * maximum.  Of the candidates that reach it the one whose source has the smallest rank wins, the rank order of the
+ * states being, with U = len, S = 2 U + 1 and p leading strict ascents y[0] < .. < y[p],
+ *   0 | (2i, 2i-1) for i = 1..p | S-1 | for i = U-1 down to p+1: (2i, 2i+1) if y[i] != y[i-1] else (2i+1, 2i) | 2p+1
+ * and of two equal end states the smaller wins: the choice of viterbiPath (shortest.cpp:190-272) whenever every token
+ * is above `blank`, and that of gtnx_batch_viterbi_align.  Every output is reproducible bit for bit.
+ *   scores_device       float32 [n][N]: the path's score, -inf without a path
+ *   starts_device,      int32, n * N rows of width L, out_stride (>= L) elements apart: the first frame of token i and
+ *   ends_device         one past its last frame (blank frames belong to no token); -1 for i >= len and in every entry
+ *                       of a pair without a path
+ *   token_scores_device float32, same layout, or null: the sum of e(t, y[i]) over the token's frames, added in
+ *                       ascending frame order from the first frame's value; -inf where starts is -1.  With normalised
+ *                       emissions exp(token_scores / (ends - starts)) is the usual confidence; nothing is subtracted
+ *   frame_tokens_device int32, n * N rows of width M, frame_stride (>= M) apart, or null: the token index of every
+ *                       frame, -1 on blank frames, from T_b on and in every entry of a pair without a path
+ * Every element of every row is written over the widths L and M, nothing beyond them.  A pair has no path where
+ * gtnx_batch_ctc_score gives -inf: len + repeats > T_b, every path crosses a -inf emission, len > max_length, a token
+ * inside the length outside 0 .. C - 1 (checked before it becomes an address), T_b == 0.  A beam slot without a
+ * hypothesis (length 0) aligns as the empty sequence: a finite score, rows of -1.  Elements at or past a length and
+ * emission rows at or past T_b are never read; the inputs are only read.  NaN emissions give unspecified values and no
+ * access outside the pair's own rows.
+ * GTNX_INVALID_ARGUMENT before a device is asked for: a null batch, tokens, lengths, scores, starts or ends pointer,
+ * negative N, L, stride or blank, row_stride < L, out_stride < L, max_length outside 1 .. 4096.  n * N == 0 returns
+ * without touching a device.  With the device: not a gtnx_batch_linear / _rows batch, a frame count outside 0 .. M,
+ * blank >= C, frame_stride < M with frame tokens, an output the engine's current device may not write.  A refused call
+ * writes nothing.
+ * One workgroup per pair (ctc_token_align.hip).  The back-pointers take 2 bits per state and frame in scratch from the
+ * stream-ordered pool, ceil(max_b T_b / 16) * (2 max_length + 1) words per pair, at most 256 MiB per launch; beyond
+ * that the pairs run in slices with the same bits (GTNX_CTC_TOKEN_ALIGN_SCRATCH_BYTES, read per call, lowers the cap: a
+ * debug switch for tests); a single pair above the cap runs alone.  Nothing is copied back, the call does not wait. */
+gtnx_status_t gtnx_batch_ctc_token_align(gtnx_batch_t ems, const int* frames, int blank, const void* tokens_device,
+                                         int64_t row_stride, const void* lengths_device, int N, int L, int max_length,
+                                         void* scores_device, void* starts_device, void* ends_device,
+                                         void* token_scores_device, int64_t out_stride, void* frame_tokens_device,
+                                         int64_t frame_stride);
+/* calls that have launched so far (process-wide) / pairs they aligned */
+gtnx_status_t gtnx_batch_ctc_token_align_stats(int64_t* calls, int64_t* pairs);
 /* rows M and labels C of the slabs of a gtnx_batch_linear / _rows batch; -1, -1 for any other batch */
 gtnx_status_t gtnx_batch_linear_shape(gtnx_batch_t ems, int* rows, int* labels);
 gtnx_status_t gtnx_batch_backward(gtnx_batch_t a, int retain_graph);                  /* autograd.cpp:17-67 */
