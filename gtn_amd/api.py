@@ -1025,6 +1025,79 @@ def make_api(lib):
                                                  _opt_ptr(starts_out), _opt_ptr(ends_out), _opt_ptr(token_scores_out),
                                                  int(out_stride), _opt_ptr(frame_tokens_out), int(frame_stride)))
 
+        def _asg_score_table(self, who, table):
+            """the [C + C * C] table of an asg_score call, checked where it is a tensor"""
+            if table is not None and hasattr(table, "data_ptr"):
+                if (str(table.dtype) != "torch.float32" or table.dim() != 1 or not table.is_contiguous()
+                        or not table.is_cuda):
+                    raise ValueError(f"{who}: table must be a float32 contiguous CUDA tensor [C + C * C]")
+                m, c = C.c_int(-1), C.c_int(-1)
+                check(lib.gtnx_batch_linear_shape(self._h, C.byref(m), C.byref(c)))
+                if c.value >= 0 and table.numel() != c.value + c.value * c.value:
+                    raise ValueError(f"{who}: table has {table.numel()} entries, {c.value} labels need "
+                                     f"{c.value + c.value * c.value}")
+            return table
+
+        def asg_score(self, table, tokens, lengths, scores_out, frames=None, max_length=None, N=None, L=None,
+                      row_stride=None):
+            """The ASG force-align term of all B * N device-resident hypotheses under the slabs of a Batch.linear, results
+            left on the device (gtnx_batch_asg_score; DESIGN section 25 holds the contract): scores_out[b, k] =
+            forwardScore(emissions_b[:T_b] o (forceAlign(tokens[b, k, :len]) o transitions)) with len = clamp(lengths[b, k],
+            0, L), log semiring, nothing subtracted.  `table`: float32 CUDA tensor [C + C * C] or a device address -- entry
+            y is start[y], entry C + i * C + j is transitions[i, j], label j followed by label i
+            (`torch_loss._asg_weights(start, transitions)`, the table `ctc_beam_decode(lm=...)` takes); `tokens`, `lengths`,
+            `frames`, `max_length`, N, L and row_stride are those of `ctc_score` (tokens are labels only: there is no
+            blank, equal neighbours are legal).  -inf, never NaN: len == 0, T_b < len, len > max_length, a token inside the
+            length outside 0 .. C - 1, no alignment above -inf.  One launch, no copy back and no wait."""
+            fr, tok, stride, ln, N, L, U = self._ctc_score_args("asg_score", tokens, lengths, frames, N, L, row_stride,
+                                                                max_length)
+            table = self._asg_score_table("asg_score", table)
+            if scores_out is not None and hasattr(scores_out, "data_ptr"):
+                if (str(scores_out.dtype) != "torch.float32" or not scores_out.is_contiguous()
+                        or scores_out.numel() != len(self) * N):
+                    raise ValueError("asg_score: scores_out must be a float32 contiguous tensor [B, N]")
+                if len(self) * N == 0:
+                    return
+            check(lib.gtnx_batch_asg_score(self._h, fr.ctypes.data if fr is not None else None, _opt_ptr(table),
+                                           _opt_ptr(tok), stride, _opt_ptr(ln), N, L, U, _opt_ptr(scores_out)))
+
+        def asg_score_grad(self, table, tokens, lengths, weights, grad_out=None, grad_table_out=None, frames=None,
+                           max_length=None, N=None, L=None, row_stride=None):
+            """The gradients of the scores of `asg_score` under `weights` (float32 [B, N] on the device), in one stateless
+            call (gtnx_batch_asg_score_grad): `grad_out` (float32 [B, M, C] or None) = sum over k of weights[b, k] * d
+            score[b, k] / d emissions[b], every element written (zeros where nothing lands, rows from T_b on included);
+            `grad_table_out` (float32 [C + C * C] or None) = sum over all pairs of weights * d score / d table, every
+            entry written; not both None.  A call without pairs (B * N == 0) writes nothing.  Pairs with a -inf score or a
+            weight of exactly 0 add nothing.  The alpha rows are recomputed into pooled scratch (sliced beyond 256 MiB,
+            same bits); the sums are taken in a fixed order without atomics, so both results have the same bits run to
+            run."""
+            fr, tok, stride, ln, N, L, U = self._ctc_score_args("asg_score_grad", tokens, lengths, frames, N, L,
+                                                                row_stride, max_length)
+            table = self._asg_score_table("asg_score_grad", table)
+            if grad_out is None and grad_table_out is None:
+                raise ValueError("asg_score_grad: neither grad_out nor grad_table_out given")
+            for o, what in ((weights, "weights must be a float32 contiguous tensor [B, N]"),
+                            (grad_out, "grad_out must be a float32 contiguous tensor [B, M, C]"),
+                            (grad_table_out, "grad_table_out must be a float32 contiguous tensor [C + C * C]")):
+                if o is not None and hasattr(o, "data_ptr"):
+                    if str(o.dtype) != "torch.float32" or not o.is_contiguous():
+                        raise ValueError(f"asg_score_grad: {what}")
+            if weights is not None and hasattr(weights, "data_ptr") and weights.numel() != len(self) * N:
+                raise ValueError("asg_score_grad: weights must be a float32 contiguous tensor [B, N]")
+            m, c = C.c_int(-1), C.c_int(-1)
+            check(lib.gtnx_batch_linear_shape(self._h, C.byref(m), C.byref(c)))
+            if grad_out is not None and hasattr(grad_out, "data_ptr"):
+                if m.value >= 0 and grad_out.numel() != len(self) * m.value * c.value:
+                    raise ValueError("asg_score_grad: grad_out must be a float32 contiguous tensor [B, M, C]")
+            if grad_table_out is not None and hasattr(grad_table_out, "data_ptr"):
+                if c.value >= 0 and grad_table_out.numel() != c.value + c.value * c.value:
+                    raise ValueError("asg_score_grad: grad_table_out must be a float32 contiguous tensor [C + C * C]")
+            if len(self) * N == 0 and any(hasattr(o, "data_ptr") for o in (grad_out, grad_table_out)):
+                return
+            check(lib.gtnx_batch_asg_score_grad(self._h, fr.ctypes.data if fr is not None else None, _opt_ptr(table),
+                                                _opt_ptr(tok), stride, _opt_ptr(ln), N, L, U, _opt_ptr(weights),
+                                                _opt_ptr(grad_out), _opt_ptr(grad_table_out)))
+
     ns.Batch = Batch
 
     def _batch_fn(cfn, *args):
@@ -1168,6 +1241,11 @@ def make_api(lib):
         (include/gtn_amd.h: gtnx_batch_ctc_token_align_stats)"""
         return _stats2(lib.gtnx_batch_ctc_token_align_stats)
 
+    def debug_asg_score_stats():
+        """(calls, pairs): calls of Batch.asg_score / Batch.asg_score_grad that have launched so far and the pairs they
+        took (include/gtn_amd.h: gtnx_batch_asg_score_stats)"""
+        return _stats2(lib.gtnx_batch_asg_score_stats)
+
     def debug_edit_distance_stats():
         """(calls, pairs): calls of edit_distance that have launched so far and the pairs they computed
         (include/gtn_amd.h: gtnx_batch_edit_distance_stats)"""
@@ -1257,6 +1335,7 @@ def make_api(lib):
     ns.debug_edit_distance_stats = debug_edit_distance_stats
     ns.debug_ctc_score_stats = debug_ctc_score_stats
     ns.debug_ctc_token_align_stats = debug_ctc_token_align_stats
+    ns.debug_asg_score_stats = debug_asg_score_stats
     ns.edit_distance = edit_distance
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties

@@ -173,5 +173,47 @@ inline void asgDecodeBatch(
                          static_cast<int*>(collapsedDev), static_cast<int*>(lengthsDev));
 }
 
+/** The force-align scores of B * N device-resident hypotheses under the B emission slabs, and (with weightsDev and at
+ *  least one of gradEmDev / gradTableDev) their gradients under those weights: `emissions` device float32 [B][T][N_],
+ *  read in place; `tableDev` device float32 [N_ + N_ * N_] in the arc order of asgTransitions (start scores, then
+ *  arc N_ + i * N_ + j = j -> i); `tokensDev` device int32 [B][N][L] (dense rows); `lengthsDev` device int32 [B][N];
+ *  `frames` host [B] or null; `scoresDev` device float32 [B][N] or null; `weightsDev` device float32 [B][N];
+ *  `gradEmDev` device float32 [B][T][N_] or null; `gradTableDev` device float32 [N_ + N_ * N_] or null.
+ *  gtnx_batch_asg_score / _grad have the contract.  Nothing is copied back. */
+inline void asgScoreBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int N_,
+    const void* tableDev,
+    const int* frames,
+    const void* tokensDev,
+    const void* lengthsDev,
+    int N,
+    int L,
+    int maxLength,
+    void* scoresDev,
+    const void* weightsDev = nullptr,
+    void* gradEmDev = nullptr,
+    void* gradTableDev = nullptr) {
+  const bool wantGrad = gradEmDev || gradTableDev;
+  if ((weightsDev != nullptr) != wantGrad) {
+    throw std::invalid_argument("asgScoreBatch: weights and a gradient come together");
+  }
+  if (!scoresDev && !wantGrad) {
+    throw std::invalid_argument("asgScoreBatch: neither scores nor a gradient asked for");
+  }
+  Batch ems = Batch::linear(B, T, N_, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  if (scoresDev) {
+    batched::asgScore(ems, static_cast<const float*>(tableDev), static_cast<const int*>(tokensDev), L,
+                      static_cast<const int*>(lengthsDev), N, L, maxLength, static_cast<float*>(scoresDev), frames);
+  }
+  if (wantGrad) {
+    batched::asgScoreGrad(ems, static_cast<const float*>(tableDev), static_cast<const int*>(tokensDev), L,
+                          static_cast<const int*>(lengthsDev), N, L, maxLength, static_cast<const float*>(weightsDev),
+                          static_cast<float*>(gradEmDev), static_cast<float*>(gradTableDev), frames);
+  }
+}
+
 } // namespace criteria
 } // namespace gtn

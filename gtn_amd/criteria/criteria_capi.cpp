@@ -230,3 +230,26 @@ GTN_EXPORT int gtn_asg_decode_n(const void* emissions, int B, int T, int N, cons
     gtn::criteria::asgDecodeBatch(emissions, B, T, N, trans, frames, labels, scores, collapsed, lengths);
   });
 }
+
+// ASG force-align scores of B * N device-resident hypotheses.  emissions: DEVICE float32 [B][T][C]; table: DEVICE float32
+// [C + C*C] as for gtn_asg_loss_n; frames: HOST int [B] or null; tokens: DEVICE int32 [B][N][L]; lengths: DEVICE int32
+// [B][N]; scores: DEVICE float32 [B][N].
+GTN_EXPORT int gtn_asg_score_n(const void* emissions, int B, int T, int C, const void* table, const int* frames,
+                               const void* tokens, const void* lengths, int N, int L, int max_length, void* scores) {
+  return guarded([&] {
+    if (!scores) throw std::invalid_argument("gtn_asg_score_n: null scores");
+    gtn::criteria::asgScoreBatch(emissions, B, T, C, table, frames, tokens, lengths, N, L, max_length, scores);
+  });
+}
+
+// ... and their gradients under weights: DEVICE float32 [B][N]: grad_em (DEVICE float32 [B][T][C], every element
+// written) and grad_table (DEVICE float32 [C + C*C], every entry written); either may be null, not both.
+GTN_EXPORT int gtn_asg_score_grad_n(const void* emissions, int B, int T, int C, const void* table, const int* frames,
+                                    const void* tokens, const void* lengths, int N, int L, int max_length,
+                                    const void* weights, void* grad_em, void* grad_table) {
+  return guarded([&] {
+    if (!weights || (!grad_em && !grad_table)) throw std::invalid_argument("gtn_asg_score_grad_n: null weights or no gradient");
+    gtn::criteria::asgScoreBatch(emissions, B, T, C, table, frames, tokens, lengths, N, L, max_length, nullptr, weights,
+                                 grad_em, grad_table);
+  });
+}

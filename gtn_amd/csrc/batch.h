@@ -253,6 +253,32 @@ void batch_ctc_token_align(const BatchP& ems, const int* frames, int blank, cons
                            int* ends_dev, float* token_scores_dev, int64_t out_stride, int* frame_tokens_dev,
                            int64_t frame_stride);
 void batch_ctc_token_align_stats(int64_t* calls, int64_t* pairs);  // calls that launched / pairs they aligned
+// The ASG force-align term of all n * N device-resident hypotheses under the n emission slabs of a native linear batch,
+// score[b * N + k] = forwardScore(emissions_b[:T_b] o (forceAlign(tokens[b, k, :len]) o transitions)) with len =
+// clamp(lengths[b, k], 0, L), log semiring, nothing subtracted, results on the device (DESIGN section 25 holds the
+// contract).  tokens_dev / lengths_dev / frames: as in batch_ctc_score (labels only: there is no blank, equal
+// neighbours are legal).  table_dev: float32 [C + C * C], DEVICE memory of the current device (the kernel gathers from
+// it), in the arc order of asgTransitions: entry y = start[y], entry C + i * C + j = transitions[i, j], label j
+// followed by i.  -inf (never NaN): len == 0, T_b < len, len > max_length, a token inside the length outside
+// 0 .. C - 1, every alignment crosses a -inf emission or table entry.
+// Invalid argument before a device is asked for: a null pointer, negative N, L or stride, row_stride < L, max_length
+// outside 1 .. 4096; n * N == 0 returns without a device.  With the device: not a native linear batch, a frame count
+// outside 0 .. M, C > 16384, a table that is not device memory of the current device, an output that is not memory of
+// the current device.  One launch, no scratch.
+void batch_asg_score(const BatchP& ems, const int* frames, const float* table_dev, const int* tokens_dev,
+                     int64_t row_stride, const int* lengths_dev, int N, int L, int max_length, float* scores_dev);
+// grad_em_dev (or null) [b][t][c] = sum over k of weights_dev[b * N + k] * d score[b, k] / d emissions[b][t][c], every
+// element of [n][M][C] written (zeros where nothing lands, pad rows included); grad_table_dev (or null) [C + C * C] =
+// sum over all pairs of weights * d score / d table, every entry written; not both null.  A pair whose score is -inf
+// or whose weight is exactly 0 adds nothing.  The alpha rows are recomputed into scratch from the stream-ordered pool
+// (max T_b * max_length floats per pair), at most 256 MiB per slice (GTNX_ASG_SCORE_SCRATCH_BYTES lowers the cap:
+// a debug switch); beyond it the pairs run in slices with the same bits.  With a table gradient the per-position
+// occupancy sums (2 * min(L, max_length) floats per pair) stay in scratch until one reduction launch behind the last
+// slice.  No floating-point atomics: bit-repeatable.
+void batch_asg_score_grad(const BatchP& ems, const int* frames, const float* table_dev, const int* tokens_dev,
+                          int64_t row_stride, const int* lengths_dev, int N, int L, int max_length,
+                          const float* weights_dev, float* grad_em_dev, float* grad_table_dev);
+void batch_asg_score_stats(int64_t* calls, int64_t* pairs);  // calls that launched (either kind) / pairs they took
 // items_dev (optional): device memory of the CALLER's that the n result values are written into directly (borrowed: it
 // must outlive the result); a later batch_items_device to the same address copies nothing
 BatchP batch_scalar(ScalarKind k, const BatchP& a, const BatchP& b, void* items_dev = nullptr);

@@ -1,7 +1,7 @@
 // batch_device_out.cpp -- the batch entry points that leave their results in the caller's device memory (declared and
 // specified in batch.h): forced alignment, decode against one shared graph, best path of the chains plus the CTC
-// collapse, CTC prefix beam search, edit distance, CTC score and its gradient.  The kernels differ; the host side around
-// them is the helpers below.
+// collapse, CTC prefix beam search, edit distance, CTC score and its gradient, CTC token alignment, ASG score and its
+// gradients.  The kernels differ; the host side around them is the helpers below.
 //
 // Recipe for the next entry point, in this order:
 //   1. GTNX_HOST_T("batch.<name>"), then every check the arguments alone decide, each message "[gtnx_batch_<name>] ...":
@@ -808,6 +808,148 @@ void batch_ctc_token_align(const BatchP& ems, const int* frames, int blank, cons
     // (the words go back to the stream-ordered pool behind the launch)
   }
   g_ctc_token_align.add(1, pairs);
+}
+
+// ---- batched ASG score of device-resident hypotheses, and its gradients (asg_score.hip) ----
+namespace {
+Counters g_asg_score;  // (calls, pairs)
+// the alpha rows of a gradient call: a pair that is above the cap by itself runs alone with scratch of its own size
+constexpr int64_t kAsgScoreScratchCap = int64_t(256) << 20;
+
+// both entry points: scores_dev for the score; weights_dev and grad_em_dev / grad_table_dev for the gradients
+void asg_score_impl(const char* who, const BatchP& ems, const int* frames, const float* table_dev,
+                    const int* tokens_dev, int64_t row_stride, const int* lengths_dev, int N, int L, int max_length,
+                    float* scores_dev, const float* weights_dev, float* grad_em_dev, float* grad_table_dev) {
+  const bool want_grad = scores_dev == nullptr;
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) refuse(who, "null batch");
+  if (!table_dev) refuse(who, "null table pointer");
+  if (!tokens_dev || !lengths_dev) refuse(who, "null input pointer (tokens and lengths are both read)");
+  if (want_grad && !weights_dev) refuse(who, "null weights pointer");
+  if (want_grad && !grad_em_dev && !grad_table_dev) refuse(who, "neither gradient asked for (both pointers null)");
+  if (N < 0 || L < 0) refuse(who, "negative N or L");
+  if (row_stride < 0) refuse(who, "negative row stride");
+  if (row_stride < L) refuse(who, "row_stride is shorter than the rows' width L");
+  if (max_length < 1 || max_length > kAsgScoreMaxU) refuse(who, "max_length outside 1 .. 4096");
+  const int n = ems->n;
+  const int64_t pairs = int64_t(n) * N;
+  if (pairs > std::numeric_limits<int>::max()) refuse(who, "n times N does not fit an int");
+  if (pairs <= 0) return;
+  Runtime& rt = Runtime::get();
+  // there is no other route: the scores are those of the slabs of a native linear batch
+  if (!native_linear(*ems)) refuse(who, "not a native linear batch (gtnx_batch_linear / _rows)");
+  Batch& x = *ems;
+  check_frames(who, frames, n, x.M, x);
+  // (the table kernel keeps one row of C floats in LDS)
+  if (x.C > kAsgScoreMaxC) refuse(who, "more than 16384 labels");
+  // (the kernel gathers from it: host memory is refused too, with one GPU as well)
+  if (!ptr_device_memory_of(table_dev, rt.device())) refuse(who, "the table is not memory of the engine's current device");
+  check_outputs_local(who, {scores_dev, grad_em_dev, grad_table_dev});
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  const std::vector<int> fr = resolve_frames(frames, x);
+  int maxT = 0;
+  double frame_sum = 0;
+  for (int t : fr) {
+    maxT = std::max(maxT, t);
+    frame_sum += t;
+  }
+  DevMemP d_frames = upload_vec(fr);
+  const int U = max_length;
+  AsgScoreArgs a{};
+  a.em = x.w_dev;
+  a.frames = d_frames->as<int>();
+  a.tokens = tokens_dev;
+  a.lengths = lengths_dev;
+  a.table = table_dev;
+  a.weights = weights_dev;
+  a.grad = grad_em_dev;
+  a.grad_table = grad_table_dev;
+  a.row_stride = row_stride;
+  a.N = N;
+  a.L = L;
+  a.U = U;
+  a.M = x.M;
+  a.C = x.C;
+  a.pairs = int(pairs);
+  a.occ_half = std::max(std::min(L, U), 1);
+  // algorithmic bytes, by the widths (the lengths are device memory: an upper bound).  forward: per pair and frame one
+  // emission per position, the tokens, two table entries per position and the length once, the score out.  With the
+  // rows kept: every alpha out as well.  backward: the alphas (twice: a position and the one before it) and the
+  // emissions back in, with an emission gradient the occupancies out in the alphas' place; the occupancy sums out.
+  // scatter: the occupancies back in, one load and one store of a gradient element per position and frame at most,
+  // and the utterance's slab zeroed once.  table: every workgroup streams the tokens, the sums come back in once, the
+  // table goes out.
+  const double per_pair_frames = frame_sum / double(n);  // (the mean: every utterance has N pairs)
+  const double width = std::min(L, U);
+  const double fwd_pair = 4.0 * double(U) * per_pair_frames + 12.0 * width + 8.0;
+  if (!want_grad) {
+    a.scores = scores_dev;
+    a.pair0 = 0;
+    a.score0 = 0;
+    a.count = int(pairs);
+    GTNX_PROF("asg_score", fwd_pair * double(pairs));
+    launch_asg_score_forward(a, rt.stream());
+  } else {
+    const int64_t per_pair = std::max<int64_t>(int64_t(maxT), 1) * U;  // floats
+    const int64_t cap = scratch_cap("GTNX_ASG_SCORE_SCRATCH_BYTES", kAsgScoreScratchCap);
+    const int64_t slice = std::max<int64_t>(1, cap / (4 * per_pair));
+    // (the scores and the occupancy sums outlive the slices: the table launch reads them)
+    DevMemP sc = rt.alloc(size_t(4 * pairs));
+    DevMemP occ;
+    if (grad_table_dev) {
+      occ = rt.alloc(size_t(8) * size_t(a.occ_half) * size_t(pairs));
+      a.occ = occ->as<float>();
+    }
+    a.scores = sc->as<float>();
+    a.score0 = 0;
+    a.pair_stride = per_pair;
+    for (int64_t p0 = 0; p0 < pairs; p0 += slice) {
+      const int64_t cnt = std::min(slice, pairs - p0);
+      DevMemP rows = rt.alloc(size_t(4 * per_pair * cnt));
+      a.alpha = rows->as<float>();
+      a.pair0 = p0;
+      a.count = int(cnt);
+      {
+        GTNX_PROF("asg_score_alpha", 2.0 * fwd_pair * double(cnt));
+        launch_asg_score_forward(a, rt.stream());
+      }
+      {
+        GTNX_PROF("asg_score_grad", ((grad_em_dev ? 4.0 : 3.0) * fwd_pair + (grad_table_dev ? 8.0 * width : 0.0)) *
+                                        double(cnt));
+        launch_asg_score_backward(a, rt.stream());
+      }
+      if (grad_em_dev) {
+        GTNX_PROF("asg_score_scatter", (3.0 * fwd_pair + 4.0 * double(x.M) * x.C / double(N)) * double(cnt));
+        launch_asg_score_scatter(a, rt.stream());
+      }
+      // (the rows go back to the stream-ordered pool behind the launches)
+    }
+    if (grad_table_dev) {
+      GTNX_PROF("asg_score_table", (4.0 * width * double(x.C + 1) + 8.0 * width + 12.0) * double(pairs) +
+                                       4.0 * double(x.C) * double(x.C + 1));
+      launch_asg_score_table(a, rt.stream());
+    }
+  }
+  g_asg_score.add(1, pairs);
+}
+}  // namespace
+
+void batch_asg_score_stats(int64_t* calls, int64_t* pairs) { g_asg_score.get(calls, pairs); }
+
+void batch_asg_score(const BatchP& ems, const int* frames, const float* table_dev, const int* tokens_dev,
+                     int64_t row_stride, const int* lengths_dev, int N, int L, int max_length, float* scores_dev) {
+  GTNX_HOST_T("batch.asg_score");
+  if (!scores_dev) throw_invalid("[gtnx_batch_asg_score] null scores pointer");
+  asg_score_impl("gtnx_batch_asg_score", ems, frames, table_dev, tokens_dev, row_stride, lengths_dev, N, L, max_length,
+                 scores_dev, nullptr, nullptr, nullptr);
+}
+
+void batch_asg_score_grad(const BatchP& ems, const int* frames, const float* table_dev, const int* tokens_dev,
+                          int64_t row_stride, const int* lengths_dev, int N, int L, int max_length,
+                          const float* weights_dev, float* grad_em_dev, float* grad_table_dev) {
+  GTNX_HOST_T("batch.asg_score_grad");
+  asg_score_impl("gtnx_batch_asg_score_grad", ems, frames, table_dev, tokens_dev, row_stride, lengths_dev, N, L,
+                 max_length, nullptr, weights_dev, grad_em_dev, grad_table_dev);
 }
 
 }  // namespace gtnx

@@ -973,6 +973,30 @@ GTNX_API gtnx_status_t gtnx_batch_ctc_token_align(gtnx_batch_t ems, const int* f
 GTNX_API gtnx_status_t gtnx_batch_ctc_token_align_stats(int64_t* calls, int64_t* pairs) {
   return guard([&] { batch_ctc_token_align_stats(calls, pairs); });
 }
+GTNX_API gtnx_status_t gtnx_batch_asg_score(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                            const void* tokens_device, int64_t row_stride, const void* lengths_device,
+                                            int N, int L, int max_length, void* scores_device) {
+  return guard([&] {
+    batch_asg_score(BH(ems), frames, static_cast<const float*>(table_device), static_cast<const int*>(tokens_device),
+                    row_stride, static_cast<const int*>(lengths_device), N, L, max_length,
+                    static_cast<float*>(scores_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_asg_score_grad(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                                 const void* tokens_device, int64_t row_stride,
+                                                 const void* lengths_device, int N, int L, int max_length,
+                                                 const void* weights_device, void* grad_emissions_device,
+                                                 void* grad_table_device) {
+  return guard([&] {
+    batch_asg_score_grad(BH(ems), frames, static_cast<const float*>(table_device),
+                         static_cast<const int*>(tokens_device), row_stride, static_cast<const int*>(lengths_device), N,
+                         L, max_length, static_cast<const float*>(weights_device),
+                         static_cast<float*>(grad_emissions_device), static_cast<float*>(grad_table_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_asg_score_stats(int64_t* calls, int64_t* pairs) {
+  return guard([&] { batch_asg_score_stats(calls, pairs); });
+}
 GTNX_API gtnx_status_t gtnx_batch_linear_shape(gtnx_batch_t ems, int* rows, int* labels) {
   return guard([&] {
     const BatchP& b = BH(ems);

@@ -896,7 +896,7 @@ struct CtcScoreArgs {
   const GTNX_G int* tokens;     // pair p's row at tokens + p * row_stride
   const GTNX_G int* lengths;    // [pairs]
   GTNX_G float* scores;         // [.. - score0]
-  GTNX_G float* alpha;          // [count][pair_stride] or null (forward); read by backward
+  GTNX_G float* alpha;          // [count][pair_stride] or null (forward); backward turns it into occupancies
   const GTNX_G float* weights;  // [pairs] (backward)
   GTNX_G float* grad;           // [n][M][C] (backward)
   int64_t row_stride, pair0, score0, pair_stride;
@@ -905,6 +905,46 @@ struct CtcScoreArgs {
 void ctc_score_config(int U, int* width, int* per_lane);  // the workgroup's width and the states a lane owns
 void launch_ctc_score_forward(const CtcScoreArgs& a, hipStream_t st);
 void launch_ctc_score_backward(const CtcScoreArgs& a, hipStream_t st);
+// asg_score.hip: the log score forwardScore(emissions_b[:T_b] o (forceAlign(y) o transitions)) of the pairs pair0 ..
+// pair0 + count - 1 in ctc_score.hip's hypothesis form (no blank: position i = 0 .. len - 1 carries y[i]), and the
+// gradients sum_p weights[p] * d score[p] / d (emissions_b, table) (the contract: DESIGN section 25).  table: [C + C * C]
+// in the arc order of asgTransitions, entry y = start[y], entry C + i * C + j = label j followed by label i.
+//   forward:  one workgroup per pair; scores[p - score0] = the score (-inf: len == 0, T_b < len, len > U, a token
+//             outside 0 .. C - 1, no alignment above -inf).  With `alpha` non-null the alpha row of every frame also
+//             goes to alpha[(p - pair0) * pair_stride + t * U + i].
+//   backward: one workgroup per pair: beta in LDS; with `grad` non-null the occupancy p_self + p_step of frame t and
+//             position i takes the place of alpha[.. + t * U + i] (that row was read for frame t + 1).  With `occ`
+//             non-null the sums over the frames, times weights[p], go to occ[p * 2 * occ_half + i] (self) and
+//             occ[p * 2 * occ_half + occ_half + i] (step; position 0: the start arc).
+//   scatter:  one workgroup per (utterance of the range, tile of 8 rows of its slab) walks the utterance's pairs of the
+//             range in k order: the occupancies of a frame summed per label along the chain of equal tokens and added
+//             into grad[b][t][label] by plain loads and stores.  The launch that holds k == 0 zeroes the rows first.
+//   table:    after the last backward; workgroup i < C owns row i of the transitions, workgroup C the start entries.
+//             It walks the pairs in p order and the positions ascending, adding one at a time into an LDS row, and
+//             writes its C entries of grad_table, zeros included.  Pairs the backward skipped are skipped again.
+// The workgroup's width and the positions per lane are chosen from U alone (asg_score_config).
+constexpr int kAsgScoreMaxU = 4096;
+constexpr int kAsgScoreMaxC = 16384;  // the table kernel's LDS row: C floats in 64 KiB
+struct AsgScoreArgs {
+  const GTNX_G float* em;       // [n][M][C]
+  const GTNX_G int* frames;     // [n]
+  const GTNX_G int* tokens;     // pair p's row at tokens + p * row_stride
+  const GTNX_G int* lengths;    // [pairs]
+  const GTNX_G float* table;    // [C + C * C]
+  GTNX_G float* scores;         // [.. - score0]
+  GTNX_G float* alpha;          // [count][pair_stride] or null (forward); backward turns it into occupancies
+  const GTNX_G float* weights;  // [pairs] (backward, table)
+  GTNX_G float* grad;           // [n][M][C] or null (backward)
+  GTNX_G float* occ;            // [pairs][2][occ_half] or null (backward); read by table
+  GTNX_G float* grad_table;     // [C + C * C] (table)
+  int64_t row_stride, pair0, score0, pair_stride;
+  int count, N, L, U, M, C, occ_half, pairs;
+};
+void asg_score_config(int U, int* width, int* per_lane);  // the workgroup's width and the positions a lane owns
+void launch_asg_score_forward(const AsgScoreArgs& a, hipStream_t st);
+void launch_asg_score_backward(const AsgScoreArgs& a, hipStream_t st);
+void launch_asg_score_scatter(const AsgScoreArgs& a, hipStream_t st);
+void launch_asg_score_table(const AsgScoreArgs& a, hipStream_t st);
 // ctc_token_align.hip: the best alignment (max-plus, the arithmetic and the tie rule of align.hip) of the pairs pair0 ..
 // pair0 + count - 1 of ctc_score.hip's hypothesis form (the contract: DESIGN section 24).  One workgroup per pair, width
 // and states per lane from ctc_score_config(U); row p of every output is written over its whole width: scores[p] the

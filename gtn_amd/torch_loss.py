@@ -1,5 +1,6 @@
 """PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
-`asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_beam_decode`, `edit_distance`, `ctc_score` and `ctc_token_align`.
+`asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_beam_decode`, `edit_distance`, `ctc_score`, `ctc_token_align` and
+`asg_score`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -36,6 +37,8 @@ _ARGTYPES = {
     "gtn_ctc_score_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P],
     "gtn_ctc_score_grad_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P],
     "gtn_ctc_token_align_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "gtn_asg_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P],
+    "gtn_asg_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
 }
 
 
@@ -756,6 +759,125 @@ def ctc_score(log_probs, tokens, lengths, blank=0, input_lengths=None, max_lengt
         tok = tok.new_empty(B, N, 1)[:, :, :0]  # (rows without an element are never read, but they need an address)
     ln = lengths.detach().to(torch.int32).reshape(B, N).contiguous()  # (int64 lengths are converted on the device)
     out = _CTCScore.apply(log_probs, tok, ln, blank, frames, max_length)
+    return out.reshape(B) if flat else out
+
+
+class _ASGScore(torch.autograd.Function):
+    """forward: one launch that stores nothing but the scores; backward: the one gradient call with grad_out as the
+    weights, asked for the emission gradient and / or the table gradient as requires_grad says.  The node keeps tensors
+    only: the backward recomputes what it needs."""
+
+    @staticmethod
+    def forward(ctx, emissions, transitions, start, tokens, lengths, frames, max_length):
+        B, T, C_ = emissions.shape
+        N, L = tokens.shape[1], tokens.shape[2]
+        x = emissions.detach().contiguous()
+        table = _asg_weights(start, transitions)
+        stream = _engine_stream(x.device)
+        scores = torch.empty(B, N, dtype=torch.float32, device=x.device)
+        if B * N == 0:
+            pass  # (no pair: nothing to launch, and an empty tensor has no address to hand over)
+        elif _has_native("asg_score", "gtn_asg_score_n"):
+            _call("gtn_asg_score_n", x.data_ptr(), B, T, C_, table.data_ptr(), _host_ptr(frames), tokens.data_ptr(),
+                  lengths.data_ptr(), N, L, max_length, scores.data_ptr())
+        else:
+            ems = gtn.Batch.linear(B, T, C_, x, calc_grad=False, borrow=True)
+            ems.asg_score(table.data_ptr(), tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr(), frames, max_length,
+                          N=N, L=L, row_stride=L)
+        _engine_done(stream)
+        ctx.save_for_backward(x, table, tokens, lengths)
+        ctx.args = (frames, max_length, transitions.dtype, start.dtype)
+        return scores
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, table, tokens, lengths = ctx.saved_tensors
+        frames, max_length, tr_dtype, st_dtype = ctx.args
+        B, T, C_ = x.shape
+        N, L = tokens.shape[1], tokens.shape[2]
+        want_em = ctx.needs_input_grad[0]
+        want_table = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        if not (want_em or want_table):
+            return (None,) * 7
+        grad = torch.empty(B, T, C_, dtype=torch.float32, device=x.device) if want_em else None
+        g_table = torch.empty(C_ + C_ * C_, dtype=torch.float32, device=x.device) if want_table else None
+        if B * N == 0 or x.numel() == 0:
+            for g in (grad, g_table):
+                if g is not None:
+                    g.zero_()
+        else:
+            w = grad_out.detach().to(torch.float32).contiguous()
+            stream = _engine_stream(x.device)
+            if _native():
+                _call("gtn_asg_score_grad_n", x.data_ptr(), B, T, C_, table.data_ptr(), _host_ptr(frames),
+                      tokens.data_ptr(), lengths.data_ptr(), N, L, max_length, w.data_ptr(), _ptr(grad), _ptr(g_table))
+            else:
+                ems = gtn.Batch.linear(B, T, C_, x, calc_grad=False, borrow=True)
+                ems.asg_score_grad(table.data_ptr(), tokens.data_ptr(), lengths.data_ptr(), w.data_ptr(), _ptr(grad),
+                                   _ptr(g_table), frames, max_length, N=N, L=L, row_stride=L)
+            _engine_done(stream)
+        g_tr = g_table[C_:].reshape(C_, C_).to(tr_dtype) if ctx.needs_input_grad[1] else None
+        g_st = g_table[:C_].to(st_dtype) if ctx.needs_input_grad[2] else None
+        return grad, g_tr, g_st, None, None, None, None
+
+
+def asg_score(emissions, transitions, tokens, lengths, start=None, input_lengths=None, max_length=None):
+    """The ASG force-align term of device-resident hypotheses, differentiable: score[b, k] = forwardScore(emissions[b,
+    :T_b] o (forceAlign(tokens[b, k, :len]) o transitions)), the log-sum over all alignments of the summed emissions, start
+    and transition scores, for all B * N hypotheses in one launch against the B shared slabs -- no download of the tokens,
+    no wait, no repeated emissions.  Nothing is subtracted: `asg_loss(x, tr, [y]) == fullConnect(x, tr) - asg_score(x, tr,
+    y)`.  It is what rescoring an N-best list, a risk or margin objective over several hypotheses per utterance, and
+    per-hypothesis weights on `transitions` and `start` need (`asg_decode(collapse=True)` -> `asg_score`).
+    emissions: float32 CUDA tensor [B, T, C] (any scores), read in place; transitions: [C, C] with transitions[i, j] the
+    score of label j followed by label i; start: [C] scores of the first label (zeros when omitted); tokens: int32 CUDA
+    tensor [B, N, L] or [B, L] of labels (there is no blank; equal neighbours are legal, as in forceAlign); lengths: int32
+    or int64 CUDA tensor [B, N] / [B], read on the device and clamped to 0 .. L there -- elements at or past a length are
+    never read; input_lengths: per-utterance frame counts (0 .. T) or None -- rows past T_b are never read and their
+    gradient is exactly 0; max_length (1 .. 4096, default min(L, T, 4096)): the caller's bound on the hypotheses'
+    lengths, which sizes the kernel's LDS and the backward's scratch.  At most 16384 labels.
+    Returns float32 [B, N] (or [B]).  A score is -inf, with zero gradient and never NaN, when the length is 0, T_b is
+    below the length (T_b == 0 included), the length is above max_length, a token inside the length lies outside
+    0 .. C - 1, or every alignment crosses a -inf emission, transition or start score.
+    The backward is one call with grad_out as per-hypothesis weights; it returns gradients for emissions, transitions and
+    start, computes only those that require grad, recomputes what it needs (the node keeps tensors only), skips pairs
+    whose score is -inf or whose incoming gradient is exactly 0, and sums in a fixed order without atomics, so it has the
+    same bits run to run.  A non-uniform grad_out is fine: this is the case `asg_loss(reduction="none")` refuses.  Without
+    requires_grad it never launches.  Runs on the caller's stream."""
+    if not (torch.is_tensor(emissions) and emissions.dim() == 3 and emissions.dtype == torch.float32):
+        raise ValueError("asg_score: emissions must be a float32 tensor [B, T, C]")
+    B, T, C_ = emissions.shape
+    if not (torch.is_tensor(transitions) and tuple(transitions.shape) == (C_, C_)):
+        raise ValueError(f"asg_score: transitions must be [{C_}, {C_}]")
+    if start is not None and not (torch.is_tensor(start) and tuple(start.shape) == (C_,)):
+        raise ValueError(f"asg_score: start must be [{C_}]")
+    if not (torch.is_tensor(tokens) and tokens.dtype == torch.int32 and tokens.dim() in (2, 3) and tokens.shape[0] == B):
+        raise ValueError(f"asg_score: tokens must be an int32 tensor [B, N, L] or [B, L] for a batch of {B}")
+    flat = tokens.dim() == 2
+    N, L = (1, tokens.shape[1]) if flat else tokens.shape[1:]
+    shape = (B,) if flat else (B, N)
+    if not (torch.is_tensor(lengths) and lengths.dtype in (torch.int32, torch.int64) and tuple(lengths.shape) == shape):
+        raise ValueError(f"asg_score: lengths must be an int32 or int64 tensor {list(shape)}")
+    if C_ < 1 or C_ > 16384:
+        raise ValueError("asg_score: the number of labels must be 1 .. 16384")
+    max_length = max(1, min(L, T, 4096)) if max_length is None else int(max_length)
+    if not 1 <= max_length <= 4096:
+        raise ValueError("asg_score: max_length outside 1 .. 4096")
+    frames = None if input_lengths is None else _frame_counts("asg_score", input_lengths, B, T, 0)
+    for t, what in ((emissions, "emissions"), (transitions, "transitions"), (start, "start"), (tokens, "tokens"),
+                    (lengths, "lengths")):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(f"asg_score: {what} must be a CUDA tensor (the scores are computed on the device)")
+        if t.device != emissions.device:
+            raise ValueError("asg_score: all tensors must be on one device")
+    if start is None:
+        start = torch.zeros(C_, dtype=torch.float32, device=emissions.device)
+    tok = tokens.detach().reshape(B, N, L).contiguous()
+    if B * N and tok.numel() == 0:
+        tok = tok.new_empty(B, N, 1)[:, :, :0]  # (rows without an element are never read, but they need an address)
+    ln = lengths.detach().to(torch.int32).reshape(B, N).contiguous()  # (int64 lengths are converted on the device)
+    out = _ASGScore.apply(emissions, transitions, start, tok, ln, frames, max_length)
     return out.reshape(B) if flat else out
 
 

@@ -245,6 +245,30 @@ inline void ctcScoreGrad(const Batch& ems, const int* tokensDevice, int64_t rowS
   detail::check(gtnx_batch_ctc_score_grad(ems.handle(), frames, blank, tokensDevice, rowStride, lengthsDevice, N, L,
                                           maxLength, weightsDevice, gradDevice));
 }
+/** The ASG force-align term of all n * N device-resident hypotheses under the slabs of a Batch::linear, results left on
+ *  the device: scoresDevice[b][k] = forwardScore(emissions_b[0 .. T_b) o (forceAlign(tokens[b][k][0 .. len)) o
+ *  transitions)), len = clamp(lengthsDevice[b][k], 0, L), log semiring, nothing subtracted.  tableDevice float32
+ *  [C + C * C] (device memory) in the arc order of criteria::asgTransitions: entry y = start[y], entry C + i * C + j =
+ *  label j followed by label i.  tokensDevice / lengthsDevice / maxLength / frames as in ctcScore; tokens are labels
+ *  only and equal neighbours are legal.  -inf: len == 0, T_b < len, len > maxLength, a token outside 0 .. C - 1, no
+ *  alignment above -inf.  One launch, no copy back, no wait -- gtnx_batch_asg_score */
+inline void asgScore(const Batch& ems, const float* tableDevice, const int* tokensDevice, int64_t rowStride,
+                     const int* lengthsDevice, int N, int L, int maxLength, float* scoresDevice,
+                     const int* frames = nullptr) {
+  detail::check(gtnx_batch_asg_score(ems.handle(), frames, tableDevice, tokensDevice, rowStride, lengthsDevice, N, L,
+                                     maxLength, scoresDevice));
+}
+/** The gradients of asgScore under the weights weightsDevice [n][N]: gradEmissionsDevice (or null) float32 [n][M][C],
+ *  every element written (zeros where nothing lands, rows from T_b on included); gradTableDevice (or null) float32
+ *  [C + C * C], every entry written; not both null.  Pairs with a -inf score or a weight of exactly 0 add nothing.
+ *  Stateless (the alpha rows are recomputed into pooled scratch, sliced beyond 256 MiB) and bit-repeatable (fixed
+ *  summation order, no atomics) -- gtnx_batch_asg_score_grad */
+inline void asgScoreGrad(const Batch& ems, const float* tableDevice, const int* tokensDevice, int64_t rowStride,
+                         const int* lengthsDevice, int N, int L, int maxLength, const float* weightsDevice,
+                         float* gradEmissionsDevice, float* gradTableDevice, const int* frames = nullptr) {
+  detail::check(gtnx_batch_asg_score_grad(ems.handle(), frames, tableDevice, tokensDevice, rowStride, lengthsDevice, N,
+                                          L, maxLength, weightsDevice, gradEmissionsDevice, gradTableDevice));
+}
 /** The best alignment of all n * N device-resident hypotheses (the form of ctcScore) under the slabs of a Batch::linear,
  *  results left on the device: scoresDevice [n][N] the Viterbi score (-inf without a path); startsDevice / endsDevice
  *  int32 n * N rows of width L, outStride (>= L) apart: the first frame of token i and one past its last, -1 for i >= len

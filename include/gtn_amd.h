@@ -535,6 +535,55 @@ gtnx_status_t gtnx_batch_ctc_token_align(gtnx_batch_t ems, const int* frames, in
                                          int64_t frame_stride);
 /* calls that have launched so far (process-wide) / pairs they aligned */
 gtnx_status_t gtnx_batch_ctc_token_align_stats(int64_t* calls, int64_t* pairs);
+/* The ASG force-align term of n * N device-resident hypotheses under the n emission slabs of a gtnx_batch_linear / _rows
+ * batch, left on the device (DESIGN section 25 holds the contract):
+ *   scores[b][k] = forwardScore(emissions_b[0 .. T_b) o (forceAlign(tokens[b][k][0 .. len)) o transitions)),
+ * len = clamp(lengths[b][k], 0, L), log semiring, nothing subtracted -- so that the ASG loss of y is
+ * forwardScore(emissions o transitions) minus this score.  tokens_device, row_stride, lengths_device, N, L, frames and
+ * max_length are those of gtnx_batch_ctc_score; tokens are labels only (ASG has no blank) and equal neighbours are
+ * legal, as in forceAlign.  table_device: float32 [C + C * C] in the arc order of asgTransitions -- entry y is
+ * start[y], entry C + i * C + j is transitions[i][j], label j followed by label i -- the table
+ * gtnx_batch_ctc_beam_decode_lm takes.  The positions are i = 0 .. len - 1, float32:
+ *   alpha_0[0] = start[y_0] + e(0, y_0), every other alpha_0[i] = -inf;
+ *   alpha_t[i] = logadd(alpha_{t-1}[i] + tr[y_i][y_i], alpha_{t-1}[i-1] + tr[y_i][y_{i-1}]) + e(t, y_i);
+ *   score = alpha_{T_b - 1}[len - 1].
+ * The score is -inf -- never NaN, and without a gradient -- when len == 0, T_b < len (T_b == 0 included), len >
+ * max_length, a token inside the length lies outside 0 .. C - 1 (checked by the kernel before it becomes an address),
+ * or every alignment crosses a -inf emission or table entry.  Elements at or past a length and emission rows at or
+ * past T_b are never read.
+ * GTNX_INVALID_ARGUMENT before a device is asked for: a null batch, table, tokens, lengths or scores pointer, negative
+ * N, L or row_stride, row_stride < L, max_length outside 1 .. 4096.  n * N == 0 returns without touching a device.
+ * With the device: not a gtnx_batch_linear / _rows batch, a frame count outside 0 .. M, more than 16384 labels (the
+ * table gradient keeps a row of C floats in LDS), table_device anything but memory allocated on the engine's current
+ * device (the kernel gathers from it: host memory is refused with one GPU as well), an output the engine's current
+ * device may not write.
+ * One launch on the engine's stream (asg_score.hip), one workgroup per pair, no scratch; nothing is copied back, the
+ * call does not wait, nothing but scores is written. */
+gtnx_status_t gtnx_batch_asg_score(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                   const void* tokens_device, int64_t row_stride, const void* lengths_device, int N,
+                                   int L, int max_length, void* scores_device);
+/* The gradients of those scores under caller-supplied weights_device (float32 [n][N], device memory), in one stateless
+ * call.  The inputs are those of gtnx_batch_asg_score with the same refusals.
+ *   grad_emissions_device (or null) float32 [n][M][C]: sum over k of weights[b][k] * d scores[b][k] / d emissions[b];
+ *     EVERY element is written: zeros where nothing lands, rows at or past T_b included.
+ *   grad_table_device (or null) float32 [C + C * C]: sum over all pairs of weights * d scores / d table in the table's
+ *     own order; EVERY entry is written.
+ * Not both null.  A pair whose score is -inf or whose weight is exactly 0 adds nothing.
+ * The alpha rows are recomputed into scratch from the stream-ordered pool, max_b T_b * max_length floats per pair, at
+ * most 256 MiB per slice of launches; beyond that the pairs run in slices, bit-equal to the unsliced run (the
+ * environment variable GTNX_ASG_SCORE_SCRATCH_BYTES, read per call, lowers the cap: a debug switch for tests); a
+ * single pair above the cap runs alone with scratch of its own size.  With a table gradient every pair also leaves 2 *
+ * min(L, max_length) floats of occupancy sums in scratch, reduced by one launch behind the last slice: workgroup i
+ * owns row i of the transitions, walks the pairs and positions in ascending order and adds one value at a time.  The
+ * emission gradient is added by one workgroup per (utterance, tile of rows), which walks the utterance's pairs in k
+ * order.  The sums are taken in one fixed order by plain loads and stores, so both gradients have the same bits run to
+ * run; there are no floating-point atomics.  n * N == 0 returns without touching a device AND WITHOUT WRITING either gradient. */
+gtnx_status_t gtnx_batch_asg_score_grad(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                        const void* tokens_device, int64_t row_stride, const void* lengths_device,
+                                        int N, int L, int max_length, const void* weights_device,
+                                        void* grad_emissions_device, void* grad_table_device);
+/* calls of either kind that have launched so far (process-wide) / pairs they took */
+gtnx_status_t gtnx_batch_asg_score_stats(int64_t* calls, int64_t* pairs);
 /* rows M and labels C of the slabs of a gtnx_batch_linear / _rows batch; -1, -1 for any other batch */
 gtnx_status_t gtnx_batch_linear_shape(gtnx_batch_t ems, int* rows, int* labels);
 gtnx_status_t gtnx_batch_backward(gtnx_batch_t a, int retain_graph);                  /* autograd.cpp:17-67 */
