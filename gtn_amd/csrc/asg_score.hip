@@ -41,37 +41,10 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "pair_kernels.h"
 
 namespace gtnx {
 namespace {
-
-constexpr float NEG_INF = -__builtin_inff();
-
-__device__ __forceinline__ float logadd(float x, float y) {
-  if (x == NEG_INF) return y;
-  if (y == NEG_INF) return x;
-  const float m = fmaxf(x, y), n = fminf(x, y);
-  return m + log1pf(expf(n - m));
-}
-
-// the workgroup's barrier; a workgroup of one wave needs its LDS and global accesses ordered, nothing more
-template <int WG>
-__device__ __forceinline__ void wg_sync() {
-  if (WG > 64) {
-    __syncthreads();
-  } else {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-// ... that also tells every lane whether any lane holds a non-zero `v`
-template <int WG>
-__device__ __forceinline__ bool wg_any(int v) {
-  if (WG > 64) return __syncthreads_or(v) != 0;
-  const bool r = __ballot(v != 0) != 0;
-  wg_sync<WG>();
-  return r;
-}
 
 // what a lane keeps of its positions: i = tid + j * WG
 template <int PER>

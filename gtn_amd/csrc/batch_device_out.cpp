@@ -13,6 +13,10 @@
 //      under GTNX_PROF with its algorithmic bytes.
 //   4. the entry's Counters, and a *_stats getter that is its get().
 //   An entry with a route for every other batch computes the path graphs and hands them to paths_to_rows(...).
+//   An entry that reads hypothesis rows (tokens [n][N][L], lengths [n][N], max_length, one workgroup per pair: CTC score,
+//   CTC token alignment, ASG score) has its own argument-only checks first, then pairs = check_hypotheses(...) and the
+//   return of a call without pairs; linear_hypothesis_batch(...) for step 2's refusals, its own checks of the shape and
+//   of the device, settle_frames(...) for step 3's opening, and for_pair_slices(...) around launches with scratch per pair.
 #include "batch.h"
 
 #include <algorithm>
@@ -77,13 +81,93 @@ std::vector<int> resolve_frames(const int* frames, const Batch& x) {
 
 // what the scratch of ONE launch may take; a call that needs more runs in slices of launches.  `env`: debug switch, read
 // per call: tests lower the cap to see a sliced call without allocating gigabytes
-int64_t scratch_cap(const char* env, int64_t cap) {
-  const char* e = std::getenv(env);
+struct ScratchCap {
+  const char* env;
+  int64_t bytes;
+};
+int64_t scratch_cap(const ScratchCap& cap) {
+  const char* e = std::getenv(cap.env);
   if (e && *e) {
     const long long v = std::atoll(e);
-    if (v > 0) return std::min<int64_t>(v, cap);
+    if (v > 0) return std::min<int64_t>(v, cap.bytes);
   }
-  return cap;
+  return cap.bytes;
+}
+
+// body(p0, count) over the pairs in slices whose scratch, `bytes_per_pair` each, stays within the cap; a pair that is
+// above the cap by itself runs alone
+template <class Body>
+void for_pair_slices(int64_t pairs, int64_t bytes_per_pair, const ScratchCap& cap, Body&& body) {
+  const int64_t room = scratch_cap(cap);
+  const int64_t slice = bytes_per_pair > 0 ? std::max<int64_t>(1, room / bytes_per_pair) : pairs;
+  for (int64_t p0 = 0; p0 < pairs; p0 += slice) body(p0, std::min(slice, pairs - p0));
+}
+
+// ---- what the entries that read hypothesis rows share (ctc_score.hip, ctc_token_align.hip, asg_score.hip) ----
+// the rows as the caller describes them: pair p = b * N + k has tokens[p * row_stride .. + L) and lengths[p], and no
+// length counts beyond max_length
+struct Hypotheses {
+  const int* tokens;
+  int64_t row_stride;
+  const int* lengths;
+  int N, L, max_length;
+};
+static_assert(kCtcScoreMaxU == 4096 && kAsgScoreMaxU == 4096, "the text below says 4096");
+
+// what the arguments alone decide about the rows.  Returns the number of pairs: a call without any returns OK without
+// asking for a device
+int64_t check_hypotheses(const char* who, const BatchP& ems, const Hypotheses& h) {
+  if (!ems) refuse(who, "null batch");
+  if (!h.tokens || !h.lengths) refuse(who, "null input pointer (tokens and lengths are both read)");
+  if (h.N < 0 || h.L < 0) refuse(who, "negative N or L");
+  if (h.row_stride < 0) refuse(who, "negative row stride");
+  if (h.row_stride < h.L) refuse(who, "row_stride is shorter than the rows' width L");
+  if (h.max_length < 1 || h.max_length > kCtcScoreMaxU) refuse(who, "max_length outside 1 .. 4096");
+  const int64_t pairs = int64_t(ems->n) * h.N;
+  if (pairs > std::numeric_limits<int>::max()) refuse(who, "n times N does not fit an int");
+  return pairs;
+}
+
+// the first refusals of the device side.  There is no other route: the results are those of the slabs of a native linear
+// batch
+Batch& linear_hypothesis_batch(const char* who, const BatchP& ems, const int* frames) {
+  Runtime::get();
+  if (!native_linear(*ems)) refuse(who, "not a native linear batch (gtnx_batch_linear / _rows)");
+  check_frames(who, frames, ems->n, ems->M, *ems);
+  return *ems;
+}
+
+// behind the last refusal: the values settled, T_b of every utterance uploaded, and what every argument struct of these
+// kernels says about the slabs and the rows filled in.  Returns the largest T_b and the mean one (every utterance has N
+// pairs: the frames of a pair of the algorithmic bytes)
+struct PairFrames {
+  DevMemP dev;
+  int maxT = 0;
+  double mean = 0;
+};
+template <class Args>
+PairFrames settle_frames(Batch& x, const int* frames, const Hypotheses& h, Args& a) {
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  const std::vector<int> fr = resolve_frames(frames, x);
+  PairFrames f;
+  double sum = 0;
+  for (int t : fr) {
+    f.maxT = std::max(f.maxT, t);
+    sum += t;
+  }
+  f.mean = sum / double(x.n);
+  f.dev = upload_vec(fr);
+  a.em = x.w_dev;
+  a.frames = f.dev->as<int>();
+  a.tokens = h.tokens;
+  a.lengths = h.lengths;
+  a.row_stride = h.row_stride;
+  a.N = h.N;
+  a.L = h.L;
+  a.U = h.max_length;
+  a.M = x.M;
+  a.C = x.C;
+  return f;
 }
 
 // The route of every batch no kernel takes: the labels of the path graphs read on the host, one upload.  Row b of
@@ -536,7 +620,7 @@ void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int 
 namespace {
 Counters g_edit_distance;  // (calls, pairs)
 // the walk's scratch: a pair at the largest widths takes 64 MiB, so a slice always holds at least one pair
-constexpr int64_t kEditDistanceScratchCap = int64_t(256) << 20;
+constexpr ScratchCap kEditDistanceScratch{"GTNX_EDIT_DISTANCE_SCRATCH_BYTES", int64_t(256) << 20};
 }  // namespace
 
 void batch_edit_distance_stats(int64_t* calls, int64_t* pairs) { g_edit_distance.get(calls, pairs); }
@@ -585,10 +669,7 @@ void batch_edit_distance(const int* hyp_dev, int64_t hyp_stride, const int* hyp_
     launch_edit_distance(a, rt.stream());
   } else {
     const int64_t per_pair = int64_t(16) * L * nbU;
-    const int64_t cap = scratch_cap("GTNX_EDIT_DISTANCE_SCRATCH_BYTES", kEditDistanceScratchCap);
-    const int64_t slice = per_pair > 0 ? std::max<int64_t>(1, cap / per_pair) : pairs;
-    for (int64_t p0 = 0; p0 < pairs; p0 += slice) {
-      const int64_t cnt = std::min(slice, pairs - p0);
+    for_pair_slices(pairs, per_pair, kEditDistanceScratch, [&](int64_t p0, int64_t cnt) {
       DevMemP words = rt.alloc(size_t(std::max<int64_t>(per_pair * cnt, 16)));
       a.scratch = words->as<gtnx_ul2>();
       a.pair0 = p0;
@@ -596,7 +677,7 @@ void batch_edit_distance(const int* hyp_dev, int64_t hyp_stride, const int* hyp_
       GTNX_PROF("edit_distance_ops", (io_bytes / double(pairs) + 2.0 * double(per_pair) + 12.0) * double(cnt));
       launch_edit_distance(a, rt.stream());
       // (the words go back to the stream-ordered pool behind the launch)
-    }
+    });
   }
   g_edit_distance.add(1, pairs);
 }
@@ -605,63 +686,33 @@ void batch_edit_distance(const int* hyp_dev, int64_t hyp_stride, const int* hyp_
 namespace {
 Counters g_ctc_score;  // (calls, pairs)
 // the alpha rows of a gradient call: a pair that is above the cap by itself runs alone with scratch of its own size
-constexpr int64_t kCtcScoreScratchCap = int64_t(256) << 20;
+constexpr ScratchCap kCtcScoreScratch{"GTNX_CTC_SCORE_SCRATCH_BYTES", int64_t(256) << 20};
 
 // both entry points: scores_dev for the score, weights_dev and grad_dev for the gradient
-void ctc_score_impl(const char* who, const BatchP& ems, const int* frames, int blank, const int* tokens_dev,
-                    int64_t row_stride, const int* lengths_dev, int N, int L, int max_length, float* scores_dev,
-                    const float* weights_dev, float* grad_dev) {
+void ctc_score_impl(const char* who, const BatchP& ems, const int* frames, int blank, const Hypotheses& h,
+                    float* scores_dev, const float* weights_dev, float* grad_dev) {
   const bool want_grad = scores_dev == nullptr;
   // what the arguments alone decide comes first: no device is asked for an invalid call
-  if (!ems) refuse(who, "null batch");
-  if (!tokens_dev || !lengths_dev) refuse(who, "null input pointer (tokens and lengths are both read)");
   if (want_grad && (!weights_dev || !grad_dev)) refuse(who, "null weights or grad pointer");
-  if (N < 0 || L < 0) refuse(who, "negative N or L");
-  if (row_stride < 0) refuse(who, "negative row stride");
   if (blank < 0) refuse(who, "negative blank");
-  if (row_stride < L) refuse(who, "row_stride is shorter than the rows' width L");
-  if (max_length < 1 || max_length > kCtcScoreMaxU) refuse(who, "max_length outside 1 .. 4096");
-  const int n = ems->n;
-  const int64_t pairs = int64_t(n) * N;
-  if (pairs > std::numeric_limits<int>::max()) refuse(who, "n times N does not fit an int");
+  const int64_t pairs = check_hypotheses(who, ems, h);
   if (pairs <= 0) return;
-  Runtime& rt = Runtime::get();
-  // there is no other route: the scores are those of the slabs of a native linear batch
-  if (!native_linear(*ems)) refuse(who, "not a native linear batch (gtnx_batch_linear / _rows)");
-  Batch& x = *ems;
-  check_frames(who, frames, n, x.M, x);
+  Batch& x = linear_hypothesis_batch(who, ems, frames);
   if (blank >= x.C) refuse(who, "blank is not below the number of labels");
   check_outputs_local(who, {want_grad ? grad_dev : scores_dev});
-  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
-  const std::vector<int> fr = resolve_frames(frames, x);
-  int maxT = 0;
-  double frame_sum = 0;
-  for (int t : fr) {
-    maxT = std::max(maxT, t);
-    frame_sum += t;
-  }
-  DevMemP d_frames = upload_vec(fr);
-  const int U = max_length;
-  const int64_t SM = 2 * int64_t(U) + 1;
+  Runtime& rt = Runtime::get();
   CtcScoreArgs a{};
-  a.em = x.w_dev;
-  a.frames = d_frames->as<int>();
-  a.tokens = tokens_dev;
-  a.lengths = lengths_dev;
+  const PairFrames fr = settle_frames(x, frames, h, a);
+  const int N = h.N, L = h.L, U = h.max_length;
+  const int64_t SM = 2 * int64_t(U) + 1;
   a.weights = weights_dev;
   a.grad = grad_dev;
-  a.row_stride = row_stride;
-  a.N = N;
-  a.L = L;
-  a.U = U;
-  a.M = x.M;
-  a.C = x.C;
   a.blank = blank;
   // algorithmic bytes, by the widths (the lengths are device memory: an upper bound).  forward: per pair and frame one
   // emission per state, the tokens and the length once, the score out.  With the rows kept: every alpha out as well.
   // backward: the alphas and the emissions back in, one load and one store of a gradient element per state and frame
   // at most, the tokens and the length, and the utterance's slab zeroed once.
-  const double per_pair_frames = frame_sum / double(n);  // (the mean: every utterance has N pairs)
+  const double per_pair_frames = fr.mean;
   const double fwd_pair = 4.0 * double(SM) * per_pair_frames + 4.0 * std::min(L, U) + 8.0;
   if (!want_grad) {
     a.scores = scores_dev;
@@ -671,12 +722,9 @@ void ctc_score_impl(const char* who, const BatchP& ems, const int* frames, int b
     GTNX_PROF("ctc_score", fwd_pair * double(pairs));
     launch_ctc_score_forward(a, rt.stream());
   } else {
-    const int64_t per_pair = std::max<int64_t>(int64_t(maxT), 1) * SM;  // floats
-    const int64_t cap = scratch_cap("GTNX_CTC_SCORE_SCRATCH_BYTES", kCtcScoreScratchCap);
-    const int64_t slice = std::max<int64_t>(1, cap / (4 * per_pair));
+    const int64_t per_pair = std::max<int64_t>(int64_t(fr.maxT), 1) * SM;  // floats
     a.pair_stride = per_pair;
-    for (int64_t p0 = 0; p0 < pairs; p0 += slice) {
-      const int64_t cnt = std::min(slice, pairs - p0);
+    for_pair_slices(pairs, 4 * per_pair, kCtcScoreScratch, [&](int64_t p0, int64_t cnt) {
       DevMemP rows = rt.alloc(size_t(4 * per_pair * cnt));
       DevMemP sc = rt.alloc(size_t(4 * cnt));
       a.alpha = rows->as<float>();
@@ -693,7 +741,7 @@ void ctc_score_impl(const char* who, const BatchP& ems, const int* frames, int b
         launch_ctc_score_backward(a, rt.stream());
       }
       // (the rows go back to the stream-ordered pool behind the launches)
-    }
+    });
   }
   g_ctc_score.add(1, pairs);
 }
@@ -705,7 +753,7 @@ void batch_ctc_score(const BatchP& ems, const int* frames, int blank, const int*
                      const int* lengths_dev, int N, int L, int max_length, float* scores_dev) {
   GTNX_HOST_T("batch.ctc_score");
   if (!scores_dev) throw_invalid("[gtnx_batch_ctc_score] null scores pointer");
-  ctc_score_impl("gtnx_batch_ctc_score", ems, frames, blank, tokens_dev, row_stride, lengths_dev, N, L, max_length,
+  ctc_score_impl("gtnx_batch_ctc_score", ems, frames, blank, {tokens_dev, row_stride, lengths_dev, N, L, max_length},
                  scores_dev, nullptr, nullptr);
 }
 
@@ -713,8 +761,8 @@ void batch_ctc_score_grad(const BatchP& ems, const int* frames, int blank, const
                           const int* lengths_dev, int N, int L, int max_length, const float* weights_dev,
                           float* grad_dev) {
   GTNX_HOST_T("batch.ctc_score_grad");
-  ctc_score_impl("gtnx_batch_ctc_score_grad", ems, frames, blank, tokens_dev, row_stride, lengths_dev, N, L,
-                 max_length, nullptr, weights_dev, grad_dev);
+  ctc_score_impl("gtnx_batch_ctc_score_grad", ems, frames, blank,
+                 {tokens_dev, row_stride, lengths_dev, N, L, max_length}, nullptr, weights_dev, grad_dev);
 }
 
 // ---- batched CTC token alignment of device-resident hypotheses (ctc_token_align.hip) ----
@@ -722,7 +770,7 @@ namespace {
 constexpr const char* kCtcTokenAlign = "gtnx_batch_ctc_token_align";
 Counters g_ctc_token_align;  // (calls, pairs)
 // the back-pointer words: a pair that is above the cap by itself runs alone with scratch of its own size
-constexpr int64_t kCtcTokenAlignScratchCap = int64_t(256) << 20;
+constexpr ScratchCap kCtcTokenAlignScratch{"GTNX_CTC_TOKEN_ALIGN_SCRATCH_BYTES", int64_t(256) << 20};
 }  // namespace
 
 void batch_ctc_token_align_stats(int64_t* calls, int64_t* pairs) { g_ctc_token_align.get(calls, pairs); }
@@ -733,72 +781,42 @@ void batch_ctc_token_align(const BatchP& ems, const int* frames, int blank, cons
                            int64_t frame_stride) {
   GTNX_HOST_T("batch.ctc_token_align");
   const char* who = kCtcTokenAlign;
+  const Hypotheses h{tokens_dev, row_stride, lengths_dev, N, L, max_length};
   // what the arguments alone decide comes first: no device is asked for an invalid call
-  if (!ems) refuse(who, "null batch");
-  if (!tokens_dev || !lengths_dev) refuse(who, "null input pointer (tokens and lengths are both read)");
   if (!scores_dev || !starts_dev || !ends_dev) refuse(who, "null output pointer (scores, starts and ends are all written)");
-  if (N < 0 || L < 0) refuse(who, "negative N or L");
-  if (row_stride < 0 || out_stride < 0 || frame_stride < 0) refuse(who, "negative row stride");
+  if (out_stride < 0 || frame_stride < 0) refuse(who, "negative row stride");
   if (blank < 0) refuse(who, "negative blank");
-  if (row_stride < L) refuse(who, "row_stride is shorter than the rows' width L");
   if (out_stride < L) refuse(who, "out_stride is shorter than the rows' width L");
-  if (max_length < 1 || max_length > kCtcScoreMaxU) refuse(who, "max_length outside 1 .. 4096");
-  const int n = ems->n;
-  const int64_t pairs = int64_t(n) * N;
-  if (pairs > std::numeric_limits<int>::max()) refuse(who, "n times N does not fit an int");
+  const int64_t pairs = check_hypotheses(who, ems, h);
   if (pairs <= 0) return;
-  Runtime& rt = Runtime::get();
-  // there is no other route: the alignments are those of the slabs of a native linear batch
-  if (!native_linear(*ems)) refuse(who, "not a native linear batch (gtnx_batch_linear / _rows)");
-  Batch& x = *ems;
-  check_frames(who, frames, n, x.M, x);
+  Batch& x = linear_hypothesis_batch(who, ems, frames);
   if (blank >= x.C) refuse(who, "blank is not below the number of labels");
   if (frame_tokens_dev && frame_stride < x.M) refuse(who, "frame_stride is shorter than the rows of the batch");
   check_outputs_local(who, {scores_dev, starts_dev, ends_dev, token_scores_dev, frame_tokens_dev});
-  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
-  const std::vector<int> fr = resolve_frames(frames, x);
-  int maxT = 0;
-  double frame_sum = 0;
-  for (int t : fr) {
-    maxT = std::max(maxT, t);
-    frame_sum += t;
-  }
-  DevMemP d_frames = upload_vec(fr);
+  Runtime& rt = Runtime::get();
+  CtcTokenAlignArgs a{};
+  const PairFrames fr = settle_frames(x, frames, h, a);
   const int U = max_length;
   const int64_t SM = 2 * int64_t(U) + 1;
-  CtcTokenAlignArgs a{};
-  a.em = x.w_dev;
-  a.frames = d_frames->as<int>();
-  a.tokens = tokens_dev;
-  a.lengths = lengths_dev;
   a.scores = scores_dev;
   a.starts = starts_dev;
   a.ends = ends_dev;
   a.token_scores = token_scores_dev;
   a.frame_tokens = frame_tokens_dev;
-  a.row_stride = row_stride;
   a.out_stride = out_stride;
   a.frame_stride = frame_stride;
-  a.N = N;
-  a.L = L;
-  a.U = U;
-  a.M = x.M;
-  a.C = x.C;
   a.blank = blank;
   // algorithmic bytes, by the widths (the lengths are device memory: an upper bound).  Per pair and frame one emission
   // per state and 2 bits per state out; the walk reads one window of 128 words per 16 frames; the tokens and the length
   // once, the score and the two span rows out; with token scores one emission per frame at most and the row; with
   // frame tokens the row.
-  const double per_pair_frames = frame_sum / double(n);  // (the mean: every utterance has N pairs)
+  const double per_pair_frames = fr.mean;
   const double pair_bytes = (4.0 + 0.25) * double(SM) * per_pair_frames + 32.0 * per_pair_frames + 4.0 * std::min(L, U) +
                             8.0 + 8.0 * L + (token_scores_dev ? 4.0 * per_pair_frames + 4.0 * L : 0.0) +
                             (frame_tokens_dev ? 4.0 * x.M : 0.0);
-  const int64_t per_pair = (std::max<int64_t>(int64_t(maxT), 1) + 15) / 16 * SM;  // words
-  const int64_t cap = scratch_cap("GTNX_CTC_TOKEN_ALIGN_SCRATCH_BYTES", kCtcTokenAlignScratchCap);
-  const int64_t slice = std::max<int64_t>(1, cap / (4 * per_pair));
+  const int64_t per_pair = (std::max<int64_t>(int64_t(fr.maxT), 1) + 15) / 16 * SM;  // words
   a.pair_stride = per_pair;
-  for (int64_t p0 = 0; p0 < pairs; p0 += slice) {
-    const int64_t cnt = std::min(slice, pairs - p0);
+  for_pair_slices(pairs, 4 * per_pair, kCtcTokenAlignScratch, [&](int64_t p0, int64_t cnt) {
     DevMemP words = rt.alloc(size_t(4 * per_pair * cnt));
     a.bp = words->as<unsigned>();
     a.pair0 = p0;
@@ -806,7 +824,7 @@ void batch_ctc_token_align(const BatchP& ems, const int* frames, int blank, cons
     GTNX_PROF("ctc_token_align", pair_bytes * double(cnt));
     launch_ctc_token_align(a, rt.stream());
     // (the words go back to the stream-ordered pool behind the launch)
-  }
+  });
   g_ctc_token_align.add(1, pairs);
 }
 
@@ -814,62 +832,32 @@ void batch_ctc_token_align(const BatchP& ems, const int* frames, int blank, cons
 namespace {
 Counters g_asg_score;  // (calls, pairs)
 // the alpha rows of a gradient call: a pair that is above the cap by itself runs alone with scratch of its own size
-constexpr int64_t kAsgScoreScratchCap = int64_t(256) << 20;
+constexpr ScratchCap kAsgScoreScratch{"GTNX_ASG_SCORE_SCRATCH_BYTES", int64_t(256) << 20};
 
 // both entry points: scores_dev for the score; weights_dev and grad_em_dev / grad_table_dev for the gradients
-void asg_score_impl(const char* who, const BatchP& ems, const int* frames, const float* table_dev,
-                    const int* tokens_dev, int64_t row_stride, const int* lengths_dev, int N, int L, int max_length,
+void asg_score_impl(const char* who, const BatchP& ems, const int* frames, const float* table_dev, const Hypotheses& h,
                     float* scores_dev, const float* weights_dev, float* grad_em_dev, float* grad_table_dev) {
   const bool want_grad = scores_dev == nullptr;
   // what the arguments alone decide comes first: no device is asked for an invalid call
-  if (!ems) refuse(who, "null batch");
   if (!table_dev) refuse(who, "null table pointer");
-  if (!tokens_dev || !lengths_dev) refuse(who, "null input pointer (tokens and lengths are both read)");
   if (want_grad && !weights_dev) refuse(who, "null weights pointer");
   if (want_grad && !grad_em_dev && !grad_table_dev) refuse(who, "neither gradient asked for (both pointers null)");
-  if (N < 0 || L < 0) refuse(who, "negative N or L");
-  if (row_stride < 0) refuse(who, "negative row stride");
-  if (row_stride < L) refuse(who, "row_stride is shorter than the rows' width L");
-  if (max_length < 1 || max_length > kAsgScoreMaxU) refuse(who, "max_length outside 1 .. 4096");
-  const int n = ems->n;
-  const int64_t pairs = int64_t(n) * N;
-  if (pairs > std::numeric_limits<int>::max()) refuse(who, "n times N does not fit an int");
+  const int64_t pairs = check_hypotheses(who, ems, h);
   if (pairs <= 0) return;
+  Batch& x = linear_hypothesis_batch(who, ems, frames);
   Runtime& rt = Runtime::get();
-  // there is no other route: the scores are those of the slabs of a native linear batch
-  if (!native_linear(*ems)) refuse(who, "not a native linear batch (gtnx_batch_linear / _rows)");
-  Batch& x = *ems;
-  check_frames(who, frames, n, x.M, x);
   // (the table kernel keeps one row of C floats in LDS)
   if (x.C > kAsgScoreMaxC) refuse(who, "more than 16384 labels");
   // (the kernel gathers from it: host memory is refused too, with one GPU as well)
   if (!ptr_device_memory_of(table_dev, rt.device())) refuse(who, "the table is not memory of the engine's current device");
   check_outputs_local(who, {scores_dev, grad_em_dev, grad_table_dev});
-  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
-  const std::vector<int> fr = resolve_frames(frames, x);
-  int maxT = 0;
-  double frame_sum = 0;
-  for (int t : fr) {
-    maxT = std::max(maxT, t);
-    frame_sum += t;
-  }
-  DevMemP d_frames = upload_vec(fr);
-  const int U = max_length;
   AsgScoreArgs a{};
-  a.em = x.w_dev;
-  a.frames = d_frames->as<int>();
-  a.tokens = tokens_dev;
-  a.lengths = lengths_dev;
+  const PairFrames fr = settle_frames(x, frames, h, a);
+  const int N = h.N, L = h.L, U = h.max_length;
   a.table = table_dev;
   a.weights = weights_dev;
   a.grad = grad_em_dev;
   a.grad_table = grad_table_dev;
-  a.row_stride = row_stride;
-  a.N = N;
-  a.L = L;
-  a.U = U;
-  a.M = x.M;
-  a.C = x.C;
   a.pairs = int(pairs);
   a.occ_half = std::max(std::min(L, U), 1);
   // algorithmic bytes, by the widths (the lengths are device memory: an upper bound).  forward: per pair and frame one
@@ -879,7 +867,7 @@ void asg_score_impl(const char* who, const BatchP& ems, const int* frames, const
   // scatter: the occupancies back in, one load and one store of a gradient element per position and frame at most,
   // and the utterance's slab zeroed once.  table: every workgroup streams the tokens, the sums come back in once, the
   // table goes out.
-  const double per_pair_frames = frame_sum / double(n);  // (the mean: every utterance has N pairs)
+  const double per_pair_frames = fr.mean;
   const double width = std::min(L, U);
   const double fwd_pair = 4.0 * double(U) * per_pair_frames + 12.0 * width + 8.0;
   if (!want_grad) {
@@ -890,9 +878,7 @@ void asg_score_impl(const char* who, const BatchP& ems, const int* frames, const
     GTNX_PROF("asg_score", fwd_pair * double(pairs));
     launch_asg_score_forward(a, rt.stream());
   } else {
-    const int64_t per_pair = std::max<int64_t>(int64_t(maxT), 1) * U;  // floats
-    const int64_t cap = scratch_cap("GTNX_ASG_SCORE_SCRATCH_BYTES", kAsgScoreScratchCap);
-    const int64_t slice = std::max<int64_t>(1, cap / (4 * per_pair));
+    const int64_t per_pair = std::max<int64_t>(int64_t(fr.maxT), 1) * U;  // floats
     // (the scores and the occupancy sums outlive the slices: the table launch reads them)
     DevMemP sc = rt.alloc(size_t(4 * pairs));
     DevMemP occ;
@@ -903,8 +889,7 @@ void asg_score_impl(const char* who, const BatchP& ems, const int* frames, const
     a.scores = sc->as<float>();
     a.score0 = 0;
     a.pair_stride = per_pair;
-    for (int64_t p0 = 0; p0 < pairs; p0 += slice) {
-      const int64_t cnt = std::min(slice, pairs - p0);
+    for_pair_slices(pairs, 4 * per_pair, kAsgScoreScratch, [&](int64_t p0, int64_t cnt) {
       DevMemP rows = rt.alloc(size_t(4 * per_pair * cnt));
       a.alpha = rows->as<float>();
       a.pair0 = p0;
@@ -923,7 +908,7 @@ void asg_score_impl(const char* who, const BatchP& ems, const int* frames, const
         launch_asg_score_scatter(a, rt.stream());
       }
       // (the rows go back to the stream-ordered pool behind the launches)
-    }
+    });
     if (grad_table_dev) {
       GTNX_PROF("asg_score_table", (4.0 * width * double(x.C + 1) + 8.0 * width + 12.0) * double(pairs) +
                                        4.0 * double(x.C) * double(x.C + 1));
@@ -940,7 +925,7 @@ void batch_asg_score(const BatchP& ems, const int* frames, const float* table_de
                      int64_t row_stride, const int* lengths_dev, int N, int L, int max_length, float* scores_dev) {
   GTNX_HOST_T("batch.asg_score");
   if (!scores_dev) throw_invalid("[gtnx_batch_asg_score] null scores pointer");
-  asg_score_impl("gtnx_batch_asg_score", ems, frames, table_dev, tokens_dev, row_stride, lengths_dev, N, L, max_length,
+  asg_score_impl("gtnx_batch_asg_score", ems, frames, table_dev, {tokens_dev, row_stride, lengths_dev, N, L, max_length},
                  scores_dev, nullptr, nullptr, nullptr);
 }
 
@@ -948,8 +933,8 @@ void batch_asg_score_grad(const BatchP& ems, const int* frames, const float* tab
                           int64_t row_stride, const int* lengths_dev, int N, int L, int max_length,
                           const float* weights_dev, float* grad_em_dev, float* grad_table_dev) {
   GTNX_HOST_T("batch.asg_score_grad");
-  asg_score_impl("gtnx_batch_asg_score_grad", ems, frames, table_dev, tokens_dev, row_stride, lengths_dev, N, L,
-                 max_length, nullptr, weights_dev, grad_em_dev, grad_table_dev);
+  asg_score_impl("gtnx_batch_asg_score_grad", ems, frames, table_dev,
+                 {tokens_dev, row_stride, lengths_dev, N, L, max_length}, nullptr, weights_dev, grad_em_dev, grad_table_dev);
 }
 
 }  // namespace gtnx

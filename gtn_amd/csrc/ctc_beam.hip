@@ -46,11 +46,11 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "pair_kernels.h"
 
 namespace gtnx {
 namespace {
 
-constexpr float NEG_INF = -__builtin_inff();
 constexpr int kRowBlock = 256;  // threads of a row-kernel workgroup
 constexpr int kRowTrips = 4;    // rows each lane group takes, one after the other
 constexpr int kMaxBeam = 64;
@@ -140,13 +140,6 @@ __global__ __launch_bounds__(kRowBlock) void ctc_beam_rows_kernel(CtcBeamArgs a)
       a.ent_cnt[row] = count;
     }
   }
-}
-
-__device__ __forceinline__ float logadd(float x, float y) {
-  if (x == NEG_INF) return y;
-  if (y == NEG_INF) return x;
-  const float m = fmaxf(x, y), n = fminf(x, y);
-  return m + log1pf(expf(n - m));
 }
 
 // a float as 32 bits that rise as the float falls (-0 counts as +0), and back

@@ -32,37 +32,10 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "pair_kernels.h"
 
 namespace gtnx {
 namespace {
-
-constexpr float NEG_INF = -__builtin_inff();
-
-__device__ __forceinline__ float logadd(float x, float y) {
-  if (x == NEG_INF) return y;
-  if (y == NEG_INF) return x;
-  const float m = fmaxf(x, y), n = fminf(x, y);
-  return m + log1pf(expf(n - m));
-}
-
-// the workgroup's barrier; a workgroup of one wave needs its LDS and global accesses ordered, nothing more
-template <int WG>
-__device__ __forceinline__ void wg_sync() {
-  if (WG > 64) {
-    __syncthreads();
-  } else {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-// ... that also tells every lane whether any lane holds a non-zero `v`
-template <int WG>
-__device__ __forceinline__ bool wg_any(int v) {
-  if (WG > 64) return __syncthreads_or(v) != 0;
-  const bool r = __ballot(v != 0) != 0;
-  wg_sync<WG>();
-  return r;
-}
 
 // what a lane keeps of its states: s = tid + j * WG
 template <int PER>
@@ -348,25 +321,14 @@ void ctc_score_config(int U, int* width, int* per_lane) {
   if (per_lane) *per_lane = per;
 }
 
-#define GTNX_CTC_SCORE_DISPATCH(fn)                \
-  int wg, per;                                     \
-  ctc_score_config(a.U, &wg, &per);                \
-  if (wg == 64) fn<64, 1>(a, st);                  \
-  else if (wg == 256 && per == 1) fn<256, 1>(a, st); \
-  else if (wg == 256) fn<256, 3>(a, st);           \
-  else if (per == 1) fn<1024, 1>(a, st);           \
-  else if (per == 2) fn<1024, 2>(a, st);           \
-  else if (per == 4) fn<1024, 4>(a, st);           \
-  else fn<1024, 9>(a, st);
-
 void launch_ctc_score_forward(const CtcScoreArgs& a, hipStream_t st) {
   if (a.count <= 0) return;
-  GTNX_CTC_SCORE_DISPATCH(launch_forward)
+  GTNX_CTC_SCORE_DISPATCH(a.U, launch_forward, a, st);
 }
 
 void launch_ctc_score_backward(const CtcScoreArgs& a, hipStream_t st) {
   if (a.count <= 0) return;
-  GTNX_CTC_SCORE_DISPATCH(launch_backward)
+  GTNX_CTC_SCORE_DISPATCH(a.U, launch_backward, a, st);
 }
 
 }  // namespace gtnx

@@ -42,22 +42,10 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "pair_kernels.h"
 
 namespace gtnx {
 namespace {
-
-constexpr float NEG_INF = -__builtin_inff();
-
-// the workgroup's barrier; a workgroup of one wave needs its LDS and global accesses ordered, nothing more
-template <int WG>
-__device__ __forceinline__ void wg_sync() {
-  if (WG > 64) {
-    __syncthreads();
-  } else {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-  }
-}
 
 // position of state m in the reference's queue (align.hip queue_rank, with the skip flag read from the tokens)
 __device__ __forceinline__ int queue_rank(int m, int S, int p, const GTNX_G int* tok) {
@@ -319,15 +307,7 @@ void launch(const CtcTokenAlignArgs& a, hipStream_t st) {
 
 void launch_ctc_token_align(const CtcTokenAlignArgs& a, hipStream_t st) {
   if (a.count <= 0) return;
-  int wg, per;
-  ctc_score_config(a.U, &wg, &per);
-  if (wg == 64) launch<64, 1>(a, st);
-  else if (wg == 256 && per == 1) launch<256, 1>(a, st);
-  else if (wg == 256) launch<256, 3>(a, st);
-  else if (per == 1) launch<1024, 1>(a, st);
-  else if (per == 2) launch<1024, 2>(a, st);
-  else if (per == 4) launch<1024, 4>(a, st);
-  else launch<1024, 9>(a, st);
+  GTNX_CTC_SCORE_DISPATCH(a.U, launch, a, st);
 }
 
 }  // namespace gtnx

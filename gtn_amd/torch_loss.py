@@ -102,6 +102,16 @@ def _engine_done(stream):
         gtn.synchronize()
 
 
+def _route(stream, x, native, symbol, args, method, *margs, **mkw):
+    """the tail of a device-output function over the slabs x [B, T, C]: where `native` says so `symbol` of
+    libgtn_criteria.so with (x, B, T, C, *args), else `method` of the linear batch that borrows x; then _engine_done"""
+    if native:
+        _call(symbol, x.data_ptr(), *x.shape, *args)
+    else:
+        getattr(gtn.Batch.linear(*x.shape, x, calc_grad=False, borrow=True), method)(*margs, **mkw)
+    _engine_done(stream)
+
+
 def _asg_weights(start, transitions):
     """[N + N*N] in the arc order of gtn::criteria::asgTransitions: N start arcs, then arc N + i*N + j = j -> i"""
     return torch.cat([start.detach().reshape(-1), transitions.detach().reshape(-1)]).to(torch.float32).contiguous()
@@ -245,6 +255,43 @@ def _frame_counts(name, input_lengths, B, T, low):
     if B and low is not None and (int(frames.min()) < low or int(frames.max()) > T):
         raise ValueError(f"{name}: an input length outside {low} .. {T}")
     return frames
+
+
+def _hypothesis_args(who, computed, x, x_name, tokens, lengths, blank, input_lengths, max_length, own_checks=None):
+    """What `ctc_score`, `asg_score` and `ctc_token_align` check and normalise alike.  `x`: the emissions, `x_name` in
+    the texts; `computed`: what the texts say the device computes; `blank`: None where there is none; `own_checks(C)`:
+    the caller's own value checks, which return the (tensor or None, name) pairs that have to be on x's device as well.
+    Returns (B, T, C, N, L, flat, tok, ln, frames, max_length): `flat` says tokens was [B, L]; tok is int32 [B, N, L]
+    with an address, ln int32 [B, N], frames the host counts or None."""
+    if not (torch.is_tensor(x) and x.dim() == 3 and x.dtype == torch.float32):
+        raise ValueError(f"{who}: {x_name} must be a float32 tensor [B, T, C]")
+    B, T, C_ = x.shape
+    if not (torch.is_tensor(tokens) and tokens.dtype == torch.int32 and tokens.dim() in (2, 3) and tokens.shape[0] == B):
+        raise ValueError(f"{who}: tokens must be an int32 tensor [B, N, L] or [B, L] for a batch of {B}")
+    flat = tokens.dim() == 2
+    N, L = (1, tokens.shape[1]) if flat else tokens.shape[1:]
+    shape = (B,) if flat else (B, N)
+    if not (torch.is_tensor(lengths) and lengths.dtype in (torch.int32, torch.int64) and tuple(lengths.shape) == shape):
+        raise ValueError(f"{who}: lengths must be an int32 or int64 tensor {list(shape)}")
+    if blank is not None and not 0 <= blank < C_:
+        raise ValueError(f"{who}: blank must be one of the {C_} labels")
+    max_length = max(1, min(L, T, 4096)) if max_length is None else int(max_length)
+    if not 1 <= max_length <= 4096:
+        raise ValueError(f"{who}: max_length outside 1 .. 4096")
+    frames = None if input_lengths is None else _frame_counts(who, input_lengths, B, T, 0)
+    more = own_checks(C_) if own_checks else ()
+    for t, what in ((x, x_name), *more, (tokens, "tokens"), (lengths, "lengths")):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {what} must be a CUDA tensor (the {computed} are computed on the device)")
+        if t.device != x.device:
+            raise ValueError(f"{who}: all tensors must be on one device")
+    tok = tokens.detach().reshape(B, N, L).contiguous()
+    if B * N and tok.numel() == 0:
+        tok = tok.new_empty(B, N, 1)[:, :, :0]  # (rows without an element are never read, but they need an address)
+    ln = lengths.detach().to(torch.int32).reshape(B, N).contiguous()  # (int64 lengths are converted on the device)
+    return B, T, C_, N, L, flat, tok, ln, frames, max_length
 
 
 def ctc_loss(log_probs, targets, blank=0, reduction="none", input_lengths=None):
@@ -516,13 +563,9 @@ def ctc_decode(log_probs, blank=0, input_lengths=None, collapse=True):
     tokens = torch.empty(B, T, dtype=torch.int32, device=x.device) if collapse else None
     starts = torch.empty(B, T, dtype=torch.int32, device=x.device) if collapse else None
     lengths = torch.empty(B, dtype=torch.int32, device=x.device) if collapse else None
-    if _has_native("ctc_decode", "gtn_ctc_decode_n"):
-        _call("gtn_ctc_decode_n", x.data_ptr(), B, T, N, blank, _host_ptr(frames), labels.data_ptr(), scores.data_ptr(),
-              _ptr(tokens), _ptr(starts), _ptr(lengths))
-    else:
-        ems = gtn.Batch.linear(B, T, N, x, calc_grad=False, borrow=True)
-        ems.linear_decode(labels, scores, frames, blank, tokens, starts, lengths, row_stride=T)
-    _engine_done(stream)
+    _route(stream, x, _has_native("ctc_decode", "gtn_ctc_decode_n"), "gtn_ctc_decode_n",
+           (blank, _host_ptr(frames), labels.data_ptr(), scores.data_ptr(), _ptr(tokens), _ptr(starts), _ptr(lengths)),
+           "linear_decode", labels, scores, frames, blank, tokens, starts, lengths, row_stride=T)
     return (labels, scores, tokens, starts, lengths) if collapse else (labels, scores)
 
 
@@ -587,23 +630,16 @@ def ctc_beam_decode(log_probs, blank=0, input_lengths=None, beam_size=16, cutoff
     scores = torch.empty(B, nbest, dtype=torch.float32, device=x.device)
     if table is not None:
         am = torch.empty(B, nbest, dtype=torch.float32, device=x.device) if return_am_scores else None
-        if _has_native("ctc_beam_decode", "gtn_ctc_beam_decode_lm_n"):
-            _call("gtn_ctc_beam_decode_lm_n", x.data_ptr(), B, T, N, blank, _host_ptr(frames), beam_size, cutoff_top_n,
-                  nbest, table.data_ptr(), lm_weight, insertion_bonus, tokens.data_ptr(), lengths.data_ptr(),
-                  scores.data_ptr(), _ptr(am))
-        else:
-            ems = gtn.Batch.linear(B, T, N, x, calc_grad=False, borrow=True)
-            ems.ctc_beam_decode(tokens, lengths, scores, frames, blank, beam_size, cutoff_top_n, nbest, row_stride=T,
-                                lm=table, lm_weight=lm_weight, insertion_bonus=insertion_bonus, am_scores_out=am)
-        _engine_done(stream)
+        _route(stream, x, _has_native("ctc_beam_decode", "gtn_ctc_beam_decode_lm_n"), "gtn_ctc_beam_decode_lm_n",
+               (blank, _host_ptr(frames), beam_size, cutoff_top_n, nbest, table.data_ptr(), lm_weight, insertion_bonus,
+                tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr(), _ptr(am)),
+               "ctc_beam_decode", tokens, lengths, scores, frames, blank, beam_size, cutoff_top_n, nbest, row_stride=T,
+               lm=table, lm_weight=lm_weight, insertion_bonus=insertion_bonus, am_scores_out=am)
         return (tokens, lengths, scores, am) if return_am_scores else (tokens, lengths, scores)
-    if _has_native("ctc_beam_decode", "gtn_ctc_beam_decode_n"):
-        _call("gtn_ctc_beam_decode_n", x.data_ptr(), B, T, N, blank, _host_ptr(frames), beam_size, cutoff_top_n, nbest,
-              tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr())
-    else:
-        ems = gtn.Batch.linear(B, T, N, x, calc_grad=False, borrow=True)
-        ems.ctc_beam_decode(tokens, lengths, scores, frames, blank, beam_size, cutoff_top_n, nbest, row_stride=T)
-    _engine_done(stream)
+    _route(stream, x, _has_native("ctc_beam_decode", "gtn_ctc_beam_decode_n"), "gtn_ctc_beam_decode_n",
+           (blank, _host_ptr(frames), beam_size, cutoff_top_n, nbest, tokens.data_ptr(), lengths.data_ptr(),
+            scores.data_ptr()),
+           "ctc_beam_decode", tokens, lengths, scores, frames, blank, beam_size, cutoff_top_n, nbest, row_stride=T)
     return tokens, lengths, scores
 
 
@@ -669,21 +705,18 @@ class _CTCScore(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, log_probs, tokens, lengths, blank, frames, max_length):
-        B, T, C_ = log_probs.shape
-        N, L = tokens.shape[1], tokens.shape[2]
+        B, N, L = tokens.shape
         x = log_probs.detach().contiguous()
         stream = _engine_stream(x.device)
         scores = torch.empty(B, N, dtype=torch.float32, device=x.device)
         if B * N == 0:
-            pass  # (no pair: nothing to launch, and an empty tensor has no address to hand over)
-        elif _has_native("ctc_score", "gtn_ctc_score_n"):
-            _call("gtn_ctc_score_n", x.data_ptr(), B, T, C_, blank, _host_ptr(frames), tokens.data_ptr(),
-                  lengths.data_ptr(), N, L, max_length, scores.data_ptr())
+            _engine_done(stream)  # (no pair: nothing to launch, and an empty tensor has no address to hand over)
         else:
-            ems = gtn.Batch.linear(B, T, C_, x, calc_grad=False, borrow=True)
-            ems.ctc_score(tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr(), frames, blank, max_length, N=N, L=L,
-                          row_stride=L)
-        _engine_done(stream)
+            _route(stream, x, _has_native("ctc_score", "gtn_ctc_score_n"), "gtn_ctc_score_n",
+                   (blank, _host_ptr(frames), tokens.data_ptr(), lengths.data_ptr(), N, L, max_length,
+                    scores.data_ptr()),
+                   "ctc_score", tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr(), frames, blank, max_length,
+                   N=N, L=L, row_stride=L)
         ctx.save_for_backward(x, tokens, lengths)
         ctx.args = (blank, frames, max_length)
         return scores
@@ -699,14 +732,11 @@ class _CTCScore(torch.autograd.Function):
         w = grad_out.detach().to(torch.float32).contiguous()
         stream = _engine_stream(x.device)
         grad = torch.empty(B, T, C_, dtype=torch.float32, device=x.device)
-        if _native():
-            _call("gtn_ctc_score_grad_n", x.data_ptr(), B, T, C_, blank, _host_ptr(frames), tokens.data_ptr(),
-                  lengths.data_ptr(), N, L, max_length, w.data_ptr(), grad.data_ptr())
-        else:
-            ems = gtn.Batch.linear(B, T, C_, x, calc_grad=False, borrow=True)
-            ems.ctc_score_grad(tokens.data_ptr(), lengths.data_ptr(), w.data_ptr(), grad.data_ptr(), frames, blank,
-                               max_length, N=N, L=L, row_stride=L)
-        _engine_done(stream)
+        _route(stream, x, _native(), "gtn_ctc_score_grad_n",
+               (blank, _host_ptr(frames), tokens.data_ptr(), lengths.data_ptr(), N, L, max_length, w.data_ptr(),
+                grad.data_ptr()),
+               "ctc_score_grad", tokens.data_ptr(), lengths.data_ptr(), w.data_ptr(), grad.data_ptr(), frames, blank,
+               max_length, N=N, L=L, row_stride=L)
         return grad, None, None, None, None, None
 
 
@@ -732,32 +762,9 @@ def ctc_score(log_probs, tokens, lengths, blank=0, input_lengths=None, max_lengt
     needs (the node keeps tensors only), skips pairs whose score is -inf or whose incoming gradient is exactly 0, and
     sums in a fixed order without atomics, so it has the same bits run to run.  Without requires_grad it never launches.
     Runs on the caller's stream."""
-    if not (torch.is_tensor(log_probs) and log_probs.dim() == 3 and log_probs.dtype == torch.float32):
-        raise ValueError("ctc_score: log_probs must be a float32 tensor [B, T, C]")
-    B, T, C_ = log_probs.shape
-    if not (torch.is_tensor(tokens) and tokens.dtype == torch.int32 and tokens.dim() in (2, 3) and tokens.shape[0] == B):
-        raise ValueError(f"ctc_score: tokens must be an int32 tensor [B, N, L] or [B, L] for a batch of {B}")
-    flat = tokens.dim() == 2
-    N, L = (1, tokens.shape[1]) if flat else tokens.shape[1:]
-    shape = (B,) if flat else (B, N)
-    if not (torch.is_tensor(lengths) and lengths.dtype in (torch.int32, torch.int64) and tuple(lengths.shape) == shape):
-        raise ValueError(f"ctc_score: lengths must be an int32 or int64 tensor {list(shape)}")
     blank = int(blank)
-    if not 0 <= blank < C_:
-        raise ValueError(f"ctc_score: blank must be one of the {C_} labels")
-    max_length = max(1, min(L, T, 4096)) if max_length is None else int(max_length)
-    if not 1 <= max_length <= 4096:
-        raise ValueError("ctc_score: max_length outside 1 .. 4096")
-    frames = None if input_lengths is None else _frame_counts("ctc_score", input_lengths, B, T, 0)
-    for t, what in ((log_probs, "log_probs"), (tokens, "tokens"), (lengths, "lengths")):
-        if not t.is_cuda:
-            raise RuntimeError(f"ctc_score: {what} must be a CUDA tensor (the scores are computed on the device)")
-        if t.device != log_probs.device:
-            raise ValueError("ctc_score: all tensors must be on one device")
-    tok = tokens.detach().reshape(B, N, L).contiguous()
-    if B * N and tok.numel() == 0:
-        tok = tok.new_empty(B, N, 1)[:, :, :0]  # (rows without an element are never read, but they need an address)
-    ln = lengths.detach().to(torch.int32).reshape(B, N).contiguous()  # (int64 lengths are converted on the device)
+    B, _, _, _, _, flat, tok, ln, frames, max_length = _hypothesis_args(
+        "ctc_score", "scores", log_probs, "log_probs", tokens, lengths, blank, input_lengths, max_length)
     out = _CTCScore.apply(log_probs, tok, ln, blank, frames, max_length)
     return out.reshape(B) if flat else out
 
@@ -769,22 +776,19 @@ class _ASGScore(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, emissions, transitions, start, tokens, lengths, frames, max_length):
-        B, T, C_ = emissions.shape
-        N, L = tokens.shape[1], tokens.shape[2]
+        B, N, L = tokens.shape
         x = emissions.detach().contiguous()
         table = _asg_weights(start, transitions)
         stream = _engine_stream(x.device)
         scores = torch.empty(B, N, dtype=torch.float32, device=x.device)
         if B * N == 0:
-            pass  # (no pair: nothing to launch, and an empty tensor has no address to hand over)
-        elif _has_native("asg_score", "gtn_asg_score_n"):
-            _call("gtn_asg_score_n", x.data_ptr(), B, T, C_, table.data_ptr(), _host_ptr(frames), tokens.data_ptr(),
-                  lengths.data_ptr(), N, L, max_length, scores.data_ptr())
+            _engine_done(stream)  # (no pair: nothing to launch, and an empty tensor has no address to hand over)
         else:
-            ems = gtn.Batch.linear(B, T, C_, x, calc_grad=False, borrow=True)
-            ems.asg_score(table.data_ptr(), tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr(), frames, max_length,
-                          N=N, L=L, row_stride=L)
-        _engine_done(stream)
+            _route(stream, x, _has_native("asg_score", "gtn_asg_score_n"), "gtn_asg_score_n",
+                   (table.data_ptr(), _host_ptr(frames), tokens.data_ptr(), lengths.data_ptr(), N, L, max_length,
+                    scores.data_ptr()),
+                   "asg_score", table.data_ptr(), tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr(), frames,
+                   max_length, N=N, L=L, row_stride=L)
         ctx.save_for_backward(x, table, tokens, lengths)
         ctx.args = (frames, max_length, transitions.dtype, start.dtype)
         return scores
@@ -807,15 +811,11 @@ class _ASGScore(torch.autograd.Function):
                     g.zero_()
         else:
             w = grad_out.detach().to(torch.float32).contiguous()
-            stream = _engine_stream(x.device)
-            if _native():
-                _call("gtn_asg_score_grad_n", x.data_ptr(), B, T, C_, table.data_ptr(), _host_ptr(frames),
-                      tokens.data_ptr(), lengths.data_ptr(), N, L, max_length, w.data_ptr(), _ptr(grad), _ptr(g_table))
-            else:
-                ems = gtn.Batch.linear(B, T, C_, x, calc_grad=False, borrow=True)
-                ems.asg_score_grad(table.data_ptr(), tokens.data_ptr(), lengths.data_ptr(), w.data_ptr(), _ptr(grad),
-                                   _ptr(g_table), frames, max_length, N=N, L=L, row_stride=L)
-            _engine_done(stream)
+            _route(_engine_stream(x.device), x, _native(), "gtn_asg_score_grad_n",
+                   (table.data_ptr(), _host_ptr(frames), tokens.data_ptr(), lengths.data_ptr(), N, L, max_length,
+                    w.data_ptr(), _ptr(grad), _ptr(g_table)),
+                   "asg_score_grad", table.data_ptr(), tokens.data_ptr(), lengths.data_ptr(), w.data_ptr(), _ptr(grad),
+                   _ptr(g_table), frames, max_length, N=N, L=L, row_stride=L)
         g_tr = g_table[C_:].reshape(C_, C_).to(tr_dtype) if ctx.needs_input_grad[1] else None
         g_st = g_table[:C_].to(st_dtype) if ctx.needs_input_grad[2] else None
         return grad, g_tr, g_st, None, None, None, None
@@ -843,40 +843,18 @@ def asg_score(emissions, transitions, tokens, lengths, start=None, input_lengths
     whose score is -inf or whose incoming gradient is exactly 0, and sums in a fixed order without atomics, so it has the
     same bits run to run.  A non-uniform grad_out is fine: this is the case `asg_loss(reduction="none")` refuses.  Without
     requires_grad it never launches.  Runs on the caller's stream."""
-    if not (torch.is_tensor(emissions) and emissions.dim() == 3 and emissions.dtype == torch.float32):
-        raise ValueError("asg_score: emissions must be a float32 tensor [B, T, C]")
-    B, T, C_ = emissions.shape
-    if not (torch.is_tensor(transitions) and tuple(transitions.shape) == (C_, C_)):
-        raise ValueError(f"asg_score: transitions must be [{C_}, {C_}]")
-    if start is not None and not (torch.is_tensor(start) and tuple(start.shape) == (C_,)):
-        raise ValueError(f"asg_score: start must be [{C_}]")
-    if not (torch.is_tensor(tokens) and tokens.dtype == torch.int32 and tokens.dim() in (2, 3) and tokens.shape[0] == B):
-        raise ValueError(f"asg_score: tokens must be an int32 tensor [B, N, L] or [B, L] for a batch of {B}")
-    flat = tokens.dim() == 2
-    N, L = (1, tokens.shape[1]) if flat else tokens.shape[1:]
-    shape = (B,) if flat else (B, N)
-    if not (torch.is_tensor(lengths) and lengths.dtype in (torch.int32, torch.int64) and tuple(lengths.shape) == shape):
-        raise ValueError(f"asg_score: lengths must be an int32 or int64 tensor {list(shape)}")
-    if C_ < 1 or C_ > 16384:
-        raise ValueError("asg_score: the number of labels must be 1 .. 16384")
-    max_length = max(1, min(L, T, 4096)) if max_length is None else int(max_length)
-    if not 1 <= max_length <= 4096:
-        raise ValueError("asg_score: max_length outside 1 .. 4096")
-    frames = None if input_lengths is None else _frame_counts("asg_score", input_lengths, B, T, 0)
-    for t, what in ((emissions, "emissions"), (transitions, "transitions"), (start, "start"), (tokens, "tokens"),
-                    (lengths, "lengths")):
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError(f"asg_score: {what} must be a CUDA tensor (the scores are computed on the device)")
-        if t.device != emissions.device:
-            raise ValueError("asg_score: all tensors must be on one device")
+    def tables(C_):
+        if not (torch.is_tensor(transitions) and tuple(transitions.shape) == (C_, C_)):
+            raise ValueError(f"asg_score: transitions must be [{C_}, {C_}]")
+        if start is not None and not (torch.is_tensor(start) and tuple(start.shape) == (C_,)):
+            raise ValueError(f"asg_score: start must be [{C_}]")
+        if C_ < 1 or C_ > 16384:
+            raise ValueError("asg_score: the number of labels must be 1 .. 16384")
+        return (transitions, "transitions"), (start, "start")
+    B, _, C_, _, _, flat, tok, ln, frames, max_length = _hypothesis_args(
+        "asg_score", "scores", emissions, "emissions", tokens, lengths, None, input_lengths, max_length, tables)
     if start is None:
         start = torch.zeros(C_, dtype=torch.float32, device=emissions.device)
-    tok = tokens.detach().reshape(B, N, L).contiguous()
-    if B * N and tok.numel() == 0:
-        tok = tok.new_empty(B, N, 1)[:, :, :0]  # (rows without an element are never read, but they need an address)
-    ln = lengths.detach().to(torch.int32).reshape(B, N).contiguous()  # (int64 lengths are converted on the device)
     out = _ASGScore.apply(emissions, transitions, start, tok, ln, frames, max_length)
     return out.reshape(B) if flat else out
 
@@ -903,32 +881,10 @@ def ctc_token_align(log_probs, tokens, lengths, blank=0, input_lengths=None, max
     hypothesis (length 0) aligns as the empty sequence: a finite score and rows of -1.  Float32 max-plus arithmetic with
     exact ties decided as `ctc_forced_align` decides them: the same bits every time.  No autograd.  Runs on the caller's
     stream."""
-    who = "ctc_token_align"
-    if not (torch.is_tensor(log_probs) and log_probs.dim() == 3 and log_probs.dtype == torch.float32):
-        raise ValueError(f"{who}: log_probs must be a float32 tensor [B, T, C]")
-    B, T, C_ = log_probs.shape
-    if not (torch.is_tensor(tokens) and tokens.dtype == torch.int32 and tokens.dim() in (2, 3) and tokens.shape[0] == B):
-        raise ValueError(f"{who}: tokens must be an int32 tensor [B, N, L] or [B, L] for a batch of {B}")
-    flat = tokens.dim() == 2
-    N, L = (1, tokens.shape[1]) if flat else tokens.shape[1:]
-    shape = (B,) if flat else (B, N)
-    if not (torch.is_tensor(lengths) and lengths.dtype in (torch.int32, torch.int64) and tuple(lengths.shape) == shape):
-        raise ValueError(f"{who}: lengths must be an int32 or int64 tensor {list(shape)}")
     blank = int(blank)
-    if not 0 <= blank < C_:
-        raise ValueError(f"{who}: blank must be one of the {C_} labels")
-    max_length = max(1, min(L, T, 4096)) if max_length is None else int(max_length)
-    if not 1 <= max_length <= 4096:
-        raise ValueError(f"{who}: max_length outside 1 .. 4096")
-    frames = None if input_lengths is None else _frame_counts(who, input_lengths, B, T, 0)
-    for t, what in ((log_probs, "log_probs"), (tokens, "tokens"), (lengths, "lengths")):
-        if not t.is_cuda:
-            raise RuntimeError(f"{who}: {what} must be a CUDA tensor (the alignments are computed on the device)")
-        if t.device != log_probs.device:
-            raise ValueError(f"{who}: all tensors must be on one device")
+    B, T, _, N, L, flat, tok, ln, frames, max_length = _hypothesis_args(
+        "ctc_token_align", "alignments", log_probs, "log_probs", tokens, lengths, blank, input_lengths, max_length)
     x = log_probs.detach().contiguous()
-    tok = tokens.detach().reshape(B, N, L).contiguous()
-    ln = lengths.detach().to(torch.int32).reshape(B, N).contiguous()  # (int64 lengths are converted on the device)
     stream = _engine_stream(x.device)
     # (rows without an element are never written, but they need an address: a width of at least 1 behind the views)
     W, F = max(L, 1), max(T, 1)
@@ -940,16 +896,14 @@ def ctc_token_align(log_probs, tokens, lengths, blank=0, input_lengths=None, max
     if tok.numel() == 0:
         tok = tok.new_empty(B, N, 1)
     if B * N == 0:
-        pass  # (no pair: nothing to launch, and an empty tensor has no address to hand over)
-    elif L == W and T == F and _has_native(who, "gtn_ctc_token_align_n", python_route=True):
-        _call("gtn_ctc_token_align_n", x.data_ptr(), B, T, C_, blank, _host_ptr(frames), tok.data_ptr(), ln.data_ptr(), N,
-              L, max_length, scores.data_ptr(), starts.data_ptr(), ends.data_ptr(), _ptr(tsc), _ptr(ftk))
+        _engine_done(stream)  # (no pair: nothing to launch, and an empty tensor has no address to hand over)
     else:
-        ems = gtn.Batch.linear(B, T, C_, x, calc_grad=False, borrow=True)
-        ems.ctc_token_align(tok.data_ptr(), ln.data_ptr(), scores.data_ptr(), starts.data_ptr(), ends.data_ptr(),
-                            _ptr(tsc), _ptr(ftk), frames, blank, max_length, N=N, L=L, row_stride=W, out_stride=W,
-                            frame_stride=F)
-    _engine_done(stream)
+        native = L == W and T == F and _has_native("ctc_token_align", "gtn_ctc_token_align_n", python_route=True)
+        _route(stream, x, native, "gtn_ctc_token_align_n",
+               (blank, _host_ptr(frames), tok.data_ptr(), ln.data_ptr(), N, L, max_length, scores.data_ptr(),
+                starts.data_ptr(), ends.data_ptr(), _ptr(tsc), _ptr(ftk)),
+               "ctc_token_align", tok.data_ptr(), ln.data_ptr(), scores.data_ptr(), starts.data_ptr(), ends.data_ptr(),
+               _ptr(tsc), _ptr(ftk), frames, blank, max_length, N=N, L=L, row_stride=W, out_stride=W, frame_stride=F)
     out = [scores, starts[:, :, :L], ends[:, :, :L]]
     if return_token_scores:
         out.append(tsc[:, :, :L])
