@@ -825,6 +825,60 @@ def make_api(lib):
                                                _opt_ptr(scores_out), _opt_ptr(collapsed_out), _opt_ptr(starts_out),
                                                _opt_ptr(lengths_out)))
 
+        def _nbest_outputs(self, who, tokens_out, nbest, row_stride, flat):
+            """the row stride of the [B, nbest, >= M] token rows of a beam search, with the outputs checked where they are
+            tensors; `flat`: (tensor, dtype, text) of its [B, nbest] outputs"""
+            n = len(self)
+            stride = row_stride
+            t = tokens_out
+            if t is not None and hasattr(t, "data_ptr"):
+                if (str(t.dtype) != "torch.int32" or t.dim() != 3 or t.shape[0] < n or t.shape[1] != int(nbest)
+                        or (t.shape[2] > 1 and t.stride(2) != 1) or (n > 1 and t.stride(0) != t.shape[1] * t.stride(1))):
+                    raise ValueError(f"{who}: tokens_out must be an int32 tensor [B, nbest, M] with contiguous "
+                                     "rows, equally spaced")
+                if stride is not None and t.stride(1) != stride:
+                    raise ValueError(f"{who}: row_stride is not the row stride of tokens_out")
+                stride = t.stride(1)
+                m, c = C.c_int(-1), C.c_int(-1)
+                check(lib.gtnx_batch_linear_shape(self._h, C.byref(m), C.byref(c)))
+                if t.shape[2] < m.value:  # (the kernel writes M entries of every row, whatever lies behind a view)
+                    raise ValueError(f"{who}: tokens_out has rows of {t.shape[2]} entries, the batch has "
+                                     f"{m.value} rows")
+            if stride is None:
+                raise ValueError(f"{who}: a device address needs row_stride")
+            for o, dt, what in flat:
+                if o is not None and hasattr(o, "data_ptr") and (str(o.dtype) != dt or not o.is_contiguous()
+                                                                 or o.numel() < n * int(nbest)):
+                    raise ValueError(f"{who}: {what} contiguous tensor [B, nbest]")
+            return stride
+
+        def asg_beam_decode(self, tokens_out, lengths_out, scores_out, frames, table, beam_size=16, cutoff_top_n=16,
+                            nbest=1, row_stride=None):
+            """ASG prefix beam search with N-best output over a Batch.linear, results left on the device
+            (gtnx_batch_asg_beam_decode; DESIGN section 27 holds the contract).  The hypotheses are the label sequences
+            without equal neighbours -- what `viterbi_decode`'s collapsed rows can hold -- each summed over all of its
+            alignments under emissions o transitions: unpruned, a hypothesis's score is `asg_score` of its tokens.
+            `tokens_out` (int32 CUDA tensor [B, nbest, >= M] with contiguous rows, or a device address of
+            [B][nbest][row_stride]) gets the labels of the `nbest` best of every utterance, best first, -1 from each
+            one's length to the row's width M; `lengths_out` (int32 [B, nbest]) their lengths; `scores_out` (float32
+            [B, nbest]) their log scores.  Slots without a hypothesis (fewer than nbest prefixes, a frame with nothing
+            above -inf, T_b = 0): -1, 0, -inf.  `table`: float32 CUDA tensor [C + C * C] or a device address -- entry c
+            is start[c], entry C + i * C + j is transitions[i, j], label j followed by label i
+            (`torch_loss._asg_weights(start, transitions)`, the table `asg_score` takes); an entry that is not finite
+            forbids its bigram or first label.  `beam_size` 1 .. 64 prefixes are kept, a frame offers its `cutoff_top_n`
+            (1 .. 32) best labels, for stays as well as extensions; `frames`: T_b per element (0 .. M, at most the rows
+            the batch carries; None: those rows).  Two launches with no copy back and no wait; rows from T_b on are never
+            read.  Any batch but a Batch.linear is an error: there is no other route."""
+            n = len(self)
+            table = self._asg_score_table("asg_beam_decode", table)
+            stride = self._nbest_outputs("asg_beam_decode", tokens_out, nbest, row_stride,
+                                         ((lengths_out, "torch.int32", "lengths_out must be an int32"),
+                                          (scores_out, "torch.float32", "scores_out must be a float32")))
+            fr, fr_ptr = _frames_arg("asg_beam_decode", frames, n)
+            check(lib.gtnx_batch_asg_beam_decode(self._h, fr_ptr, _opt_ptr(table), int(beam_size), int(cutoff_top_n),
+                                                 int(nbest), _opt_ptr(tokens_out), int(stride), _opt_ptr(lengths_out),
+                                                 _opt_ptr(scores_out)))
+
         def ctc_beam_decode(self, tokens_out, lengths_out, scores_out, frames=None, blank=0, beam_size=16,
                             cutoff_top_n=16, nbest=1, row_stride=None, lm=None, lm_weight=1.0, insertion_bonus=0.0,
                             am_scores_out=None):
@@ -856,29 +910,10 @@ def make_api(lib):
                 if c.value >= 0 and lm.numel() != c.value + c.value * c.value:
                     raise ValueError(f"ctc_beam_decode: lm has {lm.numel()} entries, {c.value} labels need "
                                      f"{c.value + c.value * c.value}")
-            stride = row_stride
-            t = tokens_out
-            if t is not None and hasattr(t, "data_ptr"):
-                if (str(t.dtype) != "torch.int32" or t.dim() != 3 or t.shape[0] < n or t.shape[1] != int(nbest)
-                        or (t.shape[2] > 1 and t.stride(2) != 1) or (n > 1 and t.stride(0) != t.shape[1] * t.stride(1))):
-                    raise ValueError("ctc_beam_decode: tokens_out must be an int32 tensor [B, nbest, M] with contiguous "
-                                     "rows, equally spaced")
-                if stride is not None and t.stride(1) != stride:
-                    raise ValueError("ctc_beam_decode: row_stride is not the row stride of tokens_out")
-                stride = t.stride(1)
-                m, c = C.c_int(-1), C.c_int(-1)
-                check(lib.gtnx_batch_linear_shape(self._h, C.byref(m), C.byref(c)))
-                if t.shape[2] < m.value:  # (the kernel writes M entries of every row, whatever lies behind a view)
-                    raise ValueError(f"ctc_beam_decode: tokens_out has rows of {t.shape[2]} entries, the batch has "
-                                     f"{m.value} rows")
-            if stride is None:
-                raise ValueError("ctc_beam_decode: a device address needs row_stride")
-            for o, dt, what in ((lengths_out, "torch.int32", "lengths_out must be an int32"),
-                                (scores_out, "torch.float32", "scores_out must be a float32"),
-                                (am_scores_out, "torch.float32", "am_scores_out must be a float32")):
-                if o is not None and hasattr(o, "data_ptr") and (str(o.dtype) != dt or not o.is_contiguous()
-                                                                 or o.numel() < n * int(nbest)):
-                    raise ValueError(f"ctc_beam_decode: {what} contiguous tensor [B, nbest]")
+            stride = self._nbest_outputs("ctc_beam_decode", tokens_out, nbest, row_stride,
+                                         ((lengths_out, "torch.int32", "lengths_out must be an int32"),
+                                          (scores_out, "torch.float32", "scores_out must be a float32"),
+                                          (am_scores_out, "torch.float32", "am_scores_out must be a float32")))
             fr, fr_ptr = _frames_arg("ctc_beam_decode", frames, n)
             if lm is not None:
                 check(lib.gtnx_batch_ctc_beam_decode_lm(self._h, fr_ptr, int(blank), int(beam_size), int(cutoff_top_n),
@@ -1246,6 +1281,11 @@ def make_api(lib):
         took (include/gtn_amd.h: gtnx_batch_asg_score_stats)"""
         return _stats2(lib.gtnx_batch_asg_score_stats)
 
+    def debug_asg_beam_stats():
+        """(calls, utterances): calls of Batch.asg_beam_decode that have launched so far and the utterances they decoded
+        (include/gtn_amd.h: gtnx_batch_asg_beam_stats)"""
+        return _stats2(lib.gtnx_batch_asg_beam_stats)
+
     def debug_edit_distance_stats():
         """(calls, pairs): calls of edit_distance that have launched so far and the pairs they computed
         (include/gtn_amd.h: gtnx_batch_edit_distance_stats)"""
@@ -1336,6 +1376,7 @@ def make_api(lib):
     ns.debug_ctc_score_stats = debug_ctc_score_stats
     ns.debug_ctc_token_align_stats = debug_ctc_token_align_stats
     ns.debug_asg_score_stats = debug_asg_score_stats
+    ns.debug_asg_beam_stats = debug_asg_beam_stats
     ns.edit_distance = edit_distance
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties

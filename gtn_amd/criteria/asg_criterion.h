@@ -215,5 +215,31 @@ inline void asgScoreBatch(
   }
 }
 
+/** ASG prefix beam search of a batch, N-best results on the device: per utterance the `nbest` best label sequences
+ *  without equal neighbours, each summed over all of its alignments under emissions o transitions (`tokensDev`, device
+ *  int32 [B][nbest][T], -1 from each length on; `lengthsDev`, device int32 [B][nbest]; `scoresDev`, device float32
+ *  [B][nbest]; slots without a hypothesis: -1, 0, -inf).  `emissions`: device float32 [B][T][N], read in place; `tableDev`
+ *  device float32 [N + N * N] in the arc order of asgTransitions (start scores, then arc N + i * N + j = j -> i);
+ *  `frames`: host [B] or null.  beamSize 1 .. 64, cutoffTopN 1 .. 32, nbest 1 .. beamSize.  gtnx_batch_asg_beam_decode
+ *  has the contract.  Nothing is copied back; the rows feed asgScoreBatch as they are. */
+inline void asgBeamDecodeBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int N,
+    const void* tableDev,
+    const int* frames,
+    int beamSize,
+    int cutoffTopN,
+    int nbest,
+    void* tokensDev,
+    void* lengthsDev,
+    void* scoresDev) {
+  Batch ems = Batch::linear(B, T, N, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  batched::asgBeamDecode(ems, static_cast<const float*>(tableDev), static_cast<int*>(tokensDev), T,
+                         static_cast<int*>(lengthsDev), static_cast<float*>(scoresDev), beamSize, cutoffTopN, nbest,
+                         frames);
+}
+
 } // namespace criteria
 } // namespace gtn

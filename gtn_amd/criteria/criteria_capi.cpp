@@ -242,6 +242,18 @@ GTN_EXPORT int gtn_asg_score_n(const void* emissions, int B, int T, int C, const
   });
 }
 
+// ASG prefix beam search with N-best output.  emissions: DEVICE float32 [B][T][C]; table: DEVICE float32 [C + C*C] as for
+// gtn_asg_score_n; frames: HOST int [B] or null; tokens: DEVICE int32 [B][nbest][T]; lengths: DEVICE int32 [B][nbest];
+// scores: DEVICE float32 [B][nbest].  The rows are what gtn_asg_score_n and gtn_edit_distance_n read.
+GTN_EXPORT int gtn_asg_beam_decode_n(const void* emissions, int B, int T, int C, const void* table, const int* frames,
+                                     int beam_size, int cutoff_top_n, int nbest, void* tokens, void* lengths,
+                                     void* scores) {
+  return guarded([&] {
+    gtn::criteria::asgBeamDecodeBatch(emissions, B, T, C, table, frames, beam_size, cutoff_top_n, nbest, tokens, lengths,
+                                      scores);
+  });
+}
+
 // ... and their gradients under weights: DEVICE float32 [B][N]: grad_em (DEVICE float32 [B][T][C], every element
 // written) and grad_table (DEVICE float32 [C + C*C], every entry written); either may be null, not both.
 GTN_EXPORT int gtn_asg_score_grad_n(const void* emissions, int B, int T, int C, const void* table, const int* frames,

@@ -200,6 +200,25 @@ struct CtcBeamLm {
 void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int beam, int topn, int nbest,
                            const CtcBeamLm* lm, int* tokens_dev, int64_t row_stride, int* lengths_dev, float* scores_dev);
 void batch_ctc_beam_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they decoded
+// ASG prefix beam search with N-best output over a native LINEAR batch, results on the device (DESIGN section 27 holds
+// the contract: the hypotheses are the label sequences without equal neighbours, each summed over its alignments under
+// emissions o transitions; token set of a frame = its topn best labels, no blank, restricting stays as well as
+// extensions; at most `beam` distinct prefixes with one score each; exact prefix merging; the total order of the
+// candidates).  table_dev: device float32 [C + C * C] in the arc order of criteria::asgTransitions -- table[c] =
+// start[c], table[C + i * C + j] = label j followed by label i; an entry that is not finite drops its candidates (-inf
+// forbids a bigram or a first label).  tokens_dev[(b * nbest + r) * row_stride + k]: the labels of hypothesis r of
+// utterance b, -1 from its length to the row's width M; lengths_dev[b * nbest + r]; scores_dev[b * nbest + r]; slots
+// without a hypothesis (fewer than nbest prefixes, a frame with an empty token set, T_b = 0): -1, 0, -inf.  frames
+// (host, [n], or null): T_b, null = rows_of(b).  Invalid argument before a device is asked for: a null batch, table or
+// output, a negative stride, beam outside 1 .. 64, topn outside 1 .. 32, nbest outside 1 .. beam; n == 0 returns
+// without a device.  With the device: a batch that is not a native LINEAR one (there is no other route), a count
+// outside 0 .. M or above rows_of(b), row_stride < M, M * beam beyond an int, more than 2^19 labels, a table that is
+// not memory allocated on the current device, outputs that are not memory of the current device.  Two launches of
+// asg_beam.hip on the engine's stream, scratch from the stream-ordered pool; rows from T_b on are never read, no
+// download, no wait.
+void batch_asg_beam_decode(const BatchP& ems, const int* frames, const float* table_dev, int beam, int topn, int nbest,
+                           int* tokens_dev, int64_t row_stride, int* lengths_dev, float* scores_dev);
+void batch_asg_beam_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they decoded
 // Levenshtein distance (unit costs) of all B * N pairs (hyp[b, k], ref[b]) of device-resident token rows, results on the
 // device (DESIGN section 21 holds the contract).  hyp_dev: int32 [B][N] rows of width L, hyp_stride elements apart;
 // hyp_len_dev: int32 [B][N]; ref_dev: int32 [B] rows of width U, ref_stride apart; ref_len_dev: int32 [B] -- lengths

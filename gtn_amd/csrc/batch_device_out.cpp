@@ -1,7 +1,7 @@
 // batch_device_out.cpp -- the batch entry points that leave their results in the caller's device memory (declared and
 // specified in batch.h): forced alignment, decode against one shared graph, best path of the chains plus the CTC
-// collapse, CTC prefix beam search, edit distance, CTC score and its gradient, CTC token alignment, ASG score and its
-// gradients.  The kernels differ; the host side around them is the helpers below.
+// collapse, CTC prefix beam search, ASG prefix beam search, edit distance, CTC score and its gradient, CTC token
+// alignment, ASG score and its gradients.  The kernels differ; the host side around them is the helpers below.
 //
 // Recipe for the next entry point, in this order:
 //   1. GTNX_HOST_T("batch.<name>"), then every check the arguments alone decide, each message "[gtnx_batch_<name>] ...":
@@ -614,6 +614,86 @@ void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int 
   }
   // (the scratch and the table go back to the stream-ordered pool behind the launches)
   g_ctc_beam.add(1, n);
+}
+
+// ---- ASG prefix beam search with N-best output, device-resident (asg_beam.hip) ----
+namespace {
+constexpr const char* kAsgBeam = "gtnx_batch_asg_beam_decode";
+Counters g_asg_beam;  // (calls, utterances)
+}  // namespace
+
+void batch_asg_beam_stats(int64_t* calls, int64_t* utterances) { g_asg_beam.get(calls, utterances); }
+
+void batch_asg_beam_decode(const BatchP& ems, const int* frames, const float* table_dev, int beam, int topn, int nbest,
+                           int* tokens_dev, int64_t row_stride, int* lengths_dev, float* scores_dev) {
+  GTNX_HOST_T("batch.asg_beam_decode");
+  const char* who = kAsgBeam;
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) refuse(who, "null batch");
+  if (!table_dev) refuse(who, "null table pointer");
+  if (!tokens_dev || !lengths_dev || !scores_dev)
+    refuse(who, "null output pointer (tokens, lengths and scores are all written)");
+  if (row_stride < 0) refuse(who, "negative row stride");
+  if (beam < 1 || beam > 64) refuse(who, "beam_size outside 1 .. 64");
+  if (topn < 1 || topn > 32) refuse(who, "cutoff_top_n outside 1 .. 32");
+  if (nbest < 1 || nbest > beam) refuse(who, "nbest outside 1 .. beam_size");
+  const int n = ems->n;
+  if (n <= 0) return;
+  Runtime& rt = Runtime::get();
+  // there is no other route: the search runs on the slabs of a native linear batch
+  if (!native_linear(*ems)) refuse(who, "not a native linear batch (gtnx_batch_linear / _rows)");
+  Batch& x = *ems;
+  check_frames(who, frames, n, x.M, x);
+  if (row_stride < x.M) refuse(who, "row_stride is shorter than the rows of the batch");
+  if (int64_t(x.M) * beam + 1 > std::numeric_limits<int>::max()) refuse(who, "rows times beam_size does not fit an int");
+  // (a candidate's key keeps its label in 19 bits, above the label's place in the token set; a table of (2^19)^2
+  //  entries is a terabyte)
+  if (x.C > (1 << 19)) refuse(who, "more than 2^19 labels");
+  // (the kernel gathers from it: host memory is refused too, with one GPU as well)
+  if (!ptr_device_memory_of(table_dev, rt.device())) refuse(who, "the table is not memory of the engine's current device");
+  check_outputs_local(who, {tokens_dev, lengths_dev, scores_dev});
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  const std::vector<int> fr = resolve_frames(frames, x);
+  // algorithmic bytes.  rows: every emission of the rows that count once, topn entries and a count out.  search: those
+  // back in, one 4-byte gather per (prefix, member of the set) and frame at the most, a trie node and a self-transition
+  // per kept extension (at most beam per frame), the output rows.
+  double row_bytes = 0, search_bytes = 0;
+  for (int t : fr) {
+    row_bytes += (4.0 * x.C + 8.0 * topn + 4.0) * t;
+    search_bytes += (8.0 * topn + 4.0 + 12.0 * beam + 4.0 * beam * topn) * t + nbest * (4.0 * x.M + 8.0);
+  }
+  DevMemP d_frames = upload_vec(fr);
+  const size_t rows = std::max<size_t>(size_t(n) * size_t(x.M), 1);
+  DevMemP entries = rt.alloc(8 * rows * size_t(topn));
+  DevMemP counts = rt.alloc(sizeof(int) * rows);
+  DevMemP trie = rt.alloc(8 * size_t(n) * (size_t(x.M) * size_t(beam) + 1));
+  AsgBeamArgs a{};
+  a.em = x.w_dev;
+  a.frames = d_frames->as<int>();
+  a.table = table_dev;
+  a.ent_val = entries->as<float>();
+  a.ent_cnt = counts->as<int>();
+  a.trie = trie->as<int>();
+  a.tokens = tokens_dev;
+  a.lengths = lengths_dev;
+  a.scores = scores_dev;
+  a.row_stride = row_stride;
+  a.n = n;
+  a.M = x.M;
+  a.C = x.C;
+  a.beam = beam;
+  a.topn = topn;
+  a.nbest = nbest;
+  {
+    GTNX_PROF("asg_beam_rows", row_bytes);
+    launch_asg_beam(a, 0, rt.stream());
+  }
+  {
+    GTNX_PROF("asg_beam_search", search_bytes);
+    launch_asg_beam(a, 1, rt.stream());
+  }
+  // (the scratch goes back to the stream-ordered pool behind the launches)
+  g_asg_beam.add(1, n);
 }
 
 // ---- batched edit distance of device-resident token rows (edit_distance.hip) ----

@@ -922,6 +922,20 @@ GTNX_API gtnx_status_t gtnx_batch_ctc_beam_decode_lm(gtnx_batch_t ems, const int
 GTNX_API gtnx_status_t gtnx_batch_ctc_beam_stats(int64_t* calls, int64_t* utterances) {
   return guard([&] { batch_ctc_beam_stats(calls, utterances); });
 }
+GTNX_API gtnx_status_t gtnx_batch_asg_beam_decode(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                                  int beam_size, int cutoff_top_n, int nbest, void* tokens_device,
+                                                  int64_t row_stride, void* lengths_device, void* scores_device) {
+  return guard([&] {
+    // (a null handle goes through: the entry refuses it under its own name)
+    batch_asg_beam_decode(ems ? BH(ems) : BatchP(), frames, static_cast<const float*>(table_device), beam_size,
+                          cutoff_top_n, nbest,
+                          static_cast<int*>(tokens_device), row_stride, static_cast<int*>(lengths_device),
+                          static_cast<float*>(scores_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_asg_beam_stats(int64_t* calls, int64_t* utterances) {
+  return guard([&] { batch_asg_beam_stats(calls, utterances); });
+}
 GTNX_API gtnx_status_t gtnx_batch_edit_distance(const void* hyp_device, int64_t hyp_stride,
                                                 const void* hyp_lengths_device, const void* ref_device,
                                                 int64_t ref_stride, const void* ref_lengths_device, int B, int N, int L,

@@ -856,6 +856,31 @@ struct CtcBeamArgs {
   GTNX_G float* am_scores;
 };
 void launch_ctc_beam(const CtcBeamArgs& a, int which, hipStream_t st);
+// asg_beam.hip: ASG prefix beam search with N-best output over every chain of an [n][M][C] tensor at its own length
+// frames[b] (device, 0 .. M), results on the device (the contract: DESIGN section 27).  The hypotheses are the label
+// sequences without equal neighbours, each summed over its alignments under emissions o transitions.  table: [C + C * C]
+// in the arc order of asgTransitions, entry c = start[c], entry C + i * C + j = label j followed by label i; an entry
+// that is not finite forbids its candidates.  which = 0: the rows -- the token set S_t of every row that counts (its
+// topn best labels, no blank), (value, label) entries [n][M][topn] and their counts [n][M] in scratch.  which = 1: one
+// workgroup per utterance, sequential over the frames -- at most `beam` prefixes with one score each, exact prefix
+// identity through the trie in scratch (node 1 + t * beam + slot = (parent node, label), node 0 the empty prefix), then
+// tokens[(b * nbest + r) * row_stride + k] (-1 from the length to M), lengths[b * nbest + r], scores[b * nbest + r];
+// slots without a hypothesis: -1, 0, -inf.  Nothing from row frames[b] on is read.
+// beam 1 .. 64, topn 1 .. 32, nbest 1 .. beam, C <= 2^19, M * beam < 2^31 (the engine has refused the rest).
+struct AsgBeamArgs {
+  const GTNX_G float* em;
+  const GTNX_G int* frames;    // [n]
+  const GTNX_G float* table;   // [C + C * C]
+  GTNX_G float* ent_val;       // [n][M][topn], interleaved with the labels as 8-byte entries: see beam_common.h
+  GTNX_G int* ent_cnt;         // [n][M]
+  GTNX_G int* trie;            // [n][M * beam + 1][2]
+  GTNX_G int* tokens;
+  GTNX_G int* lengths;
+  GTNX_G float* scores;
+  int64_t row_stride;
+  int n, M, C, beam, topn, nbest;
+};
+void launch_asg_beam(const AsgBeamArgs& a, int which, hipStream_t st);
 // edit_distance.hip: Levenshtein distance (unit costs) of the pairs pair0 .. pair0 + count - 1, pair p = b * N + k being
 // (hyp + p * hyp_stride, hyp_len[p]) against (ref + b * ref_stride, ref_len[b]) -- one launch, one wave per pair, Myers'
 // bit-vector recurrence in Hyyro's block form with the wave as the 64-bit word (the contract: DESIGN section 21).

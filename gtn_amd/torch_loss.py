@@ -1,6 +1,6 @@
 """PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
-`asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_beam_decode`, `edit_distance`, `ctc_score`, `ctc_token_align` and
-`asg_score`.
+`asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_beam_decode`, `asg_beam_decode`, `edit_distance`, `ctc_score`,
+`ctc_token_align` and `asg_score`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -39,6 +39,7 @@ _ARGTYPES = {
     "gtn_ctc_token_align_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gtn_asg_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "gtn_asg_beam_decode_n": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P],
 }
 
 
@@ -640,6 +641,58 @@ def ctc_beam_decode(log_probs, blank=0, input_lengths=None, beam_size=16, cutoff
            (blank, _host_ptr(frames), beam_size, cutoff_top_n, nbest, tokens.data_ptr(), lengths.data_ptr(),
             scores.data_ptr()),
            "ctc_beam_decode", tokens, lengths, scores, frames, blank, beam_size, cutoff_top_n, nbest, row_stride=T)
+    return tokens, lengths, scores
+
+
+def asg_beam_decode(emissions, transitions, start=None, input_lengths=None, beam_size=16, cutoff_top_n=16, nbest=1):
+    """ASG prefix beam search of a batch with N-best output, device-resident: the best label sequences without equal
+    neighbours -- the sequences `asg_decode(collapse=True)` can emit -- each summed over all of its alignments under
+    emissions o transitions, where `asg_decode` gives the best alignment.  Two launches whatever the lengths, nothing
+    copied back.
+    emissions: float32 CUDA tensor [B, T, N] (any scores), read in place and left untouched; rows past an utterance's
+    length are never read; transitions: [N, N] with transitions[i, j] the score of label j followed by label i; start:
+    [N] scores of the first label (zeros when omitted) -- both detached, and a -inf entry forbids its bigram or first
+    label; input_lengths: per-utterance frame counts (0 .. T) or None; beam_size: prefixes kept per frame (1 .. 64);
+    cutoff_top_n: the best labels of a frame that a prefix may stay in or grow by (1 .. 32); nbest: hypotheses returned
+    (1 .. beam_size).
+    Returns (tokens int32 [B, nbest, T], lengths int32 [B, nbest], scores float32 [B, nbest]) on emissions.device, best
+    first: the labels of each hypothesis, -1 from its length on, and its log score summed over the alignments the beam
+    kept (float32 log-add; unpruned it is `asg_score` of that sequence).  Of exactly equal scores the order is: a prefix
+    that stayed before one that grew, then the parent's rank, then the label; NaN and -inf are never chosen.  Slots
+    without a hypothesis -- fewer than nbest prefixes, a frame with nothing above -inf, an utterance without frames --
+    get -1, length 0 and score -inf.  The outputs feed `asg_score` and `edit_distance` as they are.  Runs on the
+    caller's stream and does not wait; no autograd."""
+    if emissions.dim() != 3 or emissions.dtype != torch.float32:
+        raise ValueError("asg_beam_decode: emissions must be a float32 tensor [B, T, N]")
+    B, T, N = emissions.shape
+    beam_size, cutoff_top_n, nbest = int(beam_size), int(cutoff_top_n), int(nbest)
+    if transitions.dim() != 2 or tuple(transitions.shape) != (N, N):
+        raise ValueError(f"asg_beam_decode: transitions must be [{N}, {N}]")
+    if start is not None and tuple(start.shape) != (N,):
+        raise ValueError(f"asg_beam_decode: start must be [{N}]")
+    if not 1 <= beam_size <= 64:
+        raise ValueError("asg_beam_decode: beam_size outside 1 .. 64")
+    if not 1 <= cutoff_top_n <= 32:
+        raise ValueError("asg_beam_decode: cutoff_top_n outside 1 .. 32")
+    if not 1 <= nbest <= beam_size:
+        raise ValueError("asg_beam_decode: nbest outside 1 .. beam_size")
+    frames = None if input_lengths is None else _frame_counts("asg_beam_decode", input_lengths, B, T, 0)
+    if not emissions.is_cuda:
+        raise RuntimeError("asg_beam_decode: emissions must be a CUDA tensor (the search runs on the device)")
+    x = emissions.detach().contiguous()
+    # (written on the caller's stream BEFORE the engine is pointed at it: on the null stream _engine_stream waits once
+    #  for what is queued so far, and the engine's own stream is ordered with nothing that comes after)
+    tr = transitions.detach().to(x.device)
+    st = torch.zeros(N, dtype=torch.float32, device=x.device) if start is None else start.detach().to(x.device)
+    table = _asg_weights(st, tr)
+    stream = _engine_stream(x.device)
+    tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=x.device)
+    lengths = torch.empty(B, nbest, dtype=torch.int32, device=x.device)
+    scores = torch.empty(B, nbest, dtype=torch.float32, device=x.device)
+    _route(stream, x, _has_native("asg_beam_decode", "gtn_asg_beam_decode_n"), "gtn_asg_beam_decode_n",
+           (table.data_ptr(), _host_ptr(frames), beam_size, cutoff_top_n, nbest, tokens.data_ptr(), lengths.data_ptr(),
+            scores.data_ptr()),
+           "asg_beam_decode", tokens, lengths, scores, frames, table, beam_size, cutoff_top_n, nbest, row_stride=T)
     return tokens, lengths, scores
 
 

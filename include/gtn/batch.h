@@ -269,6 +269,22 @@ inline void asgScoreGrad(const Batch& ems, const float* tableDevice, const int* 
   detail::check(gtnx_batch_asg_score_grad(ems.handle(), frames, tableDevice, tokensDevice, rowStride, lengthsDevice, N,
                                           L, maxLength, weightsDevice, gradEmissionsDevice, gradTableDevice));
 }
+/** ASG prefix beam search with N-best output over a Batch::linear, results left on the device: the hypotheses are the
+ *  label sequences without equal neighbours (what viterbiDecode's collapsed rows can hold), each summed over all of its
+ *  alignments under emissions o transitions -- unpruned, asgScore of the tokens.  tableDevice float32 [C + C * C]
+ *  (device memory) in the arc order of criteria::asgTransitions: entry c = start[c], entry C + i * C + j = label j
+ *  followed by label i; an entry that is not finite forbids its bigram or first label.  tokensDevice int32
+ *  [n][nbest][rowStride] (the labels of hypothesis r, then -1 up to the row's width M), lengthsDevice int32 [n][nbest],
+ *  scoresDevice float32 [n][nbest]; slots without a hypothesis: -1, 0, -inf.  beamSize 1 .. 64 prefixes, the cutoffTopN
+ *  (1 .. 32) best labels of a frame for stays and extensions alike, nbest <= beamSize; frames (host, [n]): T_b, null =
+ *  the rows the batch carries.  Two launches, no copy back, no wait, rows from T_b on are never read --
+ *  gtnx_batch_asg_beam_decode */
+inline void asgBeamDecode(const Batch& ems, const float* tableDevice, int* tokensDevice, int64_t rowStride,
+                          int* lengthsDevice, float* scoresDevice, int beamSize = 16, int cutoffTopN = 16, int nbest = 1,
+                          const int* frames = nullptr) {
+  detail::check(gtnx_batch_asg_beam_decode(ems.handle(), frames, tableDevice, beamSize, cutoffTopN, nbest, tokensDevice,
+                                           rowStride, lengthsDevice, scoresDevice));
+}
 /** The best alignment of all n * N device-resident hypotheses (the form of ctcScore) under the slabs of a Batch::linear,
  *  results left on the device: scoresDevice [n][N] the Viterbi score (-inf without a path); startsDevice / endsDevice
  *  int32 n * N rows of width L, outStride (>= L) apart: the first frame of token i and one past its last, -1 for i >= len

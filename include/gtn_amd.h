@@ -584,6 +584,55 @@ gtnx_status_t gtnx_batch_asg_score_grad(gtnx_batch_t ems, const int* frames, con
                                         void* grad_emissions_device, void* grad_table_device);
 /* calls of either kind that have launched so far (process-wide) / pairs they took */
 gtnx_status_t gtnx_batch_asg_score_stats(int64_t* calls, int64_t* pairs);
+/* ASG prefix beam search with N-best output over the n emission slabs of a gtnx_batch_linear / _rows batch
+ * ([n][M][C]), results left on the device.  The hypotheses are the label sequences WITHOUT EQUAL
+ * NEIGHBOURS -- what gtnx_batch_viterbi_decode's collapsed rows can hold -- each summed over all of its alignments
+ * under emissions o transitions.  Every frame labelling collapses to exactly one such sequence, so the hypotheses
+ * partition the paths: unpruned, a hypothesis's score is gtnx_batch_asg_score of its tokens, and the log-sum over all
+ * hypotheses is forwardScore(emissions o transitions).
+ * table_device: DEVICE float32 [C + C * C] in the arc order of gtn::criteria::asgTransitions: table[c] is start[c],
+ * table[C + i * C + j] is transitions[i][j], the score of label j followed by label i -- the table
+ * gtnx_batch_asg_score takes.  frames: HOST, [n], T_b in 0 .. M, or null (the rows the batch carries).
+ * Per utterance, float32 throughout, with x = emissions[b][t]:
+ *   token set   S_t = the cutoff_top_n (1 .. 32) best labels of row t: value descending, of equal values the smaller
+ *               label; NaN and -inf are never chosen; no blank is appended.  S_t restricts EVERY use of frame t, stays
+ *               as well as extensions: with an unbounded list the result is the exact N-best of the lattice restricted
+ *               to S_t per frame.
+ *   state       at most beam_size (1 .. 64) distinct prefixes, each with ONE score a(p): the log-sum of the alignments
+ *               of frames 0 .. t to p that end in last(p).  Before frame 0: the empty prefix with score 0.  It has no
+ *               stay, so it is gone after frame 0.
+ *   frame t     with l = last(p): the stay (p not empty, l in S_t) scores (a(p) + tr[l][l]) + x[l]; the extension by c
+ *               in S_t, c != l, scores s = (a(p) + w) + x[c], w = start[c] for the empty prefix and tr[c][l] otherwise.
+ *               A w that is -inf, +inf or NaN drops its candidate, so a -inf entry forbids a bigram or a first label;
+ *               a candidate whose value is not above -inf is dropped.  An extension that spells a prefix q of the list
+ *               is no candidate: its s is log-added into q's stay value (from -inf if q has no stay), and the merged q
+ *               competes as a stay.  Identity is exact, by the labels: a prefix that left the list and was created
+ *               again is still recognised as the parent of its child that stayed.
+ *   order       total descending, then stays before extensions, then the parent's rank ascending, then the label
+ *               ascending; the first beam_size with a total above -inf form the new list.
+ *   arithmetic  the sums in exactly the order written; log-add(a, b) = b if a = -inf, a if b = -inf, else m +
+ *               log1p(exp(n - m)), m the larger, n the smaller.
+ * tokens_device: int32 [n][nbest] rows of width M, row_stride (>= M) elements apart: the labels of hypothesis r of
+ * utterance b, -1 from its length on up to column M; lengths_device: int32 [n][nbest]; scores_device: float32
+ * [n][nbest].  A slot without a hypothesis (T_b == 0, a frame with nothing above -inf, fewer hypotheses than nbest) gets
+ * -1, 0, -inf.  Rows at or past T_b are never read: what they hold never changes a bit of any output.  No global or
+ * floating-point atomics: the same bits run to run.
+ * GTNX_INVALID_ARGUMENT, each with a text that begins "[gtnx_batch_asg_beam_decode]", and nothing is written.  Before a
+ * device is asked for: a null batch, a null table, a null output pointer, a negative row_stride, beam_size outside
+ * 1 .. 64, cutoff_top_n outside 1 .. 32, nbest outside 1 .. beam_size.  n == 0 then returns without touching a device.
+ * With the device: not a gtnx_batch_linear / _rows batch (there is no other route), a frame count outside 0 .. M or
+ * above the rows the batch carries, row_stride < M, M * beam_size beyond an int, more than 2^19 labels (a candidate's
+ * sort key keeps its label in 19 bits; such a table has no device to live on), table_device anything but memory
+ * allocated on the engine's current device (the kernel gathers from it: host memory is refused with one GPU as well),
+ * an output the engine's current device may not write.
+ * Two launches on the engine's stream (asg_beam.hip): the token sets of all rows, then one workgroup per utterance.
+ * Scratch from the stream-ordered pool: 8 * cutoff_top_n + 4 bytes per row and 8 * (M * beam_size + 1) bytes per
+ * utterance.  Nothing is copied back, the call does not wait. */
+gtnx_status_t gtnx_batch_asg_beam_decode(gtnx_batch_t ems, const int* frames, const void* table_device, int beam_size,
+                                         int cutoff_top_n, int nbest, void* tokens_device, int64_t row_stride,
+                                         void* lengths_device, void* scores_device);
+/* calls that have launched so far (process-wide) / utterances they decoded */
+gtnx_status_t gtnx_batch_asg_beam_stats(int64_t* calls, int64_t* utterances);
 /* rows M and labels C of the slabs of a gtnx_batch_linear / _rows batch; -1, -1 for any other batch */
 gtnx_status_t gtnx_batch_linear_shape(gtnx_batch_t ems, int* rows, int* labels);
 gtnx_status_t gtnx_batch_backward(gtnx_batch_t a, int retain_graph);                  /* autograd.cpp:17-67 */
