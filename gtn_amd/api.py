@@ -1008,22 +1008,11 @@ def make_api(lib):
                                                 _opt_ptr(tok), stride, _opt_ptr(ln), N, L, U, _opt_ptr(weights),
                                                 _opt_ptr(grad_out)))
 
-        def ctc_token_align(self, tokens, lengths, scores_out, starts_out, ends_out, token_scores_out=None,
-                            frame_tokens_out=None, frames=None, blank=0, max_length=None, N=None, L=None,
-                            row_stride=None, out_stride=None, frame_stride=None):
-            """The best alignment of all B * N device-resident hypotheses under the slabs of a Batch.linear, results left
-            on the device (gtnx_batch_ctc_token_align; DESIGN section 24 holds the contract).  `tokens`, `lengths`,
-            `frames`, `blank`, `max_length`, N, L and row_stride are those of `ctc_score`.  `scores_out` float32 [B, N]:
-            the Viterbi score, -inf without a path; `starts_out` / `ends_out` int32 [B, N, L]: the first frame of token i
-            and one past its last, -1 for i >= len and without a path; `token_scores_out` float32 [B, N, L] or None: the
-            token's emissions summed in frame order; `frame_tokens_out` int32 [B, N, M] or None: the token index of every
-            frame, -1 on blank frames and from T_b on.  Tensors need contiguous, equally spaced rows (views of wider
-            tensors are fine: only the widths L and M are written); device addresses go with `out_stride` (>= L, default
-            L) and `frame_stride` (>= M, default M).  Float32 max-plus with the tie rule of `viterbi_align`: the same bits
-            every time.  No copy back and no wait."""
-            who = "ctc_token_align"
+        def _token_align_outputs(self, who, N, L, scores_out, starts_out, ends_out, token_scores_out, frame_tokens_out,
+                                 out_stride, frame_stride):
+            """What `ctc_token_align` and `asg_token_align` check of their outputs alike.  Returns (out_stride,
+            frame_stride), or (None, None) for a call without pairs whose scores are a tensor: nothing to do."""
             n = len(self)
-            fr, tok, stride, ln, N, L, U = self._ctc_score_args(who, tokens, lengths, frames, N, L, row_stride, max_length)
 
             def rows_of(t, name, dtype, width, given):
                 """the row stride of an output: that of a tensor [B, N, width], else `given`"""
@@ -1054,7 +1043,29 @@ def make_api(lib):
                         or scores_out.numel() != n * N):
                     raise ValueError(f"{who}: scores_out must be a float32 contiguous tensor [B, N]")
                 if n * N == 0:
-                    return
+                    return None, None
+            return int(out_stride), int(frame_stride)
+
+        def ctc_token_align(self, tokens, lengths, scores_out, starts_out, ends_out, token_scores_out=None,
+                            frame_tokens_out=None, frames=None, blank=0, max_length=None, N=None, L=None,
+                            row_stride=None, out_stride=None, frame_stride=None):
+            """The best alignment of all B * N device-resident hypotheses under the slabs of a Batch.linear, results left
+            on the device (gtnx_batch_ctc_token_align; DESIGN section 24 holds the contract).  `tokens`, `lengths`,
+            `frames`, `blank`, `max_length`, N, L and row_stride are those of `ctc_score`.  `scores_out` float32 [B, N]:
+            the Viterbi score, -inf without a path; `starts_out` / `ends_out` int32 [B, N, L]: the first frame of token i
+            and one past its last, -1 for i >= len and without a path; `token_scores_out` float32 [B, N, L] or None: the
+            token's emissions summed in frame order; `frame_tokens_out` int32 [B, N, M] or None: the token index of every
+            frame, -1 on blank frames and from T_b on.  Tensors need contiguous, equally spaced rows (views of wider
+            tensors are fine: only the widths L and M are written); device addresses go with `out_stride` (>= L, default
+            L) and `frame_stride` (>= M, default M).  Float32 max-plus with the tie rule of `viterbi_align`: the same bits
+            every time.  No copy back and no wait."""
+            who = "ctc_token_align"
+            fr, tok, stride, ln, N, L, U = self._ctc_score_args(who, tokens, lengths, frames, N, L, row_stride, max_length)
+            out_stride, frame_stride = self._token_align_outputs(who, N, L, scores_out, starts_out, ends_out,
+                                                                 token_scores_out, frame_tokens_out, out_stride,
+                                                                 frame_stride)
+            if out_stride is None:
+                return
             check(lib.gtnx_batch_ctc_token_align(self._h, fr.ctypes.data if fr is not None else None, int(blank),
                                                  _opt_ptr(tok), stride, _opt_ptr(ln), N, L, U, _opt_ptr(scores_out),
                                                  _opt_ptr(starts_out), _opt_ptr(ends_out), _opt_ptr(token_scores_out),
@@ -1095,6 +1106,29 @@ def make_api(lib):
                     return
             check(lib.gtnx_batch_asg_score(self._h, fr.ctypes.data if fr is not None else None, _opt_ptr(table),
                                            _opt_ptr(tok), stride, _opt_ptr(ln), N, L, U, _opt_ptr(scores_out)))
+
+        def asg_token_align(self, tokens, lengths, scores_out, starts_out, ends_out, token_scores_out=None,
+                            frame_tokens_out=None, frames=None, table=None, max_length=None, N=None, L=None,
+                            row_stride=None, out_stride=None, frame_stride=None):
+            """The best ASG alignment of all B * N device-resident hypotheses under the slabs of a Batch.linear, results
+            left on the device (gtnx_batch_asg_token_align; DESIGN section 28 holds the contract).  `table`, `tokens`,
+            `lengths`, `frames`, `max_length`, N, L and row_stride are those of `asg_score`; the outputs, `out_stride` and
+            `frame_stride` are those of `ctc_token_align`, except that `frame_tokens_out` is never -1 inside a path (ASG
+            has no blank).  A pair has no path (-inf, rows of -1) exactly where `asg_score` gives -inf.  Float32 max-plus
+            with the arithmetic of `asg_forced_align`, of two equal candidates the step: the same bits every time, and
+            its scores where both apply.  No copy back and no wait."""
+            who = "asg_token_align"
+            fr, tok, stride, ln, N, L, U = self._ctc_score_args(who, tokens, lengths, frames, N, L, row_stride, max_length)
+            table = self._asg_score_table(who, table)
+            out_stride, frame_stride = self._token_align_outputs(who, N, L, scores_out, starts_out, ends_out,
+                                                                 token_scores_out, frame_tokens_out, out_stride,
+                                                                 frame_stride)
+            if out_stride is None:
+                return
+            check(lib.gtnx_batch_asg_token_align(self._h, fr.ctypes.data if fr is not None else None, _opt_ptr(table),
+                                                 _opt_ptr(tok), stride, _opt_ptr(ln), N, L, U, _opt_ptr(scores_out),
+                                                 _opt_ptr(starts_out), _opt_ptr(ends_out), _opt_ptr(token_scores_out),
+                                                 int(out_stride), _opt_ptr(frame_tokens_out), int(frame_stride)))
 
         def asg_score_grad(self, table, tokens, lengths, weights, grad_out=None, grad_table_out=None, frames=None,
                            max_length=None, N=None, L=None, row_stride=None):
@@ -1281,6 +1315,11 @@ def make_api(lib):
         took (include/gtn_amd.h: gtnx_batch_asg_score_stats)"""
         return _stats2(lib.gtnx_batch_asg_score_stats)
 
+    def debug_asg_token_align_stats():
+        """(calls, pairs): calls of Batch.asg_token_align that have launched so far and the pairs they aligned
+        (include/gtn_amd.h: gtnx_batch_asg_token_align_stats)"""
+        return _stats2(lib.gtnx_batch_asg_token_align_stats)
+
     def debug_asg_beam_stats():
         """(calls, utterances): calls of Batch.asg_beam_decode that have launched so far and the utterances they decoded
         (include/gtn_amd.h: gtnx_batch_asg_beam_stats)"""
@@ -1376,6 +1415,7 @@ def make_api(lib):
     ns.debug_ctc_score_stats = debug_ctc_score_stats
     ns.debug_ctc_token_align_stats = debug_ctc_token_align_stats
     ns.debug_asg_score_stats = debug_asg_score_stats
+    ns.debug_asg_token_align_stats = debug_asg_token_align_stats
     ns.debug_asg_beam_stats = debug_asg_beam_stats
     ns.edit_distance = edit_distance
     ns.debug_symbolic_route = debug_symbolic_route

@@ -241,5 +241,36 @@ inline void asgBeamDecodeBatch(
                          frames);
 }
 
+/** The best alignment of B * N device-resident hypotheses under the B emission slabs -- when each token was spoken and
+ *  how well the frames support it: `emissions` device float32 [B][T][N_], read in place; `tableDev` device float32
+ *  [N_ + N_ * N_] in the arc order of asgTransitions; `tokensDev` device int32 [B][N][L] and `lengthsDev` device int32
+ *  [B][N] (dense rows, what asgBeamDecodeBatch wrote when L == T); `frames` host [B] or null; `scoresDev` device float32
+ *  [B][N]; `startsDev` / `endsDev` device int32 [B][N][L]; `tokenScoresDev` device float32 [B][N][L] or null;
+ *  `frameTokensDev` device int32 [B][N][T] or null.  gtnx_batch_asg_token_align has the contract.  Nothing is copied
+ *  back. */
+inline void asgTokenAlignBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int N_,
+    const void* tableDev,
+    const int* frames,
+    const void* tokensDev,
+    const void* lengthsDev,
+    int N,
+    int L,
+    int maxLength,
+    void* scoresDev,
+    void* startsDev,
+    void* endsDev,
+    void* tokenScoresDev = nullptr,
+    void* frameTokensDev = nullptr) {
+  Batch ems = Batch::linear(B, T, N_, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  batched::asgTokenAlign(ems, static_cast<const float*>(tableDev), static_cast<const int*>(tokensDev), L,
+                         static_cast<const int*>(lengthsDev), N, L, maxLength, static_cast<float*>(scoresDev),
+                         static_cast<int*>(startsDev), static_cast<int*>(endsDev), static_cast<float*>(tokenScoresDev), L,
+                         static_cast<int*>(frameTokensDev), T, frames);
+}
+
 } // namespace criteria
 } // namespace gtn

@@ -265,3 +265,16 @@ GTN_EXPORT int gtn_asg_score_grad_n(const void* emissions, int B, int T, int C, 
                                  grad_em, grad_table);
   });
 }
+
+// The best ASG alignment of B * N device-resident hypotheses.  emissions: DEVICE float32 [B][T][C]; table: DEVICE float32
+// [C + C*C] as for gtn_asg_score_n; frames: HOST int [B] or null; tokens: DEVICE int32 [B][N][L]; lengths: DEVICE int32
+// [B][N]; scores: DEVICE float32 [B][N]; starts / ends: DEVICE int32 [B][N][L]; token_scores: DEVICE float32 [B][N][L] or
+// null; frame_tokens: DEVICE int32 [B][N][T] or null.
+GTN_EXPORT int gtn_asg_token_align_n(const void* emissions, int B, int T, int C, const void* table, const int* frames,
+                                     const void* tokens, const void* lengths, int N, int L, int max_length,
+                                     void* scores, void* starts, void* ends, void* token_scores, void* frame_tokens) {
+  return guarded([&] {
+    gtn::criteria::asgTokenAlignBatch(emissions, B, T, C, table, frames, tokens, lengths, N, L, max_length, scores,
+                                      starts, ends, token_scores, frame_tokens);
+  });
+}

@@ -298,6 +298,25 @@ void batch_asg_score_grad(const BatchP& ems, const int* frames, const float* tab
                           int64_t row_stride, const int* lengths_dev, int N, int L, int max_length,
                           const float* weights_dev, float* grad_em_dev, float* grad_table_dev);
 void batch_asg_score_stats(int64_t* calls, int64_t* pairs);  // calls that launched (either kind) / pairs they took
+// The best ASG alignment of all n * N device-resident hypotheses (the pair form and the table of batch_asg_score) under
+// the n emission slabs of a native linear batch, results on the device (DESIGN section 28 holds the contract): the
+// outputs are those of batch_ctc_token_align, frame_tokens_dev never -1 inside a path (there is no blank).  Float32
+// max-plus with the association of asg_align.hip, alpha + (w + e), of two equal candidates the step: bit-reproducible,
+// scores bit-equal to batch_viterbi_align's ASG launch where both apply.  -1 / -inf wherever no path covers an entry; a
+// pair has no path where batch_asg_score gives -inf.  Every element of every row is written over its width, nothing
+// beyond.  No cap on C of its own: table indices are 64-bit and there is no per-label LDS row.
+// Invalid argument before a device is asked for: a null table, scores, starts or ends pointer, negative out_stride or
+// frame_stride, out_stride < L, then check_hypotheses; n * N == 0 returns without a device.  With the device: not a
+// native linear batch, a frame count outside 0 .. M, frame_stride < M with frame tokens, a table that is not device
+// memory of the current device, an output that is not memory of the current device.  The back-pointers (1 bit per
+// position and frame, ceil(max T_b / 32) * max_length words per pair) come from the stream-ordered pool, at most 256 MiB
+// per launch (GTNX_ASG_TOKEN_ALIGN_SCRATCH_BYTES lowers the cap: a debug switch); beyond it the pairs run in slices, same
+// bits.
+void batch_asg_token_align(const BatchP& ems, const int* frames, const float* table_dev, const int* tokens_dev,
+                           int64_t row_stride, const int* lengths_dev, int N, int L, int max_length, float* scores_dev,
+                           int* starts_dev, int* ends_dev, float* token_scores_dev, int64_t out_stride,
+                           int* frame_tokens_dev, int64_t frame_stride);
+void batch_asg_token_align_stats(int64_t* calls, int64_t* pairs);  // calls that launched / pairs they aligned
 // items_dev (optional): device memory of the CALLER's that the n result values are written into directly (borrowed: it
 // must outlive the result); a later batch_items_device to the same address copies nothing
 BatchP batch_scalar(ScalarKind k, const BatchP& a, const BatchP& b, void* items_dev = nullptr);

@@ -1,7 +1,8 @@
 // batch_device_out.cpp -- the batch entry points that leave their results in the caller's device memory (declared and
 // specified in batch.h): forced alignment, decode against one shared graph, best path of the chains plus the CTC
 // collapse, CTC prefix beam search, ASG prefix beam search, edit distance, CTC score and its gradient, CTC token
-// alignment, ASG score and its gradients.  The kernels differ; the host side around them is the helpers below.
+// alignment, ASG score and its gradients, ASG token alignment.  The kernels differ; the host side around them is the
+// helpers below.
 //
 // Recipe for the next entry point, in this order:
 //   1. GTNX_HOST_T("batch.<name>"), then every check the arguments alone decide, each message "[gtnx_batch_<name>] ...":
@@ -14,9 +15,10 @@
 //   4. the entry's Counters, and a *_stats getter that is its get().
 //   An entry with a route for every other batch computes the path graphs and hands them to paths_to_rows(...).
 //   An entry that reads hypothesis rows (tokens [n][N][L], lengths [n][N], max_length, one workgroup per pair: CTC score,
-//   CTC token alignment, ASG score) has its own argument-only checks first, then pairs = check_hypotheses(...) and the
-//   return of a call without pairs; linear_hypothesis_batch(...) for step 2's refusals, its own checks of the shape and
-//   of the device, settle_frames(...) for step 3's opening, and for_pair_slices(...) around launches with scratch per pair.
+//   CTC token alignment, ASG score, ASG token alignment) has its own argument-only checks first, then pairs =
+//   check_hypotheses(...) and the return of a call without pairs; linear_hypothesis_batch(...) for step 2's refusals,
+//   its own checks of the shape and of the device, settle_frames(...) for step 3's opening, and for_pair_slices(...)
+//   around launches with scratch per pair.
 #include "batch.h"
 
 #include <algorithm>
@@ -103,7 +105,8 @@ void for_pair_slices(int64_t pairs, int64_t bytes_per_pair, const ScratchCap& ca
   for (int64_t p0 = 0; p0 < pairs; p0 += slice) body(p0, std::min(slice, pairs - p0));
 }
 
-// ---- what the entries that read hypothesis rows share (ctc_score.hip, ctc_token_align.hip, asg_score.hip) ----
+// ---- what the entries that read hypothesis rows share (ctc_score.hip, ctc_token_align.hip, asg_score.hip,
+// asg_token_align.hip) ----
 // the rows as the caller describes them: pair p = b * N + k has tokens[p * row_stride .. + L) and lengths[p], and no
 // length counts beyond max_length
 struct Hypotheses {
@@ -1015,6 +1018,70 @@ void batch_asg_score_grad(const BatchP& ems, const int* frames, const float* tab
   GTNX_HOST_T("batch.asg_score_grad");
   asg_score_impl("gtnx_batch_asg_score_grad", ems, frames, table_dev,
                  {tokens_dev, row_stride, lengths_dev, N, L, max_length}, nullptr, weights_dev, grad_em_dev, grad_table_dev);
+}
+
+// ---- batched ASG token alignment of device-resident hypotheses (asg_token_align.hip) ----
+namespace {
+constexpr const char* kAsgTokenAlign = "gtnx_batch_asg_token_align";
+Counters g_asg_token_align;  // (calls, pairs)
+// the back-pointer words: a pair that is above the cap by itself runs alone with scratch of its own size
+constexpr ScratchCap kAsgTokenAlignScratch{"GTNX_ASG_TOKEN_ALIGN_SCRATCH_BYTES", int64_t(256) << 20};
+}  // namespace
+
+void batch_asg_token_align_stats(int64_t* calls, int64_t* pairs) { g_asg_token_align.get(calls, pairs); }
+
+void batch_asg_token_align(const BatchP& ems, const int* frames, const float* table_dev, const int* tokens_dev,
+                           int64_t row_stride, const int* lengths_dev, int N, int L, int max_length, float* scores_dev,
+                           int* starts_dev, int* ends_dev, float* token_scores_dev, int64_t out_stride,
+                           int* frame_tokens_dev, int64_t frame_stride) {
+  GTNX_HOST_T("batch.asg_token_align");
+  const char* who = kAsgTokenAlign;
+  const Hypotheses h{tokens_dev, row_stride, lengths_dev, N, L, max_length};
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!table_dev) refuse(who, "null table pointer");
+  if (!scores_dev || !starts_dev || !ends_dev) refuse(who, "null output pointer (scores, starts and ends are all written)");
+  if (out_stride < 0 || frame_stride < 0) refuse(who, "negative row stride");
+  if (out_stride < L) refuse(who, "out_stride is shorter than the rows' width L");
+  const int64_t pairs = check_hypotheses(who, ems, h);
+  if (pairs <= 0) return;
+  Batch& x = linear_hypothesis_batch(who, ems, frames);
+  if (frame_tokens_dev && frame_stride < x.M) refuse(who, "frame_stride is shorter than the rows of the batch");
+  Runtime& rt = Runtime::get();
+  // (the kernel gathers from it: host memory is refused too, with one GPU as well)
+  if (!ptr_device_memory_of(table_dev, rt.device())) refuse(who, "the table is not memory of the engine's current device");
+  check_outputs_local(who, {scores_dev, starts_dev, ends_dev, token_scores_dev, frame_tokens_dev});
+  AsgTokenAlignArgs a{};
+  const PairFrames fr = settle_frames(x, frames, h, a);
+  const int U = max_length;
+  a.table = table_dev;
+  a.scores = scores_dev;
+  a.starts = starts_dev;
+  a.ends = ends_dev;
+  a.token_scores = token_scores_dev;
+  a.frame_tokens = frame_tokens_dev;
+  a.out_stride = out_stride;
+  a.frame_stride = frame_stride;
+  // algorithmic bytes, by the widths (the lengths are device memory: an upper bound).  Per pair and frame one emission
+  // per position and 1 bit per position out; the walk reads one window of 64 words per 32 frames; the tokens, two table
+  // entries per position and the length once, the score and the two span rows out; with token scores one emission per
+  // frame at most and the row; with frame tokens the row.
+  const double per_pair_frames = fr.mean;
+  const double pair_bytes = (4.0 + 0.125) * double(U) * per_pair_frames + 8.0 * per_pair_frames +
+                            12.0 * std::min(L, U) + 8.0 + 8.0 * L +
+                            (token_scores_dev ? 4.0 * per_pair_frames + 4.0 * L : 0.0) +
+                            (frame_tokens_dev ? 4.0 * x.M : 0.0);
+  const int64_t per_pair = (std::max<int64_t>(int64_t(fr.maxT), 1) + 31) / 32 * U;  // words
+  a.pair_stride = per_pair;
+  for_pair_slices(pairs, 4 * per_pair, kAsgTokenAlignScratch, [&](int64_t p0, int64_t cnt) {
+    DevMemP words = rt.alloc(size_t(4 * per_pair * cnt));
+    a.bp = words->as<unsigned>();
+    a.pair0 = p0;
+    a.count = int(cnt);
+    GTNX_PROF("asg_token_align", pair_bytes * double(cnt));
+    launch_asg_token_align(a, rt.stream());
+    // (the words go back to the stream-ordered pool behind the launch)
+  });
+  g_asg_token_align.add(1, pairs);
 }
 
 }  // namespace gtnx

@@ -1011,6 +1011,23 @@ GTNX_API gtnx_status_t gtnx_batch_asg_score_grad(gtnx_batch_t ems, const int* fr
 GTNX_API gtnx_status_t gtnx_batch_asg_score_stats(int64_t* calls, int64_t* pairs) {
   return guard([&] { batch_asg_score_stats(calls, pairs); });
 }
+GTNX_API gtnx_status_t gtnx_batch_asg_token_align(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                                  const void* tokens_device, int64_t row_stride,
+                                                  const void* lengths_device, int N, int L, int max_length,
+                                                  void* scores_device, void* starts_device, void* ends_device,
+                                                  void* token_scores_device, int64_t out_stride,
+                                                  void* frame_tokens_device, int64_t frame_stride) {
+  return guard([&] {
+    batch_asg_token_align(BH(ems), frames, static_cast<const float*>(table_device),
+                          static_cast<const int*>(tokens_device), row_stride, static_cast<const int*>(lengths_device), N,
+                          L, max_length, static_cast<float*>(scores_device), static_cast<int*>(starts_device),
+                          static_cast<int*>(ends_device), static_cast<float*>(token_scores_device), out_stride,
+                          static_cast<int*>(frame_tokens_device), frame_stride);
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_asg_token_align_stats(int64_t* calls, int64_t* pairs) {
+  return guard([&] { batch_asg_token_align_stats(calls, pairs); });
+}
 GTNX_API gtnx_status_t gtnx_batch_linear_shape(gtnx_batch_t ems, int* rows, int* labels) {
   return guard([&] {
     const BatchP& b = BH(ems);

@@ -992,6 +992,27 @@ struct CtcTokenAlignArgs {
   int count, N, L, U, M, C, blank;
 };
 void launch_ctc_token_align(const CtcTokenAlignArgs& a, hipStream_t st);
+// asg_token_align.hip: the best alignment (max-plus, the arithmetic and the tie rule of asg_align.hip: of equals the
+// step) of the pairs pair0 .. pair0 + count - 1 of asg_score.hip's hypothesis form (the contract: DESIGN section 28).
+// One workgroup per pair, width and positions per lane from asg_score_config(U); the outputs are those of
+// CtcTokenAlignArgs, frame_tokens never -1 inside a path.  table: [C + C * C] as in AsgScoreArgs.  bp: the back-pointers
+// of the launch, 1 bit per position and frame, word (t / 32) * U + i of the pair_stride words of workgroup blockIdx.x.
+struct AsgTokenAlignArgs {
+  const GTNX_G float* em;      // [n][M][C]
+  const GTNX_G int* frames;    // [n]
+  const GTNX_G int* tokens;    // pair p's row at tokens + p * row_stride
+  const GTNX_G int* lengths;   // [pairs]
+  const GTNX_G float* table;   // [C + C * C]
+  GTNX_G float* scores;        // [pairs]
+  GTNX_G int* starts;          // pair p's row at starts + p * out_stride, width L
+  GTNX_G int* ends;            // the same
+  GTNX_G float* token_scores;  // the same, or null
+  GTNX_G int* frame_tokens;    // pair p's row at frame_tokens + p * frame_stride, width M, or null
+  GTNX_G unsigned* bp;         // [count][pair_stride]
+  int64_t row_stride, out_stride, frame_stride, pair0, pair_stride;
+  int count, N, L, U, M, C;
+};
+void launch_asg_token_align(const AsgTokenAlignArgs& a, hipStream_t st);
 // materialise a KIND_LINEAR graph's arc arrays
 void launch_linear_materialize(int M, int C, int* src, int* dst, int* il, int* ol, hipStream_t st);
 

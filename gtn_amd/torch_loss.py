@@ -1,6 +1,6 @@
 """PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
 `asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_beam_decode`, `asg_beam_decode`, `edit_distance`, `ctc_score`,
-`ctc_token_align` and `asg_score`.
+`ctc_token_align`, `asg_score` and `asg_token_align`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -40,6 +40,7 @@ _ARGTYPES = {
     "gtn_asg_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
     "gtn_asg_beam_decode_n": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P],
+    "gtn_asg_token_align_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
 }
 
 
@@ -259,7 +260,7 @@ def _frame_counts(name, input_lengths, B, T, low):
 
 
 def _hypothesis_args(who, computed, x, x_name, tokens, lengths, blank, input_lengths, max_length, own_checks=None):
-    """What `ctc_score`, `asg_score` and `ctc_token_align` check and normalise alike.  `x`: the emissions, `x_name` in
+    """What `ctc_score`, `asg_score`, `ctc_token_align` and `asg_token_align` check and normalise alike.  `x`: the emissions, `x_name` in
     the texts; `computed`: what the texts say the device computes; `blank`: None where there is none; `own_checks(C)`:
     the caller's own value checks, which return the (tensor or None, name) pairs that have to be on x's device as well.
     Returns (B, T, C, N, L, flat, tok, ln, frames, max_length): `flat` says tokens was [B, L]; tok is int32 [B, N, L]
@@ -957,6 +958,75 @@ def ctc_token_align(log_probs, tokens, lengths, blank=0, input_lengths=None, max
                 starts.data_ptr(), ends.data_ptr(), _ptr(tsc), _ptr(ftk)),
                "ctc_token_align", tok.data_ptr(), ln.data_ptr(), scores.data_ptr(), starts.data_ptr(), ends.data_ptr(),
                _ptr(tsc), _ptr(ftk), frames, blank, max_length, N=N, L=L, row_stride=W, out_stride=W, frame_stride=F)
+    out = [scores, starts[:, :, :L], ends[:, :, :L]]
+    if return_token_scores:
+        out.append(tsc[:, :, :L])
+    if return_frames:
+        out.append(ftk[:, :, :T])
+    if flat:
+        out = [o.reshape(B, *o.shape[2:]) for o in out]
+    return tuple(out)
+
+
+def asg_token_align(emissions, transitions, tokens, lengths, start=None, input_lengths=None, max_length=None,
+                    return_token_scores=False, return_frames=False):
+    """When each token of each device-resident ASG hypothesis was spoken, and how well the frames support it: the best
+    alignment (the reference's viterbiPath over emissions[b, :T_b] o (forceAlign(tokens[b, k, :len]) o transitions)) of
+    all B * N hypotheses in one call against the B shared slabs -- no download of the tokens, no wait, no host loop over
+    frames.  It takes the tensors where `asg_beam_decode` or `asg_decode(collapse=True)` left them.
+    emissions, transitions, start, tokens ([B, N, L] or [B, L]), lengths (int32 or int64, clamped to 0 .. L on the
+    device), input_lengths and max_length (1 .. 4096, default min(L, T, 4096)) are those of `asg_score`; transitions and
+    start are detached.  There is no cap on the number of labels of this call's own.
+    Returns (scores, starts, ends[, token_scores][, frame_tokens]) on emissions.device:
+      scores        float32 [B, N] (or [B]): the score of the best path (emissions, start and transitions), -inf without
+                    one;
+      starts, ends  int32 [B, N, L] (or [B, L]): the first frame of token i and one past its last; with a path starts[0]
+                    is 0, ends[i] is starts[i + 1] and ends[len - 1] is T_b; -1 for i >= len and for a pair without a
+                    path;
+      token_scores  float32, same shape (return_token_scores): the sum of emissions[b, t, token] over the token's frames,
+                    emissions only; -inf where starts is -1.  With normalised emissions exp(token_scores / (ends -
+                    starts)) is the same per-token confidence as `ctc_token_align`'s;
+      frame_tokens  int32 [B, N, T] (or [B, T]) (return_frames): the token index of every frame, never -1 inside a path,
+                    -1 from T_b on -- the `tokens` plane of `asg_forced_align`.
+    A pair has no path exactly where `asg_score` gives -inf: the length is 0 (a beam slot without a hypothesis), T_b is
+    below the length, the length is above max_length, a token inside the length is outside 0 .. C - 1, or every
+    alignment crosses a -inf emission, transition or start score.  Float32 max-plus with the arithmetic of
+    `asg_forced_align` (its scores and tokens bit for bit where both apply); of two exactly equal candidates the step
+    wins: the same bits every time.  No autograd.  Runs on the caller's stream and does not wait."""
+    def tables(C_):
+        if not (torch.is_tensor(transitions) and tuple(transitions.shape) == (C_, C_)):
+            raise ValueError(f"asg_token_align: transitions must be [{C_}, {C_}]")
+        if start is not None and not (torch.is_tensor(start) and tuple(start.shape) == (C_,)):
+            raise ValueError(f"asg_token_align: start must be [{C_}]")
+        if C_ < 1:
+            raise ValueError("asg_token_align: no labels")
+        return (transitions, "transitions"), (start, "start")
+    B, T, C_, N, L, flat, tok, ln, frames, max_length = _hypothesis_args(
+        "asg_token_align", "alignments", emissions, "emissions", tokens, lengths, None, input_lengths, max_length, tables)
+    x = emissions.detach().contiguous()
+    # (written on the caller's stream BEFORE the engine is pointed at it, as in asg_beam_decode)
+    st = torch.zeros(C_, dtype=torch.float32, device=x.device) if start is None else start
+    table = _asg_weights(st, transitions)
+    stream = _engine_stream(x.device)
+    # (rows without an element are never written, but they need an address: a width of at least 1 behind the views)
+    W, F = max(L, 1), max(T, 1)
+    scores = torch.empty(B, N, dtype=torch.float32, device=x.device)
+    starts = torch.empty(B, N, W, dtype=torch.int32, device=x.device)
+    ends = torch.empty(B, N, W, dtype=torch.int32, device=x.device)
+    tsc = torch.empty(B, N, W, dtype=torch.float32, device=x.device) if return_token_scores else None
+    ftk = torch.empty(B, N, F, dtype=torch.int32, device=x.device) if return_frames else None
+    if tok.numel() == 0:
+        tok = tok.new_empty(B, N, 1)
+    if B * N == 0:
+        _engine_done(stream)  # (no pair: nothing to launch, and an empty tensor has no address to hand over)
+    else:
+        native = L == W and T == F and _has_native("asg_token_align", "gtn_asg_token_align_n")
+        _route(stream, x, native, "gtn_asg_token_align_n",
+               (table.data_ptr(), _host_ptr(frames), tok.data_ptr(), ln.data_ptr(), N, L, max_length, scores.data_ptr(),
+                starts.data_ptr(), ends.data_ptr(), _ptr(tsc), _ptr(ftk)),
+               "asg_token_align", tok.data_ptr(), ln.data_ptr(), scores.data_ptr(), starts.data_ptr(), ends.data_ptr(),
+               _ptr(tsc), _ptr(ftk), frames, table.data_ptr(), max_length, N=N, L=L, row_stride=W, out_stride=W,
+               frame_stride=F)
     out = [scores, starts[:, :, :L], ends[:, :, :L]]
     if return_token_scores:
         out.append(tsc[:, :, :L])

@@ -300,6 +300,19 @@ inline void ctcTokenAlign(const Batch& ems, const int* tokensDevice, int64_t row
                                            maxLength, scoresDevice, startsDevice, endsDevice, tokenScoresDevice,
                                            outStride, frameTokensDevice, frameStride));
 }
+/** The best ASG alignment of all n * N device-resident hypotheses (the form and the table of asgScore) under the slabs
+ *  of a Batch::linear, results left on the device: the outputs are those of ctcTokenAlign, frameTokensDevice never -1
+ *  inside a path (ASG has no blank).  Positions i = 0 .. len - 1, a frame enters i from i or i - 1; float32 max-plus
+ *  alpha + (w + e), of two equal candidates the step, as viterbiAlign's ASG launch: reproducible bit for bit.  No path
+ *  where asgScore gives -inf.  No copy back, no wait -- gtnx_batch_asg_token_align */
+inline void asgTokenAlign(const Batch& ems, const float* tableDevice, const int* tokensDevice, int64_t rowStride,
+                          const int* lengthsDevice, int N, int L, int maxLength, float* scoresDevice, int* startsDevice,
+                          int* endsDevice, float* tokenScoresDevice, int64_t outStride,
+                          int* frameTokensDevice = nullptr, int64_t frameStride = 0, const int* frames = nullptr) {
+  detail::check(gtnx_batch_asg_token_align(ems.handle(), frames, tableDevice, tokensDevice, rowStride, lengthsDevice, N,
+                                           L, maxLength, scoresDevice, startsDevice, endsDevice, tokenScoresDevice,
+                                           outStride, frameTokensDevice, frameStride));
+}
 inline void backward(const Batch& a, bool retainGraph = false) { detail::check(gtnx_batch_backward(a.handle(), retainGraph)); }
 } // namespace batched
 

@@ -584,6 +584,50 @@ gtnx_status_t gtnx_batch_asg_score_grad(gtnx_batch_t ems, const int* frames, con
                                         void* grad_emissions_device, void* grad_table_device);
 /* calls of either kind that have launched so far (process-wide) / pairs they took */
 gtnx_status_t gtnx_batch_asg_score_stats(int64_t* calls, int64_t* pairs);
+/* The best ASG alignment of those hypotheses: WHEN each token was spoken and how well the frames support it, for all
+ * n * N pairs in one call, results left on the device (DESIGN section 28 holds the contract).  The inputs are those of
+ * gtnx_batch_asg_score with the same meaning: pair (b, k) is y = tokens[b][k][0 .. len), len = clamp(lengths[b][k], 0,
+ * L), under emissions_b[0 .. T_b); table_device is float32 [C + C * C], entry y is start[y], entry C + i * C + j is
+ * transitions[i][j], label j followed by label i; its indices are computed in 64 bits and the call has no cap on C of
+ * its own.  Position i = 0 .. len - 1 means the first i + 1 labels are consumed; a frame enters i from i (self) and
+ * from i - 1 (step); paths start in position 0 at frame 0 and end in position len - 1 behind frame T_b - 1.  Equal
+ * neighbouring tokens are legal, there is no blank.  Float32 max-plus with the association of
+ * gtnx_batch_viterbi_align's ASG launch, so that the scores are bit-equal to it where both apply: with w_self[i] =
+ * tr[y_i][y_i], w_step[i] = tr[y_i][y_{i-1}] and w_step[0] = start[y_0],
+ *   alpha_0[0] = 0.0f + (w_step[0] + e(0, y_0)), every other alpha_0[i] = -inf;
+ *   c0 = alpha_{t-1}[i] + (w_self[i] + e(t, y_i)), c1 = alpha_{t-1}[i-1] + (w_step[i] + e(t, y_i));
+ *   alpha_t[i] = max(c0, c1), exact; of two equal candidates THE STEP WINS (c1 >= c0), the choice of viterbiPath on
+ *   this lattice.  Every output is reproducible bit for bit.
+ *   scores_device       float32 [n][N]: alpha_{T_b - 1}[len - 1], -inf without a path
+ *   starts_device,      int32, n * N rows of width L, out_stride (>= L) elements apart: the first frame of token i and
+ *   ends_device         one past its last frame; with a path starts[0] == 0, ends[i] == starts[i + 1], ends[len - 1] ==
+ *                       T_b; -1 for i >= len and in every entry of a pair without a path
+ *   token_scores_device float32, same layout, or null: the sum of e(t, y[i]) over the token's frames, added in
+ *                       ascending frame order from the first frame's value, emissions only; -inf where starts is -1
+ *   frame_tokens_device int32, n * N rows of width M, frame_stride (>= M) apart, or null: the token index of every
+ *                       frame, never -1 inside a path; -1 from T_b on and in every entry of a pair without a path
+ * Every element of every row is written over the widths L and M, nothing beyond them.  A pair has no path exactly where
+ * gtnx_batch_asg_score gives -inf: len == 0 (a beam slot without a hypothesis: rows of -1 and -inf), T_b < len, len >
+ * max_length, a token inside the length outside 0 .. C - 1 (checked before it becomes an address), a -inf emission or
+ * table entry on every alignment.  Elements at or past a length and emission rows at or past T_b are never read; the
+ * inputs are only read.  NaN or +inf inputs give unspecified values and no access outside the pair's own rows.
+ * GTNX_INVALID_ARGUMENT before a device is asked for: a null table, scores, starts or ends pointer, a negative
+ * out_stride or frame_stride, out_stride < L, then what gtnx_batch_asg_score refuses about the batch, tokens, lengths,
+ * N, L, row_stride and max_length (1 .. 4096).  n * N == 0 returns without touching a device.  With the device: not a
+ * gtnx_batch_linear / _rows batch, a frame count outside 0 .. M, frame_stride < M with frame tokens, table_device
+ * anything but memory allocated on the engine's current device, an output the engine's current device may not write.
+ * A refused call writes nothing.
+ * One workgroup per pair (asg_token_align.hip).  The back-pointers take 1 bit per position and frame in scratch from
+ * the stream-ordered pool, ceil(max_b T_b / 32) * max_length words per pair, at most 256 MiB per launch; beyond that
+ * the pairs run in slices with the same bits (GTNX_ASG_TOKEN_ALIGN_SCRATCH_BYTES, read per call, lowers the cap: a
+ * debug switch for tests); a single pair above the cap runs alone.  Nothing is copied back, the call does not wait. */
+gtnx_status_t gtnx_batch_asg_token_align(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                         const void* tokens_device, int64_t row_stride, const void* lengths_device,
+                                         int N, int L, int max_length, void* scores_device, void* starts_device,
+                                         void* ends_device, void* token_scores_device, int64_t out_stride,
+                                         void* frame_tokens_device, int64_t frame_stride);
+/* calls that have launched so far (process-wide) / pairs they aligned */
+gtnx_status_t gtnx_batch_asg_token_align_stats(int64_t* calls, int64_t* pairs);
 /* ASG prefix beam search with N-best output over the n emission slabs of a gtnx_batch_linear / _rows batch
  * ([n][M][C]), results left on the device.  The hypotheses are the label sequences WITHOUT EQUAL
  * NEIGHBOURS -- what gtnx_batch_viterbi_decode's collapsed rows can hold -- each summed over all of its alignments
