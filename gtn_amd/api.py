@@ -1280,6 +1280,19 @@ def make_api(lib):
         the ones whose product was too large to rebuild and replay the reference's queue on (include/gtn_amd.h)"""
         return _stats2(lib.gtnx_debug_viterbi_ties)
 
+    def debug_shortest_routes():
+        """{cell name: launches since the process started} of the built-graph shortest-distance kernels
+        (gtn_amd/csrc/shortest.hip; include/gtn_amd.h: gtnx_debug_shortest_routes).  Needs no GPU."""
+        n = C.c_int(0)
+        check(lib.gtnx_debug_shortest_routes(-1, None, 0, None, C.byref(n)))
+        out = {}
+        for cell in range(n.value):
+            buf = C.create_string_buffer(48)
+            cnt = C.c_int64(0)
+            check(lib.gtnx_debug_shortest_routes(cell, buf, 48, C.byref(cnt), None))
+            out[buf.value.decode()] = int(cnt.value)
+        return out
+
     def debug_align_stats():
         """(fast, fallback): utterances Batch.viterbi_align has aligned so far by its one launch / through the path
         graphs of viterbi_path (include/gtn_amd.h: gtnx_batch_align_stats)"""
@@ -1420,6 +1433,8 @@ def make_api(lib):
     ns.edit_distance = edit_distance
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties
+    if hasattr(lib, "gtnx_debug_shortest_routes"):  # (the engine's kernels: not in the reference-backed shim)
+        ns.debug_shortest_routes = debug_shortest_routes
 
     def debug_tie_ranks(g):
         """(queue_rank, creation_rank) of a CTC-shaped target's nodes, or None (gtn_amd.h: gtnx_debug_tie_ranks)"""

@@ -1131,6 +1131,16 @@ GTNX_API gtnx_status_t gtnx_debug_route_name(int route, char* buf, size_t cap) {
     }
   });
 }
+GTNX_API gtnx_status_t gtnx_debug_shortest_routes(int cell, char* buf, size_t cap, int64_t* launches, int* n_cells) {
+  return guard([&] {
+    if (buf && cap) {
+      std::strncpy(buf, sd_route_name(cell), cap - 1);
+      buf[cap - 1] = 0;
+    }
+    if (launches) *launches = sd_route_launches(cell);
+    if (n_cells) *n_cells = sd_route_cells();
+  });
+}
 GTNX_API gtnx_status_t gtnx_prof_names(char* buf, size_t cap) {
   return guard([&] {
     std::string s = Runtime::get().prof_names();

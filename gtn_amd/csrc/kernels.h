@@ -192,6 +192,11 @@ int sd_narrow_ring_backward();
 void launch_sd_backward(const SdArgs* d_args, int n, int mode, int narrow, int avg_out_degree_x16, hipStream_t st,
                         int fuse_lds_bytes = 0);
 void sd_narrow_fuse_caps(int* cap_fixed, int* cap_chain);
+// diagnostics: launches per kernel cell (direction / family / mode / lanes per node) since the process started, counted
+// on the host by the four launch functions above (gtn_amd.h: gtnx_debug_shortest_routes)
+int sd_route_cells();
+const char* sd_route_name(int cell);  // "" outside [0, sd_route_cells())
+int64_t sd_route_launches(int cell);
 
 // viterbiPath pointer chase (shortest.cpp:239-245): writes path arc ids first-arc-first
 struct PathArgs {

@@ -1287,7 +1287,40 @@ int pick_group(int avg_deg_x16) {
   return 1;
 }
 
+// ---- route counters (diagnostics; host side only): one per kernel the launch functions below can pick
+enum : int {
+  RT_FWD_GENERIC = 0,  // + 4 * mode + (g = 1, 8, 64, 256 -> 0..3)
+  RT_FWD_NARROW = 12,
+  RT_FWD_NARROW_INW = 13,
+  RT_FWD_NARROW_TROP = 14,
+  RT_FWD_NARROW_PATH = 15,
+  RT_FWD_DEEP = 16,
+  RT_BWD_GENERIC = 17,  // + 4 * mode + g index (log and tropical only)
+  RT_BWD_NARROW = 25,
+  RT_BWD_NARROW_FUSED = 26,
+  RT_BWD_DEEP = 27,
+  RT_CELLS = 28
+};
+const char* const kRouteNames[RT_CELLS] = {
+    "fwd/generic/log/g1",      "fwd/generic/log/g8",      "fwd/generic/log/g64",      "fwd/generic/log/g256",
+    "fwd/generic/tropical/g1", "fwd/generic/tropical/g8", "fwd/generic/tropical/g64", "fwd/generic/tropical/g256",
+    "fwd/generic/path/g1",     "fwd/generic/path/g8",     "fwd/generic/path/g64",     "fwd/generic/path/g256",
+    "fwd/narrow/log",          "fwd/narrow/log/inw",      "fwd/narrow/tropical/inw",  "fwd/narrow/path/inw",
+    "fwd/deep",
+    "bwd/generic/log/g1",      "bwd/generic/log/g8",      "bwd/generic/log/g64",      "bwd/generic/log/g256",
+    "bwd/generic/tropical/g1", "bwd/generic/tropical/g8", "bwd/generic/tropical/g64", "bwd/generic/tropical/g256",
+    "bwd/narrow",              "bwd/narrow/fused",        "bwd/deep"};
+std::atomic<int64_t> g_route_launches[RT_CELLS];
+void count_route(int cell) { g_route_launches[cell].fetch_add(1, std::memory_order_relaxed); }
+int group_index(int g) { return g >= 256 ? 3 : g >= 64 ? 2 : g >= 8 ? 1 : 0; }
+
 } // namespace
+
+int sd_route_cells() { return RT_CELLS; }
+const char* sd_route_name(int cell) { return cell >= 0 && cell < RT_CELLS ? kRouteNames[cell] : ""; }
+int64_t sd_route_launches(int cell) {
+  return cell >= 0 && cell < RT_CELLS ? g_route_launches[cell].load(std::memory_order_relaxed) : 0;
+}
 
 int sd_narrow_ring() { return kRing; }
 int sd_narrow_tmp_cap() { return kCA; }
@@ -1305,6 +1338,7 @@ void launch_sd_forward_deep(const SdArgs* d_args, int n, int maxP, hipStream_t s
   if (gtnx_first_on_device first{done})
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sd_forward_deep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               int(deep_lds_bytes(kDeepP, false)));
+  count_route(RT_FWD_DEEP);
   hipLaunchKernelGGL(sd_forward_deep_kernel, dim3(n), dim3(64), deep_lds_bytes(maxP, false), st, d_args);
 }
 void launch_sd_backward_deep(const SdArgs* d_args, int n, int maxP, hipStream_t st) {
@@ -1313,6 +1347,7 @@ void launch_sd_backward_deep(const SdArgs* d_args, int n, int maxP, hipStream_t 
   if (gtnx_first_on_device first{done})
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sd_backward_deep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               int(deep_lds_bytes(kDeepP, true)));
+  count_route(RT_BWD_DEEP);
   hipLaunchKernelGGL(sd_backward_deep_kernel, dim3(n), dim3(64), deep_lds_bytes(maxP, true), st, d_args);
 }
 
@@ -1320,6 +1355,7 @@ void launch_sd_forward(const SdArgs* d_args, int n, int mode, int narrow,
                        int avg_in_degree_x16, hipStream_t st) {
   if (n <= 0) return;
   if (narrow && mode == SD_LOG) {
+    count_route(narrow == 2 ? RT_FWD_NARROW_INW : RT_FWD_NARROW);
     if (narrow == 2)
       hipLaunchKernelGGL(sd_forward_narrow_kernel<true>, dim3(n), dim3(kBlock), 0, st, d_args);
     else
@@ -1327,14 +1363,17 @@ void launch_sd_forward(const SdArgs* d_args, int n, int mode, int narrow,
     return;
   }
   if (narrow == 2 && mode == SD_TROPICAL) {  // row-ordered weights + arc ids of the in-row slots
+    count_route(RT_FWD_NARROW_TROP);
     hipLaunchKernelGGL((sd_forward_narrow_kernel<true, true>), dim3(n), dim3(kBlock), 0, st, d_args);
     return;
   }
   if (narrow == 2 && mode == SD_PATH) {
+    count_route(RT_FWD_NARROW_PATH);
     hipLaunchKernelGGL((sd_forward_narrow_kernel<true, true, true>), dim3(n), dim3(kBlock), 0, st, d_args);
     return;
   }
   const int g = pick_group(avg_in_degree_x16);
+  count_route(RT_FWD_GENERIC + 4 * mode + group_index(g));
   if (mode == SD_LOG)
     launch_fwd_mode<SD_LOG>(d_args, n, g, st);
   else if (mode == SD_TROPICAL)
@@ -1353,11 +1392,13 @@ void launch_sd_backward(const SdArgs* d_args, int n, int mode, int narrow, int a
                         int fuse_lds_bytes) {
   if (n <= 0) return;
   if (narrow && mode == SD_LOG) {
+    count_route(narrow == 2 ? RT_BWD_NARROW_FUSED : RT_BWD_NARROW);
     if (narrow == 2) hipLaunchKernelGGL(sd_backward_narrow_kernel<true>, dim3(n), dim3(kBlock), size_t(fuse_lds_bytes), st, d_args);
     else hipLaunchKernelGGL(sd_backward_narrow_kernel<false>, dim3(n), dim3(kBlock), 0, st, d_args);
     return;
   }
   const int g = pick_group(avg_out_degree_x16);
+  count_route(RT_BWD_GENERIC + 4 * (mode == SD_LOG ? 0 : 1) + group_index(g));
   if (mode == SD_LOG)
     launch_bwd_mode<SD_LOG>(d_args, n, g, st);
   else

@@ -749,6 +749,13 @@ gtnx_status_t gtnx_prof_names(char* buf, size_t cap);
  * "maxplus", "walk" (gtnx_debug_route_name), or -1 when `g` is not a symbolic product.  No reference analogue. */
 gtnx_status_t gtnx_debug_symbolic_route(gtnx_graph_t g, int tropical, int* route);
 gtnx_status_t gtnx_debug_route_name(int route, char* buf, size_t cap);
+/* Diagnostics (host only, no GPU needed): which kernel of gtn_amd/csrc/shortest.hip the forwardScore / viterbiScore /
+ * viterbiPath sweeps of BUILT graphs and their gradients were given to.  Cell `cell` of *n_cells: its name
+ * ("fwd/generic/log/g8", "fwd/narrow/log/inw", "fwd/deep", "bwd/generic/tropical/g64", "bwd/narrow/fused", ...:
+ * direction / family / semiring or mode / lanes per node) into buf, and the number of launches it took since the
+ * process started into *launches.  A cell outside [0, *n_cells) gives an empty name and 0.  Any pointer may be NULL.
+ * No reference analogue. */
+gtnx_status_t gtnx_debug_shortest_routes(int cell, char* buf, size_t cap, int64_t* launches, int* n_cells);
 
 #ifdef __cplusplus
 }
