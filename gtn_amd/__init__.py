@@ -15,6 +15,7 @@ _api = make_api(_lib)
 
 Graph = _api.Graph
 Batch = _api.Batch
+LmGraph = _api.LmGraph  # (a language model graph compiled for Batch.ctc_beam_decode(lm=...))
 epsilon = _api.epsilon
 negate = _api.negate
 add = _api.add

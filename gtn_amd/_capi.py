@@ -137,6 +137,12 @@ _SIGS = {
                                    C.c_void_p, C.c_void_p],
     "gtnx_batch_ctc_beam_decode_lm": [c_graph, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float,
                                       C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "gtnx_batch_ctc_beam_decode_graph": [c_graph, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float,
+                                         C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "gtnx_lm_graph_create": [c_graph, C.POINTER(C.c_void_p)],
+    "gtnx_lm_graph_destroy": [C.c_void_p],
+    "gtnx_lm_graph_walk": [C.c_void_p, C.c_int, C.c_int, c_f32_p, c_i32_p],
+    "gtnx_lm_graph_info": [C.c_void_p, C.c_void_p],
     "gtnx_batch_ctc_beam_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_linear_shape": [c_graph, c_i32_p, c_i32_p],
     "gtnx_batch_edit_distance": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int,
@@ -225,7 +231,7 @@ def load(path=None):
         except AttributeError:
             # engine extensions (batch records, borrowed tensors, collectives between devices): absent from the reference-backed
             # test shim (oracle/ref_shim.cpp), which only tests/refbackend/gtn_ref.py loads
-            if name.startswith("gtnx_batch_") or name.startswith("gtnx_comm_") or name in ("gtnx_linear_graph_borrow_n", "gtnx_grads_bind_device_n",
+            if name.startswith(("gtnx_batch_", "gtnx_comm_", "gtnx_lm_graph_")) or name in ("gtnx_linear_graph_borrow_n", "gtnx_grads_bind_device_n",
                                                              "gtnx_parallel_enter", "gtnx_parallel_leave", "gtnx_parallel_flush",
                                                              "gtnx_debug_shortest_routes"):
                 continue

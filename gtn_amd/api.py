@@ -665,6 +665,61 @@ def make_api(lib):
     ns.items_to_device = items_to_device
     ns.grads_to_device = grads_to_device
 
+    # ---------------------------------------------------------------- compiled LM graphs (gtnx_lm_graph_*)
+    class _LmGraphInfo(C.Structure):
+        _fields_ = [("num_states", C.c_int64), ("num_arcs", C.c_int64), ("start_state", C.c_int32),
+                    ("longest_epsilon_chain", C.c_int32)]
+
+    class LmGraph:
+        """A language model held as a Graph, compiled for `Batch.ctc_beam_decode(lm=...)` (gtnx_lm_graph_create; DESIGN
+        section 30): a deterministic acceptor with back-off (failure) arcs -- an n-gram model in ARPA form, or a lexicon
+        or grammar acceptor that forbids label sequences.  A SNAPSHOT of the graph's input labels and weights at this
+        moment: later changes of `graph` are not seen, and there is no autograd.  Output labels and accept flags are
+        ignored (an n-gram acceptor accepts everywhere; end-of-sentence handling is out of scope).  The arcs need not be
+        sorted.  Compiling and `walk` are host work and need no GPU; the first decode uploads the compiled form.
+        ValueError, nothing is repaired: no start node or several, two arcs with one input label out of a node, several
+        epsilon arcs out of a node, an epsilon chain that is cyclic or longer than 8 arcs, a label below -1, more than
+        2^24 nodes."""
+
+        __slots__ = ("_h", "__weakref__")
+
+        def __init__(self, graph):
+            self._h = None
+            h = C.c_void_p()
+            check(lib.gtnx_lm_graph_create(graph._h, C.byref(h)))
+            self._h = h.value
+
+        def destroy(self):
+            """let go of the compiled form now; a decode with this object is refused from here on"""
+            h, self._h = self._h, None
+            if h:
+                check(lib.gtnx_lm_graph_destroy(h))
+
+        def __del__(self):
+            h = getattr(self, "_h", None)
+            if h:
+                try:
+                    lib.gtnx_lm_graph_destroy(h)
+                except Exception:
+                    pass
+                self._h = None
+
+        def walk(self, state, label):
+            """(weight, next_state) of `label` from `state`, failure-arc semantics: the arc labelled `label` if the
+            state has one, else its epsilon arc and the same question at its destination; the weight is the float32
+            sum of the walked weights in walk order.  A forbidden label gives (-inf, -1)."""
+            w, nx = C.c_float(), C.c_int()
+            check(lib.gtnx_lm_graph_walk(self._h, int(state), int(label), C.byref(w), C.byref(nx)))
+            return w.value, nx.value
+
+        def info(self):
+            """dict: num_states, num_arcs (epsilon arcs included), start_state, longest_epsilon_chain"""
+            i = _LmGraphInfo()
+            check(lib.gtnx_lm_graph_info(self._h, C.byref(i)))
+            return {k: int(getattr(i, k)) for k, _ in _LmGraphInfo._fields_}
+
+    ns.LmGraph = LmGraph
+
     # ---------------------------------------------------------------- batch records (gtnx_batch_*)
     class Batch:
         """B graphs held as one record: what the list forms of the functions return when
@@ -898,7 +953,11 @@ def make_api(lib):
             transitions)`.  A prefix carries L = the sum over its labels of lm_weight * lm(...) + insertion_bonus;
             candidates rank by acoustic total + L, a -inf entry forbids its bigram or first label, row pruning stays
             acoustic.  `scores_out` then gets acoustic + L and `am_scores_out` (float32 [B, nbest], optional) the
-            acoustic total alone; slots without a hypothesis hold -inf in both."""
+            acoustic total alone; slots without a hypothesis hold -inf in both.
+            `lm` may also be an `LmGraph` (gtnx_batch_ctc_beam_decode_graph): a prefix then carries
+            its LM state too, and the table entry of an extension is the weight of the walk of (state, label) through
+            the graph -- failure-arc semantics, see `LmGraph.walk`; a label the walk forbids, or whose weight is not
+            finite, is dropped.  `blank` is never walked.  Everything else is as with the table."""
             n = len(self)
             if lm is None and am_scores_out is not None:
                 raise ValueError("ctc_beam_decode: am_scores_out needs lm")
@@ -915,6 +974,13 @@ def make_api(lib):
                                           (scores_out, "torch.float32", "scores_out must be a float32"),
                                           (am_scores_out, "torch.float32", "am_scores_out must be a float32")))
             fr, fr_ptr = _frames_arg("ctc_beam_decode", frames, n)
+            if isinstance(lm, LmGraph):
+                # (a destroyed object has no handle: the engine refuses the null one)
+                check(lib.gtnx_batch_ctc_beam_decode_graph(self._h, fr_ptr, int(blank), int(beam_size), int(cutoff_top_n),
+                                                           int(nbest), lm._h, float(lm_weight), float(insertion_bonus),
+                                                           _opt_ptr(tokens_out), int(stride), _opt_ptr(lengths_out),
+                                                           _opt_ptr(scores_out), _opt_ptr(am_scores_out)))
+                return
             if lm is not None:
                 check(lib.gtnx_batch_ctc_beam_decode_lm(self._h, fr_ptr, int(blank), int(beam_size), int(cutoff_top_n),
                                                         int(nbest), _opt_ptr(lm), float(lm_weight),

@@ -111,6 +111,19 @@ GTN_EXPORT int gtn_ctc_beam_decode_lm_n(const void* emissions, int B, int T, int
   });
 }
 
+// The same with a compiled LM graph in the table's place.  lm_graph: a handle of gtnx_lm_graph_create (libgtn_amd.so),
+// passed through as a pointer: both libraries live in one process.
+GTN_EXPORT int gtn_ctc_beam_decode_graph_n(const void* emissions, int B, int T, int C, int blank, const int* frames,
+                                           int beam_size, int cutoff_top_n, int nbest, void* lm_graph, float lm_weight,
+                                           float insertion_bonus, void* tokens, void* lengths, void* scores,
+                                           void* am_scores) {
+  return guarded([&] {
+    gtn::criteria::ctcBeamDecodeBatch(emissions, B, T, C, blank, frames, beam_size, cutoff_top_n, nbest,
+                                      static_cast<gtnx_lm_graph_t>(lm_graph), lm_weight, insertion_bonus, tokens, lengths,
+                                      scores, am_scores);
+  });
+}
+
 // Exact CTC log scores of B * N device-resident hypotheses.  emissions: DEVICE float32 [B][T][C]; frames: HOST int [B] or
 // null; tokens: DEVICE int32 [B][N][L]; lengths: DEVICE int32 [B][N]; scores: DEVICE float32 [B][N].
 GTN_EXPORT int gtn_ctc_score_n(const void* emissions, int B, int T, int C, int blank, const int* frames,

@@ -214,6 +214,33 @@ inline void ctcBeamDecodeBatch(
                          static_cast<float*>(amScoresDev), blank, beamSize, cutoffTopN, nbest, frames);
 }
 
+/** The same search with a compiled LM graph in the table's place (gtnx_batch_ctc_beam_decode_graph has the contract):
+ *  `lmGraph` is the handle of a gtn::batched::LmGraph or of gtnx_lm_graph_create -- it is passed on as it is, the engine
+ *  refuses one that is not live. */
+inline void ctcBeamDecodeBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int C,
+    int blank,
+    const int* frames,
+    int beamSize,
+    int cutoffTopN,
+    int nbest,
+    gtnx_lm_graph_t lmGraph,
+    float lmWeight,
+    float insertionBonus,
+    void* tokensDev,
+    void* lengthsDev,
+    void* scoresDev,
+    void* amScoresDev) {
+  Batch ems = Batch::linear(B, T, C, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  detail::check(gtnx_batch_ctc_beam_decode_graph(ems.handle(), frames, blank, beamSize, cutoffTopN, nbest, lmGraph,
+                                                 lmWeight, insertionBonus, static_cast<int*>(tokensDev), T,
+                                                 static_cast<int*>(lengthsDev), static_cast<float*>(scoresDev),
+                                                 static_cast<float*>(amScoresDev)));
+}
+
 /** The exact log scores of B * N device-resident hypotheses under the B emission slabs, and (with weightsDev and gradDev)
  *  the gradient sum_k weights[b][k] * d score[b][k] / d emissions_b: `emissions` device float32 [B][T][C], read in
  *  place; `tokensDev` device int32 [B][N][L] (dense rows); `lengthsDev` device int32 [B][N]; `frames` host [B] or null;

@@ -192,10 +192,17 @@ void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int 
 // than 2^19 labels, a table that is not memory allocated on the current device (pageable, pinned or registered host
 // memory and managed memory are all refused: the kernel gathers from it), an am_scores_dev the device may not write.
 // Counted by batch_ctc_beam_stats like the call above.
+// With a compiled LM graph in the table's place (lm_graph.h): `graph` is a handle of
+// lm_graph_register and table_dev is null.  A prefix then also carries its LM state, an extension's table entry is the
+// weight of the walk of (state, label) -- failure-arc semantics -- and a label the walk does not find, or whose weight
+// is not finite, is forbidden.  Everything else is as with the table, C <= 2^19 included.  Refused on top, before a
+// device is asked for: a table and a graph together, a handle that is not a live one.  The first decode with a graph
+// uploads it and waits for the copy, once.
 struct CtcBeamLm {
   const float* table_dev;
   float weight, bonus;
   float* am_scores_dev;
+  const void* graph = nullptr;
 };
 void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int beam, int topn, int nbest,
                            const CtcBeamLm* lm, int* tokens_dev, int64_t row_stride, int* lengths_dev, float* scores_dev);

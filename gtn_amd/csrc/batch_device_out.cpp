@@ -20,6 +20,7 @@
 //   its own checks of the shape and of the device, settle_frames(...) for step 3's opening, and for_pair_slices(...)
 //   around launches with scratch per pair.
 #include "batch.h"
+#include "lm_graph.h"
 
 #include <algorithm>
 #include <atomic>
@@ -539,8 +540,14 @@ void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int 
   if (nbest < 1) throw_invalid("[gtnx_batch_ctc_beam_decode] nbest below 1");
   if (nbest > beam) throw_invalid("[gtnx_batch_ctc_beam_decode] nbest above beam_size");
   if (blank < 0) throw_invalid("[gtnx_batch_ctc_beam_decode] negative blank");
+  LmGraphP lmg;
+  if (lm && lm->graph) {
+    if (lm->table_dev) throw_invalid("[gtnx_batch_ctc_beam_decode] a language model table and an LM graph together");
+    lmg = lm_graph_lookup(lm->graph);
+    if (!lmg) throw_invalid("[gtnx_batch_ctc_beam_decode] not a live LM graph handle (destroyed, or not from gtnx_lm_graph_create)");
+  }
   if (lm) {
-    if (!lm->table_dev) throw_invalid("[gtnx_batch_ctc_beam_decode] null language model table");
+    if (!lm->table_dev && !lmg) throw_invalid("[gtnx_batch_ctc_beam_decode] null language model table");
     if (!std::isfinite(lm->weight) || !std::isfinite(lm->bonus))
       throw_invalid("[gtnx_batch_ctc_beam_decode] lm_weight and insertion_bonus must be finite");
   }
@@ -565,9 +572,11 @@ void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int 
   if (lm) {
     check_outputs_local(kCtcBeam, {lm->am_scores_dev});
     // (the kernel gathers from it: host memory is refused too, with one GPU as well)
-    if (!ptr_device_memory_of(lm->table_dev, rt.device()))
+    if (!lmg && !ptr_device_memory_of(lm->table_dev, rt.device()))
       refuse(kCtcBeam, "the language model table is not memory of the engine's current device");
   }
+  // (uploaded by the first decode that uses it; a graph that lives on another device is refused here)
+  const gtnx_i4* lmg_dev = lmg ? lm_graph_device(*lmg) : nullptr;
   if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
   const std::vector<int> fr = resolve_frames(frames, x);
   // algorithmic bytes.  rows: every emission of the rows that count once, topn + 1 entries and a count out.  search:
@@ -606,6 +615,11 @@ void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int 
     a.lm_weight = lm->weight;
     a.lm_bonus = lm->bonus;
     a.am_scores = lm->am_scores_dev;
+  }
+  if (lmg) {
+    a.lmg = lmg_dev;
+    a.lmg_states = lmg->states;
+    a.lmg_start = lmg->start;
   }
   {
     GTNX_PROF("ctc_beam_rows", row_bytes);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "batch.h"
+#include "lm_graph.h"
 #include "ops.h"
 #include "ops_internal.h"
 #include "region.h"
@@ -917,6 +918,51 @@ GTNX_API gtnx_status_t gtnx_batch_ctc_beam_decode_lm(gtnx_batch_t ems, const int
                        static_cast<float*>(am_scores_device)};
     batch_ctc_beam_decode(BH(ems), frames, blank, beam_size, cutoff_top_n, nbest, &lm, static_cast<int*>(tokens_device),
                           row_stride, static_cast<int*>(lengths_device), static_cast<float*>(scores_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_ctc_beam_decode_graph(gtnx_batch_t ems, const int* frames, int blank, int beam_size,
+                                                        int cutoff_top_n, int nbest, gtnx_lm_graph_t lm_graph,
+                                                        float lm_weight, float insertion_bonus, void* tokens_device,
+                                                        int64_t row_stride, void* lengths_device, void* scores_device,
+                                                        void* am_scores_device) {
+  return guard([&] {
+    if (!lm_graph) throw_invalid("[gtnx_batch_ctc_beam_decode] null LM graph handle");
+    const CtcBeamLm lm{nullptr, lm_weight, insertion_bonus, static_cast<float*>(am_scores_device), lm_graph};
+    batch_ctc_beam_decode(BH(ems), frames, blank, beam_size, cutoff_top_n, nbest, &lm, static_cast<int*>(tokens_device),
+                          row_stride, static_cast<int*>(lengths_device), static_cast<float*>(scores_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_lm_graph_create(gtnx_graph_t g, gtnx_lm_graph_t* out) {
+  return guard([&] {
+    if (!out) throw_invalid("[gtnx_lm_graph_create] null output pointer");
+    *out = reinterpret_cast<gtnx_lm_graph_t>(lm_graph_register(lm_graph_compile(G(g))));
+  });
+}
+GTNX_API gtnx_status_t gtnx_lm_graph_destroy(gtnx_lm_graph_t lm) {
+  return guard([&] {
+    if (lm && !lm_graph_unregister(lm)) throw_invalid("[gtnx_lm_graph_destroy] not a live LM graph handle");
+  });
+}
+GTNX_API gtnx_status_t gtnx_lm_graph_walk(gtnx_lm_graph_t lm, int state, int label, float* weight, int* next_state) {
+  return guard([&] {
+    LmGraphP p = lm_graph_lookup(lm);
+    if (!p) throw_invalid("[gtnx_lm_graph_walk] not a live LM graph handle");
+    float w;
+    int nx;
+    lm_graph_walk(*p, state, label, &w, &nx);
+    if (weight) *weight = w;
+    if (next_state) *next_state = nx;
+  });
+}
+GTNX_API gtnx_status_t gtnx_lm_graph_info(gtnx_lm_graph_t lm, gtnx_lm_graph_info_t* out) {
+  return guard([&] {
+    LmGraphP p = lm_graph_lookup(lm);
+    if (!p) throw_invalid("[gtnx_lm_graph_info] not a live LM graph handle");
+    if (!out) throw_invalid("[gtnx_lm_graph_info] null output pointer");
+    out->num_states = p->states;
+    out->num_arcs = p->arcs;
+    out->start_state = p->start;
+    out->longest_epsilon_chain = p->eps_chain;
   });
 }
 GTNX_API gtnx_status_t gtnx_batch_ctc_beam_stats(int64_t* calls, int64_t* utterances) {

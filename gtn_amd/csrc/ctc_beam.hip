@@ -32,14 +32,20 @@
 //                 1 + t * beam + r = (node of its parent, label)
 //            At the end thread r < nbest walks the parents of slot r and stores the tokens back to front; all threads
 //            fill the rest of the rows with -1.
-// With a bigram table (tests/ctc_beam_lm_fp.py) the search kernel is its LM = true instantiation:
+// With a bigram table (tests/ctc_beam_lm_fp.py) the search kernel is its LM = kLmTable instantiation:
 // every beam also carries L, the table's score of its prefix, candidates rank by acoustic total + L, and pb / pnb stay
 // acoustic.  The gathers inc(i, k) = lm_weight * w(last_i -> label_k) + lm_bonus go out after step 1, when S_t and the
 // last labels are known (wave v takes beams v, v + 4, ..., its lane k member k of the set), fly during step 2 and are
 // parked in LDS before its barrier; step 4 reads them from there.  A key then holds the combined total, so step 6
 // computes an extension's score again, by step 4's expression; for that the key keeps the member's place in the set in
 // its lowest 6 bits, below a label of 19 bits (the engine refuses more labels with a table: it would not fit a device).
-// LM = false is the code above, statement for statement: everything else sits under `if constexpr (LM)`.
+// LM = kLmNone is the code above, statement for statement: everything else sits under `if constexpr (LM != kLmNone)`.
+// With a compiled LM graph (lm_graph.h has the words; tests/ctc_beam_graph_fp.py) it is the third
+// instantiation, LM = kLmGraph: everything the table has, and every beam also carries its LM state (slot 0 starts at the
+// graph's start state, a stay copies it, an extension takes next(i, k)).  Where the table is gathered the thread walks
+// (state_i, label_k) instead -- all its walks together, one probe of each per round, so that the dependent loads of up
+// to 8 walks overlap -- and parks next(i, k) beside inc(i, k).  Every loop of the walk has a compile-time bound, and a
+// walk that exhausts one forbids its extension.
 // No global atomics; nothing depends on the order in which waves arrive (keys are distinct, every slot has one writer).
 // Every store is a plain C++ store; there is no inline assembly.
 #include <hip/hip_runtime.h>
@@ -71,15 +77,24 @@ struct Beams {
   unsigned long long hash[kMaxBeam], phash[kMaxBeam];  // of the prefix / of the prefix without its last label
 };
 
-// what the LM = true kernel keeps in LDS on top of the lists: L of every beam in both list copies, and inc(i, k) of the
-// frame at [i * kMaxSet + k]
-template <bool LM>
+constexpr int kLmNone = 0, kLmTable = 1, kLmGraph = 2;  // what ranks beside the acoustic score
+
+// what the LM kernels keep in LDS on top of the lists: L of every beam in both list copies, and inc(i, k) of the
+// frame at [i * kMaxSet + k]; with a graph also the LM state of every beam and next(i, k)
+template <int LM>
 struct LmLds {
   float L[2][kMaxBeam];
   float inc[kMaxBeam * kMaxSet];
 };
 template <>
-struct LmLds<false> {};
+struct LmLds<kLmNone> {};
+template <>
+struct LmLds<kLmGraph> {
+  float L[2][kMaxBeam];
+  float inc[kMaxBeam * kMaxSet];
+  int st[2][kMaxBeam];
+  int nxt[kMaxBeam * kMaxSet];
+};
 constexpr int kSearchWaves = kSearchBlock / 64;
 constexpr int kIncTrips = kMaxBeam / kSearchWaves;  // gathers a thread holds at most: one per beam of its wave
 
@@ -90,7 +105,98 @@ __device__ __forceinline__ float lm_term(float weight, float w, float bonus) {
   return scaled + bonus;
 }
 
-template <bool LM>
+// The walks of one thread: label c from the states st[q] of the trips q < ntrip, trip q being live when act[q].  A walk
+// is a chain of dependent loads (the state's two words, then one arc word per probe of the bisection, then the next
+// state of the back-off chain), so they advance together: a round loads the next word of every walk, then every walk
+// takes its step.  A walk that is over, or a trip without one, loads word 0.  at[q] is the word a walk reads next
+// (below 2 * states: a state; above: an arc; -1: over), [lo, hi) the arcs that may still hold the label.
+// kWalkChunk trips go together (the trips Q0 .. Q0 + kWalkChunk - 1 of one call): with all 16 in flight the kernel
+// needs 346 registers, only one workgroup fits a compute unit where two of the table's do, and the batch takes twice
+// as long -- measured, DESIGN section 30.  Eight cover a beam of 32 in one pass; a larger beam walks twice.
+// Bounds, all compile-time: a walk visits at most kWalkStates states and probes a state's arcs at most kWalkBisect
+// times, and the rounds stop at their product whatever the words hold.  A walk that runs out of either is forbidden.
+constexpr int kWalkStates = 9, kWalkBisect = 32;
+constexpr int kWalkRounds = kWalkStates * (1 + kWalkBisect);
+constexpr int kWalkChunk = 8;
+template <int Q0>
+__device__ __forceinline__ void lm_walks(const GTNX_G gtnx_i4* g, int states2, int c, int ntrip,
+                                         const int (&st)[kIncTrips], const bool (&act)[kIncTrips],
+                                         float (&wsum)[kIncTrips], int (&next)[kIncTrips]) {
+  const GTNX_G gtnx_i2* g2 = reinterpret_cast<const GTNX_G gtnx_i2*>(g);
+  int at[kWalkChunk], lo[kWalkChunk], hi[kWalkChunk], epsd[kWalkChunk], epsw[kWalkChunk], seen[kWalkChunk];
+#pragma unroll
+  for (int q = 0; q < kWalkChunk; ++q) {
+    at[q] = act[Q0 + q] ? 2 * st[Q0 + q] : -1;
+    lo[q] = hi[q] = 0;
+    epsd[q] = -1;
+    epsw[q] = 0;
+    seen[q] = 0;  // states visited so far, and from bit 8 the probes of this state's arcs
+  }
+  for (int round = 0; round < kWalkRounds; ++round) {
+    gtnx_i4 w0[kWalkChunk];
+    gtnx_i2 w1[kWalkChunk];
+#pragma unroll
+    for (int q = 0; q < kWalkChunk; ++q) {
+      if (Q0 + q >= ntrip) continue;  // (the same in every thread)
+      const int p = at[q] < 0 ? 0 : at[q];
+      w0[q] = g[p];
+      w1[q] = g2[2 * (p + 1)];  // (a state's second word: first label, dense; the form ends with a spare word)
+    }
+    bool more = false;
+#pragma unroll
+    for (int q = 0; q < kWalkChunk; ++q) {
+      if (Q0 + q >= ntrip) continue;
+      if (at[q] < 0) continue;
+      const bool first = (seen[q] & 255) <= 1;  // no back-off weight yet: the sum starts from the first weight
+      if (at[q] < states2) {
+        seen[q] = (seen[q] & 255) + 1;
+        epsd[q] = w0[q].z;
+        epsw[q] = w0[q].w;
+        lo[q] = w0[q].x;
+        hi[q] = w0[q].x + w0[q].y;
+        if (w1[q].y) {  // labels first .. first + count - 1: the one arc it can be
+          const unsigned j = unsigned(c) - unsigned(w1[q].x);
+          if (j < unsigned(w0[q].y)) {
+            lo[q] += int(j);
+            hi[q] = lo[q] + 1;
+          } else {
+            hi[q] = lo[q];
+          }
+        }
+      } else {
+        seen[q] += 256;
+        if (w0[q].x == c) {
+          const float w = __int_as_float(w0[q].z);
+          wsum[Q0 + q] = first ? w : wsum[Q0 + q] + w;
+          next[Q0 + q] = w0[q].y;
+          at[q] = -1;
+          continue;
+        }
+        if (w0[q].x < c) lo[q] = at[q] + 1;
+        else hi[q] = at[q];
+      }
+      if (lo[q] < hi[q] && (seen[q] >> 8) < kWalkBisect) {
+        at[q] = lo[q] + ((hi[q] - lo[q]) >> 1);
+        more = true;
+      } else if (epsd[q] >= 0 && (seen[q] & 255) < kWalkStates) {
+        const float w = __int_as_float(epsw[q]);
+        wsum[Q0 + q] = (seen[q] & 255) <= 1 ? w : wsum[Q0 + q] + w;
+        at[q] = 2 * epsd[q];
+        more = true;
+      } else {
+        wsum[Q0 + q] = NEG_INF;  // forbidden: the term is not finite, whatever the weight
+        next[Q0 + q] = 0;
+        at[q] = -1;
+      }
+    }
+    if (!more) break;
+  }
+#pragma unroll
+  for (int q = 0; q < kWalkChunk; ++q)
+    if (at[q] >= 0) wsum[Q0 + q] = NEG_INF;  // (the rounds ran out)
+}
+
+template <int LM>
 __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamArgs a) {
   __shared__ Beams beams[2];
   __shared__ LmLds<LM> lmv;
@@ -122,7 +228,8 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
     beams[0].len[0] = 0;
     beams[0].hash[0] = 0ull;
     beams[0].phash[0] = 0ull;
-    if constexpr (LM) lmv.L[0][0] = 0.0f;
+    if constexpr (LM != kLmNone) lmv.L[0][0] = 0.0f;
+    if constexpr (LM == kLmGraph) lmv.st[0][0] = a.lmg_start;
   }
   // the token set of the coming frame, one entry per thread, loaded a frame ahead
   gtnx_i2 nxt = entry(NEG_INF, -1);
@@ -159,7 +266,29 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
     // the gathers of the frame go out: lane k of wave v holds inc(i, k) of the beams i = v, v + 4, ...  (the blank is
     // no extension: its row and column are never read; a label of S_t is below C, a last label too)
     [[maybe_unused]] float incr[kIncTrips];
-    if constexpr (LM) {
+    [[maybe_unused]] int nxtr[kIncTrips];
+    if constexpr (LM == kLmGraph) {
+      // the walks of the frame, where the table's gathers are: the same lanes serve the same (beam, member)
+      const int lane = tid & 63, wave = tid >> 6;
+      const int cl = sl[lane < kMaxSet ? lane : 0];
+      int stq[kIncTrips];
+      bool act[kIncTrips];
+#pragma unroll
+      for (int q = 0; q < kIncTrips; ++q) stq[q] = lmv.st[cur][wave + q * kSearchWaves];
+      const int c = (lane < cnt && lane != bk) ? cl : -1;
+#pragma unroll
+      for (int q = 0; q < kIncTrips; ++q) act[q] = wave + q * kSearchWaves < nb && c >= 0;
+#pragma unroll
+      for (int q = 0; q < kIncTrips; ++q) {
+        incr[q] = 0.0f;
+        nxtr[q] = 0;
+      }
+      const int ntrip = (nb + kSearchWaves - 1) / kSearchWaves;
+      static_assert(kIncTrips == 2 * kWalkChunk, "two passes cover every trip");
+      lm_walks<0>(a.lmg, 2 * a.lmg_states, c, ntrip, stq, act, incr, nxtr);
+      if (ntrip > kWalkChunk) lm_walks<kWalkChunk>(a.lmg, 2 * a.lmg_states, c, ntrip, stq, act, incr, nxtr);
+    }
+    if constexpr (LM == kLmTable) {
       // (every LDS read first and unconditionally, so that they travel together: a slot past the list or the set
       //  holds some int, and its gather is not issued)
       const int lane = tid & 63, wave = tid >> 6;
@@ -193,7 +322,7 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
       spnb[tid] = (lk >= 0 && pnb > NEG_INF) ? pnb + sv[lk] : NEG_INF;
       lastk[tid] = lk;
     }
-    if constexpr (LM) {
+    if constexpr (LM != kLmNone) {
       // (slots that are no extension -- past the set, the blank -- get the term of 0: finite, and never used)
       const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
@@ -201,6 +330,8 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
         const int i = wave + q * kSearchWaves;
         if (q * kSearchWaves >= nb) continue;
         if (i < nb && lane < kMaxSet) lmv.inc[i * kMaxSet + lane] = lm_term(a.lm_weight, incr[q], a.lm_bonus);
+        if constexpr (LM == kLmGraph)
+          if (i < nb && lane < kMaxSet) lmv.nxt[i * kMaxSet + lane] = nxtr[q];
       }
     }
     __syncthreads();
@@ -236,7 +367,7 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
       unsigned long long kk = ~0ull;
       if (idx < nb) {
         const float total = logadd(spb[idx], spnb[idx]);
-        if constexpr (LM) {
+        if constexpr (LM != kLmNone) {
           if (total > NEG_INF)
             kk = (static_cast<unsigned long long>(falling_bits(total + lmv.L[cur][idx])) << 32) | (uint32_t(idx) << 25);
         } else {
@@ -247,7 +378,7 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
         const int c = sl[k];
         const float base = c == B.last[i] ? B.pb[i] : tot[i];
         const float s = base + sv[k];
-        if constexpr (LM) {
+        if constexpr (LM != kLmNone) {
           const float inc = lmv.inc[i * kMaxSet + k];  // (the blank's slot is finite, and the test on k drops it)
           const float Li = lmv.L[cur][i];
           if (k != bk && !((struck[i] >> k) & 1ull) && base > NEG_INF && s > NEG_INF && finite_bits(inc))
@@ -297,18 +428,20 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
           N.len[place] = B.len[i];
           N.hash[place] = B.hash[i];
           N.phash[place] = B.phash[i];
-          if constexpr (LM) lmv.L[cur ^ 1][place] = lmv.L[cur][i];
+          if constexpr (LM != kLmNone) lmv.L[cur ^ 1][place] = lmv.L[cur][i];
+          if constexpr (LM == kLmGraph) lmv.st[cur ^ 1][place] = lmv.st[cur][i];
         } else {
           const int c = LM ? int((lo >> 6) & 0x7ffffu) : int(lo & 0x1ffffffu);
           const int nd = 1 + t * W + place;  // (M * beam < 2^31)
           N.pb[place] = NEG_INF;
-          if constexpr (LM) {
+          if constexpr (LM != kLmNone) {
             // the key holds the combined total: the acoustic score again, by step 4's expression (the same bits; +0
             // for -0, as the key's bits give it), and L of the new prefix, by step 4's too
             const int k = int(lo & 63u);
             const float s = (c == B.last[i] ? B.pb[i] : tot[i]) + sv[k];
             N.pnb[place] = s + 0.0f;
             lmv.L[cur ^ 1][place] = lmv.L[cur][i] + lmv.inc[i * kMaxSet + k];
+            if constexpr (LM == kLmGraph) lmv.st[cur ^ 1][place] = lmv.nxt[i * kMaxSet + k];
           } else {
             N.pnb[place] = from_falling_bits(uint32_t(mine >> 32));
           }
@@ -348,7 +481,7 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
     if (r < nb) {
       len = F.len[r];  // (a prefix grows by at most one label per frame: len <= T <= M)
       score = logadd(F.pb[r], F.pnb[r]);
-      if constexpr (LM) {
+      if constexpr (LM != kLmNone) {
         am = score;
         score = am + lmv.L[cur][r];
       }
@@ -365,7 +498,7 @@ __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamAr
     }
     a.lengths[int64_t(b) * nbest + r] = len;
     a.scores[int64_t(b) * nbest + r] = score;
-    if constexpr (LM)
+    if constexpr (LM != kLmNone)
       if (a.am_scores) a.am_scores[int64_t(b) * nbest + r] = am;
   }
 }
@@ -390,10 +523,12 @@ void launch_ctc_beam(const CtcBeamArgs& a, int which, hipStream_t st) {
     else launch_rows<64>(a, st);
     return;
   }
-  if (a.lm)
-    hipLaunchKernelGGL(ctc_beam_search_kernel<true>, dim3(static_cast<unsigned>(a.n)), dim3(kSearchBlock), 0, st, a);
+  if (a.lmg)
+    hipLaunchKernelGGL(ctc_beam_search_kernel<kLmGraph>, dim3(static_cast<unsigned>(a.n)), dim3(kSearchBlock), 0, st, a);
+  else if (a.lm)
+    hipLaunchKernelGGL(ctc_beam_search_kernel<kLmTable>, dim3(static_cast<unsigned>(a.n)), dim3(kSearchBlock), 0, st, a);
   else
-    hipLaunchKernelGGL(ctc_beam_search_kernel<false>, dim3(static_cast<unsigned>(a.n)), dim3(kSearchBlock), 0, st, a);
+    hipLaunchKernelGGL(ctc_beam_search_kernel<kLmNone>, dim3(static_cast<unsigned>(a.n)), dim3(kSearchBlock), 0, st, a);
 }
 
 }  // namespace gtnx

@@ -859,6 +859,11 @@ struct CtcBeamArgs {
   const GTNX_G float* lm;
   float lm_weight, lm_bonus;
   GTNX_G float* am_scores;
+  // the compiled LM graph (lm_graph.h has the layout), or null; never together with `lm`.  One
+  // array of 16-byte words: two per state, [0, 2 * lmg_states), then one per arc.  A prefix then also carries its state,
+  // the term of an extension is lm_weight * walk(state, label) + lm_bonus, and everything else is as with the table.
+  const GTNX_G gtnx_i4* lmg;
+  int lmg_states, lmg_start;
 };
 void launch_ctc_beam(const CtcBeamArgs& a, int which, hipStream_t st);
 // asg_beam.hip: ASG prefix beam search with N-best output over every chain of an [n][M][C] tensor at its own length

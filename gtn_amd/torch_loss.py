@@ -33,6 +33,7 @@ _ARGTYPES = {
     "gtn_ctc_decode_n": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "gtn_ctc_beam_decode_n": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P],
     "gtn_ctc_beam_decode_lm_n": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _F, _F, _P, _P, _P, _P],
+    "gtn_ctc_beam_decode_graph_n": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _F, _F, _P, _P, _P, _P],
     "gtn_edit_distance_n": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "gtn_ctc_score_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P],
     "gtn_ctc_score_grad_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P],
@@ -572,7 +573,7 @@ def ctc_decode(log_probs, blank=0, input_lengths=None, collapse=True):
 
 
 def ctc_beam_decode(log_probs, blank=0, input_lengths=None, beam_size=16, cutoff_top_n=16, nbest=1, transitions=None,
-                    start=None, lm_weight=1.0, insertion_bonus=0.0, return_am_scores=False):
+                    start=None, lm_weight=1.0, insertion_bonus=0.0, return_am_scores=False, lm_graph=None):
     """CTC prefix beam search of a batch with N-best output, device-resident: the best label sequences, summed over
     their alignments, where `ctc_decode` gives the best alignment -- two launches whatever the lengths, nothing copied
     back.
@@ -594,7 +595,20 @@ def ctc_beam_decode(log_probs, blank=0, input_lengths=None, beam_size=16, cutoff
     stays acoustic and rows and columns of `blank` are never read.  Both tables are detached and may be non-contiguous.
     `scores` is then acoustic + L; with return_am_scores a fourth tensor, float32 [B, nbest], has the acoustic total
     alone (unpruned, `ctc_score` of those tokens), -inf in empty slots.  transitions=None is the search without a
-    language model, whatever the other four say."""
+    language model, whatever the other four say.
+    lm_graph: a `gtn_amd.LmGraph` -- a language model held as a graph, a deterministic acceptor with back-off arcs -- in
+    the tables' place; giving both raises ValueError.  A prefix then also carries its state in the graph, and its labels
+    add lm_weight * (the weight of the walk of (state, label), failure-arc semantics: `LmGraph.walk`) +
+    insertion_bonus; a label the walk forbids is dropped.  lm_weight, insertion_bonus and return_am_scores mean what
+    they mean with the tables.  The graph is a snapshot taken when the LmGraph was made: no gradient reaches it."""
+    if lm_graph is not None:
+        if transitions is not None or start is not None:
+            raise ValueError("ctc_beam_decode: give either transitions / start or lm_graph, not both")
+        if not isinstance(lm_graph, gtn.LmGraph):
+            raise ValueError("ctc_beam_decode: lm_graph must be a gtn_amd.LmGraph")
+        lm_weight, insertion_bonus = float(lm_weight), float(insertion_bonus)
+        if not (math.isfinite(lm_weight) and math.isfinite(insertion_bonus)):
+            raise ValueError("ctc_beam_decode: lm_weight and insertion_bonus must be finite")
     if log_probs.dim() != 3 or log_probs.dtype != torch.float32:
         raise ValueError("ctc_beam_decode: log_probs must be a float32 tensor [B, T, C]")
     B, T, N = log_probs.shape
@@ -630,6 +644,14 @@ def ctc_beam_decode(log_probs, blank=0, input_lengths=None, beam_size=16, cutoff
     tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=x.device)
     lengths = torch.empty(B, nbest, dtype=torch.int32, device=x.device)
     scores = torch.empty(B, nbest, dtype=torch.float32, device=x.device)
+    if lm_graph is not None:
+        am = torch.empty(B, nbest, dtype=torch.float32, device=x.device) if return_am_scores else None
+        _route(stream, x, _has_native("ctc_beam_decode", "gtn_ctc_beam_decode_graph_n"), "gtn_ctc_beam_decode_graph_n",
+               (blank, _host_ptr(frames), beam_size, cutoff_top_n, nbest, lm_graph._h, lm_weight, insertion_bonus,
+                tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr(), _ptr(am)),
+               "ctc_beam_decode", tokens, lengths, scores, frames, blank, beam_size, cutoff_top_n, nbest, row_stride=T,
+               lm=lm_graph, lm_weight=lm_weight, insertion_bonus=insertion_bonus, am_scores_out=am)
+        return (tokens, lengths, scores, am) if return_am_scores else (tokens, lengths, scores)
     if table is not None:
         am = torch.empty(B, nbest, dtype=torch.float32, device=x.device) if return_am_scores else None
         _route(stream, x, _has_native("ctc_beam_decode", "gtn_ctc_beam_decode_lm_n"), "gtn_ctc_beam_decode_lm_n",

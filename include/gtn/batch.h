@@ -211,6 +211,61 @@ inline void ctcBeamDecode(const Batch& ems, const float* lmDevice, float lmWeigh
                                               lmWeight, insertionBonus, tokensDevice, rowStride, lengthsDevice,
                                               scoresDevice, amScoresDevice));
 }
+/** A language model held as a graph, compiled for ctcBeamDecode (gtnx_lm_graph_create has the contract): a
+ *  deterministic acceptor with back-off (failure) arcs.  A snapshot of the graph's input labels and weights at
+ *  construction; no autograd; accept flags and output labels are ignored.  Host work: needs no device until a decode
+ *  uses it. */
+class LmGraph {
+ public:
+  struct Info {
+    int64_t numStates, numArcs;
+    int startState, longestEpsilonChain;
+  };
+  explicit LmGraph(const Graph& g) { detail::check(gtnx_lm_graph_create(g.handle(), &h_)); }
+  LmGraph(const LmGraph&) = delete;
+  LmGraph& operator=(const LmGraph&) = delete;
+  LmGraph(LmGraph&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  LmGraph& operator=(LmGraph&& o) noexcept {
+    if (this != &o) {
+      if (h_) gtnx_lm_graph_destroy(h_);
+      h_ = o.h_;
+      o.h_ = nullptr;
+    }
+    return *this;
+  }
+  ~LmGraph() {
+    if (h_) gtnx_lm_graph_destroy(h_);
+  }
+  /** the walk of `label` from `state` (failure-arc semantics): false when the label is forbidden there */
+  bool walk(int state, int label, float* weight, int* nextState) const {
+    float w;
+    int nx;
+    detail::check(gtnx_lm_graph_walk(h_, state, label, &w, &nx));
+    if (weight) *weight = w;
+    if (nextState) *nextState = nx;
+    return nx >= 0;
+  }
+  Info info() const {
+    gtnx_lm_graph_info_t i;
+    detail::check(gtnx_lm_graph_info(h_, &i));
+    return Info{i.num_states, i.num_arcs, i.start_state, i.longest_epsilon_chain};
+  }
+  gtnx_lm_graph_t handle() const { return h_; }
+
+ private:
+  gtnx_lm_graph_t h_ = nullptr;
+};
+/** The same search with a compiled LM graph in the table's place: every prefix also carries its LM state, an extension
+ *  adds lmWeight * (weight of the walk of (state, label)) + insertionBonus, a label the walk forbids is dropped --
+ *  gtnx_batch_ctc_beam_decode_graph */
+inline void ctcBeamDecode(const Batch& ems, const LmGraph& lm, float lmWeight, float insertionBonus, int* tokensDevice,
+                          int64_t rowStride, int* lengthsDevice, float* scoresDevice, float* amScoresDevice = nullptr,
+                          int blank = 0, int beamSize = 16, int cutoffTopN = 16, int nbest = 1,
+                          const int* frames = nullptr) {
+  detail::check(gtnx_batch_ctc_beam_decode_graph(ems.handle(), frames, blank, beamSize, cutoffTopN, nbest, lm.handle(),
+                                                 lmWeight, insertionBonus, tokensDevice, rowStride, lengthsDevice,
+                                                 scoresDevice, amScoresDevice));
+}
 /** Levenshtein distance (unit costs) of all B * N pairs (hyp[b, k], ref[b]) of device-resident token rows, results left
  *  on the device: hypDevice int32 B * N rows of width L, hypStride (>= L) apart, hypLengthsDevice int32 [B][N];
  *  refDevice int32 B rows of width U, refStride (>= U) apart, refLengthsDevice int32 [B] -- the lengths are device

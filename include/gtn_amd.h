@@ -419,6 +419,50 @@ gtnx_status_t gtnx_batch_ctc_beam_decode_lm(gtnx_batch_t ems, const int* frames,
                                             float insertion_bonus, void* tokens_device, int64_t row_stride,
                                             void* lengths_device, void* scores_device,
                                             void* am_scores_device /* may be null */);
+/* A language model held as a graph, compiled for the search above: a deterministic acceptor with
+ * back-off (failure) arcs -- an n-gram model in ARPA form, or a lexicon or grammar acceptor that forbids sequences.
+ * gtnx_lm_graph_create reads the input labels of g's arcs (output labels and accept flags are ignored: an n-gram
+ * acceptor accepts everywhere, and end-of-sentence handling is out of scope) and its weights AS THEY ARE AT THAT
+ * MOMENT: a snapshot, later changes of g are not seen, and there is no autograd. The arcs need not be sorted. It is
+ * host work and needs no device; the compiled form is uploaded once, by the first decode that uses it, which waits for
+ * that copy.
+ * Walk semantics, the same on host and device. From state s with label c: if s has an arc labelled c, add its weight
+ * and move to its destination; otherwise, if s has an epsilon arc (label -1, gtn::epsilon), add its weight, go to its
+ * destination and repeat; if neither exists, c is forbidden from s. The weight of a walk is the float32 sum of the
+ * walked weights in walk order, starting from the first one. These are failure (phi) semantics, what ARPA back-off
+ * means -- not what compose does with epsilon, where the direct arc and the back-off path would both count.
+ * GTNX_INVALID_ARGUMENT, with a message, nothing is repaired: no start node or more than one; two arcs with the same
+ * input label out of one node; more than one epsilon arc out of a node; an epsilon chain that is cyclic or longer than
+ * 8 arcs; a label below -1; more than 2^24 nodes; a linear graph. */
+typedef struct gtnx_lm_graph_s* gtnx_lm_graph_t;
+typedef struct {
+  int64_t num_states;        /* the nodes of the graph */
+  int64_t num_arcs;          /* its arcs, epsilon arcs included */
+  int32_t start_state;
+  int32_t longest_epsilon_chain; /* epsilon arcs on the longest back-off chain, 0 .. 8 */
+} gtnx_lm_graph_info_t;
+gtnx_status_t gtnx_lm_graph_create(gtnx_graph_t g, gtnx_lm_graph_t* out);
+gtnx_status_t gtnx_lm_graph_destroy(gtnx_lm_graph_t lm); /* null: nothing; a handle that is not live is refused */
+/* the host-side probe: the walk of `label` from `state`. A forbidden label gives *weight = -inf and *next_state = -1;
+ * a walk that is found may still have a weight that is not finite, which the search drops. GTNX_OUT_OF_RANGE for a
+ * state that is none; a label below 0 is forbidden. */
+gtnx_status_t gtnx_lm_graph_walk(gtnx_lm_graph_t lm, int state, int label, float* weight, int* next_state);
+gtnx_status_t gtnx_lm_graph_info(gtnx_lm_graph_t lm, gtnx_lm_graph_info_t* out);
+/* gtnx_batch_ctc_beam_decode_lm with a compiled LM graph in the table's place. Every prefix also carries its LM state:
+ * the empty prefix the start state; an extension of y by c walks (state(y), c) and gets
+ * inc = lm_weight * (weight of the walk) + insertion_bonus (the product rounded, then the sum) and the walk's
+ * destination as its state. A label that is forbidden, or whose walk weight is not finite, is dropped as a -inf table
+ * entry is. `blank` and labels outside the token set are never walked, so arcs labelled blank or >= C are never found.
+ * The graph is deterministic, so equal prefixes have equal states and equal L: the total order, prefix identity and
+ * all four outputs are as with the table, and a graph that spells a bigram table gives byte-identical results.
+ * GTNX_INVALID_ARGUMENT on top of gtnx_batch_ctc_beam_decode's, before a device is asked for: a null, destroyed or
+ * foreign lm_graph, an lm_weight or insertion_bonus that is not finite; with the device: more than 2^19 labels, a
+ * graph that was uploaded to another device. Nothing is written by a refused call. */
+gtnx_status_t gtnx_batch_ctc_beam_decode_graph(gtnx_batch_t ems, const int* frames, int blank, int beam_size,
+                                               int cutoff_top_n, int nbest, gtnx_lm_graph_t lm_graph, float lm_weight,
+                                               float insertion_bonus, void* tokens_device, int64_t row_stride,
+                                               void* lengths_device, void* scores_device,
+                                               void* am_scores_device /* may be null */);
 /* calls that have launched so far (process-wide) / utterances they decoded */
 gtnx_status_t gtnx_batch_ctc_beam_stats(int64_t* calls, int64_t* utterances);
 /* Levenshtein distance of all B * N pairs (hyp[b, k], ref[b]) of token rows that live on the device, results left on
