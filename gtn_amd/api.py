@@ -14,6 +14,7 @@ hold the product (libgtn_amd.so) and the reference shim (libgtn_ref.so) side by
 side.
 """
 import ctypes as C
+import math
 import types
 
 import numpy as np
@@ -671,12 +672,13 @@ def make_api(lib):
                     ("longest_epsilon_chain", C.c_int32)]
 
     class LmGraph:
-        """A language model held as a Graph, compiled for `Batch.ctc_beam_decode(lm=...)` (gtnx_lm_graph_create; DESIGN
-        section 30): a deterministic acceptor with back-off (failure) arcs -- an n-gram model in ARPA form, or a lexicon
-        or grammar acceptor that forbids label sequences.  A SNAPSHOT of the graph's input labels and weights at this
-        moment: later changes of `graph` are not seen, and there is no autograd.  Output labels and accept flags are
-        ignored (an n-gram acceptor accepts everywhere; end-of-sentence handling is out of scope).  The arcs need not be
-        sorted.  Compiling and `walk` are host work and need no GPU; the first decode uploads the compiled form.
+        """A language model held as a Graph, compiled for `Batch.ctc_beam_decode(lm=...)` and
+        `Batch.asg_beam_decode(lm=...)` (gtnx_lm_graph_create; DESIGN sections 30 and 31): a deterministic acceptor
+        with back-off (failure) arcs -- an n-gram model in ARPA form, or a lexicon or grammar acceptor that forbids
+        label sequences.  A SNAPSHOT of the graph's input labels and weights at this moment: later changes of `graph`
+        are not seen, and there is no autograd.  Output labels and accept flags are ignored (an n-gram acceptor accepts
+        everywhere; end-of-sentence handling is out of scope).  The arcs need not be sorted.  Compiling and `walk` are
+        host work and need no GPU; the first decode uploads the compiled form.
         ValueError, nothing is repaired: no start node or several, two arcs with one input label out of a node, several
         epsilon arcs out of a node, an epsilon chain that is cyclic or longer than 8 arcs, a label below -1, more than
         2^24 nodes."""
@@ -908,7 +910,7 @@ def make_api(lib):
             return stride
 
         def asg_beam_decode(self, tokens_out, lengths_out, scores_out, frames, table, beam_size=16, cutoff_top_n=16,
-                            nbest=1, row_stride=None):
+                            nbest=1, row_stride=None, lm=None, lm_weight=1.0, insertion_bonus=0.0, am_scores_out=None):
             """ASG prefix beam search with N-best output over a Batch.linear, results left on the device
             (gtnx_batch_asg_beam_decode; DESIGN section 27 holds the contract).  The hypotheses are the label sequences
             without equal neighbours -- what `viterbi_decode`'s collapsed rows can hold -- each summed over all of its
@@ -923,13 +925,41 @@ def make_api(lib):
             forbids its bigram or first label.  `beam_size` 1 .. 64 prefixes are kept, a frame offers its `cutoff_top_n`
             (1 .. 32) best labels, for stays as well as extensions; `frames`: T_b per element (0 .. M, at most the rows
             the batch carries; None: those rows).  Two launches with no copy back and no wait; rows from T_b on are never
-            read.  Any batch but a Batch.linear is an error: there is no other route."""
+            read.  Any batch but a Batch.linear is an error: there is no other route.
+            `lm` (an `LmGraph`; None: no language model, the call above) fuses a language model held as a graph -- a
+            lexicon, a grammar, an n-gram model -- into the ranking (gtnx_batch_asg_beam_decode_graph; DESIGN section
+            31); `table` stays the criterion's own.  A prefix then also carries L and its state in the graph: an
+            extension walks (state, label) -- failure-arc semantics, see `LmGraph.walk` -- and adds lm_weight * (the
+            walk's weight) + insertion_bonus to L; a label the walk forbids, or whose term is not finite, is dropped.
+            Candidates rank by acoustic score + L; stays, merging and the token sets stay acoustic.  `scores_out` then
+            gets acoustic + L and `am_scores_out` (float32 [B, nbest], optional) the acoustic score alone -- unpruned,
+            `asg_score` of those tokens; slots without a hypothesis hold -inf in both.  ValueError: an `lm` that is no
+            `LmGraph`; `lm_weight`, `insertion_bonus` or `am_scores_out` given without `lm`; a weight or bonus that
+            is not finite; a destroyed `LmGraph`."""
             n = len(self)
+            if lm is None:
+                if lm_weight != 1.0 or insertion_bonus != 0.0 or am_scores_out is not None:
+                    raise ValueError("asg_beam_decode: lm_weight, insertion_bonus and am_scores_out need lm")
+            else:
+                if not isinstance(lm, LmGraph):
+                    raise ValueError("asg_beam_decode: lm must be an LmGraph")
+                lm_weight, insertion_bonus = float(lm_weight), float(insertion_bonus)
+                if not (math.isfinite(lm_weight) and math.isfinite(insertion_bonus)):
+                    raise ValueError("asg_beam_decode: lm_weight and insertion_bonus must be finite")
             table = self._asg_score_table("asg_beam_decode", table)
             stride = self._nbest_outputs("asg_beam_decode", tokens_out, nbest, row_stride,
                                          ((lengths_out, "torch.int32", "lengths_out must be an int32"),
-                                          (scores_out, "torch.float32", "scores_out must be a float32")))
+                                          (scores_out, "torch.float32", "scores_out must be a float32"),
+                                          (am_scores_out, "torch.float32", "am_scores_out must be a float32")))
             fr, fr_ptr = _frames_arg("asg_beam_decode", frames, n)
+            if lm is not None:
+                # (a destroyed object has no handle: the engine refuses the null one)
+                check(lib.gtnx_batch_asg_beam_decode_graph(self._h, fr_ptr, _opt_ptr(table), int(beam_size),
+                                                           int(cutoff_top_n), int(nbest), lm._h, lm_weight,
+                                                           insertion_bonus, _opt_ptr(tokens_out), int(stride),
+                                                           _opt_ptr(lengths_out), _opt_ptr(scores_out),
+                                                           _opt_ptr(am_scores_out)))
+                return
             check(lib.gtnx_batch_asg_beam_decode(self._h, fr_ptr, _opt_ptr(table), int(beam_size), int(cutoff_top_n),
                                                  int(nbest), _opt_ptr(tokens_out), int(stride), _opt_ptr(lengths_out),
                                                  _opt_ptr(scores_out)))

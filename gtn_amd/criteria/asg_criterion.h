@@ -241,6 +241,34 @@ inline void asgBeamDecodeBatch(
                          frames);
 }
 
+/** The same search with a compiled LM graph fused into the ranking (gtnx_batch_asg_beam_decode_graph has the contract):
+ *  `lmGraph` is the handle of a gtn::batched::LmGraph or of gtnx_lm_graph_create -- it is passed on as it is, the engine
+ *  refuses one that is not live.  `scoresDev` gets acoustic + L, `amScoresDev` (device float32 [B][nbest], may be null)
+ *  the acoustic score alone. */
+inline void asgBeamDecodeBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int N,
+    const void* tableDev,
+    const int* frames,
+    int beamSize,
+    int cutoffTopN,
+    int nbest,
+    gtnx_lm_graph_t lmGraph,
+    float lmWeight,
+    float insertionBonus,
+    void* tokensDev,
+    void* lengthsDev,
+    void* scoresDev,
+    void* amScoresDev) {
+  Batch ems = Batch::linear(B, T, N, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  detail::check(gtnx_batch_asg_beam_decode_graph(ems.handle(), frames, tableDev, beamSize, cutoffTopN, nbest, lmGraph,
+                                                 lmWeight, insertionBonus, static_cast<int*>(tokensDev), T,
+                                                 static_cast<int*>(lengthsDev), static_cast<float*>(scoresDev),
+                                                 static_cast<float*>(amScoresDev)));
+}
+
 /** The best alignment of B * N device-resident hypotheses under the B emission slabs -- when each token was spoken and
  *  how well the frames support it: `emissions` device float32 [B][T][N_], read in place; `tableDev` device float32
  *  [N_ + N_ * N_] in the arc order of asgTransitions; `tokensDev` device int32 [B][N][L] and `lengthsDev` device int32

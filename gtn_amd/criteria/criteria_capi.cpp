@@ -267,6 +267,19 @@ GTN_EXPORT int gtn_asg_beam_decode_n(const void* emissions, int B, int T, int C,
   });
 }
 
+// The same with a compiled LM graph fused into the ranking.  lm_graph: a handle of gtnx_lm_graph_create (libgtn_amd.so),
+// passed through as a pointer: both libraries live in one process.  am_scores: DEVICE float32 [B][nbest] or null.
+GTN_EXPORT int gtn_asg_beam_decode_graph_n(const void* emissions, int B, int T, int C, const void* table,
+                                           const int* frames, int beam_size, int cutoff_top_n, int nbest, void* lm_graph,
+                                           float lm_weight, float insertion_bonus, void* tokens, void* lengths,
+                                           void* scores, void* am_scores) {
+  return guarded([&] {
+    gtn::criteria::asgBeamDecodeBatch(emissions, B, T, C, table, frames, beam_size, cutoff_top_n, nbest,
+                                      static_cast<gtnx_lm_graph_t>(lm_graph), lm_weight, insertion_bonus, tokens, lengths,
+                                      scores, am_scores);
+  });
+}
+
 // ... and their gradients under weights: DEVICE float32 [B][N]: grad_em (DEVICE float32 [B][T][C], every element
 // written) and grad_table (DEVICE float32 [C + C*C], every entry written); either may be null, not both.
 GTN_EXPORT int gtn_asg_score_grad_n(const void* emissions, int B, int T, int C, const void* table, const int* frames,

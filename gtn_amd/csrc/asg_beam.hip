@@ -28,6 +28,14 @@
 //            At the end thread r < nbest walks the parents of slot r and stores the tokens back to front; all threads
 //            fill the rest of the rows with -1.
 // Every sum is float32 in the contract's order: (a + w) + x.  A table entry that is not finite drops its candidate.
+// With a compiled LM graph (lm_graph.h has the words; tests/asg_beam_graph_fp.py) the search kernel is
+// its LM = kLmGraph instantiation: every prefix also carries L and its LM state (slot 0 starts with 0 in the graph's
+// start state, a stay copies both, an extension takes L + inc(i, k) and next(i, k)), and candidates rank by acoustic
+// score + L; the stays, step 3 and the rows stay acoustic.  The walks of (state_i, label_k) (lm_walk.h, shared with
+// ctc_beam.hip) go where step 2's gathers go out, in the same lanes -- the label that is the prefix's last is never
+// walked -- and inc(i, k) = lm_weight * walk + lm_bonus and next(i, k) are parked in LDS beside w(i, k).  A key then
+// holds the combined total, so step 6 computes an extension's score again, by step 4's expression.
+// LM = kLmNone is the code above, statement for statement: everything else sits under `if constexpr (LM != kLmNone)`.
 // No global atomics; nothing depends on the order in which waves arrive (keys are distinct, every slot has one writer).
 // Every store is a plain C++ store; there is no inline assembly.
 #include <hip/hip_runtime.h>
@@ -36,6 +44,7 @@
 
 #include "beam_common.h"
 #include "kernels.h"
+#include "lm_walk.h"
 #include "pair_kernels.h"
 
 namespace gtnx {
@@ -60,14 +69,36 @@ struct Prefixes {
   unsigned long long hash[kMaxBeam], phash[kMaxBeam];  // of the prefix / of the prefix without its last label
 };
 
+// what the graph kernel keeps in LDS on top of the lists: L and the LM state of every prefix in both list copies, and
+// inc(i, k) and next(i, k) of the frame at [i * kMaxSet + k], beside wtr
+template <int LM>
+struct LmLds {
+  float L[2][kMaxBeam];
+  int st[2][kMaxBeam];
+  float inc[kMaxBeam * kMaxSet];
+  int nxt[kMaxBeam * kMaxSet];
+};
+template <>
+struct LmLds<kLmNone> {};
+static_assert(kGatherTrips == kWalkTrips, "lm_walk.h: a thread holds one walk per prefix of its wave");
+// A workgroup may have 64 KB of static LDS.  The large arrays of the graph instantiation -- the two lists, the keys,
+// wtr and LmLds -- take 63 488 of them, and the small per-prefix and per-member arrays of the kernel about 1.5 KB
+// more: whatever is added to these has to fit the 2 KB that are left.
+constexpr size_t kSearchLdsLimit = 64 * 1024, kSearchLdsSmall = 2 * 1024;
+static_assert(2 * sizeof(Prefixes) + sizeof(unsigned long long) * kKeySlots + sizeof(float) * kMaxBeam * kMaxSet +
+                      sizeof(LmLds<kLmGraph>) + kSearchLdsSmall <= kSearchLdsLimit,
+              "asg_beam_search_kernel<kLmGraph>: the static LDS would pass 64 KB");
+
 // (a + w) + x: two sums, each rounded
 __device__ __forceinline__ float step_score(float a, float w, float x) {
   const float aw = a + w;
   return aw + x;
 }
 
+template <int LM>
 __global__ __launch_bounds__(kSearchBlock) void asg_beam_search_kernel(AsgBeamArgs a) {
   __shared__ Prefixes lists[2];
+  __shared__ LmLds<LM> lmv;
   __shared__ unsigned long long key[kKeySlots];
   __shared__ float wtr[kMaxBeam * kMaxSet];        // w(i, k) of the frame at [i * kMaxSet + k]
   __shared__ float stay[kMaxBeam];
@@ -98,6 +129,10 @@ __global__ __launch_bounds__(kSearchBlock) void asg_beam_search_kernel(AsgBeamAr
     lists[0].len[0] = 0;
     lists[0].hash[0] = 0ull;
     lists[0].phash[0] = 0ull;
+    if constexpr (LM != kLmNone) {
+      lmv.L[0][0] = 0.0f;
+      lmv.st[0][0] = a.lmg_start;
+    }
   }
   // the token set of the coming frame, one entry per thread, loaded a frame ahead
   gtnx_i2 nxt = entry(NEG_INF, -1);
@@ -130,6 +165,8 @@ __global__ __launch_bounds__(kSearchBlock) void asg_beam_search_kernel(AsgBeamAr
     // ---- 2. the gathers of the frame go out: lane k of wave v holds w(i, k) of the prefixes i = v, v + 4, ...  (a label
     // of S_t is below C, a last label too; the slot of the last label itself is the stay's and is not gathered)
     float wq[kGatherTrips];
+    [[maybe_unused]] float incr[kGatherTrips];
+    [[maybe_unused]] int nxtr[kGatherTrips];
     const int lane = tid & 63, wave = tid >> 6;
     {
       // (every LDS read first and unconditionally, so that they travel together: a slot past the list or the set
@@ -152,6 +189,25 @@ __global__ __launch_bounds__(kSearchBlock) void asg_beam_search_kernel(AsgBeamAr
           }
         }
       }
+      if constexpr (LM != kLmNone) {
+        // the walks of the frame, in the lanes of the gathers: (state of prefix i, label k), never the prefix's own last
+        // label (a sequence with equal neighbours is no hypothesis)
+        int stq[kGatherTrips];
+        bool act[kGatherTrips];
+#pragma unroll
+        for (int q = 0; q < kGatherTrips; ++q) stq[q] = lmv.st[cur][wave + q * kSearchWaves];
+#pragma unroll
+        for (int q = 0; q < kGatherTrips; ++q) act[q] = wave + q * kSearchWaves < nb && c >= 0 && c != lastq[q];
+#pragma unroll
+        for (int q = 0; q < kGatherTrips; ++q) {
+          incr[q] = 0.0f;
+          nxtr[q] = 0;
+        }
+        const int ntrip = (nb + kSearchWaves - 1) / kSearchWaves;
+        static_assert(kGatherTrips == 2 * kWalkChunk, "two passes cover every trip");
+        lm_walks<0>(a.lmg, 2 * a.lmg_states, c, ntrip, stq, act, incr, nxtr);
+        if (ntrip > kWalkChunk) lm_walks<kWalkChunk>(a.lmg, 2 * a.lmg_states, c, ntrip, stq, act, incr, nxtr);
+      }
     }
     // the stays
     if (tid < nb) {
@@ -171,6 +227,13 @@ __global__ __launch_bounds__(kSearchBlock) void asg_beam_search_kernel(AsgBeamAr
       const int i = wave + q * kSearchWaves;
       if (q * kSearchWaves >= nb) continue;
       if (i < nb && lane < kMaxSet) wtr[i * kMaxSet + lane] = wq[q];
+      if constexpr (LM != kLmNone) {
+        // (the term of a slot that was not walked is that of 0: finite, and never used)
+        if (i < nb && lane < kMaxSet) {
+          lmv.inc[i * kMaxSet + lane] = lm_term(a.lm_weight, incr[q], a.lm_bonus);
+          lmv.nxt[i * kMaxSet + lane] = nxtr[q];
+        }
+      }
     }
     __syncthreads();
     // ---- 3. the extension that is a prefix of the list joins it.  Prefix i is the parent of prefix j when it spells
@@ -207,15 +270,28 @@ __global__ __launch_bounds__(kSearchBlock) void asg_beam_search_kernel(AsgBeamAr
       unsigned long long kk = ~0ull;
       if (idx < nb) {
         const float total = stay[idx];
-        if (total > NEG_INF) kk = (static_cast<unsigned long long>(falling_bits(total)) << 32) | (uint32_t(idx) << 25);
+        if constexpr (LM != kLmNone) {
+          if (total > NEG_INF)
+            kk = (static_cast<unsigned long long>(falling_bits(total + lmv.L[cur][idx])) << 32) | (uint32_t(idx) << 25);
+        } else {
+          if (total > NEG_INF) kk = (static_cast<unsigned long long>(falling_bits(total)) << 32) | (uint32_t(idx) << 25);
+        }
       } else if (idx < ncand) {
         const int e = idx - nb, i = e / cnt, k = e - i * cnt;
         const int c = sl[k];
         const float w = wtr[i * kMaxSet + k];
         const float s = step_score(B.a[i], w, sv[k]);
-        if (c != B.last[i] && !((struck[i] >> k) & 1ull) && finite_bits(w) && s > NEG_INF)
-          kk = (static_cast<unsigned long long>(falling_bits(s)) << 32) | 0x80000000u | (uint32_t(i) << 25) |
-               (uint32_t(c) << 6) | uint32_t(k);  // (C <= 2^19; k < 32)
+        if constexpr (LM != kLmNone) {
+          const float inc = lmv.inc[i * kMaxSet + k];
+          const float Li = lmv.L[cur][i];
+          if (c != B.last[i] && !((struck[i] >> k) & 1ull) && finite_bits(w) && s > NEG_INF && finite_bits(inc))
+            kk = (static_cast<unsigned long long>(falling_bits(s + (Li + inc))) << 32) | 0x80000000u |
+                 (uint32_t(i) << 25) | (uint32_t(c) << 6) | uint32_t(k);
+        } else {
+          if (c != B.last[i] && !((struck[i] >> k) & 1ull) && finite_bits(w) && s > NEG_INF)
+            kk = (static_cast<unsigned long long>(falling_bits(s)) << 32) | 0x80000000u | (uint32_t(i) << 25) |
+                 (uint32_t(c) << 6) | uint32_t(k);  // (C <= 2^19; k < 32)
+        }
       }
       key[idx] = kk;
     }
@@ -252,10 +328,23 @@ __global__ __launch_bounds__(kSearchBlock) void asg_beam_search_kernel(AsgBeamAr
           N.len[place] = B.len[i];
           N.hash[place] = B.hash[i];
           N.phash[place] = B.phash[i];
+          if constexpr (LM != kLmNone) {
+            lmv.L[cur ^ 1][place] = lmv.L[cur][i];
+            lmv.st[cur ^ 1][place] = lmv.st[cur][i];
+          }
         } else {
           const int c = int((lo >> 6) & 0x7ffffu);
           const int nd = 1 + t * W + place;  // (M * beam < 2^31)
-          N.a[place] = from_falling_bits(uint32_t(mine >> 32));  // (the key's bits are the score's)
+          if constexpr (LM != kLmNone) {
+            // the key holds the combined total: the acoustic score again, by step 4's expression (the same bits; +0
+            // for -0, as the key's bits give it), and L and the state of the new prefix
+            const int k = int(lo & 63u);
+            N.a[place] = step_score(B.a[i], wtr[i * kMaxSet + k], sv[k]) + 0.0f;
+            lmv.L[cur ^ 1][place] = lmv.L[cur][i] + lmv.inc[i * kMaxSet + k];
+            lmv.st[cur ^ 1][place] = lmv.nxt[i * kMaxSet + k];
+          } else {
+            N.a[place] = from_falling_bits(uint32_t(mine >> 32));  // (the key's bits are the score's)
+          }
           N.self[place] = table[int64_t(C) + int64_t(c) * C + c];
           N.node[place] = nd;
           N.last[place] = c;
@@ -289,9 +378,14 @@ __global__ __launch_bounds__(kSearchBlock) void asg_beam_search_kernel(AsgBeamAr
     GTNX_G int* row = a.tokens + (int64_t(b) * nbest + r) * a.row_stride;
     int len = 0;
     float score = NEG_INF;
+    [[maybe_unused]] float am = NEG_INF;
     if (r < nb) {
       len = F.len[r];  // (a prefix grows by at most one label per frame: len <= T <= M)
       score = F.a[r];
+      if constexpr (LM != kLmNone) {
+        am = score;
+        score = am + lmv.L[cur][r];
+      }
       int nd = F.node[r], lab = F.last[r], par = F.parent[r];
       for (int k = len - 1; k >= 0 && nd > 0; --k) {
         row[k] = lab;
@@ -305,6 +399,8 @@ __global__ __launch_bounds__(kSearchBlock) void asg_beam_search_kernel(AsgBeamAr
     }
     a.lengths[int64_t(b) * nbest + r] = len;
     a.scores[int64_t(b) * nbest + r] = score;
+    if constexpr (LM != kLmNone)
+      if (a.am_scores) a.am_scores[int64_t(b) * nbest + r] = am;
   }
 }
 
@@ -328,7 +424,10 @@ void launch_asg_beam(const AsgBeamArgs& a, int which, hipStream_t st) {
     else launch_rows<64>(a, st);
     return;
   }
-  hipLaunchKernelGGL(asg_beam_search_kernel, dim3(static_cast<unsigned>(a.n)), dim3(kSearchBlock), 0, st, a);
+  if (a.lmg)
+    hipLaunchKernelGGL(asg_beam_search_kernel<kLmGraph>, dim3(static_cast<unsigned>(a.n)), dim3(kSearchBlock), 0, st, a);
+  else
+    hipLaunchKernelGGL(asg_beam_search_kernel<kLmNone>, dim3(static_cast<unsigned>(a.n)), dim3(kSearchBlock), 0, st, a);
 }
 
 }  // namespace gtnx

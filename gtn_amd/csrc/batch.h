@@ -225,6 +225,25 @@ void batch_ctc_beam_stats(int64_t* calls, int64_t* utterances);  // calls that l
 // download, no wait.
 void batch_asg_beam_decode(const BatchP& ems, const int* frames, const float* table_dev, int beam, int topn, int nbest,
                            int* tokens_dev, int64_t row_stride, int* lengths_dev, float* scores_dev);
+// The same search with a compiled LM graph fused into the ranking (lm_graph.h): `graph` is a handle
+// of lm_graph_register.  Every prefix also carries L and its LM state -- the empty prefix 0 and the start state; an
+// extension by c walks (state, c) with failure-arc semantics and adds weight * walk + bonus (the product rounded, then
+// the sum) to L; a stay copies both -- and candidates rank by acoustic score + L.  A label the walk forbids, or whose
+// term is not finite, drops the extension; the stays, the merging and the rows stay acoustic; table_dev is still the
+// criterion's own table.  scores_dev gets acoustic + L and am_scores_dev (may be null) the acoustic score alone, -inf
+// in slots without a hypothesis.  Refused on top, under the name gtnx_batch_asg_beam_decode_graph like every refusal
+// of this call: before a device is asked for a handle that is not a live one and a weight or bonus that is not finite;
+// with the device an am_scores_dev that is not memory allocated on the current device (host memory included, with one
+// GPU as well) and a graph that lives on another device.  The first decode with a graph uploads it and waits for the
+// copy, once.  Counted by batch_asg_beam_stats like the call above.
+struct AsgBeamLm {
+  const void* graph;
+  float weight, bonus;
+  float* am_scores_dev;
+};
+void batch_asg_beam_decode(const BatchP& ems, const int* frames, const float* table_dev, int beam, int topn, int nbest,
+                           const AsgBeamLm* lm, int* tokens_dev, int64_t row_stride, int* lengths_dev,
+                           float* scores_dev);
 void batch_asg_beam_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they decoded
 // Levenshtein distance (unit costs) of all B * N pairs (hyp[b, k], ref[b]) of device-resident token rows, results on the
 // device (DESIGN section 21 holds the contract).  hyp_dev: int32 [B][N] rows of width L, hyp_stride elements apart;

@@ -576,7 +576,7 @@ void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int 
       refuse(kCtcBeam, "the language model table is not memory of the engine's current device");
   }
   // (uploaded by the first decode that uses it; a graph that lives on another device is refused here)
-  const gtnx_i4* lmg_dev = lmg ? lm_graph_device(*lmg) : nullptr;
+  const gtnx_i4* lmg_dev = lmg ? lm_graph_device(*lmg, kCtcBeam) : nullptr;
   if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
   const std::vector<int> fr = resolve_frames(frames, x);
   // algorithmic bytes.  rows: every emission of the rows that count once, topn + 1 entries and a count out.  search:
@@ -636,6 +636,7 @@ void batch_ctc_beam_decode(const BatchP& ems, const int* frames, int blank, int 
 // ---- ASG prefix beam search with N-best output, device-resident (asg_beam.hip) ----
 namespace {
 constexpr const char* kAsgBeam = "gtnx_batch_asg_beam_decode";
+constexpr const char* kAsgBeamGraph = "gtnx_batch_asg_beam_decode_graph";
 Counters g_asg_beam;  // (calls, utterances)
 }  // namespace
 
@@ -643,8 +644,15 @@ void batch_asg_beam_stats(int64_t* calls, int64_t* utterances) { g_asg_beam.get(
 
 void batch_asg_beam_decode(const BatchP& ems, const int* frames, const float* table_dev, int beam, int topn, int nbest,
                            int* tokens_dev, int64_t row_stride, int* lengths_dev, float* scores_dev) {
+  batch_asg_beam_decode(ems, frames, table_dev, beam, topn, nbest, nullptr, tokens_dev, row_stride, lengths_dev,
+                        scores_dev);
+}
+
+void batch_asg_beam_decode(const BatchP& ems, const int* frames, const float* table_dev, int beam, int topn, int nbest,
+                           const AsgBeamLm* lm, int* tokens_dev, int64_t row_stride, int* lengths_dev,
+                           float* scores_dev) {
   GTNX_HOST_T("batch.asg_beam_decode");
-  const char* who = kAsgBeam;
+  const char* who = lm ? kAsgBeamGraph : kAsgBeam;
   // what the arguments alone decide comes first: no device is asked for an invalid call
   if (!ems) refuse(who, "null batch");
   if (!table_dev) refuse(who, "null table pointer");
@@ -654,6 +662,13 @@ void batch_asg_beam_decode(const BatchP& ems, const int* frames, const float* ta
   if (beam < 1 || beam > 64) refuse(who, "beam_size outside 1 .. 64");
   if (topn < 1 || topn > 32) refuse(who, "cutoff_top_n outside 1 .. 32");
   if (nbest < 1 || nbest > beam) refuse(who, "nbest outside 1 .. beam_size");
+  LmGraphP lmg;
+  if (lm) {
+    if (!lm->graph) refuse(who, "null LM graph handle");
+    lmg = lm_graph_lookup(lm->graph);
+    if (!lmg) refuse(who, "not a live LM graph handle (destroyed, or not from gtnx_lm_graph_create)");
+    if (!std::isfinite(lm->weight) || !std::isfinite(lm->bonus)) refuse(who, "lm_weight and insertion_bonus must be finite");
+  }
   const int n = ems->n;
   if (n <= 0) return;
   Runtime& rt = Runtime::get();
@@ -669,15 +684,22 @@ void batch_asg_beam_decode(const BatchP& ems, const int* frames, const float* ta
   // (the kernel gathers from it: host memory is refused too, with one GPU as well)
   if (!ptr_device_memory_of(table_dev, rt.device())) refuse(who, "the table is not memory of the engine's current device");
   check_outputs_local(who, {tokens_dev, lengths_dev, scores_dev});
+  // (always asked, with one GPU as well: host memory handed over as the optional output is refused, not written)
+  if (lm && lm->am_scores_dev && !ptr_device_memory_of(lm->am_scores_dev, rt.device()))
+    refuse(who, "am_scores is not memory of the engine's current device");
+  // (uploaded by the first decode that uses it; a graph that lives on another device is refused here)
+  const gtnx_i4* lmg_dev = lmg ? lm_graph_device(*lmg, who) : nullptr;
   if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
   const std::vector<int> fr = resolve_frames(frames, x);
   // algorithmic bytes.  rows: every emission of the rows that count once, topn entries and a count out.  search: those
   // back in, one 4-byte gather per (prefix, member of the set) and frame at the most, a trie node and a self-transition
-  // per kept extension (at most beam per frame), the output rows.
+  // per kept extension (at most beam per frame), the output rows; with a graph the walk of every (prefix, member) at its
+  // shortest -- the state's two 16-byte words and one arc word -- and the second score.
   double row_bytes = 0, search_bytes = 0;
   for (int t : fr) {
     row_bytes += (4.0 * x.C + 8.0 * topn + 4.0) * t;
     search_bytes += (8.0 * topn + 4.0 + 12.0 * beam + 4.0 * beam * topn) * t + nbest * (4.0 * x.M + 8.0);
+    if (lm) search_bytes += 48.0 * beam * topn * t + (lm->am_scores_dev ? 4.0 * nbest : 0.0);
   }
   DevMemP d_frames = upload_vec(fr);
   const size_t rows = std::max<size_t>(size_t(n) * size_t(x.M), 1);
@@ -701,6 +723,14 @@ void batch_asg_beam_decode(const BatchP& ems, const int* frames, const float* ta
   a.beam = beam;
   a.topn = topn;
   a.nbest = nbest;
+  if (lm) {
+    a.lmg = lmg_dev;
+    a.lmg_states = lmg->states;
+    a.lmg_start = lmg->start;
+    a.lm_weight = lm->weight;
+    a.lm_bonus = lm->bonus;
+    a.am_scores = lm->am_scores_dev;
+  }
   {
     GTNX_PROF("asg_beam_rows", row_bytes);
     launch_asg_beam(a, 0, rt.stream());

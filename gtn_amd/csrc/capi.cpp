@@ -979,6 +979,19 @@ GTNX_API gtnx_status_t gtnx_batch_asg_beam_decode(gtnx_batch_t ems, const int* f
                           static_cast<float*>(scores_device));
   });
 }
+GTNX_API gtnx_status_t gtnx_batch_asg_beam_decode_graph(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                                        int beam_size, int cutoff_top_n, int nbest,
+                                                        gtnx_lm_graph_t lm_graph, float lm_weight, float insertion_bonus,
+                                                        void* tokens_device, int64_t row_stride, void* lengths_device,
+                                                        void* scores_device, void* am_scores_device) {
+  return guard([&] {
+    // (null handles go through: the entry refuses them under its own name)
+    const AsgBeamLm lm{lm_graph, lm_weight, insertion_bonus, static_cast<float*>(am_scores_device)};
+    batch_asg_beam_decode(ems ? BH(ems) : BatchP(), frames, static_cast<const float*>(table_device), beam_size,
+                          cutoff_top_n, nbest, &lm, static_cast<int*>(tokens_device), row_stride,
+                          static_cast<int*>(lengths_device), static_cast<float*>(scores_device));
+  });
+}
 GTNX_API gtnx_status_t gtnx_batch_asg_beam_stats(int64_t* calls, int64_t* utterances) {
   return guard([&] { batch_asg_beam_stats(calls, utterances); });
 }

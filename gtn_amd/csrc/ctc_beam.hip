@@ -43,9 +43,9 @@
 // With a compiled LM graph (lm_graph.h has the words; tests/ctc_beam_graph_fp.py) it is the third
 // instantiation, LM = kLmGraph: everything the table has, and every beam also carries its LM state (slot 0 starts at the
 // graph's start state, a stay copies it, an extension takes next(i, k)).  Where the table is gathered the thread walks
-// (state_i, label_k) instead -- all its walks together, one probe of each per round, so that the dependent loads of up
-// to 8 walks overlap -- and parks next(i, k) beside inc(i, k).  Every loop of the walk has a compile-time bound, and a
-// walk that exhausts one forbids its extension.
+// (state_i, label_k) instead (lm_walk.h, shared with asg_beam.hip) -- all its walks together, one probe of each per
+// round, so that the dependent loads of up to 8 walks overlap -- and parks next(i, k) beside inc(i, k).  Every loop of
+// the walk has a compile-time bound, and a walk that exhausts one forbids its extension.
 // No global atomics; nothing depends on the order in which waves arrive (keys are distinct, every slot has one writer).
 // Every store is a plain C++ store; there is no inline assembly.
 #include <hip/hip_runtime.h>
@@ -54,6 +54,7 @@
 
 #include "beam_common.h"
 #include "kernels.h"
+#include "lm_walk.h"
 #include "pair_kernels.h"
 
 namespace gtnx {
@@ -77,8 +78,6 @@ struct Beams {
   unsigned long long hash[kMaxBeam], phash[kMaxBeam];  // of the prefix / of the prefix without its last label
 };
 
-constexpr int kLmNone = 0, kLmTable = 1, kLmGraph = 2;  // what ranks beside the acoustic score
-
 // what the LM kernels keep in LDS on top of the lists: L of every beam in both list copies, and inc(i, k) of the
 // frame at [i * kMaxSet + k]; with a graph also the LM state of every beam and next(i, k)
 template <int LM>
@@ -98,103 +97,7 @@ struct LmLds<kLmGraph> {
 constexpr int kSearchWaves = kSearchBlock / 64;
 constexpr int kIncTrips = kMaxBeam / kSearchWaves;  // gathers a thread holds at most: one per beam of its wave
 
-// lm_weight * w + lm_bonus: a product rounded, then a sum rounded -- never fused, the order of the host forms
-__device__ __forceinline__ float lm_term(float weight, float w, float bonus) {
-#pragma clang fp contract(off)
-  const float scaled = weight * w;
-  return scaled + bonus;
-}
-
-// The walks of one thread: label c from the states st[q] of the trips q < ntrip, trip q being live when act[q].  A walk
-// is a chain of dependent loads (the state's two words, then one arc word per probe of the bisection, then the next
-// state of the back-off chain), so they advance together: a round loads the next word of every walk, then every walk
-// takes its step.  A walk that is over, or a trip without one, loads word 0.  at[q] is the word a walk reads next
-// (below 2 * states: a state; above: an arc; -1: over), [lo, hi) the arcs that may still hold the label.
-// kWalkChunk trips go together (the trips Q0 .. Q0 + kWalkChunk - 1 of one call): with all 16 in flight the kernel
-// needs 346 registers, only one workgroup fits a compute unit where two of the table's do, and the batch takes twice
-// as long -- measured, DESIGN section 30.  Eight cover a beam of 32 in one pass; a larger beam walks twice.
-// Bounds, all compile-time: a walk visits at most kWalkStates states and probes a state's arcs at most kWalkBisect
-// times, and the rounds stop at their product whatever the words hold.  A walk that runs out of either is forbidden.
-constexpr int kWalkStates = 9, kWalkBisect = 32;
-constexpr int kWalkRounds = kWalkStates * (1 + kWalkBisect);
-constexpr int kWalkChunk = 8;
-template <int Q0>
-__device__ __forceinline__ void lm_walks(const GTNX_G gtnx_i4* g, int states2, int c, int ntrip,
-                                         const int (&st)[kIncTrips], const bool (&act)[kIncTrips],
-                                         float (&wsum)[kIncTrips], int (&next)[kIncTrips]) {
-  const GTNX_G gtnx_i2* g2 = reinterpret_cast<const GTNX_G gtnx_i2*>(g);
-  int at[kWalkChunk], lo[kWalkChunk], hi[kWalkChunk], epsd[kWalkChunk], epsw[kWalkChunk], seen[kWalkChunk];
-#pragma unroll
-  for (int q = 0; q < kWalkChunk; ++q) {
-    at[q] = act[Q0 + q] ? 2 * st[Q0 + q] : -1;
-    lo[q] = hi[q] = 0;
-    epsd[q] = -1;
-    epsw[q] = 0;
-    seen[q] = 0;  // states visited so far, and from bit 8 the probes of this state's arcs
-  }
-  for (int round = 0; round < kWalkRounds; ++round) {
-    gtnx_i4 w0[kWalkChunk];
-    gtnx_i2 w1[kWalkChunk];
-#pragma unroll
-    for (int q = 0; q < kWalkChunk; ++q) {
-      if (Q0 + q >= ntrip) continue;  // (the same in every thread)
-      const int p = at[q] < 0 ? 0 : at[q];
-      w0[q] = g[p];
-      w1[q] = g2[2 * (p + 1)];  // (a state's second word: first label, dense; the form ends with a spare word)
-    }
-    bool more = false;
-#pragma unroll
-    for (int q = 0; q < kWalkChunk; ++q) {
-      if (Q0 + q >= ntrip) continue;
-      if (at[q] < 0) continue;
-      const bool first = (seen[q] & 255) <= 1;  // no back-off weight yet: the sum starts from the first weight
-      if (at[q] < states2) {
-        seen[q] = (seen[q] & 255) + 1;
-        epsd[q] = w0[q].z;
-        epsw[q] = w0[q].w;
-        lo[q] = w0[q].x;
-        hi[q] = w0[q].x + w0[q].y;
-        if (w1[q].y) {  // labels first .. first + count - 1: the one arc it can be
-          const unsigned j = unsigned(c) - unsigned(w1[q].x);
-          if (j < unsigned(w0[q].y)) {
-            lo[q] += int(j);
-            hi[q] = lo[q] + 1;
-          } else {
-            hi[q] = lo[q];
-          }
-        }
-      } else {
-        seen[q] += 256;
-        if (w0[q].x == c) {
-          const float w = __int_as_float(w0[q].z);
-          wsum[Q0 + q] = first ? w : wsum[Q0 + q] + w;
-          next[Q0 + q] = w0[q].y;
-          at[q] = -1;
-          continue;
-        }
-        if (w0[q].x < c) lo[q] = at[q] + 1;
-        else hi[q] = at[q];
-      }
-      if (lo[q] < hi[q] && (seen[q] >> 8) < kWalkBisect) {
-        at[q] = lo[q] + ((hi[q] - lo[q]) >> 1);
-        more = true;
-      } else if (epsd[q] >= 0 && (seen[q] & 255) < kWalkStates) {
-        const float w = __int_as_float(epsw[q]);
-        wsum[Q0 + q] = (seen[q] & 255) <= 1 ? w : wsum[Q0 + q] + w;
-        at[q] = 2 * epsd[q];
-        more = true;
-      } else {
-        wsum[Q0 + q] = NEG_INF;  // forbidden: the term is not finite, whatever the weight
-        next[Q0 + q] = 0;
-        at[q] = -1;
-      }
-    }
-    if (!more) break;
-  }
-#pragma unroll
-  for (int q = 0; q < kWalkChunk; ++q)
-    if (at[q] >= 0) wsum[Q0 + q] = NEG_INF;  // (the rounds ran out)
-}
+static_assert(kIncTrips == kWalkTrips, "lm_walk.h: a thread holds one walk per beam of its wave");
 
 template <int LM>
 __global__ __launch_bounds__(kSearchBlock) void ctc_beam_search_kernel(CtcBeamArgs a) {

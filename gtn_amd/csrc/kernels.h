@@ -889,6 +889,14 @@ struct AsgBeamArgs {
   GTNX_G float* scores;
   int64_t row_stride;
   int n, M, C, beam, topn, nbest;
+  // the compiled LM graph (lm_graph.h has the layout), or null: the words, two per state in
+  // [0, 2 * lmg_states), then one per arc.  With it a prefix also carries L and its LM state, an extension adds
+  // lm_weight * walk(state, label) + lm_bonus to L, candidates rank by acoustic score + L, scores holds acoustic + L and
+  // am_scores (may be null) the acoustic score alone.  which = 1 then launches the graph instantiation.
+  const GTNX_G gtnx_i4* lmg;
+  int lmg_states, lmg_start;
+  float lm_weight, lm_bonus;
+  GTNX_G float* am_scores;
 };
 void launch_asg_beam(const AsgBeamArgs& a, int which, hipStream_t st);
 // edit_distance.hip: Levenshtein distance (unit costs) of the pairs pair0 .. pair0 + count - 1, pair p = b * N + k being

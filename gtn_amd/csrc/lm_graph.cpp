@@ -169,7 +169,7 @@ bool lm_graph_walk(const LmGraph& lm, int state, int label, float* weight, int* 
   return false;
 }
 
-const gtnx_i4* lm_graph_device(LmGraph& lm) {
+const gtnx_i4* lm_graph_device(LmGraph& lm, const char* who) {
   Runtime& rt = Runtime::get();
   std::lock_guard<std::mutex> lock(lm.mu);
   if (!lm.dev) {
@@ -184,7 +184,7 @@ const gtnx_i4* lm_graph_device(LmGraph& lm) {
     lm.device = rt.device();
   }
   if (lm.device != rt.device())
-    throw_invalid("[gtnx_batch_ctc_beam_decode] the LM graph was uploaded to device " + std::to_string(lm.device) +
+    throw_invalid(std::string("[") + who + "] the LM graph was uploaded to device " + std::to_string(lm.device) +
                   ", the calling thread is on device " + std::to_string(rt.device()));
   return lm.dev->as<gtnx_i4>();
 }

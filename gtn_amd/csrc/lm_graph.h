@@ -1,5 +1,6 @@
-// lm_graph.h -- a deterministic acceptor with back-off (failure) arcs, compiled for the CTC prefix beam search
-// (DESIGN section 30 holds the contract; ctc_beam.hip walks the same words on the device).
+// lm_graph.h -- a deterministic acceptor with back-off (failure) arcs, compiled for the two prefix beam searches
+// (DESIGN section 30 holds the contract, section 31 the ASG search's; lm_walk.h walks the same words on the device, for
+// ctc_beam.hip and asg_beam.hip alike).
 //
 // The compiled form is ONE array of 16-byte words, so that every probe of a walk is the same load:
 //   state s, words [2 s] and [2 s + 1]:  { begin, count, eps_dst, eps_weight bits }  { first label, dense, 0, 0 }
@@ -51,8 +52,9 @@ LmGraphP lm_graph_compile(Graph& g);
 // false: `label` is forbidden from `state` (weight and next are then -inf and -1).  A found walk may still have a
 // weight that is not finite: the search drops such an extension.
 bool lm_graph_walk(const LmGraph& lm, int state, int label, float* weight, int* next);
-// the words on the calling thread's device (uploaded on first use; a graph that lives on another device is refused)
-const gtnx_i4* lm_graph_device(LmGraph& lm);
+// the words on the calling thread's device (uploaded on first use; a graph that lives on another device is refused,
+// under the name `who` of the entry that asked)
+const gtnx_i4* lm_graph_device(LmGraph& lm, const char* who);
 
 // handles of the C ABI: a registry, so that a destroyed or foreign pointer is refused and not followed
 void* lm_graph_register(LmGraphP lm);

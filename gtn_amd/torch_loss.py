@@ -41,6 +41,7 @@ _ARGTYPES = {
     "gtn_asg_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
     "gtn_asg_beam_decode_n": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P],
+    "gtn_asg_beam_decode_graph_n": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _F, _F, _P, _P, _P, _P],
     "gtn_asg_token_align_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
 }
 
@@ -667,7 +668,8 @@ def ctc_beam_decode(log_probs, blank=0, input_lengths=None, beam_size=16, cutoff
     return tokens, lengths, scores
 
 
-def asg_beam_decode(emissions, transitions, start=None, input_lengths=None, beam_size=16, cutoff_top_n=16, nbest=1):
+def asg_beam_decode(emissions, transitions, start=None, input_lengths=None, beam_size=16, cutoff_top_n=16, nbest=1,
+                    lm_graph=None, lm_weight=1.0, insertion_bonus=0.0, return_am_scores=False):
     """ASG prefix beam search of a batch with N-best output, device-resident: the best label sequences without equal
     neighbours -- the sequences `asg_decode(collapse=True)` can emit -- each summed over all of its alignments under
     emissions o transitions, where `asg_decode` gives the best alignment.  Two launches whatever the lengths, nothing
@@ -684,7 +686,25 @@ def asg_beam_decode(emissions, transitions, start=None, input_lengths=None, beam
     that stayed before one that grew, then the parent's rank, then the label; NaN and -inf are never chosen.  Slots
     without a hypothesis -- fewer than nbest prefixes, a frame with nothing above -inf, an utterance without frames --
     get -1, length 0 and score -inf.  The outputs feed `asg_score` and `edit_distance` as they are.  Runs on the
-    caller's stream and does not wait; no autograd."""
+    caller's stream and does not wait; no autograd.
+    lm_graph: a `gtn_amd.LmGraph` -- a language model held as a graph: a lexicon, a grammar, an n-gram model with
+    back-off arcs -- fused into the ranking; `transitions` and `start` stay the criterion's own.  A prefix then also
+    carries its state in the graph, and each of its labels adds lm_weight * (the weight of the walk of (state, label),
+    failure-arc semantics: `LmGraph.walk`) + insertion_bonus to its LM score L; a label the walk forbids is dropped.
+    Hypotheses rank by acoustic score + L, which is what `scores` then holds; with return_am_scores a fourth tensor,
+    float32 [B, nbest], has the acoustic score alone (unpruned, `asg_score` of those tokens), -inf in empty slots.  The
+    graph is a snapshot taken when the LmGraph was made: no gradient reaches it.  ValueError: an lm_graph that is no
+    LmGraph, a weight or bonus that is not finite, and lm_weight, insertion_bonus or return_am_scores without
+    lm_graph."""
+    if lm_graph is None:
+        if lm_weight != 1.0 or insertion_bonus != 0.0 or return_am_scores:
+            raise ValueError("asg_beam_decode: lm_weight, insertion_bonus and return_am_scores need lm_graph")
+    else:
+        if not isinstance(lm_graph, gtn.LmGraph):
+            raise ValueError("asg_beam_decode: lm_graph must be a gtn_amd.LmGraph")
+        lm_weight, insertion_bonus = float(lm_weight), float(insertion_bonus)
+        if not (math.isfinite(lm_weight) and math.isfinite(insertion_bonus)):
+            raise ValueError("asg_beam_decode: lm_weight and insertion_bonus must be finite")
     if emissions.dim() != 3 or emissions.dtype != torch.float32:
         raise ValueError("asg_beam_decode: emissions must be a float32 tensor [B, T, N]")
     B, T, N = emissions.shape
@@ -712,6 +732,14 @@ def asg_beam_decode(emissions, transitions, start=None, input_lengths=None, beam
     tokens = torch.empty(B, nbest, T, dtype=torch.int32, device=x.device)
     lengths = torch.empty(B, nbest, dtype=torch.int32, device=x.device)
     scores = torch.empty(B, nbest, dtype=torch.float32, device=x.device)
+    if lm_graph is not None:
+        am = torch.empty(B, nbest, dtype=torch.float32, device=x.device) if return_am_scores else None
+        _route(stream, x, _has_native("asg_beam_decode", "gtn_asg_beam_decode_graph_n"), "gtn_asg_beam_decode_graph_n",
+               (table.data_ptr(), _host_ptr(frames), beam_size, cutoff_top_n, nbest, lm_graph._h, lm_weight,
+                insertion_bonus, tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr(), _ptr(am)),
+               "asg_beam_decode", tokens, lengths, scores, frames, table, beam_size, cutoff_top_n, nbest, row_stride=T,
+               lm=lm_graph, lm_weight=lm_weight, insertion_bonus=insertion_bonus, am_scores_out=am)
+        return (tokens, lengths, scores, am) if return_am_scores else (tokens, lengths, scores)
     _route(stream, x, _has_native("asg_beam_decode", "gtn_asg_beam_decode_n"), "gtn_asg_beam_decode_n",
            (table.data_ptr(), _host_ptr(frames), beam_size, cutoff_top_n, nbest, tokens.data_ptr(), lengths.data_ptr(),
             scores.data_ptr()),

@@ -340,6 +340,19 @@ inline void asgBeamDecode(const Batch& ems, const float* tableDevice, int* token
   detail::check(gtnx_batch_asg_beam_decode(ems.handle(), frames, tableDevice, beamSize, cutoffTopN, nbest, tokensDevice,
                                            rowStride, lengthsDevice, scoresDevice));
 }
+/** The same search with a compiled LM graph fused into the ranking: every prefix also carries L and its LM state, an
+ *  extension adds lmWeight * (weight of the walk of (state, label)) + insertionBonus to L and is dropped when the walk
+ *  forbids the label; candidates rank by acoustic score + L; stays, merging and the token sets stay acoustic, and
+ *  tableDevice is still the criterion's own table.  scoresDevice gets acoustic + L, amScoresDevice (optional) the
+ *  acoustic score alone -- unpruned, asgScore of the tokens -- gtnx_batch_asg_beam_decode_graph */
+inline void asgBeamDecode(const Batch& ems, const float* tableDevice, const LmGraph& lm, float lmWeight,
+                          float insertionBonus, int* tokensDevice, int64_t rowStride, int* lengthsDevice,
+                          float* scoresDevice, float* amScoresDevice = nullptr, int beamSize = 16, int cutoffTopN = 16,
+                          int nbest = 1, const int* frames = nullptr) {
+  detail::check(gtnx_batch_asg_beam_decode_graph(ems.handle(), frames, tableDevice, beamSize, cutoffTopN, nbest,
+                                                 lm.handle(), lmWeight, insertionBonus, tokensDevice, rowStride,
+                                                 lengthsDevice, scoresDevice, amScoresDevice));
+}
 /** The best alignment of all n * N device-resident hypotheses (the form of ctcScore) under the slabs of a Batch::linear,
  *  results left on the device: scoresDevice [n][N] the Viterbi score (-inf without a path); startsDevice / endsDevice
  *  int32 n * N rows of width L, outStride (>= L) apart: the first frame of token i and one past its last, -1 for i >= len

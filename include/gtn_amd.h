@@ -719,6 +719,37 @@ gtnx_status_t gtnx_batch_asg_token_align_stats(int64_t* calls, int64_t* pairs);
 gtnx_status_t gtnx_batch_asg_beam_decode(gtnx_batch_t ems, const int* frames, const void* table_device, int beam_size,
                                          int cutoff_top_n, int nbest, void* tokens_device, int64_t row_stride,
                                          void* lengths_device, void* scores_device);
+/* gtnx_batch_asg_beam_decode with a compiled LM graph (gtnx_lm_graph_create; its walk semantics are stated there) fused
+ * into the ranking -- a lexicon, a grammar or an n-gram model beside the criterion's own transitions, which stay what
+ * they are: table_device is still the acoustic model's table.  DESIGN section 31 holds the contract:
+ *   state       every prefix also carries L (float32) and its LM state; the empty prefix has L = 0 and the graph's start
+ *               state.
+ *   extension   of prefix p by c in S_t, c != last(p): (wt, next) = the walk of (state(p), c);
+ *               inc = lm_weight * wt + insertion_bonus (the product rounded, then the sum; never fused).  The acoustic
+ *               score is unchanged, s = (a(p) + w) + x[c]; L' = L(p) + inc, state' = next, total = s + L'.  Dropped
+ *               when the walk forbids c or inc is not finite, and for every reason it is dropped without a graph.
+ *   stay        unchanged, the graph is not consulted: total = stay + L(p); L and the state are copied.
+ *   merging     acoustic and unchanged: an extension that spells a prefix q of the list is log-added into q's stay and
+ *               struck.  The graph is deterministic, so q has that extension's L and state already.
+ *   order       by total descending, then as without a graph.  The token sets and their pruning stay acoustic.  A total
+ *               is not examined beyond that: a candidate is dropped by its acoustic score and its inc alone.
+ * Labels of the graph at or above C are never walked, accept flags are ignored, and (state, c) with c == last(p) is
+ * never walked: a sequence with equal neighbours is no hypothesis.
+ * scores_device: acoustic + L (one float32 add); am_scores_device (float32 [n][nbest], may be null): the acoustic
+ * score alone -- unpruned, gtnx_batch_asg_score of those tokens.  A slot without a hypothesis gets -1, 0, -inf, -inf.
+ * With lm_weight = 0, insertion_bonus = 0 and a graph that permits every label with a finite weight, tokens, lengths
+ * and scores are the bytes of gtnx_batch_asg_beam_decode, and am_scores equals scores.
+ * GTNX_INVALID_ARGUMENT, each with a text that begins "[gtnx_batch_asg_beam_decode_graph]", and nothing is written:
+ * everything gtnx_batch_asg_beam_decode refuses, and before a device is asked for: a null, destroyed or foreign
+ * lm_graph, an lm_weight or insertion_bonus that is not finite; with the device: an am_scores_device that is not
+ * memory allocated on the engine's current device (host memory is refused with one GPU as well), a graph that was
+ * uploaded to another device.  The first decode with a graph uploads it (16 bytes per arc, 32 per state) and waits for
+ * that copy, once.  Counted by gtnx_batch_asg_beam_stats. */
+gtnx_status_t gtnx_batch_asg_beam_decode_graph(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                               int beam_size, int cutoff_top_n, int nbest, gtnx_lm_graph_t lm_graph,
+                                               float lm_weight, float insertion_bonus, void* tokens_device,
+                                               int64_t row_stride, void* lengths_device, void* scores_device,
+                                               void* am_scores_device /* may be null */);
 /* calls that have launched so far (process-wide) / utterances they decoded */
 gtnx_status_t gtnx_batch_asg_beam_stats(int64_t* calls, int64_t* utterances);
 /* rows M and labels C of the slabs of a gtnx_batch_linear / _rows batch; -1, -1 for any other batch */

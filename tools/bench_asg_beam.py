@@ -19,6 +19,15 @@ There is no route for the ASG call on the previous commit, so no speed-up is cla
         adds those means to the record: the rows kernels on their byte model (4 C in, 8 K + 4 out per row; K + 1 for
         CTC) at the stream rate, the search kernels per batch and per frame, ASG over CTC.
 
+    python tools/bench_asg_beam.py --graph [--parent TREE] [--out profiles/asg_beam_graph_c4.json]
+        the same tensor and table with a compiled LM graph fused in (Batch.asg_beam_decode(lm=gtn_amd.LmGraph(...));
+        DESIGN section 31) beside the call without one: the table's own bigram spelled as a graph (a start state and a
+        state per label, C + C * C arcs, every state dense) and the synthetic back-off trigram of
+        tools/bench_ctc_beam.py --graph over this alphabet, at that tool's weight and bonus.  Three samples of each,
+        alternating, every sample a process of its own.  With --parent, the call without a graph is also run from
+        TREE -- a built tree of the commit to compare with -- alternating with this tree's, and the record gets both
+        and the run-to-run spread.
+
 Needs a GPU; a measurement path that finds none fails.
 """
 import argparse
@@ -77,6 +86,24 @@ def worker(kind):
         ems = gtn.Batch.linear(B, T, C, em, False, True)
         ems.asg_beam_decode(tokens, lengths, scores, None, table, BEAM, TOPN, NBEST)
 
+    lmg = None
+    if kind in ("asg_bigram", "asg_trigram"):
+        # the graph generators of tools/bench_ctc_beam.py, over this tool's alphabet
+        import numpy as np
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        import bench_ctc_beam as cb
+        lmg = gtn.LmGraph(cb.bigram_graph(gtn, np, table.cpu().numpy(), C=C) if kind == "asg_bigram"
+                          else cb.trigram_graph(gtn, np, C=C))
+        # (a full bigram has a state per label and the start; the trigram a unigram state, C bigram states and more)
+        states = lmg.info()["num_states"]
+        assert states == 1 + C if kind == "asg_bigram" else states > 1 + C, states
+        am_scores = torch.empty((B, NBEST), dtype=torch.float32, device="cuda")
+
+    def asg_graph_step():
+        ems = gtn.Batch.linear(B, T, C, em, False, True)
+        ems.asg_beam_decode(tokens, lengths, scores, None, table, BEAM, TOPN, NBEST, lm=lmg, lm_weight=cb.LM_WEIGHT,
+                            insertion_bonus=cb.LM_BONUS, am_scores_out=am_scores)
+
     def ctc_lm_step():
         ems = gtn.Batch.linear(B, T, C, em, False, True)
         ems.ctc_beam_decode(tokens, lengths, scores, None, BLANK, BEAM, TOPN, NBEST, lm=table, lm_weight=1.0,
@@ -107,12 +134,17 @@ def worker(kind):
         print(json.dumps({"trace": "done"}))
         return
     c0 = gtn.debug_asg_beam_stats()
-    ms, n = timed({"asg": asg_step, "ctc_lm": ctc_lm_step}[kind])
+    ms, n = timed({"asg": asg_step, "ctc_lm": ctc_lm_step, "asg_bigram": asg_graph_step,
+                   "asg_trigram": asg_graph_step}[kind])
     sync()
     c1 = gtn.debug_asg_beam_stats()
     rec = {"kind": kind, "utterances": B, "ms_per_batch": ms, "iters": n, "asg_beam_utterances": c1[1] - c0[1],
            "mean_length": float(lengths.float().mean().item()), "mean_score": float(scores.mean().item()),
            "slots_with_a_hypothesis": int(torch.isfinite(scores).sum().item())}
+    if lmg is not None:
+        rec["graph"] = lmg.info()
+        rec["mean_am_score"] = float(am_scores.mean().item())
+        rec["lm_weight"], rec["insertion_bonus"] = cb.LM_WEIGHT, cb.LM_BONUS
     if kind == "asg":
         first = scores.clone()
         asg_step()
@@ -121,14 +153,18 @@ def worker(kind):
     print(json.dumps(rec))
 
 
-def run_worker(kind):
+def run_worker(kind, tree=None):
+    """a sample in a process of its own; `tree`: run this tool's copy in that built tree instead (the commit to
+    compare with)"""
     env = dict(os.environ)
     env.pop("PYTHONPATH", None)
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", kind], env=env,
+    script = os.path.abspath(__file__) if tree is None else os.path.join(os.path.abspath(tree), "tools",
+                                                                         os.path.basename(__file__))
+    out = subprocess.run([sys.executable, script, "--worker", kind], env=env,
                          stdout=subprocess.PIPE, timeout=500, check=True).stdout.decode()
     rec = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
-    print(f"[bench_asg_beam] {kind}: {rec['ms_per_batch']:.3f} ms per batch of {rec['utterances']}", file=sys.stderr,
-          flush=True)
+    print(f"[bench_asg_beam] {kind}{'' if tree is None else ' (parent tree)'}: {rec['ms_per_batch']:.3f} ms per batch "
+          f"of {rec['utterances']}", file=sys.stderr, flush=True)
     return rec
 
 
@@ -136,19 +172,69 @@ def spread(v):
     return {"samples": v, "min": min(v), "max": max(v), "median": sorted(v)[len(v) // 2]}
 
 
+# (the search kernel is a template since the graph instantiation; the trace worker launches the graph-less one only)
 KERNELS = {"asg_beam_rows_kernel": ("asg_beam_rows_kernel",), "asg_beam_search_kernel": ("asg_beam_search_kernel",),
            "ctc_beam_rows_kernel": ("ctc_beam_rows_kernel",),
            "ctc_beam_search_kernel<true>": ("ctc_beam_search_kernel<true>", "ctc_beam_search_kernelILb1E")}
 
 
+def main_graph(a):
+    """the --graph record: end to end without a graph (from this tree and, with --parent, from that one), with the
+    bigram graph and with the trigram graph"""
+    kinds = ("asg", "asg_bigram", "asg_trigram")
+    samples, last, parent = {k: [] for k in kinds}, {}, []
+    for _ in range(3):
+        if a.parent:
+            parent.append(run_worker("asg", a.parent)["ms_per_batch"])
+        for k in kinds:
+            last[k] = run_worker(k)
+            assert last[k]["asg_beam_utterances"] > 0, last[k]
+            samples[k].append(last[k]["ms_per_batch"])
+    med = {k: sorted(v)[1] for k, v in samples.items()}
+    rec = {"shape": {"B": B, "T": T, "C": C, "beam_size": BEAM, "cutoff_top_n": TOPN, "nbest": NBEST,
+                     "table": "normal(0, 1), seeded, C + C * C float32", "lm_weight": last["asg_bigram"]["lm_weight"],
+                     "insertion_bonus": last["asg_bigram"]["insertion_bonus"]},
+           "unit": "ms per batch, host clock around a closing synchronise, windows >= 0.5 s",
+           "asg": dict(spread(samples["asg"]), what="Batch.asg_beam_decode without a graph, this tree", utterances=B,
+                       mean_length=last["asg"]["mean_length"], mean_score=last["asg"]["mean_score"]),
+           "asg_bigram": dict(spread(samples["asg_bigram"]), what="lm = the table's own bigram as an LmGraph",
+                              utterances=B, graph=last["asg_bigram"]["graph"],
+                              mean_length=last["asg_bigram"]["mean_length"]),
+           "asg_trigram": dict(spread(samples["asg_trigram"]), what="lm = a synthetic back-off trigram LmGraph",
+                               utterances=B, graph=last["asg_trigram"]["graph"],
+                               mean_length=last["asg_trigram"]["mean_length"]),
+           "asg_bigram_over_asg": med["asg_bigram"] / med["asg"],
+           "asg_trigram_over_asg": med["asg_trigram"] / med["asg"],
+           "walks_per_frame_at_most": BEAM * TOPN}
+    if a.parent:
+        both = samples["asg"] + parent
+        rec["asg_parent"] = dict(spread(parent), what="Batch.asg_beam_decode, the parent commit's tree, alternating "
+                                 "with this tree's samples", utterances=B)
+        rec["run_to_run_spread_ms"] = max(max(parent) - min(parent), max(samples["asg"]) - min(samples["asg"]))
+        rec["asg_median_minus_parent_median_ms"] = med["asg"] - sorted(parent)[1]
+        rec["all_six_samples_range_ms"] = max(both) - min(both)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--worker", choices=["asg", "ctc_lm", "trace"])
+    ap.add_argument("--worker", choices=["asg", "ctc_lm", "asg_bigram", "asg_trigram", "trace"])
     ap.add_argument("--merge-stats")
-    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "asg_beam_c4.json"))
+    ap.add_argument("--graph", action="store_true")
+    ap.add_argument("--parent")
+    ap.add_argument("--out")
     a = ap.parse_args()
     if a.worker:
         worker(a.worker)
+        return
+    if not a.out:
+        a.out = os.path.join(HERE, "profiles", "asg_beam_graph_c4.json" if a.graph else "asg_beam_c4.json")
+    if a.graph:
+        main_graph(a)
         return
     rec = {}
     if os.path.exists(a.out):

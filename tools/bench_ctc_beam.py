@@ -81,8 +81,8 @@ def lm_table(torch):
     return (torch.randn((C + C * C,), generator=g, device="cuda", dtype=torch.float32) * 2.0).contiguous()
 
 
-def bigram_graph(gtn, np, table):
-    """the table as a graph: state 0 the start, state 1 + c after label c, every arc"""
+def bigram_graph(gtn, np, table, C=C):
+    """the table [C + C * C] as a graph: state 0 the start, state 1 + c after label c, every arc"""
     g = gtn.Graph(False)
     g.add_nodes(np.arange(1 + C) == 0, np.ones(1 + C, bool))
     lab = np.arange(C)
@@ -92,11 +92,11 @@ def bigram_graph(gtn, np, table):
     return g
 
 
-def trigram_graph(gtn, np, seed=4321, arcs_share=0.25, pairs_share=0.1):
-    """a seeded back-off trigram: state 0 the unigram state (every label) and the start, 1 + i the bigram state after
-    i, then a trigram state per kept pair (j, i); a state has `arcs_share` of the labels and an epsilon arc one order
-    down; an arc labelled k out of a state that ends in i leads to the trigram state (i, k) where that is kept, else to
-    the bigram state k"""
+def trigram_graph(gtn, np, seed=4321, arcs_share=0.25, pairs_share=0.1, C=C):
+    """a seeded back-off trigram over C labels: state 0 the unigram state (every label) and the start, 1 + i the bigram
+    state after i, then a trigram state per kept pair (j, i); a state has `arcs_share` of the labels and an epsilon arc
+    one order down; an arc labelled k out of a state that ends in i leads to the trigram state (i, k) where that is
+    kept, else to the bigram state k"""
     rng = np.random.default_rng(seed)
     kept = rng.random((C, C)) < pairs_share
     tri = np.full((C, C), -1, np.int64)
