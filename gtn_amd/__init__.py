@@ -72,6 +72,7 @@ debug_decode_stats = _api.debug_decode_stats  # (Batch.viterbi_decode: which rou
 debug_full_connect_stats = _api.debug_full_connect_stats  # (forward_score of a padded batch o ASG transitions: which route)
 debug_linear_decode_stats = _api.debug_linear_decode_stats  # (Batch.linear_decode: which route decoded how many)
 debug_ctc_beam_stats = _api.debug_ctc_beam_stats  # (Batch.ctc_beam_decode: calls that launched, utterances decoded)
+debug_ctc_sample_stats = _api.debug_ctc_sample_stats  # (Batch.ctc_sample: calls that launched, utterances sampled)
 edit_distance = _api.edit_distance  # (batched Levenshtein distance of device-resident token rows)
 debug_edit_distance_stats = _api.debug_edit_distance_stats  # (edit_distance: calls that launched, pairs computed)
 debug_ctc_score_stats = _api.debug_ctc_score_stats  # (Batch.ctc_score / ctc_score_grad: calls that launched, pairs taken)

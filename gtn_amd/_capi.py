@@ -133,6 +133,9 @@ _SIGS = {
     "gtnx_batch_linear_decode": [c_graph, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p],
     "gtnx_batch_linear_decode_stats": [c_i64_p, c_i64_p],
+    "gtnx_batch_ctc_sample": [c_graph, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_float, C.c_void_p, C.c_int64,
+                              C.c_void_p, C.c_void_p, C.c_void_p],
+    "gtnx_batch_ctc_sample_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_ctc_beam_decode": [c_graph, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64,
                                    C.c_void_p, C.c_void_p],
     "gtnx_batch_ctc_beam_decode_lm": [c_graph, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float,

@@ -909,6 +909,40 @@ def make_api(lib):
                     raise ValueError(f"{who}: {what} contiguous tensor [B, nbest]")
             return stride
 
+        def ctc_sample(self, tokens_out, lengths_out, logq_out=None, labels_out=None, frames=None, blank=0,
+                       num_samples=4, seed=0, temperature=1.0, row_stride=None):
+            """`num_samples` label sequences per utterance drawn from the CTC posterior of a Batch.linear, results left on
+            the device (gtnx_batch_ctc_sample; DESIGN section 32 holds the contract).  Frame t < T_b of sample k takes
+            label c with probability exp(x[b, t, c] / temperature) / Z[b, t], independently -- only finite entries carry
+            mass -- by inverse CDF in label order against a Philox4x32-10 uniform keyed by `seed` and counted by
+            (t, b, k): the same seed gives the same bytes whatever the strides, the other utterances' frame counts or
+            the pad rows hold, and the first N samples of a larger call are those of a call with N.
+            `tokens_out` (int32 CUDA tensor [B, num_samples, >= M] with contiguous rows, or a device address of
+            [B][num_samples][row_stride]) gets every alignment with repeats merged and `blank` dropped (blank = -1:
+            repeats merged only), -1 from its length to the row's width M -- the layout `ctc_beam_decode` writes, so
+            `ctc_score`, `edit_distance` and `ctc_token_align` take it as it is; `lengths_out` (int32
+            [B, num_samples]) the lengths; `logq_out` (float32 [B, num_samples], optional) the log-probability of each
+            drawn alignment, sum_t (x / temperature - log Z), float32 in frame order; `labels_out` (rows like
+            tokens_out, optional) the frame labels, -1 from T_b on.  A frame without a finite entry, or T_b = 0: -1
+            rows, length 0, logq -inf for every sample of that utterance.  `num_samples` 1 .. 1024, `temperature`
+            finite and > 0, `seed` 0 .. 2^64 - 1; `frames`: T_b per element (0 .. M, at most the rows the batch
+            carries; None: those rows).  Two launches with no copy back and no wait; rows from T_b on are never read.
+            Any batch but a Batch.linear is an error: there is no other route."""
+            n = len(self)
+            seed = int(seed)
+            if not 0 <= seed < (1 << 64):
+                raise ValueError("ctc_sample: seed must be in 0 .. 2^64 - 1")
+            stride = self._nbest_outputs("ctc_sample", tokens_out, num_samples, row_stride,
+                                         ((lengths_out, "torch.int32", "lengths_out must be an int32"),
+                                          (logq_out, "torch.float32", "logq_out must be a float32")))
+            if labels_out is not None and hasattr(labels_out, "data_ptr"):
+                if self._nbest_outputs("ctc_sample", labels_out, num_samples, None, ()) != stride:
+                    raise ValueError("ctc_sample: labels_out must have the row stride of tokens_out")
+            fr, fr_ptr = _frames_arg("ctc_sample", frames, n)
+            check(lib.gtnx_batch_ctc_sample(self._h, fr_ptr, int(blank), int(num_samples), seed, float(temperature),
+                                            _opt_ptr(tokens_out), int(stride), _opt_ptr(lengths_out),
+                                            _opt_ptr(logq_out), _opt_ptr(labels_out)))
+
         def asg_beam_decode(self, tokens_out, lengths_out, scores_out, frames, table, beam_size=16, cutoff_top_n=16,
                             nbest=1, row_stride=None, lm=None, lm_weight=1.0, insertion_bonus=0.0, am_scores_out=None):
             """ASG prefix beam search with N-best output over a Batch.linear, results left on the device
@@ -1409,6 +1443,11 @@ def make_api(lib):
         decoded (include/gtn_amd.h: gtnx_batch_ctc_beam_stats)"""
         return _stats2(lib.gtnx_batch_ctc_beam_stats)
 
+    def debug_ctc_sample_stats():
+        """(calls, utterances): calls of Batch.ctc_sample that have launched so far and the utterances they sampled
+        (include/gtn_amd.h: gtnx_batch_ctc_sample_stats)"""
+        return _stats2(lib.gtnx_batch_ctc_sample_stats)
+
     def debug_ctc_score_stats():
         """(calls, pairs): calls of Batch.ctc_score / Batch.ctc_score_grad that have launched so far and the pairs they
         took (include/gtn_amd.h: gtnx_batch_ctc_score_stats)"""
@@ -1520,6 +1559,7 @@ def make_api(lib):
     ns.debug_decode_stats = debug_decode_stats
     ns.debug_linear_decode_stats = debug_linear_decode_stats
     ns.debug_ctc_beam_stats = debug_ctc_beam_stats
+    ns.debug_ctc_sample_stats = debug_ctc_sample_stats
     ns.debug_edit_distance_stats = debug_edit_distance_stats
     ns.debug_ctc_score_stats = debug_ctc_score_stats
     ns.debug_ctc_token_align_stats = debug_ctc_token_align_stats

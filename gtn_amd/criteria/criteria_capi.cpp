@@ -88,6 +88,18 @@ GTN_EXPORT int gtn_ctc_decode_n(const void* emissions, int B, int T, int C, int 
   });
 }
 
+// num_samples label sequences per utterance drawn from the CTC posterior.  emissions: DEVICE float [B][T][C]; frames:
+// host int32 [B] or null; tokens: DEVICE int32 [B][num_samples][T]; lengths: DEVICE int32 [B][num_samples]; logq: DEVICE
+// float [B][num_samples] or null; labels: DEVICE int32 [B][num_samples][T] or null.
+GTN_EXPORT int gtn_ctc_sample_n(const void* emissions, int B, int T, int C, int blank, const int* frames,
+                                int num_samples, unsigned long long seed, float temperature, void* tokens,
+                                void* lengths, void* logq, void* labels) {
+  return guarded([&] {
+    gtn::criteria::ctcSampleBatch(emissions, B, T, C, blank, frames, num_samples, seed, temperature, tokens, lengths,
+                                  logq, labels);
+  });
+}
+
 // CTC prefix beam search with N-best output.  emissions: DEVICE float [B][T][C]; frames: host int32 [B] or null; tokens:
 // DEVICE int32 [B][nbest][T]; lengths: DEVICE int32 [B][nbest]; scores: DEVICE float [B][nbest].
 GTN_EXPORT int gtn_ctc_beam_decode_n(const void* emissions, int B, int T, int C, int blank, const int* frames,

@@ -163,6 +163,33 @@ inline void ctcDecodeBatch(
                         static_cast<int*>(collapsedDev), static_cast<int*>(startsDev), static_cast<int*>(lengthsDev));
 }
 
+/** `numSamples` label sequences per utterance drawn from the CTC posterior, results on the device: every frame takes a
+ *  label with probability exp(x / temperature) / Z over its finite entries, the alignment is collapsed
+ *  (gtnx_batch_ctc_sample has the contract; Philox4x32-10 keyed by `seed`, so a seed repeats a run).  `tokensDev`: device
+ *  int32 [B][numSamples][T], -1 from a sample's length on; `lengthsDev`: device int32 [B][numSamples]; `logqDev`: device
+ *  float [B][numSamples] or null, the log-probability of the drawn alignment; `labelsDev`: device int32
+ *  [B][numSamples][T] or null, the frame labels.  `frames`: host [B] or null -- how many of the T rows of each utterance
+ *  count (0 .. T); rows past them are never read.  `emissions`: device [B][T][C], read in place.  Two launches; nothing is
+ *  copied back. */
+inline void ctcSampleBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int C,
+    int blank,
+    const int* frames,
+    int numSamples,
+    uint64_t seed,
+    float temperature,
+    void* tokensDev,
+    void* lengthsDev,
+    void* logqDev,
+    void* labelsDev) {
+  Batch ems = Batch::linear(B, T, C, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  batched::ctcSample(ems, static_cast<int*>(tokensDev), T, static_cast<int*>(lengthsDev), static_cast<float*>(logqDev),
+                     static_cast<int*>(labelsDev), blank, numSamples, seed, temperature, frames);
+}
+
 /** CTC prefix beam search of a batch with N-best output, results on the device: per utterance the `nbest` best label
  *  sequences, summed over the alignments the beam kept (gtnx_batch_ctc_beam_decode has the contract).  `tokensDev`:
  *  device int32 [B][nbest][T], -1 from a hypothesis's length on; `lengthsDev`: device int32 [B][nbest]; `scoresDev`:

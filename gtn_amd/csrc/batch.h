@@ -169,6 +169,25 @@ void batch_decode_stats(int64_t* fast, int64_t* fallback);  // utterances decode
 void batch_linear_decode(const BatchP& ems, const int* frames, int blank, int* labels_dev, int64_t row_stride,
                          float* scores_dev, int* collapsed_dev, int* starts_dev, int* lengths_dev);
 void batch_linear_decode_stats(int64_t* fast, int64_t* fallback);  // utterances decoded by the launches / the path graphs
+// N alignments of every chain of a native LINEAR batch drawn from its frame posteriors, plus the CTC collapse, results
+// on the device (DESIGN section 32 holds the contract: frame t < T_b of sample k takes label c with probability
+// exp(x[b,t,c] / temperature) / Z[b,t] over the finite entries, by inverse CDF in label order against the uniform of
+// Philox4x32-10 at key `seed`, counter (t, b, k >> 2, 0), word k & 3).  tokens_dev[(b * N + k) * row_stride + i]: the
+// alignment with repeats merged and `blank` dropped (blank < 0: nothing dropped), -1 from its length to the row's width
+// M; lengths_dev[b * N + k]; logq_dev[b * N + k] (or null) = sum_t (x[b,t,c_t] / temperature - log Z[b,t]) in float32
+// in frame order; labels_dev (or null) the frame labels in the layout of tokens_dev, -1 from T_b to M.  A frame without
+// a finite entry, or T_b = 0: no path -- every sample of the utterance gets -1 rows, length 0, logq -inf.  frames (host,
+// [n], or null): T_b, null = rows_of(b).  Invalid argument before a device is asked for: a null batch, tokens or
+// lengths pointer, a negative stride, N outside 1 .. 1024, a temperature that is not finite and > 0.  With the device:
+// a batch that is not a native LINEAR one (there is no other route), a count outside 0 .. M or above rows_of(b),
+// row_stride < M, blank >= C, n * N beyond an int, outputs that are not memory of the current device.  Two launches of
+// ctc_sample.hip on the engine's stream per slice; 4 (with labels_dev) or 8 bytes per (b, k, t) of scratch from the
+// stream-ordered pool, at most 256 MiB per launch: beyond that the utterances run in slices with the same bytes (the
+// environment variable GTNX_CTC_SAMPLE_SCRATCH_BYTES, read per call, lowers the cap: a debug switch for tests).  Rows
+// from T_b on are never read, no download, no wait.
+void batch_ctc_sample(const BatchP& ems, const int* frames, int blank, int N, uint64_t seed, float temperature,
+                      int* tokens_dev, int64_t row_stride, int* lengths_dev, float* logq_dev, int* labels_dev);
+void batch_ctc_sample_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they sampled
 // CTC prefix beam search with N-best output over a native LINEAR batch, results on the device (DESIGN section 20 holds
 // the contract: token set of a frame = its topn best labels plus blank, at most `beam` distinct prefixes with (pb, pnb),
 // exact prefix merging, the total order of the candidates).  tokens_dev[(b * nbest + r) * row_stride + k]: the labels of

@@ -513,6 +513,88 @@ void batch_linear_decode(const BatchP& ems, const int* frames, int blank, int* l
   g_linear_decode.add(n, 0);
 }
 
+// ---- N sampled alignments per chain plus the CTC collapse, device-resident (ctc_sample.hip) ----
+namespace {
+constexpr const char* kCtcSample = "gtnx_batch_ctc_sample";
+Counters g_ctc_sample;  // (calls, utterances)
+// label and term of every (b, k, t) of one launch
+constexpr ScratchCap kCtcSampleScratch{"GTNX_CTC_SAMPLE_SCRATCH_BYTES", int64_t(256) << 20};
+}  // namespace
+
+void batch_ctc_sample_stats(int64_t* calls, int64_t* utterances) { g_ctc_sample.get(calls, utterances); }
+
+void batch_ctc_sample(const BatchP& ems, const int* frames, int blank, int N, uint64_t seed, float temperature,
+                      int* tokens_dev, int64_t row_stride, int* lengths_dev, float* logq_dev, int* labels_dev) {
+  GTNX_HOST_T("batch.ctc_sample");
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) refuse(kCtcSample, "null batch");
+  if (!tokens_dev || !lengths_dev) refuse(kCtcSample, "null output pointer (tokens and lengths are both written)");
+  if (row_stride < 0) refuse(kCtcSample, "negative row stride");
+  if (N < 1 || N > kCtcSampleMaxN) refuse(kCtcSample, "num_samples outside 1 .. 1024");
+  if (!std::isfinite(temperature) || !(temperature > 0.0f)) refuse(kCtcSample, "temperature must be finite and above 0");
+  Runtime& rt = Runtime::get();
+  const int n = ems->n;
+  // there is no other route: the sampler reads the slabs of a native linear batch
+  if (!native_linear(*ems)) refuse(kCtcSample, "not a native linear batch (gtnx_batch_linear / _rows)");
+  Batch& x = *ems;
+  check_frames(kCtcSample, frames, n, x.M, x);
+  if (n > 0 && row_stride < x.M) refuse(kCtcSample, "row_stride is shorter than the rows of the batch");
+  if (blank >= x.C) refuse(kCtcSample, "blank is not below the number of labels");
+  if (int64_t(n) * N > std::numeric_limits<int>::max()) refuse(kCtcSample, "n times num_samples does not fit an int");
+  if (n <= 0) return;
+  check_outputs_local(kCtcSample, {tokens_dev, lengths_dev, logq_dev, labels_dev});
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  const std::vector<int> fr = resolve_frames(frames, x);
+  DevMemP d_frames = upload_vec(fr);
+  CtcSampleArgs a{};
+  a.row_stride = row_stride;
+  a.label_stride = labels_dev ? row_stride : x.M;
+  a.M = x.M;
+  a.C = x.C;
+  a.blank = blank;
+  a.N = N;
+  a.fill_labels = labels_dev ? 1 : 0;
+  a.seed_lo = static_cast<unsigned>(seed & 0xffffffffu);
+  a.seed_hi = static_cast<unsigned>(seed >> 32);
+  a.temperature = temperature;
+  // the utterances in slices whose scratch stays within the cap: the term of every (b, k, t), and its label where the
+  // caller takes none
+  const int64_t per_utt = int64_t(N) * x.M * (labels_dev ? 4 : 8);
+  for_pair_slices(n, per_utt, kCtcSampleScratch, [&](int64_t b0, int64_t count) {
+    // algorithmic bytes.  rows: every emission of the rows that count once, label and term out.  collapse: those back
+    // in, the pad of the label rows, the token rows, length and logq.
+    double row_bytes = 0, col_bytes = 0;
+    for (int64_t b = b0; b < b0 + count; ++b) {
+      const int t = fr[size_t(b)];
+      row_bytes += 4.0 * x.C * t + 8.0 * N * t;
+      col_bytes += N * (8.0 * t + (labels_dev ? 4.0 * (x.M - t) : 0.0) + 4.0 * x.M + 8.0);
+    }
+    const size_t cells = std::max<size_t>(size_t(count) * size_t(N) * size_t(x.M), 1);
+    DevMemP terms = rt.alloc(sizeof(float) * cells);
+    DevMemP labs = labels_dev ? DevMemP() : rt.alloc(sizeof(int) * cells);
+    CtcSampleArgs s = a;
+    s.em = x.w_dev + b0 * x.M * x.C;
+    s.frames = d_frames->as<int>() + b0;
+    s.labels = labels_dev ? labels_dev + b0 * N * row_stride : labs->as<int>();
+    s.terms = terms->as<float>();
+    s.tokens = tokens_dev + b0 * N * row_stride;
+    s.lengths = lengths_dev + b0 * N;
+    s.logq = logq_dev ? logq_dev + b0 * N : nullptr;
+    s.n = static_cast<int>(count);
+    s.b0 = static_cast<int>(b0);
+    {
+      GTNX_PROF("ctc_sample_rows", row_bytes);
+      launch_ctc_sample(s, 0, rt.stream());
+    }
+    {
+      GTNX_PROF("ctc_sample_collapse", col_bytes);
+      launch_ctc_sample(s, 1, rt.stream());
+    }
+    // (the scratch goes back to the stream-ordered pool behind the launches)
+  });
+  g_ctc_sample.add(1, n);
+}
+
 // ---- CTC prefix beam search with N-best output, device-resident (ctc_beam.hip) ----
 namespace {
 constexpr const char* kCtcBeam = "gtnx_batch_ctc_beam_decode";

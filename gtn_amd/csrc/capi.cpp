@@ -900,6 +900,18 @@ GTNX_API gtnx_status_t gtnx_batch_linear_decode(gtnx_batch_t ems, const int* fra
 GTNX_API gtnx_status_t gtnx_batch_linear_decode_stats(int64_t* fast, int64_t* fallback) {
   return guard([&] { batch_linear_decode_stats(fast, fallback); });
 }
+GTNX_API gtnx_status_t gtnx_batch_ctc_sample(gtnx_batch_t ems, const int* frames, int blank, int num_samples,
+                                             uint64_t seed, float temperature, void* tokens_device, int64_t row_stride,
+                                             void* lengths_device, void* logq_device, void* labels_device) {
+  return guard([&] {
+    batch_ctc_sample(BH(ems), frames, blank, num_samples, seed, temperature, static_cast<int*>(tokens_device),
+                     row_stride, static_cast<int*>(lengths_device), static_cast<float*>(logq_device),
+                     static_cast<int*>(labels_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_ctc_sample_stats(int64_t* calls, int64_t* utterances) {
+  return guard([&] { batch_ctc_sample_stats(calls, utterances); });
+}
 GTNX_API gtnx_status_t gtnx_batch_ctc_beam_decode(gtnx_batch_t ems, const int* frames, int blank, int beam_size,
                                                   int cutoff_top_n, int nbest, void* tokens_device, int64_t row_stride,
                                                   void* lengths_device, void* scores_device) {

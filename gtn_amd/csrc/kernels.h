@@ -833,6 +833,32 @@ struct LinearDecodeArgs {
   int n, M, C, blank;
 };
 void launch_linear_decode(const LinearDecodeArgs& a, int which, hipStream_t st);
+// ctc_sample.hip: N alignments of every chain of an [n][M][C] tensor drawn from its frame posteriors at its own length
+// frames[b] (device, 0 .. M), then the CTC collapse, results on the device (the contract: DESIGN section 32).  Frame t
+// of sample k of utterance b0 + b takes label c with probability exp(x[c] / temperature) / Z over the finite entries,
+// by inverse CDF in label order against u = (2 * (word >> 9) + 1) * 2^-24, word = output (k & 3) of Philox4x32-10 with
+// key (seed_lo, seed_hi) and counter (t, b0 + b, k >> 2, 0).  which = 0: the rows -- labels[(b * N + k) * label_stride
+// + t] and terms[(b * N + k) * M + t] = x[c] / temperature - log Z; a row without a finite entry: label -1.
+// which = 1: one wave per (b, k) -- logq[b * N + k] (or null) = the terms added in frame order from 0, tokens[(b * N +
+// k) * row_stride + i] the labels with repeats merged and `blank` dropped (blank < 0: nothing dropped), -1 from
+// lengths[b * N + k] to M, the labels -1 from frames[b] to M when fill_labels is set (they are the caller's).  A label
+// of -1 below frames[b], or frames[b] = 0: no path -- -1 rows, length 0, logq -inf.  Nothing from row frames[b] on is
+// read.  N 1 .. 1024, temperature finite and > 0 (the engine has refused the rest).
+constexpr int kCtcSampleMaxN = 1024;
+struct CtcSampleArgs {
+  const GTNX_G float* em;
+  const GTNX_G int* frames;  // [n]
+  GTNX_G int* labels;        // [n][N][label_stride]: the caller's rows, or scratch with label_stride = M
+  GTNX_G float* terms;       // [n][N][M] of scratch
+  GTNX_G int* tokens;
+  GTNX_G int* lengths;
+  GTNX_G float* logq;
+  int64_t row_stride, label_stride;
+  int n, M, C, blank, N, b0, fill_labels;
+  unsigned seed_lo, seed_hi;
+  float temperature;
+};
+void launch_ctc_sample(const CtcSampleArgs& a, int which, hipStream_t st);
 // ctc_beam.hip: CTC prefix beam search with N-best output over every chain of an [n][M][C] tensor at its own length
 // frames[b] (device, 0 .. M), results on the device (the contract: DESIGN section 20).  which = 0: the rows -- the
 // token set S_t of every row that counts, (value, label) entries [n][M][topn + 1] and their counts [n][M] in scratch.

@@ -1,6 +1,6 @@
 """PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
-`asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_beam_decode`, `asg_beam_decode`, `edit_distance`, `ctc_score`,
-`ctc_token_align`, `asg_score` and `asg_token_align`.
+`asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_sample`, `ctc_beam_decode`, `asg_beam_decode`, `edit_distance`,
+`ctc_score`, `ctc_token_align`, `asg_score` and `asg_token_align`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -31,6 +31,7 @@ _ARGTYPES = {
     "gtn_asg_align_n": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gtn_asg_decode_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "gtn_ctc_decode_n": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "gtn_ctc_sample_n": [_P, _I, _I, _I, _I, _P, _I, C.c_uint64, _F, _P, _P, _P, _P],
     "gtn_ctc_beam_decode_n": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P],
     "gtn_ctc_beam_decode_lm_n": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _F, _F, _P, _P, _P, _P],
     "gtn_ctc_beam_decode_graph_n": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _F, _F, _P, _P, _P, _P],
@@ -571,6 +572,57 @@ def ctc_decode(log_probs, blank=0, input_lengths=None, collapse=True):
            (blank, _host_ptr(frames), labels.data_ptr(), scores.data_ptr(), _ptr(tokens), _ptr(starts), _ptr(lengths)),
            "linear_decode", labels, scores, frames, blank, tokens, starts, lengths, row_stride=T)
     return (labels, scores, tokens, starts, lengths) if collapse else (labels, scores)
+
+
+def ctc_sample(log_probs, blank=0, input_lengths=None, num_samples=4, temperature=1.0, seed=None, return_labels=False):
+    """`num_samples` label sequences per utterance drawn from the CTC posterior, device-resident: the frames of a CTC
+    alignment are independent, so one categorical draw per frame plus the CTC collapse is an exact sample of P(y | x)
+    -- one stream over the emissions and one collapse, two launches whatever the lengths, nothing copied back.  What
+    sampled minimum Bayes risk, scheduled sampling and calibration need where `ctc_beam_decode` gives the top of the
+    distribution.
+    log_probs: float32 CUDA tensor [B, T, C] (any scores: frame t takes label c with probability
+    exp(x[b, t, c] / temperature) / Z[b, t]), read in place and left untouched; rows past an utterance's length are
+    never read; blank: the label the collapse drops (negative: none, repeats are merged only); input_lengths:
+    per-utterance frame counts (0 .. T) or None; num_samples 1 .. 1024; temperature finite and > 0; seed: 0 .. 2^64 - 1
+    keys the Philox4x32-10 counters (t, b, k), so a seed repeats a run bit for bit -- None takes one 63-bit integer
+    from torch's default CPU generator, so that `torch.manual_seed` repeats a run, without a device sync.
+    Returns (tokens int32 [B, num_samples, T], lengths int32 [B, num_samples], logq float32 [B, num_samples]) on
+    log_probs.device -- the layout of `ctc_beam_decode`, which `ctc_score`, `edit_distance` and `ctc_token_align` take
+    as it is: the collapsed alignment, -1 from its length on, and the log-probability of the drawn ALIGNMENT,
+    sum_t (x / temperature - log Z), float32 in frame order (the sequence's own log-probability is `ctc_score` minus
+    the sum of log Z).  With return_labels a fourth tensor, int32 [B, num_samples, T], has the frame labels, -1 from
+    the utterance's length on.  Only finite entries carry mass: -inf, +inf and NaN are never drawn, and a frame
+    without a finite entry, or an utterance without frames, leaves every sample of that utterance at -1, length 0 and
+    logq -inf.  Runs on the caller's stream; no autograd."""
+    if log_probs.dim() != 3 or log_probs.dtype != torch.float32:
+        raise ValueError("ctc_sample: log_probs must be a float32 tensor [B, T, C]")
+    B, T, N = log_probs.shape
+    blank, num_samples, temperature = int(blank), int(num_samples), float(temperature)
+    if blank >= N:
+        raise ValueError(f"ctc_sample: blank must be below the {N} labels (negative: no blank)")
+    if not 1 <= num_samples <= 1024:
+        raise ValueError("ctc_sample: num_samples outside 1 .. 1024")
+    if not (math.isfinite(temperature) and temperature > 0.0):
+        raise ValueError("ctc_sample: temperature must be finite and above 0")
+    frames = None if input_lengths is None else _frame_counts("ctc_sample", input_lengths, B, T, 0)
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())  # (a CPU tensor: no device sync)
+    seed = int(seed)
+    if not 0 <= seed < (1 << 64):
+        raise ValueError("ctc_sample: seed must be in 0 .. 2^64 - 1")
+    if not log_probs.is_cuda:
+        raise RuntimeError("ctc_sample: log_probs must be a CUDA tensor (the sampler runs on the device)")
+    x = log_probs.detach().contiguous()
+    stream = _engine_stream(x.device)
+    tokens = torch.empty(B, num_samples, T, dtype=torch.int32, device=x.device)
+    lengths = torch.empty(B, num_samples, dtype=torch.int32, device=x.device)
+    logq = torch.empty(B, num_samples, dtype=torch.float32, device=x.device)
+    labels = torch.empty(B, num_samples, T, dtype=torch.int32, device=x.device) if return_labels else None
+    _route(stream, x, _has_native("ctc_sample", "gtn_ctc_sample_n"), "gtn_ctc_sample_n",
+           (blank, _host_ptr(frames), num_samples, seed, temperature, tokens.data_ptr(), lengths.data_ptr(),
+            logq.data_ptr(), _ptr(labels)),
+           "ctc_sample", tokens, lengths, logq, labels, frames, blank, num_samples, seed, temperature, row_stride=T)
+    return (tokens, lengths, logq, labels) if return_labels else (tokens, lengths, logq)
 
 
 def ctc_beam_decode(log_probs, blank=0, input_lengths=None, beam_size=16, cutoff_top_n=16, nbest=1, transitions=None,

@@ -186,6 +186,20 @@ inline void linearDecode(const Batch& ems, int* labelsDevice, int64_t rowStride,
   detail::check(gtnx_batch_linear_decode(ems.handle(), frames, blank, labelsDevice, rowStride, scoresDevice,
                                          collapsedDevice, startsDevice, lengthsDevice));
 }
+/** numSamples alignments of every chain of a Batch::linear drawn from its frame posteriors (label c of frame t with
+ *  probability exp(x / temperature) / Z over the finite entries, inverse CDF in label order, Philox4x32-10 keyed by
+ *  `seed`), plus the CTC collapse, results left on the device: tokensDevice int32 [n][numSamples][rowStride] (the
+ *  alignment with repeats merged and `blank` dropped, then -1 up to the row's width M), lengthsDevice int32
+ *  [n][numSamples], logqDevice (may be null) float32 [n][numSamples] the log-probability of the drawn alignment,
+ *  labelsDevice (may be null) int32 [n][numSamples][rowStride] the frame labels.  A frame without a finite entry or
+ *  T_b = 0: -1, 0, -inf.  numSamples 1 .. 1024; frames (host, [n]): T_b, null = the rows the batch carries.  Two
+ *  launches, no copy back, no wait, rows from T_b on are never read -- gtnx_batch_ctc_sample */
+inline void ctcSample(const Batch& ems, int* tokensDevice, int64_t rowStride, int* lengthsDevice,
+                      float* logqDevice = nullptr, int* labelsDevice = nullptr, int blank = 0, int numSamples = 4,
+                      uint64_t seed = 0, float temperature = 1.0f, const int* frames = nullptr) {
+  detail::check(gtnx_batch_ctc_sample(ems.handle(), frames, blank, numSamples, seed, temperature, tokensDevice,
+                                      rowStride, lengthsDevice, logqDevice, labelsDevice));
+}
 /** CTC prefix beam search with N-best output over a Batch::linear, results left on the device: tokensDevice int32
  *  [n][nbest][rowStride] (the labels of hypothesis r, then -1 up to the row's width M), lengthsDevice int32 [n][nbest],
  *  scoresDevice float32 [n][nbest] (the log score summed over the alignments the beam kept); slots without a hypothesis:

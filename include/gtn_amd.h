@@ -370,6 +370,40 @@ gtnx_status_t gtnx_batch_linear_decode(gtnx_batch_t ems, const int* frames, int 
                                        void* starts_device, void* lengths_device);
 /* utterances decoded so far (process-wide) by the launches / by the path-graph route */
 gtnx_status_t gtnx_batch_linear_decode_stats(int64_t* fast, int64_t* fallback);
+/* num_samples alignments of every chain of a batch drawn from its frame posteriors, plus the CTC collapse, results left
+ * on the device: exact samples of P(y | x) of a CTC model, whose frames are independent (DESIGN section 32 has the
+ * whole contract).  For utterance b, sample k and frame t < T_b the label is c with probability
+ * exp(x[b,t,c] / temperature) / Z[b,t], independently, Z[b,t] the sum over the entries that carry mass.
+ *   Mass: only finite entries carry mass; -inf, +inf and NaN are never chosen and are left out of Z.  A frame without a
+ *   finite entry, or T_b == 0, leaves the utterance without a path: every sample of it gets -1 rows, length 0 and
+ *   logq = -inf (what gtnx_batch_linear_decode does).  No output is ever NaN.
+ *   Draw: inverse CDF in label order.  With u the uniform of (b, k, t), the label is the smallest c whose cumulative
+ *   mass over labels 0 .. c exceeds u * Z; if rounding leaves none, the last label with mass.  A label without mass is
+ *   never returned.
+ *   Randomness is counter-based: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (t, b, k >> 2, 0);
+ *   sample k uses output word k & 3, u = (2 * (word >> 9) + 1) * 2^-24, strictly inside (0, 1) and exact in float32.
+ *   The same seed gives the same bytes whatever the strides, the slicing, the frame counts of the other utterances or
+ *   the contents of pad rows, and the first N samples of a call with more are those of a call with N.
+ * tokens_device: int32 [n][num_samples][row_stride], row_stride >= M: the alignment with repeats merged and `blank`
+ * dropped (blank = -1: repeats merged only), -1 from its length to M -- the layout gtnx_batch_ctc_beam_decode writes;
+ * lengths_device: int32 [n][num_samples]; logq_device (may be null): float32 [n][num_samples], sum_t (x[b,t,c_t] /
+ * temperature - log Z[b,t]), added in frame order from 0 in float32; labels_device (may be null): int32
+ * [n][num_samples][row_stride], the frame labels, -1 from T_b to M.
+ * frames (host, [n], or null): T_b; null means the rows the batch carries.  Rows from T_b on are never read.
+ * GTNX_INVALID_ARGUMENT before a device is asked for: a null batch, tokens or lengths pointer, a negative stride,
+ * num_samples outside 1 .. 1024, a temperature that is not finite and > 0.  With the device: ems is not a
+ * gtnx_batch_linear / _rows batch (there is no other route), a count outside 0 .. M or above the rows the batch carries,
+ * row_stride < M, blank >= C, n * num_samples beyond an int, outputs the engine's current device may not write.  A
+ * refused call writes nothing.
+ * Two launches on the engine's stream (ctc_sample.hip); the label and term of every (b, k, t) live in scratch from the
+ * stream-ordered pool, at most 256 MiB per launch: beyond that the utterances run in slices with the same bytes
+ * (GTNX_CTC_SAMPLE_SCRATCH_BYTES, read per call, lowers the cap: a debug switch for tests).  Nothing is copied back and
+ * the call does not wait for the device. */
+gtnx_status_t gtnx_batch_ctc_sample(gtnx_batch_t ems, const int* frames, int blank, int num_samples, uint64_t seed,
+                                    float temperature, void* tokens_device, int64_t row_stride, void* lengths_device,
+                                    void* logq_device /* may be null */, void* labels_device /* may be null */);
+/* calls that have launched so far (process-wide) / utterances they sampled */
+gtnx_status_t gtnx_batch_ctc_sample_stats(int64_t* calls, int64_t* utterances);
 /* CTC prefix beam search with N-best output over a whole batch of chains, results left on the device: the best LABEL
  * SEQUENCES, summed over their alignments, where gtnx_batch_linear_decode gives the best alignment.  Per frame the
  * token set is the cutoff_top_n best labels of the row (value descending, of equal values the smaller label; NaN and
