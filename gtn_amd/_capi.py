@@ -109,6 +109,10 @@ _SIGS = {
     "gtnx_union": [c_graph_p, C.c_int, c_graph_p],
     "gtnx_batch_from_graphs": [c_graph_p, C.c_int, c_graph_p],
     "gtnx_batch_ctc_targets": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_graph_p],
+    "gtnx_batch_ctc_loss_step": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                 C.c_void_p, C.c_int, C.c_void_p],
+    "gtnx_batch_ctc_loss_step_ok": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.POINTER(C.c_int)],
     "gtnx_batch_asg_force_align": [C.c_void_p, C.c_void_p, C.c_int, c_graph, C.c_int, c_graph_p],
     "gtnx_batch_linear": [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, c_graph_p],
     "gtnx_batch_linear_rows": [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, c_graph_p],

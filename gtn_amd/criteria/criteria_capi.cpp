@@ -191,6 +191,19 @@ GTN_EXPORT int gtn_ctc_loss_target_grads_n(const void* emissions, const int* tar
   });
 }
 
+// ctcLossBatch as it stands, every switch of it: frames (host int32 [B]) or null; grad may be null; target_grad != 0:
+// the targets are built with calcGrad = true, and target_grad_dev (DEVICE float, or null) receives their arc gradients,
+// utterance b's at the running sum of the arc counts in front of it.  Which path ran -- the one-launch step or the
+// graph-level operations (GTNX_CTC_STEP_FUSED=0, or a batch the launch does not take) -- is ctcLossBatch's decision.
+GTN_EXPORT int gtn_ctc_loss_step_n(const void* emissions, const int* targets, const int* lengths, int B, int T, int C,
+                                   int blank, const int* frames, void* loss, void* grad, int target_grad,
+                                   void* target_grad_dev) {
+  return guarded([&] {
+    gtn::criteria::ctcLossBatch(emissions, targets, lengths, B, T, C, blank, loss, grad, target_grad != 0, nullptr, nullptr,
+                                frames, target_grad_dev);
+  });
+}
+
 // ASG over a shared transitions graph.  emissions: DEVICE float [B][T][N]; targets / lengths:
 // host int32 (concatenated / [B]); trans_w: DEVICE float [N + N*N] in the arc order of
 // gtn::criteria::asgTransitions BEFORE its arcSort (arc i: <s> -> i; arc N + i*N + j: j -> i);

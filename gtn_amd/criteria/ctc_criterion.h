@@ -8,6 +8,7 @@
 
 #include <chrono>
 #include <cstdint>
+#include <cstdlib>
 #include <stdexcept>
 #include <vector>
 
@@ -51,7 +52,9 @@ struct CtcStepTimes {
  *  per-utterance graphs.  `emissions`: device [B][T][C], read in place; `lossDev`: device [B];
  *  `gradDev`: device [B][T][C] (d loss / d emissions, written in place) or null.  Targets may have
  *  different lengths.  `frames` (host [B], or null): a padded batch -- utterance b has frames[b] <= T frames, the
- *  loss is that of emissions_b[:frames[b]], rows past them are never read and their gradient is 0. */
+ *  loss is that of emissions_b[:frames[b]], rows past them are never read and their gradient is 0.
+ *  A batch with a gradient buffer, no `targetsOut`, full frame counts and a shape the engine's one-launch step takes
+ *  (gtnx_batch_ctc_loss_step_ok) runs as that ONE launch; GTNX_CTC_STEP_FUSED=0 keeps the graph-level operations. */
 inline void ctcLossBatch(
     const void* emissions,
     const int* labels,   // target sequences back to back
@@ -65,12 +68,33 @@ inline void ctcLossBatch(
     bool targetGrad = true,  // benchmarks/ctc.cpp builds its targets with calcGrad = true
     CtcStepTimes* times = nullptr,
     Batch* targetsOut = nullptr,  // the target acceptors (their gradients populated when targetGrad) handed back
-    const int* frames = nullptr) {
+    const int* frames = nullptr,
+    void* targetGradDev = nullptr) {  // device float, or null: the targets' arc gradients (targetGrad), utterance b's at
+                                      // the running sum of the arc counts in front of it
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
   if (frames)  // (before anything is launched)
     for (int b = 0; b < B; ++b)
       if (frames[b] < 1 || frames[b] > T) throw std::invalid_argument("[ctcLossBatch] a frame count outside 1 .. T");
+  // The whole step as ONE launch (gtnx_batch_ctc_loss_step: target records, both band sweeps and the loss by one
+  // workgroup per utterance) when the batch is one that launch takes; everything else, and GTNX_CTC_STEP_FUSED=0 (read
+  // on every call: one process can run both paths), runs the graph-level operations below.  Decided here, on the host,
+  // before anything is launched; the results are the same bit for bit.
+  if (gradDev && !targetsOut && B > 0) {
+    bool full = true;  // (padded batches stay on the graph-level path)
+    for (int b = 0; frames && b < B && full; ++b) full = frames[b] == T;
+    const char* sw = std::getenv("GTNX_CTC_STEP_FUSED");
+    int ok = 0;
+    if (full && !(sw && sw[0] == '0' && sw[1] == 0))
+      detail::check(gtnx_batch_ctc_loss_step_ok(labels, lengths, B, T, C, blank, emissions, gradDev, &ok));
+    if (ok) {
+      auto t0 = now();
+      detail::check(gtnx_batch_ctc_loss_step(emissions, labels, lengths, B, T, C, blank, lossDev, gradDev, targetGrad ? 1 : 0,
+                                             targetGrad ? targetGradDev : nullptr));
+      if (times) *times = {0, 0, 0, ms(t0, now()), 0};  // (one phase carries the whole call)
+      return;
+    }
+  }
   auto t0 = now();
   Batch ctcs = Batch::ctcTargets(labels, lengths, B, blank, targetGrad);
   auto t1 = now();
@@ -93,6 +117,18 @@ inline void ctcLossBatch(
   if (times) *times = {ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4), ms(t4, t5)};
   losses.itemsToDevice(lossDev);
   if (gradDev) ems.gradsToDevice(gradDev, off.data());  // (nothing to copy when the rows were written in place)
+  if (targetGradDev && targetGrad && gradDev) {
+    std::vector<int64_t> goff(static_cast<size_t>(B));
+    int64_t run = 0, lo = 0;
+    for (int b = 0; b < B; ++b) {  // arcs of acceptor b: 2U+1 self loops, 2U steps, a skip per change of label
+      const int U = lengths[b];
+      goff[static_cast<size_t>(b)] = run;
+      run += 4 * int64_t(U) + 1;
+      for (int u = 1; u < U; ++u) run += labels[lo + u] != labels[lo + u - 1] ? 1 : 0;
+      lo += U;
+    }
+    ctcs.gradsToDevice(targetGradDev, goff.data());
+  }
   if (targetsOut) *targetsOut = std::move(ctcs);
 }
 

@@ -167,7 +167,17 @@
       h2 = __builtin_elementwise_fma(f2v{v[k].x, v[k].y}, f2v{R.hot[k].x, R.hot[k].y}, h2);
       h2 = __builtin_elementwise_fma(f2v{v[k].z, v[k].w}, f2v{R.hot[k].z, R.hot[k].w}, h2);
     }
-    float all = (a2.x + a2.y) * R.in, hotp = h2.x + h2.y;
+#ifdef GTNX_BWD_RS4_LEAN
+    // (set by a kernel that has one vector register less for this sweep -- ctc_step.hip: "is this lane's group of sixteen
+    //  nodes inside the row" is worked out again at every use, a handful of instructions in a wave that idles through
+    //  half of a tick, instead of living in a register across the loop; settle() keeps it from being hoisted back out)
+    int nb_l = 16 * (l & 15);
+    settle(nb_l);
+    const float r_in = nb_l < NSmax ? 1.0f : 0.0f;
+#else
+    const float r_in = R.in;
+#endif
+    float all = (a2.x + a2.y) * r_in, hotp = h2.x + h2.y;
     if (dead_r) all = hotp = 0.0f;  // nothing wrote the ring
     row_sum15x2(all, hotp);          // totals of row r in lane 16 r + 15
     const bool have = all != 0.0f && !dead_r;

@@ -4,6 +4,8 @@
 // (-DGTNX_FWD_SHIFT_ROWS=8: one shift per block of eight rows -- measured: the forward sweep 2.3 % faster (0.214 against
 //  0.219 ms), emission gradients 2.2e-5 instead of 1.9e-5 from float64 and target-arc gradients 1.3e-4 instead of 8e-5
 //  at C3; the accuracy is kept)
+// (-DGTNX_FWD_IDLE_FROM=w, set by the including kernel: waves w and up have no role and only keep the barrier count;
+//  not defined -- band.hip -- the workgroup is the eight waves of the two roles)
 #ifndef GTNX_FWD_SHIFT_ROWS
 #define GTNX_FWD_SHIFT_ROWS 4
 #endif
@@ -215,6 +217,14 @@
       M.fin[2 * w + 1] = s;
       M.find[w] = off;
     }
+#ifdef GTNX_FWD_IDLE_FROM
+  } else if (wv >= GTNX_FWD_IDLE_FROM) {
+    // ------------------------------------------------------------------ waves without a role in this sweep (a workgroup
+    // shared with the backward sweep's twelve, ctc_step.hip): a wave that has ended no longer counts at a barrier, so
+    // these stay and meet every barrier the other roles do -- the prologue's and one per tick
+    lds_barrier();
+    for (int tau = 0; tau < nticks; ++tau) lds_barrier();
+#endif
   } else {
     // ------------------------------------------------------------------ helpers: everything else
     const int hid = threadIdx.x - BW;

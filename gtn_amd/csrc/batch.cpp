@@ -512,6 +512,141 @@ BatchP batch_ctc_targets(const int* labels, const int* lengths, int n, int blank
   return b;
 }
 
+// ---- the CTC criterion step as ONE launch (ctc_step.hip)
+namespace {
+// every argument the launch cannot take, before anything is allocated; what it can take but has no cell for is
+// ctc_step_fused_ok's to say
+void ctc_step_validate(const void* emissions, const int* labels, const int* lengths, int n, int T, int C, const void* loss,
+                       const void* grad) {
+  if (n <= 0) throw_invalid("[gtnx_batch_ctc_loss_step] the batch size must be positive");
+  if (!emissions || !lengths || !loss || !grad) throw_invalid("[gtnx_batch_ctc_loss_step] null emissions, lengths, loss or gradient");
+  if (T < 1 || C < 1) throw_invalid("[gtnx_batch_ctc_loss_step] T and C must be positive");
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (lengths[i] < 0) throw_invalid("[gtnx_batch_ctc_loss_step] negative length");
+    total += lengths[i];
+  }
+  if (total > 0 && !labels) throw_invalid("[gtnx_batch_ctc_loss_step] null labels");
+}
+}  // namespace
+
+bool ctc_step_fused_ok(const int* labels, const int* lengths, int n, int T, int C, int blank, const void* emissions,
+                       const void* grad) {
+  if (n <= 0 || !lengths || !emissions || !grad) return false;
+  if (T < 1 || T > (1 << 20) || C < band_min_labels() || C % 4 != 0) return false;
+  if (blank < 0 || blank >= C) return false;
+  // (16-byte rows: the sweeps stage emissions and the caller's gradient rows by whole 16-byte pieces)
+  if ((reinterpret_cast<uintptr_t>(emissions) & 15) != 0 || (reinterpret_cast<uintptr_t>(grad) & 15) != 0) return false;
+  int max_len = 0;
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (lengths[i] < 0) return false;
+    max_len = std::max(max_len, lengths[i]);
+    total += lengths[i];
+  }
+  if (2 * max_len + 1 > 256) return false;  // one node per lane of the four sweeper waves
+  if (total > 0 && !labels) return false;
+  for (int64_t i = 0; i < total; ++i)
+    if (labels[i] < 0 || labels[i] >= C) return false;
+  if (total * 3 + 2 * int64_t(n) > (int64_t(1) << 30)) return false;  // (arc-gradient offsets are 32-bit)
+  // The launch reads its staging block (entries, labels) in place from pinned host memory.  GTNX_H2D_KERNEL_BYTES is the
+  // largest pinned block a kernel of ours may fetch (runtime.cpp: h2d_pinned, default 1 MB): a larger block, or the
+  // switch at 0, keeps the step on the graph-level path, whose tables then travel by the runtime's copies.
+  static const size_t pinned_lim = [] {
+    const char* e = std::getenv("GTNX_H2D_KERNEL_BYTES");
+    return e ? size_t(std::atol(e)) : size_t(1) << 20;
+  }();
+  if (align_up(sizeof(int) * 4 * size_t(n), 256) + sizeof(int) * size_t(total ? total : 1) > pinned_lim) return false;
+  return ctc_step_cell(C, band_row_stride(2 * max_len + 1, 1));
+}
+
+void batch_ctc_loss_step(const void* emissions, const int* labels, const int* lengths, int n, int T, int C, int blank,
+                         void* loss, void* grad, bool target_grad, void* target_grad_dev) {
+  GTNX_HOST_T("batch.ctc_loss_step");
+  ctc_step_validate(emissions, labels, lengths, n, T, C, loss, grad);
+  if (!ctc_step_fused_ok(labels, lengths, n, T, C, blank, emissions, grad))
+    throw_invalid("[gtnx_batch_ctc_loss_step] not a batch the one-launch step takes (gtnx_batch_ctc_loss_step_ok)");
+  Runtime& rt = Runtime::get();
+  int max_len = 0;
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    max_len = std::max(max_len, lengths[i]);
+    total += lengths[i];
+  }
+  const int max_n = 2 * max_len + 1, max_ns = band_row_stride(max_n, 1);
+  // ---- staging, one pinned block the kernel reads in place: [n] entries {label offset, U, rows, arc offset} | labels
+  const size_t ent_bytes = align_up(sizeof(int) * 4 * size_t(n), 256);
+  PinnedMemP pin = rt.alloc_pinned(ent_bytes + sizeof(int) * size_t(total ? total : 1));
+  int* ent = pin->as<int>();
+  int* lab = pin->as<int>(ent_bytes);
+  if (total) std::memcpy(lab, labels, sizeof(int) * size_t(total));
+  int64_t lab_off = 0, arcs = 0;
+  double bytes = 0;
+  for (int i = 0; i < n; ++i) {
+    const int U = lengths[i], N = 2 * U + 1;
+    // arcs of the acceptor (benchmarks/ctc.cpp:40-58): a self loop per node, a step arc per node but the first, a skip
+    // arc into every label node whose label differs from the label before it
+    int64_t a = int64_t(N) + (N - 1);
+    for (int u = 1; u < U; ++u) a += labels[lab_off + u] != labels[lab_off + u - 1] ? 1 : 0;
+    ent[4 * i + 0] = int(lab_off);
+    ent[4 * i + 1] = U;
+    ent[4 * i + 2] = T;
+    ent[4 * i + 3] = int(arcs);
+    bytes += 12.0 * T * C + 8.0 * double(T + 1) * band_row_stride(N, 1) + (target_grad ? 4.0 * double(a) : 0.0);
+    lab_off += U;
+    arcs += a;
+  }
+  // ---- one arena, every per-utterance stride that of the widest target:
+  // score [n] | norm [n] | rowlse [n][T] | shifts [n][4T + 16] doubles | alpha planes | band records | (arc gradients)
+  const size_t aoff_stride = align_up(4 * size_t(T) + 16, 32);                         // doubles
+  const size_t alpha_stride = align_up(size_t(T + 1) * size_t(max_ns), 64);            // floats
+  const size_t o_flags = align_up(sizeof(BandNode) * size_t(max_n), 64), o_snode = o_flags + align_up(size_t(max_n), 64),
+               o_slab = o_snode + align_up(4 * size_t(max_n), 64), rec_stride = o_slab + align_up(4 * size_t(max_n), 64);
+  size_t at = 0;
+  auto take = [&](size_t b) {
+    const size_t o = at;
+    at = align_up(at + b, 256);
+    return o;
+  };
+  const size_t o_score = take(4 * size_t(n)), o_norm = take(4 * size_t(n)), o_lse = take(4 * size_t(n) * size_t(T)),
+               o_aoff = take(8 * size_t(n) * aoff_stride), o_alpha = take(4 * size_t(n) * alpha_stride),
+               o_rec = take(size_t(n) * rec_stride),
+               o_tg = take(target_grad && !target_grad_dev ? 4 * size_t(arcs ? arcs : 1) : 0);
+  DevMemP arena = rt.alloc(at);
+  CtcStepDesc d{};
+  d.stage = ent;
+  d.labels = lab;
+  d.em = static_cast<const float*>(emissions);
+  d.grad = static_cast<float*>(grad);
+  d.loss = static_cast<float*>(loss);
+  d.tgrad = target_grad ? (target_grad_dev ? static_cast<float*>(target_grad_dev) : arena->as<float>(o_tg)) : nullptr;
+  d.rec = arena->as<char>(o_rec);
+  d.alpha = arena->as<float>(o_alpha);
+  d.aoff = arena->as<double>(o_aoff);
+  d.rowlse = arena->as<float>(o_lse);
+  d.score = arena->as<float>(o_score);
+  d.norm = arena->as<float>(o_norm);
+  d.em_stride = int64_t(T) * C;
+  d.rec_stride = int64_t(rec_stride);
+  d.alpha_stride = int64_t(alpha_stride);
+  d.aoff_stride = int64_t(aoff_stride);
+  d.o_flags = int(o_flags);
+  d.o_snode = int(o_snode);
+  d.o_slab = int(o_slab);
+  d.T = T;
+  d.C = C;
+  d.blank = blank;
+  d.lgrn = band_forward_lgrn(C);
+  {
+    // (the family of the backward sweep: the launch does that sweep's work and the forward sweep's, and is priced
+    //  with the algorithmic bytes of both -- 12 T C + 8 (T + 1) NS + 4 A per utterance)
+    GTNX_PROF("band_forward_score_grad", bytes);
+    launch_ctc_step(d, n, max_ns, target_grad, rt.stream());
+  }
+  // (pin and arena go back to their pools here: the stream is in order, and a pinned block is handed out again only
+  //  after an event recorded behind this launch has passed -- runtime.cpp)
+}
+
 
 BatchP batch_asg_force_align(const int* labels, const int* lengths, int n, Graph& transitions, int n_labels) {
   if (n < 0) throw_invalid("[gtnx_batch_asg_force_align] negative batch size");

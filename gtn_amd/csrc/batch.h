@@ -118,6 +118,16 @@ struct Batch {
 
 BatchP batch_from_graphs(std::vector<Graph> gs);
 BatchP batch_ctc_targets(const int* labels, const int* lengths, int n, int blank, bool calc_grad);
+// One CTC criterion step in ONE launch (ctc_step.hip): loss_b = forwardScore(emissions_b) - forwardScore(target_b o
+// emissions_b) into loss[b], d loss / d emissions into grad, and -- target_grad -- the targets' arc gradients into
+// target_grad_dev (utterance b's at the running sum of the arc counts in front of it; null: computed and dropped).
+// What the graph-level operations compute for the same batch, bit for bit.  ctc_step_fused_ok: is the batch one the
+// launch is instantiated for?  A pure host function (no device is asked); batch_ctc_loss_step throws
+// GTNX_INVALID_ARGUMENT for a batch it is not.
+bool ctc_step_fused_ok(const int* labels, const int* lengths, int n, int T, int C, int blank, const void* emissions,
+                       const void* grad);
+void batch_ctc_loss_step(const void* emissions, const int* labels, const int* lengths, int n, int T, int C, int blank,
+                         void* loss, void* grad, bool target_grad, void* target_grad_dev);
 BatchP batch_asg_force_align(const int* labels, const int* lengths, int n, Graph& transitions, int n_labels);
 // rows (host, [n], or null): the rows of each element that count (Batch::rows); outside 1 .. M: invalid argument
 BatchP batch_linear(int n, int M, int C, bool calc_grad, const void* dev, bool borrow, const int* rows = nullptr);

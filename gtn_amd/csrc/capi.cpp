@@ -806,6 +806,20 @@ GTNX_API gtnx_status_t gtnx_batch_ctc_targets(const int* labels, const int* leng
                                               gtnx_batch_t* out) {
   return guard([&] { *out = HB(batch_ctc_targets(labels, lengths, n, blank, cg != 0)); });
 }
+GTNX_API gtnx_status_t gtnx_batch_ctc_loss_step(const void* emissions, const int* labels, const int* lengths, int n, int T,
+                                                int C, int blank, void* loss, void* grad, int target_grad,
+                                                void* target_grad_dev) {
+  return guard([&] {
+    batch_ctc_loss_step(emissions, labels, lengths, n, T, C, blank, loss, grad, target_grad != 0, target_grad_dev);
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_ctc_loss_step_ok(const int* labels, const int* lengths, int n, int T, int C, int blank,
+                                                   const void* emissions, const void* grad, int* ok) {
+  return guard([&] {
+    if (!ok) throw_invalid("[gtnx_batch_ctc_loss_step_ok] null result pointer");
+    *ok = ctc_step_fused_ok(labels, lengths, n, T, C, blank, emissions, grad) ? 1 : 0;
+  });
+}
 GTNX_API gtnx_status_t gtnx_batch_asg_force_align(const int* labels, const int* lengths, int n, gtnx_graph_t transitions,
                                                   int n_labels, gtnx_batch_t* out) {
   return guard([&] { *out = HB(batch_asg_force_align(labels, lengths, n, G(transitions), n_labels)); });

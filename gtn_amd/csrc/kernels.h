@@ -658,6 +658,29 @@ struct CtcTargetArgs {
   int N, pad;
 };
 void launch_ctc_targets(const CtcTargetArgs* d_args, int n, int blank, hipStream_t st);
+// One CTC criterion step of a batch in ONE launch (ctc_step.hip): workgroup b builds utterance b's target records, runs
+// both band sweeps and writes loss_b in between.  Travels BY VALUE with the launch: every per-utterance address is a
+// base + b * a stride sized by the batch's largest target, so no table is uploaded.
+struct CtcStepDesc {
+  const GTNX_G int* stage;    // PINNED HOST memory, read in place: [n] entries {label offset, U, rows, arc-gradient offset}
+  const GTNX_G int* labels;   // PINNED HOST memory: the label sequences back to back
+  const GTNX_G float* em;     // [n][T][C]
+  GTNX_G float* grad;         // [n][T][C], every row written
+  GTNX_G float* loss;         // [n]
+  GTNX_G float* tgrad;        // the targets' arc gradients, utterance b's at its entry's offset; null: not wanted
+  GTNX_G char* rec;           // band records: per utterance nodes | flags (+ o_flags) | snode (+ o_snode) | slab (+ o_slab)
+  GTNX_G float* alpha;        // [n] planes of [T + 1][NS_b] floats
+  GTNX_G double* aoff;        // [n] x (4 T + 16) doubles: score and row shifts (BandPair::aoff)
+  GTNX_G float* rowlse;       // [n][T]
+  GTNX_G float* score;        // [n]
+  GTNX_G float* norm;         // [n]
+  int64_t em_stride, rec_stride, alpha_stride, aoff_stride;  // in elements of the array (rec: bytes)
+  int o_flags, o_snode, o_slab;
+  int T, C, blank, lgrn;
+};
+int band_block_rows(int C, int max_NS, bool backward);
+bool ctc_step_cell(int C, int max_NS);  // is there an instantiated cell for rows of C labels and targets of max_NS (row stride) nodes?
+void launch_ctc_step(const CtcStepDesc& d, int n, int max_NS, bool gradg, hipStream_t st);
 // one force-alignment acceptor o transitions per label sequence (examples/asg.cpp:50-68), as band records
 struct AsgFalArgs {
   const GTNX_G int* labels;      // [U]

@@ -396,6 +396,22 @@ inline void asgTokenAlign(const Batch& ems, const float* tableDevice, const int*
                                            outStride, frameTokensDevice, frameStride));
 }
 inline void backward(const Batch& a, bool retainGraph = false) { detail::check(gtnx_batch_backward(a.handle(), retainGraph)); }
+/** One CTC criterion step in ONE launch, no batch record and no tape: losses, emission gradients and (targetGrad) the
+ *  targets' arc gradients of n utterances over a device tensor [n][T][C] -- bit for bit what ctcTargets, linear,
+ *  intersect, the two forwardScore, subtract and backward compute.  ctcLossStepOk (a pure host function) says whether the
+ *  batch is one the launch takes; gtn::criteria::ctcLossBatch asks it and falls back to those operations.
+ *  gtnx_batch_ctc_loss_step has the contract. */
+inline bool ctcLossStepOk(const int* labels, const int* lengths, int n, int T, int C, int blank, const void* emissionsDevice,
+                          const void* gradDevice) {
+  int ok = 0;
+  detail::check(gtnx_batch_ctc_loss_step_ok(labels, lengths, n, T, C, blank, emissionsDevice, gradDevice, &ok));
+  return ok != 0;
+}
+inline void ctcLossStep(const void* emissionsDevice, const int* labels, const int* lengths, int n, int T, int C, int blank,
+                        void* lossDevice, void* gradDevice, bool targetGrad = true, void* targetGradDevice = nullptr) {
+  detail::check(gtnx_batch_ctc_loss_step(emissionsDevice, labels, lengths, n, T, C, blank, lossDevice, gradDevice,
+                                         targetGrad ? 1 : 0, targetGradDevice));
+}
 } // namespace batched
 
 } // namespace gtn

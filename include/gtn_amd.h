@@ -261,6 +261,21 @@ gtnx_status_t gtnx_batch_from_graphs(const gtnx_graph_t* g, int n, gtnx_batch_t*
  * sequences (labels back to back, lengths[i] each), built on the device */
 gtnx_status_t gtnx_batch_ctc_targets(const int* labels, const int* lengths, int n, int blank, int calc_grad,
                                      gtnx_batch_t* out);
+/* One CTC criterion step (benchmarks/ctc.cpp:150-165 for a batch) in ONE launch: loss[b] = forwardScore(emissions_b) -
+ * forwardScore(target_b o emissions_b), grad = d loss / d emissions, and -- target_grad != 0 -- the arc gradients of the
+ * target acceptors (arc ids in benchmarks/ctc.cpp:40-58's addArc order; utterance b's at target_grad_dev + the number of
+ * arcs of utterances 0 .. b-1; target_grad_dev may be NULL: computed and dropped).  Bit for bit what gtnx_batch_ctc_targets,
+ * gtnx_batch_linear, gtnx_batch_intersect, the two gtnx_batch_forward_score, gtnx_batch_subtract_into and
+ * gtnx_batch_backward compute.  emissions, loss, grad, target_grad_dev: DEVICE float [n][T][C], [n], [n][T][C], [arcs];
+ * labels, lengths: host.  No batch record, no tape.  GTNX_INVALID_ARGUMENT before anything is launched for n <= 0, a
+ * negative length, a null emissions / lengths / loss / grad pointer, or a batch for which gtnx_batch_ctc_loss_step_ok
+ * says 0: labels outside 0 .. C-1, a target longer than 127 labels, C not a multiple of 4 or above 512, emissions or
+ * grad not 16-byte aligned (such batches take the graph-level operations; gtn::criteria::ctcLossBatch decides).
+ * gtnx_batch_ctc_loss_step_ok is a pure host function: no device is asked. */
+gtnx_status_t gtnx_batch_ctc_loss_step(const void* emissions, const int* labels, const int* lengths, int n, int T, int C,
+                                       int blank, void* loss, void* grad, int target_grad, void* target_grad_dev);
+gtnx_status_t gtnx_batch_ctc_loss_step_ok(const int* labels, const int* lengths, int n, int T, int C, int blank,
+                                          const void* emissions, const void* grad, int* ok);
 /* compose(forceAlign(target), transitions) of examples/asg.cpp:50-68 for n label sequences, built
  * on the device: `transitions` must have the arc layout of examples/asg.cpp:36-47 over n_labels labels
  * (arc i: start -> label i; arc n_labels + i * n_labels + j: label j -> label i); its weights are
