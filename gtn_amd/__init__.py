@@ -80,6 +80,7 @@ debug_ctc_token_align_stats = _api.debug_ctc_token_align_stats  # (Batch.ctc_tok
 debug_asg_token_align_stats = _api.debug_asg_token_align_stats  # (Batch.asg_token_align: calls that launched, pairs aligned)
 debug_asg_score_stats = _api.debug_asg_score_stats  # (Batch.asg_score / asg_score_grad: calls that launched, pairs taken)
 debug_asg_beam_stats = _api.debug_asg_beam_stats  # (Batch.asg_beam_decode: calls that launched, utterances decoded)
+debug_asg_sample_stats = _api.debug_asg_sample_stats  # (Batch.asg_sample: calls that launched, utterances sampled)
 
 
 def load_txt(text):

@@ -178,6 +178,9 @@ _SIGS = {
     "gtnx_batch_asg_beam_decode_graph": [c_graph, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_float, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "gtnx_batch_asg_beam_stats": [c_i64_p, c_i64_p],
+    "gtnx_batch_asg_sample": [c_graph, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_float, C.c_void_p, C.c_int64,
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "gtnx_batch_asg_sample_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_backward": [c_graph, C.c_int],
     "gtnx_batch_items": [c_graph, C.c_void_p],
     "gtnx_batch_items_device": [c_graph, C.c_void_p],

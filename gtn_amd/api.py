@@ -998,6 +998,50 @@ def make_api(lib):
                                                  int(nbest), _opt_ptr(tokens_out), int(stride), _opt_ptr(lengths_out),
                                                  _opt_ptr(scores_out)))
 
+        def asg_sample(self, tokens_out, lengths_out, table, logq_out=None, labels_out=None, logz_out=None, frames=None,
+                       num_samples=4, seed=0, temperature=1.0, row_stride=None):
+            """`num_samples` alignments per utterance drawn from the posterior of the ASG model emissions o transitions
+            over a Batch.linear, equal neighbours merged, results left on the device (gtnx_batch_asg_sample; DESIGN
+            section 34 holds the contract).  ASG frames are not independent, so the call filters forward -- alpha planes
+            in a per-frame rescaled form -- and samples backward: frame T_b - 1 from exp(alpha), frame t below it from
+            exp(alpha_t[j] + transitions[y_{t+1}, j] / temperature), by inverse CDF in label order against a
+            Philox4x32-10 uniform keyed by `seed` and counted by (t, b, k): alignment y comes with probability
+            exp(s(y) / temperature - logZ_b).  The same seed gives the same bytes whatever the strides, the other
+            utterances' frame counts or the pad rows hold, and the first N samples of a larger call are those of a call
+            with N.  `table`: float32 CUDA tensor [C + C * C] or a device address, the table `asg_score` and
+            `asg_beam_decode` take (`torch_loss._asg_weights(start, transitions)`); only finite entries, of it and of
+            the emissions, carry mass.
+            `tokens_out` (int32 CUDA tensor [B, num_samples, >= M] with contiguous rows, or a device address of
+            [B][num_samples][row_stride]) gets every alignment with equal neighbours merged, -1 from its length to the
+            row's width M -- the layout `asg_beam_decode` writes, so `asg_score`, `edit_distance` and `asg_token_align`
+            take it as it is; `lengths_out` (int32 [B, num_samples]) the lengths; `logq_out` (float32 [B, num_samples],
+            optional) the log-probability of each drawn alignment, the drawn conditionals' logs added in draw order in
+            float32; `labels_out` (rows like tokens_out, optional) the frame labels, -1 from T_b on; `logz_out` (float32
+            [B], optional) logZ_b, at temperature 1 the full-connect score of the utterance.  No alignment of finite
+            score, or T_b = 0: -1 rows, length 0, logq -inf for every sample of that utterance, logz -inf.
+            `num_samples` 1 .. 1024, `temperature` finite and > 0, `seed` 0 .. 2^64 - 1, 1 .. 1024 labels; `frames`:
+            T_b per element (0 .. M, at most the rows the batch carries; None: those rows).  No copy back and no wait;
+            rows from T_b on are never read.  Any batch but a Batch.linear is an error: there is no other route."""
+            n = len(self)
+            seed = int(seed)
+            if not 0 <= seed < (1 << 64):
+                raise ValueError("asg_sample: seed must be in 0 .. 2^64 - 1")
+            table = self._asg_score_table("asg_sample", table)
+            stride = self._nbest_outputs("asg_sample", tokens_out, num_samples, row_stride,
+                                         ((lengths_out, "torch.int32", "lengths_out must be an int32"),
+                                          (logq_out, "torch.float32", "logq_out must be a float32")))
+            if labels_out is not None and hasattr(labels_out, "data_ptr"):
+                if self._nbest_outputs("asg_sample", labels_out, num_samples, None, ()) != stride:
+                    raise ValueError("asg_sample: labels_out must have the row stride of tokens_out")
+            if logz_out is not None and hasattr(logz_out, "data_ptr"):
+                if str(logz_out.dtype) != "torch.float32" or tuple(logz_out.shape) != (n,) or not logz_out.is_contiguous():
+                    raise ValueError("asg_sample: logz_out must be a float32 contiguous tensor [B]")
+            fr, fr_ptr = _frames_arg("asg_sample", frames, n)
+            check(lib.gtnx_batch_asg_sample(self._h, fr_ptr, _opt_ptr(table), int(num_samples), seed,
+                                            float(temperature), _opt_ptr(tokens_out), int(stride),
+                                            _opt_ptr(lengths_out), _opt_ptr(logq_out), _opt_ptr(labels_out),
+                                            _opt_ptr(logz_out)))
+
         def ctc_beam_decode(self, tokens_out, lengths_out, scores_out, frames=None, blank=0, beam_size=16,
                             cutoff_top_n=16, nbest=1, row_stride=None, lm=None, lm_weight=1.0, insertion_bonus=0.0,
                             am_scores_out=None):
@@ -1448,6 +1492,11 @@ def make_api(lib):
         (include/gtn_amd.h: gtnx_batch_ctc_sample_stats)"""
         return _stats2(lib.gtnx_batch_ctc_sample_stats)
 
+    def debug_asg_sample_stats():
+        """(calls, utterances): calls of Batch.asg_sample that have launched so far and the utterances they sampled
+        (include/gtn_amd.h: gtnx_batch_asg_sample_stats)"""
+        return _stats2(lib.gtnx_batch_asg_sample_stats)
+
     def debug_ctc_score_stats():
         """(calls, pairs): calls of Batch.ctc_score / Batch.ctc_score_grad that have launched so far and the pairs they
         took (include/gtn_amd.h: gtnx_batch_ctc_score_stats)"""
@@ -1566,6 +1615,7 @@ def make_api(lib):
     ns.debug_asg_score_stats = debug_asg_score_stats
     ns.debug_asg_token_align_stats = debug_asg_token_align_stats
     ns.debug_asg_beam_stats = debug_asg_beam_stats
+    ns.debug_asg_sample_stats = debug_asg_sample_stats
     ns.edit_distance = edit_distance
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties

@@ -215,6 +215,36 @@ inline void asgScoreBatch(
   }
 }
 
+/** `numSamples` alignments per utterance drawn from the posterior of emissions o transitions, results on the device:
+ *  forward filtering, backward sampling, then equal neighbours merged (gtnx_batch_asg_sample has the contract;
+ *  Philox4x32-10 keyed by `seed`, so a seed repeats a run).  `emissions`: device float32 [B][T][N], read in place;
+ *  `tableDev` device float32 [N + N * N] in the arc order of asgTransitions; `frames`: host [B] or null -- how many of
+ *  the T rows of each utterance count (0 .. T); rows past them are never read.  `tokensDev`: device int32
+ *  [B][numSamples][T], -1 from a sample's length on; `lengthsDev`: device int32 [B][numSamples]; `logqDev`: device float
+ *  [B][numSamples] or null, the log-probability of the drawn alignment; `labelsDev`: device int32 [B][numSamples][T] or
+ *  null, the frame labels; `logzDev`: device float [B] or null, the log partition function.  1 .. 1024 labels.  Nothing
+ *  is copied back; the rows feed asgScoreBatch as they are. */
+inline void asgSampleBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int N,
+    const void* tableDev,
+    const int* frames,
+    int numSamples,
+    uint64_t seed,
+    float temperature,
+    void* tokensDev,
+    void* lengthsDev,
+    void* logqDev,
+    void* labelsDev,
+    void* logzDev) {
+  Batch ems = Batch::linear(B, T, N, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  batched::asgSample(ems, static_cast<const float*>(tableDev), static_cast<int*>(tokensDev), T,
+                     static_cast<int*>(lengthsDev), static_cast<float*>(logqDev), static_cast<int*>(labelsDev),
+                     static_cast<float*>(logzDev), numSamples, seed, temperature, frames);
+}
+
 /** ASG prefix beam search of a batch, N-best results on the device: per utterance the `nbest` best label sequences
  *  without equal neighbours, each summed over all of its alignments under emissions o transitions (`tokensDev`, device
  *  int32 [B][nbest][T], -1 from each length on; `lengthsDev`, device int32 [B][nbest]; `scoresDev`, device float32

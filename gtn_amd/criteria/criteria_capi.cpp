@@ -280,6 +280,19 @@ GTN_EXPORT int gtn_asg_score_n(const void* emissions, int B, int T, int C, const
   });
 }
 
+// num_samples alignments per utterance drawn from the posterior of emissions o transitions, equal neighbours merged.
+// emissions: DEVICE float [B][T][C]; table: DEVICE float [C + C * C]; frames: host int32 [B] or null; tokens: DEVICE
+// int32 [B][num_samples][T]; lengths: DEVICE int32 [B][num_samples]; logq: DEVICE float [B][num_samples] or null; labels:
+// DEVICE int32 [B][num_samples][T] or null; logz: DEVICE float [B] or null.
+GTN_EXPORT int gtn_asg_sample_n(const void* emissions, int B, int T, int C, const void* table, const int* frames,
+                                int num_samples, unsigned long long seed, float temperature, void* tokens,
+                                void* lengths, void* logq, void* labels, void* logz) {
+  return guarded([&] {
+    gtn::criteria::asgSampleBatch(emissions, B, T, C, table, frames, num_samples, seed, temperature, tokens, lengths,
+                                  logq, labels, logz);
+  });
+}
+
 // ASG prefix beam search with N-best output.  emissions: DEVICE float32 [B][T][C]; table: DEVICE float32 [C + C*C] as for
 // gtn_asg_score_n; frames: HOST int [B] or null; tokens: DEVICE int32 [B][nbest][T]; lengths: DEVICE int32 [B][nbest];
 // scores: DEVICE float32 [B][nbest].  The rows are what gtn_asg_score_n and gtn_edit_distance_n read.

@@ -274,6 +274,30 @@ void batch_asg_beam_decode(const BatchP& ems, const int* frames, const float* ta
                            const AsgBeamLm* lm, int* tokens_dev, int64_t row_stride, int* lengths_dev,
                            float* scores_dev);
 void batch_asg_beam_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they decoded
+// N alignments of every chain of a native LINEAR batch drawn from the posterior of emissions o transitions, plus the
+// merge of equal neighbours, results on the device (DESIGN section 34 holds the contract: forward filtering in a
+// per-frame rescaled form, then backward sampling -- frame T_b - 1 from exp(alpha), frame t below it from exp(alpha_t[j]
+// + table[C + y_{t+1} * C + j] / temperature), by inverse CDF in label order against the uniform of Philox4x32-10 at
+// key `seed`, counter (t, b, k >> 2, 1), word k & 3).  table_dev: [C + C * C], the table of batch_asg_score.
+// tokens_dev[(b * N + k) * row_stride + i]: the alignment with equal neighbours merged, -1 from its length to the
+// row's width M; lengths_dev[b * N + k]; logq_dev[b * N + k] (or null): the sum of the drawn conditionals' logs in
+// draw order in float32 (= s(y) / temperature - logZ_b); labels_dev (or null): the frame labels in the layout of
+// tokens_dev, -1 from T_b to M; logz_dev[b] (or null): logZ_b.  An utterance without an alignment of finite score, or
+// T_b = 0: no path -- every sample of it gets -1 rows, length 0, logq -inf, and logz -inf.  frames (host, [n], or
+// null): T_b, null = rows_of(b).  Invalid argument before a device is asked for: a null batch, table, tokens or
+// lengths pointer, a negative stride, N outside 1 .. 1024, a temperature that is not finite and > 0, C outside 1 ..
+// 1024 (the filter is O(T C^2) per utterance and the draw keeps a row in the registers of one wave).  With the device:
+// a batch that is not a native LINEAR one (there is no other route), a count outside 0 .. M or above rows_of(b),
+// row_stride < M, n * N beyond an int, a table or outputs that are not memory of the current device.  Per slice three
+// launches of asg_sample.hip on the engine's stream (filter, draw, collapse), before them one prep launch per call
+// above 128 labels; 4 M C bytes of planes per utterance plus 4 (with labels_dev) or 8 bytes per (b, k, t) of scratch
+// from the stream-ordered pool, at most 256 MiB per slice: beyond that the utterances run in slices with the same
+// bytes (the environment variable GTNX_ASG_SAMPLE_SCRATCH_BYTES, read per call, lowers the cap: a debug switch for
+// tests).  Rows from T_b on are never read, no download, no wait.
+void batch_asg_sample(const BatchP& ems, const int* frames, const float* table_dev, int N, uint64_t seed,
+                      float temperature, int* tokens_dev, int64_t row_stride, int* lengths_dev, float* logq_dev,
+                      int* labels_dev, float* logz_dev);
+void batch_asg_sample_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they sampled
 // Levenshtein distance (unit costs) of all B * N pairs (hyp[b, k], ref[b]) of device-resident token rows, results on the
 // device (DESIGN section 21 holds the contract).  hyp_dev: int32 [B][N] rows of width L, hyp_stride elements apart;
 // hyp_len_dev: int32 [B][N]; ref_dev: int32 [B] rows of width U, ref_stride apart; ref_len_dev: int32 [B] -- lengths

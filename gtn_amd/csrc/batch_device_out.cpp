@@ -1,8 +1,8 @@
 // batch_device_out.cpp -- the batch entry points that leave their results in the caller's device memory (declared and
 // specified in batch.h): forced alignment, decode against one shared graph, best path of the chains plus the CTC
 // collapse, CTC prefix beam search, ASG prefix beam search, edit distance, CTC score and its gradient, CTC token
-// alignment, ASG score and its gradients, ASG token alignment.  The kernels differ; the host side around them is the
-// helpers below.
+// alignment, ASG score and its gradients, ASG token alignment, CTC and ASG posterior sampling.  The kernels differ;
+// the host side around them is the helpers below.
 //
 // Recipe for the next entry point, in this order:
 //   1. GTNX_HOST_T("batch.<name>"), then every check the arguments alone decide, each message "[gtnx_batch_<name>] ...":
@@ -823,6 +823,116 @@ void batch_asg_beam_decode(const BatchP& ems, const int* frames, const float* ta
   }
   // (the scratch goes back to the stream-ordered pool behind the launches)
   g_asg_beam.add(1, n);
+}
+
+// ---- N sampled alignments per chain of emissions o transitions plus the merge, device-resident (asg_sample.hip) ----
+namespace {
+constexpr const char* kAsgSample = "gtnx_batch_asg_sample";
+Counters g_asg_sample;  // (calls, utterances)
+// the alpha planes of every utterance of one slice, and label and term of every (b, k, t)
+constexpr ScratchCap kAsgSampleScratch{"GTNX_ASG_SAMPLE_SCRATCH_BYTES", int64_t(256) << 20};
+}  // namespace
+
+void batch_asg_sample_stats(int64_t* calls, int64_t* utterances) { g_asg_sample.get(calls, utterances); }
+
+void batch_asg_sample(const BatchP& ems, const int* frames, const float* table_dev, int N, uint64_t seed,
+                      float temperature, int* tokens_dev, int64_t row_stride, int* lengths_dev, float* logq_dev,
+                      int* labels_dev, float* logz_dev) {
+  GTNX_HOST_T("batch.asg_sample");
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) refuse(kAsgSample, "null batch");
+  if (!table_dev) refuse(kAsgSample, "null table pointer");
+  if (!tokens_dev || !lengths_dev) refuse(kAsgSample, "null output pointer (tokens and lengths are both written)");
+  if (row_stride < 0) refuse(kAsgSample, "negative row stride");
+  if (N < 1 || N > kAsgSampleMaxN) refuse(kAsgSample, "num_samples outside 1 .. 1024");
+  if (!std::isfinite(temperature) || !(temperature > 0.0f)) refuse(kAsgSample, "temperature must be finite and above 0");
+  static_assert(kAsgSampleMaxC == 1024, "the text below says 1024");
+  if (ems->kind == Batch::LINEAR && (ems->C < 1 || ems->C > kAsgSampleMaxC))
+    refuse(kAsgSample, "the number of labels is outside 1 .. 1024 (the filter is O(T C^2) per utterance and the draw "
+                       "keeps a row in the registers of one wave)");
+  Runtime& rt = Runtime::get();
+  const int n = ems->n;
+  // there is no other route: the sampler reads the slabs of a native linear batch
+  if (!native_linear(*ems)) refuse(kAsgSample, "not a native linear batch (gtnx_batch_linear / _rows)");
+  Batch& x = *ems;
+  check_frames(kAsgSample, frames, n, x.M, x);
+  if (n > 0 && row_stride < x.M) refuse(kAsgSample, "row_stride is shorter than the rows of the batch");
+  if (int64_t(n) * N > std::numeric_limits<int>::max()) refuse(kAsgSample, "n times num_samples does not fit an int");
+  if (n <= 0) return;
+  // (the kernels gather from it: host memory is refused too, with one GPU as well)
+  if (!ptr_device_memory_of(table_dev, rt.device())) refuse(kAsgSample, "the table is not memory of the engine's current device");
+  check_outputs_local(kAsgSample, {tokens_dev, lengths_dev, logq_dev, labels_dev, logz_dev});
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  const std::vector<int> fr = resolve_frames(frames, x);
+  DevMemP d_frames = upload_vec(fr);
+  AsgSampleArgs a{};
+  a.table = table_dev;
+  a.row_stride = row_stride;
+  a.label_stride = labels_dev ? row_stride : x.M;
+  a.M = x.M;
+  a.C = x.C;
+  a.N = N;
+  a.fill_labels = labels_dev ? 1 : 0;
+  a.seed_lo = static_cast<unsigned>(seed & 0xffffffffu);
+  a.seed_hi = static_cast<unsigned>(seed >> 32);
+  a.temperature = temperature;
+  // above the register variant's labels: exp(table / temperature - rowmax), transposed and padded, once per call
+  const int stride = asg_sample_et_stride(x.C);
+  DevMemP et, rmax;
+  if (stride > 0) {
+    const size_t rows4 = (size_t(x.C) + 3) & ~size_t(3);
+    et = rt.alloc(sizeof(float) * rows4 * size_t(stride));
+    rmax = rt.alloc(sizeof(float) * size_t(stride));
+    a.et = et->as<float>();
+    a.rmax = rmax->as<float>();
+    GTNX_PROF("asg_sample_prep", 4.0 * x.C * x.C + 4.0 * double(rows4) * stride + 4.0 * stride);
+    launch_asg_sample(a, 0, rt.stream());
+  }
+  // the utterances in slices whose scratch stays within the cap: the planes, the term of every (b, k, t), and its label
+  // where the caller takes none
+  const int64_t per_utt = 4 * int64_t(x.M) * x.C + int64_t(N) * x.M * (labels_dev ? 4 : 8);
+  for_pair_slices(n, per_utt, kAsgSampleScratch, [&](int64_t b0, int64_t count) {
+    // algorithmic bytes.  filter: every emission of the rows that count once, the planes out, the table once per
+    // utterance (registers) or once per frame and workgroup of four utterances (L2).  draw: per (b, k, t) a plane row and a table row in,
+    // label and term out.  collapse: those back in, the pad of the label rows, the token rows, length and logq.
+    double fil_bytes = 0, draw_bytes = 0, col_bytes = 0;
+    for (int64_t b = b0; b < b0 + count; ++b) {
+      const int t = fr[size_t(b)];
+      fil_bytes += 8.0 * x.C * t + (stride > 0 ? 1.0 * x.C * x.C * t : 4.0 * x.C * x.C) + 4.0;
+      draw_bytes += N * t * (8.0 * x.C + 8.0);
+      col_bytes += N * (8.0 * t + (labels_dev ? 4.0 * (x.M - t) : 0.0) + 4.0 * x.M + 8.0);
+    }
+    const size_t cells = std::max<size_t>(size_t(count) * size_t(N) * size_t(x.M), 1);
+    DevMemP planes = rt.alloc(std::max<size_t>(sizeof(float) * size_t(count) * size_t(x.M) * size_t(x.C), 4));
+    DevMemP terms = rt.alloc(sizeof(float) * cells);
+    DevMemP labs = labels_dev ? DevMemP() : rt.alloc(sizeof(int) * cells);
+    AsgSampleArgs s = a;
+    s.em = x.w_dev + b0 * x.M * x.C;
+    s.frames = d_frames->as<int>() + b0;
+    s.planes = planes->as<float>();
+    s.labels = labels_dev ? labels_dev + b0 * N * row_stride : labs->as<int>();
+    s.terms = terms->as<float>();
+    s.tokens = tokens_dev + b0 * N * row_stride;
+    s.lengths = lengths_dev + b0 * N;
+    s.logq = logq_dev ? logq_dev + b0 * N : nullptr;
+    s.logz = logz_dev ? logz_dev + b0 : nullptr;
+    s.n = static_cast<int>(count);
+    s.b0 = static_cast<int>(b0);
+    {
+      GTNX_PROF("asg_sample_filter", fil_bytes);
+      launch_asg_sample(s, 1, rt.stream());
+    }
+    {
+      GTNX_PROF("asg_sample_draw", draw_bytes);
+      launch_asg_sample(s, 2, rt.stream());
+    }
+    {
+      GTNX_PROF("asg_sample_collapse", col_bytes);
+      launch_asg_sample(s, 3, rt.stream());
+    }
+    // (the scratch goes back to the stream-ordered pool behind the launches)
+  });
+  g_asg_sample.add(1, n);
 }
 
 // ---- batched edit distance of device-resident token rows (edit_distance.hip) ----

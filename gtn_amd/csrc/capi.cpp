@@ -926,6 +926,20 @@ GTNX_API gtnx_status_t gtnx_batch_ctc_sample(gtnx_batch_t ems, const int* frames
 GTNX_API gtnx_status_t gtnx_batch_ctc_sample_stats(int64_t* calls, int64_t* utterances) {
   return guard([&] { batch_ctc_sample_stats(calls, utterances); });
 }
+GTNX_API gtnx_status_t gtnx_batch_asg_sample(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                             int num_samples, uint64_t seed, float temperature, void* tokens_device,
+                                             int64_t row_stride, void* lengths_device, void* logq_device,
+                                             void* labels_device, void* logz_device) {
+  return guard([&] {
+    batch_asg_sample(BH(ems), frames, static_cast<const float*>(table_device), num_samples, seed, temperature,
+                     static_cast<int*>(tokens_device), row_stride, static_cast<int*>(lengths_device),
+                     static_cast<float*>(logq_device), static_cast<int*>(labels_device),
+                     static_cast<float*>(logz_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_asg_sample_stats(int64_t* calls, int64_t* utterances) {
+  return guard([&] { batch_asg_sample_stats(calls, utterances); });
+}
 GTNX_API gtnx_status_t gtnx_batch_ctc_beam_decode(gtnx_batch_t ems, const int* frames, int blank, int beam_size,
                                                   int cutoff_top_n, int nbest, void* tokens_device, int64_t row_stride,
                                                   void* lengths_device, void* scores_device) {

@@ -882,6 +882,44 @@ struct CtcSampleArgs {
   float temperature;
 };
 void launch_ctc_sample(const CtcSampleArgs& a, int which, hipStream_t st);
+// asg_sample.hip: N alignments of every chain of an [n][M][C] tensor drawn from the posterior of emissions o
+// transitions at its own length frames[b] (device, 0 .. M) by forward filtering, backward sampling, then the merge of
+// equal neighbours, results on the device (the contract: DESIGN section 34).  table [C + C * C]: start scores, then
+// table[C + i * C + j] = the score of moving from label j to label i.  which = 0 (C > kAsgSampleRegisterC only, once per
+// call): rmax [stride] and et [roundup4(C)][stride] = exp(table / temperature - rowmax) transposed, stride =
+// asg_sample_et_stride(C), pads zero.  which = 1: the filter -- planes[(b * M + t) * C + i] = alpha_t[i] minus the
+// running reference, -inf without mass, and logz[b] (or null) = logZ, -inf without a path.  which = 2: the draw, one
+// wave per (b, k), from frames[b] - 1 down, against u = (2 * (word >> 9) + 1) * 2^-24, word = output (k & 3) of
+// Philox4x32-10 with key (seed_lo, seed_hi) and counter (t, b0 + b, k >> 2, 1) -- labels[(b * N + k) * label_stride +
+// t] and terms[(b * N + k) * M + (frames[b] - 1 - t)] = log(mass / total) of the drawn label; an utterance without a
+// path: labels -1.  which = 3: one wave per (b, k) -- logq[b * N + k] (or null) = the terms added in draw order from
+// 0, tokens[(b * N + k) * row_stride + i] the labels with equal neighbours merged, -1 from lengths[b * N + k] to M,
+// the labels -1 from frames[b] to M when fill_labels is set (they are the caller's).  A label of -1 below frames[b], or
+// frames[b] = 0: no path -- -1 rows, length 0, logq -inf.  Nothing from row frames[b] on is read.  N 1 .. 1024, C 1 ..
+// 1024, temperature finite and > 0 (the engine has refused the rest).
+constexpr int kAsgSampleMaxN = 1024;
+constexpr int kAsgSampleMaxC = 1024;
+constexpr int kAsgSampleRegisterC = 128;  // up to here the filter keeps the transitions in registers
+struct AsgSampleArgs {
+  const GTNX_G float* em;
+  const GTNX_G int* frames;    // [n]
+  const GTNX_G float* table;   // [C + C * C]
+  GTNX_G float* planes;        // [n][M][C] of scratch
+  GTNX_G float* et;            // [roundup4(C)][stride] of scratch (C > kAsgSampleRegisterC)
+  GTNX_G float* rmax;          // [stride] of scratch (C > kAsgSampleRegisterC)
+  GTNX_G int* labels;          // [n][N][label_stride]: the caller's rows, or scratch with label_stride = M
+  GTNX_G float* terms;         // [n][N][M] of scratch
+  GTNX_G int* tokens;
+  GTNX_G int* lengths;
+  GTNX_G float* logq;
+  GTNX_G float* logz;
+  int64_t row_stride, label_stride;
+  int n, M, C, N, b0, fill_labels;
+  unsigned seed_lo, seed_hi;
+  float temperature;
+};
+int asg_sample_et_stride(int C);  // 0 up to kAsgSampleRegisterC labels
+void launch_asg_sample(const AsgSampleArgs& a, int which, hipStream_t st);
 // ctc_beam.hip: CTC prefix beam search with N-best output over every chain of an [n][M][C] tensor at its own length
 // frames[b] (device, 0 .. M), results on the device (the contract: DESIGN section 20).  which = 0: the rows -- the
 // token set S_t of every row that counts, (value, label) entries [n][M][topn + 1] and their counts [n][M] in scratch.

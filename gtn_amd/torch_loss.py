@@ -1,6 +1,6 @@
 """PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
-`asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_sample`, `ctc_beam_decode`, `asg_beam_decode`, `edit_distance`,
-`ctc_score`, `ctc_token_align`, `asg_score` and `asg_token_align`.
+`asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_sample`, `ctc_beam_decode`, `asg_beam_decode`, `asg_sample`,
+`edit_distance`, `ctc_score`, `ctc_token_align`, `asg_score` and `asg_token_align`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -42,6 +42,7 @@ _ARGTYPES = {
     "gtn_asg_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
     "gtn_asg_beam_decode_n": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P],
+    "gtn_asg_sample_n": [_P, _I, _I, _I, _P, _P, _I, C.c_uint64, _F, _P, _P, _P, _P, _P],
     "gtn_asg_beam_decode_graph_n": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _F, _F, _P, _P, _P, _P],
     "gtn_asg_token_align_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
 }
@@ -797,6 +798,75 @@ def asg_beam_decode(emissions, transitions, start=None, input_lengths=None, beam
             scores.data_ptr()),
            "asg_beam_decode", tokens, lengths, scores, frames, table, beam_size, cutoff_top_n, nbest, row_stride=T)
     return tokens, lengths, scores
+
+
+def asg_sample(emissions, transitions, start=None, input_lengths=None, num_samples=4, temperature=1.0, seed=None,
+               return_labels=False, return_logz=False):
+    """`num_samples` label sequences per utterance drawn from the posterior of the ASG model emissions o transitions,
+    device-resident.  ASG frames are not independent, so a draw per frame would be wrong: the call runs a log-semiring
+    forward sweep that keeps the alpha planes, then samples backward from them (forward filtering, backward sampling),
+    which is an exact sample -- alignment y comes with probability exp(s(y) / temperature - logZ), s(y) = start[y_0] +
+    x[0, y_0] + sum_t (transitions[y_t, y_{t-1}] + x[t, y_t]) -- then merges equal neighbours.  What sampled minimum
+    Bayes risk, scheduled sampling and calibration need where `asg_beam_decode` gives the top of the distribution.
+    emissions: float32 CUDA tensor [B, T, N] (any scores), read in place and left untouched; rows past an utterance's
+    length are never read; transitions: [N, N] with transitions[i, j] the score of label j followed by label i; start:
+    [N] scores of the first label (zeros when omitted) -- both detached; 1 <= N <= 1024; input_lengths: per-utterance
+    frame counts (0 .. T) or None; num_samples 1 .. 1024; temperature finite and > 0; seed: 0 .. 2^64 - 1 keys the
+    Philox4x32-10 counters (t, b, k), so a seed repeats a run bit for bit -- None takes one 63-bit integer from torch's
+    default CPU generator, so that `torch.manual_seed` repeats a run, without a device sync.
+    Returns (tokens int32 [B, num_samples, T], lengths int32 [B, num_samples], logq float32 [B, num_samples]) on
+    emissions.device -- the layout of `asg_beam_decode`, which `asg_score`, `edit_distance` and `asg_token_align` take
+    as it is: the merged alignment, -1 from its length on, and the log-probability of the drawn ALIGNMENT, s(y) /
+    temperature - logZ, added in float32 in draw order (the sequence's own log-probability is `asg_score` minus logZ).
+    With return_labels a further tensor, int32 [B, num_samples, T], has the frame labels, -1 from the utterance's
+    length on; with return_logz a last one, float32 [B], has logZ -- at temperature 1 the full-connect term of
+    `asg_loss`.  Only finite entries carry mass: a -inf, +inf or NaN emission, transition or start score is never on a
+    drawn path, and an utterance without an alignment of finite score, or without frames, leaves every sample of it at
+    -1, length 0 and logq -inf, and logZ at -inf.  Runs on the caller's stream; no autograd."""
+    if emissions.dim() != 3 or emissions.dtype != torch.float32:
+        raise ValueError("asg_sample: emissions must be a float32 tensor [B, T, N]")
+    B, T, N = emissions.shape
+    num_samples, temperature = int(num_samples), float(temperature)
+    if transitions.dim() != 2 or tuple(transitions.shape) != (N, N):
+        raise ValueError(f"asg_sample: transitions must be [{N}, {N}]")
+    if start is not None and tuple(start.shape) != (N,):
+        raise ValueError(f"asg_sample: start must be [{N}]")
+    if not 1 <= N <= 1024:
+        raise ValueError("asg_sample: the number of labels is outside 1 .. 1024")
+    if not 1 <= num_samples <= 1024:
+        raise ValueError("asg_sample: num_samples outside 1 .. 1024")
+    if not (math.isfinite(temperature) and temperature > 0.0):
+        raise ValueError("asg_sample: temperature must be finite and above 0")
+    frames = None if input_lengths is None else _frame_counts("asg_sample", input_lengths, B, T, 0)
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())  # (a CPU tensor: no device sync)
+    seed = int(seed)
+    if not 0 <= seed < (1 << 64):
+        raise ValueError("asg_sample: seed must be in 0 .. 2^64 - 1")
+    if not emissions.is_cuda:
+        raise RuntimeError("asg_sample: emissions must be a CUDA tensor (the sampler runs on the device)")
+    x = emissions.detach().contiguous()
+    # (written on the caller's stream BEFORE the engine is pointed at it, as in asg_beam_decode)
+    tr = transitions.detach().to(x.device)
+    st = torch.zeros(N, dtype=torch.float32, device=x.device) if start is None else start.detach().to(x.device)
+    table = _asg_weights(st, tr)
+    stream = _engine_stream(x.device)
+    tokens = torch.empty(B, num_samples, T, dtype=torch.int32, device=x.device)
+    lengths = torch.empty(B, num_samples, dtype=torch.int32, device=x.device)
+    logq = torch.empty(B, num_samples, dtype=torch.float32, device=x.device)
+    labels = torch.empty(B, num_samples, T, dtype=torch.int32, device=x.device) if return_labels else None
+    logz = torch.empty(B, dtype=torch.float32, device=x.device) if return_logz else None
+    _route(stream, x, _has_native("asg_sample", "gtn_asg_sample_n"), "gtn_asg_sample_n",
+           (table.data_ptr(), _host_ptr(frames), num_samples, seed, temperature, tokens.data_ptr(), lengths.data_ptr(),
+            logq.data_ptr(), _ptr(labels), _ptr(logz)),
+           "asg_sample", tokens, lengths, table, logq, labels, logz, frames, num_samples, seed, temperature,
+           row_stride=T)
+    out = (tokens, lengths, logq)
+    if return_labels:
+        out += (labels,)
+    if return_logz:
+        out += (logz,)
+    return out
 
 
 def edit_distance(hyp, hyp_lengths, ref, ref_lengths, return_ops=False):

@@ -338,6 +338,22 @@ inline void asgScoreGrad(const Batch& ems, const float* tableDevice, const int* 
   detail::check(gtnx_batch_asg_score_grad(ems.handle(), frames, tableDevice, tokensDevice, rowStride, lengthsDevice, N,
                                           L, maxLength, weightsDevice, gradEmissionsDevice, gradTableDevice));
 }
+/** numSamples alignments of every chain of a Batch::linear drawn from the posterior of emissions o transitions (forward
+ *  filtering, backward sampling; inverse CDF in label order, Philox4x32-10 keyed by `seed`), plus the merge of equal
+ *  neighbours, results left on the device: tableDevice float32 [C + C * C] (start scores, then arc C + i * C + j = j ->
+ *  i); tokensDevice int32 [n][numSamples][rowStride] (the merged alignment, then -1 up to the row's width M),
+ *  lengthsDevice int32 [n][numSamples], logqDevice (may be null) float32 [n][numSamples] the log-probability of the
+ *  drawn alignment, labelsDevice (may be null) int32 [n][numSamples][rowStride] the frame labels, logzDevice (may be
+ *  null) float32 [n] the log partition function.  No alignment of finite score or T_b = 0: -1, 0, -inf, -inf.
+ *  numSamples 1 .. 1024, 1 .. 1024 labels; frames (host, [n]): T_b, null = the rows the batch carries.  No copy back,
+ *  no wait, rows from T_b on are never read -- gtnx_batch_asg_sample */
+inline void asgSample(const Batch& ems, const float* tableDevice, int* tokensDevice, int64_t rowStride,
+                      int* lengthsDevice, float* logqDevice = nullptr, int* labelsDevice = nullptr,
+                      float* logzDevice = nullptr, int numSamples = 4, uint64_t seed = 0, float temperature = 1.0f,
+                      const int* frames = nullptr) {
+  detail::check(gtnx_batch_asg_sample(ems.handle(), frames, tableDevice, numSamples, seed, temperature, tokensDevice,
+                                      rowStride, lengthsDevice, logqDevice, labelsDevice, logzDevice));
+}
 /** ASG prefix beam search with N-best output over a Batch::linear, results left on the device: the hypotheses are the
  *  label sequences without equal neighbours (what viterbiDecode's collapsed rows can hold), each summed over all of its
  *  alignments under emissions o transitions -- unpruned, asgScore of the tokens.  tableDevice float32 [C + C * C]

@@ -801,6 +801,52 @@ gtnx_status_t gtnx_batch_asg_beam_decode_graph(gtnx_batch_t ems, const int* fram
                                                void* am_scores_device /* may be null */);
 /* calls that have launched so far (process-wide) / utterances they decoded */
 gtnx_status_t gtnx_batch_asg_beam_stats(int64_t* calls, int64_t* utterances);
+/* num_samples alignments of every chain of a batch drawn from the posterior of the ASG model emissions o transitions,
+ * plus the merge of equal neighbours, results left on the device (DESIGN section 34 has the whole contract).  ASG frames
+ * are not independent: the sample is exact by forward filtering, backward sampling.
+ *   Model: table_device is float32 [C + C * C] on the device in the arc order of asgTransitions -- table[c] the start
+ *   score of label c, table[C + i * C + j] the score of moving from label j to label i -- the table of
+ *   gtnx_batch_asg_score.  s(y) = table[y0] + x[b,0,y0] + sum_{t>=1} (table[C + y_t * C + y_{t-1}] + x[b,t,y_t]), and
+ *   alignment y of utterance b is drawn with probability exp(s(y) / temperature - logZ_b).
+ *   Mass: only finite entries carry mass.  A -inf, +inf or NaN emission or table entry makes every alignment through it
+ *   impossible, and it is never drawn.  An utterance without an alignment of finite score, or with T_b == 0, has no
+ *   path: every sample of it gets -1 rows, length 0, logq = -inf, and its logz is -inf.  No output is ever NaN.
+ *   Filter: alpha_0[i] = (table[i] + x[0,i]) / temperature, alpha_t[i] = x[t,i] / temperature + logsumexp_j(table[C +
+ *   i * C + j] / temperature + alpha_{t-1}[j]), kept per frame as a float32 plane relative to a float64 running
+ *   reference; logZ_b = logsumexp_i alpha_{T_b-1}[i].
+ *   Draw: backward, one uniform per (b, k, t).  Frame T_b - 1 has masses exp(alpha[j] - ref), frame t below it, given
+ *   i = y_{t+1}, masses exp(alpha_t[j] + table[C + i * C + j] / temperature - ref).  Inverse CDF in label order: the
+ *   smallest j whose cumulative mass over 0 .. j exceeds u * total (the total as the sampler summed it); if rounding
+ *   leaves none, the last label with mass.  A label without mass is never returned.
+ *   Randomness is counter-based: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (t, b, k >> 2, 1)
+ *   (gtnx_batch_ctc_sample has 0 in the last word); sample k uses output word k & 3, u = (2 * (word >> 9) + 1) * 2^-24.
+ *   The same seed gives the same bytes whatever the strides, the slicing, the frame counts of the other utterances or
+ *   the contents of pad rows, and the first N samples of a call with more are those of a call with N.
+ * tokens_device: int32 [n][num_samples][row_stride], row_stride >= M: the alignment with equal neighbours merged (ASG
+ * has no blank), -1 from its length to M -- the layout gtnx_batch_asg_beam_decode writes; lengths_device: int32
+ * [n][num_samples]; logq_device (may be null): float32 [n][num_samples], the sum of the drawn conditionals' logs
+ * log(mass / total), added in draw order (frame T_b - 1 first) from 0 in float32 -- in exact arithmetic s(y) /
+ * temperature - logZ_b; labels_device (may be null): int32 [n][num_samples][row_stride], the frame labels, -1 from T_b
+ * to M; logz_device (may be null): float32 [n], logZ_b -- at temperature 1 the full-connect score
+ * forwardScore(emissions_b[:T_b] o transitions).
+ * frames (host, [n], or null): T_b; null means the rows the batch carries.  Rows from T_b on are never read.
+ * GTNX_INVALID_ARGUMENT before a device is asked for: a null batch, table, tokens or lengths pointer, a negative
+ * stride, num_samples outside 1 .. 1024, a temperature that is not finite and > 0, a number of labels outside 1 .. 1024
+ * (the filter is O(T C^2) per utterance and the draw keeps a row in the registers of one wave).  With the device: ems
+ * is not a gtnx_batch_linear / _rows batch (there is no other route), a count outside 0 .. M or above the rows the batch
+ * carries, row_stride < M, n * num_samples beyond an int, a table or outputs that are not memory of the engine's current
+ * device.  A refused call writes nothing.
+ * Launches on the engine's stream (asg_sample.hip): filter, draw and collapse per slice, one prep launch before them
+ * above 128 labels.  The planes (4 M C bytes per utterance) and the label and term of every (b, k, t) live in scratch
+ * from the stream-ordered pool, at most 256 MiB per slice: beyond that the utterances run in slices with the same bytes
+ * (GTNX_ASG_SAMPLE_SCRATCH_BYTES, read per call, lowers the cap: a debug switch for tests).  Nothing is copied back and
+ * the call does not wait for the device. */
+gtnx_status_t gtnx_batch_asg_sample(gtnx_batch_t ems, const int* frames, const void* table_device, int num_samples,
+                                    uint64_t seed, float temperature, void* tokens_device, int64_t row_stride,
+                                    void* lengths_device, void* logq_device /* may be null */,
+                                    void* labels_device /* may be null */, void* logz_device /* may be null */);
+/* calls that have launched so far (process-wide) / utterances they sampled */
+gtnx_status_t gtnx_batch_asg_sample_stats(int64_t* calls, int64_t* utterances);
 /* rows M and labels C of the slabs of a gtnx_batch_linear / _rows batch; -1, -1 for any other batch */
 gtnx_status_t gtnx_batch_linear_shape(gtnx_batch_t ems, int* rows, int* labels);
 gtnx_status_t gtnx_batch_backward(gtnx_batch_t a, int retain_graph);                  /* autograd.cpp:17-67 */
