@@ -76,11 +76,14 @@ debug_ctc_sample_stats = _api.debug_ctc_sample_stats  # (Batch.ctc_sample: calls
 edit_distance = _api.edit_distance  # (batched Levenshtein distance of device-resident token rows)
 debug_edit_distance_stats = _api.debug_edit_distance_stats  # (edit_distance: calls that launched, pairs computed)
 debug_ctc_score_stats = _api.debug_ctc_score_stats  # (Batch.ctc_score / ctc_score_grad: calls that launched, pairs taken)
+debug_ctc_lattice_score_stats = _api.debug_ctc_lattice_score_stats  # (Batch.ctc_lattice_score / _grad: calls, utterances)
 debug_ctc_token_align_stats = _api.debug_ctc_token_align_stats  # (Batch.ctc_token_align: calls that launched, pairs aligned)
 debug_asg_token_align_stats = _api.debug_asg_token_align_stats  # (Batch.asg_token_align: calls that launched, pairs aligned)
 debug_asg_score_stats = _api.debug_asg_score_stats  # (Batch.asg_score / asg_score_grad: calls that launched, pairs taken)
 debug_asg_beam_stats = _api.debug_asg_beam_stats  # (Batch.asg_beam_decode: calls that launched, utterances decoded)
 debug_asg_sample_stats = _api.debug_asg_sample_stats  # (Batch.asg_sample: calls that launched, utterances sampled)
+
+from .lattice import decomposition_lattice, lattice_from_graph, pack_lattices  # noqa: E402  (host builders of token lattices)
 
 
 def load_txt(text):

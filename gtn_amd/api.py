@@ -1182,6 +1182,94 @@ def make_api(lib):
                                                 _opt_ptr(tok), stride, _opt_ptr(ln), N, L, U, _opt_ptr(weights),
                                                 _opt_ptr(grad_out)))
 
+        def _ctc_lattice_args(self, who, arcs, num_arcs, num_nodes, arc_weights, frames, A, row_stride, max_states):
+            """(frames array or None, A, row stride, max_states) of a ctc_lattice_score call"""
+            n = len(self)
+            if arcs is not None and hasattr(arcs, "data_ptr"):
+                t = arcs
+                if str(t.dtype) != "torch.int32" or t.dim() != 3 or t.shape[0] != n or t.shape[2] != 3:
+                    raise ValueError(f"{who}: arcs must be an int32 tensor [B, A, 3]")
+                if t.stride(2) != 1 or (t.shape[1] > 1 and t.stride(1) != 3):
+                    raise ValueError(f"{who}: arcs must have contiguous rows of (src, dst, label)")
+                rows = t.stride(0) if t.shape[0] > 1 else max(3 * t.shape[1], 1)
+                for name, given, have in (("A", A, t.shape[1]), ("row_stride", row_stride, rows)):
+                    if given is not None and int(given) != int(have):
+                        raise ValueError(f"{who}: {name} = {given} is not what arcs says ({have})")
+                A, row_stride = t.shape[1], rows
+                if hasattr(t, "is_cuda") and not t.is_cuda:
+                    raise ValueError(f"{who}: arcs must be a CUDA tensor")
+            if A is None or row_stride is None:
+                raise ValueError(f"{who}: a device address needs A and row_stride")
+            A = int(A)
+            for t, name in ((num_arcs, "num_arcs"), (num_nodes, "num_nodes")):
+                if t is not None and hasattr(t, "data_ptr"):
+                    if str(t.dtype) != "torch.int32" or not t.is_contiguous() or t.numel() != n:
+                        raise ValueError(f"{who}: {name} must be an int32 contiguous tensor [B]")
+                    if hasattr(t, "is_cuda") and not t.is_cuda:
+                        raise ValueError(f"{who}: {name} must be a CUDA tensor")
+            if arc_weights is not None and hasattr(arc_weights, "data_ptr"):
+                t = arc_weights
+                if str(t.dtype) != "torch.float32" or not t.is_contiguous() or t.numel() != n * A:
+                    raise ValueError(f"{who}: arc_weights must be a float32 contiguous tensor [B, A]")
+                if hasattr(t, "is_cuda") and not t.is_cuda:
+                    raise ValueError(f"{who}: arc_weights must be a CUDA tensor")
+            fr, _ = _frames_arg(who, frames, n)
+            if max_states is None:
+                max_states = max(1, min(2 * A + 1, 4096))  # (a lattice of A arcs that reach its end has <= A + 1 nodes)
+            return fr, A, int(row_stride), int(max_states)
+
+        def ctc_lattice_score(self, arcs, num_arcs, num_nodes, scores_out, arc_weights=None, frames=None, blank=0,
+                              max_states=None, A=None, row_stride=None):
+            """The exact CTC log score of one device-resident acyclic token lattice per utterance under the slabs of a
+            Batch.linear, results left on the device (gtnx_batch_ctc_lattice_score; DESIGN section 35 holds the
+            contract): scores_out[b] = log sum over the lattice's paths p of exp(w(p) + ctc_score(emissions_b[:T_b],
+            labels(p))), every decomposition and every alignment at once, nothing subtracted.  `arcs`: int32 CUDA tensor
+            [B, A, 3] of (src, dst, label) rows, 0 <= src < dst < num_nodes, sorted by dst within an utterance, or a
+            device address with A and row_stride (elements between utterances, >= 3 A); `num_arcs`, `num_nodes`: int32
+            [B] on the device (node 0 starts, the last node accepts); `arc_weights`: float32 [B, A] or None (zeros);
+            `scores_out`: float32 [B]; `frames`: T_b per element (0 .. M) or None; `max_states` (1 .. 4096, default
+            min(2 A + 1, 4096)): the bound on nodes + arcs that sizes LDS -- larger lattices score -inf, as do invalid
+            ones (an arc that is none, a label outside 0 .. C - 1, a weight that is +inf or NaN), ones no alignment
+            fits, and T_b == 0.  One launch, no copy back and no wait."""
+            fr, A, stride, SM = self._ctc_lattice_args("ctc_lattice_score", arcs, num_arcs, num_nodes, arc_weights,
+                                                       frames, A, row_stride, max_states)
+            if scores_out is not None and hasattr(scores_out, "data_ptr"):
+                if (str(scores_out.dtype) != "torch.float32" or not scores_out.is_contiguous()
+                        or scores_out.numel() != len(self)):
+                    raise ValueError("ctc_lattice_score: scores_out must be a float32 contiguous tensor [B]")
+            check(lib.gtnx_batch_ctc_lattice_score(self._h, fr.ctypes.data if fr is not None else None, int(blank),
+                                                   _opt_ptr(arcs), stride, _opt_ptr(num_arcs), _opt_ptr(num_nodes),
+                                                   _opt_ptr(arc_weights), A, SM, _opt_ptr(scores_out)))
+
+        def ctc_lattice_score_grad(self, arcs, num_arcs, num_nodes, weights, grad_out, arc_grad_out=None,
+                                   arc_weights=None, frames=None, blank=0, max_states=None, A=None, row_stride=None):
+            """grad_out[b, t, c] = weights[b] * d score[b] / d emissions[b, t, c] for the scores of `ctc_lattice_score`
+            (gtnx_batch_ctc_lattice_score_grad): `weights` float32 [B] on the device, `grad_out` float32 [B, M, C], every
+            element written (zeros where nothing lands, rows from T_b on included); `arc_grad_out` float32 [B, A] or None:
+            weights[b] * d score[b] / d arc_weights[b, a], weights[b] times the posterior that the arc is used, zeros at
+            or past num_arcs[b].  Utterances with a -inf score or a weight of exactly 0 get zeros.  Stateless: the alpha
+            rows are recomputed into pooled scratch (sliced beyond 256 MiB, same bits); the sums are taken in a fixed
+            order without atomics, so the results have the same bits run to run."""
+            who = "ctc_lattice_score_grad"
+            fr, A, stride, SM = self._ctc_lattice_args(who, arcs, num_arcs, num_nodes, arc_weights, frames, A,
+                                                       row_stride, max_states)
+            n = len(self)
+            for o, count, what in ((weights, n, "weights must be a float32 contiguous tensor [B]"),
+                                   (arc_grad_out, n * A, "arc_grad_out must be a float32 contiguous tensor [B, A]")):
+                if o is not None and hasattr(o, "data_ptr"):
+                    if str(o.dtype) != "torch.float32" or not o.is_contiguous() or o.numel() != count:
+                        raise ValueError(f"{who}: {what}")
+            if grad_out is not None and hasattr(grad_out, "data_ptr"):
+                m, c = C.c_int(-1), C.c_int(-1)
+                check(lib.gtnx_batch_linear_shape(self._h, C.byref(m), C.byref(c)))
+                if (str(grad_out.dtype) != "torch.float32" or not grad_out.is_contiguous()
+                        or (m.value >= 0 and grad_out.numel() != n * m.value * c.value)):
+                    raise ValueError(f"{who}: grad_out must be a float32 contiguous tensor [B, M, C]")
+            check(lib.gtnx_batch_ctc_lattice_score_grad(self._h, fr.ctypes.data if fr is not None else None, int(blank),
+                                                        _opt_ptr(arcs), stride, _opt_ptr(num_arcs), _opt_ptr(num_nodes),
+                                                        _opt_ptr(arc_weights), A, SM, _opt_ptr(weights),
+                                                        _opt_ptr(grad_out), _opt_ptr(arc_grad_out)))
+
         def _token_align_outputs(self, who, N, L, scores_out, starts_out, ends_out, token_scores_out, frame_tokens_out,
                                  out_stride, frame_stride):
             """What `ctc_token_align` and `asg_token_align` check of their outputs alike.  Returns (out_stride,
@@ -1596,6 +1684,11 @@ def make_api(lib):
                                            int(ref_stride), _opt_ptr(ref_lengths), b, n, l, u, _opt_ptr(dist_out),
                                            _opt_ptr(ops_out)))
 
+    def debug_ctc_lattice_score_stats():
+        """(calls, utterances): calls of Batch.ctc_lattice_score / Batch.ctc_lattice_score_grad that have launched so
+        far and the utterances they took (include/gtn_amd.h: gtnx_batch_ctc_lattice_score_stats)"""
+        return _stats2(lib.gtnx_batch_ctc_lattice_score_stats)
+
     def debug_full_connect_stats():
         """(fast, fallback): utterances whose ASG full-connect score forward_score(compose(Batch.linear(rows=...),
         transitions)) came from the one launch of asg_full.hip / utterances of such a padded batch that took the composed
@@ -1612,6 +1705,7 @@ def make_api(lib):
     ns.debug_edit_distance_stats = debug_edit_distance_stats
     ns.debug_ctc_score_stats = debug_ctc_score_stats
     ns.debug_ctc_token_align_stats = debug_ctc_token_align_stats
+    ns.debug_ctc_lattice_score_stats = debug_ctc_lattice_score_stats
     ns.debug_asg_score_stats = debug_asg_score_stats
     ns.debug_asg_token_align_stats = debug_asg_token_align_stats
     ns.debug_asg_beam_stats = debug_asg_beam_stats

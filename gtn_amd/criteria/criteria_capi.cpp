@@ -158,6 +158,32 @@ GTN_EXPORT int gtn_ctc_score_grad_n(const void* emissions, int B, int T, int C, 
   });
 }
 
+// Exact CTC log scores of one device-resident token lattice per utterance.  emissions: DEVICE float32 [B][T][C]; frames:
+// HOST int [B] or null; arcs: DEVICE int32 [B][A][3]; num_arcs / num_nodes: DEVICE int32 [B]; arc_weights: DEVICE
+// float32 [B][A] or null; scores: DEVICE float32 [B].
+GTN_EXPORT int gtn_ctc_lattice_score_n(const void* emissions, int B, int T, int C, int blank, const int* frames,
+                                       const void* arcs, const void* num_arcs, const void* num_nodes,
+                                       const void* arc_weights, int A, int max_states, void* scores) {
+  return guarded([&] {
+    if (!scores) throw std::invalid_argument("gtn_ctc_lattice_score_n: null scores");
+    gtn::criteria::ctcLatticeScoreBatch(emissions, B, T, C, blank, frames, arcs, num_arcs, num_nodes, arc_weights, A,
+                                        max_states, scores);
+  });
+}
+
+// ... and their gradients for weights: DEVICE float32 [B]: grad (DEVICE float32 [B][T][C], every element written) and
+// arc_grad (DEVICE float32 [B][A] or null).
+GTN_EXPORT int gtn_ctc_lattice_score_grad_n(const void* emissions, int B, int T, int C, int blank, const int* frames,
+                                            const void* arcs, const void* num_arcs, const void* num_nodes,
+                                            const void* arc_weights, int A, int max_states, const void* weights,
+                                            void* grad, void* arc_grad) {
+  return guarded([&] {
+    if (!weights || !grad) throw std::invalid_argument("gtn_ctc_lattice_score_grad_n: null weights or grad");
+    gtn::criteria::ctcLatticeScoreBatch(emissions, B, T, C, blank, frames, arcs, num_arcs, num_nodes, arc_weights, A,
+                                        max_states, nullptr, weights, grad, arc_grad);
+  });
+}
+
 // The best alignment of B * N device-resident hypotheses.  emissions: DEVICE float32 [B][T][C]; frames: HOST int [B] or
 // null; tokens: DEVICE int32 [B][N][L]; lengths: DEVICE int32 [B][N]; scores: DEVICE float32 [B][N]; starts / ends: DEVICE
 // int32 [B][N][L]; token_scores: DEVICE float32 [B][N][L] or null; frame_tokens: DEVICE int32 [B][N][T] or null.

@@ -341,6 +341,54 @@ inline void ctcScoreBatch(
   }
 }
 
+/** The exact CTC log scores of one device-resident token lattice per utterance under the B emission slabs, and (with
+ *  weightsDev and gradDev) the gradients weights[b] * d score[b] / d (emissions_b, arc weights): `emissions` device
+ *  float32 [B][T][C], read in place; `arcsDev` device int32 [B][A][3] (dense rows of (src, dst, label), dst-sorted);
+ *  `numArcsDev` / `numNodesDev` device int32 [B]; `arcWeightsDev` device float32 [B][A] or null; `frames` host [B] or
+ *  null; `scoresDev` device float32 [B] or null; `weightsDev` device float32 [B] and `gradDev` device float32 [B][T][C],
+ *  both or neither; `arcGradDev` device float32 [B][A] or null, with gradDev only.  gtnx_batch_ctc_lattice_score / _grad
+ *  have the contract.  Nothing is copied back. */
+inline void ctcLatticeScoreBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int C,
+    int blank,
+    const int* frames,
+    const void* arcsDev,
+    const void* numArcsDev,
+    const void* numNodesDev,
+    const void* arcWeightsDev,
+    int A,
+    int maxStates,
+    void* scoresDev,
+    const void* weightsDev = nullptr,
+    void* gradDev = nullptr,
+    void* arcGradDev = nullptr) {
+  if ((weightsDev == nullptr) != (gradDev == nullptr)) {
+    throw std::invalid_argument("ctcLatticeScoreBatch: weights and grad come together");
+  }
+  if (arcGradDev && !gradDev) {
+    throw std::invalid_argument("ctcLatticeScoreBatch: the arcs' gradient comes with grad only");
+  }
+  if (!scoresDev && !gradDev) {
+    throw std::invalid_argument("ctcLatticeScoreBatch: neither scores nor grad asked for");
+  }
+  Batch ems = Batch::linear(B, T, C, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  if (scoresDev) {
+    batched::ctcLatticeScore(ems, static_cast<const int*>(arcsDev), 3 * int64_t(A), static_cast<const int*>(numArcsDev),
+                             static_cast<const int*>(numNodesDev), static_cast<const float*>(arcWeightsDev), A,
+                             maxStates, static_cast<float*>(scoresDev), blank, frames);
+  }
+  if (gradDev) {
+    batched::ctcLatticeScoreGrad(ems, static_cast<const int*>(arcsDev), 3 * int64_t(A),
+                                 static_cast<const int*>(numArcsDev), static_cast<const int*>(numNodesDev),
+                                 static_cast<const float*>(arcWeightsDev), A, maxStates,
+                                 static_cast<const float*>(weightsDev), static_cast<float*>(gradDev),
+                                 static_cast<float*>(arcGradDev), blank, frames);
+  }
+}
+
 /** The best alignment of B * N device-resident hypotheses under the B emission slabs -- when each token was spoken and
  *  how well the frames support it: `emissions` device float32 [B][T][C], read in place; `tokensDev` device int32
  *  [B][N][L] and `lengthsDev` device int32 [B][N] (dense rows, what ctcBeamDecodeBatch wrote); `frames` host [B] or null;

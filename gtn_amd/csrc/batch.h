@@ -333,6 +333,31 @@ void batch_ctc_score_grad(const BatchP& ems, const int* frames, int blank, const
                           const int* lengths_dev, int N, int L, int max_length, const float* weights_dev,
                           float* grad_dev);
 void batch_ctc_score_stats(int64_t* calls, int64_t* pairs);  // calls that launched (either kind) / pairs they took
+// The exact CTC log score of one device-resident acyclic token lattice per utterance under the n emission slabs of a
+// native linear batch, results on the device (DESIGN section 35 holds the contract): scores_dev[b] = log sum over the
+// lattice's paths p of exp(w(p) + ctc_score(emissions_b[:T_b], labels(p))), nothing subtracted.  arcs_dev: int32 n rows
+// of A arcs (src, dst, label), row_stride (>= 3 A) elements apart, dst-sorted within a row; num_arcs_dev / num_nodes_dev:
+// int32 [n], DEVICE memory (node 0 starts, node num_nodes - 1 accepts); arc_weights_dev: float32 [n][A] or null (zeros);
+// max_states (1 .. 4096) bounds nodes + arcs and sizes LDS and scratch; frames: HOST, T_b per element or null.
+// -inf (never NaN): T_b == 0, num_nodes < 1, nodes + arcs > max_states, an arc with src < 0, src >= dst or dst >=
+// num_nodes, an arc out of dst order, a label outside 0 .. C - 1, a weight that is +inf or NaN, no alignment.  Invalid
+// argument before a device is asked for: a null pointer, negative A or blank, row_stride < 3 A, max_states outside
+// 1 .. 4096; n == 0 returns without a device.  With the device: not a native linear batch, a frame count outside 0 .. M,
+// blank >= C, an output that is not memory of the current device.  One launch, no scratch, no download, no wait.
+void batch_ctc_lattice_score(const BatchP& ems, const int* frames, int blank, const int* arcs_dev, int64_t row_stride,
+                             const int* num_arcs_dev, const int* num_nodes_dev, const float* arc_weights_dev, int A,
+                             int max_states, float* scores_dev);
+// grad_dev[b][t][c] = weights_dev[b] * d score[b] / d emissions[b][t][c], every element of [n][M][C] written (zeros where
+// nothing lands, pad rows included); arc_grad_dev (or null) [n][A] = weights_dev[b] * d score[b] / d arc weight, the
+// posterior of the arc, zeros at or past num_arcs[b]; an utterance whose score is -inf or whose weight is exactly 0 gets
+// zeros.  The alpha rows are recomputed into scratch from the stream-ordered pool (max T_b * max_states floats per
+// utterance), at most 256 MiB per launch pair (GTNX_CTC_LATTICE_SCRATCH_BYTES lowers the cap: a debug switch); beyond it
+// the utterances run in slices with the same bits.  No floating-point atomics: bit-repeatable.
+void batch_ctc_lattice_score_grad(const BatchP& ems, const int* frames, int blank, const int* arcs_dev,
+                                  int64_t row_stride, const int* num_arcs_dev, const int* num_nodes_dev,
+                                  const float* arc_weights_dev, int A, int max_states, const float* weights_dev,
+                                  float* grad_dev, float* arc_grad_dev);
+void batch_ctc_lattice_score_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
 // The best alignment of all n * N device-resident hypotheses (the pair form of batch_ctc_score) under the n emission
 // slabs of a native linear batch, results on the device (DESIGN section 24 holds the contract): scores_dev [n][N] the
 // Viterbi score, starts_dev / ends_dev (n * N rows of width L, out_stride apart) the first frame of token i and one past

@@ -1,7 +1,8 @@
 // batch_device_out.cpp -- the batch entry points that leave their results in the caller's device memory (declared and
 // specified in batch.h): forced alignment, decode against one shared graph, best path of the chains plus the CTC
 // collapse, CTC prefix beam search, ASG prefix beam search, edit distance, CTC score and its gradient, CTC token
-// alignment, ASG score and its gradients, ASG token alignment, CTC and ASG posterior sampling.  The kernels differ;
+// alignment, CTC lattice score and its gradients, ASG score and its gradients, ASG token alignment, CTC and ASG posterior
+// sampling.  The kernels differ;
 // the host side around them is the helpers below.
 //
 // Recipe for the next entry point, in this order:
@@ -1082,6 +1083,128 @@ void batch_ctc_score_grad(const BatchP& ems, const int* frames, int blank, const
   GTNX_HOST_T("batch.ctc_score_grad");
   ctc_score_impl("gtnx_batch_ctc_score_grad", ems, frames, blank,
                  {tokens_dev, row_stride, lengths_dev, N, L, max_length}, nullptr, weights_dev, grad_dev);
+}
+
+// ---- batched CTC score of one device-resident token lattice per utterance, and its gradients (ctc_lattice.hip) ----
+namespace {
+Counters g_ctc_lattice;  // (calls, utterances)
+// the alpha rows of a gradient call: an utterance that is above the cap by itself runs alone with scratch of its own size
+constexpr ScratchCap kCtcLatticeScratch{"GTNX_CTC_LATTICE_SCRATCH_BYTES", int64_t(256) << 20};
+static_assert(kCtcLatticeMaxStates == 4096, "the text below says 4096");
+
+struct Lattices {
+  const int* arcs;
+  int64_t row_stride;
+  const int *num_arcs, *num_nodes;
+  const float* arc_weights;
+  int A, max_states;
+};
+
+// both entry points: scores_dev for the score; weights_dev, grad_dev and arc_grad_dev (or null) for the gradients
+void ctc_lattice_impl(const char* who, const BatchP& ems, const int* frames, int blank, const Lattices& h,
+                      float* scores_dev, const float* weights_dev, float* grad_dev, float* arc_grad_dev) {
+  const bool want_grad = scores_dev == nullptr;
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) refuse(who, "null batch");
+  if (!h.arcs || !h.num_arcs || !h.num_nodes)
+    refuse(who, "null input pointer (arcs, num_arcs and num_nodes are all read)");
+  if (want_grad && (!weights_dev || !grad_dev)) refuse(who, "null weights or grad pointer");
+  if (blank < 0) refuse(who, "negative blank");
+  if (h.A < 0) refuse(who, "negative A");
+  if (h.row_stride < 3 * int64_t(h.A)) refuse(who, "row_stride is shorter than the rows' width 3 A");
+  if (h.max_states < 1 || h.max_states > kCtcLatticeMaxStates) refuse(who, "max_states outside 1 .. 4096");
+  const int n = ems->n;
+  if (n <= 0) return;
+  Batch& x = linear_hypothesis_batch(who, ems, frames);
+  if (blank >= x.C) refuse(who, "blank is not below the number of labels");
+  check_outputs_local(who, {want_grad ? grad_dev : scores_dev, arc_grad_dev});
+  Runtime& rt = Runtime::get();
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  const std::vector<int> fr = resolve_frames(frames, x);
+  int maxT = 0;
+  double sumT = 0;
+  for (int t : fr) {
+    maxT = std::max(maxT, t);
+    sumT += t;
+  }
+  DevMemP fr_dev = upload_vec(fr);
+  const int64_t SM = h.max_states;
+  CtcLatticeArgs a{};
+  a.em = x.w_dev;
+  a.frames = fr_dev->as<int>();
+  a.arcs = h.arcs;
+  a.num_arcs = h.num_arcs;
+  a.num_nodes = h.num_nodes;
+  a.arc_weights = h.arc_weights;
+  a.weights = weights_dev;
+  a.grad = grad_dev;
+  a.arc_grad = arc_grad_dev;
+  a.row_stride = h.row_stride;
+  a.A = h.A;
+  a.SM = h.max_states;
+  a.M = x.M;
+  a.C = x.C;
+  a.blank = blank;
+  // algorithmic bytes, by the widths (the counts are device memory: an upper bound).  forward: per utterance and frame
+  // one emission per state, the arcs (and their weights) once, the score out.  With the rows kept: every alpha out as
+  // well.  backward: the alphas and the emissions back in, one store of a gradient element per state and frame at most,
+  // the arcs again, the slab zeroed once, the arcs' gradient out.
+  const int64_t states = std::min<int64_t>(SM, int64_t(h.A) + SM);
+  const double lattice = (h.arc_weights ? 16.0 : 12.0) * std::min<int64_t>(h.A, SM) + 12.0;
+  const double fwd_utt = 4.0 * double(states) * (sumT / double(n)) + lattice;
+  if (!want_grad) {
+    a.scores = scores_dev;
+    a.utt0 = 0;
+    a.score0 = 0;
+    a.count = n;
+    GTNX_PROF("ctc_lattice", fwd_utt * double(n));
+    launch_ctc_lattice_forward(a, rt.stream());
+  } else {
+    const int64_t per_utt = std::max<int64_t>(int64_t(maxT), 1) * SM;  // floats
+    a.utt_stride = per_utt;
+    for_pair_slices(n, 4 * per_utt, kCtcLatticeScratch, [&](int64_t u0, int64_t cnt) {
+      DevMemP rows = rt.alloc(size_t(4 * per_utt * cnt));
+      DevMemP sc = rt.alloc(size_t(4 * cnt));
+      a.alpha = rows->as<float>();
+      a.scores = sc->as<float>();
+      a.utt0 = int(u0);
+      a.score0 = int(u0);
+      a.count = int(cnt);
+      {
+        GTNX_PROF("ctc_lattice_alpha", 2.0 * fwd_utt * double(cnt));
+        launch_ctc_lattice_forward(a, rt.stream());
+      }
+      {
+        GTNX_PROF("ctc_lattice_grad", (3.0 * fwd_utt + 4.0 * double(x.M) * x.C + (arc_grad_dev ? 4.0 * h.A : 0.0)) * double(cnt));
+        launch_ctc_lattice_backward(a, rt.stream());
+      }
+      // (the rows go back to the stream-ordered pool behind the launches)
+    });
+  }
+  g_ctc_lattice.add(1, n);
+}
+}  // namespace
+
+void batch_ctc_lattice_score_stats(int64_t* calls, int64_t* utterances) { g_ctc_lattice.get(calls, utterances); }
+
+void batch_ctc_lattice_score(const BatchP& ems, const int* frames, int blank, const int* arcs_dev, int64_t row_stride,
+                             const int* num_arcs_dev, const int* num_nodes_dev, const float* arc_weights_dev, int A,
+                             int max_states, float* scores_dev) {
+  GTNX_HOST_T("batch.ctc_lattice_score");
+  if (!scores_dev) throw_invalid("[gtnx_batch_ctc_lattice_score] null scores pointer");
+  ctc_lattice_impl("gtnx_batch_ctc_lattice_score", ems, frames, blank,
+                   {arcs_dev, row_stride, num_arcs_dev, num_nodes_dev, arc_weights_dev, A, max_states}, scores_dev,
+                   nullptr, nullptr, nullptr);
+}
+
+void batch_ctc_lattice_score_grad(const BatchP& ems, const int* frames, int blank, const int* arcs_dev,
+                                  int64_t row_stride, const int* num_arcs_dev, const int* num_nodes_dev,
+                                  const float* arc_weights_dev, int A, int max_states, const float* weights_dev,
+                                  float* grad_dev, float* arc_grad_dev) {
+  GTNX_HOST_T("batch.ctc_lattice_score_grad");
+  ctc_lattice_impl("gtnx_batch_ctc_lattice_score_grad", ems, frames, blank,
+                   {arcs_dev, row_stride, num_arcs_dev, num_nodes_dev, arc_weights_dev, A, max_states}, nullptr,
+                   weights_dev, grad_dev, arc_grad_dev);
 }
 
 // ---- batched CTC token alignment of device-resident hypotheses (ctc_token_align.hip) ----

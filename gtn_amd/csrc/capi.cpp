@@ -1069,6 +1069,35 @@ GTNX_API gtnx_status_t gtnx_batch_ctc_score_grad(gtnx_batch_t ems, const int* fr
 GTNX_API gtnx_status_t gtnx_batch_ctc_score_stats(int64_t* calls, int64_t* pairs) {
   return guard([&] { batch_ctc_score_stats(calls, pairs); });
 }
+GTNX_API gtnx_status_t gtnx_batch_ctc_lattice_score(gtnx_batch_t ems, const int* frames, int blank,
+                                                    const void* arcs_device, int64_t row_stride,
+                                                    const void* num_arcs_device, const void* num_nodes_device,
+                                                    const void* arc_weights_device, int A, int max_states,
+                                                    void* scores_device) {
+  return guard([&] {
+    batch_ctc_lattice_score(BH(ems), frames, blank, static_cast<const int*>(arcs_device), row_stride,
+                            static_cast<const int*>(num_arcs_device), static_cast<const int*>(num_nodes_device),
+                            static_cast<const float*>(arc_weights_device), A, max_states,
+                            static_cast<float*>(scores_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_ctc_lattice_score_grad(gtnx_batch_t ems, const int* frames, int blank,
+                                                         const void* arcs_device, int64_t row_stride,
+                                                         const void* num_arcs_device, const void* num_nodes_device,
+                                                         const void* arc_weights_device, int A, int max_states,
+                                                         const void* weights_device, void* grad_device,
+                                                         void* arc_grad_device) {
+  return guard([&] {
+    batch_ctc_lattice_score_grad(BH(ems), frames, blank, static_cast<const int*>(arcs_device), row_stride,
+                                 static_cast<const int*>(num_arcs_device), static_cast<const int*>(num_nodes_device),
+                                 static_cast<const float*>(arc_weights_device), A, max_states,
+                                 static_cast<const float*>(weights_device), static_cast<float*>(grad_device),
+                                 static_cast<float*>(arc_grad_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_ctc_lattice_score_stats(int64_t* calls, int64_t* utterances) {
+  return guard([&] { batch_ctc_lattice_score_stats(calls, utterances); });
+}
 GTNX_API gtnx_status_t gtnx_batch_ctc_token_align(gtnx_batch_t ems, const int* frames, int blank,
                                                   const void* tokens_device, int64_t row_stride,
                                                   const void* lengths_device, int N, int L, int max_length,

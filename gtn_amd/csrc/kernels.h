@@ -1035,6 +1035,35 @@ struct CtcScoreArgs {
 void ctc_score_config(int U, int* width, int* per_lane);  // the workgroup's width and the states a lane owns
 void launch_ctc_score_forward(const CtcScoreArgs& a, hipStream_t st);
 void launch_ctc_score_backward(const CtcScoreArgs& a, hipStream_t st);
+// ctc_lattice.hip: the log score forwardScore(ctcAlignmentGraph(lattice_b) o emissions_b[:T_b]) of the utterances utt0 ..
+// utt0 + count - 1, each with one acyclic token lattice of its own in device memory, and the gradients g[b] * d score[b] /
+// d (emissions_b, arc weights of b) (the contract: DESIGN section 35).  Utterance b: K = num_nodes[b] nodes, the arcs
+// arcs[b * row_stride + 3 a ..] = (src, dst, label), a < clamp(num_arcs[b], 0, A), dst-sorted, arc_weights[b * A + a].
+//   forward:  one workgroup per utterance; scores[b - score0] = the score (-inf: T_b == 0, K < 1, K + arcs > SM, an arc
+//             that is none, a weight that is +inf or NaN, no alignment).  With `alpha` non-null the alpha row of every
+//             frame also goes to alpha[(b - utt0) * utt_stride + t * SM + s].
+//   backward: one workgroup per utterance zeroes grad[b] (and arc_grad[b] if asked for), then writes weights[b] times the
+//             occupancies summed per label in a fixed order by plain stores, and the arcs' posteriors.
+// The workgroup's width and the states per lane are chosen from SM = max_states alone (ctc_lattice_config).
+constexpr int kCtcLatticeMaxStates = 4096;
+struct CtcLatticeArgs {
+  const GTNX_G float* em;           // [n][M][C]
+  const GTNX_G int* frames;         // [n]
+  const GTNX_G int* arcs;           // utterance b's row at arcs + b * row_stride
+  const GTNX_G int* num_arcs;       // [n]
+  const GTNX_G int* num_nodes;      // [n]
+  const GTNX_G float* arc_weights;  // [n][A] or null: all zeros
+  GTNX_G float* scores;             // [.. - score0]
+  GTNX_G float* alpha;              // [count][utt_stride] or null (forward)
+  const GTNX_G float* weights;      // [n] (backward)
+  GTNX_G float* grad;               // [n][M][C] (backward)
+  GTNX_G float* arc_grad;           // [n][A] or null (backward)
+  int64_t row_stride, utt_stride;
+  int utt0, score0, count, A, SM, M, C, blank;
+};
+void ctc_lattice_config(int max_states, int* width, int* per_lane);  // the workgroup's width, the states a lane owns
+void launch_ctc_lattice_forward(const CtcLatticeArgs& a, hipStream_t st);
+void launch_ctc_lattice_backward(const CtcLatticeArgs& a, hipStream_t st);
 // asg_score.hip: the log score forwardScore(emissions_b[:T_b] o (forceAlign(y) o transitions)) of the pairs pair0 ..
 // pair0 + count - 1 in ctc_score.hip's hypothesis form (no blank: position i = 0 .. len - 1 carries y[i]), and the
 // gradients sum_p weights[p] * d score[p] / d (emissions_b, table) (the contract: DESIGN section 25).  table: [C + C * C]

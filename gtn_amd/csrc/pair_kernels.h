@@ -1,5 +1,6 @@
 // pair_kernels.h -- what the kernels that run one workgroup per (utterance, hypothesis) pair share (ctc_score.hip,
-// ctc_token_align.hip, asg_score.hip, asg_token_align.hip; ctc_beam.hip takes the log-add): the -inf, the log-add, the
+// ctc_token_align.hip, asg_score.hip, asg_token_align.hip; ctc_beam.hip takes the log-add, ctc_lattice.hip that and
+// the barrier): the -inf, the log-add, the
 // workgroup barrier of a width known at compile time, and the dispatch from ctc_score_config to a <width, states per
 // lane> instantiation.
 // For .hip files only; everything here is inlined, so a file's code object holds nothing it does not call.

@@ -1,6 +1,7 @@
 """PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
 `asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_sample`, `ctc_beam_decode`, `asg_beam_decode`, `asg_sample`,
-`edit_distance`, `ctc_score`, `ctc_token_align`, `asg_score` and `asg_token_align`.
+`edit_distance`, `ctc_score`, `ctc_lattice_score`, `ctc_lattice_loss`, `ctc_token_align`, `asg_score` and
+`asg_token_align`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -38,6 +39,8 @@ _ARGTYPES = {
     "gtn_edit_distance_n": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "gtn_ctc_score_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P],
     "gtn_ctc_score_grad_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P],
+    "gtn_ctc_lattice_score_n": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P],
+    "gtn_ctc_lattice_score_grad_n": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P],
     "gtn_ctc_token_align_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gtn_asg_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
@@ -993,6 +996,130 @@ def ctc_score(log_probs, tokens, lengths, blank=0, input_lengths=None, max_lengt
         "ctc_score", "scores", log_probs, "log_probs", tokens, lengths, blank, input_lengths, max_length)
     out = _CTCScore.apply(log_probs, tok, ln, blank, frames, max_length)
     return out.reshape(B) if flat else out
+
+
+class _CTCLatticeScore(torch.autograd.Function):
+    """forward: one launch that stores nothing but the scores; backward: the one gradient call with grad_out as the
+    weights, asked for the arcs' gradient as well when the arc weights require one.  The node keeps tensors only."""
+
+    @staticmethod
+    def forward(ctx, log_probs, arc_weights, arcs, num_arcs, num_nodes, blank, frames, max_states):
+        B, A = arcs.shape[:2]
+        x = log_probs.detach().contiguous()
+        w = None if arc_weights is None else arc_weights.detach().to(torch.float32).contiguous()
+        stream = _engine_stream(x.device)
+        scores = torch.empty(B, dtype=torch.float32, device=x.device)
+        if B == 0:
+            _engine_done(stream)  # (no utterance: nothing to launch, and an empty tensor has no address to hand over)
+        else:
+            _route(stream, x, _has_native("ctc_lattice_score", "gtn_ctc_lattice_score_n"), "gtn_ctc_lattice_score_n",
+                   (blank, _host_ptr(frames), arcs.data_ptr(), num_arcs.data_ptr(), num_nodes.data_ptr(), _ptr(w), A,
+                    max_states, scores.data_ptr()),
+                   "ctc_lattice_score", arcs.data_ptr(), num_arcs.data_ptr(), num_nodes.data_ptr(), scores.data_ptr(),
+                   _ptr(w), frames, blank, max_states, A=A, row_stride=3 * A)
+        ctx.save_for_backward(x, arcs, num_arcs, num_nodes, *(() if w is None else (w,)))
+        ctx.args = (blank, frames, max_states, None if arc_weights is None else arc_weights.dtype)
+        return scores
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, arcs, num_arcs, num_nodes, *rest = ctx.saved_tensors
+        w = rest[0] if rest else None
+        blank, frames, max_states, w_dtype = ctx.args
+        B, T, C_ = x.shape
+        A = arcs.shape[1]
+        want_w = w is not None and ctx.needs_input_grad[1]
+        none = (None,) * 6
+        if B == 0 or x.numel() == 0:
+            return (torch.zeros_like(x), torch.zeros(B, A, dtype=w_dtype, device=x.device) if want_w else None) + none
+        g = grad_out.detach().to(torch.float32).contiguous()
+        stream = _engine_stream(x.device)
+        grad = torch.empty(B, T, C_, dtype=torch.float32, device=x.device)
+        garc = torch.empty(B, A, dtype=torch.float32, device=x.device) if want_w else None
+        _route(stream, x, _native(), "gtn_ctc_lattice_score_grad_n",
+               (blank, _host_ptr(frames), arcs.data_ptr(), num_arcs.data_ptr(), num_nodes.data_ptr(), _ptr(w), A,
+                max_states, g.data_ptr(), grad.data_ptr(), _ptr(garc)),
+               "ctc_lattice_score_grad", arcs.data_ptr(), num_arcs.data_ptr(), num_nodes.data_ptr(), g.data_ptr(),
+               grad.data_ptr(), _ptr(garc), _ptr(w), frames, blank, max_states, A=A, row_stride=3 * A)
+        return (grad, garc.to(w_dtype) if want_w else None) + none
+
+
+def ctc_lattice_score(log_probs, arcs, num_arcs, num_nodes, arc_weights=None, blank=0, input_lengths=None,
+                      max_states=None):
+    """The exact CTC log score of one acyclic token lattice per utterance, differentiable: score[b] = log sum over the
+    lattice's paths p of exp(w(p) + ctc_score(log_probs[b, :T_b], labels(p))) -- every word-piece decomposition,
+    pronunciation or optional token the lattice holds and every alignment of each, marginalised in one launch; the
+    lattices are read where they lie on the device.  No normaliser is subtracted (`ctc_lattice_loss` does that).
+    log_probs: float32 CUDA tensor [B, T, C] (any scores), read in place; arcs: int32 CUDA tensor [B, A, 3] of (src, dst,
+    label) rows with 0 <= src < dst < num_nodes[b], sorted by dst within an utterance (`gtn_amd.pack_lattices` gives
+    this form); num_arcs, num_nodes: int32 or int64 CUDA tensors [B] -- node 0 starts, node num_nodes - 1 accepts, arcs
+    at or past num_arcs[b] are never read; arc_weights: float32 CUDA tensor [B, A] or None (zeros), added once per use
+    of an arc, -inf forbids it; blank: 0 .. C - 1 (a label equal to blank is a label like any other); input_lengths:
+    per-utterance frame counts (0 .. T) or None -- rows past T_b are never read and their gradient is exactly 0;
+    max_states (1 .. 4096, default min(2 A + 1, 4096)): the caller's bound on nodes + arcs, which sizes the kernel's
+    LDS and the backward's scratch.
+    Returns float32 [B].  A score is -inf, with zero gradients and never NaN, when T_b == 0, num_nodes < 1, nodes +
+    arcs > max_states, an arc has src < 0, src >= dst or dst >= num_nodes, an arc is out of dst order, a label lies
+    outside 0 .. C - 1, a weight is +inf or NaN, or no alignment fits.  Two paths that spell the same labels both count.
+    The backward is one call that returns grad_out[b] * d score[b] / d log_probs and, when arc_weights requires a
+    gradient, grad_out[b] * the posterior probability of every arc; it recomputes what it needs and sums in a fixed
+    order without atomics, so it has the same bits run to run.  Runs on the caller's stream."""
+    who = "ctc_lattice_score"
+    x = log_probs
+    if not (torch.is_tensor(x) and x.dim() == 3 and x.dtype == torch.float32):
+        raise ValueError(f"{who}: log_probs must be a float32 tensor [B, T, C]")
+    B, T, C_ = x.shape
+    if not (torch.is_tensor(arcs) and arcs.dtype == torch.int32 and arcs.dim() == 3 and arcs.shape[0] == B
+            and arcs.shape[2] == 3):
+        raise ValueError(f"{who}: arcs must be an int32 tensor [B, A, 3] for a batch of {B}")
+    A = arcs.shape[1]
+    for t, name in ((num_arcs, "num_arcs"), (num_nodes, "num_nodes")):
+        if not (torch.is_tensor(t) and t.dtype in (torch.int32, torch.int64) and tuple(t.shape) == (B,)):
+            raise ValueError(f"{who}: {name} must be an int32 or int64 tensor [{B}]")
+    if arc_weights is not None and not (torch.is_tensor(arc_weights) and arc_weights.is_floating_point()
+                                        and tuple(arc_weights.shape) == (B, A)):
+        raise ValueError(f"{who}: arc_weights must be a floating-point tensor [{B}, {A}]")
+    blank = int(blank)
+    if not 0 <= blank < C_:
+        raise ValueError(f"{who}: blank must be one of the {C_} labels")
+    max_states = max(1, min(2 * A + 1, 4096)) if max_states is None else int(max_states)
+    if not 1 <= max_states <= 4096:
+        raise ValueError(f"{who}: max_states outside 1 .. 4096")
+    frames = None if input_lengths is None else _frame_counts(who, input_lengths, B, T, 0)
+    for t, what in ((x, "log_probs"), (arcs, "arcs"), (num_arcs, "num_arcs"), (num_nodes, "num_nodes"),
+                    (arc_weights, "arc_weights")):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {what} must be a CUDA tensor (the scores are computed on the device)")
+        if t.device != x.device:
+            raise ValueError(f"{who}: all tensors must be on one device")
+    arcs_c = arcs.detach().contiguous()
+    na = num_arcs.detach().to(torch.int32).contiguous()  # (int64 counts are converted on the device)
+    nn_ = num_nodes.detach().to(torch.int32).contiguous()
+    if A == 0:
+        # (an empty tensor has no address to hand over: one row that no count reaches stands in for none)
+        out = _CTCLatticeScore.apply(x, None, arcs_c.new_zeros(B, 1, 3), torch.zeros_like(na), nn_, blank, frames,
+                                     max_states)
+        return out if arc_weights is None else out + (arc_weights.sum() * 0).to(out.dtype)  # (a gradient of zeros)
+    return _CTCLatticeScore.apply(x, arc_weights, arcs_c, na, nn_, blank, frames, max_states)
+
+
+def ctc_lattice_loss(log_probs, arcs, num_arcs, num_nodes, arc_weights=None, blank=0, input_lengths=None,
+                     max_states=None):
+    """The CTC criterion whose target is a token lattice: loss[b] = sum over t < T_b of logsumexp(log_probs[b, t]) -
+    ctc_lattice_score(...)[b], float32 [B], differentiable in log_probs and arc_weights -- the negative log-likelihood
+    of the lattice, marginalised over its paths (weighted by exp of their arc weights) and their alignments.  For a
+    chain lattice without weights this is `ctc_loss`.  +inf where the score is -inf.  The arguments are those of
+    `ctc_lattice_score`; rows past T_b are never read (their gradient is exactly 0)."""
+    score = ctc_lattice_score(log_probs, arcs, num_arcs, num_nodes, arc_weights, blank, input_lengths, max_states)
+    B, T, _ = log_probs.shape
+    if input_lengths is None:
+        return torch.logsumexp(log_probs, dim=2).sum(dim=1) - score
+    frames = torch.as_tensor(_frame_counts("ctc_lattice_loss", input_lengths, B, T, 0), device=log_probs.device)
+    inside = torch.arange(T, device=log_probs.device)[None, :] < frames[:, None]
+    rows = torch.logsumexp(torch.where(inside[:, :, None], log_probs, torch.zeros_like(log_probs)), dim=2)
+    return torch.where(inside, rows, torch.zeros_like(rows)).sum(dim=1) - score
 
 
 class _ASGScore(torch.autograd.Function):

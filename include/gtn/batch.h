@@ -314,6 +314,30 @@ inline void ctcScoreGrad(const Batch& ems, const int* tokensDevice, int64_t rowS
   detail::check(gtnx_batch_ctc_score_grad(ems.handle(), frames, blank, tokensDevice, rowStride, lengthsDevice, N, L,
                                           maxLength, weightsDevice, gradDevice));
 }
+/** The exact CTC log score of one device-resident acyclic token lattice per utterance under the slabs of a
+ *  Batch::linear, results left on the device: scoresDevice[b] = log sum over the lattice's paths p of exp(w(p) +
+ *  ctcScore(emissions_b[0 .. T_b), labels(p))), nothing subtracted.  arcsDevice int32 n rows of A arcs (src, dst, label),
+ *  rowStride (>= 3 A) apart, dst-sorted; numArcsDevice / numNodesDevice int32 [n]; arcWeightsDevice float32 [n][A] or
+ *  null; maxStates 1 .. 4096 bounds nodes + arcs (larger lattices score -inf, as do invalid ones and T_b == 0).  One
+ *  launch, no copy back, no wait -- gtnx_batch_ctc_lattice_score */
+inline void ctcLatticeScore(const Batch& ems, const int* arcsDevice, int64_t rowStride, const int* numArcsDevice,
+                            const int* numNodesDevice, const float* arcWeightsDevice, int A, int maxStates,
+                            float* scoresDevice, int blank = 0, const int* frames = nullptr) {
+  detail::check(gtnx_batch_ctc_lattice_score(ems.handle(), frames, blank, arcsDevice, rowStride, numArcsDevice,
+                                             numNodesDevice, arcWeightsDevice, A, maxStates, scoresDevice));
+}
+/** gradDevice[b][t][c] = weightsDevice[b] * d score[b] / d emissions[b][t][c], every element of float32 [n][M][C]
+ *  written; arcGradDevice (or null) float32 [n][A] = weightsDevice[b] * d score[b] / d arc weight, the arcs' posteriors,
+ *  zeros past numArcs.  Stateless (the alpha rows are recomputed into pooled scratch, sliced beyond 256 MiB) and
+ *  bit-repeatable (fixed summation order, no atomics) -- gtnx_batch_ctc_lattice_score_grad */
+inline void ctcLatticeScoreGrad(const Batch& ems, const int* arcsDevice, int64_t rowStride, const int* numArcsDevice,
+                                const int* numNodesDevice, const float* arcWeightsDevice, int A, int maxStates,
+                                const float* weightsDevice, float* gradDevice, float* arcGradDevice = nullptr,
+                                int blank = 0, const int* frames = nullptr) {
+  detail::check(gtnx_batch_ctc_lattice_score_grad(ems.handle(), frames, blank, arcsDevice, rowStride, numArcsDevice,
+                                                  numNodesDevice, arcWeightsDevice, A, maxStates, weightsDevice,
+                                                  gradDevice, arcGradDevice));
+}
 /** The ASG force-align term of all n * N device-resident hypotheses under the slabs of a Batch::linear, results left on
  *  the device: scoresDevice[b][k] = forwardScore(emissions_b[0 .. T_b) o (forceAlign(tokens[b][k][0 .. len)) o
  *  transitions)), len = clamp(lengthsDevice[b][k], 0, L), log semiring, nothing subtracted.  tableDevice float32

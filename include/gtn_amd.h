@@ -585,6 +585,60 @@ gtnx_status_t gtnx_batch_ctc_score_grad(gtnx_batch_t ems, const int* frames, int
                                         const void* weights_device, void* grad_device);
 /* calls of either kind that have launched so far (process-wide) / pairs they took */
 gtnx_status_t gtnx_batch_ctc_score_stats(int64_t* calls, int64_t* pairs);
+/* The exact CTC log score of ONE ACYCLIC TOKEN LATTICE PER UTTERANCE -- several word-piece decompositions of a
+ * transcript, alternative pronunciations, optional tokens, weighted or not -- under the n emission slabs of a
+ * gtnx_batch_linear / _rows batch, lattices read where they lie on the device, scores left there:
+ *   scores[b] = log sum over the lattice's paths p of exp(w(p) + ctc_score(emissions_b[0 .. T_b), labels(p))),
+ * every decomposition and every alignment at once, nothing subtracted.  Utterance b's lattice has K = num_nodes[b]
+ * nodes (node 0 starts, node K - 1 accepts) and the arcs arcs[b][a] = (src, dst, label), a < clamp(num_arcs[b], 0, A),
+ * with 0 <= src < dst < K, sorted by dst (non-decreasing) within the utterance; arc_weights[b][a] is added once per use
+ * of the arc.  Equivalently scores[b] = forwardScore(G_b o emissions_b) for the CTC alignment graph G_b of the lattice:
+ * one blank state per node, one token state per arc, self-loops on both, blank(src) -> token(a), token(a) -> blank(dst),
+ * token(a') -> token(a) when dst(a') == src(a) and the labels differ, the arc's weight on every transition that enters
+ * token(a); paths start in blank(0) before frame 0 (so frame 0 is spent in blank(0) or in a token that leaves node 0,
+ * which pays its weight there) and end in blank(K - 1) or a token that enters node K - 1.  Two lattice paths that spell the same labels both count; a label equal to `blank` is a label like any other.
+ * arcs_device: int32, n rows of A arcs, row_stride (>= 3 A) elements apart; num_arcs_device, num_nodes_device: int32 [n];
+ * arc_weights_device: float32 [n][A] or null (all zeros) -- all DEVICE memory, none is downloaded.  frames: HOST, [n],
+ * T_b in 0 .. M, or null.  max_states (1 .. 4096) is the caller's bound on K + arcs; it sizes LDS and scratch.
+ * scores_device: float32 [n].  Float32, in this order (alpha' the next frame's row):
+ *   token a: x = logadd(alpha[a], alpha[blank src] + w_a); for a' entering src, ascending, label(a') != label(a):
+ *            x = logadd(x, alpha[a'] + w_a); alpha'[a] = x + e(t, label a)
+ *   blank n: x = alpha[n]; for a' entering n, ascending: x = logadd(x, alpha[a']); alpha'[n] = x + e(t, blank)
+ *   score = logadd over blank(K - 1), then the arcs entering K - 1 ascending.
+ * The score is -inf -- never NaN, and without a gradient -- when T_b == 0, K < 1, K + arcs > max_states, an arc has
+ * src < 0, src >= dst or dst >= K, an arc is out of dst order, a label lies outside 0 .. C - 1, a weight is +inf or NaN,
+ * or no alignment fits.  A -inf weight forbids its arc.  Nodes that cannot be reached and arcs that lead nowhere are
+ * legal and add nothing.  Every arc field is checked by the kernel before it becomes an address; nothing at or past
+ * num_arcs[b], a frame count or a row's width is read.
+ * GTNX_INVALID_ARGUMENT before a device is asked for: a null batch, arcs, num_arcs, num_nodes or scores pointer,
+ * negative A or blank, row_stride < 3 A, max_states outside 1 .. 4096.  A batch without an utterance returns without
+ * touching a device.  With the device: not a gtnx_batch_linear / _rows batch, a frame count outside 0 .. M, blank >= C,
+ * an output the engine's current device may not write.
+ * One launch on the engine's stream (ctc_lattice.hip), one workgroup per utterance, no scratch; nothing is copied back
+ * and the call does not wait. */
+gtnx_status_t gtnx_batch_ctc_lattice_score(gtnx_batch_t ems, const int* frames, int blank, const void* arcs_device,
+                                           int64_t row_stride, const void* num_arcs_device,
+                                           const void* num_nodes_device, const void* arc_weights_device, int A,
+                                           int max_states, void* scores_device);
+/* The gradients of those scores for caller-supplied weights_device (float32 [n], device memory; grad_out under
+ * autograd).  grad_device: float32 [n][M][C] = weights[b] * d scores[b] / d emissions[b]; EVERY element is written: zeros
+ * where nothing lands, rows at or past T_b included.  arc_grad_device: float32 [n][A] or null = weights[b] * d scores[b] /
+ * d arc_weights[b][a], weights[b] times the posterior probability that the arc is used; entries at or past num_arcs[b]
+ * are written as 0.  An utterance whose score is -inf or whose weight is exactly 0 gets zeros in both.  The inputs are
+ * those of gtnx_batch_ctc_lattice_score with the same meaning and refusals (weights and grad in the place of scores).
+ * The call is stateless: it recomputes the alpha rows into scratch from the stream-ordered pool, max_b T_b * max_states
+ * floats per utterance, at most 256 MiB per pair of launches; beyond that the utterances run in slices, bit-equal to the
+ * unsliced run (GTNX_CTC_LATTICE_SCRATCH_BYTES, read per call, lowers the cap: a debug switch for tests).  The sums are
+ * taken in one fixed order by plain stores -- the blank states by lane, wave tree and waves ascending, the tokens of one
+ * label ascending by arc index, the frames of an arc descending -- so both gradients have the same bits run to run;
+ * there are no floating-point atomics. */
+gtnx_status_t gtnx_batch_ctc_lattice_score_grad(gtnx_batch_t ems, const int* frames, int blank, const void* arcs_device,
+                                                int64_t row_stride, const void* num_arcs_device,
+                                                const void* num_nodes_device, const void* arc_weights_device, int A,
+                                                int max_states, const void* weights_device, void* grad_device,
+                                                void* arc_grad_device);
+/* calls of either kind that have launched so far (process-wide) / utterances they took */
+gtnx_status_t gtnx_batch_ctc_lattice_score_stats(int64_t* calls, int64_t* utterances);
 /* The best alignment of those hypotheses: WHEN each token was spoken and how well the frames support it, for all n * N
  * pairs in one call, results left on the device.  The inputs are those of gtnx_batch_ctc_score with the same meaning:
  * pair (b, k) is y = tokens[b][k][0 .. len), len = clamp(lengths[b][k], 0, L), under emissions_b[0 .. T_b).  The states
