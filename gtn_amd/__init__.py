@@ -66,6 +66,7 @@ prof_names = _api.prof_names
 debug_symbolic_route = _api.debug_symbolic_route
 debug_viterbi_ties = _api.debug_viterbi_ties
 debug_shortest_routes = _api.debug_shortest_routes  # (built-graph forward / viterbi sweeps: launches per kernel cell)
+debug_compose_routes = _api.debug_compose_routes  # (compose / intersect: products per dispatch cell)
 debug_tie_ranks = _api.debug_tie_ranks
 debug_align_stats = getattr(_api, "debug_align_stats", None)  # (Batch.viterbi_align: which route aligned how many)
 debug_decode_stats = _api.debug_decode_stats  # (Batch.viterbi_decode: which route decoded how many)

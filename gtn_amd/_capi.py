@@ -209,6 +209,7 @@ _SIGS = {
     "gtnx_debug_route_name": [C.c_int, C.c_char_p, C.c_size_t],
     "gtnx_debug_viterbi_ties": [c_i64_p, c_i64_p],
     "gtnx_debug_shortest_routes": [C.c_int, C.c_char_p, C.c_size_t, c_i64_p, c_i32_p],
+    "gtnx_debug_compose_routes": [C.c_int, C.c_char_p, C.c_size_t, c_i64_p, c_i32_p],
     "gtnx_debug_tie_ranks": [c_graph, C.c_void_p, C.c_void_p, C.c_void_p],
     "gtnx_comm_create": [c_i32_p, C.c_int, C.POINTER(C.c_void_p)],
     "gtnx_comm_destroy": [C.c_void_p],
@@ -250,7 +251,7 @@ def load(path=None):
             # test shim (oracle/ref_shim.cpp), which only tests/refbackend/gtn_ref.py loads
             if name.startswith(("gtnx_batch_", "gtnx_comm_", "gtnx_lm_graph_")) or name in ("gtnx_linear_graph_borrow_n", "gtnx_grads_bind_device_n",
                                                              "gtnx_parallel_enter", "gtnx_parallel_leave", "gtnx_parallel_flush",
-                                                             "gtnx_debug_shortest_routes"):
+                                                             "gtnx_debug_shortest_routes", "gtnx_debug_compose_routes"):
                 continue
             raise
         fn.argtypes = args

@@ -1555,6 +1555,20 @@ def make_api(lib):
             out[buf.value.decode()] = int(cnt.value)
         return out
 
+    def debug_compose_routes():
+        """{cell name: products since the process started} of compose / intersect: first kernel, hand-backs, bitmap
+        layout and the finished product's attributes (gtn_amd/csrc/ops_compose.cpp; include/gtn_amd.h:
+        gtnx_debug_compose_routes).  Needs no GPU."""
+        n = C.c_int(0)
+        check(lib.gtnx_debug_compose_routes(-1, None, 0, None, C.byref(n)))
+        out = {}
+        for cell in range(n.value):
+            buf = C.create_string_buffer(48)
+            cnt = C.c_int64(0)
+            check(lib.gtnx_debug_compose_routes(cell, buf, 48, C.byref(cnt), None))
+            out[buf.value.decode()] = int(cnt.value)
+        return out
+
     def debug_align_stats():
         """(fast, fallback): utterances Batch.viterbi_align has aligned so far by its one launch / through the path
         graphs of viterbi_path (include/gtn_amd.h: gtnx_batch_align_stats)"""
@@ -1715,6 +1729,8 @@ def make_api(lib):
     ns.debug_viterbi_ties = debug_viterbi_ties
     if hasattr(lib, "gtnx_debug_shortest_routes"):  # (the engine's kernels: not in the reference-backed shim)
         ns.debug_shortest_routes = debug_shortest_routes
+    if hasattr(lib, "gtnx_debug_compose_routes"):
+        ns.debug_compose_routes = debug_compose_routes
 
     def debug_tie_ranks(g):
         """(queue_rank, creation_rank) of a CTC-shaped target's nodes, or None (gtn_amd.h: gtnx_debug_tie_ranks)"""

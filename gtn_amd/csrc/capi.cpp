@@ -1269,6 +1269,16 @@ GTNX_API gtnx_status_t gtnx_debug_shortest_routes(int cell, char* buf, size_t ca
     if (n_cells) *n_cells = sd_route_cells();
   });
 }
+GTNX_API gtnx_status_t gtnx_debug_compose_routes(int cell, char* buf, size_t cap, int64_t* count, int* n_cells) {
+  return guard([&] {
+    if (buf && cap) {
+      std::strncpy(buf, compose_route_name(cell), cap - 1);
+      buf[cap - 1] = 0;
+    }
+    if (count) *count = compose_route_count(cell);
+    if (n_cells) *n_cells = compose_route_cells();
+  });
+}
 GTNX_API gtnx_status_t gtnx_prof_names(char* buf, size_t cap) {
   return guard([&] {
     std::string s = Runtime::get().prof_names();

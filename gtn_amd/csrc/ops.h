@@ -96,6 +96,11 @@ void op_backward(std::vector<Graph>& roots, Graph* grad, bool retain, bool seed 
 void backward_validate(Graph& root);
 // per-thread hint of gtnx_compose_mode (include/gtn_amd.h); returns the previous value
 int compose_mode_hint(int mode);
+// diagnostics: which way compose / intersect took, counted per PRODUCT on the host since the process started
+// (ops_compose.cpp; gtn_amd.h: gtnx_debug_compose_routes)
+int compose_route_cells();
+const char* compose_route_name(int cell);  // "" outside [0, compose_route_cells())
+int64_t compose_route_count(int cell);
 // build a symbolic (lazy) chain product for real, in place; no-op otherwise
 void realize(Graph& g);
 

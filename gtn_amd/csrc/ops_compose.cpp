@@ -121,6 +121,42 @@ int64_t match_bound(const LabelHist& a, const LabelHist& b) {
   return t;
 }
 
+// ---- diagnostics: the way every PRODUCT took through op_compose_impl (gtn_amd.h: gtnx_debug_compose_routes).
+// Host side only: the cells are what this file decides or reads back from ComposeOut; no kernel knows of them.
+// A call's products are counted together when the call has built (or kept symbolic) all of them, so a call that
+// throws counts nothing.
+namespace {
+enum ComposeRoute : int {
+  CR_FAST256 = 0, CR_FAST512, CR_GENERAL_LDS, CR_GENERAL_HBM, CR_WIDE_CHAIN, CR_PAIRS,
+  CR_REDO_FAST_WIDE, CR_REDO_FAST_PAIRS, CR_REDO_FAST_GENERAL, CR_REDO_WIDE_GENERAL,
+  CR_BM_CLASSIC, CR_BM_WINDOW_FULL, CR_BM_WINDOW_PARTIAL,
+  CR_SIZES_DEFERRED, CR_SIZES_READ, CR_ARRAYS_SKIPPED, CR_ARRAYS_FULL, CR_REP_INLINE, CR_REP_GRID,
+  CR_G1_CACHE_ON, CR_G1_CACHE_OFF, CR_TRANSPOSE, CR_LAYERED, CR_NOT_LAYERED, CR_SYMBOLIC,
+  CR_CELLS
+};
+const char* const kComposeRouteNames[CR_CELLS] = {
+    "fast256", "fast512", "general/lds", "general/hbm", "wide_chain", "pairs",
+    "redo/fast->wide_chain", "redo/fast->pairs", "redo/fast->general", "redo/wide_chain->general",
+    "bitmap/classic", "bitmap/window_full", "bitmap/window_partial",
+    "sizes/deferred", "sizes/read", "arrays/skipped", "arrays/full", "replicate/inline", "replicate/grid",
+    "g1_cache/on", "g1_cache/off", "transpose", "layered", "not_layered", "symbolic"};
+std::atomic<int64_t> g_compose_routes[CR_CELLS];
+struct ComposeRouteHits {  // one call's cells, added to the process-wide counters when the call has its products
+  int64_t n[CR_CELLS] = {};
+  void hit(int cell) { ++n[cell]; }
+};
+void count_compose_routes(const ComposeRouteHits& hits) {
+  for (int c = 0; c < CR_CELLS; ++c)
+    if (hits.n[c]) g_compose_routes[c].fetch_add(hits.n[c], std::memory_order_relaxed);
+}
+void count_symbolic_products(size_t n) { g_compose_routes[CR_SYMBOLIC].fetch_add(int64_t(n), std::memory_order_relaxed); }
+}  // namespace
+int compose_route_cells() { return CR_CELLS; }
+const char* compose_route_name(int cell) { return cell >= 0 && cell < CR_CELLS ? kComposeRouteNames[cell] : ""; }
+int64_t compose_route_count(int cell) {
+  return cell >= 0 && cell < CR_CELLS ? g_compose_routes[cell].load(std::memory_order_relaxed) : 0;
+}
+
 std::vector<Graph> op_compose(std::vector<Graph>& av, std::vector<Graph>& bv, bool intersect) {
   GraphSlabScope slab_scope(std::max(av.size(), bv.size()));  // the results' pieces out of one allocation (graph.h)
   return op_compose_impl(av, bv, intersect, true);
@@ -196,6 +232,7 @@ std::vector<Graph> op_compose_impl(std::vector<Graph>& av, std::vector<Graph>& b
           outs.push_back(std::move(out));
         }
         ht_phase("compose.0_symbolic_band");
+        count_symbolic_products(n);
         return outs;
       }
     }
@@ -329,6 +366,7 @@ std::vector<Graph> op_compose_impl(std::vector<Graph>& av, std::vector<Graph>& b
         out.s->lazy = std::make_shared<LazyProduct>(LazyProduct{l1 ? a : b, l1 ? b : a, l1 ? 1 : 2, intersect});
         outs.push_back(std::move(out));
       }
+      count_symbolic_products(n);
       return outs;
     }
   }
@@ -601,11 +639,33 @@ std::vector<Graph> op_compose_impl(std::vector<Graph>& av, std::vector<Graph>& b
     if (rep_env) return rep_env[0] == '0';
     return pairs > 128;
   };
+  // route diagnostics (top of the file): the kind of each product's last run, who wrote its stationary levels, whether
+  // it needed the transpose passes; `route_hits` collects the cells of the whole call
+  ComposeRouteHits route_hits;
+  std::vector<int> route_last(n, -1);
+  std::vector<char> route_grid(n, 0), route_tr(n, 0);
   // kind: 0 the general variant, 1 FAST, 2 compose_wide.hip (chain products), 3 compose_wide.hip (explicit pairs)
   auto run = [&](std::vector<size_t> order, int kind) {
     const bool fast = kind == 1;
     const size_t m = order.size();
     const bool inline_rep = inline_rep_for(m);
+    for (size_t i : order) {
+      const bool chain = (args[i].g1.kind == KIND_LINEAR) != (args[i].g2.kind == KIND_LINEAR);
+      const int prev = route_last[i];
+      if (prev < 0) {
+        route_hits.hit(kind == 1 ? (wide ? CR_FAST512 : CR_FAST256)
+                       : kind == 0 ? (classic_ok[i] ? CR_GENERAL_LDS : CR_GENERAL_HBM)
+                       : kind == 2 ? CR_WIDE_CHAIN : CR_PAIRS);
+        if (fast && chain)
+          route_hits.hit(chain_slices[i] > 0 ? (full_window[i] ? CR_BM_WINDOW_FULL : CR_BM_WINDOW_PARTIAL) : CR_BM_CLASSIC);
+      } else {
+        route_hits.hit(prev == 2 ? CR_REDO_WIDE_GENERAL
+                       : kind == 2 ? CR_REDO_FAST_WIDE : kind == 3 ? CR_REDO_FAST_PAIRS : CR_REDO_FAST_GENERAL);
+      }
+      route_last[i] = kind;
+      route_grid[i] = fast && chain && !inline_rep;
+      route_tr[i] = 0;
+    }
     double alg = 0;
     for (size_t i : order) alg += 36.0 * double(caps[i].Acap) + 8.0 * double(caps[i].Ncap);
     if (kind == 2)  // one launch per side the chain is on
@@ -701,6 +761,7 @@ std::vector<Graph> op_compose_impl(std::vector<Graph>& av, std::vector<Graph>& b
     for (size_t i = 0; i < m; ++i) {
       const ComposeOut& co = res_out[order[i]];
       need_tr = need_tr || (!co.csr_built && co.overflow == 0);
+      route_tr[order[i]] = !co.csr_built && co.overflow == 0;
     }
     if (need_tr) {
       zero_cursors();
@@ -758,6 +819,14 @@ std::vector<Graph> op_compose_impl(std::vector<Graph>& av, std::vector<Graph>& b
     }
     if (co.overflow) throw_runtime("[gtn::compose] internal capacity bound exceeded");
     const ComposeArgs& x = args[i];
+    route_hits.hit(deferred ? CR_SIZES_DEFERRED : CR_SIZES_READ);
+    route_hits.hit(co.skipped ? CR_ARRAYS_SKIPPED : CR_ARRAYS_FULL);
+    route_hits.hit(co.layered ? CR_LAYERED : CR_NOT_LAYERED);
+    if (route_tr[i]) route_hits.hit(CR_TRANSPOSE);
+    if (route_last[i] == 1) {  // finished by the FAST variant
+      route_hits.hit(cache1 ? CR_G1_CACHE_ON : CR_G1_CACHE_OFF);
+      if ((x.g1.kind == KIND_LINEAR) != (x.g2.kind == KIND_LINEAR)) route_hits.hit(route_grid[i] ? CR_REP_GRID : CR_REP_INLINE);
+    }
     Graph& a = const_cast<Graph&>(bcast(av, n, i));
     Graph& b = const_cast<Graph&>(bcast(bv, n, i));
     Graph out = make_output(op, int(i), {a, b});
@@ -885,6 +954,7 @@ std::vector<Graph> op_compose_impl(std::vector<Graph>& av, std::vector<Graph>& b
     deferred_register(deferred);
   }
   ht_phase("compose.5_outputs");
+  count_compose_routes(route_hits);
   return outs;
 }
 

@@ -980,6 +980,18 @@ gtnx_status_t gtnx_debug_route_name(int route, char* buf, size_t cap);
  * process started into *launches.  A cell outside [0, *n_cells) gives an empty name and 0.  Any pointer may be NULL.
  * No reference analogue. */
 gtnx_status_t gtnx_debug_shortest_routes(int cell, char* buf, size_t cap, int64_t* launches, int* n_cells);
+/* Diagnostics (host only, no GPU needed): the way compose / intersect took (gtn_amd/csrc/ops_compose.cpp), counted per
+ * PRODUCT -- not per launch -- since the process started.  Cell `cell` of *n_cells: its name into buf and its count into
+ * *count.  The cells: the kernel of a product's first run ("fast256", "fast512", "general/lds", "general/hbm",
+ * "wide_chain", "pairs"); the hand-backs a kernel asked for ("redo/fast->wide_chain", "redo/fast->pairs",
+ * "redo/fast->general", "redo/wide_chain->general"); the bitmap layout of a chain product whose first run was the FAST
+ * variant ("bitmap/classic", "bitmap/window_full", "bitmap/window_partial"); and attributes of the finished product:
+ * "sizes/deferred" | "sizes/read", "arrays/skipped" | "arrays/full", "layered" | "not_layered", "transpose" (it needed
+ * the transpose passes), for products the FAST variant finished "g1_cache/on" | "g1_cache/off" and, chain products
+ * only, "replicate/inline" | "replicate/grid"; "symbolic": the product stayed lazy and nothing was built.  A call that
+ * throws counts nothing.  A cell outside [0, *n_cells) gives an empty name and 0.  Any pointer may be NULL.  No
+ * reference analogue. */
+gtnx_status_t gtnx_debug_compose_routes(int cell, char* buf, size_t cap, int64_t* count, int* n_cells);
 
 #ifdef __cplusplus
 }
