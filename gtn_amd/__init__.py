@@ -81,6 +81,7 @@ debug_ctc_lattice_score_stats = _api.debug_ctc_lattice_score_stats  # (Batch.ctc
 debug_ctc_token_align_stats = _api.debug_ctc_token_align_stats  # (Batch.ctc_token_align: calls that launched, pairs aligned)
 debug_asg_token_align_stats = _api.debug_asg_token_align_stats  # (Batch.asg_token_align: calls that launched, pairs aligned)
 debug_asg_score_stats = _api.debug_asg_score_stats  # (Batch.asg_score / asg_score_grad: calls that launched, pairs taken)
+debug_asg_lattice_score_stats = _api.debug_asg_lattice_score_stats  # (Batch.asg_lattice_score / _grad: calls, utterances)
 debug_asg_beam_stats = _api.debug_asg_beam_stats  # (Batch.asg_beam_decode: calls that launched, utterances decoded)
 debug_asg_sample_stats = _api.debug_asg_sample_stats  # (Batch.asg_sample: calls that launched, utterances sampled)
 

@@ -174,6 +174,12 @@ _SIGS = {
     "gtnx_batch_asg_score_grad": [c_graph, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int,
                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "gtnx_batch_asg_score_stats": [c_i64_p, c_i64_p],
+    "gtnx_batch_asg_lattice_score": [c_graph, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "gtnx_batch_asg_lattice_score_grad": [c_graph, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p],
+    "gtnx_batch_asg_lattice_score_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_asg_token_align": [c_graph, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int,
                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                    C.c_int64],

@@ -1429,6 +1429,70 @@ def make_api(lib):
                                                 _opt_ptr(tok), stride, _opt_ptr(ln), N, L, U, _opt_ptr(weights),
                                                 _opt_ptr(grad_out), _opt_ptr(grad_table_out)))
 
+        def asg_lattice_score(self, table, arcs, num_arcs, num_nodes, scores_out, arc_weights=None, frames=None,
+                              max_states=None, max_edges=None, A=None, row_stride=None):
+            """The exact ASG log score of one device-resident acyclic token lattice per utterance under the slabs of a
+            Batch.linear, results left on the device (gtnx_batch_asg_lattice_score; DESIGN section 37 holds the contract):
+            scores_out[b] = log sum over the lattice's paths p of exp(w(p) + asg_score(emissions_b[:T_b], table,
+            labels(p))), nothing subtracted.  `table` is that of `asg_score`; `arcs`, `num_arcs`, `num_nodes`,
+            `arc_weights`, `frames`, `max_states`, A and row_stride are those of `ctc_lattice_score` (the states are the
+            arcs: there is no blank, equal neighbours are legal).  `max_edges` (1 .. 2^21, default min(8 * max_states,
+            2^21)): the caller's bound on the sum over the arcs of the in-degree of their src.  -inf, never NaN: T_b == 0,
+            num_nodes < 1, nodes + arcs > max_states, more edges than max_edges, an invalid arc or weight, no alignment
+            (a one-node lattice has none).  One launch, no copy back and no wait."""
+            who = "asg_lattice_score"
+            fr, A, stride, SM = self._ctc_lattice_args(who, arcs, num_arcs, num_nodes, arc_weights, frames, A, row_stride,
+                                                       max_states)
+            table = self._asg_score_table(who, table)
+            if max_edges is None:
+                max_edges = min(8 * SM, 1 << 21)
+            if scores_out is not None and hasattr(scores_out, "data_ptr"):
+                if (str(scores_out.dtype) != "torch.float32" or not scores_out.is_contiguous()
+                        or scores_out.numel() != len(self)):
+                    raise ValueError(f"{who}: scores_out must be a float32 contiguous tensor [B]")
+            check(lib.gtnx_batch_asg_lattice_score(self._h, fr.ctypes.data if fr is not None else None, _opt_ptr(table),
+                                                   _opt_ptr(arcs), stride, _opt_ptr(num_arcs), _opt_ptr(num_nodes),
+                                                   _opt_ptr(arc_weights), A, SM, int(max_edges), _opt_ptr(scores_out)))
+
+        def asg_lattice_score_grad(self, table, arcs, num_arcs, num_nodes, weights, grad_out=None, grad_table_out=None,
+                                   arc_grad_out=None, arc_weights=None, frames=None, max_states=None, max_edges=None,
+                                   A=None, row_stride=None):
+            """The gradients of the scores of `asg_lattice_score` under `weights` (float32 [B] on the device), in one
+            stateless call (gtnx_batch_asg_lattice_score_grad): `grad_out` (float32 [B, M, C] or None) = weights[b] * d
+            score[b] / d emissions[b]; `grad_table_out` (float32 [C + C * C] or None) = sum over b of weights[b] * d
+            score[b] / d table; `arc_grad_out` (float32 [B, A] or None) = weights[b] * the posterior of every arc, zeros
+            at or past num_arcs[b]; not all three None, and every element of a given output is written.  Utterances with
+            a -inf score or a weight of exactly 0 add nothing.  Alpha rows and one cell per edge are recomputed into
+            pooled scratch (sliced beyond 256 MiB, same bits); the sums are taken in a fixed order without atomics, so
+            the results have the same bits run to run."""
+            who = "asg_lattice_score_grad"
+            fr, A, stride, SM = self._ctc_lattice_args(who, arcs, num_arcs, num_nodes, arc_weights, frames, A, row_stride,
+                                                       max_states)
+            table = self._asg_score_table(who, table)
+            if max_edges is None:
+                max_edges = min(8 * SM, 1 << 21)
+            if grad_out is None and grad_table_out is None and arc_grad_out is None:
+                raise ValueError(f"{who}: none of grad_out, grad_table_out and arc_grad_out given")
+            n = len(self)
+            m, c = C.c_int(-1), C.c_int(-1)
+            check(lib.gtnx_batch_linear_shape(self._h, C.byref(m), C.byref(c)))
+            known = m.value >= 0
+            for o, count, what in ((weights, n, "weights must be a float32 contiguous tensor [B]"),
+                                   (grad_out, n * m.value * c.value if known else None,
+                                    "grad_out must be a float32 contiguous tensor [B, M, C]"),
+                                   (grad_table_out, c.value + c.value * c.value if known else None,
+                                    "grad_table_out must be a float32 contiguous tensor [C + C * C]"),
+                                   (arc_grad_out, n * A, "arc_grad_out must be a float32 contiguous tensor [B, A]")):
+                if o is not None and hasattr(o, "data_ptr"):
+                    if (str(o.dtype) != "torch.float32" or not o.is_contiguous()
+                            or (count is not None and o.numel() != count)):
+                        raise ValueError(f"{who}: {what}")
+            check(lib.gtnx_batch_asg_lattice_score_grad(self._h, fr.ctypes.data if fr is not None else None,
+                                                        _opt_ptr(table), _opt_ptr(arcs), stride, _opt_ptr(num_arcs),
+                                                        _opt_ptr(num_nodes), _opt_ptr(arc_weights), A, SM, int(max_edges),
+                                                        _opt_ptr(weights), _opt_ptr(grad_out), _opt_ptr(grad_table_out),
+                                                        _opt_ptr(arc_grad_out)))
+
     ns.Batch = Batch
 
     def _batch_fn(cfn, *args):
@@ -1703,6 +1767,11 @@ def make_api(lib):
         far and the utterances they took (include/gtn_amd.h: gtnx_batch_ctc_lattice_score_stats)"""
         return _stats2(lib.gtnx_batch_ctc_lattice_score_stats)
 
+    def debug_asg_lattice_score_stats():
+        """(calls, utterances): calls of Batch.asg_lattice_score / Batch.asg_lattice_score_grad that have launched so
+        far and the utterances they took (include/gtn_amd.h: gtnx_batch_asg_lattice_score_stats)"""
+        return _stats2(lib.gtnx_batch_asg_lattice_score_stats)
+
     def debug_full_connect_stats():
         """(fast, fallback): utterances whose ASG full-connect score forward_score(compose(Batch.linear(rows=...),
         transitions)) came from the one launch of asg_full.hip / utterances of such a padded batch that took the composed
@@ -1721,6 +1790,7 @@ def make_api(lib):
     ns.debug_ctc_token_align_stats = debug_ctc_token_align_stats
     ns.debug_ctc_lattice_score_stats = debug_ctc_lattice_score_stats
     ns.debug_asg_score_stats = debug_asg_score_stats
+    ns.debug_asg_lattice_score_stats = debug_asg_lattice_score_stats
     ns.debug_asg_token_align_stats = debug_asg_token_align_stats
     ns.debug_asg_beam_stats = debug_asg_beam_stats
     ns.debug_asg_sample_stats = debug_asg_sample_stats

@@ -102,6 +102,35 @@ inline void asgLossBatch(
   asgLossBatch(emissions, flat.data(), len.data(), (int)targets.size(), T, N, transitions, lossDev, gradDev, frames);
 }
 
+/** The full-connect term of asgLossBatch on its own: scores[b] = forwardScore(emissions_b[:frames[b]] o transitions),
+ *  the first half of the criterion, for criteria that subtract another numerator from it (asgLatticeScoreBatch's).
+ *  `emissions`: device [B][T][N], read in place; `transitions`: the graph of asgTransitions(N) with the caller's weights
+ *  (with calcGrad its gradient accumulates over the batch with unit seeds, as in asgLossBatch); `scoresDev`: device
+ *  [B]; `gradDev`: device [B][T][N] or null, d scores[b] / d emissions_b, rows past frames[b] 0; `frames`: host [B]
+ *  (1 .. T) or null.  The same launches asgLossBatch runs for this term; nothing new is compiled for it. */
+inline void asgFullConnectBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int N,
+    Graph& transitions,
+    void* scoresDev,
+    void* gradDev,
+    const int* frames = nullptr) {
+  if (frames)  // (before anything is launched)
+    for (int b = 0; b < B; ++b)
+      if (frames[b] < 1 || frames[b] > T) throw std::invalid_argument("[asgFullConnectBatch] a frame count outside 1 .. T");
+  Batch ems = Batch::linear(B, T, N, emissions, gradDev != nullptr, /*borrow=*/true, frames);
+  std::vector<int64_t> off(B);
+  for (int b = 0; b < B; ++b) off[b] = (int64_t)b * T * N;
+  Batch trans(std::vector<Graph>{transitions});
+  SymbolicCompose symbolic;  // the product is never built
+  Batch fcc = batched::forwardScore(batched::compose(ems, trans));
+  if (gradDev || transitions.calcGrad()) batched::backward(fcc);
+  fcc.itemsToDevice(scoresDev);
+  if (gradDev) ems.gradsToDevice(gradDev, off.data());
+}
+
 /** ASG forced alignment of a batch, results on the device: per utterance the best path of
  *  emissions_b o (forceAlign_b o transitions) (viterbiPath, shortest.cpp:190-272) as the label of every frame
  *  (`labelsDev`, device int32 [B][T]), the index of that label in the target (`tokensDev`, device int32 [B][T] or
@@ -212,6 +241,56 @@ inline void asgScoreBatch(
     batched::asgScoreGrad(ems, static_cast<const float*>(tableDev), static_cast<const int*>(tokensDev), L,
                           static_cast<const int*>(lengthsDev), N, L, maxLength, static_cast<const float*>(weightsDev),
                           static_cast<float*>(gradEmDev), static_cast<float*>(gradTableDev), frames);
+  }
+}
+
+/** The exact ASG log scores of one device-resident token lattice per utterance under the B emission slabs, and (with
+ *  weightsDev and at least one gradient) the gradients under those weights: `emissions` device float32 [B][T][N_], read
+ *  in place; `tableDev` device float32 [N_ + N_ * N_] as for asgScoreBatch; `arcsDev` device int32 [B][A][3] (dense rows
+ *  of (src, dst, label), dst-sorted); `numArcsDev` / `numNodesDev` device int32 [B]; `arcWeightsDev` device float32
+ *  [B][A] or null; `frames` host [B] or null; `scoresDev` device float32 [B] or null; `weightsDev` device float32 [B];
+ *  `gradEmDev` device float32 [B][T][N_] or null; `gradTableDev` device float32 [N_ + N_ * N_] or null; `arcGradDev`
+ *  device float32 [B][A] or null.  gtnx_batch_asg_lattice_score / _grad have the contract.  Nothing is copied back. */
+inline void asgLatticeScoreBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int N_,
+    const void* tableDev,
+    const int* frames,
+    const void* arcsDev,
+    const void* numArcsDev,
+    const void* numNodesDev,
+    const void* arcWeightsDev,
+    int A,
+    int maxStates,
+    int maxEdges,
+    void* scoresDev,
+    const void* weightsDev = nullptr,
+    void* gradEmDev = nullptr,
+    void* gradTableDev = nullptr,
+    void* arcGradDev = nullptr) {
+  const bool wantGrad = gradEmDev || gradTableDev || arcGradDev;
+  if ((weightsDev != nullptr) != wantGrad) {
+    throw std::invalid_argument("asgLatticeScoreBatch: weights and a gradient come together");
+  }
+  if (!scoresDev && !wantGrad) {
+    throw std::invalid_argument("asgLatticeScoreBatch: neither scores nor a gradient asked for");
+  }
+  Batch ems = Batch::linear(B, T, N_, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  if (scoresDev) {
+    batched::asgLatticeScore(ems, static_cast<const float*>(tableDev), static_cast<const int*>(arcsDev), 3 * int64_t(A),
+                             static_cast<const int*>(numArcsDev), static_cast<const int*>(numNodesDev),
+                             static_cast<const float*>(arcWeightsDev), A, maxStates, maxEdges,
+                             static_cast<float*>(scoresDev), frames);
+  }
+  if (wantGrad) {
+    batched::asgLatticeScoreGrad(ems, static_cast<const float*>(tableDev), static_cast<const int*>(arcsDev),
+                                 3 * int64_t(A), static_cast<const int*>(numArcsDev),
+                                 static_cast<const int*>(numNodesDev), static_cast<const float*>(arcWeightsDev), A,
+                                 maxStates, maxEdges, static_cast<const float*>(weightsDev),
+                                 static_cast<float*>(gradEmDev), static_cast<float*>(gradTableDev),
+                                 static_cast<float*>(arcGradDev), frames);
   }
 }
 

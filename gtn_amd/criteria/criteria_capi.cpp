@@ -270,6 +270,31 @@ GTN_EXPORT int gtn_asg_loss_frames_n(const void* emissions, const int* targets, 
   });
 }
 
+// The full-connect term of the ASG criterion alone.  emissions / trans_w as for gtn_asg_loss_n; frames: host int32 [B]
+// (1 .. T) or null; scores: DEVICE float [B]; grad_em: DEVICE [B][T][N] or null; grad_trans: DEVICE [N + N*N] or null
+// (summed over the batch with unit seeds).
+GTN_EXPORT int gtn_asg_full_connect_n(const void* emissions, int B, int T, int N, const void* trans_w, const int* frames,
+                                      void* scores, void* grad_em, void* grad_trans) {
+  return guarded([&] {
+    if (!scores) throw std::invalid_argument("[gtn_asg_full_connect_n] null scores");
+    if (frames)  // (before the weights are handed to the engine: no device is asked for an invalid call)
+      for (int b = 0; b < B; ++b)
+        if (frames[b] < 1 || frames[b] > T)
+          throw std::invalid_argument("[gtn_asg_full_connect_n] a frame count outside 1 .. T");
+    std::lock_guard<std::mutex> lk(g_loss_transitions.mu);
+    gtn::Graph& trans = transitions_for(g_loss_transitions, N, grad_trans != nullptr);
+    trans.setCalcGrad(grad_trans != nullptr);
+    trans.zeroGrad();
+    trans.setWeightsDevice(trans_w);  // arc ids are creation order: arcSort permutes lists, not ids
+    gtn::criteria::asgFullConnectBatch(emissions, B, T, N, trans, scores, grad_em, frames);
+    if (grad_trans) {
+      gtnx_graph_t h = trans.handle();
+      int64_t off = 0;
+      gtn::detail::check(gtnx_grads_device_n(&h, 1, grad_trans, &off));
+    }
+  });
+}
+
 // ASG forced alignment.  emissions / targets / lengths / trans_w as for gtn_asg_loss_n; frames: host int32 [B] or null;
 // labels: DEVICE int32 [B][T]; tokens: DEVICE int32 [B][T] or null; scores: DEVICE float [B] or null.
 GTN_EXPORT int gtn_asg_align_n(const void* emissions, const int* targets, const int* lengths, int B, int T, int N,
@@ -353,6 +378,34 @@ GTN_EXPORT int gtn_asg_score_grad_n(const void* emissions, int B, int T, int C, 
     if (!weights || (!grad_em && !grad_table)) throw std::invalid_argument("gtn_asg_score_grad_n: null weights or no gradient");
     gtn::criteria::asgScoreBatch(emissions, B, T, C, table, frames, tokens, lengths, N, L, max_length, nullptr, weights,
                                  grad_em, grad_table);
+  });
+}
+
+// Exact ASG log scores of one device-resident token lattice per utterance.  emissions: DEVICE float32 [B][T][C]; table:
+// DEVICE float32 [C + C*C] as for gtn_asg_score_n; frames: HOST int [B] or null; arcs: DEVICE int32 [B][A][3]; num_arcs /
+// num_nodes: DEVICE int32 [B]; arc_weights: DEVICE float32 [B][A] or null; scores: DEVICE float32 [B].
+GTN_EXPORT int gtn_asg_lattice_score_n(const void* emissions, int B, int T, int C, const void* table, const int* frames,
+                                       const void* arcs, const void* num_arcs, const void* num_nodes,
+                                       const void* arc_weights, int A, int max_states, int max_edges, void* scores) {
+  return guarded([&] {
+    if (!scores) throw std::invalid_argument("gtn_asg_lattice_score_n: null scores");
+    gtn::criteria::asgLatticeScoreBatch(emissions, B, T, C, table, frames, arcs, num_arcs, num_nodes, arc_weights, A,
+                                        max_states, max_edges, scores);
+  });
+}
+
+// ... and their gradients under weights: DEVICE float32 [B]: grad_em (DEVICE float32 [B][T][C]), grad_table (DEVICE
+// float32 [C + C*C]) and arc_grad (DEVICE float32 [B][A]), every element written; each may be null, not all three.
+GTN_EXPORT int gtn_asg_lattice_score_grad_n(const void* emissions, int B, int T, int C, const void* table,
+                                            const int* frames, const void* arcs, const void* num_arcs,
+                                            const void* num_nodes, const void* arc_weights, int A, int max_states,
+                                            int max_edges, const void* weights, void* grad_em, void* grad_table,
+                                            void* arc_grad) {
+  return guarded([&] {
+    if (!weights || (!grad_em && !grad_table && !arc_grad))
+      throw std::invalid_argument("gtn_asg_lattice_score_grad_n: null weights or no gradient");
+    gtn::criteria::asgLatticeScoreBatch(emissions, B, T, C, table, frames, arcs, num_arcs, num_nodes, arc_weights, A,
+                                        max_states, max_edges, nullptr, weights, grad_em, grad_table, arc_grad);
   });
 }
 

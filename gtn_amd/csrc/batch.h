@@ -402,6 +402,35 @@ void batch_asg_score_grad(const BatchP& ems, const int* frames, const float* tab
                           int64_t row_stride, const int* lengths_dev, int N, int L, int max_length,
                           const float* weights_dev, float* grad_em_dev, float* grad_table_dev);
 void batch_asg_score_stats(int64_t* calls, int64_t* pairs);  // calls that launched (either kind) / pairs they took
+// The exact ASG log score of one device-resident acyclic token lattice per utterance (batch_ctc_lattice_score's form)
+// under the n emission slabs of a native linear batch and the [C + C * C] table of batch_asg_score, results on the device
+// (DESIGN section 37 holds the contract): scores_dev[b] = log sum over the lattice's paths p of exp(w(p) +
+// asg_score(emissions_b[:T_b], table, labels(p))), nothing subtracted.  The states are the arcs: there is no blank and
+// equal neighbouring labels are legal.  max_states (1 .. 4096) bounds nodes + arcs, as for the CTC call; max_edges
+// (1 .. 2^21) bounds E_b = the sum over the arcs of the in-degree of their src -- the kernel counts E_b and an utterance
+// above the bound scores -inf.  -inf (never NaN): T_b == 0, num_nodes < 1, nodes + arcs > max_states, E_b > max_edges,
+// every arc field batch_ctc_lattice_score refuses, a weight that is +inf or NaN, no alignment (a one-node lattice has
+// none), every alignment through a -inf emission or table entry.  Invalid argument before a device is asked for: a null
+// pointer, negative A, row_stride < 3 A, max_states outside 1 .. 4096, max_edges outside 1 .. 2^21; n == 0 returns
+// without a device.  With the device: not a native linear batch, a frame count outside 0 .. M, more than 16384 labels, a
+// table that is not device memory, an output that is not memory of the current device.  One launch, no scratch, no wait.
+void batch_asg_lattice_score(const BatchP& ems, const int* frames, const float* table_dev, const int* arcs_dev,
+                             int64_t row_stride, const int* num_arcs_dev, const int* num_nodes_dev,
+                             const float* arc_weights_dev, int A, int max_states, int max_edges, float* scores_dev);
+// The gradients for weights_dev [n], each output nullable but not all three: grad_em_dev [n][M][C] = weights[b] * d
+// score[b] / d emissions (every element written, pad rows included); grad_table_dev [C + C * C] = sum_b weights[b] * d
+// score[b] / d table (every element written); arc_grad_dev [n][A] = weights[b] * the posterior of the arc, zeros at or
+// past num_arcs[b].  An utterance whose score is -inf or whose weight is exactly 0 adds nothing.  The alpha rows (max T_b
+// * max_states floats per utterance), and with a table or arc gradient one cell per edge (max_edges floats) plus five
+// rows of max_states words, come from the stream-ordered pool, at most 256 MiB per launch group
+// (GTNX_ASG_LATTICE_SCRATCH_BYTES lowers the cap: a debug switch); beyond it the utterances run in slices with the same
+// bits, the table launch of a slice carrying on from what the one before stored.  No floating-point atomics.
+void batch_asg_lattice_score_grad(const BatchP& ems, const int* frames, const float* table_dev, const int* arcs_dev,
+                                  int64_t row_stride, const int* num_arcs_dev, const int* num_nodes_dev,
+                                  const float* arc_weights_dev, int A, int max_states, int max_edges,
+                                  const float* weights_dev, float* grad_em_dev, float* grad_table_dev,
+                                  float* arc_grad_dev);
+void batch_asg_lattice_score_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
 // The best ASG alignment of all n * N device-resident hypotheses (the pair form and the table of batch_asg_score) under
 // the n emission slabs of a native linear batch, results on the device (DESIGN section 28 holds the contract): the
 // outputs are those of batch_ctc_token_align, frame_tokens_dev never -1 inside a path (there is no blank).  Float32

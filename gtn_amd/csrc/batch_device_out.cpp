@@ -1,8 +1,8 @@
 // batch_device_out.cpp -- the batch entry points that leave their results in the caller's device memory (declared and
 // specified in batch.h): forced alignment, decode against one shared graph, best path of the chains plus the CTC
 // collapse, CTC prefix beam search, ASG prefix beam search, edit distance, CTC score and its gradient, CTC token
-// alignment, CTC lattice score and its gradients, ASG score and its gradients, ASG token alignment, CTC and ASG posterior
-// sampling.  The kernels differ;
+// alignment, CTC lattice score and its gradients, ASG score and its gradients, ASG lattice score and its gradients, ASG
+// token alignment, CTC and ASG posterior sampling.  The kernels differ;
 // the host side around them is the helpers below.
 //
 // Recipe for the next entry point, in this order:
@@ -1377,6 +1377,154 @@ void batch_asg_score_grad(const BatchP& ems, const int* frames, const float* tab
   GTNX_HOST_T("batch.asg_score_grad");
   asg_score_impl("gtnx_batch_asg_score_grad", ems, frames, table_dev,
                  {tokens_dev, row_stride, lengths_dev, N, L, max_length}, nullptr, weights_dev, grad_em_dev, grad_table_dev);
+}
+
+// ---- batched ASG score of one device-resident token lattice per utterance, and its gradients (asg_lattice.hip) ----
+namespace {
+Counters g_asg_lattice;  // (calls, utterances)
+// the alpha rows and the edge rows of a gradient call: an utterance that is above the cap by itself runs alone
+constexpr ScratchCap kAsgLatticeScratch{"GTNX_ASG_LATTICE_SCRATCH_BYTES", int64_t(256) << 20};
+static_assert(kAsgLatticeMaxStates == 4096 && kAsgLatticeMaxEdges == 1 << 21, "the text below says 4096 and 2^21");
+
+// both entry points: scores_dev for the score; weights_dev and the three gradients (each or null) for the gradients
+void asg_lattice_impl(const char* who, const BatchP& ems, const int* frames, const float* table_dev, const Lattices& h,
+                      int max_edges, float* scores_dev, const float* weights_dev, float* grad_em_dev,
+                      float* grad_table_dev, float* arc_grad_dev) {
+  const bool want_grad = scores_dev == nullptr;
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) refuse(who, "null batch");
+  if (!table_dev) refuse(who, "null table pointer");
+  if (!h.arcs || !h.num_arcs || !h.num_nodes)
+    refuse(who, "null input pointer (arcs, num_arcs and num_nodes are all read)");
+  if (want_grad && !weights_dev) refuse(who, "null weights pointer");
+  if (want_grad && !grad_em_dev && !grad_table_dev && !arc_grad_dev)
+    refuse(who, "no gradient asked for (all three pointers null)");
+  if (h.A < 0) refuse(who, "negative A");
+  if (h.row_stride < 3 * int64_t(h.A)) refuse(who, "row_stride is shorter than the rows' width 3 A");
+  if (h.max_states < 1 || h.max_states > kAsgLatticeMaxStates) refuse(who, "max_states outside 1 .. 4096");
+  if (max_edges < 1 || max_edges > kAsgLatticeMaxEdges) refuse(who, "max_edges outside 1 .. 2^21");
+  const int n = ems->n;
+  if (n <= 0) return;
+  Batch& x = linear_hypothesis_batch(who, ems, frames);
+  Runtime& rt = Runtime::get();
+  // (the table kernel keeps one row of C floats in LDS)
+  if (x.C > kAsgScoreMaxC) refuse(who, "more than 16384 labels");
+  // (the kernel gathers from it: host memory is refused too, with one GPU as well)
+  if (!ptr_device_memory_of(table_dev, rt.device())) refuse(who, "the table is not memory of the engine's current device");
+  check_outputs_local(who, {scores_dev, grad_em_dev, grad_table_dev, arc_grad_dev});
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  const std::vector<int> fr = resolve_frames(frames, x);
+  int maxT = 0;
+  double sumT = 0;
+  for (int t : fr) {
+    maxT = std::max(maxT, t);
+    sumT += t;
+  }
+  DevMemP fr_dev = upload_vec(fr);
+  const int64_t SM = h.max_states;
+  AsgLatticeArgs a{};
+  a.em = x.w_dev;
+  a.frames = fr_dev->as<int>();
+  a.table = table_dev;
+  a.arcs = h.arcs;
+  a.num_arcs = h.num_arcs;
+  a.num_nodes = h.num_nodes;
+  a.arc_weights = h.arc_weights;
+  a.weights = weights_dev;
+  a.grad = grad_em_dev;
+  a.grad_table = grad_table_dev;
+  a.arc_grad = arc_grad_dev;
+  a.row_stride = h.row_stride;
+  a.A = h.A;
+  a.SM = h.max_states;
+  a.M = x.M;
+  a.C = x.C;
+  a.max_edges = max_edges;
+  // algorithmic bytes, by the widths and the caller's bounds (the counts are device memory: an upper bound).  forward:
+  // per utterance and frame one emission per arc and one table entry per edge, the arcs (and their weights) once, the
+  // score out.  With the rows kept: every alpha out as well.  backward: the alphas and the emissions back in, two table
+  // entries per edge and frame, an edge cell in and out per frame, one store of a gradient element per arc and frame at
+  // most, the slab zeroed once.  table: every workgroup streams the labels, the sums come back in once, the table out.
+  const int64_t arcs_max = std::min<int64_t>(h.A, SM);
+  const double mean_t = sumT / double(n);
+  const double lattice = (h.arc_weights ? 16.0 : 12.0) * double(arcs_max) + 12.0;
+  const double fwd_utt = 4.0 * (double(arcs_max) + double(max_edges)) * mean_t + lattice;
+  if (!want_grad) {
+    a.scores = scores_dev;
+    a.utt0 = 0;
+    a.score0 = 0;
+    a.count = n;
+    GTNX_PROF("asg_lattice", fwd_utt * double(n));
+    launch_asg_lattice_forward(a, rt.stream());
+  } else {
+    const bool want_edges = grad_table_dev || arc_grad_dev;
+    const int64_t alpha_utt = std::max<int64_t>(int64_t(maxT), 1) * SM;  // floats
+    const int64_t per_utt = alpha_utt + (want_edges ? int64_t(max_edges) : 0) + (grad_table_dev ? 5 * SM : 0);
+    a.utt_stride = alpha_utt;
+    a.table_first = 1;
+    for_pair_slices(n, 4 * per_utt, kAsgLatticeScratch, [&](int64_t u0, int64_t cnt) {
+      DevMemP rows = rt.alloc(size_t(4 * alpha_utt * cnt));
+      DevMemP sc = rt.alloc(size_t(4 * cnt));
+      DevMemP edges, occ, csr;
+      if (want_edges) {
+        edges = rt.alloc(size_t(4) * size_t(max_edges) * size_t(cnt));
+        a.edge = edges->as<float>();
+      }
+      if (grad_table_dev) {
+        occ = rt.alloc(size_t(8 * SM * cnt));
+        csr = rt.alloc(size_t(12 * SM * cnt));
+        a.occ = occ->as<float>();
+        a.csr = csr->as<int>();
+      }
+      a.alpha = rows->as<float>();
+      a.scores = sc->as<float>();
+      a.utt0 = int(u0);
+      a.score0 = int(u0);
+      a.count = int(cnt);
+      {
+        GTNX_PROF("asg_lattice_alpha", (fwd_utt + 4.0 * double(arcs_max) * mean_t) * double(cnt));
+        launch_asg_lattice_forward(a, rt.stream());
+      }
+      {
+        GTNX_PROF("asg_lattice_grad", (2.0 * fwd_utt + (want_edges ? 8.0 * double(max_edges) * mean_t : 0.0) +
+                                       (grad_em_dev ? 4.0 * double(x.M) * x.C : 0.0) + (arc_grad_dev ? 4.0 * h.A : 0.0)) *
+                                          double(cnt));
+        launch_asg_lattice_backward(a, rt.stream());
+      }
+      if (grad_table_dev) {
+        GTNX_PROF("asg_lattice_table", (4.0 * double(arcs_max) * double(x.C + 1) + 8.0 * double(max_edges)) * double(cnt) +
+                                           8.0 * double(x.C) * double(x.C + 1));
+        launch_asg_lattice_table(a, rt.stream());
+        a.table_first = 0;
+      }
+      // (the rows go back to the stream-ordered pool behind the launches)
+    });
+  }
+  g_asg_lattice.add(1, n);
+}
+}  // namespace
+
+void batch_asg_lattice_score_stats(int64_t* calls, int64_t* utterances) { g_asg_lattice.get(calls, utterances); }
+
+void batch_asg_lattice_score(const BatchP& ems, const int* frames, const float* table_dev, const int* arcs_dev,
+                             int64_t row_stride, const int* num_arcs_dev, const int* num_nodes_dev,
+                             const float* arc_weights_dev, int A, int max_states, int max_edges, float* scores_dev) {
+  GTNX_HOST_T("batch.asg_lattice_score");
+  if (!scores_dev) throw_invalid("[gtnx_batch_asg_lattice_score] null scores pointer");
+  asg_lattice_impl("gtnx_batch_asg_lattice_score", ems, frames, table_dev,
+                   {arcs_dev, row_stride, num_arcs_dev, num_nodes_dev, arc_weights_dev, A, max_states}, max_edges,
+                   scores_dev, nullptr, nullptr, nullptr, nullptr);
+}
+
+void batch_asg_lattice_score_grad(const BatchP& ems, const int* frames, const float* table_dev, const int* arcs_dev,
+                                  int64_t row_stride, const int* num_arcs_dev, const int* num_nodes_dev,
+                                  const float* arc_weights_dev, int A, int max_states, int max_edges,
+                                  const float* weights_dev, float* grad_em_dev, float* grad_table_dev,
+                                  float* arc_grad_dev) {
+  GTNX_HOST_T("batch.asg_lattice_score_grad");
+  asg_lattice_impl("gtnx_batch_asg_lattice_score_grad", ems, frames, table_dev,
+                   {arcs_dev, row_stride, num_arcs_dev, num_nodes_dev, arc_weights_dev, A, max_states}, max_edges, nullptr,
+                   weights_dev, grad_em_dev, grad_table_dev, arc_grad_dev);
 }
 
 // ---- batched ASG token alignment of device-resident hypotheses (asg_token_align.hip) ----

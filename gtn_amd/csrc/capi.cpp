@@ -1139,6 +1139,37 @@ GTNX_API gtnx_status_t gtnx_batch_asg_score_grad(gtnx_batch_t ems, const int* fr
 GTNX_API gtnx_status_t gtnx_batch_asg_score_stats(int64_t* calls, int64_t* pairs) {
   return guard([&] { batch_asg_score_stats(calls, pairs); });
 }
+GTNX_API gtnx_status_t gtnx_batch_asg_lattice_score(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                                    const void* arcs_device, int64_t row_stride,
+                                                    const void* num_arcs_device, const void* num_nodes_device,
+                                                    const void* arc_weights_device, int A, int max_states,
+                                                    int max_edges, void* scores_device) {
+  return guard([&] {
+    batch_asg_lattice_score(BH(ems), frames, static_cast<const float*>(table_device),
+                            static_cast<const int*>(arcs_device), row_stride, static_cast<const int*>(num_arcs_device),
+                            static_cast<const int*>(num_nodes_device), static_cast<const float*>(arc_weights_device), A,
+                            max_states, max_edges, static_cast<float*>(scores_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_asg_lattice_score_grad(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                                         const void* arcs_device, int64_t row_stride,
+                                                         const void* num_arcs_device, const void* num_nodes_device,
+                                                         const void* arc_weights_device, int A, int max_states,
+                                                         int max_edges, const void* weights_device,
+                                                         void* grad_emissions_device, void* grad_table_device,
+                                                         void* arc_grad_device) {
+  return guard([&] {
+    batch_asg_lattice_score_grad(BH(ems), frames, static_cast<const float*>(table_device),
+                                 static_cast<const int*>(arcs_device), row_stride,
+                                 static_cast<const int*>(num_arcs_device), static_cast<const int*>(num_nodes_device),
+                                 static_cast<const float*>(arc_weights_device), A, max_states, max_edges,
+                                 static_cast<const float*>(weights_device), static_cast<float*>(grad_emissions_device),
+                                 static_cast<float*>(grad_table_device), static_cast<float*>(arc_grad_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_asg_lattice_score_stats(int64_t* calls, int64_t* utterances) {
+  return guard([&] { batch_asg_lattice_score_stats(calls, utterances); });
+}
 GTNX_API gtnx_status_t gtnx_batch_asg_token_align(gtnx_batch_t ems, const int* frames, const void* table_device,
                                                   const void* tokens_device, int64_t row_stride,
                                                   const void* lengths_device, int N, int L, int max_length,

@@ -1104,6 +1104,49 @@ void launch_asg_score_forward(const AsgScoreArgs& a, hipStream_t st);
 void launch_asg_score_backward(const AsgScoreArgs& a, hipStream_t st);
 void launch_asg_score_scatter(const AsgScoreArgs& a, hipStream_t st);
 void launch_asg_score_table(const AsgScoreArgs& a, hipStream_t st);
+// asg_lattice.hip: the ASG log score of the utterances utt0 .. utt0 + count - 1, each with one acyclic token lattice of its
+// own in device memory (ctc_lattice.hip's form), under asg_score.hip's [C + C * C] table, and the gradients g[b] * d
+// score[b] / d (emissions_b, table, arc weights of b) (the contract: DESIGN section 37).  The states are the arcs; an
+// edge (a' -> a), dst a' == src a, pays w_a + table[C + lab a * C + lab a'].
+//   forward:  one workgroup per utterance; scores[b - score0] = the score (-inf: T_b == 0, K < 1, K + arcs > SM, more
+//             than max_edges edges, an arc that is none, a weight that is +inf or NaN, no alignment).  With `alpha`
+//             non-null the alpha row of every frame also goes to alpha[(b - utt0) * utt_stride + t * SM + a].
+//   backward: one workgroup per utterance zeroes grad[b] and arc_grad[b] (those asked for), then writes weights[b] times
+//             the occupancies summed per label in a fixed order by plain stores.  With `edge` non-null the occupancy of
+//             every edge is summed over the frames in edge[(b - utt0) * max_edges + off a + k] (k-th arc entering src a);
+//             with `occ` / `csr` non-null occ[(b - utt0) * 2 SM + a] = weights[b] * the self sum, [.. + SM + a] the start
+//             term, csr[(b - utt0) * 3 SM + a] = off a, [.. + SM + a] the first arc entering src a, [.. + 2 SM + a] how
+//             many.
+//   table:    behind the backward of the same utterances; workgroup i < C owns row i of the transitions, workgroup C the
+//             start entries.  It walks the utterances in order and the arcs ascending, adding one value at a time into
+//             an LDS row that starts from zeros (table_first) or from what grad_table holds, and stores the row whole.
+// The workgroup's width and the arcs per lane are chosen from SM = max_states alone (asg_lattice_config).
+constexpr int kAsgLatticeMaxStates = 4096;
+constexpr int kAsgLatticeMaxEdges = 1 << 21;
+struct AsgLatticeArgs {
+  const GTNX_G float* em;           // [n][M][C]
+  const GTNX_G int* frames;         // [n]
+  const GTNX_G float* table;        // [C + C * C]
+  const GTNX_G int* arcs;           // utterance b's row at arcs + b * row_stride
+  const GTNX_G int* num_arcs;       // [n]
+  const GTNX_G int* num_nodes;      // [n]
+  const GTNX_G float* arc_weights;  // [n][A] or null: all zeros
+  GTNX_G float* scores;             // [.. - score0]
+  GTNX_G float* alpha;              // [count][utt_stride] or null (forward)
+  const GTNX_G float* weights;      // [n] (backward, table)
+  GTNX_G float* grad;               // [n][M][C] or null (backward)
+  GTNX_G float* arc_grad;           // [n][A] or null (backward)
+  GTNX_G float* grad_table;         // [C + C * C] (table)
+  GTNX_G float* edge;               // [count][max_edges] or null (backward); read by table
+  GTNX_G float* occ;                // [count][2][SM] or null (backward); read by table
+  GTNX_G int* csr;                  // [count][3][SM] or null (backward); read by table
+  int64_t row_stride, utt_stride;
+  int utt0, score0, count, A, SM, M, C, max_edges, table_first;
+};
+void asg_lattice_config(int max_states, int* width, int* per_lane);  // the workgroup's width, the arcs a lane owns
+void launch_asg_lattice_forward(const AsgLatticeArgs& a, hipStream_t st);
+void launch_asg_lattice_backward(const AsgLatticeArgs& a, hipStream_t st);
+void launch_asg_lattice_table(const AsgLatticeArgs& a, hipStream_t st);
 // ctc_token_align.hip: the best alignment (max-plus, the arithmetic and the tie rule of align.hip) of the pairs pair0 ..
 // pair0 + count - 1 of ctc_score.hip's hypothesis form (the contract: DESIGN section 24).  One workgroup per pair, width
 // and states per lane from ctc_score_config(U); row p of every output is written over its whole width: scores[p] the

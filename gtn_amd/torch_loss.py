@@ -1,7 +1,7 @@
 """PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
 `asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_sample`, `ctc_beam_decode`, `asg_beam_decode`, `asg_sample`,
-`edit_distance`, `ctc_score`, `ctc_lattice_score`, `ctc_lattice_loss`, `ctc_token_align`, `asg_score` and
-`asg_token_align`.
+`edit_distance`, `ctc_score`, `ctc_lattice_score`, `ctc_lattice_loss`, `ctc_token_align`, `asg_score`,
+`asg_lattice_score`, `asg_full_connect`, `asg_lattice_loss` and `asg_token_align`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -44,6 +44,9 @@ _ARGTYPES = {
     "gtn_ctc_token_align_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gtn_asg_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "gtn_asg_lattice_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "gtn_asg_lattice_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "gtn_asg_full_connect_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gtn_asg_beam_decode_n": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P],
     "gtn_asg_sample_n": [_P, _I, _I, _I, _P, _P, _I, C.c_uint64, _F, _P, _P, _P, _P, _P],
     "gtn_asg_beam_decode_graph_n": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _F, _F, _P, _P, _P, _P],
@@ -1210,6 +1213,229 @@ def asg_score(emissions, transitions, tokens, lengths, start=None, input_lengths
         start = torch.zeros(C_, dtype=torch.float32, device=emissions.device)
     out = _ASGScore.apply(emissions, transitions, start, tok, ln, frames, max_length)
     return out.reshape(B) if flat else out
+
+
+class _ASGLatticeScore(torch.autograd.Function):
+    """forward: one launch that stores nothing but the scores; backward: the one gradient call with grad_out as the
+    weights, asked for the emission, table and arc gradients as requires_grad says.  The node keeps tensors only."""
+
+    @staticmethod
+    def forward(ctx, emissions, transitions, start, arc_weights, arcs, num_arcs, num_nodes, frames, max_states, max_edges):
+        B, A = arcs.shape[:2]
+        x = emissions.detach().contiguous()
+        table = _asg_weights(start, transitions)
+        w = None if arc_weights is None else arc_weights.detach().to(torch.float32).contiguous()
+        stream = _engine_stream(x.device)
+        scores = torch.empty(B, dtype=torch.float32, device=x.device)
+        if B == 0:
+            _engine_done(stream)  # (no utterance: nothing to launch, and an empty tensor has no address to hand over)
+        else:
+            _route(stream, x, _has_native("asg_lattice_score", "gtn_asg_lattice_score_n"), "gtn_asg_lattice_score_n",
+                   (table.data_ptr(), _host_ptr(frames), arcs.data_ptr(), num_arcs.data_ptr(), num_nodes.data_ptr(),
+                    _ptr(w), A, max_states, max_edges, scores.data_ptr()),
+                   "asg_lattice_score", table.data_ptr(), arcs.data_ptr(), num_arcs.data_ptr(), num_nodes.data_ptr(),
+                   scores.data_ptr(), _ptr(w), frames, max_states, max_edges, A=A, row_stride=3 * A)
+        ctx.save_for_backward(x, table, arcs, num_arcs, num_nodes, *(() if w is None else (w,)))
+        ctx.args = (frames, max_states, max_edges, transitions.dtype, start.dtype,
+                    None if arc_weights is None else arc_weights.dtype)
+        return scores
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, table, arcs, num_arcs, num_nodes, *rest = ctx.saved_tensors
+        w = rest[0] if rest else None
+        frames, max_states, max_edges, tr_dtype, st_dtype, w_dtype = ctx.args
+        B, T, C_ = x.shape
+        A = arcs.shape[1]
+        want_em = ctx.needs_input_grad[0]
+        want_table = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        want_w = w is not None and ctx.needs_input_grad[3]
+        none = (None,) * 6
+        if not (want_em or want_table or want_w):
+            return (None,) * 4 + none
+        grad = torch.empty(B, T, C_, dtype=torch.float32, device=x.device) if want_em else None
+        g_table = torch.empty(C_ + C_ * C_, dtype=torch.float32, device=x.device) if want_table else None
+        garc = torch.empty(B, A, dtype=torch.float32, device=x.device) if want_w else None
+        if B == 0 or x.numel() == 0:
+            for g in (grad, g_table, garc):
+                if g is not None:
+                    g.zero_()
+        else:
+            g = grad_out.detach().to(torch.float32).contiguous()
+            _route(_engine_stream(x.device), x, _native(), "gtn_asg_lattice_score_grad_n",
+                   (table.data_ptr(), _host_ptr(frames), arcs.data_ptr(), num_arcs.data_ptr(), num_nodes.data_ptr(),
+                    _ptr(w), A, max_states, max_edges, g.data_ptr(), _ptr(grad), _ptr(g_table), _ptr(garc)),
+                   "asg_lattice_score_grad", table.data_ptr(), arcs.data_ptr(), num_arcs.data_ptr(),
+                   num_nodes.data_ptr(), g.data_ptr(), _ptr(grad), _ptr(g_table), _ptr(garc), _ptr(w), frames,
+                   max_states, max_edges, A=A, row_stride=3 * A)
+        g_tr = g_table[C_:].reshape(C_, C_).to(tr_dtype) if ctx.needs_input_grad[1] else None
+        g_st = g_table[:C_].to(st_dtype) if ctx.needs_input_grad[2] else None
+        return (grad, g_tr, g_st, garc.to(w_dtype) if want_w else None) + none
+
+
+def asg_lattice_score(emissions, transitions, arcs, num_arcs, num_nodes, arc_weights=None, start=None,
+                      input_lengths=None, max_states=None, max_edges=None):
+    """The exact ASG log score of one acyclic token lattice per utterance, differentiable: score[b] = log sum over the
+    lattice's paths p of exp(w(p) + asg_score(emissions[b, :T_b], transitions, labels(p))) -- every word-piece
+    decomposition, pronunciation or optional token the lattice holds and every alignment of each, marginalised in one
+    launch; the lattices are read where they lie on the device.  Nothing is subtracted (`asg_lattice_loss` does that).
+    emissions: float32 CUDA tensor [B, T, C] (any scores), read in place; transitions: [C, C] with transitions[i, j] the
+    score of label j followed by label i; start: [C] scores of the first label (zeros when omitted); arcs, num_arcs,
+    num_nodes, arc_weights and input_lengths are those of `ctc_lattice_score` (arcs sorted by dst; `gtn_amd.pack_lattices`
+    gives this form) -- the states are the arcs: there is no blank and equal neighbouring labels are legal, as in
+    `asg_score`.  max_states (1 .. 4096, default min(2 A + 1, 4096)): the caller's bound on nodes + arcs, the same
+    argument as for `ctc_lattice_score`; max_edges (1 .. 2^21, default min(8 * max_states, 2^21)): the caller's bound on
+    the edges, the sum over the arcs of the in-degree of their src -- the lattices live on the device and the backward
+    sizes its scratch by this bound without a download.  At most 16384 labels.
+    Returns float32 [B].  A score is -inf, with zero gradients and never NaN, when T_b == 0, num_nodes < 1, nodes + arcs
+    > max_states, the lattice has more edges than max_edges, an arc or a weight is invalid as for `ctc_lattice_score`,
+    no alignment fits (a one-node lattice has none: ASG has no empty alignment), or every alignment crosses a -inf
+    emission, transition or start score.
+    The backward is one call with grad_out as per-utterance weights; it returns gradients for emissions, transitions,
+    start and arc_weights (grad_out[b] times the posterior of every arc), computes only those that require grad,
+    recomputes what it needs and sums in a fixed order without atomics, so it has the same bits run to run.  Without
+    requires_grad it never launches.  Runs on the caller's stream."""
+    who = "asg_lattice_score"
+    x = emissions
+    if not (torch.is_tensor(x) and x.dim() == 3 and x.dtype == torch.float32):
+        raise ValueError(f"{who}: emissions must be a float32 tensor [B, T, C]")
+    B, T, C_ = x.shape
+    if not (torch.is_tensor(transitions) and tuple(transitions.shape) == (C_, C_)):
+        raise ValueError(f"{who}: transitions must be [{C_}, {C_}]")
+    if start is not None and not (torch.is_tensor(start) and tuple(start.shape) == (C_,)):
+        raise ValueError(f"{who}: start must be [{C_}]")
+    if C_ < 1 or C_ > 16384:
+        raise ValueError(f"{who}: the number of labels must be 1 .. 16384")
+    if not (torch.is_tensor(arcs) and arcs.dtype == torch.int32 and arcs.dim() == 3 and arcs.shape[0] == B
+            and arcs.shape[2] == 3):
+        raise ValueError(f"{who}: arcs must be an int32 tensor [B, A, 3] for a batch of {B}")
+    A = arcs.shape[1]
+    for t, name in ((num_arcs, "num_arcs"), (num_nodes, "num_nodes")):
+        if not (torch.is_tensor(t) and t.dtype in (torch.int32, torch.int64) and tuple(t.shape) == (B,)):
+            raise ValueError(f"{who}: {name} must be an int32 or int64 tensor [{B}]")
+    if arc_weights is not None and not (torch.is_tensor(arc_weights) and arc_weights.is_floating_point()
+                                        and tuple(arc_weights.shape) == (B, A)):
+        raise ValueError(f"{who}: arc_weights must be a floating-point tensor [{B}, {A}]")
+    max_states = max(1, min(2 * A + 1, 4096)) if max_states is None else int(max_states)
+    if not 1 <= max_states <= 4096:
+        raise ValueError(f"{who}: max_states outside 1 .. 4096")
+    max_edges = min(8 * max_states, 1 << 21) if max_edges is None else int(max_edges)
+    if not 1 <= max_edges <= 1 << 21:
+        raise ValueError(f"{who}: max_edges outside 1 .. 2^21")
+    frames = None if input_lengths is None else _frame_counts(who, input_lengths, B, T, 0)
+    for t, what in ((x, "emissions"), (transitions, "transitions"), (start, "start"), (arcs, "arcs"),
+                    (num_arcs, "num_arcs"), (num_nodes, "num_nodes"), (arc_weights, "arc_weights")):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {what} must be a CUDA tensor (the scores are computed on the device)")
+        if t.device != x.device:
+            raise ValueError(f"{who}: all tensors must be on one device")
+    if start is None:
+        start = torch.zeros(C_, dtype=torch.float32, device=x.device)
+    arcs_c = arcs.detach().contiguous()
+    na = num_arcs.detach().to(torch.int32).contiguous()  # (int64 counts are converted on the device)
+    nn_ = num_nodes.detach().to(torch.int32).contiguous()
+    if A == 0:
+        # (an empty tensor has no address to hand over: one row that no count reaches stands in for none)
+        out = _ASGLatticeScore.apply(x, transitions, start, None, arcs_c.new_zeros(B, 1, 3), torch.zeros_like(na), nn_,
+                                     frames, max_states, max_edges)
+        return out if arc_weights is None else out + (arc_weights.sum() * 0).to(out.dtype)  # (a gradient of zeros)
+    return _ASGLatticeScore.apply(x, transitions, start, arc_weights, arcs_c, na, nn_, frames, max_states, max_edges)
+
+
+class _ASGFullConnect(torch.autograd.Function):
+    """the full-connect half of _ASGLoss: the gradients come with the forward, for unit seeds"""
+
+    @staticmethod
+    def forward(ctx, emissions, transitions, start, reduction, frames):
+        B, T, N = emissions.shape
+        lib = _native()
+        if not lib or not hasattr(lib, "gtn_asg_full_connect_n"):
+            raise RuntimeError("asg_full_connect needs gtn_asg_full_connect_n in gtn_amd/lib/libgtn_criteria.so "
+                               "(run __graft_entry__.build())")
+        x = emissions.detach().contiguous()
+        w = _asg_weights(start, transitions)
+        stream = _engine_stream(x.device)
+        out = torch.empty(B, dtype=torch.float32, device=x.device)
+        gem = torch.empty(B, T, N, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[0] else None
+        need_tr = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        gtr = torch.empty(N + N * N, dtype=torch.float32, device=x.device) if need_tr else None
+        if B == 0:
+            if gtr is not None:
+                gtr.zero_()
+        else:
+            _call("gtn_asg_full_connect_n", x.data_ptr(), B, T, N, w.data_ptr(), _host_ptr(frames), out.data_ptr(),
+                  _ptr(gem), _ptr(gtr))
+        _engine_done(stream)
+        ctx.grads = (gem, gtr)
+        ctx.shape = (B, T, N)
+        ctx.reduction = reduction
+        ctx.dtypes = (transitions.dtype, start.dtype)
+        return out.mean() if reduction == "mean" else (out.sum() if reduction == "sum" else out)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        B, T, N = ctx.shape
+        gem, gtr = ctx.grads
+        if ctx.reduction == "none":
+            # the table gradient was summed over the batch with unit seeds: per-utterance seeds must be uniform
+            scale_em = grad_out.reshape(B, 1, 1)
+            scale_tr = grad_out.reshape(-1)[0] if gtr is not None and B else None
+            if gtr is not None and B and not bool((grad_out == grad_out.reshape(-1)[0]).all()):
+                raise RuntimeError("asg_full_connect(reduction='none'): transition gradients need a uniform upstream "
+                                   "gradient; use reduction='sum' or 'mean'")
+        else:
+            scale_em = (grad_out / B if ctx.reduction == "mean" else grad_out).reshape(1, 1, 1)
+            scale_tr = scale_em.reshape(())
+        g_em = gem * scale_em if gem is not None and ctx.needs_input_grad[0] else None
+        g_tr = g_st = None
+        if gtr is not None:
+            scaled = gtr * scale_tr if scale_tr is not None else gtr
+            g_st = scaled[:N].to(ctx.dtypes[1]) if ctx.needs_input_grad[2] else None
+            g_tr = scaled[N:].reshape(N, N).to(ctx.dtypes[0]) if ctx.needs_input_grad[1] else None
+        return g_em, g_tr, g_st, None, None
+
+
+def asg_full_connect(emissions, transitions, start=None, input_lengths=None, reduction="none"):
+    """The full-connect term of the ASG criterion on its own, differentiable: score[b] = forwardScore(emissions[b, :T_b] o
+    transitions), the log-sum over every label sequence and every alignment -- the normaliser `asg_loss` subtracts its
+    force-align term from, for criteria with another numerator (`asg_lattice_loss`).  `asg_loss(x, tr, [y]) ==
+    asg_full_connect(x, tr) - asg_score(x, tr, y)`.  It runs the launches `asg_loss` runs for this term and has its
+    rules: emissions float32 CUDA [B, T, C]; transitions [C, C]; start [C] or None (zeros); input_lengths: frame counts
+    1 .. T or None; reduction "none", "sum" or "mean".  The transitions and start gradients are summed over the batch
+    with unit seeds, so under reduction="none" they need a uniform upstream gradient (a RuntimeError otherwise)."""
+    who = "asg_full_connect"
+    x = emissions
+    if not (torch.is_tensor(x) and x.dim() == 3 and x.dtype == torch.float32):
+        raise ValueError(f"{who}: emissions must be a float32 tensor [B, T, C]")
+    B, T, C_ = x.shape
+    if not (torch.is_tensor(transitions) and tuple(transitions.shape) == (C_, C_)):
+        raise ValueError(f"{who}: transitions must be [{C_}, {C_}]")
+    if start is not None and not (torch.is_tensor(start) and tuple(start.shape) == (C_,)):
+        raise ValueError(f"{who}: start must be [{C_}]")
+    if reduction not in ("none", "sum", "mean"):
+        raise ValueError(f"{who}: reduction must be 'none', 'sum' or 'mean'")
+    frames = None if input_lengths is None else _frame_counts(who, input_lengths, B, T, 1)
+    for t, what in ((x, "emissions"), (transitions, "transitions"), (start, "start")):
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{who}: {what} must be a CUDA tensor (the scores are computed on the device)")
+    if start is None:
+        start = torch.zeros(C_, dtype=torch.float32, device=x.device)
+    return _ASGFullConnect.apply(x, transitions, start, reduction, frames)
+
+
+def asg_lattice_loss(emissions, transitions, arcs, num_arcs, num_nodes, arc_weights=None, start=None,
+                     input_lengths=None, max_states=None, max_edges=None):
+    """The ASG criterion whose target is a token lattice: loss[b] = asg_full_connect(...)[b] - asg_lattice_score(...)[b],
+    float32 [B], differentiable in emissions, transitions, start and arc_weights -- the negative log-likelihood of the
+    lattice, marginalised over its paths (weighted by exp of their arc weights) and their alignments.  For a chain
+    lattice without weights this is `asg_loss`.  +inf where the score is -inf.  The arguments are those of
+    `asg_lattice_score`, except that the frame counts are 1 .. T (the full-connect term's rule).  The full-connect term's
+    table gradient needs a uniform upstream gradient: reduce the losses with .sum() or .mean()."""
+    score = asg_lattice_score(emissions, transitions, arcs, num_arcs, num_nodes, arc_weights, start, input_lengths,
+                              max_states, max_edges)
+    return asg_full_connect(emissions, transitions, start, input_lengths) - score
 
 
 def ctc_token_align(log_probs, tokens, lengths, blank=0, input_lengths=None, max_length=None, return_token_scores=False,

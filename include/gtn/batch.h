@@ -362,6 +362,32 @@ inline void asgScoreGrad(const Batch& ems, const float* tableDevice, const int* 
   detail::check(gtnx_batch_asg_score_grad(ems.handle(), frames, tableDevice, tokensDevice, rowStride, lengthsDevice, N,
                                           L, maxLength, weightsDevice, gradEmissionsDevice, gradTableDevice));
 }
+/** The exact ASG log score of one device-resident acyclic token lattice per utterance (ctcLatticeScore's lattices) under
+ *  the slabs of a Batch::linear and asgScore's table, results left on the device: scoresDevice[b] = log sum over the
+ *  lattice's paths p of exp(w(p) + asgScore(emissions_b[0 .. T_b), table, labels(p))), nothing subtracted.  The states
+ *  are the arcs: no blank, equal neighbours legal.  maxStates 1 .. 4096 bounds nodes + arcs (the CTC call's argument),
+ *  maxEdges 1 .. 2^21 bounds the sum over the arcs of the in-degree of their src; lattices above either score -inf, as
+ *  do invalid ones, T_b == 0 and a lattice without an alignment (one node included).  One launch, no copy back, no wait
+ *  -- gtnx_batch_asg_lattice_score */
+inline void asgLatticeScore(const Batch& ems, const float* tableDevice, const int* arcsDevice, int64_t rowStride,
+                            const int* numArcsDevice, const int* numNodesDevice, const float* arcWeightsDevice, int A,
+                            int maxStates, int maxEdges, float* scoresDevice, const int* frames = nullptr) {
+  detail::check(gtnx_batch_asg_lattice_score(ems.handle(), frames, tableDevice, arcsDevice, rowStride, numArcsDevice,
+                                             numNodesDevice, arcWeightsDevice, A, maxStates, maxEdges, scoresDevice));
+}
+/** The gradients of asgLatticeScore under the weights weightsDevice [n], each output nullable but not all three:
+ *  gradEmissionsDevice float32 [n][M][C], gradTableDevice float32 [C + C * C], arcGradDevice float32 [n][A] (the arcs'
+ *  posteriors times the weight, zeros past numArcs); every element of an output is written.  Stateless (alpha rows and
+ *  one cell per edge in pooled scratch, sliced beyond 256 MiB) and bit-repeatable (fixed summation order, no atomics)
+ *  -- gtnx_batch_asg_lattice_score_grad */
+inline void asgLatticeScoreGrad(const Batch& ems, const float* tableDevice, const int* arcsDevice, int64_t rowStride,
+                                const int* numArcsDevice, const int* numNodesDevice, const float* arcWeightsDevice, int A,
+                                int maxStates, int maxEdges, const float* weightsDevice, float* gradEmissionsDevice,
+                                float* gradTableDevice, float* arcGradDevice, const int* frames = nullptr) {
+  detail::check(gtnx_batch_asg_lattice_score_grad(ems.handle(), frames, tableDevice, arcsDevice, rowStride,
+                                                  numArcsDevice, numNodesDevice, arcWeightsDevice, A, maxStates, maxEdges,
+                                                  weightsDevice, gradEmissionsDevice, gradTableDevice, arcGradDevice));
+}
 /** numSamples alignments of every chain of a Batch::linear drawn from the posterior of emissions o transitions (forward
  *  filtering, backward sampling; inverse CDF in label order, Philox4x32-10 keyed by `seed`), plus the merge of equal
  *  neighbours, results left on the device: tableDevice float32 [C + C * C] (start scores, then arc C + i * C + j = j ->

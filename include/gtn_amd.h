@@ -731,6 +731,55 @@ gtnx_status_t gtnx_batch_asg_score_grad(gtnx_batch_t ems, const int* frames, con
                                         void* grad_emissions_device, void* grad_table_device);
 /* calls of either kind that have launched so far (process-wide) / pairs they took */
 gtnx_status_t gtnx_batch_asg_score_stats(int64_t* calls, int64_t* pairs);
+/* The exact ASG log score of ONE ACYCLIC TOKEN LATTICE PER UTTERANCE -- gtnx_batch_ctc_lattice_score's lattices under
+ * gtnx_batch_asg_score's criterion:
+ *   scores[b] = log sum over the lattice's paths p of exp(w(p) + asg_score(emissions_b[0 .. T_b), table, labels(p))),
+ * every decomposition and every alignment at once, nothing subtracted.  table_device: float32 [C + C * C], entry c =
+ * start[c], entry C + i * C + j = transitions[i][j] (label j followed by label i).  The lattice arguments are those of
+ * gtnx_batch_ctc_lattice_score with the same meaning: arcs (src, dst, label) with 0 <= src < dst < num_nodes, dst-sorted,
+ * node 0 starts, the last node accepts, arc_weights added once per use of the arc, -inf forbids it.  The states are the
+ * arcs: one token state per arc, NO blank states, equal neighbouring labels are legal.  Float32, in this order:
+ *   frame 0: alpha[a] = (w_a + table[lab a]) + e(0, lab a) for src a == 0, -inf otherwise
+ *   frame t: x = alpha[a] + table[C + lab a * C + lab a]; for a' entering src a, ascending:
+ *            x = logadd(x, alpha[a'] + (w_a + table[C + lab a * C + lab a'])); alpha'[a] = x + e(t, lab a)
+ *   score = logadd over the arcs entering the last node, ascending.
+ * max_states (1 .. 4096) is the caller's bound on nodes + arcs, exactly as for the CTC call, so the same lattices and
+ * the same argument serve both criteria.  max_edges (1 .. 2^21) is the caller's bound on E_b = the sum over the arcs of
+ * the in-degree of their src; the kernel counts E_b when it stages the lattice (the gradient call sizes its scratch by
+ * the bound without a download).  The score is -inf -- never NaN, and without a gradient -- when T_b == 0, num_nodes <
+ * 1, nodes + clamp(num_arcs) > max_states, E_b > max_edges, any arc field gtnx_batch_ctc_lattice_score refuses, a weight
+ * that is +inf or NaN, no alignment fits (a one-node lattice has none: ASG has no empty alignment), or every alignment
+ * passes a -inf emission, start or transition entry.  Every arc field is checked before it becomes an address or an
+ * index; nothing at or past num_arcs[b] is read.  At most 16384 labels; table indices are computed in 64 bits.
+ * GTNX_INVALID_ARGUMENT before a device is asked for: a null batch, table, arcs, num_arcs, num_nodes or scores pointer,
+ * negative A, row_stride < 3 A, max_states outside 1 .. 4096, max_edges outside 1 .. 2^21.  A batch without an utterance
+ * returns without touching a device.  With the device: not a gtnx_batch_linear / _rows batch, a frame count outside
+ * 0 .. M, more than 16384 labels, a table that is not device memory, an output the current device may not write.
+ * One launch on the engine's stream (asg_lattice.hip), one workgroup per utterance, no scratch, no copy back, no wait. */
+gtnx_status_t gtnx_batch_asg_lattice_score(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                           const void* arcs_device, int64_t row_stride, const void* num_arcs_device,
+                                           const void* num_nodes_device, const void* arc_weights_device, int A,
+                                           int max_states, int max_edges, void* scores_device);
+/* The gradients of those scores for caller-supplied weights_device (float32 [n]; grad_out under autograd).  Each output
+ * may be null, not all three.  grad_emissions_device: float32 [n][M][C] = weights[b] * d scores[b] / d emissions[b];
+ * grad_table_device: float32 [C + C * C] = sum over b of weights[b] * d scores[b] / d table; arc_grad_device: float32
+ * [n][A] = weights[b] * the posterior probability that the arc is used.  EVERY element of an output is written: zeros
+ * where nothing lands, rows at or past T_b and arcs at or past num_arcs[b] included.  An utterance whose score is -inf
+ * or whose weight is exactly 0 adds nothing.  Stateless: alpha is recomputed into scratch from the stream-ordered pool
+ * (max_b T_b * max_states floats per utterance; with a table or arc gradient max_edges floats per utterance on top, one
+ * cell per edge), at most 256 MiB per launch group; beyond that the utterances run in slices, bit-equal to the unsliced
+ * run (GTNX_ASG_LATTICE_SCRATCH_BYTES, read per call, lowers the cap: a debug switch for tests).  Every sum has one
+ * order -- a label's arcs ascending, an arc's frames descending, an edge's frames descending in its own cell, a table
+ * row's utterances, arcs and edges ascending, one value at a time -- and every store is a plain store: the same bits run
+ * to run; there are no floating-point atomics. */
+gtnx_status_t gtnx_batch_asg_lattice_score_grad(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                                const void* arcs_device, int64_t row_stride,
+                                                const void* num_arcs_device, const void* num_nodes_device,
+                                                const void* arc_weights_device, int A, int max_states, int max_edges,
+                                                const void* weights_device, void* grad_emissions_device,
+                                                void* grad_table_device, void* arc_grad_device);
+/* calls of either kind that have launched so far (process-wide) / utterances they took */
+gtnx_status_t gtnx_batch_asg_lattice_score_stats(int64_t* calls, int64_t* utterances);
 /* The best ASG alignment of those hypotheses: WHEN each token was spoken and how well the frames support it, for all
  * n * N pairs in one call, results left on the device (DESIGN section 28 holds the contract).  The inputs are those of
  * gtnx_batch_asg_score with the same meaning: pair (b, k) is y = tokens[b][k][0 .. len), len = clamp(lengths[b][k], 0,
