@@ -78,6 +78,7 @@ edit_distance = _api.edit_distance  # (batched Levenshtein distance of device-re
 debug_edit_distance_stats = _api.debug_edit_distance_stats  # (edit_distance: calls that launched, pairs computed)
 debug_ctc_score_stats = _api.debug_ctc_score_stats  # (Batch.ctc_score / ctc_score_grad: calls that launched, pairs taken)
 debug_ctc_lattice_score_stats = _api.debug_ctc_lattice_score_stats  # (Batch.ctc_lattice_score / _grad: calls, utterances)
+debug_ctc_lattice_align_stats = _api.debug_ctc_lattice_align_stats  # (Batch.ctc_lattice_align: calls, utterances)
 debug_ctc_token_align_stats = _api.debug_ctc_token_align_stats  # (Batch.ctc_token_align: calls that launched, pairs aligned)
 debug_asg_token_align_stats = _api.debug_asg_token_align_stats  # (Batch.asg_token_align: calls that launched, pairs aligned)
 debug_asg_score_stats = _api.debug_asg_score_stats  # (Batch.asg_score / asg_score_grad: calls that launched, pairs taken)

@@ -165,6 +165,10 @@ _SIGS = {
     "gtnx_batch_ctc_lattice_score_grad": [c_graph, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "gtnx_batch_ctc_lattice_score_stats": [c_i64_p, c_i64_p],
+    "gtnx_batch_ctc_lattice_align": [c_graph, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64],
+    "gtnx_batch_ctc_lattice_align_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_ctc_token_align": [c_graph, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int,
                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                    C.c_int64],

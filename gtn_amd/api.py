@@ -1270,6 +1270,68 @@ def make_api(lib):
                                                         _opt_ptr(arc_weights), A, SM, _opt_ptr(weights),
                                                         _opt_ptr(grad_out), _opt_ptr(arc_grad_out)))
 
+        def ctc_lattice_align(self, arcs, num_arcs, num_nodes, scores_out, path_len_out, path_arcs_out,
+                              path_tokens_out, starts_out, ends_out, token_scores_out=None, frame_arcs_out=None,
+                              arc_weights=None, frames=None, blank=0, max_states=None, A=None, row_stride=None, P=None,
+                              out_stride=None, frame_stride=None):
+            """The best (lattice path, alignment) pair of one device-resident token lattice per utterance under the
+            slabs of a Batch.linear, results left on the device (gtnx_batch_ctc_lattice_align; DESIGN section 38 holds
+            the contract).  `arcs`, `num_arcs`, `num_nodes`, `arc_weights`, `frames`, `blank`, `max_states`, A and
+            row_stride are those of `ctc_lattice_score`.  `scores_out` float32 [B]: the best w(p) + alignment score, -inf
+            without a path; `path_len_out` int32 [B]: the arcs on the best path; `path_arcs_out` / `path_tokens_out` /
+            `starts_out` / `ends_out` int32 [B, P]: the arc indices in path order, their labels, the first frame of each
+            and one past its last, -1 from path_len on and without a path (a path longer than P keeps its length and
+            writes its first P); `token_scores_out` float32 [B, P] or None: the arc's emissions summed in frame order;
+            `frame_arcs_out` int32 [B, M] or None: the arc of every frame, -1 on blank frames and from T_b on.  Tensors
+            need contiguous, equally spaced rows (views of wider tensors are fine: only the widths P and M are
+            written); device addresses go with P, `out_stride` (>= P, default P) and `frame_stride` (>= M, default M).
+            Float32 max-plus, of equal candidates the first in the forward's order: the same bits every time.  No copy
+            back and no wait."""
+            who = "ctc_lattice_align"
+            fr, A, stride, SM = self._ctc_lattice_args(who, arcs, num_arcs, num_nodes, arc_weights, frames, A,
+                                                       row_stride, max_states)
+            n = len(self)
+
+            def rows_of(t, name, dtype, width, given):
+                """(width, row stride) of an output: those of a tensor [B, width], else what was given"""
+                if t is None or not hasattr(t, "data_ptr"):
+                    return width, given
+                if str(t.dtype) != dtype or t.dim() != 2 or t.shape[0] != n or (width is not None
+                                                                                 and t.shape[1] != width):
+                    raise ValueError(f"{who}: {name} must be a {dtype[6:]} tensor [B, {'M' if name == 'frame_arcs_out' else 'P'}]")
+                if t.shape[1] > 1 and t.stride(1) != 1:
+                    raise ValueError(f"{who}: {name} must have contiguous rows")
+                rows = t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
+                if given is not None and int(given) != int(rows):
+                    raise ValueError(f"{who}: the outputs must have one row stride ({name} has {rows}, not {given})")
+                return t.shape[1], rows
+            P = None if P is None else int(P)
+            for t, name, dtype in ((path_arcs_out, "path_arcs_out", "torch.int32"),
+                                   (path_tokens_out, "path_tokens_out", "torch.int32"),
+                                   (starts_out, "starts_out", "torch.int32"), (ends_out, "ends_out", "torch.int32"),
+                                   (token_scores_out, "token_scores_out", "torch.float32")):
+                P, out_stride = rows_of(t, name, dtype, P, out_stride)
+            _, frame_stride = rows_of(frame_arcs_out, "frame_arcs_out", "torch.int32", None, frame_stride)
+            if P is None:
+                raise ValueError(f"{who}: device addresses need P")
+            if out_stride is None:
+                out_stride = P
+            if frame_stride is None:
+                m, c = C.c_int(-1), C.c_int(-1)
+                check(lib.gtnx_batch_linear_shape(self._h, C.byref(m), C.byref(c)))
+                frame_stride = max(m.value, 0)
+            for o, dtype, name in ((scores_out, "torch.float32", "scores_out"), (path_len_out, "torch.int32", "path_len_out")):
+                if o is not None and hasattr(o, "data_ptr"):
+                    if str(o.dtype) != dtype or not o.is_contiguous() or o.numel() != n:
+                        raise ValueError(f"{who}: {name} must be a {dtype[6:]} contiguous tensor [B]")
+            check(lib.gtnx_batch_ctc_lattice_align(self._h, fr.ctypes.data if fr is not None else None, int(blank),
+                                                   _opt_ptr(arcs), stride, _opt_ptr(num_arcs), _opt_ptr(num_nodes),
+                                                   _opt_ptr(arc_weights), A, SM, _opt_ptr(scores_out),
+                                                   _opt_ptr(path_len_out), _opt_ptr(path_arcs_out),
+                                                   _opt_ptr(path_tokens_out), _opt_ptr(starts_out), _opt_ptr(ends_out),
+                                                   _opt_ptr(token_scores_out), int(P), int(out_stride),
+                                                   _opt_ptr(frame_arcs_out), int(frame_stride)))
+
         def _token_align_outputs(self, who, N, L, scores_out, starts_out, ends_out, token_scores_out, frame_tokens_out,
                                  out_stride, frame_stride):
             """What `ctc_token_align` and `asg_token_align` check of their outputs alike.  Returns (out_stride,
@@ -1767,6 +1829,11 @@ def make_api(lib):
         far and the utterances they took (include/gtn_amd.h: gtnx_batch_ctc_lattice_score_stats)"""
         return _stats2(lib.gtnx_batch_ctc_lattice_score_stats)
 
+    def debug_ctc_lattice_align_stats():
+        """(calls, utterances): calls of Batch.ctc_lattice_align that have launched so far and the utterances they took
+        (include/gtn_amd.h: gtnx_batch_ctc_lattice_align_stats)"""
+        return _stats2(lib.gtnx_batch_ctc_lattice_align_stats)
+
     def debug_asg_lattice_score_stats():
         """(calls, utterances): calls of Batch.asg_lattice_score / Batch.asg_lattice_score_grad that have launched so
         far and the utterances they took (include/gtn_amd.h: gtnx_batch_asg_lattice_score_stats)"""
@@ -1789,6 +1856,7 @@ def make_api(lib):
     ns.debug_ctc_score_stats = debug_ctc_score_stats
     ns.debug_ctc_token_align_stats = debug_ctc_token_align_stats
     ns.debug_ctc_lattice_score_stats = debug_ctc_lattice_score_stats
+    ns.debug_ctc_lattice_align_stats = debug_ctc_lattice_align_stats
     ns.debug_asg_score_stats = debug_asg_score_stats
     ns.debug_asg_lattice_score_stats = debug_asg_lattice_score_stats
     ns.debug_asg_token_align_stats = debug_asg_token_align_stats

@@ -184,6 +184,21 @@ GTN_EXPORT int gtn_ctc_lattice_score_grad_n(const void* emissions, int B, int T,
   });
 }
 
+// The best (lattice path, alignment) pair of one device-resident token lattice per utterance: the inputs of
+// gtn_ctc_lattice_score_n; scores: DEVICE float32 [B]; path_len: DEVICE int32 [B]; path_arcs / path_tokens / starts /
+// ends: DEVICE int32 [B][P]; token_scores: DEVICE float32 [B][P] or null; frame_arcs: DEVICE int32 [B][T] or null.
+GTN_EXPORT int gtn_ctc_lattice_align_n(const void* emissions, int B, int T, int C, int blank, const int* frames,
+                                       const void* arcs, const void* num_arcs, const void* num_nodes,
+                                       const void* arc_weights, int A, int max_states, int P, void* scores,
+                                       void* path_len, void* path_arcs, void* path_tokens, void* starts, void* ends,
+                                       void* token_scores, void* frame_arcs) {
+  return guarded([&] {
+    gtn::criteria::ctcLatticeAlignBatch(emissions, B, T, C, blank, frames, arcs, num_arcs, num_nodes, arc_weights, A,
+                                        max_states, P, scores, path_len, path_arcs, path_tokens, starts, ends,
+                                        token_scores, frame_arcs);
+  });
+}
+
 // The best alignment of B * N device-resident hypotheses.  emissions: DEVICE float32 [B][T][C]; frames: HOST int [B] or
 // null; tokens: DEVICE int32 [B][N][L]; lengths: DEVICE int32 [B][N]; scores: DEVICE float32 [B][N]; starts / ends: DEVICE
 // int32 [B][N][L]; token_scores: DEVICE float32 [B][N][L] or null; frame_tokens: DEVICE int32 [B][N][T] or null.

@@ -389,6 +389,42 @@ inline void ctcLatticeScoreBatch(
   }
 }
 
+/** The best (lattice path, alignment) pair of one device-resident token lattice per utterance under the B emission slabs
+ *  -- which decomposition the model chose and when each of its tokens was spoken: the inputs are those of
+ *  ctcLatticeScoreBatch; `scoresDev` device float32 [B]; `pathLenDev` device int32 [B]; `pathArcsDev` / `pathTokensDev` /
+ *  `startsDev` / `endsDev` device int32 [B][P] (dense rows); `tokenScoresDev` device float32 [B][P] or null;
+ *  `frameArcsDev` device int32 [B][T] or null.  gtnx_batch_ctc_lattice_align has the contract.  Nothing is copied
+ *  back. */
+inline void ctcLatticeAlignBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int C,
+    int blank,
+    const int* frames,
+    const void* arcsDev,
+    const void* numArcsDev,
+    const void* numNodesDev,
+    const void* arcWeightsDev,
+    int A,
+    int maxStates,
+    int P,
+    void* scoresDev,
+    void* pathLenDev,
+    void* pathArcsDev,
+    void* pathTokensDev,
+    void* startsDev,
+    void* endsDev,
+    void* tokenScoresDev = nullptr,
+    void* frameArcsDev = nullptr) {
+  Batch ems = Batch::linear(B, T, C, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  batched::ctcLatticeAlign(ems, static_cast<const int*>(arcsDev), 3 * int64_t(A), static_cast<const int*>(numArcsDev),
+                           static_cast<const int*>(numNodesDev), static_cast<const float*>(arcWeightsDev), A, maxStates,
+                           static_cast<float*>(scoresDev), static_cast<int*>(pathLenDev), static_cast<int*>(pathArcsDev),
+                           static_cast<int*>(pathTokensDev), static_cast<int*>(startsDev), static_cast<int*>(endsDev),
+                           static_cast<float*>(tokenScoresDev), P, P, static_cast<int*>(frameArcsDev), T, blank, frames);
+}
+
 /** The best alignment of B * N device-resident hypotheses under the B emission slabs -- when each token was spoken and
  *  how well the frames support it: `emissions` device float32 [B][T][C], read in place; `tokensDev` device int32
  *  [B][N][L] and `lengthsDev` device int32 [B][N] (dense rows, what ctcBeamDecodeBatch wrote); `frames` host [B] or null;

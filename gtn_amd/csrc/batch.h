@@ -358,6 +358,29 @@ void batch_ctc_lattice_score_grad(const BatchP& ems, const int* frames, int blan
                                   const float* arc_weights_dev, int A, int max_states, const float* weights_dev,
                                   float* grad_dev, float* arc_grad_dev);
 void batch_ctc_lattice_score_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
+// The best (lattice path, alignment) pair of one device-resident acyclic token lattice per utterance (the lattice
+// arguments, blank, frames and max_states of batch_ctc_lattice_score, with the same meaning), results on the device
+// (DESIGN section 38 holds the contract): scores_dev [n] the best w(p) + alignment score, path_len_dev [n] the arcs on the
+// best path, path_arcs_dev / path_tokens_dev / starts_dev / ends_dev (n rows of width P, out_stride apart) the arc
+// indices in path order, their labels, the first frame of each and one past its last (the first P of a longer path),
+// token_scores_dev (same layout, or null) the arc's emissions summed in frame order, frame_arcs_dev (n rows of width M,
+// frame_stride apart, or null) the arc of every frame, -1 on blank frames.  Float32 max-plus; of equal candidates the
+// first in the forward recurrence's order wins: bit-reproducible.  -1 / -inf wherever no path covers an entry (path_len
+// 0, score -inf); an utterance has no path where batch_ctc_lattice_score gives -inf.  Every element of every row is
+// written over its width, nothing beyond.
+// Invalid argument before a device is asked for: what batch_ctc_lattice_score refuses there, a null scores, path_len,
+// path_arcs, path_tokens, starts or ends pointer, P < 1, out_stride < P; n == 0 returns without a device.  With the
+// device: not a native linear batch, a frame count outside 0 .. M, blank >= C, frame_stride < M with frame arcs, an
+// output that is not memory of the current device.  The back-pointers (16 bits per state and frame, max T_b * max_states
+// of them per utterance) come from the stream-ordered pool, at most 256 MiB per launch
+// (GTNX_CTC_LATTICE_ALIGN_SCRATCH_BYTES lowers the cap: a debug switch); beyond it the utterances run in slices, same
+// bits.
+void batch_ctc_lattice_align(const BatchP& ems, const int* frames, int blank, const int* arcs_dev, int64_t row_stride,
+                             const int* num_arcs_dev, const int* num_nodes_dev, const float* arc_weights_dev, int A,
+                             int max_states, float* scores_dev, int* path_len_dev, int* path_arcs_dev,
+                             int* path_tokens_dev, int* starts_dev, int* ends_dev, float* token_scores_dev, int P,
+                             int64_t out_stride, int* frame_arcs_dev, int64_t frame_stride);
+void batch_ctc_lattice_align_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
 // The best alignment of all n * N device-resident hypotheses (the pair form of batch_ctc_score) under the n emission
 // slabs of a native linear batch, results on the device (DESIGN section 24 holds the contract): scores_dev [n][N] the
 // Viterbi score, starts_dev / ends_dev (n * N rows of width L, out_stride apart) the first frame of token i and one past

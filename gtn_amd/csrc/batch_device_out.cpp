@@ -1207,6 +1207,99 @@ void batch_ctc_lattice_score_grad(const BatchP& ems, const int* frames, int blan
                    weights_dev, grad_dev, arc_grad_dev);
 }
 
+// ---- batched CTC Viterbi alignment of one device-resident token lattice per utterance (ctc_lattice_align.hip) ----
+namespace {
+constexpr const char* kCtcLatticeAlign = "gtnx_batch_ctc_lattice_align";
+Counters g_ctc_lattice_align;  // (calls, utterances)
+// the back-pointers: an utterance that is above the cap by itself runs alone with scratch of its own size
+constexpr ScratchCap kCtcLatticeAlignScratch{"GTNX_CTC_LATTICE_ALIGN_SCRATCH_BYTES", int64_t(256) << 20};
+}  // namespace
+
+void batch_ctc_lattice_align_stats(int64_t* calls, int64_t* utterances) { g_ctc_lattice_align.get(calls, utterances); }
+
+void batch_ctc_lattice_align(const BatchP& ems, const int* frames, int blank, const int* arcs_dev, int64_t row_stride,
+                             const int* num_arcs_dev, const int* num_nodes_dev, const float* arc_weights_dev, int A,
+                             int max_states, float* scores_dev, int* path_len_dev, int* path_arcs_dev,
+                             int* path_tokens_dev, int* starts_dev, int* ends_dev, float* token_scores_dev, int P,
+                             int64_t out_stride, int* frame_arcs_dev, int64_t frame_stride) {
+  GTNX_HOST_T("batch.ctc_lattice_align");
+  const char* who = kCtcLatticeAlign;
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) refuse(who, "null batch");
+  if (!arcs_dev || !num_arcs_dev || !num_nodes_dev)
+    refuse(who, "null input pointer (arcs, num_arcs and num_nodes are all read)");
+  if (!scores_dev || !path_len_dev || !path_arcs_dev || !path_tokens_dev || !starts_dev || !ends_dev)
+    refuse(who, "null output pointer (scores, path_len, path_arcs, path_tokens, starts and ends are all written)");
+  if (blank < 0) refuse(who, "negative blank");
+  if (A < 0) refuse(who, "negative A");
+  if (row_stride < 3 * int64_t(A)) refuse(who, "row_stride is shorter than the rows' width 3 A");
+  if (max_states < 1 || max_states > kCtcLatticeMaxStates) refuse(who, "max_states outside 1 .. 4096");
+  if (P < 1) refuse(who, "P below 1");
+  if (out_stride < P) refuse(who, "out_stride is shorter than the rows' width P");
+  const int n = ems->n;
+  if (n <= 0) return;
+  Batch& x = linear_hypothesis_batch(who, ems, frames);
+  if (blank >= x.C) refuse(who, "blank is not below the number of labels");
+  if (frame_arcs_dev && frame_stride < x.M) refuse(who, "frame_stride is shorter than the rows of the batch");
+  check_outputs_local(who, {scores_dev, path_len_dev, path_arcs_dev, path_tokens_dev, starts_dev, ends_dev,
+                            token_scores_dev, frame_arcs_dev});
+  Runtime& rt = Runtime::get();
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  const std::vector<int> fr = resolve_frames(frames, x);
+  int maxT = 0;
+  double sumT = 0;
+  for (int t : fr) {
+    maxT = std::max(maxT, t);
+    sumT += t;
+  }
+  DevMemP fr_dev = upload_vec(fr);
+  const int64_t SM = max_states;
+  CtcLatticeAlignArgs a{};
+  a.em = x.w_dev;
+  a.frames = fr_dev->as<int>();
+  a.arcs = arcs_dev;
+  a.num_arcs = num_arcs_dev;
+  a.num_nodes = num_nodes_dev;
+  a.arc_weights = arc_weights_dev;
+  a.scores = scores_dev;
+  a.path_len = path_len_dev;
+  a.path_arcs = path_arcs_dev;
+  a.path_tokens = path_tokens_dev;
+  a.starts = starts_dev;
+  a.ends = ends_dev;
+  a.token_scores = token_scores_dev;
+  a.frame_arcs = frame_arcs_dev;
+  a.row_stride = row_stride;
+  a.out_stride = out_stride;
+  a.frame_stride = frame_stride;
+  a.A = A;
+  a.SM = max_states;
+  a.P = P;
+  a.M = x.M;
+  a.C = x.C;
+  a.blank = blank;
+  // algorithmic bytes, by the widths (the counts are device memory: an upper bound).  Per utterance and frame one
+  // emission per state in and 2 bytes per state out; the walk reads one back-pointer per frame; the arcs (and their
+  // weights) once, the score and the length out, the four path rows; with token scores one emission per frame at most
+  // and the row; with frame arcs the row.
+  const double frames_utt = sumT / double(n);
+  const double lattice = (arc_weights_dev ? 16.0 : 12.0) * std::min<int64_t>(A, SM) + 12.0;
+  const double utt_bytes = (4.0 + 2.0) * double(SM) * frames_utt + 2.0 * frames_utt + lattice + 8.0 + 16.0 * P +
+                           (token_scores_dev ? 4.0 * frames_utt + 4.0 * P : 0.0) + (frame_arcs_dev ? 4.0 * x.M : 0.0);
+  const int64_t per_utt = std::max<int64_t>(int64_t(maxT), 1) * SM;  // 16-bit entries
+  a.utt_stride = per_utt;
+  for_pair_slices(n, 2 * per_utt, kCtcLatticeAlignScratch, [&](int64_t u0, int64_t cnt) {
+    DevMemP ptrs = rt.alloc(size_t(2 * per_utt * cnt));
+    a.bp = ptrs->as<unsigned short>();
+    a.utt0 = int(u0);
+    a.count = int(cnt);
+    GTNX_PROF("ctc_lattice_align", utt_bytes * double(cnt));
+    launch_ctc_lattice_align(a, rt.stream());
+    // (the back-pointers go back to the stream-ordered pool behind the launch)
+  });
+  g_ctc_lattice_align.add(1, n);
+}
+
 // ---- batched CTC token alignment of device-resident hypotheses (ctc_token_align.hip) ----
 namespace {
 constexpr const char* kCtcTokenAlign = "gtnx_batch_ctc_token_align";

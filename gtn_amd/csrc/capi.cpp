@@ -1098,6 +1098,29 @@ GTNX_API gtnx_status_t gtnx_batch_ctc_lattice_score_grad(gtnx_batch_t ems, const
 GTNX_API gtnx_status_t gtnx_batch_ctc_lattice_score_stats(int64_t* calls, int64_t* utterances) {
   return guard([&] { batch_ctc_lattice_score_stats(calls, utterances); });
 }
+GTNX_API gtnx_status_t gtnx_batch_ctc_lattice_align(gtnx_batch_t ems, const int* frames, int blank,
+                                                    const void* arcs_device, int64_t row_stride,
+                                                    const void* num_arcs_device, const void* num_nodes_device,
+                                                    const void* arc_weights_device, int A, int max_states,
+                                                    void* scores_device, void* path_len_device,
+                                                    void* path_arcs_device, void* path_tokens_device,
+                                                    void* starts_device, void* ends_device, void* token_scores_device,
+                                                    int P, int64_t out_stride, void* frame_arcs_device,
+                                                    int64_t frame_stride) {
+  return guard([&] {
+    batch_ctc_lattice_align(BH(ems), frames, blank, static_cast<const int*>(arcs_device), row_stride,
+                            static_cast<const int*>(num_arcs_device), static_cast<const int*>(num_nodes_device),
+                            static_cast<const float*>(arc_weights_device), A, max_states,
+                            static_cast<float*>(scores_device), static_cast<int*>(path_len_device),
+                            static_cast<int*>(path_arcs_device), static_cast<int*>(path_tokens_device),
+                            static_cast<int*>(starts_device), static_cast<int*>(ends_device),
+                            static_cast<float*>(token_scores_device), P, out_stride,
+                            static_cast<int*>(frame_arcs_device), frame_stride);
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_ctc_lattice_align_stats(int64_t* calls, int64_t* utterances) {
+  return guard([&] { batch_ctc_lattice_align_stats(calls, utterances); });
+}
 GTNX_API gtnx_status_t gtnx_batch_ctc_token_align(gtnx_batch_t ems, const int* frames, int blank,
                                                   const void* tokens_device, int64_t row_stride,
                                                   const void* lengths_device, int N, int L, int max_length,

@@ -1064,6 +1064,35 @@ struct CtcLatticeArgs {
 void ctc_lattice_config(int max_states, int* width, int* per_lane);  // the workgroup's width, the states a lane owns
 void launch_ctc_lattice_forward(const CtcLatticeArgs& a, hipStream_t st);
 void launch_ctc_lattice_backward(const CtcLatticeArgs& a, hipStream_t st);
+// ctc_lattice_align.hip: the best (lattice path, alignment) pair (max-plus, of equal candidates the first in the
+// forward's order) of the utterances utt0 .. utt0 + count - 1 in ctc_lattice.hip's lattice form (the contract: DESIGN
+// section 38).  One workgroup per utterance, width and states per lane from ctc_lattice_config(SM); row b of every
+// output is written over its whole width: scores[b] the pair's score, path_len[b] the arcs on the path, path_arcs /
+// path_tokens / starts / ends [b * out_stride + i] the i-th arc, its label, its first frame and one past its last (the
+// first P of a longer path), token_scores (or null) the arc's emissions summed in frame order, frame_arcs[b *
+// frame_stride + t] (or null) the arc of frame t; -1 / -inf where no path covers an entry.  bp: the back-pointers of the
+// launch, the 16-bit source state of every state and frame, entry t * SM + s of the utt_stride entries of workgroup
+// blockIdx.x.
+struct CtcLatticeAlignArgs {
+  const GTNX_G float* em;           // [n][M][C]
+  const GTNX_G int* frames;         // [n]
+  const GTNX_G int* arcs;           // utterance b's row at arcs + b * row_stride
+  const GTNX_G int* num_arcs;       // [n]
+  const GTNX_G int* num_nodes;      // [n]
+  const GTNX_G float* arc_weights;  // [n][A] or null: all zeros
+  GTNX_G float* scores;             // [n]
+  GTNX_G int* path_len;             // [n]
+  GTNX_G int* path_arcs;            // utterance b's row at path_arcs + b * out_stride, width P
+  GTNX_G int* path_tokens;          // the same
+  GTNX_G int* starts;               // the same
+  GTNX_G int* ends;                 // the same
+  GTNX_G float* token_scores;       // the same, or null
+  GTNX_G int* frame_arcs;           // utterance b's row at frame_arcs + b * frame_stride, width M, or null
+  GTNX_G unsigned short* bp;        // [count][utt_stride]
+  int64_t row_stride, out_stride, frame_stride, utt_stride;
+  int utt0, count, A, SM, P, M, C, blank;
+};
+void launch_ctc_lattice_align(const CtcLatticeAlignArgs& a, hipStream_t st);
 // asg_score.hip: the log score forwardScore(emissions_b[:T_b] o (forceAlign(y) o transitions)) of the pairs pair0 ..
 // pair0 + count - 1 in ctc_score.hip's hypothesis form (no blank: position i = 0 .. len - 1 carries y[i]), and the
 // gradients sum_p weights[p] * d score[p] / d (emissions_b, table) (the contract: DESIGN section 25).  table: [C + C * C]

@@ -1,7 +1,7 @@
 """PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
 `asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_sample`, `ctc_beam_decode`, `asg_beam_decode`, `asg_sample`,
-`edit_distance`, `ctc_score`, `ctc_lattice_score`, `ctc_lattice_loss`, `ctc_token_align`, `asg_score`,
-`asg_lattice_score`, `asg_full_connect`, `asg_lattice_loss` and `asg_token_align`.
+`edit_distance`, `ctc_score`, `ctc_lattice_score`, `ctc_lattice_loss`, `ctc_lattice_align`, `ctc_token_align`,
+`asg_score`, `asg_lattice_score`, `asg_full_connect`, `asg_lattice_loss` and `asg_token_align`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -41,6 +41,7 @@ _ARGTYPES = {
     "gtn_ctc_score_grad_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P],
     "gtn_ctc_lattice_score_n": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P],
     "gtn_ctc_lattice_score_grad_n": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P],
+    "gtn_ctc_lattice_align_n": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "gtn_ctc_token_align_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gtn_asg_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
@@ -1047,27 +1048,9 @@ class _CTCLatticeScore(torch.autograd.Function):
         return (grad, garc.to(w_dtype) if want_w else None) + none
 
 
-def ctc_lattice_score(log_probs, arcs, num_arcs, num_nodes, arc_weights=None, blank=0, input_lengths=None,
-                      max_states=None):
-    """The exact CTC log score of one acyclic token lattice per utterance, differentiable: score[b] = log sum over the
-    lattice's paths p of exp(w(p) + ctc_score(log_probs[b, :T_b], labels(p))) -- every word-piece decomposition,
-    pronunciation or optional token the lattice holds and every alignment of each, marginalised in one launch; the
-    lattices are read where they lie on the device.  No normaliser is subtracted (`ctc_lattice_loss` does that).
-    log_probs: float32 CUDA tensor [B, T, C] (any scores), read in place; arcs: int32 CUDA tensor [B, A, 3] of (src, dst,
-    label) rows with 0 <= src < dst < num_nodes[b], sorted by dst within an utterance (`gtn_amd.pack_lattices` gives
-    this form); num_arcs, num_nodes: int32 or int64 CUDA tensors [B] -- node 0 starts, node num_nodes - 1 accepts, arcs
-    at or past num_arcs[b] are never read; arc_weights: float32 CUDA tensor [B, A] or None (zeros), added once per use
-    of an arc, -inf forbids it; blank: 0 .. C - 1 (a label equal to blank is a label like any other); input_lengths:
-    per-utterance frame counts (0 .. T) or None -- rows past T_b are never read and their gradient is exactly 0;
-    max_states (1 .. 4096, default min(2 A + 1, 4096)): the caller's bound on nodes + arcs, which sizes the kernel's
-    LDS and the backward's scratch.
-    Returns float32 [B].  A score is -inf, with zero gradients and never NaN, when T_b == 0, num_nodes < 1, nodes +
-    arcs > max_states, an arc has src < 0, src >= dst or dst >= num_nodes, an arc is out of dst order, a label lies
-    outside 0 .. C - 1, a weight is +inf or NaN, or no alignment fits.  Two paths that spell the same labels both count.
-    The backward is one call that returns grad_out[b] * d score[b] / d log_probs and, when arc_weights requires a
-    gradient, grad_out[b] * the posterior probability of every arc; it recomputes what it needs and sums in a fixed
-    order without atomics, so it has the same bits run to run.  Runs on the caller's stream."""
-    who = "ctc_lattice_score"
+def _lattice_args(who, log_probs, arcs, num_arcs, num_nodes, arc_weights, blank, input_lengths, max_states):
+    """what `ctc_lattice_score` and `ctc_lattice_align` check of their arguments alike.  Returns (A, arcs contiguous,
+    num_arcs and num_nodes as int32, blank, frames or None, max_states)"""
     x = log_probs
     if not (torch.is_tensor(x) and x.dim() == 3 and x.dtype == torch.float32):
         raise ValueError(f"{who}: log_probs must be a float32 tensor [B, T, C]")
@@ -1100,6 +1083,33 @@ def ctc_lattice_score(log_probs, arcs, num_arcs, num_nodes, arc_weights=None, bl
     arcs_c = arcs.detach().contiguous()
     na = num_arcs.detach().to(torch.int32).contiguous()  # (int64 counts are converted on the device)
     nn_ = num_nodes.detach().to(torch.int32).contiguous()
+    return A, arcs_c, na, nn_, blank, frames, max_states
+
+
+def ctc_lattice_score(log_probs, arcs, num_arcs, num_nodes, arc_weights=None, blank=0, input_lengths=None,
+                      max_states=None):
+    """The exact CTC log score of one acyclic token lattice per utterance, differentiable: score[b] = log sum over the
+    lattice's paths p of exp(w(p) + ctc_score(log_probs[b, :T_b], labels(p))) -- every word-piece decomposition,
+    pronunciation or optional token the lattice holds and every alignment of each, marginalised in one launch; the
+    lattices are read where they lie on the device.  No normaliser is subtracted (`ctc_lattice_loss` does that).
+    log_probs: float32 CUDA tensor [B, T, C] (any scores), read in place; arcs: int32 CUDA tensor [B, A, 3] of (src, dst,
+    label) rows with 0 <= src < dst < num_nodes[b], sorted by dst within an utterance (`gtn_amd.pack_lattices` gives
+    this form); num_arcs, num_nodes: int32 or int64 CUDA tensors [B] -- node 0 starts, node num_nodes - 1 accepts, arcs
+    at or past num_arcs[b] are never read; arc_weights: float32 CUDA tensor [B, A] or None (zeros), added once per use
+    of an arc, -inf forbids it; blank: 0 .. C - 1 (a label equal to blank is a label like any other); input_lengths:
+    per-utterance frame counts (0 .. T) or None -- rows past T_b are never read and their gradient is exactly 0;
+    max_states (1 .. 4096, default min(2 A + 1, 4096)): the caller's bound on nodes + arcs, which sizes the kernel's
+    LDS and the backward's scratch.
+    Returns float32 [B].  A score is -inf, with zero gradients and never NaN, when T_b == 0, num_nodes < 1, nodes +
+    arcs > max_states, an arc has src < 0, src >= dst or dst >= num_nodes, an arc is out of dst order, a label lies
+    outside 0 .. C - 1, a weight is +inf or NaN, or no alignment fits.  Two paths that spell the same labels both count.
+    The backward is one call that returns grad_out[b] * d score[b] / d log_probs and, when arc_weights requires a
+    gradient, grad_out[b] * the posterior probability of every arc; it recomputes what it needs and sums in a fixed
+    order without atomics, so it has the same bits run to run.  Runs on the caller's stream."""
+    x = log_probs
+    A, arcs_c, na, nn_, blank, frames, max_states = _lattice_args(
+        "ctc_lattice_score", log_probs, arcs, num_arcs, num_nodes, arc_weights, blank, input_lengths, max_states)
+    B = x.shape[0]
     if A == 0:
         # (an empty tensor has no address to hand over: one row that no count reaches stands in for none)
         out = _CTCLatticeScore.apply(x, None, arcs_c.new_zeros(B, 1, 3), torch.zeros_like(na), nn_, blank, frames,
@@ -1123,6 +1133,67 @@ def ctc_lattice_loss(log_probs, arcs, num_arcs, num_nodes, arc_weights=None, bla
     inside = torch.arange(T, device=log_probs.device)[None, :] < frames[:, None]
     rows = torch.logsumexp(torch.where(inside[:, :, None], log_probs, torch.zeros_like(log_probs)), dim=2)
     return torch.where(inside, rows, torch.zeros_like(rows)).sum(dim=1) - score
+
+
+def ctc_lattice_align(log_probs, arcs, num_arcs, num_nodes, arc_weights=None, blank=0, input_lengths=None,
+                      max_states=None, max_path=None, return_token_scores=False, return_frames=False):
+    """Which path of its token lattice the model chose for each utterance, and when each token of that path was spoken:
+    the best (lattice path, alignment) pair -- the maximum over the lattice's paths p and the alignments of labels(p) of
+    w(p) + the summed log_probs -- in one call, the lattices read where they lie on the device.  It is the max-plus
+    partner of `ctc_lattice_score`: forced alignment with pronunciation variants or optional tokens, and the chosen
+    word-piece decomposition after training with `ctc_lattice_loss`.
+    log_probs, arcs, num_arcs, num_nodes, arc_weights (detached), blank, input_lengths and max_states are those of
+    `ctc_lattice_score`; max_path (>= 1, default max(1, min(A, max_states))) is the width P of the path rows.
+    Returns (scores, path_len, path_arcs, path_tokens, starts, ends[, token_scores][, frame_arcs]) on log_probs.device:
+      scores        float32 [B]: the best w(p) + alignment score, -inf without a path;
+      path_len      int32 [B]: the arcs on the best path, 0 without one; a path longer than P keeps its true length;
+      path_arcs     int32 [B, P]: the arc indices in path order (the first P of a longer path);
+      path_tokens   int32 [B, P]: their labels -- with path_len the layout `ctc_score`, `edit_distance` and
+                    `ctc_token_align` take;
+      starts, ends  int32 [B, P]: the first frame of each arc and one past its last (blank frames belong to no arc);
+                    all four rows hold -1 at and past path_len and for an utterance without a path;
+      token_scores  float32 [B, P] (return_token_scores): the sum of log_probs[b, t, label] over the arc's frames; -inf
+                    where starts is -1;
+      frame_arcs    int32 [B, T] (return_frames): the arc index of every frame, -1 on blank frames and from T_b on.
+    An utterance has no path exactly where `ctc_lattice_score` gives -inf.  A one-node lattice has the empty path: a
+    finite score and rows of -1.  Float32 max-plus arithmetic; of equal candidates the first in the forward recurrence's
+    order wins (the state itself, the blank of the arc's source, the arcs entering it in ascending order): the same bits
+    every time.  No autograd.  Runs on the caller's stream."""
+    who = "ctc_lattice_align"
+    if max_path is not None and int(max_path) < 1:
+        raise ValueError(f"{who}: max_path must be at least 1")
+    A, arcs_c, na, nn_, blank, frames, max_states = _lattice_args(
+        who, log_probs, arcs, num_arcs, num_nodes, arc_weights, blank, input_lengths, max_states)
+    P = max(1, min(A, max_states)) if max_path is None else int(max_path)
+    x = log_probs.detach().contiguous()
+    B, T, _ = x.shape
+    w = None if arc_weights is None else arc_weights.detach().to(torch.float32).contiguous()
+    if A == 0:
+        # (an empty tensor has no address to hand over: one row that no count reaches stands in for none)
+        A, arcs_c, na, w = 1, arcs_c.new_zeros(B, 1, 3), torch.zeros_like(na), None
+    stream = _engine_stream(x.device)
+    F = max(T, 1)  # (rows without an element are never written, but they need an address)
+    scores = torch.empty(B, dtype=torch.float32, device=x.device)
+    plen = torch.empty(B, dtype=torch.int32, device=x.device)
+    rows = [torch.empty(B, P, dtype=torch.int32, device=x.device) for _ in range(4)]
+    tsc = torch.empty(B, P, dtype=torch.float32, device=x.device) if return_token_scores else None
+    fa = torch.empty(B, F, dtype=torch.int32, device=x.device) if return_frames else None
+    if B == 0:
+        _engine_done(stream)  # (no utterance: nothing to launch, and an empty tensor has no address to hand over)
+    else:
+        native = T == F and _has_native(who, "gtn_ctc_lattice_align_n")
+        _route(stream, x, native, "gtn_ctc_lattice_align_n",
+               (blank, _host_ptr(frames), arcs_c.data_ptr(), na.data_ptr(), nn_.data_ptr(), _ptr(w), A, max_states, P,
+                scores.data_ptr(), plen.data_ptr(), *(r.data_ptr() for r in rows), _ptr(tsc), _ptr(fa)),
+               "ctc_lattice_align", arcs_c.data_ptr(), na.data_ptr(), nn_.data_ptr(), scores.data_ptr(), plen.data_ptr(),
+               *(r.data_ptr() for r in rows), _ptr(tsc), _ptr(fa), _ptr(w), frames, blank, max_states, A=A,
+               row_stride=3 * A, P=P, out_stride=P, frame_stride=F)
+    out = [scores, plen, *rows]
+    if return_token_scores:
+        out.append(tsc)
+    if return_frames:
+        out.append(fa[:, :T])
+    return tuple(out)
 
 
 class _ASGScore(torch.autograd.Function):

@@ -338,6 +338,26 @@ inline void ctcLatticeScoreGrad(const Batch& ems, const int* arcsDevice, int64_t
                                                   numNodesDevice, arcWeightsDevice, A, maxStates, weightsDevice,
                                                   gradDevice, arcGradDevice));
 }
+/** The best (lattice path, alignment) pair of one device-resident token lattice per utterance (ctcLatticeScore's
+ *  lattices, blank, frames and maxStates) under the slabs of a Batch::linear, results left on the device: scoresDevice
+ *  [n] the best w(p) + alignment score (-inf without a path), pathLenDevice [n] the arcs on the best path;
+ *  pathArcsDevice / pathTokensDevice / startsDevice / endsDevice int32 n rows of width P, outStride (>= P) apart: the arc
+ *  indices in path order, their labels, the first frame of each and one past its last, -1 from pathLen on and without a
+ *  path (a path longer than P keeps its length and writes its first P); tokenScoresDevice (same layout, or null) the
+ *  arc's emissions summed in frame order; frameArcsDevice (n rows of width M, frameStride >= M apart, or null) the arc of
+ *  every frame, -1 on blank frames and from T_b on.  Float32 max-plus, of equal candidates the first in the forward's
+ *  order: reproducible bit for bit.  No copy back, no wait -- gtnx_batch_ctc_lattice_align */
+inline void ctcLatticeAlign(const Batch& ems, const int* arcsDevice, int64_t rowStride, const int* numArcsDevice,
+                            const int* numNodesDevice, const float* arcWeightsDevice, int A, int maxStates,
+                            float* scoresDevice, int* pathLenDevice, int* pathArcsDevice, int* pathTokensDevice,
+                            int* startsDevice, int* endsDevice, float* tokenScoresDevice, int P, int64_t outStride,
+                            int* frameArcsDevice = nullptr, int64_t frameStride = 0, int blank = 0,
+                            const int* frames = nullptr) {
+  detail::check(gtnx_batch_ctc_lattice_align(ems.handle(), frames, blank, arcsDevice, rowStride, numArcsDevice,
+                                             numNodesDevice, arcWeightsDevice, A, maxStates, scoresDevice, pathLenDevice,
+                                             pathArcsDevice, pathTokensDevice, startsDevice, endsDevice,
+                                             tokenScoresDevice, P, outStride, frameArcsDevice, frameStride));
+}
 /** The ASG force-align term of all n * N device-resident hypotheses under the slabs of a Batch::linear, results left on
  *  the device: scoresDevice[b][k] = forwardScore(emissions_b[0 .. T_b) o (forceAlign(tokens[b][k][0 .. len)) o
  *  transitions)), len = clamp(lengthsDevice[b][k], 0, L), log semiring, nothing subtracted.  tableDevice float32

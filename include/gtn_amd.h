@@ -639,6 +639,56 @@ gtnx_status_t gtnx_batch_ctc_lattice_score_grad(gtnx_batch_t ems, const int* fra
                                                 void* arc_grad_device);
 /* calls of either kind that have launched so far (process-wide) / utterances they took */
 gtnx_status_t gtnx_batch_ctc_lattice_score_stats(int64_t* calls, int64_t* utterances);
+/* The best (lattice path, alignment) pair of those lattices: WHICH decomposition or pronunciation the model chose and
+ * WHEN each of its tokens was spoken, for every utterance in one call, results left on the device.
+ * The lattice arguments, blank, frames and max_states are those of gtnx_batch_ctc_lattice_score with the same meaning,
+ * the same state space (state n < K the blank of node n, state K + a the token of arc a) and the same rules about what
+ * is invalid.  Float32 max-plus, the forward recurrence's candidates in its order with max for logadd:
+ *   frame 0: alpha[blank 0] = e(0, blank); alpha[a] = w_a + e(0, label a) for src a == 0; -inf elsewhere
+ *   token a: alpha[a] | alpha[blank src] + w_a | alpha[a'] + w_a for a' entering src, ascending, label(a') != label(a);
+ *            x = their maximum; alpha'[a] = x == -inf ? -inf : x + e(t, label a)
+ *   blank n: alpha[n] | alpha[a'] for a' entering n, ascending; alpha'[n] likewise with e(t, blank)
+ *   end:     alpha[blank(K - 1)] | alpha[a'] for a' entering K - 1, ascending; the score is their maximum
+ * An addition with a -inf operand gives -inf.  Of the candidates that reach the maximum the FIRST in that order wins (a
+ * later one replaces it only if strictly greater), a -inf candidate is never chosen and a state whose maximum is -inf is
+ * dead: this project's own rule (the reference has no canonical alignment graph of a lattice).  Every output is
+ * reproducible bit for bit; a chain lattice without weights has the score bits of gtnx_batch_ctc_token_align.
+ *   scores_device       float32 [n]: the best w(p) + alignment score, -inf without a path
+ *   path_len_device     int32 [n]: the arcs on the best lattice path (0 .. K - 1), 0 without a path
+ *   path_arcs_device,   int32, n rows of width P (>= 1), out_stride (>= P) elements apart: the arc indices in path order,
+ *   path_tokens_device, their labels, the first frame of each and one past its last (blank frames belong to no arc); -1
+ *   starts_device,      at and past path_len and in every entry of an utterance without a path.  A path longer than P
+ *   ends_device         keeps its true path_len and writes its first P entries.  path_tokens + path_len have the layout
+ *                       gtnx_batch_ctc_score, gtnx_batch_edit_distance and gtnx_batch_ctc_token_align take
+ *   token_scores_device float32, same layout, or null: the sum of e(t, label) over the arc's frames, added in ascending
+ *                       frame order from the first frame's value; -inf where starts is -1
+ *   frame_arcs_device   int32, n rows of width M, frame_stride (>= M) apart, or null: the arc index of every frame, -1 on
+ *                       blank frames, from T_b on and in every entry of an utterance without a path
+ * Every element of every row is written over the widths P and M, nothing beyond them.  An utterance has no path exactly
+ * where gtnx_batch_ctc_lattice_score gives -inf: T_b == 0, an invalid or too large lattice, a +inf or NaN weight, no
+ * alignment fits or survives -inf emissions.  A one-node lattice has the empty path: a finite score (the blank
+ * emissions summed), rows of -1.  Every arc field is checked before it becomes an address; nothing at or past
+ * num_arcs[b], T_b or a width is read; the inputs are only read.  NaN emissions give unspecified values and no access
+ * outside the utterance's own rows.
+ * GTNX_INVALID_ARGUMENT before a device is asked for: what gtnx_batch_ctc_lattice_score refuses there, a null scores,
+ * path_len, path_arcs, path_tokens, starts or ends pointer, P < 1, out_stride < P.  A batch without an utterance returns
+ * without touching a device.  With the device: not a gtnx_batch_linear / _rows batch, a frame count outside 0 .. M,
+ * blank >= C, frame_stride < M with frame arcs, an output the engine's current device may not write.  A refused call
+ * writes nothing.
+ * One workgroup per utterance (ctc_lattice_align.hip).  The back-pointers take 16 bits per state and frame in scratch
+ * from the stream-ordered pool, 2 * max_states * max_b T_b bytes per utterance, at most 256 MiB per launch; beyond that
+ * the utterances run in slices with the same bits (GTNX_CTC_LATTICE_ALIGN_SCRATCH_BYTES, read per call, lowers the cap: a
+ * debug switch for tests); a single utterance above the cap runs alone.  Nothing is copied back, the call does not
+ * wait. */
+gtnx_status_t gtnx_batch_ctc_lattice_align(gtnx_batch_t ems, const int* frames, int blank, const void* arcs_device,
+                                           int64_t row_stride, const void* num_arcs_device,
+                                           const void* num_nodes_device, const void* arc_weights_device, int A,
+                                           int max_states, void* scores_device, void* path_len_device,
+                                           void* path_arcs_device, void* path_tokens_device, void* starts_device,
+                                           void* ends_device, void* token_scores_device, int P, int64_t out_stride,
+                                           void* frame_arcs_device, int64_t frame_stride);
+/* calls that have launched so far (process-wide) / utterances they took */
+gtnx_status_t gtnx_batch_ctc_lattice_align_stats(int64_t* calls, int64_t* utterances);
 /* The best alignment of those hypotheses: WHEN each token was spoken and how well the frames support it, for all n * N
  * pairs in one call, results left on the device.  The inputs are those of gtnx_batch_ctc_score with the same meaning:
  * pair (b, k) is y = tokens[b][k][0 .. len), len = clamp(lengths[b][k], 0, L), under emissions_b[0 .. T_b).  The states
