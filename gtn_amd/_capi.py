@@ -184,6 +184,11 @@ _SIGS = {
                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p],
     "gtnx_batch_asg_lattice_score_stats": [c_i64_p, c_i64_p],
+    "gtnx_batch_asg_lattice_align": [c_graph, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
+                                     C.c_int64],
+    "gtnx_batch_asg_lattice_align_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_asg_token_align": [c_graph, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int,
                                    C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                    C.c_int64],

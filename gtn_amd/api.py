@@ -1290,6 +1290,21 @@ def make_api(lib):
             who = "ctc_lattice_align"
             fr, A, stride, SM = self._ctc_lattice_args(who, arcs, num_arcs, num_nodes, arc_weights, frames, A,
                                                        row_stride, max_states)
+            P, out_stride, frame_stride = self._lattice_align_outputs(
+                who, scores_out, path_len_out, path_arcs_out, path_tokens_out, starts_out, ends_out, token_scores_out,
+                frame_arcs_out, P, out_stride, frame_stride)
+            check(lib.gtnx_batch_ctc_lattice_align(self._h, fr.ctypes.data if fr is not None else None, int(blank),
+                                                   _opt_ptr(arcs), stride, _opt_ptr(num_arcs), _opt_ptr(num_nodes),
+                                                   _opt_ptr(arc_weights), A, SM, _opt_ptr(scores_out),
+                                                   _opt_ptr(path_len_out), _opt_ptr(path_arcs_out),
+                                                   _opt_ptr(path_tokens_out), _opt_ptr(starts_out), _opt_ptr(ends_out),
+                                                   _opt_ptr(token_scores_out), int(P), int(out_stride),
+                                                   _opt_ptr(frame_arcs_out), int(frame_stride)))
+
+        def _lattice_align_outputs(self, who, scores_out, path_len_out, path_arcs_out, path_tokens_out, starts_out,
+                                   ends_out, token_scores_out, frame_arcs_out, P, out_stride, frame_stride):
+            """What `ctc_lattice_align` and `asg_lattice_align` check of their outputs alike.  Returns (P, out_stride,
+            frame_stride)."""
             n = len(self)
 
             def rows_of(t, name, dtype, width, given):
@@ -1324,13 +1339,7 @@ def make_api(lib):
                 if o is not None and hasattr(o, "data_ptr"):
                     if str(o.dtype) != dtype or not o.is_contiguous() or o.numel() != n:
                         raise ValueError(f"{who}: {name} must be a {dtype[6:]} contiguous tensor [B]")
-            check(lib.gtnx_batch_ctc_lattice_align(self._h, fr.ctypes.data if fr is not None else None, int(blank),
-                                                   _opt_ptr(arcs), stride, _opt_ptr(num_arcs), _opt_ptr(num_nodes),
-                                                   _opt_ptr(arc_weights), A, SM, _opt_ptr(scores_out),
-                                                   _opt_ptr(path_len_out), _opt_ptr(path_arcs_out),
-                                                   _opt_ptr(path_tokens_out), _opt_ptr(starts_out), _opt_ptr(ends_out),
-                                                   _opt_ptr(token_scores_out), int(P), int(out_stride),
-                                                   _opt_ptr(frame_arcs_out), int(frame_stride)))
+            return int(P), int(out_stride), int(frame_stride)
 
         def _token_align_outputs(self, who, N, L, scores_out, starts_out, ends_out, token_scores_out, frame_tokens_out,
                                  out_stride, frame_stride):
@@ -1554,6 +1563,35 @@ def make_api(lib):
                                                         _opt_ptr(num_nodes), _opt_ptr(arc_weights), A, SM, int(max_edges),
                                                         _opt_ptr(weights), _opt_ptr(grad_out), _opt_ptr(grad_table_out),
                                                         _opt_ptr(arc_grad_out)))
+
+        def asg_lattice_align(self, table, arcs, num_arcs, num_nodes, scores_out, path_len_out, path_arcs_out,
+                              path_tokens_out, starts_out, ends_out, token_scores_out=None, frame_arcs_out=None,
+                              arc_weights=None, frames=None, max_states=None, max_edges=None, A=None, row_stride=None,
+                              P=None, out_stride=None, frame_stride=None):
+            """The best (lattice path, alignment) pair of one device-resident token lattice per utterance under the ASG
+            criterion, results left on the device (gtnx_batch_asg_lattice_align; DESIGN section 39 holds the contract).
+            `table`, `arcs`, `num_arcs`, `num_nodes`, `arc_weights`, `frames`, `max_states`, `max_edges`, A and
+            row_stride are those of `asg_lattice_score`: an utterance has no path exactly where that call gives -inf.
+            The outputs, P, `out_stride` and `frame_stride` are those of `ctc_lattice_align`; there is no blank, so the
+            spans tile 0 .. T_b and `frame_arcs_out` is never -1 inside a path.  Float32 max-plus, of equal candidates
+            the first in the forward's order (not `asg_token_align`'s rule): the same bits every time.  No copy back and
+            no wait."""
+            who = "asg_lattice_align"
+            fr, A, stride, SM = self._ctc_lattice_args(who, arcs, num_arcs, num_nodes, arc_weights, frames, A, row_stride,
+                                                       max_states)
+            table = self._asg_score_table(who, table)
+            if max_edges is None:
+                max_edges = min(8 * SM, 1 << 21)
+            P, out_stride, frame_stride = self._lattice_align_outputs(
+                who, scores_out, path_len_out, path_arcs_out, path_tokens_out, starts_out, ends_out, token_scores_out,
+                frame_arcs_out, P, out_stride, frame_stride)
+            check(lib.gtnx_batch_asg_lattice_align(self._h, fr.ctypes.data if fr is not None else None, _opt_ptr(table),
+                                                   _opt_ptr(arcs), stride, _opt_ptr(num_arcs), _opt_ptr(num_nodes),
+                                                   _opt_ptr(arc_weights), A, SM, int(max_edges), _opt_ptr(scores_out),
+                                                   _opt_ptr(path_len_out), _opt_ptr(path_arcs_out),
+                                                   _opt_ptr(path_tokens_out), _opt_ptr(starts_out), _opt_ptr(ends_out),
+                                                   _opt_ptr(token_scores_out), P, out_stride, _opt_ptr(frame_arcs_out),
+                                                   frame_stride))
 
     ns.Batch = Batch
 
@@ -1839,6 +1877,11 @@ def make_api(lib):
         far and the utterances they took (include/gtn_amd.h: gtnx_batch_asg_lattice_score_stats)"""
         return _stats2(lib.gtnx_batch_asg_lattice_score_stats)
 
+    def debug_asg_lattice_align_stats():
+        """(calls, utterances): calls of Batch.asg_lattice_align that have launched so far and the utterances they took
+        (include/gtn_amd.h: gtnx_batch_asg_lattice_align_stats)"""
+        return _stats2(lib.gtnx_batch_asg_lattice_align_stats)
+
     def debug_full_connect_stats():
         """(fast, fallback): utterances whose ASG full-connect score forward_score(compose(Batch.linear(rows=...),
         transitions)) came from the one launch of asg_full.hip / utterances of such a padded batch that took the composed
@@ -1859,6 +1902,7 @@ def make_api(lib):
     ns.debug_ctc_lattice_align_stats = debug_ctc_lattice_align_stats
     ns.debug_asg_score_stats = debug_asg_score_stats
     ns.debug_asg_lattice_score_stats = debug_asg_lattice_score_stats
+    ns.debug_asg_lattice_align_stats = debug_asg_lattice_align_stats
     ns.debug_asg_token_align_stats = debug_asg_token_align_stats
     ns.debug_asg_beam_stats = debug_asg_beam_stats
     ns.debug_asg_sample_stats = debug_asg_sample_stats

@@ -294,6 +294,44 @@ inline void asgLatticeScoreBatch(
   }
 }
 
+/** The best (lattice path, alignment) pair of one device-resident token lattice per utterance under the B emission slabs
+ *  -- which decomposition the model chose and when each of its tokens was spoken: the inputs are those of
+ *  asgLatticeScoreBatch; `scoresDev` device float32 [B]; `pathLenDev` device int32 [B]; `pathArcsDev` / `pathTokensDev` /
+ *  `startsDev` / `endsDev` device int32 [B][P] (dense rows); `tokenScoresDev` device float32 [B][P] or null;
+ *  `frameArcsDev` device int32 [B][T] or null.  gtnx_batch_asg_lattice_align has the contract.  Nothing is copied
+ *  back. */
+inline void asgLatticeAlignBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int N_,
+    const void* tableDev,
+    const int* frames,
+    const void* arcsDev,
+    const void* numArcsDev,
+    const void* numNodesDev,
+    const void* arcWeightsDev,
+    int A,
+    int maxStates,
+    int maxEdges,
+    int P,
+    void* scoresDev,
+    void* pathLenDev,
+    void* pathArcsDev,
+    void* pathTokensDev,
+    void* startsDev,
+    void* endsDev,
+    void* tokenScoresDev = nullptr,
+    void* frameArcsDev = nullptr) {
+  Batch ems = Batch::linear(B, T, N_, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  batched::asgLatticeAlign(ems, static_cast<const float*>(tableDev), static_cast<const int*>(arcsDev), 3 * int64_t(A),
+                           static_cast<const int*>(numArcsDev), static_cast<const int*>(numNodesDev),
+                           static_cast<const float*>(arcWeightsDev), A, maxStates, maxEdges,
+                           static_cast<float*>(scoresDev), static_cast<int*>(pathLenDev), static_cast<int*>(pathArcsDev),
+                           static_cast<int*>(pathTokensDev), static_cast<int*>(startsDev), static_cast<int*>(endsDev),
+                           static_cast<float*>(tokenScoresDev), P, P, static_cast<int*>(frameArcsDev), T, frames);
+}
+
 /** `numSamples` alignments per utterance drawn from the posterior of emissions o transitions, results on the device:
  *  forward filtering, backward sampling, then equal neighbours merged (gtnx_batch_asg_sample has the contract;
  *  Philox4x32-10 keyed by `seed`, so a seed repeats a run).  `emissions`: device float32 [B][T][N], read in place;

@@ -454,6 +454,30 @@ void batch_asg_lattice_score_grad(const BatchP& ems, const int* frames, const fl
                                   const float* weights_dev, float* grad_em_dev, float* grad_table_dev,
                                   float* arc_grad_dev);
 void batch_asg_lattice_score_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
+// The best (lattice path, alignment) pair of those lattices under the ASG criterion (the inputs of
+// batch_asg_lattice_score, with the same meaning), results on the device (DESIGN section 39 holds the contract): the
+// outputs, their layout and their fills are batch_ctc_lattice_align's -- scores_dev [n] the best w(p) + start, transition
+// and emission terms, path_len_dev [n] the arcs on the best path (1 .. K - 1, 0 without one), path_arcs_dev /
+// path_tokens_dev / starts_dev / ends_dev (n rows of width P, out_stride apart), token_scores_dev (same layout, or null)
+// the arc's emissions alone summed in frame order, frame_arcs_dev (n rows of width M, frame_stride apart, or null) the
+// arc of every frame.  There is no blank: starts[0] == 0, ends[i] == starts[i + 1], the last end is T_b and frame_arcs is
+// never -1 inside a path.  Float32 max-plus; of equal candidates the first in the forward recurrence's order wins (the
+// arc itself, then the arcs entering its src ascending): bit-reproducible, and not batch_asg_token_align's rule (there
+// the step wins and the sum is associated otherwise).  An utterance has no path exactly where batch_asg_lattice_score
+// with the same arguments gives -inf; nothing is kept per edge, max_edges is taken for that rule alone.
+// Invalid argument before a device is asked for: what batch_asg_lattice_score refuses there, a null scores, path_len,
+// path_arcs, path_tokens, starts or ends pointer, P < 1, out_stride < P; n == 0 returns without a device.  With the
+// device: what batch_asg_lattice_score refuses there, frame_stride < M with frame arcs, an output that is not memory of
+// the current device.  The back-pointers (16 bits per arc and frame, max T_b * max_states of them per utterance) come
+// from the stream-ordered pool, at most 256 MiB per launch (GTNX_ASG_LATTICE_ALIGN_SCRATCH_BYTES lowers the cap: a debug
+// switch); beyond it the utterances run in slices, same bits.
+void batch_asg_lattice_align(const BatchP& ems, const int* frames, const float* table_dev, const int* arcs_dev,
+                             int64_t row_stride, const int* num_arcs_dev, const int* num_nodes_dev,
+                             const float* arc_weights_dev, int A, int max_states, int max_edges, float* scores_dev,
+                             int* path_len_dev, int* path_arcs_dev, int* path_tokens_dev, int* starts_dev, int* ends_dev,
+                             float* token_scores_dev, int P, int64_t out_stride, int* frame_arcs_dev,
+                             int64_t frame_stride);
+void batch_asg_lattice_align_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
 // The best ASG alignment of all n * N device-resident hypotheses (the pair form and the table of batch_asg_score) under
 // the n emission slabs of a native linear batch, results on the device (DESIGN section 28 holds the contract): the
 // outputs are those of batch_ctc_token_align, frame_tokens_dev never -1 inside a path (there is no blank).  Float32

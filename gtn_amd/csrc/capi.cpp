@@ -1193,6 +1193,29 @@ GTNX_API gtnx_status_t gtnx_batch_asg_lattice_score_grad(gtnx_batch_t ems, const
 GTNX_API gtnx_status_t gtnx_batch_asg_lattice_score_stats(int64_t* calls, int64_t* utterances) {
   return guard([&] { batch_asg_lattice_score_stats(calls, utterances); });
 }
+GTNX_API gtnx_status_t gtnx_batch_asg_lattice_align(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                                    const void* arcs_device, int64_t row_stride,
+                                                    const void* num_arcs_device, const void* num_nodes_device,
+                                                    const void* arc_weights_device, int A, int max_states,
+                                                    int max_edges, void* scores_device, void* path_len_device,
+                                                    void* path_arcs_device, void* path_tokens_device,
+                                                    void* starts_device, void* ends_device, void* token_scores_device,
+                                                    int P, int64_t out_stride, void* frame_arcs_device,
+                                                    int64_t frame_stride) {
+  return guard([&] {
+    batch_asg_lattice_align(BH(ems), frames, static_cast<const float*>(table_device),
+                            static_cast<const int*>(arcs_device), row_stride, static_cast<const int*>(num_arcs_device),
+                            static_cast<const int*>(num_nodes_device), static_cast<const float*>(arc_weights_device), A,
+                            max_states, max_edges, static_cast<float*>(scores_device),
+                            static_cast<int*>(path_len_device), static_cast<int*>(path_arcs_device),
+                            static_cast<int*>(path_tokens_device), static_cast<int*>(starts_device),
+                            static_cast<int*>(ends_device), static_cast<float*>(token_scores_device), P, out_stride,
+                            static_cast<int*>(frame_arcs_device), frame_stride);
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_asg_lattice_align_stats(int64_t* calls, int64_t* utterances) {
+  return guard([&] { batch_asg_lattice_align_stats(calls, utterances); });
+}
 GTNX_API gtnx_status_t gtnx_batch_asg_token_align(gtnx_batch_t ems, const int* frames, const void* table_device,
                                                   const void* tokens_device, int64_t row_stride,
                                                   const void* lengths_device, int N, int L, int max_length,

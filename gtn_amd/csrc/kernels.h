@@ -1176,6 +1176,34 @@ void asg_lattice_config(int max_states, int* width, int* per_lane);  // the work
 void launch_asg_lattice_forward(const AsgLatticeArgs& a, hipStream_t st);
 void launch_asg_lattice_backward(const AsgLatticeArgs& a, hipStream_t st);
 void launch_asg_lattice_table(const AsgLatticeArgs& a, hipStream_t st);
+// asg_lattice_align.hip: the best (lattice path, alignment) pair (max-plus, of equal candidates the first in the
+// forward's order) of the utterances utt0 .. utt0 + count - 1 in asg_lattice.hip's lattice form under its table (the
+// contract: DESIGN section 39).  One workgroup per utterance, width and arcs per lane from asg_lattice_config(SM); the
+// outputs are CtcLatticeAlignArgs', row b of each written over its whole width, frame_arcs never -1 inside a path (there
+// is no blank); -1 / -inf where no path covers an entry, which is where the forward scores -inf (more than max_edges
+// edges included).  bp: the back-pointers of the launch, the 16-bit source arc of every arc and frame, entry t * SM + a
+// of the utt_stride entries of workgroup blockIdx.x.
+struct AsgLatticeAlignArgs {
+  const GTNX_G float* em;           // [n][M][C]
+  const GTNX_G int* frames;         // [n]
+  const GTNX_G float* table;        // [C + C * C]
+  const GTNX_G int* arcs;           // utterance b's row at arcs + b * row_stride
+  const GTNX_G int* num_arcs;       // [n]
+  const GTNX_G int* num_nodes;      // [n]
+  const GTNX_G float* arc_weights;  // [n][A] or null: all zeros
+  GTNX_G float* scores;             // [n]
+  GTNX_G int* path_len;             // [n]
+  GTNX_G int* path_arcs;            // utterance b's row at path_arcs + b * out_stride, width P
+  GTNX_G int* path_tokens;          // the same
+  GTNX_G int* starts;               // the same
+  GTNX_G int* ends;                 // the same
+  GTNX_G float* token_scores;       // the same, or null
+  GTNX_G int* frame_arcs;           // utterance b's row at frame_arcs + b * frame_stride, width M, or null
+  GTNX_G unsigned short* bp;        // [count][utt_stride]
+  int64_t row_stride, out_stride, frame_stride, utt_stride;
+  int utt0, count, A, SM, P, M, C, max_edges;
+};
+void launch_asg_lattice_align(const AsgLatticeAlignArgs& a, hipStream_t st);
 // ctc_token_align.hip: the best alignment (max-plus, the arithmetic and the tie rule of align.hip) of the pairs pair0 ..
 // pair0 + count - 1 of ctc_score.hip's hypothesis form (the contract: DESIGN section 24).  One workgroup per pair, width
 // and states per lane from ctc_score_config(U); row p of every output is written over its whole width: scores[p] the

@@ -1,7 +1,7 @@
 """PyTorch entry points of the hot path: `ctc_loss`, `asg_loss`, `ctc_forced_align`,
 `asg_forced_align`, `asg_decode`, `ctc_decode`, `ctc_sample`, `ctc_beam_decode`, `asg_beam_decode`, `asg_sample`,
 `edit_distance`, `ctc_score`, `ctc_lattice_score`, `ctc_lattice_loss`, `ctc_lattice_align`, `ctc_token_align`,
-`asg_score`, `asg_lattice_score`, `asg_full_connect`, `asg_lattice_loss` and `asg_token_align`.
+`asg_score`, `asg_lattice_score`, `asg_full_connect`, `asg_lattice_loss`, `asg_lattice_align` and `asg_token_align`.
 
 `ctc_loss` is the device-resident counterpart of the reference's
 bindings/python/examples/pytorch_loss.py:19-102: the emissions tensor never leaves
@@ -47,6 +47,7 @@ _ARGTYPES = {
     "gtn_asg_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
     "gtn_asg_lattice_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_lattice_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "gtn_asg_lattice_align_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "gtn_asg_full_connect_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gtn_asg_beam_decode_n": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P],
     "gtn_asg_sample_n": [_P, _I, _I, _I, _P, _P, _I, C.c_uint64, _F, _P, _P, _P, _P, _P],
@@ -1344,29 +1345,10 @@ class _ASGLatticeScore(torch.autograd.Function):
         return (grad, g_tr, g_st, garc.to(w_dtype) if want_w else None) + none
 
 
-def asg_lattice_score(emissions, transitions, arcs, num_arcs, num_nodes, arc_weights=None, start=None,
-                      input_lengths=None, max_states=None, max_edges=None):
-    """The exact ASG log score of one acyclic token lattice per utterance, differentiable: score[b] = log sum over the
-    lattice's paths p of exp(w(p) + asg_score(emissions[b, :T_b], transitions, labels(p))) -- every word-piece
-    decomposition, pronunciation or optional token the lattice holds and every alignment of each, marginalised in one
-    launch; the lattices are read where they lie on the device.  Nothing is subtracted (`asg_lattice_loss` does that).
-    emissions: float32 CUDA tensor [B, T, C] (any scores), read in place; transitions: [C, C] with transitions[i, j] the
-    score of label j followed by label i; start: [C] scores of the first label (zeros when omitted); arcs, num_arcs,
-    num_nodes, arc_weights and input_lengths are those of `ctc_lattice_score` (arcs sorted by dst; `gtn_amd.pack_lattices`
-    gives this form) -- the states are the arcs: there is no blank and equal neighbouring labels are legal, as in
-    `asg_score`.  max_states (1 .. 4096, default min(2 A + 1, 4096)): the caller's bound on nodes + arcs, the same
-    argument as for `ctc_lattice_score`; max_edges (1 .. 2^21, default min(8 * max_states, 2^21)): the caller's bound on
-    the edges, the sum over the arcs of the in-degree of their src -- the lattices live on the device and the backward
-    sizes its scratch by this bound without a download.  At most 16384 labels.
-    Returns float32 [B].  A score is -inf, with zero gradients and never NaN, when T_b == 0, num_nodes < 1, nodes + arcs
-    > max_states, the lattice has more edges than max_edges, an arc or a weight is invalid as for `ctc_lattice_score`,
-    no alignment fits (a one-node lattice has none: ASG has no empty alignment), or every alignment crosses a -inf
-    emission, transition or start score.
-    The backward is one call with grad_out as per-utterance weights; it returns gradients for emissions, transitions,
-    start and arc_weights (grad_out[b] times the posterior of every arc), computes only those that require grad,
-    recomputes what it needs and sums in a fixed order without atomics, so it has the same bits run to run.  Without
-    requires_grad it never launches.  Runs on the caller's stream."""
-    who = "asg_lattice_score"
+def _asg_lattice_args(who, emissions, transitions, arcs, num_arcs, num_nodes, arc_weights, start, input_lengths,
+                      max_states, max_edges):
+    """what `asg_lattice_score` and `asg_lattice_align` check of their arguments alike.  Returns (A, start (zeros for
+    None), arcs contiguous, num_arcs and num_nodes as int32, frames or None, max_states, max_edges)"""
     x = emissions
     if not (torch.is_tensor(x) and x.dim() == 3 and x.dtype == torch.float32):
         raise ValueError(f"{who}: emissions must be a float32 tensor [B, T, C]")
@@ -1407,6 +1389,36 @@ def asg_lattice_score(emissions, transitions, arcs, num_arcs, num_nodes, arc_wei
     arcs_c = arcs.detach().contiguous()
     na = num_arcs.detach().to(torch.int32).contiguous()  # (int64 counts are converted on the device)
     nn_ = num_nodes.detach().to(torch.int32).contiguous()
+    return A, start, arcs_c, na, nn_, frames, max_states, max_edges
+
+
+def asg_lattice_score(emissions, transitions, arcs, num_arcs, num_nodes, arc_weights=None, start=None,
+                      input_lengths=None, max_states=None, max_edges=None):
+    """The exact ASG log score of one acyclic token lattice per utterance, differentiable: score[b] = log sum over the
+    lattice's paths p of exp(w(p) + asg_score(emissions[b, :T_b], transitions, labels(p))) -- every word-piece
+    decomposition, pronunciation or optional token the lattice holds and every alignment of each, marginalised in one
+    launch; the lattices are read where they lie on the device.  Nothing is subtracted (`asg_lattice_loss` does that).
+    emissions: float32 CUDA tensor [B, T, C] (any scores), read in place; transitions: [C, C] with transitions[i, j] the
+    score of label j followed by label i; start: [C] scores of the first label (zeros when omitted); arcs, num_arcs,
+    num_nodes, arc_weights and input_lengths are those of `ctc_lattice_score` (arcs sorted by dst; `gtn_amd.pack_lattices`
+    gives this form) -- the states are the arcs: there is no blank and equal neighbouring labels are legal, as in
+    `asg_score`.  max_states (1 .. 4096, default min(2 A + 1, 4096)): the caller's bound on nodes + arcs, the same
+    argument as for `ctc_lattice_score`; max_edges (1 .. 2^21, default min(8 * max_states, 2^21)): the caller's bound on
+    the edges, the sum over the arcs of the in-degree of their src -- the lattices live on the device and the backward
+    sizes its scratch by this bound without a download.  At most 16384 labels.
+    Returns float32 [B].  A score is -inf, with zero gradients and never NaN, when T_b == 0, num_nodes < 1, nodes + arcs
+    > max_states, the lattice has more edges than max_edges, an arc or a weight is invalid as for `ctc_lattice_score`,
+    no alignment fits (a one-node lattice has none: ASG has no empty alignment), or every alignment crosses a -inf
+    emission, transition or start score.
+    The backward is one call with grad_out as per-utterance weights; it returns gradients for emissions, transitions,
+    start and arc_weights (grad_out[b] times the posterior of every arc), computes only those that require grad,
+    recomputes what it needs and sums in a fixed order without atomics, so it has the same bits run to run.  Without
+    requires_grad it never launches.  Runs on the caller's stream."""
+    x = emissions
+    A, start, arcs_c, na, nn_, frames, max_states, max_edges = _asg_lattice_args(
+        "asg_lattice_score", emissions, transitions, arcs, num_arcs, num_nodes, arc_weights, start, input_lengths,
+        max_states, max_edges)
+    B = x.shape[0]
     if A == 0:
         # (an empty tensor has no address to hand over: one row that no count reaches stands in for none)
         out = _ASGLatticeScore.apply(x, transitions, start, None, arcs_c.new_zeros(B, 1, 3), torch.zeros_like(na), nn_,
@@ -1507,6 +1519,74 @@ def asg_lattice_loss(emissions, transitions, arcs, num_arcs, num_nodes, arc_weig
     score = asg_lattice_score(emissions, transitions, arcs, num_arcs, num_nodes, arc_weights, start, input_lengths,
                               max_states, max_edges)
     return asg_full_connect(emissions, transitions, start, input_lengths) - score
+
+
+def asg_lattice_align(emissions, transitions, arcs, num_arcs, num_nodes, arc_weights=None, start=None,
+                      input_lengths=None, max_states=None, max_edges=None, max_path=None, return_token_scores=False,
+                      return_frames=False):
+    """Which path of its token lattice an ASG model chose for each utterance, and when each token of that path was
+    spoken: the best (lattice path, alignment) pair -- the maximum over the lattice's paths p and the alignments of
+    labels(p) of w(p) + the start, transition and emission scores -- in one call, the lattices read where they lie on
+    the device.  It is the max-plus partner of `asg_lattice_score`: forced alignment with pronunciation variants, and
+    the chosen word-piece decomposition after training with `asg_lattice_loss`.
+    emissions, transitions, arcs, num_arcs, num_nodes, arc_weights, start (all detached), input_lengths, max_states and
+    max_edges are those of `asg_lattice_score`, so the same tensors serve both; max_path (>= 1, default max(1, min(A,
+    max_states))) is the width P of the path rows.
+    Returns (scores, path_len, path_arcs, path_tokens, starts, ends[, token_scores][, frame_arcs]) on emissions.device:
+      scores        float32 [B]: the best pair's score, -inf without a path;
+      path_len      int32 [B]: the arcs on the best path, 0 without one; a path longer than P keeps its true length;
+      path_arcs     int32 [B, P]: the arc indices in path order (the first P of a longer path);
+      path_tokens   int32 [B, P]: their labels -- with path_len the layout `asg_score`, `asg_token_align` and
+                    `edit_distance` take;
+      starts, ends  int32 [B, P]: the first frame of each arc and one past its last; there are no blank frames, so
+                    starts[0] == 0, ends[i] == starts[i + 1] and the last end is T_b; all four rows hold -1 at and past
+                    path_len and for an utterance without a path;
+      token_scores  float32 [B, P] (return_token_scores): the sum of emissions[b, t, label] over the arc's frames
+                    (emissions only); -inf where starts is -1;
+      frame_arcs    int32 [B, T] (return_frames): the arc index of every frame, -1 from T_b on.
+    An utterance has no path exactly where `asg_lattice_score` with the same arguments gives -inf (a one-node lattice
+    and more edges than max_edges included), so a finite loss always has an alignment.  Float32 max-plus arithmetic; of
+    equal candidates the first in the forward recurrence's order wins (the arc itself, then the arcs entering its source
+    in ascending order): the same bits every time.  This is not `asg_token_align`'s rule (there the step wins a tie and
+    the sum is associated otherwise), so on a chain lattice the two agree in bits only where every sum is exact.  No
+    autograd.  Runs on the caller's stream."""
+    who = "asg_lattice_align"
+    if max_path is not None and int(max_path) < 1:
+        raise ValueError(f"{who}: max_path must be at least 1")
+    A, start, arcs_c, na, nn_, frames, max_states, max_edges = _asg_lattice_args(
+        who, emissions, transitions, arcs, num_arcs, num_nodes, arc_weights, start, input_lengths, max_states, max_edges)
+    P = max(1, min(A, max_states)) if max_path is None else int(max_path)
+    x = emissions.detach().contiguous()
+    B, T, _ = x.shape
+    table = _asg_weights(start, transitions)
+    w = None if arc_weights is None else arc_weights.detach().to(torch.float32).contiguous()
+    if A == 0:
+        # (an empty tensor has no address to hand over: one row that no count reaches stands in for none)
+        A, arcs_c, na, w = 1, arcs_c.new_zeros(B, 1, 3), torch.zeros_like(na), None
+    stream = _engine_stream(x.device)
+    F = max(T, 1)  # (rows without an element are never written, but they need an address)
+    scores = torch.empty(B, dtype=torch.float32, device=x.device)
+    plen = torch.empty(B, dtype=torch.int32, device=x.device)
+    rows = [torch.empty(B, P, dtype=torch.int32, device=x.device) for _ in range(4)]
+    tsc = torch.empty(B, P, dtype=torch.float32, device=x.device) if return_token_scores else None
+    fa = torch.empty(B, F, dtype=torch.int32, device=x.device) if return_frames else None
+    if B == 0:
+        _engine_done(stream)  # (no utterance: nothing to launch, and an empty tensor has no address to hand over)
+    else:
+        native = T == F and _has_native(who, "gtn_asg_lattice_align_n")
+        _route(stream, x, native, "gtn_asg_lattice_align_n",
+               (table.data_ptr(), _host_ptr(frames), arcs_c.data_ptr(), na.data_ptr(), nn_.data_ptr(), _ptr(w), A,
+                max_states, max_edges, P, scores.data_ptr(), plen.data_ptr(), *(r.data_ptr() for r in rows), _ptr(tsc),
+                _ptr(fa)),
+               "asg_lattice_align", table.data_ptr(), arcs_c.data_ptr(), na.data_ptr(), nn_.data_ptr(),
+               scores.data_ptr(), plen.data_ptr(), *(r.data_ptr() for r in rows), _ptr(tsc), _ptr(fa), _ptr(w), frames,
+               max_states, max_edges, A=A, row_stride=3 * A, P=P, out_stride=P, frame_stride=F)
+    out = [scores, plen, *rows]
+    if return_token_scores:
+        out.append(tsc)
+    if return_frames:
+        out.append(fa[:, :T])
+    return tuple(out)
 
 
 def ctc_token_align(log_probs, tokens, lengths, blank=0, input_lengths=None, max_length=None, return_token_scores=False,

@@ -408,6 +408,26 @@ inline void asgLatticeScoreGrad(const Batch& ems, const float* tableDevice, cons
                                                   numArcsDevice, numNodesDevice, arcWeightsDevice, A, maxStates, maxEdges,
                                                   weightsDevice, gradEmissionsDevice, gradTableDevice, arcGradDevice));
 }
+/** The best (lattice path, alignment) pair of one device-resident token lattice per utterance under the ASG criterion
+ *  (asgLatticeScore's inputs, with the same meaning) under the slabs of a Batch::linear, results left on the device.  The
+ *  outputs, their layout and their fills are ctcLatticeAlign's: scoresDevice [n] (-inf without a path), pathLenDevice
+ *  [n]; pathArcsDevice / pathTokensDevice / startsDevice / endsDevice int32 n rows of width P, outStride (>= P) apart, -1
+ *  from pathLen on and without a path; tokenScoresDevice (same layout, or null) the arc's emissions summed in frame
+ *  order; frameArcsDevice (n rows of width M, frameStride >= M apart, or null) the arc of every frame, -1 from T_b on.
+ *  There is no blank: the spans tile 0 .. T_b.  Float32 max-plus, of equal candidates the first in the forward's order
+ *  (not asgTokenAlign's rule): reproducible bit for bit.  An utterance has no path exactly where asgLatticeScore with
+ *  the same arguments gives -inf.  No copy back, no wait -- gtnx_batch_asg_lattice_align */
+inline void asgLatticeAlign(const Batch& ems, const float* tableDevice, const int* arcsDevice, int64_t rowStride,
+                            const int* numArcsDevice, const int* numNodesDevice, const float* arcWeightsDevice, int A,
+                            int maxStates, int maxEdges, float* scoresDevice, int* pathLenDevice, int* pathArcsDevice,
+                            int* pathTokensDevice, int* startsDevice, int* endsDevice, float* tokenScoresDevice, int P,
+                            int64_t outStride, int* frameArcsDevice = nullptr, int64_t frameStride = 0,
+                            const int* frames = nullptr) {
+  detail::check(gtnx_batch_asg_lattice_align(ems.handle(), frames, tableDevice, arcsDevice, rowStride, numArcsDevice,
+                                             numNodesDevice, arcWeightsDevice, A, maxStates, maxEdges, scoresDevice,
+                                             pathLenDevice, pathArcsDevice, pathTokensDevice, startsDevice, endsDevice,
+                                             tokenScoresDevice, P, outStride, frameArcsDevice, frameStride));
+}
 /** numSamples alignments of every chain of a Batch::linear drawn from the posterior of emissions o transitions (forward
  *  filtering, backward sampling; inverse CDF in label order, Philox4x32-10 keyed by `seed`), plus the merge of equal
  *  neighbours, results left on the device: tableDevice float32 [C + C * C] (start scores, then arc C + i * C + j = j ->

@@ -830,6 +830,61 @@ gtnx_status_t gtnx_batch_asg_lattice_score_grad(gtnx_batch_t ems, const int* fra
                                                 void* grad_table_device, void* arc_grad_device);
 /* calls of either kind that have launched so far (process-wide) / utterances they took */
 gtnx_status_t gtnx_batch_asg_lattice_score_stats(int64_t* calls, int64_t* utterances);
+/* The best (lattice path, alignment) pair of those lattices under the ASG criterion: WHICH decomposition or pronunciation
+ * the model chose and WHEN each of its tokens was spoken, for every utterance in one call, results left on the device
+ * (DESIGN section 39).  The inputs are exactly those of gtnx_batch_asg_lattice_score, with the same meaning, the same
+ * state space (the arcs; no blank, equal neighbouring labels legal) and the same rules about what is invalid, so the
+ * same tensors and the same values serve both calls.  Float32 max-plus, the forward recurrence's candidates in its order
+ * and with its association, max for logadd; plus(x, y) is -inf when either operand is:
+ *   frame 0: alpha[a] = plus(plus(w_a, table[lab a]), e(0, lab a)) if src a == 0, else -inf
+ *   frame t: plus(alpha[a], table[C + lab a * C + lab a]) | plus(alpha[a'], plus(w_a, table[C + lab a * C + lab a']))
+ *            for a' entering src a, ascending; x = their maximum; alpha'[a] = x == -inf ? -inf : x + e(t, lab a)
+ *   end:     alpha[a'] for a' entering node K - 1, ascending; the score is their maximum
+ * Of the candidates that reach the maximum the FIRST in that order wins (a later one replaces it only if strictly
+ * greater), a -inf candidate is never chosen and a state whose maximum is -inf is dead: gtnx_batch_ctc_lattice_align's
+ * rule.  Every output is reproducible bit for bit.  It is NOT gtnx_batch_asg_token_align's rule: there the step wins a
+ * tie and the sum is associated as alpha + (w + e), so on a chain lattice the two calls agree in bits only where every
+ * sum is exact.
+ * The outputs, their layout and their fills are gtnx_batch_ctc_lattice_align's:
+ *   scores_device       float32 [n]: w(p) plus the start, transition and emission terms of the best pair, -inf without a
+ *                       path
+ *   path_len_device     int32 [n]: the arcs on the best lattice path (1 .. K - 1), 0 without a path
+ *   path_arcs_device,   int32, n rows of width P (>= 1), out_stride (>= P) elements apart: the arc indices in path order,
+ *   path_tokens_device, their labels, the first frame of each and one past its last; -1 at and past path_len and in
+ *   starts_device,      every entry of an utterance without a path.  There are no blank frames: starts[0] == 0, ends[i]
+ *   ends_device         == starts[i + 1], ends[path_len - 1] == T_b.  A path longer than P keeps its true path_len and
+ *                       writes its first P entries.  path_tokens + path_len have the layout gtnx_batch_asg_score,
+ *                       gtnx_batch_asg_token_align and gtnx_batch_edit_distance take
+ *   token_scores_device float32, same layout, or null: the sum of e(t, label) over the arc's frames (emissions only),
+ *                       added in ascending frame order from the first frame's value; -inf where starts is -1
+ *   frame_arcs_device   int32, n rows of width M, frame_stride (>= M) apart, or null: the arc index of every frame, never
+ *                       -1 inside a path; -1 from T_b on and in every entry of an utterance without a path
+ * Every element of every row is written over the widths P and M, nothing beyond them.  An utterance has no path exactly
+ * where gtnx_batch_asg_lattice_score with the same arguments gives -inf: T_b == 0, num_nodes < 1, nodes +
+ * clamp(num_arcs) > max_states, E_b > max_edges (the kernel keeps nothing per edge; the bound is taken for this rule
+ * alone, so a finite loss always has an alignment), an invalid arc field, a +inf or NaN weight, a one-node lattice,
+ * fewer frames than the shortest path, every alignment through a -inf emission, start or transition entry.  Every arc
+ * field is checked before it becomes an address or an index; nothing at or past num_arcs[b], T_b or a width is read;
+ * the inputs are only read.  NaN or +inf emissions or table entries give unspecified values and no access outside the
+ * utterance's own rows.  At most 16384 labels; table indices are computed in 64 bits.
+ * GTNX_INVALID_ARGUMENT before a device is asked for: what gtnx_batch_asg_lattice_score refuses there, a null scores,
+ * path_len, path_arcs, path_tokens, starts or ends pointer, P < 1, out_stride < P.  A batch without an utterance returns
+ * without touching a device.  With the device: what gtnx_batch_asg_lattice_score refuses there, frame_stride < M with
+ * frame arcs, an output the engine's current device may not write.  A refused call writes nothing.
+ * One workgroup per utterance (asg_lattice_align.hip).  The back-pointers take 16 bits per arc and frame in scratch from
+ * the stream-ordered pool, 2 * max_states * max_b T_b bytes per utterance, at most 256 MiB per launch; beyond that the
+ * utterances run in slices with the same bits (GTNX_ASG_LATTICE_ALIGN_SCRATCH_BYTES, read per call, lowers the cap: a
+ * debug switch for tests); a single utterance above the cap runs alone.  Nothing is copied back, the call does not
+ * wait. */
+gtnx_status_t gtnx_batch_asg_lattice_align(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                           const void* arcs_device, int64_t row_stride, const void* num_arcs_device,
+                                           const void* num_nodes_device, const void* arc_weights_device, int A,
+                                           int max_states, int max_edges, void* scores_device, void* path_len_device,
+                                           void* path_arcs_device, void* path_tokens_device, void* starts_device,
+                                           void* ends_device, void* token_scores_device, int P, int64_t out_stride,
+                                           void* frame_arcs_device, int64_t frame_stride);
+/* calls that have launched so far (process-wide) / utterances they took */
+gtnx_status_t gtnx_batch_asg_lattice_align_stats(int64_t* calls, int64_t* utterances);
 /* The best ASG alignment of those hypotheses: WHEN each token was spoken and how well the frames support it, for all
  * n * N pairs in one call, results left on the device (DESIGN section 28 holds the contract).  The inputs are those of
  * gtnx_batch_asg_score with the same meaning: pair (b, k) is y = tokens[b][k][0 .. len), len = clamp(lengths[b][k], 0,
