@@ -1862,6 +1862,38 @@ def make_api(lib):
                                            int(ref_stride), _opt_ptr(ref_lengths), b, n, l, u, _opt_ptr(dist_out),
                                            _opt_ptr(ops_out)))
 
+    def ctc_loss_step16(emissions, targets, loss_out, grad_out, blank=0, input_lengths=None):
+        """One CTC criterion step over 16-bit emissions in one launch (gtnx_batch_ctc_loss_step16 has the contract).
+        `emissions`: bfloat16 or float16 CUDA tensor [B, T, C], contiguous, read in place; `targets`: B label sequences;
+        `loss_out`: float32 [B]; `grad_out`: [B, T, C], contiguous, of the emissions' dtype (the float32 value rounded
+        to nearest even) or float32; `input_lengths`: B frame counts in 1 .. T, or None.  An utterance whose target does
+        not fit into its frames gets loss +inf and a gradient of zeros; pad rows are never read and their gradient rows
+        are zeros.  A shape outside the launch's range (C a multiple of 8 in 8 .. 4096, at most 511 labels per target)
+        raises ValueError before anything is written.  No copy back and no wait.  The launch runs on the ENGINE's stream
+        (`set_stream`), not on torch's: unless that stream is the one torch works on, whatever torch still has queued
+        on `emissions`, `loss_out` and `grad_out` must be finished first (`torch.cuda.synchronize()`), and
+        `gtn_amd.synchronize()` comes before torch reads the outputs; `gtn_amd.torch_loss.ctc_loss` does both."""
+        codes = {"torch.float16": 1, "torch.bfloat16": 2, "torch.float32": 3}
+        dt, gdt = codes.get(str(emissions.dtype)), codes.get(str(grad_out.dtype))
+        if dt not in (1, 2) or emissions.dim() != 3 or not emissions.is_contiguous():
+            raise ValueError("ctc_loss_step16: emissions must be a contiguous bfloat16 or float16 tensor [B, T, C]")
+        B, T, C_ = emissions.shape
+        if gdt not in (dt, 3) or tuple(grad_out.shape) != (B, T, C_) or not grad_out.is_contiguous():
+            raise ValueError("ctc_loss_step16: grad_out must be contiguous [B, T, C], of the emissions' dtype or float32")
+        if str(loss_out.dtype) != "torch.float32" or loss_out.numel() != B or not loss_out.is_contiguous():
+            raise ValueError("ctc_loss_step16: loss_out must be a float32 contiguous tensor [B]")
+        if len(targets) != B:
+            raise ValueError(f"ctc_loss_step16: {len(targets)} target sequences for a batch of {B}")
+        for name, t in (("emissions", emissions), ("loss_out", loss_out), ("grad_out", grad_out)):
+            if not t.is_cuda:
+                raise ValueError(f"ctc_loss_step16: {name} must be a CUDA tensor")
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int32).reshape(-1) for t in targets])
+                                    if B else np.zeros(0, np.int32), dtype=np.int32)
+        lens = np.ascontiguousarray([len(t) for t in targets], dtype=np.int32)
+        fr, fr_ptr = _frames_arg("ctc_loss_step16", input_lengths, B)
+        check(lib.gtnx_batch_ctc_loss_step16(emissions.data_ptr(), dt, flat.ctypes.data, lens.ctypes.data, fr_ptr, B, T,
+                                             C_, int(blank), loss_out.data_ptr(), grad_out.data_ptr(), gdt))
+
     def debug_ctc_lattice_score_stats():
         """(calls, utterances): calls of Batch.ctc_lattice_score / Batch.ctc_lattice_score_grad that have launched so
         far and the utterances they took (include/gtn_amd.h: gtnx_batch_ctc_lattice_score_stats)"""
@@ -1907,6 +1939,7 @@ def make_api(lib):
     ns.debug_asg_beam_stats = debug_asg_beam_stats
     ns.debug_asg_sample_stats = debug_asg_sample_stats
     ns.edit_distance = edit_distance
+    ns.ctc_loss_step16 = ctc_loss_step16
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties
     if hasattr(lib, "gtnx_debug_shortest_routes"):  # (the engine's kernels: not in the reference-backed shim)

@@ -68,6 +68,23 @@ GTN_EXPORT int gtn_ctc_loss_frames_n(const void* emissions, const int* targets, 
   });
 }
 
+// The same over 16-bit emissions in one launch (gtn::criteria::ctcLossBatch16): emissions DEVICE [B][T][C] of `dtype`
+// (1: IEEE half, 2: bfloat16); frames: host int32 [B] or null; loss: DEVICE float [B]; grad: DEVICE [B][T][C] of
+// grad_dtype (`dtype`, or 3: float32).  gtn_ctc_loss16_ok_n: 1 when the batch is in the launch's range, else 0 (a pure
+// host function).
+GTN_EXPORT int gtn_ctc_loss16_n(const void* emissions, int dtype, const int* targets, const int* lengths, int B, int T,
+                                int C, int blank, const int* frames, void* loss, void* grad, int grad_dtype) {
+  return guarded([&] {
+    gtn::criteria::ctcLossBatch16(emissions, dtype, targets, lengths, B, T, C, blank, loss, grad, grad_dtype, frames);
+  });
+}
+GTN_EXPORT int gtn_ctc_loss16_ok_n(const void* emissions, const int* targets, const int* lengths, int B, int T, int C,
+                                   int blank, const int* frames, const void* grad) {
+  int ok = 0;
+  guarded([&] { ok = gtn::criteria::ctcLossBatch16Ok(emissions, targets, lengths, B, T, C, blank, grad, frames) ? 1 : 0; });
+  return ok;
+}
+
 // CTC forced alignment.  emissions: DEVICE float [B][T][C]; targets / lengths: host int32 (concatenated / [B]);
 // frames: host int32 [B] or null; labels: DEVICE int32 [B][T]; tokens: DEVICE int32 [B][T] or null; scores: DEVICE
 // float [B] or null.

@@ -150,6 +150,21 @@ inline void ctcLossBatch(
   ctcLossBatch(emissions, flat.data(), len.data(), (int)targets.size(), T, C, blank, lossDev, gradDev, targetGrad, times);
 }
 
+/** The same criterion over bfloat16 / float16 emissions (`dtype`: GTNX_DTYPE_F16 / GTNX_DTYPE_BF16), one launch for
+ *  the whole step, padded batches and targets of up to 511 labels included: `emissions` device [B][T][C] of `dtype`,
+ *  read in place and converted exactly; `lossDev` device float [B]; `gradDev` device [B][T][C] of `gradDtype` (`dtype`,
+ *  rounded to nearest even, or GTNX_DTYPE_F32); `frames` host [B] or null.  An utterance whose target does not fit into
+ *  its frames has loss +inf and a gradient of zeros.  A batch outside the launch's range (ctcLossBatch16Ok) throws: the
+ *  caller converts to float32 and calls ctcLossBatch. */
+inline bool ctcLossBatch16Ok(const void* emissions, const int* labels, const int* lengths, int B, int T, int C, int blank,
+                             const void* gradDev, const int* frames = nullptr) {
+  return batched::ctcLossStep16Ok(labels, lengths, frames, B, T, C, blank, emissions, gradDev);
+}
+inline void ctcLossBatch16(const void* emissions, int dtype, const int* labels, const int* lengths, int B, int T, int C,
+                           int blank, void* lossDev, void* gradDev, int gradDtype, const int* frames = nullptr) {
+  batched::ctcLossStep16(emissions, dtype, labels, lengths, frames, B, T, C, blank, lossDev, gradDev, gradDtype);
+}
+
 /** CTC forced alignment of a batch, results on the device: per utterance the best path of target_b ∩ emissions_b
  *  (viterbiPath, shortest.cpp:190-272) as the label of every frame (`labels`, device int32 [B][T]), the index of the
  *  frame's token in the target, -1 on blank frames (`tokens`, device int32 [B][T] or null) and the path score

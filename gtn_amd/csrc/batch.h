@@ -128,6 +128,16 @@ bool ctc_step_fused_ok(const int* labels, const int* lengths, int n, int T, int 
                        const void* grad);
 void batch_ctc_loss_step(const void* emissions, const int* labels, const int* lengths, int n, int T, int C, int blank,
                          void* loss, void* grad, bool target_grad, void* target_grad_dev);
+// The same step over bfloat16 / float16 emissions (dtype: GTNX_DTYPE_F16 / GTNX_DTYPE_BF16) in ONE launch
+// (ctc_step16.hip), over a padded batch when `frames` (host [n], 1 .. T) is given: float32 losses, the gradient in the
+// emissions' type or in float32 (grad_dtype), its pad rows zero; an utterance without an alignment has loss +inf and a
+// slab of zeros.  ctc_step16_ok: is the batch in the launch's range (C a multiple of 8 in 8 .. 4096, targets up to 511
+// labels, T up to 2^20, labels and frame counts valid, both slabs 16-byte aligned)?  A pure host function;
+// batch_ctc_loss_step16 throws GTNX_INVALID_ARGUMENT before anything is launched for a batch it is not.
+bool ctc_step16_ok(const int* labels, const int* lengths, const int* frames, int n, int T, int C, int blank,
+                   const void* emissions, const void* grad);
+void batch_ctc_loss_step16(const void* emissions, int dtype, const int* labels, const int* lengths, const int* frames,
+                           int n, int T, int C, int blank, void* loss, void* grad, int grad_dtype);
 BatchP batch_asg_force_align(const int* labels, const int* lengths, int n, Graph& transitions, int n_labels);
 // rows (host, [n], or null): the rows of each element that count (Batch::rows); outside 1 .. M: invalid argument
 BatchP batch_linear(int n, int M, int C, bool calc_grad, const void* dev, bool borrow, const int* rows = nullptr);

@@ -1784,4 +1784,110 @@ void batch_asg_token_align(const BatchP& ems, const int* frames, const float* ta
   g_asg_token_align.add(1, pairs);
 }
 
+// ---- one CTC criterion step over bfloat16 / float16 emissions in one launch (ctc_step16.hip) ----
+namespace {
+// the alpha planes and the row log-sum-exps of one launch
+constexpr ScratchCap kCtcStep16Scratch{"GTNX_CTC_STEP16_SCRATCH_BYTES", int64_t(256) << 20};
+bool dtype16(int dtype) { return dtype == GTNX_DTYPE_F16 || dtype == GTNX_DTYPE_BF16; }
+}  // namespace
+
+bool ctc_step16_ok(const int* labels, const int* lengths, const int* frames, int n, int T, int C, int blank,
+                   const void* emissions, const void* grad) {
+  if (n <= 0 || !lengths || !emissions || !grad) return false;
+  if (T < 1 || T > (1 << 20) || C < kCtcStep16MinC || C > kCtcStep16MaxC || C % 8 != 0) return false;
+  if (blank < 0 || blank >= C) return false;
+  // (rows travel in 16-byte pieces of eight elements)
+  if ((reinterpret_cast<uintptr_t>(emissions) & 15) != 0 || (reinterpret_cast<uintptr_t>(grad) & 15) != 0) return false;
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (lengths[i] < 0 || lengths[i] > kCtcStep16MaxU) return false;
+    if (frames && (frames[i] < 1 || frames[i] > T)) return false;
+    total += lengths[i];
+  }
+  if (total > 0 && !labels) return false;
+  for (int64_t i = 0; i < total; ++i)
+    if (labels[i] < 0 || labels[i] >= C) return false;
+  return true;
+}
+
+void batch_ctc_loss_step16(const void* emissions, int dtype, const int* labels, const int* lengths, const int* frames,
+                           int n, int T, int C, int blank, void* loss, void* grad, int grad_dtype) {
+  GTNX_HOST_T("batch.ctc_loss_step16");
+  const char* who = "gtnx_batch_ctc_loss_step16";
+  if (n <= 0) refuse(who, "the batch size must be positive");
+  if (!emissions || !lengths || !loss || !grad) refuse(who, "null emissions, lengths, loss or gradient");
+  if (!dtype16(dtype)) refuse(who, "the emissions must be GTNX_DTYPE_F16 or GTNX_DTYPE_BF16");
+  if (grad_dtype != dtype && grad_dtype != GTNX_DTYPE_F32) refuse(who, "the gradient must have the emissions' type or GTNX_DTYPE_F32");
+  if (T < 1 || C < 1) refuse(who, "T and C must be positive");
+  for (int i = 0; i < n; ++i) {
+    if (lengths[i] < 0) refuse(who, "negative length");
+    if (frames && (frames[i] < 1 || frames[i] > T)) refuse(who, "a frame count outside 1 .. T");
+  }
+  if ((reinterpret_cast<uintptr_t>(emissions) & 15) != 0 || (reinterpret_cast<uintptr_t>(grad) & 15) != 0)
+    refuse(who, "emissions and gradient must be 16-byte aligned");
+  if (!ctc_step16_ok(labels, lengths, frames, n, T, C, blank, emissions, grad))
+    refuse(who, "not a batch the 16-bit step takes (gtnx_batch_ctc_loss_step16_ok)");
+  Runtime& rt = Runtime::get();
+  check_outputs_local(who, {loss, grad});
+  int max_u = 0;
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    max_u = std::max(max_u, lengths[i]);
+    total += lengths[i];
+  }
+  // ---- staging, one pinned block: [n] entries {label offset, U, T_b, 0} | labels.  The kernel reads it in place up to
+  // the size a kernel of ours may fetch from pinned memory (runtime.cpp: h2d_pinned); a larger one is copied first.
+  const size_t ent_bytes = align_up(sizeof(int) * 4 * size_t(n), 256);
+  const size_t stage_bytes = ent_bytes + sizeof(int) * size_t(total ? total : 1);
+  PinnedMemP pin = rt.alloc_pinned(stage_bytes);
+  int* ent = pin->as<int>();
+  if (total) std::memcpy(pin->as<int>(ent_bytes), labels, sizeof(int) * size_t(total));
+  int64_t lab_off = 0;
+  double frames_sum = 0;
+  for (int i = 0; i < n; ++i) {
+    // (label offsets count from the labels' start; a slice moves `stage` and keeps `labels`)
+    ent[4 * i + 0] = int(lab_off);
+    ent[4 * i + 1] = lengths[i];
+    ent[4 * i + 2] = frames ? frames[i] : T;
+    ent[4 * i + 3] = 0;
+    lab_off += lengths[i];
+    frames_sum += ent[4 * i + 2];
+  }
+  const char* lim_env = std::getenv("GTNX_H2D_KERNEL_BYTES");
+  const size_t in_place = lim_env ? size_t(std::atol(lim_env)) : size_t(1) << 20;
+  DevMemP stage_dev;
+  const char* stage = pin->as<char>();
+  if (stage_bytes > in_place) {
+    stage_dev = rt.alloc(stage_bytes);
+    rt.h2d_pinned(stage_dev->ptr, pin->ptr, stage_bytes);
+    stage = stage_dev->as<char>();
+  }
+  const int NS = int(align_up(size_t(2 * max_u + 1), 16));
+  const int64_t alpha_stride = int64_t(T + 1) * NS;  // floats
+  const int64_t per_utt = 4 * (alpha_stride + int64_t(align_up(size_t(T), 16)));
+  const size_t esz = 2, gsz = grad_dtype == GTNX_DTYPE_F32 ? 4 : 2;
+  CtcStep16Desc d{};
+  d.labels = reinterpret_cast<const int*>(stage + ent_bytes);
+  d.alpha_stride = alpha_stride;
+  d.T = T;
+  d.C = C;
+  d.blank = blank;
+  d.NS = NS;
+  d.max_u = max_u;
+  d.bf16 = dtype == GTNX_DTYPE_BF16 ? 1 : 0;
+  const double bytes_per_frame = double(2 * esz + gsz) * C + 8.0 * NS;
+  for_pair_slices(n, per_utt, kCtcStep16Scratch, [&](int64_t b0, int64_t cnt) {
+    DevMemP scratch = rt.alloc(size_t(per_utt * cnt));
+    d.stage = reinterpret_cast<const int*>(stage) + 4 * b0;
+    d.em = reinterpret_cast<const uint16_t*>(static_cast<const char*>(emissions) + size_t(b0) * T * C * esz);
+    d.grad = static_cast<char*>(grad) + size_t(b0) * T * C * gsz;
+    d.loss = static_cast<float*>(loss) + b0;
+    d.alpha = scratch->as<float>();
+    d.rowlse = scratch->as<float>(size_t(4 * alpha_stride * cnt));
+    GTNX_PROF("ctc_step16", bytes_per_frame * frames_sum * double(cnt) / double(n));
+    launch_ctc_step16(d, int(cnt), grad_dtype == GTNX_DTYPE_F32, rt.stream());
+    // (the scratch goes back to the stream-ordered pool behind the launch)
+  });
+}
+
 }  // namespace gtnx

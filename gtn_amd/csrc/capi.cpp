@@ -820,6 +820,20 @@ GTNX_API gtnx_status_t gtnx_batch_ctc_loss_step_ok(const int* labels, const int*
     *ok = ctc_step_fused_ok(labels, lengths, n, T, C, blank, emissions, grad) ? 1 : 0;
   });
 }
+GTNX_API gtnx_status_t gtnx_batch_ctc_loss_step16(const void* emissions, int dtype, const int* labels, const int* lengths,
+                                                  const int* frames, int n, int T, int C, int blank, void* loss,
+                                                  void* grad, int grad_dtype) {
+  return guard([&] {
+    batch_ctc_loss_step16(emissions, dtype, labels, lengths, frames, n, T, C, blank, loss, grad, grad_dtype);
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_ctc_loss_step16_ok(const int* labels, const int* lengths, const int* frames, int n, int T,
+                                                     int C, int blank, const void* emissions, const void* grad, int* ok) {
+  return guard([&] {
+    if (!ok) throw_invalid("[gtnx_batch_ctc_loss_step16_ok] null result pointer");
+    *ok = ctc_step16_ok(labels, lengths, frames, n, T, C, blank, emissions, grad) ? 1 : 0;
+  });
+}
 GTNX_API gtnx_status_t gtnx_batch_asg_force_align(const int* labels, const int* lengths, int n, gtnx_graph_t transitions,
                                                   int n_labels, gtnx_batch_t* out) {
   return guard([&] { *out = HB(batch_asg_force_align(labels, lengths, n, G(transitions), n_labels)); });

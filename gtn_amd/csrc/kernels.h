@@ -681,6 +681,24 @@ struct CtcStepDesc {
 int band_block_rows(int C, int max_NS, bool backward);
 bool ctc_step_cell(int C, int max_NS);  // is there an instantiated cell for rows of C labels and targets of max_NS (row stride) nodes?
 void launch_ctc_step(const CtcStepDesc& d, int n, int max_NS, bool gradg, hipStream_t st);
+// One CTC criterion step over bfloat16 / float16 emissions in ONE launch (ctc_step16.hip): workgroup b streams utterance
+// b's T_b rows through a ring of kCtcStep16Ring raw rows in LDS, runs both sweeps over the 2 U_b + 1 states and stores
+// loss_b and the gradient slab, pad rows included, in the emissions' type or in float32.  Travels by value; every
+// pointer is that of the launch's first utterance.
+constexpr int kCtcStep16MaxU = 511, kCtcStep16MinC = 8, kCtcStep16MaxC = 4096, kCtcStep16Ring = 8;
+struct CtcStep16Desc {
+  const GTNX_G int* stage;      // [count] entries {label offset, U, T_b, 0}: pinned host memory read in place, or a copy
+  const GTNX_G int* labels;     // the label sequences back to back, next to `stage`
+  const GTNX_G uint16_t* em;    // [count][T][C], bfloat16 (bf16 != 0) or IEEE half
+  GTNX_G void* grad;            // [count][T][C], the emissions' type or float32 (launch_ctc_step16: grad32)
+  GTNX_G float* loss;           // [count]
+  GTNX_G float* alpha;          // [count] planes of [T][NS] floats
+  GTNX_G float* rowlse;         // [count][T]
+  int64_t alpha_stride;         // floats between planes
+  int T, C, blank, NS, max_u, bf16;  // max_u: the longest target of the CALL (it sizes the LDS and the states per lane)
+};
+size_t ctc_step16_lds(int C, int max_u);
+void launch_ctc_step16(const CtcStep16Desc& d, int count, bool grad32, hipStream_t st);
 // one force-alignment acceptor o transitions per label sequence (examples/asg.cpp:50-68), as band records
 struct AsgFalArgs {
   const GTNX_G int* labels;      // [U]

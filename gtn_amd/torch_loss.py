@@ -26,6 +26,8 @@ _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 _ARGTYPES = {
     "gtn_ctc_loss_n": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
     "gtn_ctc_loss_frames_n": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "gtn_ctc_loss16_n": [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I],
+    "gtn_ctc_loss16_ok_n": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
     "gtn_asg_loss_n": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "gtn_asg_loss_frames_n": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gtn_ctc_align_n": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
@@ -260,6 +262,61 @@ class _CTCLoss(torch.autograd.Function):
         return (grad * scale, None, None, None) + ((None,) if ctx.ragged else ())
 
 
+_DTYPE16 = {torch.float16: 1, torch.bfloat16: 2}  # (the dtype codes of include/gtn_amd.h)
+
+
+class _CTCLoss16(torch.autograd.Function):
+    """the whole step on bfloat16 / float16 emissions in one launch (gtn_ctc_loss16_n): float32 losses, the gradient in
+    the emissions' dtype, computed with the forward pass"""
+
+    @staticmethod
+    def forward(ctx, x, flat, lens, blank, reduction, frames):
+        B = x.shape[0]
+        stream = _engine_stream(x.device)
+        out = torch.empty(B, dtype=torch.float32, device=x.device)
+        grad = torch.empty_like(x)
+        code = _DTYPE16[x.dtype]
+        _call("gtn_ctc_loss16_n", x.data_ptr(), code, flat.ctypes.data, lens.ctypes.data, *x.shape, int(blank),
+              _host_ptr(frames), out.data_ptr(), grad.data_ptr(), code)
+        _engine_done(stream)
+        ctx.grad, ctx.reduction = grad, reduction
+        return out.mean() if reduction == "mean" else (out.sum() if reduction == "sum" else out)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        B = ctx.grad.shape[0]
+        if ctx.reduction == "none":
+            scale = grad_out.reshape(B, 1, 1)
+        else:
+            scale = (grad_out / B if ctx.reduction == "mean" else grad_out).reshape(1, 1, 1)
+        # (one pass that reads and writes 16-bit elements: the product is formed in float32 inside the kernel and
+        #  rounded once, so a scale of 1 returns the launch's bits)
+        return torch.mul(ctx.grad, scale, out=torch.empty_like(ctx.grad)), None, None, None, None, None
+
+
+def _ctc_loss16(log_probs, targets, blank, reduction, input_lengths):
+    """ctc_loss on bfloat16 / float16 emissions: the one-launch 16-bit step where the batch is in its range, else the
+    float32 path around a cast, with the gradients of utterances without an alignment set to 0 as the step does"""
+    if not (log_probs.is_cuda and log_probs.dim() == 3):
+        raise ValueError("ctc_loss: log_probs must be a CUDA tensor [B, T, C]")
+    B, T, C_ = log_probs.shape
+    if len(targets) != B:
+        raise ValueError(f"ctc_loss: {len(targets)} target sequences for a batch of {B}")
+    frames = None if input_lengths is None else _frame_counts("ctc_loss", input_lengths, B, T, 1)
+    if _has_native("ctc_loss on 16-bit emissions", "gtn_ctc_loss16_n"):
+        x = log_probs.contiguous()
+        flat, lens = _flat_targets(targets)
+        if B and _native().gtn_ctc_loss16_ok_n(x.data_ptr(), flat.ctypes.data, lens.ctypes.data, B, T, C_, int(blank),
+                                               _host_ptr(frames), x.data_ptr()):
+            return _CTCLoss16.apply(x, flat, lens, blank, reduction, frames)
+    x32 = log_probs.float()
+    losses = ctc_loss(x32, targets, blank, "none", input_lengths)
+    if x32.requires_grad:
+        dead = ~torch.isfinite(losses.detach()).reshape(B, 1, 1)
+        x32.register_hook(lambda g: g.masked_fill(dead, 0.0))
+    return losses.mean() if reduction == "mean" else (losses.sum() if reduction == "sum" else losses)
+
+
 def _frame_counts(name, input_lengths, B, T, low):
     """per-utterance frame counts as a host int32 array [B], each in low .. T (low None: the engine checks the range)"""
     vals = input_lengths.tolist() if hasattr(input_lengths, "tolist") else list(input_lengths)
@@ -315,7 +372,14 @@ def ctc_loss(log_probs, targets, blank=0, reduction="none", input_lengths=None):
     counts (1 .. T) for a padded batch, or None: utterance b's loss is that of log_probs[b, :T_b]
     (+inf when its target does not fit into T_b frames), rows past T_b are never read and their
     gradient is 0.  Returns per-utterance losses (or their mean / sum over B); differentiable
-    w.r.t. log_probs."""
+    w.r.t. log_probs.
+    A bfloat16 or float16 tensor (what autocast hands over) is taken as it is: the losses are float32, log_probs.grad
+    has the tensor's dtype, and a batch with C a multiple of 8 in 8 .. 4096 and targets of at most 511 labels runs as
+    ONE launch that reads 16-bit rows and writes 16-bit gradient rows, padded batches included; any other shape is
+    cast to float32 and back inside.  On either route an utterance whose target does not fit has loss +inf and a
+    gradient of zeros."""
+    if log_probs.dtype in _DTYPE16:
+        return _ctc_loss16(log_probs, targets, blank, reduction, input_lengths)
     if input_lengths is None:
         return _CTCLoss.apply(log_probs, targets, blank, reduction)
     frames = _frame_counts("ctc_loss", input_lengths, log_probs.shape[0], log_probs.shape[1], 1)

@@ -518,6 +518,21 @@ inline void ctcLossStep(const void* emissionsDevice, const int* labels, const in
   detail::check(gtnx_batch_ctc_loss_step(emissionsDevice, labels, lengths, n, T, C, blank, lossDevice, gradDevice,
                                          targetGrad ? 1 : 0, targetGradDevice));
 }
+/** The CTC criterion step over bfloat16 / float16 emissions in ONE launch, padded batches included
+ *  (gtnx_batch_ctc_loss_step16 has the contract): dtype GTNX_DTYPE_F16 / GTNX_DTYPE_BF16, frames host [n] or null,
+ *  float32 losses, the gradient in gradDtype (the emissions' type or GTNX_DTYPE_F32).  ctcLossStep16Ok (a pure host
+ *  function) says whether the batch is in the launch's range. */
+inline bool ctcLossStep16Ok(const int* labels, const int* lengths, const int* frames, int n, int T, int C, int blank,
+                            const void* emissionsDevice, const void* gradDevice) {
+  int ok = 0;
+  detail::check(gtnx_batch_ctc_loss_step16_ok(labels, lengths, frames, n, T, C, blank, emissionsDevice, gradDevice, &ok));
+  return ok != 0;
+}
+inline void ctcLossStep16(const void* emissionsDevice, int dtype, const int* labels, const int* lengths, const int* frames,
+                          int n, int T, int C, int blank, void* lossDevice, void* gradDevice, int gradDtype) {
+  detail::check(gtnx_batch_ctc_loss_step16(emissionsDevice, dtype, labels, lengths, frames, n, T, C, blank, lossDevice,
+                                           gradDevice, gradDtype));
+}
 } // namespace batched
 
 } // namespace gtn

@@ -276,6 +276,24 @@ gtnx_status_t gtnx_batch_ctc_loss_step(const void* emissions, const int* labels,
                                        int blank, void* loss, void* grad, int target_grad, void* target_grad_dev);
 gtnx_status_t gtnx_batch_ctc_loss_step_ok(const int* labels, const int* lengths, int n, int T, int C, int blank,
                                           const void* emissions, const void* grad, int* ok);
+/* The same step over 16-bit emissions in ONE launch, padded batches included: emissions DEVICE [n][T][C] of `dtype`
+ * (GTNX_DTYPE_F16: IEEE half, GTNX_DTYPE_BF16: bfloat16), converted exactly; frames: host [n] frame counts in 1 .. T, or
+ * NULL (all T); loss: DEVICE float [n]; grad: DEVICE [n][T][C] of grad_dtype, which is `dtype` (the float32 value
+ * rounded to nearest even) or GTNX_DTYPE_F32.  loss[b] is that of emissions[b][:frames[b]]; rows past frames[b] are
+ * never read and their gradient rows are zeros.  An utterance whose target does not fit into its frames, or with a row
+ * without a finite entry, has loss +inf and a gradient slab of zeros.  Float32 arithmetic in a fixed order: the same
+ * bits run to run and however the call is cut into launches.  GTNX_INVALID_ARGUMENT before anything is launched or
+ * written for n <= 0, a null pointer, another dtype, or a batch for which gtnx_batch_ctc_loss_step16_ok says 0: C not a
+ * multiple of 8 in 8 .. 4096, a target longer than 511 labels, T above 2^20, a label or blank outside 0 .. C-1, a frame
+ * count outside 1 .. T, emissions or grad not 16-byte aligned.  The predicate is a pure host function. */
+#define GTNX_DTYPE_F16 1
+#define GTNX_DTYPE_BF16 2
+#define GTNX_DTYPE_F32 3
+gtnx_status_t gtnx_batch_ctc_loss_step16(const void* emissions, int dtype, const int* labels, const int* lengths,
+                                         const int* frames, int n, int T, int C, int blank, void* loss, void* grad,
+                                         int grad_dtype);
+gtnx_status_t gtnx_batch_ctc_loss_step16_ok(const int* labels, const int* lengths, const int* frames, int n, int T, int C,
+                                            int blank, const void* emissions, const void* grad, int* ok);
 /* compose(forceAlign(target), transitions) of examples/asg.cpp:50-68 for n label sequences, built
  * on the device: `transitions` must have the arc layout of examples/asg.cpp:36-47 over n_labels labels
  * (arc i: start -> label i; arc n_labels + i * n_labels + j: label j -> label i); its weights are
