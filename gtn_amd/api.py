@@ -1500,6 +1500,51 @@ def make_api(lib):
                                                 _opt_ptr(tok), stride, _opt_ptr(ln), N, L, U, _opt_ptr(weights),
                                                 _opt_ptr(grad_out), _opt_ptr(grad_table_out)))
 
+        def asg_full_score(self, table, scores_out, frames=None):
+            """The ASG full-connect score -- the criterion's normaliser -- of every utterance of a padded Batch.linear for
+            1 .. 1024 labels, left on the device (gtnx_batch_asg_full_score; DESIGN section 41 holds the contract):
+            scores_out[b] = forwardScore(emissions_b[:T_b] o asgTransitions(table)), float32 [B].  `table` is that of
+            `asg_score`; `frames`: host counts T_b in 0 .. M or None.  -inf, never NaN: T_b == 0, no finite path.  Rows
+            from T_b on are never read.  Two launches whatever the frame counts are, no copy back and no wait."""
+            who = "asg_full_score"
+            fr, fr_ptr = _frames_arg(who, frames, len(self))
+            table = self._asg_score_table(who, table)
+            if scores_out is not None and hasattr(scores_out, "data_ptr"):
+                if (str(scores_out.dtype) != "torch.float32" or not scores_out.is_contiguous()
+                        or scores_out.numel() != len(self)):
+                    raise ValueError(f"{who}: scores_out must be a float32 contiguous tensor [B]")
+                if len(self) == 0:
+                    return
+            check(lib.gtnx_batch_asg_full_score(self._h, fr_ptr, _opt_ptr(table), _opt_ptr(scores_out)))
+
+        def asg_full_score_grad(self, table, weights, grad_out=None, grad_table_out=None, frames=None):
+            """The gradients of the scores of `asg_full_score` under `weights` (float32 [B] on the device), in one
+            stateless call (gtnx_batch_asg_full_score_grad): `grad_out` (float32 [B, M, C] or None) = weights[b] * d
+            score[b] / d emissions[b], every element written (rows from T_b on with zeros); `grad_table_out` (float32
+            [C + C * C] or None) = sum over b of weights[b] * d score[b] / d table; not both None.  Utterances with a
+            -inf score or a weight of exactly 0 add exact zeros.  The planes are recomputed into pooled scratch (sliced
+            beyond 2.5 GiB in whole blocks of 16 utterances, same bits); no atomics, the same bits run to run."""
+            who = "asg_full_score_grad"
+            fr, fr_ptr = _frames_arg(who, frames, len(self))
+            table = self._asg_score_table(who, table)
+            if grad_out is None and grad_table_out is None:
+                raise ValueError(f"{who}: neither grad_out nor grad_table_out given")
+            n = len(self)
+            m, c = C.c_int(-1), C.c_int(-1)
+            check(lib.gtnx_batch_linear_shape(self._h, C.byref(m), C.byref(c)))
+            known = m.value >= 0
+            for o, count, what in ((weights, n, "weights must be a float32 contiguous tensor [B]"),
+                                   (grad_out, n * m.value * c.value if known else None,
+                                    "grad_out must be a float32 contiguous tensor [B, M, C]"),
+                                   (grad_table_out, c.value + c.value * c.value if known else None,
+                                    "grad_table_out must be a float32 contiguous tensor [C + C * C]")):
+                if o is not None and hasattr(o, "data_ptr"):
+                    if (str(o.dtype) != "torch.float32" or not o.is_contiguous()
+                            or (count is not None and o.numel() != count)):
+                        raise ValueError(f"{who}: {what}")
+            check(lib.gtnx_batch_asg_full_score_grad(self._h, fr_ptr, _opt_ptr(table), _opt_ptr(weights),
+                                                     _opt_ptr(grad_out), _opt_ptr(grad_table_out)))
+
         def asg_lattice_score(self, table, arcs, num_arcs, num_nodes, scores_out, arc_weights=None, frames=None,
                               max_states=None, max_edges=None, A=None, row_stride=None):
             """The exact ASG log score of one device-resident acyclic token lattice per utterance under the slabs of a
@@ -1904,6 +1949,11 @@ def make_api(lib):
         (include/gtn_amd.h: gtnx_batch_ctc_lattice_align_stats)"""
         return _stats2(lib.gtnx_batch_ctc_lattice_align_stats)
 
+    def debug_asg_full_score_stats():
+        """(calls, utterances): calls of Batch.asg_full_score / Batch.asg_full_score_grad that have launched so far and
+        the utterances they took (include/gtn_amd.h: gtnx_batch_asg_full_score_stats)"""
+        return _stats2(lib.gtnx_batch_asg_full_score_stats)
+
     def debug_asg_lattice_score_stats():
         """(calls, utterances): calls of Batch.asg_lattice_score / Batch.asg_lattice_score_grad that have launched so
         far and the utterances they took (include/gtn_amd.h: gtnx_batch_asg_lattice_score_stats)"""
@@ -1933,6 +1983,7 @@ def make_api(lib):
     ns.debug_ctc_lattice_score_stats = debug_ctc_lattice_score_stats
     ns.debug_ctc_lattice_align_stats = debug_ctc_lattice_align_stats
     ns.debug_asg_score_stats = debug_asg_score_stats
+    ns.debug_asg_full_score_stats = debug_asg_full_score_stats
     ns.debug_asg_lattice_score_stats = debug_asg_lattice_score_stats
     ns.debug_asg_lattice_align_stats = debug_asg_lattice_align_stats
     ns.debug_asg_token_align_stats = debug_asg_token_align_stats

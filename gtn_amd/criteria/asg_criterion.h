@@ -244,6 +244,39 @@ inline void asgScoreBatch(
   }
 }
 
+/** The full-connect scores of the B padded utterances (1 .. 1024 labels), and (with weightsDev and at least one of
+ *  gradEmDev / gradTableDev) their gradients under those weights: `emissions` device float32 [B][T][N_], read in place;
+ *  `tableDev` device float32 [N_ + N_ * N_] as for asgScoreBatch; `frames` host [B] or null; `scoresDev` device float32
+ *  [B] or null; `weightsDev` device float32 [B]; `gradEmDev` device float32 [B][T][N_] or null; `gradTableDev` device
+ *  float32 [N_ + N_ * N_] or null.  gtnx_batch_asg_full_score / _grad have the contract.  Nothing is copied back. */
+inline void asgFullScoreBatch(
+    const void* emissions,
+    int B,
+    int T,
+    int N_,
+    const void* tableDev,
+    const int* frames,
+    void* scoresDev,
+    const void* weightsDev = nullptr,
+    void* gradEmDev = nullptr,
+    void* gradTableDev = nullptr) {
+  const bool wantGrad = gradEmDev || gradTableDev;
+  if ((weightsDev != nullptr) != wantGrad) {
+    throw std::invalid_argument("asgFullScoreBatch: weights and a gradient come together");
+  }
+  if (!scoresDev && !wantGrad) {
+    throw std::invalid_argument("asgFullScoreBatch: neither scores nor a gradient asked for");
+  }
+  Batch ems = Batch::linear(B, T, N_, emissions, /*calcGrad=*/false, /*borrow=*/true);
+  if (scoresDev) {
+    batched::asgFullScore(ems, static_cast<const float*>(tableDev), static_cast<float*>(scoresDev), frames);
+  }
+  if (wantGrad) {
+    batched::asgFullScoreGrad(ems, static_cast<const float*>(tableDev), static_cast<const float*>(weightsDev),
+                              static_cast<float*>(gradEmDev), static_cast<float*>(gradTableDev), frames);
+  }
+}
+
 /** The exact ASG log scores of one device-resident token lattice per utterance under the B emission slabs, and (with
  *  weightsDev and at least one gradient) the gradients under those weights: `emissions` device float32 [B][T][N_], read
  *  in place; `tableDev` device float32 [N_ + N_ * N_] as for asgScoreBatch; `arcsDev` device int32 [B][A][3] (dense rows

@@ -413,6 +413,27 @@ GTN_EXPORT int gtn_asg_score_grad_n(const void* emissions, int B, int T, int C, 
   });
 }
 
+// ASG full-connect scores of a padded batch, 1 .. 1024 labels.  emissions: DEVICE float32 [B][T][C]; table: DEVICE
+// float32 [C + C*C] as for gtn_asg_score_n; frames: HOST int [B] or null; scores: DEVICE float32 [B].
+GTN_EXPORT int gtn_asg_full_score_n(const void* emissions, int B, int T, int C, const void* table, const int* frames,
+                                    void* scores) {
+  return guarded([&] {
+    if (!scores) throw std::invalid_argument("gtn_asg_full_score_n: null scores");
+    gtn::criteria::asgFullScoreBatch(emissions, B, T, C, table, frames, scores);
+  });
+}
+
+// ... and their gradients under weights: DEVICE float32 [B]: grad_em (DEVICE float32 [B][T][C], every element written)
+// and grad_table (DEVICE float32 [C + C*C]); either may be null, not both.
+GTN_EXPORT int gtn_asg_full_score_grad_n(const void* emissions, int B, int T, int C, const void* table,
+                                         const int* frames, const void* weights, void* grad_em, void* grad_table) {
+  return guarded([&] {
+    if (!weights || (!grad_em && !grad_table))
+      throw std::invalid_argument("gtn_asg_full_score_grad_n: null weights or no gradient");
+    gtn::criteria::asgFullScoreBatch(emissions, B, T, C, table, frames, nullptr, weights, grad_em, grad_table);
+  });
+}
+
 // Exact ASG log scores of one device-resident token lattice per utterance.  emissions: DEVICE float32 [B][T][C]; table:
 // DEVICE float32 [C + C*C] as for gtn_asg_score_n; frames: HOST int [B] or null; arcs: DEVICE int32 [B][A][3]; num_arcs /
 // num_nodes: DEVICE int32 [B]; arc_weights: DEVICE float32 [B][A] or null; scores: DEVICE float32 [B].

@@ -435,6 +435,23 @@ void batch_asg_score_grad(const BatchP& ems, const int* frames, const float* tab
                           int64_t row_stride, const int* lengths_dev, int N, int L, int max_length,
                           const float* weights_dev, float* grad_em_dev, float* grad_table_dev);
 void batch_asg_score_stats(int64_t* calls, int64_t* pairs);  // calls that launched (either kind) / pairs they took
+// The ASG full-connect score of a padded batch for 1 .. 1024 labels (DESIGN section 41 holds the contract): scores_dev[b]
+// = forwardScore(emissions_b[:T_b] o asgTransitions(table)) under the n slabs of a native linear batch and the [C + C * C]
+// table of batch_asg_score, written on the device.  T_b == 0 and an utterance without a finite path give -inf, never NaN;
+// rows at or past T_b are never read.  Invalid argument before a device is asked for: a null batch, table or scores
+// pointer; n == 0 returns without a device.  With the device: not a native linear batch, a frame count outside 0 .. M,
+// more than 1024 labels, a table that is not device memory, an output that is not memory of the current device.  Two
+// launches (prep, forward), no planes, never sliced, no wait.
+void batch_asg_full_score(const BatchP& ems, const int* frames, const float* table_dev, float* scores_dev);
+// The gradients for weights_dev [n], either output nullable but not both: grad_em_dev [n][M][C] = weights[b] * d score[b]
+// / d emissions (every element written, pad rows zero); grad_table_dev [C + C * C] = sum_b weights[b] * d score[b] / d
+// table.  An utterance whose score is -inf or whose weight is exactly 0 adds exact zeros.  Stateless: the planes (two of
+// M * Cpad floats per utterance with a table gradient, one without) come from the stream-ordered pool, at most 2.5 GiB
+// per slice (GTNX_ASG_FULL_SCORE_SCRATCH_BYTES lowers the cap: a debug switch); beyond it the utterances run in slices
+// of whole blocks of 16 with the same bits.  No floating-point atomics.
+void batch_asg_full_score_grad(const BatchP& ems, const int* frames, const float* table_dev, const float* weights_dev,
+                               float* grad_em_dev, float* grad_table_dev);
+void batch_asg_full_score_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
 // The exact ASG log score of one device-resident acyclic token lattice per utterance (batch_ctc_lattice_score's form)
 // under the n emission slabs of a native linear batch and the [C + C * C] table of batch_asg_score, results on the device
 // (DESIGN section 37 holds the contract): scores_dev[b] = log sum over the lattice's paths p of exp(w(p) +

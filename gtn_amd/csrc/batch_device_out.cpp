@@ -1472,6 +1472,139 @@ void batch_asg_score_grad(const BatchP& ems, const int* frames, const float* tab
                  {tokens_dev, row_stride, lengths_dev, N, L, max_length}, nullptr, weights_dev, grad_em_dev, grad_table_dev);
 }
 
+// ---- batched ASG full-connect score of a padded batch up to 1024 labels, and its gradients (asg_full_wide.hip) ----
+namespace {
+Counters g_asg_full_score;  // (calls, utterances)
+// the planes of a gradient call.  The sweeps' parallelism is utterances, so a slice is a chain of launches with most
+// compute units idle: the default holds the benchmark shape (512 x 1000 x 512: 2 GiB of planes) in one slice
+constexpr ScratchCap kAsgFullScoreScratch{"GTNX_ASG_FULL_SCORE_SCRATCH_BYTES", int64_t(2560) << 20};
+static_assert(kAsgFullWideMaxC == 1024 && kAsgFullWideBlock == 16, "the texts say 1024 and 16");
+
+// both entry points: scores_dev for the score; weights_dev and grad_em_dev / grad_table_dev for the gradients
+void asg_full_score_impl(const char* who, const BatchP& ems, const int* frames, const float* table_dev,
+                         float* scores_dev, const float* weights_dev, float* grad_em_dev, float* grad_table_dev) {
+  const bool want_grad = scores_dev == nullptr;
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!ems) refuse(who, "null batch");
+  if (!table_dev) refuse(who, "null table pointer");
+  if (want_grad && !weights_dev) refuse(who, "null weights pointer");
+  if (want_grad && !grad_em_dev && !grad_table_dev) refuse(who, "neither gradient asked for (both pointers null)");
+  const int n = ems->n;
+  if (n <= 0) return;
+  Runtime& rt = Runtime::get();
+  Batch& x = *ems;
+  if (!native_linear(x)) refuse(who, "not a native linear batch (gtnx_batch_linear / _rows)");
+  check_frames(who, frames, n, x.M, x);
+  if (x.C > kAsgFullWideMaxC) refuse(who, "more than 1024 labels");
+  if (!ptr_device_memory_of(table_dev, rt.device())) refuse(who, "the table is not memory of the engine's current device");
+  check_outputs_local(who, {scores_dev, grad_em_dev, grad_table_dev});
+  if (x.w_pend) x.w_pend->settle();  // (the values are read here: graph.h PendingCopy)
+  const std::vector<int> fr = resolve_frames(frames, x);
+  double sumT = 0;
+  for (int t : fr) sumT += t;
+  DevMemP fr_dev = upload_vec(fr);
+  const int C = x.C, M = x.M, Cpad = (C + 31) / 32 * 32;
+  const size_t mat = sizeof(float) * size_t(Cpad) * size_t(Cpad);
+  DevMemP prep = rt.alloc(2 * mat + sizeof(float) * size_t(Cpad));
+  AsgFullWideArgs a{};
+  a.em = x.w_dev;
+  a.frames = fr_dev->as<int>();
+  a.table = table_dev;
+  a.e_fwd = prep->as<float>();
+  a.e_bwd = prep->as<float>(mat);
+  a.rmax = prep->as<float>(2 * mat);
+  a.n = n;
+  a.M = M;
+  a.C = C;
+  a.Cpad = Cpad;
+  a.G = asg_full_wide_group(n);
+  // (a measuring switch, read per call: the bits of an utterance do not depend on it)
+  if (const char* e = std::getenv("GTNX_ASG_FULL_SCORE_GROUP")) {
+    const int g = std::atoi(e);
+    if (g == 4 || g == 8 || g == 16) a.G = g;
+  }
+  // algorithmic bytes.  prep: the table in, both copies out.  A sweep: the emissions of the live rows in, and per frame
+  // and workgroup one copy of E from L2; with the planes kept one plane out (forward), one in and with a table gradient
+  // one out, plus the gradient rows (backward).  table: both planes in once per block column of X, the partials out.
+  const double groups = double((n + a.G - 1) / a.G);
+  const double em_bytes = 4.0 * sumT * C, plane_bytes = 4.0 * sumT * Cpad;
+  const double e_stream = groups * 4.0 * double(Cpad) * Cpad * (sumT / double(n));
+  {
+    GTNX_PROF("asg_full_score_prep", 4.0 * double(C) * C + 2.0 * double(mat));
+    launch_asg_full_wide_prep(a, rt.stream());
+  }
+  if (!want_grad) {
+    a.scores = scores_dev;
+    a.utt0 = 0;
+    a.count = n;
+    GTNX_PROF("asg_full_score_forward", em_bytes + e_stream + 4.0 * n);
+    launch_asg_full_wide_forward(a, rt.stream());
+  } else {
+    // (the scores, the start rows and the partials outlive the slices: the reduce launch reads them)
+    const int64_t blocks = (int64_t(n) + kAsgFullWideBlock - 1) / kAsgFullWideBlock;
+    DevMemP sc = rt.alloc(sizeof(float) * size_t(n));
+    DevMemP keep;
+    a.scores = sc->as<float>();
+    a.weights = weights_dev;
+    a.grad = grad_em_dev;
+    a.grad_table = grad_table_dev;
+    if (grad_table_dev) {
+      keep = rt.alloc(mat * size_t(blocks) + sizeof(float) * size_t(n) * size_t(Cpad));
+      a.partial = keep->as<float>();
+      a.start_rows = keep->as<float>(mat * size_t(blocks));
+    }
+    const int64_t plane = int64_t(sizeof(float)) * std::max(M, 1) * Cpad;  // bytes per utterance and plane
+    const int64_t lt_bytes = int64_t(sizeof(double)) * std::max(M, 1);
+    const int64_t per_block = kAsgFullWideBlock * ((grad_table_dev ? 2 : 1) * plane + lt_bytes);
+    for_pair_slices(blocks, per_block, kAsgFullScoreScratch, [&](int64_t k0, int64_t cnt) {
+      a.utt0 = int(k0) * kAsgFullWideBlock;
+      a.count = int(std::min<int64_t>(cnt * kAsgFullWideBlock, n - a.utt0));
+      const size_t planes = size_t(plane) * size_t(a.count);
+      DevMemP work = rt.alloc((grad_table_dev ? 2 : 1) * planes + size_t(lt_bytes) * size_t(a.count));
+      a.la = work->as<float>();
+      a.fw = grad_table_dev ? work->as<float>(planes) : nullptr;
+      a.lt = work->as<double>((grad_table_dev ? 2 : 1) * planes);
+      const double share = double(a.count) / double(n);
+      {
+        GTNX_PROF("asg_full_score_forward", (em_bytes + e_stream + plane_bytes) * share);
+        launch_asg_full_wide_forward(a, rt.stream());
+      }
+      {
+        GTNX_PROF("asg_full_score_backward",
+                  (em_bytes + e_stream + plane_bytes * (grad_table_dev ? 2.0 : 1.0)) * share +
+                      (grad_em_dev ? 4.0 * double(a.count) * M * C : 0.0));
+        launch_asg_full_wide_backward(a, rt.stream());
+      }
+      if (grad_table_dev) {
+        GTNX_PROF("asg_full_score_table", 2.0 * plane_bytes * share * double((Cpad + 127) / 128) + double(mat) * double(cnt));
+        launch_asg_full_wide_table(a, rt.stream());
+      }
+      // (the planes go back to the stream-ordered pool behind the launches)
+    });
+    if (grad_table_dev) {
+      GTNX_PROF("asg_full_score_reduce", double(mat) * double(blocks + 1) + 4.0 * double(n) * Cpad + 4.0 * double(C) * (C + 1));
+      launch_asg_full_wide_reduce(a, rt.stream());
+    }
+  }
+  g_asg_full_score.add(1, n);
+}
+}  // namespace
+
+void batch_asg_full_score_stats(int64_t* calls, int64_t* utterances) { g_asg_full_score.get(calls, utterances); }
+
+void batch_asg_full_score(const BatchP& ems, const int* frames, const float* table_dev, float* scores_dev) {
+  GTNX_HOST_T("batch.asg_full_score");
+  if (!scores_dev) throw_invalid("[gtnx_batch_asg_full_score] null scores pointer");
+  asg_full_score_impl("gtnx_batch_asg_full_score", ems, frames, table_dev, scores_dev, nullptr, nullptr, nullptr);
+}
+
+void batch_asg_full_score_grad(const BatchP& ems, const int* frames, const float* table_dev, const float* weights_dev,
+                               float* grad_em_dev, float* grad_table_dev) {
+  GTNX_HOST_T("batch.asg_full_score_grad");
+  asg_full_score_impl("gtnx_batch_asg_full_score_grad", ems, frames, table_dev, nullptr, weights_dev, grad_em_dev,
+                      grad_table_dev);
+}
+
 // ---- batched ASG score of one device-resident token lattice per utterance, and its gradients (asg_lattice.hip) ----
 namespace {
 Counters g_asg_lattice;  // (calls, utterances)

@@ -1151,6 +1151,43 @@ void launch_asg_score_forward(const AsgScoreArgs& a, hipStream_t st);
 void launch_asg_score_backward(const AsgScoreArgs& a, hipStream_t st);
 void launch_asg_score_scatter(const AsgScoreArgs& a, hipStream_t st);
 void launch_asg_score_table(const AsgScoreArgs& a, hipStream_t st);
+// asg_full_wide.hip: the ASG full-connect score forwardScore(emissions_b[:T_b] o asgTransitions(table)) of the utterances
+// utt0 .. utt0 + count - 1 for 1 .. 1024 labels, and the gradients weights[b] * d score[b] / d (emissions_b, table) (the
+// contract: DESIGN section 41).  table: [C + C * C] as in AsgScoreArgs.  Cpad: C rounded up to a multiple of 32.
+//   prep:     rmax [Cpad] and E = exp(W - rmax) in the MFMA operand layout, e_fwd and its transpose e_bwd [Cpad * Cpad].
+//   forward:  one workgroup per G consecutive utterances (G 4, 8 or 16; utt0 a multiple of 16); scores[b] for every b of
+//             the range.  With `la` non-null the relative planes la_t = alpha_t - L_t go to la[(b - utt0) * M * Cpad + t *
+//             Cpad + i] and L_t (float64) to lt[(b - utt0) * M + t].
+//   backward: reads scores, weights, la, lt; with `grad` non-null every element of grad[b] is written, with `start_rows`
+//             non-null row b of [n][Cpad] gets weights[b] * gamma_0, with `fw` non-null the plane of weights[b] * f_t.
+//   table:    one partial [Cpad][Cpad] per block of kAsgFullWideBlock utterances, at partial + (b / 16) * Cpad * Cpad.
+//   reduce:   grad_table from all ceil(n / 16) partials and the n start rows, in that order.
+constexpr int kAsgFullWideMaxC = 1024;
+constexpr int kAsgFullWideBlock = 16;  // the utterances of one split-K partial; slices are whole blocks
+struct AsgFullWideArgs {
+  const GTNX_G float* em;       // [n][M][C]
+  const GTNX_G int* frames;     // [n]
+  const GTNX_G float* table;    // [C + C * C]
+  GTNX_G float* rmax;           // [Cpad]
+  GTNX_G float* e_fwd;          // [Cpad * Cpad]
+  GTNX_G float* e_bwd;          // [Cpad * Cpad]
+  GTNX_G float* scores;         // [n]
+  const GTNX_G float* weights;  // [n] (backward, table)
+  GTNX_G float* grad;           // [n][M][C] or null
+  GTNX_G float* grad_table;     // [C + C * C] (reduce)
+  GTNX_G float* la;             // [count][M][Cpad] or null
+  GTNX_G float* fw;             // [count][M][Cpad] or null
+  GTNX_G double* lt;            // [count][M] or null
+  GTNX_G float* start_rows;     // [n][Cpad] or null
+  GTNX_G float* partial;        // [ceil(n / 16)][Cpad][Cpad] or null
+  int n, M, C, Cpad, utt0, count, G;
+};
+int asg_full_wide_group(int n);  // the default G of a call over n utterances
+void launch_asg_full_wide_prep(const AsgFullWideArgs& a, hipStream_t st);
+void launch_asg_full_wide_forward(const AsgFullWideArgs& a, hipStream_t st);
+void launch_asg_full_wide_backward(const AsgFullWideArgs& a, hipStream_t st);
+void launch_asg_full_wide_table(const AsgFullWideArgs& a, hipStream_t st);
+void launch_asg_full_wide_reduce(const AsgFullWideArgs& a, hipStream_t st);
 // asg_lattice.hip: the ASG log score of the utterances utt0 .. utt0 + count - 1, each with one acyclic token lattice of its
 // own in device memory (ctc_lattice.hip's form), under asg_score.hip's [C + C * C] table, and the gradients g[b] * d
 // score[b] / d (emissions_b, table, arc weights of b) (the contract: DESIGN section 37).  The states are the arcs; an

@@ -47,6 +47,8 @@ _ARGTYPES = {
     "gtn_ctc_token_align_n": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gtn_asg_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
+    "gtn_asg_full_score_n": [_P, _I, _I, _I, _P, _P, _P],
+    "gtn_asg_full_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gtn_asg_lattice_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_lattice_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "gtn_asg_lattice_align_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
@@ -1349,6 +1351,92 @@ def asg_score(emissions, transitions, tokens, lengths, start=None, input_lengths
         start = torch.zeros(C_, dtype=torch.float32, device=emissions.device)
     out = _ASGScore.apply(emissions, transitions, start, tok, ln, frames, max_length)
     return out.reshape(B) if flat else out
+
+
+class _ASGFullScore(torch.autograd.Function):
+    """forward: the launches that store nothing but the scores; backward: the one stateless gradient call with grad_out
+    as the weights, asked for the emission and table gradients as requires_grad says.  The node keeps tensors only."""
+
+    @staticmethod
+    def forward(ctx, emissions, transitions, start, frames):
+        x = emissions.detach().contiguous()
+        B = x.shape[0]
+        table = _asg_weights(start, transitions)
+        stream = _engine_stream(x.device)
+        scores = torch.empty(B, dtype=torch.float32, device=x.device)
+        if B == 0:
+            _engine_done(stream)  # (no utterance: nothing to launch)
+        elif x.shape[1] == 0:
+            scores.fill_(float("-inf"))  # (no frame: an empty tensor has no address to hand over)
+            _engine_done(stream)
+        else:
+            _route(stream, x, _has_native("asg_full_score", "gtn_asg_full_score_n"), "gtn_asg_full_score_n",
+                   (table.data_ptr(), _host_ptr(frames), scores.data_ptr()),
+                   "asg_full_score", table.data_ptr(), scores.data_ptr(), frames)
+        ctx.save_for_backward(x, table)
+        ctx.args = (frames, transitions.dtype, start.dtype)
+        return scores
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, table = ctx.saved_tensors
+        frames, tr_dtype, st_dtype = ctx.args
+        B, T, C_ = x.shape
+        want_em = ctx.needs_input_grad[0]
+        want_table = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        if not (want_em or want_table):
+            return None, None, None, None
+        grad = torch.empty(B, T, C_, dtype=torch.float32, device=x.device) if want_em else None
+        g_table = torch.empty(C_ + C_ * C_, dtype=torch.float32, device=x.device) if want_table else None
+        if B == 0 or x.numel() == 0:
+            for g in (grad, g_table):
+                if g is not None:
+                    g.zero_()
+        else:
+            g = grad_out.detach().to(torch.float32).contiguous()
+            _route(_engine_stream(x.device), x, _native(), "gtn_asg_full_score_grad_n",
+                   (table.data_ptr(), _host_ptr(frames), g.data_ptr(), _ptr(grad), _ptr(g_table)),
+                   "asg_full_score_grad", table.data_ptr(), g.data_ptr(), _ptr(grad), _ptr(g_table), frames)
+        g_tr = g_table[C_:].reshape(C_, C_).to(tr_dtype) if ctx.needs_input_grad[1] else None
+        g_st = g_table[:C_].to(st_dtype) if ctx.needs_input_grad[2] else None
+        return grad, g_tr, g_st, None
+
+
+def asg_full_score(emissions, transitions, start=None, input_lengths=None):
+    """The ASG full-connect score of a padded batch -- the criterion's normaliser -- for 1 .. 1024 labels,
+    differentiable: score[b] = forwardScore(emissions[b, :T_b] o transitions), every label sequence and every alignment
+    of T_b frames.  emissions: float32 CUDA tensor [B, T, C] (any scores), read in place; transitions: [C, C] with
+    transitions[i, j] the score of label j followed by label i; start: [C] scores of the first label (zeros when
+    omitted); input_lengths: T_b in 0 .. T per utterance (all T when omitted).  The launch count does not depend on how
+    many distinct lengths the batch holds.  A padded word-piece criterion is `asg_full_score(x, tr, st, lens) -
+    asg_lattice_score(x, tr, ..., start=st, input_lengths=lens)`, or `- asg_score(...)`.
+    Returns float32 [B].  A score is -inf, with zero gradients and never NaN, when T_b == 0 or every path crosses a -inf
+    emission, transition or start score.  Rows from T_b on are never read.
+    The backward is one stateless call with grad_out as per-utterance weights -- any grad_out, non-uniform ones
+    included; it returns gradients for emissions, transitions and start, computes only those that require grad and sums
+    in a fixed order without atomics, so it has the same bits run to run.  Runs on the caller's stream."""
+    who = "asg_full_score"
+    x = emissions
+    if not (torch.is_tensor(x) and x.dim() == 3 and x.dtype == torch.float32):
+        raise ValueError(f"{who}: emissions must be a float32 tensor [B, T, C]")
+    B, T, C_ = x.shape
+    if not (torch.is_tensor(transitions) and tuple(transitions.shape) == (C_, C_)):
+        raise ValueError(f"{who}: transitions must be [{C_}, {C_}]")
+    if start is not None and not (torch.is_tensor(start) and tuple(start.shape) == (C_,)):
+        raise ValueError(f"{who}: start must be [{C_}]")
+    if C_ < 1 or C_ > 1024:
+        raise ValueError(f"{who}: the number of labels must be 1 .. 1024")
+    frames = None if input_lengths is None else _frame_counts(who, input_lengths, B, T, 0)
+    for t, what in ((x, "emissions"), (transitions, "transitions"), (start, "start")):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {what} must be a CUDA tensor (the scores are computed on the device)")
+        if t.device != x.device:
+            raise ValueError(f"{who}: all tensors must be on one device")
+    if start is None:
+        start = torch.zeros(C_, dtype=torch.float32, device=x.device)
+    return _ASGFullScore.apply(x, transitions, start, frames)
 
 
 class _ASGLatticeScore(torch.autograd.Function):

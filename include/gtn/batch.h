@@ -382,6 +382,23 @@ inline void asgScoreGrad(const Batch& ems, const float* tableDevice, const int* 
   detail::check(gtnx_batch_asg_score_grad(ems.handle(), frames, tableDevice, tokensDevice, rowStride, lengthsDevice, N,
                                           L, maxLength, weightsDevice, gradEmissionsDevice, gradTableDevice));
 }
+/** The ASG full-connect score of a padded batch for 1 .. 1024 labels, left on the device: scoresDevice[b] =
+ *  forwardScore(emissions_b[0 .. T_b) o asgTransitions(table)), float32 [n].  tableDevice float32 [C + C * C] as for
+ *  asgScore.  T_b == 0 and an utterance without a finite path give -inf, never NaN; rows from T_b on are never read.
+ *  Two launches whatever the frame counts are, no copy back, no wait -- gtnx_batch_asg_full_score */
+inline void asgFullScore(const Batch& ems, const float* tableDevice, float* scoresDevice, const int* frames = nullptr) {
+  detail::check(gtnx_batch_asg_full_score(ems.handle(), frames, tableDevice, scoresDevice));
+}
+/** The gradients of asgFullScore under the weights weightsDevice [n]: gradEmissionsDevice (or null) float32 [n][M][C],
+ *  every element written (rows from T_b on with zeros); gradTableDevice (or null) float32 [C + C * C]; not both null.
+ *  Utterances with a -inf score or a weight of exactly 0 add exact zeros.  Stateless (the planes are recomputed into
+ *  pooled scratch, sliced beyond 2.5 GiB) and bit-repeatable, sliced or not (no atomics)
+ *  -- gtnx_batch_asg_full_score_grad */
+inline void asgFullScoreGrad(const Batch& ems, const float* tableDevice, const float* weightsDevice,
+                             float* gradEmissionsDevice, float* gradTableDevice, const int* frames = nullptr) {
+  detail::check(gtnx_batch_asg_full_score_grad(ems.handle(), frames, tableDevice, weightsDevice, gradEmissionsDevice,
+                                               gradTableDevice));
+}
 /** The exact ASG log score of one device-resident acyclic token lattice per utterance (ctcLatticeScore's lattices) under
  *  the slabs of a Batch::linear and asgScore's table, results left on the device: scoresDevice[b] = log sum over the
  *  lattice's paths p of exp(w(p) + asgScore(emissions_b[0 .. T_b), table, labels(p))), nothing subtracted.  The states

@@ -799,6 +799,38 @@ gtnx_status_t gtnx_batch_asg_score_grad(gtnx_batch_t ems, const int* frames, con
                                         void* grad_emissions_device, void* grad_table_device);
 /* calls of either kind that have launched so far (process-wide) / pairs they took */
 gtnx_status_t gtnx_batch_asg_score_stats(int64_t* calls, int64_t* pairs);
+/* The ASG full-connect score -- the criterion's normaliser -- of a padded batch for 1 .. 1024 labels (DESIGN section
+ * 41):
+ *   scores[b] = forwardScore(emissions_b[0 .. T_b) o asgTransitions(table)), float32 [n], written on the device.
+ * ems: a gtnx_batch_linear / _rows batch, emissions [n][M][C] read in place.  frames: HOST, [n], T_b in 0 .. M, or null
+ * (the rows the batch carries).  table_device: the float32 [C + C * C] table of gtnx_batch_asg_score.  T_b == 0 gives
+ * -inf; a -inf emission, start or transition is probability 0 and an utterance without a finite path scores -inf, never
+ * NaN; rows at or past T_b are never read; +inf and NaN inside the live rows or the table are outside the contract.
+ * Scaled linear-domain recursion: q_t = exp(alpha_t - L_t), E = exp(W - rowmax), L_t the sum of the per-frame maxima in
+ * float64, Z = L + log sum q.  The same bits run to run and for an utterance whatever its neighbours are.
+ * GTNX_INVALID_ARGUMENT before a device is asked for: a null batch, table or scores pointer.  n == 0 returns without
+ * touching a device.  With the device: not a gtnx_batch_linear / _rows batch, a frame count outside 0 .. M, more than
+ * 1024 labels, a table that is not device memory, an output the engine's current device may not write.
+ * Two launches on the engine's stream (asg_full_wide.hip: prep, forward), whatever the frame counts are; no copy back,
+ * no wait. */
+gtnx_status_t gtnx_batch_asg_full_score(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                        void* scores_device);
+/* The gradients of those scores under caller-supplied weights_device (float32 [n]; grad_out under autograd), in one
+ * stateless call with the same inputs and refusals (plus a null weights pointer, and both outputs null).
+ *   grad_emissions_device (or null) float32 [n][M][C] = weights[b] * d scores[b] / d emissions[b]; EVERY element is
+ *     written, rows at or past T_b with zeros.
+ *   grad_table_device (or null) float32 [C + C * C] = sum over b of weights[b] * d scores[b] / d table.
+ * An utterance whose score is -inf or whose weight is exactly 0 adds exact zeros.  The planes (M * Cpad floats per
+ * utterance, two with a table gradient; Cpad = C rounded up to 32) come from the stream-ordered pool, at most 2.5 GiB
+ * per slice; beyond that the utterances run in slices of whole blocks of 16 (GTNX_ASG_FULL_SCORE_SCRATCH_BYTES, read
+ * per call, lowers the cap: a debug switch).  Launches: prep, then forward, backward and table per slice, then reduce.
+ * The table gradient is summed per block of 16 utterances and the blocks are added in order in float64 by the last
+ * launch: the same bits run to run, sliced or not; there are no floating-point atomics. */
+gtnx_status_t gtnx_batch_asg_full_score_grad(gtnx_batch_t ems, const int* frames, const void* table_device,
+                                             const void* weights_device, void* grad_emissions_device,
+                                             void* grad_table_device);
+/* calls of either kind that have launched so far (process-wide) / utterances they took */
+gtnx_status_t gtnx_batch_asg_full_score_stats(int64_t* calls, int64_t* utterances);
 /* The exact ASG log score of ONE ACYCLIC TOKEN LATTICE PER UTTERANCE -- gtnx_batch_ctc_lattice_score's lattices under
  * gtnx_batch_asg_score's criterion:
  *   scores[b] = log sum over the lattice's paths p of exp(w(p) + asg_score(emissions_b[0 .. T_b), table, labels(p))),
