@@ -75,6 +75,9 @@ debug_linear_decode_stats = _api.debug_linear_decode_stats  # (Batch.linear_deco
 debug_ctc_beam_stats = _api.debug_ctc_beam_stats  # (Batch.ctc_beam_decode: calls that launched, utterances decoded)
 debug_ctc_sample_stats = _api.debug_ctc_sample_stats  # (Batch.ctc_sample: calls that launched, utterances sampled)
 edit_distance = _api.edit_distance  # (batched Levenshtein distance of device-resident token rows)
+transducer_score = _api.transducer_score  # (batched transducer / RNN-T log score over device-resident joint logits)
+transducer_score_grad = _api.transducer_score_grad  # (its gradient under per-utterance weights, every row written)
+debug_transducer_stats = _api.debug_transducer_stats  # (transducer_score / _grad: calls that launched, utterances)
 ctc_loss_step16 = _api.ctc_loss_step16  # (one CTC criterion step over bfloat16 / float16 emissions, one launch)
 debug_edit_distance_stats = _api.debug_edit_distance_stats  # (edit_distance: calls that launched, pairs computed)
 debug_ctc_score_stats = _api.debug_ctc_score_stats  # (Batch.ctc_score / ctc_score_grad: calls that launched, pairs taken)

@@ -1907,6 +1907,90 @@ def make_api(lib):
                                            int(ref_stride), _opt_ptr(ref_lengths), b, n, l, u, _opt_ptr(dist_out),
                                            _opt_ptr(ops_out)))
 
+    def debug_transducer_stats():
+        """(calls, utterances): calls of transducer_score / transducer_score_grad that have launched so far and the
+        utterances they took (include/gtn_amd.h: gtnx_batch_transducer_stats)"""
+        return _stats2(lib.gtnx_batch_transducer_stats)
+
+    def _transducer_args(who, logits, targets, frames, target_lengths, blank, dims, outs):
+        """(B, T, U, C) of a transducer call: from `logits` [B, T, U + 1, C] when it is a tensor, else from `dims`
+        (a device address says nothing); the tensors among the arguments are checked against them.  `outs`: (tensor or
+        address or None, dtype, count function, text) of the other arguments."""
+        if hasattr(logits, "data_ptr"):
+            if str(logits.dtype) != "torch.float32" or logits.dim() != 4 or not logits.is_contiguous():
+                raise ValueError(f"{who}: logits must be a float32 contiguous tensor [B, T, U + 1, C]")
+            shape = (logits.shape[0], logits.shape[1], logits.shape[2] - 1, logits.shape[3])
+            for name, have, want in zip("BTUC", dims, shape):
+                if have is not None and int(have) != want:
+                    raise ValueError(f"{who}: {name} = {have} is not what logits says ({want})")
+            dims = shape
+        if any(d is None for d in dims):
+            raise ValueError(f"{who}: a device address needs B, T, U and C")
+        b, t, u, c = (int(d) for d in dims)
+        if not 0 <= int(blank) < max(c, 1):
+            raise ValueError(f"{who}: blank must be one of the {c} labels")
+        checks = [(logits, "torch.float32", None, "logits"),
+                  (targets, "torch.int32", b * u, "targets must be an int32 contiguous tensor [B, U]"),
+                  (frames, "torch.int32", b, "frames must be an int32 contiguous tensor [B]"),
+                  (target_lengths, "torch.int32", b, "target_lengths must be an int32 contiguous tensor [B]")]
+        for o, dtype, count, what in checks + [(o, "torch.float32", n(b, t, u, c), w) for o, n, w in outs]:
+            if o is not None and hasattr(o, "data_ptr"):
+                if count is not None and (str(o.dtype) != dtype or not o.is_contiguous() or o.numel() != count):
+                    raise ValueError(f"{who}: {what}")
+                if hasattr(o, "is_cuda") and not o.is_cuda:  # (a host tensor's address means nothing to the kernel)
+                    raise ValueError(f"{who}: {what.split()[0]} must be a CUDA tensor")
+        return b, t, u, c
+
+    def _transducer_targets(targets, b, u):
+        """the targets' address; an empty [B, 0] tensor has none and is never read"""
+        if hasattr(targets, "data_ptr") and b * u == 0:
+            return None
+        return _opt_ptr(targets)
+
+    def transducer_score(logits, targets, frames, target_lengths, scores_out, rows_out=None, blank=0, normalize=True,
+                         B=None, T=None, U=None, C=None):
+        """The transducer (RNN-T) log score of every utterance over device-resident joint logits, left on the device
+        (gtnx_batch_transducer_score; DESIGN section 42 holds the contract).  `logits`: float32 CUDA tensor [B, T, U + 1,
+        C], contiguous, or a device address with B, T, U and C; `targets`: int32 [B, U]; `frames`, `target_lengths`:
+        int32 [B], T_b and U_b, read on the device; `scores_out`: float32 [B] = log P(y_b | x_b) with `normalize` (the
+        kernel takes the log-softmax of every live row), the path score of the rows as they are without.  -inf, never
+        NaN: T_b == 0 or beyond T, U_b beyond U, a token outside 0 .. C - 1 or equal to `blank`, no finite path.
+        `rows_out` (float32 [B, T, U + 1, 3] or None) keeps (lp_blank, lp_label, lse) of every live node for
+        `transducer_score_grad`.  U + 1 <= 1024, T <= 65535, C <= 2^20, B * T * (U + 1) < 2^31.  No copy back, no wait."""
+        who = "transducer_score"
+        b, t, u, c = _transducer_args(
+            who, logits, targets, frames, target_lengths, blank, (B, T, U, C),
+            [(scores_out, lambda b, t, u, c: b, "scores_out must be a float32 contiguous tensor [B]"),
+             (rows_out, lambda b, t, u, c: 3 * b * t * (u + 1),
+              "rows_out must be a float32 contiguous tensor [B, T, U + 1, 3]")])
+        if b == 0 and hasattr(logits, "data_ptr"):
+            return  # (no utterance, nothing to launch -- and an empty tensor has no address to hand to the engine)
+        check(lib.gtnx_batch_transducer_score(_opt_ptr(logits), _transducer_targets(targets, b, u), _opt_ptr(frames),
+                                              _opt_ptr(target_lengths), b, t, u, c, int(blank), int(bool(normalize)),
+                                              _opt_ptr(scores_out), _opt_ptr(rows_out)))
+
+    def transducer_score_grad(logits, targets, frames, target_lengths, weights, grad_out, rows=None, blank=0,
+                              normalize=True, B=None, T=None, U=None, C=None):
+        """The gradient of the scores of `transducer_score` under `weights` (float32 [B] on the device), in one
+        stateless call (gtnx_batch_transducer_score_grad): `grad_out` (float32 [B, T, U + 1, C]) = weights[b] * d
+        score[b] / d logits[b], every row stored exactly once -- the rows that are never read (t >= T_b, u > U_b), those
+        of an utterance that scores -inf and dead rows with zeros.  `rows`: the plane `transducer_score` left in
+        `rows_out` for the same inputs, or None (then it is recomputed: one more pass over the logits).  Pooled scratch,
+        sliced beyond 256 MiB with the same bits; no atomics, the same bits run to run."""
+        who = "transducer_score_grad"
+        b, t, u, c = _transducer_args(
+            who, logits, targets, frames, target_lengths, blank, (B, T, U, C),
+            [(weights, lambda b, t, u, c: b, "weights must be a float32 contiguous tensor [B]"),
+             (grad_out, lambda b, t, u, c: b * t * (u + 1) * c,
+              "grad_out must be a float32 contiguous tensor [B, T, U + 1, C]"),
+             (rows, lambda b, t, u, c: 3 * b * t * (u + 1), "rows must be a float32 contiguous tensor [B, T, U + 1, 3]")])
+        if b == 0 and hasattr(logits, "data_ptr"):
+            return
+        check(lib.gtnx_batch_transducer_score_grad(_opt_ptr(logits), _transducer_targets(targets, b, u),
+                                                   _opt_ptr(frames), _opt_ptr(target_lengths), b, t, u, c, int(blank),
+                                                   int(bool(normalize)), _opt_ptr(weights), _opt_ptr(grad_out),
+                                                   _opt_ptr(rows)))
+
     def ctc_loss_step16(emissions, targets, loss_out, grad_out, blank=0, input_lengths=None):
         """One CTC criterion step over 16-bit emissions in one launch (gtnx_batch_ctc_loss_step16 has the contract).
         `emissions`: bfloat16 or float16 CUDA tensor [B, T, C], contiguous, read in place; `targets`: B label sequences;
@@ -1990,6 +2074,9 @@ def make_api(lib):
     ns.debug_asg_beam_stats = debug_asg_beam_stats
     ns.debug_asg_sample_stats = debug_asg_sample_stats
     ns.edit_distance = edit_distance
+    ns.transducer_score = transducer_score
+    ns.transducer_score_grad = transducer_score_grad
+    ns.debug_transducer_stats = debug_transducer_stats
     ns.ctc_loss_step16 = ctc_loss_step16
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties

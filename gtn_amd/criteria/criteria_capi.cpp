@@ -11,6 +11,7 @@
 #include "asg_criterion.h"
 #include "ctc_criterion.h"
 #include "edit_distance.h"
+#include "transducer_criterion.h"
 
 #define GTN_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -431,6 +432,28 @@ GTN_EXPORT int gtn_asg_full_score_grad_n(const void* emissions, int B, int T, in
     if (!weights || (!grad_em && !grad_table))
       throw std::invalid_argument("gtn_asg_full_score_grad_n: null weights or no gradient");
     gtn::criteria::asgFullScoreBatch(emissions, B, T, C, table, frames, nullptr, weights, grad_em, grad_table);
+  });
+}
+
+// Transducer (RNN-T) log scores over joint logits.  logits: DEVICE float32 [B][T][U+1][C]; targets: DEVICE int32 [B][U];
+// frames / target_lengths: DEVICE int32 [B]; scores: DEVICE float32 [B]; rows: DEVICE float32 [B][T][U+1][3] or null.
+GTN_EXPORT int gtn_transducer_score_n(const void* logits, const void* targets, const void* frames,
+                                      const void* target_lengths, int B, int T, int U, int C, int blank, int normalize,
+                                      void* scores, void* rows) {
+  return guarded([&] {
+    gtn::criteria::transducerScoreBatch(logits, targets, frames, target_lengths, B, T, U, C, blank, normalize != 0,
+                                        scores, rows);
+  });
+}
+
+// ... and their gradient under weights: DEVICE float32 [B]: grad (DEVICE float32 [B][T][U+1][C], every row written);
+// rows: the plane gtn_transducer_score_n left for the same inputs, or null.
+GTN_EXPORT int gtn_transducer_score_grad_n(const void* logits, const void* targets, const void* frames,
+                                           const void* target_lengths, int B, int T, int U, int C, int blank,
+                                           int normalize, const void* weights, void* grad, const void* rows) {
+  return guarded([&] {
+    gtn::criteria::transducerScoreGradBatch(logits, targets, frames, target_lengths, B, T, U, C, blank, normalize != 0,
+                                            weights, grad, rows);
   });
 }
 

@@ -1,0 +1,64 @@
+// transducer_criterion.h -- the transducer (RNN-T) criterion over joint logits that live on the device, written against
+// the drop-in C++ API of include/gtn: one call for the scores, one for the gradient, results left on the device.
+// Header-only; used by gtn_amd/criteria/criteria_capi.cpp (torch_loss.transducer_score / transducer_loss).
+#pragma once
+
+#include <stdexcept>
+
+#include "gtn/gtn.h"
+
+namespace gtn {
+namespace criteria {
+
+/** The transducer log scores of B utterances: `logitsDev` device float32 [B][T][U + 1][C], read in place; `targetsDev`
+ *  device int32 [B][U]; `framesDev` / `targetLengthsDev` device int32 [B]; `scoresDev` device float32 [B]; `rowsDev`
+ *  device float32 [B][T][U + 1][3] or null (the compact plane, kept for the gradient call).
+ *  gtnx_batch_transducer_score has the contract.  Nothing is copied back. */
+inline void transducerScoreBatch(
+    const void* logitsDev,
+    const void* targetsDev,
+    const void* framesDev,
+    const void* targetLengthsDev,
+    int B,
+    int T,
+    int U,
+    int C,
+    int blank,
+    bool normalize,
+    void* scoresDev,
+    void* rowsDev = nullptr) {
+  if (!scoresDev) {
+    throw std::invalid_argument("transducerScoreBatch: null scores");
+  }
+  batched::transducerScore(static_cast<const float*>(logitsDev), static_cast<const int*>(targetsDev),
+                           static_cast<const int*>(framesDev), static_cast<const int*>(targetLengthsDev), B, T, U, C,
+                           blank, normalize, static_cast<float*>(scoresDev), static_cast<float*>(rowsDev));
+}
+
+/** Their gradient under `weightsDev` (device float32 [B]): `gradDev` device float32 [B][T][U + 1][C], every row written;
+ *  `rowsDev` the plane transducerScoreBatch left for the same inputs, or null (then it is recomputed). */
+inline void transducerScoreGradBatch(
+    const void* logitsDev,
+    const void* targetsDev,
+    const void* framesDev,
+    const void* targetLengthsDev,
+    int B,
+    int T,
+    int U,
+    int C,
+    int blank,
+    bool normalize,
+    const void* weightsDev,
+    void* gradDev,
+    const void* rowsDev = nullptr) {
+  if (!weightsDev || !gradDev) {
+    throw std::invalid_argument("transducerScoreGradBatch: null weights or gradient");
+  }
+  batched::transducerScoreGrad(static_cast<const float*>(logitsDev), static_cast<const int*>(targetsDev),
+                               static_cast<const int*>(framesDev), static_cast<const int*>(targetLengthsDev), B, T, U, C,
+                               blank, normalize, static_cast<const float*>(weightsDev), static_cast<float*>(gradDev),
+                               static_cast<const float*>(rowsDev));
+}
+
+} // namespace criteria
+} // namespace gtn

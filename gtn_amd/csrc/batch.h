@@ -452,6 +452,26 @@ void batch_asg_full_score(const BatchP& ems, const int* frames, const float* tab
 void batch_asg_full_score_grad(const BatchP& ems, const int* frames, const float* table_dev, const float* weights_dev,
                                float* grad_em_dev, float* grad_table_dev);
 void batch_asg_full_score_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
+// The transducer (RNN-T) log score of B utterances over device-resident joint logits (DESIGN section 42 holds the
+// contract): logits_dev float32 [B][T][U + 1][C], targets_dev int32 [B][U], frames_dev / target_lengths_dev int32 [B], all
+// read on the device; scores_dev[b] = alpha[T_b - 1, U_b] + lp[T_b - 1, U_b, blank] with lp the log-softmax of a row
+// (normalize != 0) or the row itself.  -inf, never NaN: T_b == 0, T_b > T, U_b > U, a token outside 0 .. C - 1 or equal to
+// blank, no finite path.  rows_dev (or null): float32 [B][T][U + 1][3], gets the compact plane (lp_blank, lp_label, lse)
+// of every live node.  Invalid argument before a device is asked for: a null pointer, a negative B, U + 1 outside
+// 1 .. 1024, T outside 1 .. 65535, C outside 1 .. 2^20, blank outside 0 .. C - 1, B * T * (U + 1) >= 2^31; B == 0 returns.
+// Without rows the plane (12 bytes per node) comes from the stream-ordered pool, at most 256 MiB per slice
+// (GTNX_TRANSDUCER_SCRATCH_BYTES lowers the cap: a debug switch).  Two launches per slice, no copy back, no wait.
+void batch_transducer_score(const float* logits_dev, const int* targets_dev, const int* frames_dev,
+                            const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
+                            float* scores_dev, float* rows_dev);
+// The gradient grad_dev [B][T][U + 1][C] = weights_dev[b] * d score[b] / d logits[b]: every row stored exactly once, the
+// never-read ones (t >= T_b, u > U_b, an utterance that scores -inf, a dead row) with zeros.  rows_dev (or null): the
+// plane batch_transducer_score left; with it the rows launch is skipped.  Stateless: 20 bytes of pooled scratch per
+// node (8 with rows), sliced under the same cap with the same bits.  No floating-point atomics.
+void batch_transducer_score_grad(const float* logits_dev, const int* targets_dev, const int* frames_dev,
+                                 const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
+                                 const float* weights_dev, float* grad_dev, const float* rows_dev);
+void batch_transducer_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
 // The exact ASG log score of one device-resident acyclic token lattice per utterance (batch_ctc_lattice_score's form)
 // under the n emission slabs of a native linear batch and the [C + C * C] table of batch_asg_score, results on the device
 // (DESIGN section 37 holds the contract): scores_dev[b] = log sum over the lattice's paths p of exp(w(p) +

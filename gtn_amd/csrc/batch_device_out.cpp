@@ -1605,6 +1605,102 @@ void batch_asg_full_score_grad(const BatchP& ems, const int* frames, const float
                       grad_table_dev);
 }
 
+// ---- batched transducer (RNN-T) score over device-resident joint logits, and its gradient (transducer.hip) ----
+namespace {
+Counters g_transducer;  // (calls, utterances)
+// the compact plane and the alpha / beta planes of one slice of utterances; an utterance above the cap runs alone
+constexpr ScratchCap kTransducerScratch{"GTNX_TRANSDUCER_SCRATCH_BYTES", int64_t(256) << 20};
+static_assert(kTransducerMaxU1 == 1024 && kTransducerMaxT == 65535 && kTransducerMaxC == (1 << 20),
+              "the texts say 1024, 65535 and 2^20");
+
+// both entry points: scores_dev for the score (rows_dev: where the compact plane is left, or null); weights_dev and
+// grad_dev for the gradient (rows_dev: the plane a score call left, or null)
+void transducer_impl(const char* who, const float* x, const int* targets, const int* frames, const int* tlen, int B,
+                     int T, int U, int C, int blank, int normalize, float* scores_dev, float* rows_dev,
+                     const float* weights_dev, float* grad_dev) {
+  const bool want_grad = scores_dev == nullptr;
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!x || (!targets && U > 0) || !frames || !tlen)
+    refuse(who, "null input pointer (logits, targets, frames and target_lengths are all read)");
+  if (want_grad && (!weights_dev || !grad_dev)) refuse(who, "null weights or grad pointer");
+  if (B < 0) refuse(who, "negative B");
+  if (U < 0 || U + 1 > kTransducerMaxU1) refuse(who, "U + 1 outside 1 .. 1024");
+  if (T < 1 || T > kTransducerMaxT) refuse(who, "T outside 1 .. 65535");
+  if (C < 1 || C > kTransducerMaxC) refuse(who, "C outside 1 .. 2^20");
+  if (blank < 0 || blank >= C) refuse(who, "blank is not one of the C labels");
+  const int U1 = U + 1;
+  const int64_t per_utt = int64_t(T) * U1;  // nodes
+  if (int64_t(B) * per_utt > std::numeric_limits<int>::max()) refuse(who, "B * T * (U + 1) does not fit an int");
+  if (B == 0) return;
+  Runtime& rt = Runtime::get();
+  if (!ptr_device_memory_of(x, rt.device())) refuse(who, "the logits are not memory of the engine's current device");
+  check_outputs_local(who, {scores_dev, grad_dev, want_grad ? nullptr : rows_dev});
+  TransducerArgs a{};
+  a.x = x;
+  a.targets = targets;
+  a.frames = frames;
+  a.tlen = tlen;
+  a.weights = weights_dev;
+  a.grad = grad_dev;
+  a.T = T;
+  a.U1 = U1;
+  a.C = C;
+  a.blank = blank;
+  a.normalize = normalize ? 1 : 0;
+  DevMemP sc;  // (the gradient's scores: a slice's own, read by its gradient launch)
+  if (want_grad) sc = rt.alloc(sizeof(float) * size_t(B));
+  a.scores = want_grad ? sc->as<float>() : scores_dev;
+  // algorithmic bytes, by the widths (the counts are device memory: an upper bound).  rows: every logit once, the
+  // triple out (unnormalised: two gathered entries).  sweep: per direction two of the three values in, one plane out.
+  // grad: every logit in (normalised) and every gradient out, the triple and three plane values in.
+  const double row_in = normalize ? 4.0 * C : 8.0;
+  const int64_t own_rows = rows_dev ? 0 : 12;
+  const int64_t per_bytes = per_utt * (own_rows + (want_grad ? 8 : 0));
+  for_pair_slices(B, per_bytes, kTransducerScratch, [&](int64_t b0, int64_t cnt) {
+    const size_t nodes = size_t(per_utt) * size_t(cnt);
+    DevMemP work = rt.alloc(std::max<size_t>(size_t(per_bytes) * size_t(cnt), 16));
+    a.utt0 = int(b0);
+    a.count = int(cnt);
+    a.rows = rows_dev ? const_cast<float*>(rows_dev) + 3 * per_utt * b0 : work->as<float>();
+    a.alpha = want_grad ? work->as<float>(size_t(own_rows) * nodes) : nullptr;
+    a.beta = want_grad ? work->as<float>(size_t(own_rows + 4) * nodes) : nullptr;
+    if (!(want_grad && rows_dev)) {
+      GTNX_PROF("transducer_rows", double(nodes) * (row_in + 12.0));
+      launch_transducer_rows(a, rt.stream());
+    }
+    {
+      GTNX_PROF("transducer_sweep", double(nodes) * (want_grad ? 24.0 : 8.0) + 4.0 * double(cnt));
+      launch_transducer_sweep(a, rt.stream());
+    }
+    if (want_grad) {
+      GTNX_PROF("transducer_grad", double(nodes) * ((normalize ? 8.0 : 4.0) * C + 24.0));
+      launch_transducer_grad(a, rt.stream());
+    }
+    // (the planes go back to the stream-ordered pool behind the launches)
+  });
+  g_transducer.add(1, B);
+}
+}  // namespace
+
+void batch_transducer_stats(int64_t* calls, int64_t* utterances) { g_transducer.get(calls, utterances); }
+
+void batch_transducer_score(const float* logits_dev, const int* targets_dev, const int* frames_dev,
+                            const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
+                            float* scores_dev, float* rows_dev) {
+  GTNX_HOST_T("batch.transducer_score");
+  if (!scores_dev) throw_invalid("[gtnx_batch_transducer_score] null scores pointer");
+  transducer_impl("gtnx_batch_transducer_score", logits_dev, targets_dev, frames_dev, target_lengths_dev, B, T, U, C,
+                  blank, normalize, scores_dev, rows_dev, nullptr, nullptr);
+}
+
+void batch_transducer_score_grad(const float* logits_dev, const int* targets_dev, const int* frames_dev,
+                                 const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
+                                 const float* weights_dev, float* grad_dev, const float* rows_dev) {
+  GTNX_HOST_T("batch.transducer_score_grad");
+  transducer_impl("gtnx_batch_transducer_score_grad", logits_dev, targets_dev, frames_dev, target_lengths_dev, B, T, U,
+                  C, blank, normalize, nullptr, const_cast<float*>(rows_dev), weights_dev, grad_dev);
+}
+
 // ---- batched ASG score of one device-resident token lattice per utterance, and its gradients (asg_lattice.hip) ----
 namespace {
 Counters g_asg_lattice;  // (calls, utterances)

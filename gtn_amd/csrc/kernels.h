@@ -1188,6 +1188,36 @@ void launch_asg_full_wide_forward(const AsgFullWideArgs& a, hipStream_t st);
 void launch_asg_full_wide_backward(const AsgFullWideArgs& a, hipStream_t st);
 void launch_asg_full_wide_table(const AsgFullWideArgs& a, hipStream_t st);
 void launch_asg_full_wide_reduce(const AsgFullWideArgs& a, hipStream_t st);
+// transducer.hip: the transducer (RNN-T) log score of the utterances utt0 .. utt0 + count - 1 over joint logits x
+// [n][T][U1][C] (U1 = U + 1) and the gradient weights[b] * d score[b] / d x[b] (the contract: DESIGN section 42).  Node
+// (b, t, u) is live when t < T_b and u <= U_b (frames[b], target_lengths[b], both read on the device; an utterance with
+// T_b outside 1 .. T or U_b outside 0 .. U has no live node).  Planes are indexed by the node's offset inside the slice,
+// ((b - utt0) * T + t) * U1 + u.
+//   rows:   per live node the compact triple (lp_blank, lp_label, lse) at rows[3 * node]; lp_label is -inf at u == U_b
+//           and for a token outside 0 .. C - 1 or equal to blank; a dead row (NaN, +inf, all -inf) gets (-inf, -inf, 0).
+//           With normalize == 0 the two entries are gathered and nothing else is read (lse 0).
+//   sweep:  one wave per utterance and direction: alpha (always; writes scores[b]) and, with `beta` non-null, beta.
+//           `alpha` null: nothing but the score is stored.
+//   grad:   every row of grad[b] for the slice's utterances, the never-read ones with zeros.
+constexpr int kTransducerMaxU1 = 1024;
+constexpr int kTransducerMaxT = 65535;
+constexpr int kTransducerMaxC = 1 << 20;
+struct TransducerArgs {
+  const GTNX_G float* x;         // [n][T][U1][C]
+  const GTNX_G int* targets;     // [n][U1 - 1]
+  const GTNX_G int* frames;      // [n]
+  const GTNX_G int* tlen;        // [n]
+  GTNX_G float* rows;            // [count][T][U1][3]
+  GTNX_G float* alpha;           // [count][T][U1] or null
+  GTNX_G float* beta;            // [count][T][U1] or null
+  GTNX_G float* scores;          // [n]
+  const GTNX_G float* weights;   // [n] (grad)
+  GTNX_G float* grad;            // [n][T][U1][C] (grad)
+  int T, U1, C, blank, normalize, utt0, count;
+};
+void launch_transducer_rows(const TransducerArgs& a, hipStream_t st);
+void launch_transducer_sweep(const TransducerArgs& a, hipStream_t st);
+void launch_transducer_grad(const TransducerArgs& a, hipStream_t st);
 // asg_lattice.hip: the ASG log score of the utterances utt0 .. utt0 + count - 1, each with one acyclic token lattice of its
 // own in device memory (ctc_lattice.hip's form), under asg_score.hip's [C + C * C] table, and the gradients g[b] * d
 // score[b] / d (emissions_b, table, arc weights of b) (the contract: DESIGN section 37).  The states are the arcs; an

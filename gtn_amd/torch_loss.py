@@ -49,6 +49,8 @@ _ARGTYPES = {
     "gtn_asg_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
     "gtn_asg_full_score_n": [_P, _I, _I, _I, _P, _P, _P],
     "gtn_asg_full_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "gtn_transducer_score_n": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
+    "gtn_transducer_score_grad_n": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "gtn_asg_lattice_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_lattice_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "gtn_asg_lattice_align_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
@@ -1437,6 +1439,105 @@ def asg_full_score(emissions, transitions, start=None, input_lengths=None):
     if start is None:
         start = torch.zeros(C_, dtype=torch.float32, device=x.device)
     return _ASGFullScore.apply(x, transitions, start, frames)
+
+
+class _TransducerScore(torch.autograd.Function):
+    """forward: the rows and alpha launches; where the logits require grad the compact plane `rows` is kept as a saved
+    tensor.  backward: the one gradient call with grad_out as the weights, which then reads the logits once."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, frames, tlen, blank, normalize):
+        x = logits.detach().contiguous()
+        B, T, U1, C_ = x.shape
+        stream = _engine_stream(x.device)
+        scores = torch.empty(B, dtype=torch.float32, device=x.device)
+        rows = torch.empty(B, T, U1, 3, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[0] else None
+        if B:
+            args = (x.data_ptr(), targets.data_ptr() if targets.numel() else None, frames.data_ptr(), tlen.data_ptr())
+            if _has_native("transducer_score", "gtn_transducer_score_n"):
+                _call("gtn_transducer_score_n", *args, B, T, U1 - 1, C_, blank, int(normalize), scores.data_ptr(),
+                      _ptr(rows))
+            else:
+                gtn.transducer_score(*args, scores.data_ptr(), _ptr(rows), blank, normalize, B=B, T=T, U=U1 - 1, C=C_)
+        _engine_done(stream)
+        ctx.save_for_backward(x, targets, frames, tlen, rows)
+        ctx.args = (blank, normalize)
+        return scores
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, targets, frames, tlen, rows = ctx.saved_tensors
+        blank, normalize = ctx.args
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        B, T, U1, C_ = x.shape
+        grad = torch.empty_like(x)
+        if B:
+            g = grad_out.detach().to(torch.float32).contiguous()
+            stream = _engine_stream(x.device)
+            args = (x.data_ptr(), targets.data_ptr() if targets.numel() else None, frames.data_ptr(), tlen.data_ptr())
+            if _native():
+                _call("gtn_transducer_score_grad_n", *args, B, T, U1 - 1, C_, blank, int(normalize), g.data_ptr(),
+                      grad.data_ptr(), _ptr(rows))
+            else:
+                gtn.transducer_score_grad(*args, g.data_ptr(), grad.data_ptr(), _ptr(rows), blank, normalize, B=B, T=T,
+                                          U=U1 - 1, C=C_)
+            _engine_done(stream)
+        return grad, None, None, None, None, None
+
+
+def transducer_score(logits, targets, input_lengths, target_lengths, blank=0, normalize=True):
+    """The transducer (RNN-T) log score of a padded batch over joint logits, differentiable: with `normalize` score[b] =
+    log P(targets[b, :U_b] | logits[b, :T_b]), the kernel taking the log-softmax of every live row itself; without it the
+    rows are taken as log-probabilities as they are.  logits: float32 CUDA tensor [B, T, U + 1, C], read in place;
+    targets: int32 or int64 CUDA tensor [B, U]; input_lengths (T_b) and target_lengths (U_b): int32 or int64 CUDA tensors
+    [B], read on the device -- nothing is downloaded.  U + 1 <= 1024, 1 <= T <= 65535, C <= 2^20, B * T * (U + 1) < 2^31.
+    Returns float32 [B].  A score is -inf, with a zero gradient and never NaN, when T_b == 0, T_b > T, U_b > U, a target
+    is outside 0 .. C - 1 or equal to `blank`, or no path has a finite score; U_b == 0 is valid.  Rows with t >= T_b or
+    u > U_b are never read and their gradient rows are exactly 0.
+    The backward is one call with grad_out as per-utterance weights -- any grad_out, non-uniform ones included -- and
+    has the same bits run to run (no atomics).  Where the logits require grad the forward keeps 12 bytes per node, so
+    forward plus backward read the logits twice and write them once.  Runs on the caller's stream."""
+    who = "transducer_score"
+    x = logits
+    if not (torch.is_tensor(x) and x.dim() == 4 and x.dtype == torch.float32 and x.shape[2] >= 1):
+        raise ValueError(f"{who}: logits must be a float32 tensor [B, T, U + 1, C]")
+    B, T, U1, C_ = x.shape
+    if not (torch.is_tensor(targets) and targets.dtype in (torch.int32, torch.int64)
+            and tuple(targets.shape) == (B, U1 - 1)):
+        raise ValueError(f"{who}: targets must be an int32 or int64 tensor [{B}, {U1 - 1}]")
+    for t, what in ((input_lengths, "input_lengths"), (target_lengths, "target_lengths")):
+        if not (torch.is_tensor(t) and t.dtype in (torch.int32, torch.int64) and tuple(t.shape) == (B,)):
+            raise ValueError(f"{who}: {what} must be an int32 or int64 tensor [{B}]")
+    if U1 > 1024:
+        raise ValueError(f"{who}: U + 1 must be 1 .. 1024")
+    if not 1 <= T <= 65535:
+        raise ValueError(f"{who}: T must be 1 .. 65535")
+    if not 1 <= C_ <= 1 << 20:
+        raise ValueError(f"{who}: the number of labels must be 1 .. 2^20")
+    if B * T * U1 >= 1 << 31:
+        raise ValueError(f"{who}: B * T * (U + 1) must be below 2^31")
+    if not 0 <= int(blank) < C_:
+        raise ValueError(f"{who}: blank must be one of the {C_} labels")
+    for t, what in ((x, "logits"), (targets, "targets"), (input_lengths, "input_lengths"),
+                    (target_lengths, "target_lengths")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {what} must be a CUDA tensor (the scores are computed on the device)")
+        if t.device != x.device:
+            raise ValueError(f"{who}: all tensors must be on one device")
+    tg = targets.detach().to(torch.int32).contiguous()  # (int64 values are converted on the device)
+    fr = input_lengths.detach().to(torch.int32).contiguous()
+    tl = target_lengths.detach().to(torch.int32).contiguous()
+    return _TransducerScore.apply(x, tg, fr, tl, int(blank), bool(normalize))
+
+
+def transducer_loss(logits, targets, input_lengths, target_lengths, blank=0, normalize=True, reduction="mean"):
+    """-transducer_score(...): float32 [B] with reduction "none", their sum with "sum", their mean over the batch with
+    "mean".  An utterance without a path has loss +inf."""
+    if reduction not in ("none", "sum", "mean"):
+        raise ValueError('transducer_loss: reduction must be "none", "sum" or "mean"')
+    loss = -transducer_score(logits, targets, input_lengths, target_lengths, blank, normalize)
+    return loss if reduction == "none" else (loss.sum() if reduction == "sum" else loss.mean())
 
 
 class _ASGLatticeScore(torch.autograd.Function):

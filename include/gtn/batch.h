@@ -399,6 +399,28 @@ inline void asgFullScoreGrad(const Batch& ems, const float* tableDevice, const f
   detail::check(gtnx_batch_asg_full_score_grad(ems.handle(), frames, tableDevice, weightsDevice, gradEmissionsDevice,
                                                gradTableDevice));
 }
+/** The transducer (RNN-T) log score of B utterances over device-resident joint logits, left on the device:
+ *  logitsDevice float32 [B][T][U + 1][C], targetsDevice int32 [B][U], framesDevice / targetLengthsDevice int32 [B] (T_b
+ *  and U_b, read on the device); scoresDevice[b] = log P(y_b | x_b) with normalize, the path score of the rows as they
+ *  are without.  -inf, never NaN: T_b == 0 or beyond T, U_b beyond U, a token outside 0 .. C - 1 or equal to blank, no
+ *  finite path.  rowsDevice (or null): float32 [B][T][U + 1][3], keeps the compact plane for transducerScoreGrad.
+ *  U + 1 <= 1024, T <= 65535, C <= 2^20, B * T * (U + 1) < 2^31.  No copy back, no wait -- gtnx_batch_transducer_score */
+inline void transducerScore(const float* logitsDevice, const int* targetsDevice, const int* framesDevice,
+                            const int* targetLengthsDevice, int B, int T, int U, int C, int blank, bool normalize,
+                            float* scoresDevice, float* rowsDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_score(logitsDevice, targetsDevice, framesDevice, targetLengthsDevice, B, T, U, C,
+                                            blank, normalize ? 1 : 0, scoresDevice, rowsDevice));
+}
+/** The gradient of transducerScore under the weights weightsDevice [B]: gradDevice float32 [B][T][U + 1][C], every row
+ *  stored exactly once (the never-read ones with zeros).  rowsDevice (or null): the plane transducerScore left for the
+ *  same inputs; with it the logits are read once, not twice.  Stateless (pooled scratch, sliced beyond 256 MiB) and
+ *  bit-repeatable, sliced or not (no atomics) -- gtnx_batch_transducer_score_grad */
+inline void transducerScoreGrad(const float* logitsDevice, const int* targetsDevice, const int* framesDevice,
+                                const int* targetLengthsDevice, int B, int T, int U, int C, int blank, bool normalize,
+                                const float* weightsDevice, float* gradDevice, const float* rowsDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_score_grad(logitsDevice, targetsDevice, framesDevice, targetLengthsDevice, B, T, U,
+                                                 C, blank, normalize ? 1 : 0, weightsDevice, gradDevice, rowsDevice));
+}
 /** The exact ASG log score of one device-resident acyclic token lattice per utterance (ctcLatticeScore's lattices) under
  *  the slabs of a Batch::linear and asgScore's table, results left on the device: scoresDevice[b] = log sum over the
  *  lattice's paths p of exp(w(p) + asgScore(emissions_b[0 .. T_b), table, labels(p))), nothing subtracted.  The states

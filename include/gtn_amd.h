@@ -831,6 +831,41 @@ gtnx_status_t gtnx_batch_asg_full_score_grad(gtnx_batch_t ems, const int* frames
                                              void* grad_table_device);
 /* calls of either kind that have launched so far (process-wide) / utterances they took */
 gtnx_status_t gtnx_batch_asg_full_score_stats(int64_t* calls, int64_t* utterances);
+/* The transducer (RNN-T) log score of B utterances over device-resident joint logits:
+ *   lp[t,u,c]  = x[b,t,u,c] - logsumexp_c x[b,t,u,:]  (normalize != 0), or x[b,t,u,c] as it is (normalize == 0)
+ *   alpha[0,0] = 0;  alpha[t,u] = logadd(alpha[t-1,u] + lp[t-1,u,blank], alpha[t,u-1] + lp[t,u-1,y[u-1]])
+ *   scores[b]  = alpha[T_b-1,U_b] + lp[T_b-1,U_b,blank], float32 [B], written on the device.
+ * logits_device: float32 [B][T][U+1][C], contiguous, read in place.  targets_device: int32 [B][U].  frames_device and
+ * target_lengths_device: int32 [B], T_b and U_b, read on the device.  Rows with t >= T_b or u > U_b are never read.
+ * -inf, never NaN: T_b == 0, T_b > T, U_b > U (or negative), a token outside 0 .. C-1 or equal to blank, no path of
+ * finite score.  A live row that holds NaN or +inf, or nothing but -inf, is a node no path leaves.  U_b == 0 is valid.
+ * rows_device (or null): float32 [B][T][U+1][3]; gets (lp_blank, lp_label, lse) of every live node, for
+ * gtnx_batch_transducer_score_grad.  GTNX_INVALID_ARGUMENT before a device is asked for: a null pointer, a negative
+ * B, U+1 outside 1 .. 1024, T outside 1 .. 65535, C outside 1 .. 2^20, blank outside 0 .. C-1, B*T*(U+1) >= 2^31.
+ * B == 0 returns without touching a device.  With the device: logits that are not device memory, an output the
+ * engine's current device may not write.  Launches on the engine's stream (transducer.hip: rows, sweep), per slice of
+ * at most 256 MiB of pooled scratch (12 bytes per node; none with rows_device); no copy back, no wait.  The same bits
+ * run to run, sliced or not, whatever an utterance's neighbours are, with or without rows_device. */
+gtnx_status_t gtnx_batch_transducer_score(const void* logits_device, const void* targets_device,
+                                          const void* frames_device, const void* target_lengths_device, int B, int T,
+                                          int U, int C, int blank, int normalize, void* scores_device,
+                                          void* rows_device);
+/* The gradient of those scores under caller-supplied weights_device (float32 [B]; grad_out under autograd):
+ *   grad_device float32 [B][T][U+1][C] = weights[b] * d scores[b] / d logits[b]
+ *     = w * ([c == blank] occ_b + [c == y[u]] occ_l - (normalize ? exp(lp[t,u,c]) * (occ_b + occ_l) : 0)).
+ * EVERY row is stored exactly once by the gradient launch itself (there is no memset): the never-read rows, the rows
+ * of an utterance that scores -inf and dead rows with zeros.  rows_device (or null): the plane the score call left in
+ * it for the SAME inputs; with it the pass that recomputes the plane is skipped.  The same refusals as the score call.
+ * Pooled scratch: 20 bytes per node (8 with rows_device), sliced over utterances under the 256 MiB cap with the same
+ * bits (GTNX_TRANSDUCER_SCRATCH_BYTES, read per call, lowers the cap: a debug switch).  Launches per slice: rows, sweep
+ * (alpha and beta side by side), gradient.  No floating-point atomics. */
+gtnx_status_t gtnx_batch_transducer_score_grad(const void* logits_device, const void* targets_device,
+                                               const void* frames_device, const void* target_lengths_device, int B,
+                                               int T, int U, int C, int blank, int normalize,
+                                               const void* weights_device, void* grad_device,
+                                               const void* rows_device);
+/* calls of either kind that have launched so far (process-wide) / utterances they took */
+gtnx_status_t gtnx_batch_transducer_stats(int64_t* calls, int64_t* utterances);
 /* The exact ASG log score of ONE ACYCLIC TOKEN LATTICE PER UTTERANCE -- gtnx_batch_ctc_lattice_score's lattices under
  * gtnx_batch_asg_score's criterion:
  *   scores[b] = log sum over the lattice's paths p of exp(w(p) + asg_score(emissions_b[0 .. T_b), table, labels(p))),
