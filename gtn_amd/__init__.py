@@ -78,6 +78,9 @@ edit_distance = _api.edit_distance  # (batched Levenshtein distance of device-re
 transducer_score = _api.transducer_score  # (batched transducer / RNN-T log score over device-resident joint logits)
 transducer_score_grad = _api.transducer_score_grad  # (its gradient under per-utterance weights, every row written)
 debug_transducer_stats = _api.debug_transducer_stats  # (transducer_score / _grad: calls that launched, utterances)
+transducer_add_score = _api.transducer_add_score  # (the same score under an additive joint am + lm, never formed)
+transducer_add_score_grad = _api.transducer_add_score_grad  # (its gradients for am and lm, every element written)
+debug_transducer_add_stats = _api.debug_transducer_add_stats  # (transducer_add_score / _grad: calls, utterances)
 ctc_loss_step16 = _api.ctc_loss_step16  # (one CTC criterion step over bfloat16 / float16 emissions, one launch)
 debug_edit_distance_stats = _api.debug_edit_distance_stats  # (edit_distance: calls that launched, pairs computed)
 debug_ctc_score_stats = _api.debug_ctc_score_stats  # (Batch.ctc_score / ctc_score_grad: calls that launched, pairs taken)

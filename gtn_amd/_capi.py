@@ -190,6 +190,12 @@ _SIGS = {
     "gtnx_batch_transducer_score_grad": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "gtnx_batch_transducer_stats": [c_i64_p, c_i64_p],
+    "gtnx_batch_transducer_add_score": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "gtnx_batch_transducer_add_score_grad": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p],
+    "gtnx_batch_transducer_add_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_asg_lattice_score": [c_graph, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "gtnx_batch_asg_lattice_score_grad": [c_graph, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

@@ -1991,6 +1991,88 @@ def make_api(lib):
                                                    int(bool(normalize)), _opt_ptr(weights), _opt_ptr(grad_out),
                                                    _opt_ptr(rows)))
 
+    def debug_transducer_add_stats():
+        """(calls, utterances): calls of transducer_add_score / transducer_add_score_grad that have launched so far and
+        the utterances they took (include/gtn_amd.h: gtnx_batch_transducer_add_stats)"""
+        return _stats2(lib.gtnx_batch_transducer_add_stats)
+
+    def _transducer_add_args(who, am, lm, targets, frames, target_lengths, blank, dims, outs):
+        """(B, T, U, C) of an additive-joint call: from `am` [B, T, C] and `lm` [B, U + 1, C] when they are tensors,
+        else from `dims`; the tensors among the arguments are checked against them, as _transducer_args does."""
+        if hasattr(am, "data_ptr") != hasattr(lm, "data_ptr"):
+            raise ValueError(f"{who}: am and lm must both be tensors or both be device addresses")
+        if hasattr(am, "data_ptr"):
+            for x, what in ((am, "am must be a float32 contiguous tensor [B, T, C]"),
+                            (lm, "lm must be a float32 contiguous tensor [B, U + 1, C]")):
+                if str(x.dtype) != "torch.float32" or x.dim() != 3 or not x.is_contiguous():
+                    raise ValueError(f"{who}: {what}")
+            if am.shape[0] != lm.shape[0] or am.shape[2] != lm.shape[2]:
+                raise ValueError(f"{who}: am {tuple(am.shape)} and lm {tuple(lm.shape)} must agree in B and C")
+            shape = (am.shape[0], am.shape[1], lm.shape[1] - 1, am.shape[2])
+            for name, have, want in zip("BTUC", dims, shape):
+                if have is not None and int(have) != want:
+                    raise ValueError(f"{who}: {name} = {have} is not what am and lm say ({want})")
+            dims = shape
+        if any(d is None for d in dims):
+            raise ValueError(f"{who}: a device address needs B, T, U and C")
+        b, t, u, c = (int(d) for d in dims)
+        if not 0 <= int(blank) < max(c, 1):
+            raise ValueError(f"{who}: blank must be one of the {c} labels")
+        checks = [(am, "torch.float32", None, "am"), (lm, "torch.float32", None, "lm"),
+                  (targets, "torch.int32", b * u, "targets must be an int32 contiguous tensor [B, U]"),
+                  (frames, "torch.int32", b, "frames must be an int32 contiguous tensor [B]"),
+                  (target_lengths, "torch.int32", b, "target_lengths must be an int32 contiguous tensor [B]")]
+        for o, dtype, count, what in checks + [(o, "torch.float32", n(b, t, u, c), w) for o, n, w in outs]:
+            if o is not None and hasattr(o, "data_ptr"):
+                if count is not None and (str(o.dtype) != dtype or not o.is_contiguous() or o.numel() != count):
+                    raise ValueError(f"{who}: {what}")
+                if hasattr(o, "is_cuda") and not o.is_cuda:  # (a host tensor's address means nothing to the kernel)
+                    raise ValueError(f"{who}: {what.split()[0]} must be a CUDA tensor")
+        return b, t, u, c
+
+    def transducer_add_score(am, lm, targets, frames, target_lengths, scores_out, rows_out=None, blank=0, B=None, T=None,
+                             U=None, C=None):
+        """The transducer (RNN-T) log score under an additive joint, without the joint tensor
+        (gtnx_batch_transducer_add_score; DESIGN section 43 holds the contract): the logits are am[b, t, c] + lm[b, u, c]
+        and are never formed.  `am`: float32 CUDA tensor [B, T, C]; `lm`: float32 CUDA tensor [B, U + 1, C] (or device
+        addresses with B, T, U and C); the other arguments and the -inf cases as `transducer_score`, always normalised.
+        The normaliser is a float32 matrix product of exponentials: accurate while every live row of am and of lm spans
+        at most 40 nats (max - finite min), -inf entries allowed; a node whose sum underflows is dead, never NaN.
+        `rows_out` (float32 [B, T, U + 1, 3] or None) keeps the compact plane for `transducer_add_score_grad`."""
+        who = "transducer_add_score"
+        b, t, u, c = _transducer_add_args(
+            who, am, lm, targets, frames, target_lengths, blank, (B, T, U, C),
+            [(scores_out, lambda b, t, u, c: b, "scores_out must be a float32 contiguous tensor [B]"),
+             (rows_out, lambda b, t, u, c: 3 * b * t * (u + 1),
+              "rows_out must be a float32 contiguous tensor [B, T, U + 1, 3]")])
+        if b == 0 and hasattr(am, "data_ptr"):
+            return  # (no utterance, nothing to launch -- and an empty tensor has no address to hand to the engine)
+        check(lib.gtnx_batch_transducer_add_score(_opt_ptr(am), _opt_ptr(lm), _transducer_targets(targets, b, u),
+                                                  _opt_ptr(frames), _opt_ptr(target_lengths), b, t, u, c, int(blank),
+                                                  _opt_ptr(scores_out), _opt_ptr(rows_out)))
+
+    def transducer_add_score_grad(am, lm, targets, frames, target_lengths, weights, grad_am_out, grad_lm_out, rows=None,
+                                  blank=0, B=None, T=None, U=None, C=None):
+        """The gradients of the scores of `transducer_add_score` under `weights` (float32 [B] on the device), in one
+        stateless call (gtnx_batch_transducer_add_score_grad): `grad_am_out` (float32 [B, T, C]) and `grad_lm_out`
+        (float32 [B, U + 1, C]) are the joint's gradient summed over u and over t, every element stored exactly once --
+        rows t >= T_b / u > U_b and utterances that score -inf with zeros.  `rows`: the plane `transducer_add_score`
+        left in `rows_out` for the same inputs, or None.  No atomics, the same bits run to run, sliced or not."""
+        who = "transducer_add_score_grad"
+        b, t, u, c = _transducer_add_args(
+            who, am, lm, targets, frames, target_lengths, blank, (B, T, U, C),
+            [(weights, lambda b, t, u, c: b, "weights must be a float32 contiguous tensor [B]"),
+             (grad_am_out, lambda b, t, u, c: b * t * c, "grad_am_out must be a float32 contiguous tensor [B, T, C]"),
+             (grad_lm_out, lambda b, t, u, c: b * (u + 1) * c,
+              "grad_lm_out must be a float32 contiguous tensor [B, U + 1, C]"),
+             (rows, lambda b, t, u, c: 3 * b * t * (u + 1), "rows must be a float32 contiguous tensor [B, T, U + 1, 3]")])
+        if b == 0 and hasattr(am, "data_ptr"):
+            return
+        check(lib.gtnx_batch_transducer_add_score_grad(_opt_ptr(am), _opt_ptr(lm), _transducer_targets(targets, b, u),
+                                                       _opt_ptr(frames), _opt_ptr(target_lengths), b, t, u, c,
+                                                       int(blank), _opt_ptr(weights), _opt_ptr(grad_am_out),
+                                                       _opt_ptr(grad_lm_out), _opt_ptr(rows)))
+
     def ctc_loss_step16(emissions, targets, loss_out, grad_out, blank=0, input_lengths=None):
         """One CTC criterion step over 16-bit emissions in one launch (gtnx_batch_ctc_loss_step16 has the contract).
         `emissions`: bfloat16 or float16 CUDA tensor [B, T, C], contiguous, read in place; `targets`: B label sequences;
@@ -2077,6 +2159,9 @@ def make_api(lib):
     ns.transducer_score = transducer_score
     ns.transducer_score_grad = transducer_score_grad
     ns.debug_transducer_stats = debug_transducer_stats
+    ns.transducer_add_score = transducer_add_score
+    ns.transducer_add_score_grad = transducer_add_score_grad
+    ns.debug_transducer_add_stats = debug_transducer_add_stats
     ns.ctc_loss_step16 = ctc_loss_step16
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties

@@ -457,6 +457,27 @@ GTN_EXPORT int gtn_transducer_score_grad_n(const void* logits, const void* targe
   });
 }
 
+// Transducer log scores under an additive joint.  am: DEVICE float32 [B][T][C]; lm: DEVICE float32 [B][U+1][C]; the
+// rest as gtn_transducer_score_n, always normalised.
+GTN_EXPORT int gtn_transducer_add_score_n(const void* am, const void* lm, const void* targets, const void* frames,
+                                          const void* target_lengths, int B, int T, int U, int C, int blank,
+                                          void* scores, void* rows) {
+  return guarded([&] {
+    gtn::criteria::transducerAddScoreBatch(am, lm, targets, frames, target_lengths, B, T, U, C, blank, scores, rows);
+  });
+}
+
+// ... and their gradients under weights: DEVICE float32 [B]: grad_am (DEVICE float32 [B][T][C]) and grad_lm (DEVICE
+// float32 [B][U+1][C]), every element written; rows: the plane gtn_transducer_add_score_n left, or null.
+GTN_EXPORT int gtn_transducer_add_score_grad_n(const void* am, const void* lm, const void* targets, const void* frames,
+                                               const void* target_lengths, int B, int T, int U, int C, int blank,
+                                               const void* weights, void* grad_am, void* grad_lm, const void* rows) {
+  return guarded([&] {
+    gtn::criteria::transducerAddScoreGradBatch(am, lm, targets, frames, target_lengths, B, T, U, C, blank, weights,
+                                               grad_am, grad_lm, rows);
+  });
+}
+
 // Exact ASG log scores of one device-resident token lattice per utterance.  emissions: DEVICE float32 [B][T][C]; table:
 // DEVICE float32 [C + C*C] as for gtn_asg_score_n; frames: HOST int [B] or null; arcs: DEVICE int32 [B][A][3]; num_arcs /
 // num_nodes: DEVICE int32 [B]; arc_weights: DEVICE float32 [B][A] or null; scores: DEVICE float32 [B].

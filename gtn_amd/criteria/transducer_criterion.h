@@ -60,5 +60,57 @@ inline void transducerScoreGradBatch(
                                static_cast<const float*>(rowsDev));
 }
 
+/** The same scores under an additive joint: `amDev` device float32 [B][T][C] and `lmDev` device float32 [B][U + 1][C]
+ *  stand for the logits amDev[b][t][c] + lmDev[b][u][c], which are never formed; always normalised.
+ *  gtnx_batch_transducer_add_score has the contract and the float32 domain.  Nothing is copied back. */
+inline void transducerAddScoreBatch(
+    const void* amDev,
+    const void* lmDev,
+    const void* targetsDev,
+    const void* framesDev,
+    const void* targetLengthsDev,
+    int B,
+    int T,
+    int U,
+    int C,
+    int blank,
+    void* scoresDev,
+    void* rowsDev = nullptr) {
+  if (!scoresDev) {
+    throw std::invalid_argument("transducerAddScoreBatch: null scores");
+  }
+  batched::transducerAddScore(static_cast<const float*>(amDev), static_cast<const float*>(lmDev),
+                              static_cast<const int*>(targetsDev), static_cast<const int*>(framesDev),
+                              static_cast<const int*>(targetLengthsDev), B, T, U, C, blank,
+                              static_cast<float*>(scoresDev), static_cast<float*>(rowsDev));
+}
+
+/** Their gradients under `weightsDev` (device float32 [B]): `gradAmDev` device float32 [B][T][C] and `gradLmDev` device
+ *  float32 [B][U + 1][C], every element written; `rowsDev` the plane transducerAddScoreBatch left, or null. */
+inline void transducerAddScoreGradBatch(
+    const void* amDev,
+    const void* lmDev,
+    const void* targetsDev,
+    const void* framesDev,
+    const void* targetLengthsDev,
+    int B,
+    int T,
+    int U,
+    int C,
+    int blank,
+    const void* weightsDev,
+    void* gradAmDev,
+    void* gradLmDev,
+    const void* rowsDev = nullptr) {
+  if (!weightsDev || !gradAmDev || !gradLmDev) {
+    throw std::invalid_argument("transducerAddScoreGradBatch: null weights or gradient");
+  }
+  batched::transducerAddScoreGrad(static_cast<const float*>(amDev), static_cast<const float*>(lmDev),
+                                  static_cast<const int*>(targetsDev), static_cast<const int*>(framesDev),
+                                  static_cast<const int*>(targetLengthsDev), B, T, U, C, blank,
+                                  static_cast<const float*>(weightsDev), static_cast<float*>(gradAmDev),
+                                  static_cast<float*>(gradLmDev), static_cast<const float*>(rowsDev));
+}
+
 } // namespace criteria
 } // namespace gtn

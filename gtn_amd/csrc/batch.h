@@ -472,6 +472,25 @@ void batch_transducer_score_grad(const float* logits_dev, const int* targets_dev
                                  const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
                                  const float* weights_dev, float* grad_dev, const float* rows_dev);
 void batch_transducer_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
+// The same score under an ADDITIVE joint, logits z[b,t,u,c] = am[b,t,c] + lm[b,u,c] that are never formed (DESIGN section
+// 43 holds the contract): am_dev float32 [B][T][C], lm_dev float32 [B][U + 1][C], the rest as batch_transducer_score;
+// always normalised.  The normaliser is a float32 matrix product of exponentials: the accuracy holds while every live
+// row of am and of lm spans at most 40 nats (max - finite min); a node whose sum underflows is dead, never NaN; -inf
+// entries are allowed.  The same refusals, the same -inf cases, the same rows_dev plane.  Pooled scratch per utterance:
+// 12 bytes per node (none with rows_dev) plus 4 (T + U + 1), sliced under GTNX_TRANSDUCER_SCRATCH_BYTES' cap.  Three
+// launches per slice (max, norm, sweep), no copy back, no wait.
+void batch_transducer_add_score(const float* am_dev, const float* lm_dev, const int* targets_dev, const int* frames_dev,
+                                const int* target_lengths_dev, int B, int T, int U, int C, int blank, float* scores_dev,
+                                float* rows_dev);
+// grad_am_dev [B][T][C] = sum over u, grad_lm_dev [B][U + 1][C] = sum over t of weights_dev[b] * d score[b] / d z[b]:
+// every element of both stored exactly once, rows t >= T_b / u > U_b and utterances that score -inf with zeros.
+// rows_dev (or null): the plane batch_transducer_add_score left; with it the norm launch is skipped.  20 bytes of pooled
+// scratch per node (8 with rows) plus 4 (T + U + 1) per utterance.  No floating-point atomics.
+void batch_transducer_add_score_grad(const float* am_dev, const float* lm_dev, const int* targets_dev,
+                                     const int* frames_dev, const int* target_lengths_dev, int B, int T, int U, int C,
+                                     int blank, const float* weights_dev, float* grad_am_dev, float* grad_lm_dev,
+                                     const float* rows_dev);
+void batch_transducer_add_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
 // The exact ASG log score of one device-resident acyclic token lattice per utterance (batch_ctc_lattice_score's form)
 // under the n emission slabs of a native linear batch and the [C + C * C] table of batch_asg_score, results on the device
 // (DESIGN section 37 holds the contract): scores_dev[b] = log sum over the lattice's paths p of exp(w(p) +

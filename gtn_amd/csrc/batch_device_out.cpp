@@ -1701,6 +1701,125 @@ void batch_transducer_score_grad(const float* logits_dev, const int* targets_dev
                   C, blank, normalize, nullptr, const_cast<float*>(rows_dev), weights_dev, grad_dev);
 }
 
+// ---- batched transducer score under an additive joint, am + lm never formed, and its gradients (transducer_add.hip) ----
+namespace {
+Counters g_transducer_add;  // (calls, utterances)
+
+// both entry points, as transducer_impl: scores_dev for the score, weights_dev and the two gradients for the gradient
+void transducer_add_impl(const char* who, const float* am, const float* lm, const int* targets, const int* frames,
+                         const int* tlen, int B, int T, int U, int C, int blank, float* scores_dev, float* rows_dev,
+                         const float* weights_dev, float* grad_am_dev, float* grad_lm_dev) {
+  const bool want_grad = scores_dev == nullptr;
+  if (!am || !lm || (!targets && U > 0) || !frames || !tlen)
+    refuse(who, "null input pointer (am, lm, targets, frames and target_lengths are all read)");
+  if (want_grad && (!weights_dev || !grad_am_dev || !grad_lm_dev)) refuse(who, "null weights or grad pointer");
+  if (B < 0) refuse(who, "negative B");
+  if (U < 0 || U + 1 > kTransducerMaxU1) refuse(who, "U + 1 outside 1 .. 1024");
+  if (T < 1 || T > kTransducerMaxT) refuse(who, "T outside 1 .. 65535");
+  if (C < 1 || C > kTransducerMaxC) refuse(who, "C outside 1 .. 2^20");
+  if (blank < 0 || blank >= C) refuse(who, "blank is not one of the C labels");
+  const int U1 = U + 1;
+  const int64_t per_utt = int64_t(T) * U1;  // nodes
+  if (int64_t(B) * per_utt > std::numeric_limits<int>::max()) refuse(who, "B * T * (U + 1) does not fit an int");
+  if (B == 0) return;
+  Runtime& rt = Runtime::get();
+  if (!ptr_device_memory_of(am, rt.device()) || !ptr_device_memory_of(lm, rt.device()))
+    refuse(who, "am or lm is not memory of the engine's current device");
+  check_outputs_local(who, {scores_dev, grad_am_dev, grad_lm_dev, want_grad ? nullptr : rows_dev});
+  TransducerAddArgs a{};
+  a.am = am;
+  a.lm = lm;
+  a.targets = targets;
+  a.frames = frames;
+  a.tlen = tlen;
+  a.weights = weights_dev;
+  a.grad_am = grad_am_dev;
+  a.grad_lm = grad_lm_dev;
+  a.T = T;
+  a.U1 = U1;
+  a.C = C;
+  a.blank = blank;
+  TransducerArgs sw{};  // the sweep's view of the same slice
+  sw.targets = targets;
+  sw.frames = frames;
+  sw.tlen = tlen;
+  sw.T = T;
+  sw.U1 = U1;
+  sw.C = C;
+  sw.blank = blank;
+  sw.normalize = 1;
+  DevMemP sc;  // (the gradient's scores: a slice's own, read by its gradient launch)
+  if (want_grad) sc = rt.alloc(sizeof(float) * size_t(B));
+  sw.scores = want_grad ? sc->as<float>() : scores_dev;
+  a.scores = sw.scores;
+  // per utterance: the triples (unless the caller keeps them), alpha and beta for the gradient, ma and ml
+  const int64_t own_rows = rows_dev ? 0 : 12;
+  const int64_t node_bytes = own_rows + (want_grad ? 8 : 0);
+  const int64_t per_bytes = per_utt * node_bytes + 4 * int64_t(T + U1);
+  const bool have_rows = want_grad && rows_dev;
+  for_pair_slices(B, per_bytes, kTransducerScratch, [&](int64_t b0, int64_t cnt) {
+    const size_t nodes = size_t(per_utt) * size_t(cnt);
+    DevMemP work = rt.alloc(size_t(per_bytes) * size_t(cnt));
+    a.utt0 = sw.utt0 = int(b0);
+    a.count = sw.count = int(cnt);
+    a.rows = rows_dev ? const_cast<float*>(rows_dev) + 3 * per_utt * b0 : work->as<float>();
+    a.alpha = want_grad ? work->as<float>(size_t(own_rows) * nodes) : nullptr;
+    a.beta = want_grad ? work->as<float>(size_t(own_rows + 4) * nodes) : nullptr;
+    a.ma = work->as<float>(size_t(node_bytes) * nodes);
+    a.ml = a.ma + size_t(T) * size_t(cnt);
+    sw.rows = a.rows;
+    sw.alpha = a.alpha;
+    sw.beta = a.beta;
+    const double in_rows = double(cnt) * (T + U1);
+    {  // (the gradient's products need ma and ml with or without the caller's triples)
+      GTNX_PROF("transducer_add_max", in_rows * (4.0 * C + 4.0));
+      launch_transducer_add_max(a, rt.stream());
+    }
+    if (!have_rows) {
+      // bytes: a t tile reads its 64 am rows once per u tile and the other way round; 12 bytes out per node
+      const double tt = (T + 63) / 64, tu = (U1 + 63) / 64;
+      GTNX_PROF("transducer_add_norm", double(cnt) * 4.0 * C * (T * tu + U1 * tt) + 12.0 * double(nodes));
+      launch_transducer_add_norm(a, rt.stream());
+    }
+    {
+      GTNX_PROF("transducer_sweep", double(nodes) * (want_grad ? 24.0 : 8.0) + 4.0 * double(cnt));
+      launch_transducer_sweep(sw, rt.stream());
+    }
+    if (want_grad) {
+      // bytes: each output element once, its own input once, the other input once per 64 output rows, and the 24
+      // bytes of a node once per tile of 64 labels and product
+      const double tc = (C + 63) / 64;
+      GTNX_PROF("transducer_add_grad", in_rows * 8.0 * C + double(cnt) * 4.0 * C * (double(U1) * ((T + 63) / 64) +
+                                                                                     double(T) * ((U1 + 63) / 64)) +
+                                           2.0 * tc * 24.0 * double(nodes));
+      launch_transducer_add_grad(a, rt.stream());
+    }
+  });
+  g_transducer_add.add(1, B);
+}
+}  // namespace
+
+void batch_transducer_add_stats(int64_t* calls, int64_t* utterances) { g_transducer_add.get(calls, utterances); }
+
+void batch_transducer_add_score(const float* am_dev, const float* lm_dev, const int* targets_dev, const int* frames_dev,
+                                const int* target_lengths_dev, int B, int T, int U, int C, int blank, float* scores_dev,
+                                float* rows_dev) {
+  GTNX_HOST_T("batch.transducer_add_score");
+  if (!scores_dev) throw_invalid("[gtnx_batch_transducer_add_score] null scores pointer");
+  transducer_add_impl("gtnx_batch_transducer_add_score", am_dev, lm_dev, targets_dev, frames_dev, target_lengths_dev, B,
+                      T, U, C, blank, scores_dev, rows_dev, nullptr, nullptr, nullptr);
+}
+
+void batch_transducer_add_score_grad(const float* am_dev, const float* lm_dev, const int* targets_dev,
+                                     const int* frames_dev, const int* target_lengths_dev, int B, int T, int U, int C,
+                                     int blank, const float* weights_dev, float* grad_am_dev, float* grad_lm_dev,
+                                     const float* rows_dev) {
+  GTNX_HOST_T("batch.transducer_add_score_grad");
+  transducer_add_impl("gtnx_batch_transducer_add_score_grad", am_dev, lm_dev, targets_dev, frames_dev,
+                      target_lengths_dev, B, T, U, C, blank, nullptr, const_cast<float*>(rows_dev), weights_dev,
+                      grad_am_dev, grad_lm_dev);
+}
+
 // ---- batched ASG score of one device-resident token lattice per utterance, and its gradients (asg_lattice.hip) ----
 namespace {
 Counters g_asg_lattice;  // (calls, utterances)

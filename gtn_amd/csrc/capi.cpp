@@ -1219,6 +1219,34 @@ GTNX_API gtnx_status_t gtnx_batch_transducer_score_grad(const void* logits_devic
 GTNX_API gtnx_status_t gtnx_batch_transducer_stats(int64_t* calls, int64_t* utterances) {
   return guard([&] { batch_transducer_stats(calls, utterances); });
 }
+GTNX_API gtnx_status_t gtnx_batch_transducer_add_score(const void* am_device, const void* lm_device,
+                                                       const void* targets_device, const void* frames_device,
+                                                       const void* target_lengths_device, int B, int T, int U, int C,
+                                                       int blank, void* scores_device, void* rows_device) {
+  return guard([&] {
+    batch_transducer_add_score(static_cast<const float*>(am_device), static_cast<const float*>(lm_device),
+                               static_cast<const int*>(targets_device), static_cast<const int*>(frames_device),
+                               static_cast<const int*>(target_lengths_device), B, T, U, C, blank,
+                               static_cast<float*>(scores_device), static_cast<float*>(rows_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_transducer_add_score_grad(const void* am_device, const void* lm_device,
+                                                            const void* targets_device, const void* frames_device,
+                                                            const void* target_lengths_device, int B, int T, int U,
+                                                            int C, int blank, const void* weights_device,
+                                                            void* grad_am_device, void* grad_lm_device,
+                                                            const void* rows_device) {
+  return guard([&] {
+    batch_transducer_add_score_grad(static_cast<const float*>(am_device), static_cast<const float*>(lm_device),
+                                    static_cast<const int*>(targets_device), static_cast<const int*>(frames_device),
+                                    static_cast<const int*>(target_lengths_device), B, T, U, C, blank,
+                                    static_cast<const float*>(weights_device), static_cast<float*>(grad_am_device),
+                                    static_cast<float*>(grad_lm_device), static_cast<const float*>(rows_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_transducer_add_stats(int64_t* calls, int64_t* utterances) {
+  return guard([&] { batch_transducer_add_stats(calls, utterances); });
+}
 GTNX_API gtnx_status_t gtnx_batch_asg_lattice_score(gtnx_batch_t ems, const int* frames, const void* table_device,
                                                     const void* arcs_device, int64_t row_stride,
                                                     const void* num_arcs_device, const void* num_nodes_device,

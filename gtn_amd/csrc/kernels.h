@@ -1218,6 +1218,35 @@ struct TransducerArgs {
 void launch_transducer_rows(const TransducerArgs& a, hipStream_t st);
 void launch_transducer_sweep(const TransducerArgs& a, hipStream_t st);
 void launch_transducer_grad(const TransducerArgs& a, hipStream_t st);
+// transducer_add.hip: the same score under an additive joint, logits z[b,t,u,c] = am[b,t,c] + lm[b,u,c] that are never
+// formed, and the gradients weights[b] * d score[b] / d am[b], d lm[b] (the contract and the float32 domain: DESIGN
+// section 43).  The slice's planes are indexed as TransducerArgs' are; ma / ml are indexed by (b - utt0) * T + t and
+// (b - utt0) * U1 + u.
+//   max:   the row maxima of the live rows of am and lm into ma and ml; +inf marks a dead row (NaN, +inf, all -inf).
+//   norm:  S = exp(am - ma) exp(lm - ml)^T in 64 x 64 MFMA tiles and, from it, the compact triple of every live node in
+//          `rows`, exactly the plane launch_transducer_rows leaves; launch_transducer_sweep then runs on it unchanged.
+//   grad:  every element of grad_am [n][T][C] and grad_lm [n][U1][C] of the slice's utterances exactly once, from ma,
+//          ml, rows, alpha, beta and scores; rows past the lengths and utterances that score -inf as zeros.
+struct TransducerAddArgs {
+  const GTNX_G float* am;        // [n][T][C]
+  const GTNX_G float* lm;        // [n][U1][C]
+  const GTNX_G int* targets;     // [n][U1 - 1]
+  const GTNX_G int* frames;      // [n]
+  const GTNX_G int* tlen;        // [n]
+  GTNX_G float* ma;              // [count][T]
+  GTNX_G float* ml;              // [count][U1]
+  GTNX_G float* rows;            // [count][T][U1][3]
+  GTNX_G float* alpha;           // [count][T][U1] (grad)
+  GTNX_G float* beta;            // [count][T][U1] (grad)
+  const GTNX_G float* scores;    // [n] (grad)
+  const GTNX_G float* weights;   // [n] (grad)
+  GTNX_G float* grad_am;         // [n][T][C] (grad)
+  GTNX_G float* grad_lm;         // [n][U1][C] (grad)
+  int T, U1, C, blank, utt0, count;
+};
+void launch_transducer_add_max(const TransducerAddArgs& a, hipStream_t st);
+void launch_transducer_add_norm(const TransducerAddArgs& a, hipStream_t st);
+void launch_transducer_add_grad(const TransducerAddArgs& a, hipStream_t st);
 // asg_lattice.hip: the ASG log score of the utterances utt0 .. utt0 + count - 1, each with one acyclic token lattice of its
 // own in device memory (ctc_lattice.hip's form), under asg_score.hip's [C + C * C] table, and the gradients g[b] * d
 // score[b] / d (emissions_b, table, arc weights of b) (the contract: DESIGN section 37).  The states are the arcs; an

@@ -51,6 +51,8 @@ _ARGTYPES = {
     "gtn_asg_full_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gtn_transducer_score_n": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "gtn_transducer_score_grad_n": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "gtn_transducer_add_score_n": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "gtn_transducer_add_score_grad_n": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "gtn_asg_lattice_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_lattice_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "gtn_asg_lattice_align_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
@@ -1537,6 +1539,110 @@ def transducer_loss(logits, targets, input_lengths, target_lengths, blank=0, nor
     if reduction not in ("none", "sum", "mean"):
         raise ValueError('transducer_loss: reduction must be "none", "sum" or "mean"')
     loss = -transducer_score(logits, targets, input_lengths, target_lengths, blank, normalize)
+    return loss if reduction == "none" else (loss.sum() if reduction == "sum" else loss.mean())
+
+
+class _TransducerAddScore(torch.autograd.Function):
+    """forward: the max, norm and alpha launches; where am or lm requires grad the compact plane `rows` is kept as a saved
+    tensor.  backward: the one gradient call with grad_out as the weights; it writes both gradients."""
+
+    @staticmethod
+    def forward(ctx, am, lm, targets, frames, tlen, blank):
+        a, l = am.detach().contiguous(), lm.detach().contiguous()
+        B, T, C_ = a.shape
+        U1 = l.shape[1]
+        stream = _engine_stream(a.device)
+        scores = torch.empty(B, dtype=torch.float32, device=a.device)
+        keep = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        rows = torch.empty(B, T, U1, 3, dtype=torch.float32, device=a.device) if keep else None
+        if B:
+            args = (a.data_ptr(), l.data_ptr(), targets.data_ptr() if targets.numel() else None, frames.data_ptr(),
+                    tlen.data_ptr())
+            if _has_native("transducer_add_score", "gtn_transducer_add_score_n"):
+                _call("gtn_transducer_add_score_n", *args, B, T, U1 - 1, C_, blank, scores.data_ptr(), _ptr(rows))
+            else:
+                gtn.transducer_add_score(*args, scores.data_ptr(), _ptr(rows), blank, B=B, T=T, U=U1 - 1, C=C_)
+        _engine_done(stream)
+        ctx.save_for_backward(a, l, targets, frames, tlen, rows)
+        ctx.blank = blank
+        return scores
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        a, l, targets, frames, tlen, rows = ctx.saved_tensors
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None, None, None, None
+        B, T, C_ = a.shape
+        U1 = l.shape[1]
+        ga, gl = torch.empty_like(a), torch.empty_like(l)
+        if B:
+            g = grad_out.detach().to(torch.float32).contiguous()
+            stream = _engine_stream(a.device)
+            args = (a.data_ptr(), l.data_ptr(), targets.data_ptr() if targets.numel() else None, frames.data_ptr(),
+                    tlen.data_ptr())
+            if _native():
+                _call("gtn_transducer_add_score_grad_n", *args, B, T, U1 - 1, C_, ctx.blank, g.data_ptr(),
+                      ga.data_ptr(), gl.data_ptr(), _ptr(rows))
+            else:
+                gtn.transducer_add_score_grad(*args, g.data_ptr(), ga.data_ptr(), gl.data_ptr(), _ptr(rows), ctx.blank,
+                                              B=B, T=T, U=U1 - 1, C=C_)
+            _engine_done(stream)
+        return (ga if ctx.needs_input_grad[0] else None, gl if ctx.needs_input_grad[1] else None, None, None, None,
+                None)
+
+
+def transducer_add_score(am, lm, targets, input_lengths, target_lengths, blank=0):
+    """The transducer (RNN-T) log score under an additive joint, differentiable with respect to both inputs, without the
+    joint tensor: score[b] = transducer_score(am[:, :, None] + lm[:, None], ...)[b], normalised, and the [B, T, U + 1, C]
+    sum is never formed.  am: float32 CUDA tensor [B, T, C] (the encoder's projection); lm: float32 CUDA tensor
+    [B, U + 1, C] (the predictor's); targets, input_lengths, target_lengths, the limits and the -inf cases as
+    transducer_score.  Rows t >= T_b of am and u > U_b of lm are never read and their gradient rows are exactly 0.
+    The normaliser and both gradients are float32 matrix products of exponentials: the accuracy holds while every live
+    row of am and of lm spans at most 40 nats (max - finite min); -inf entries (masked labels) are allowed; a node whose
+    sum underflows is a dead node, never NaN.  The backward is one call, bit-repeatable (no atomics); the forward keeps
+    12 bytes per node where a gradient is wanted.  Runs on the caller's stream."""
+    who = "transducer_add_score"
+    for x, what in ((am, "am must be a float32 tensor [B, T, C]"), (lm, "lm must be a float32 tensor [B, U + 1, C]")):
+        if not (torch.is_tensor(x) and x.dim() == 3 and x.dtype == torch.float32):
+            raise ValueError(f"{who}: {what}")
+    B, T, C_ = am.shape
+    U1 = lm.shape[1]
+    if lm.shape[0] != B or lm.shape[2] != C_:
+        raise ValueError(f"{who}: am {tuple(am.shape)} and lm {tuple(lm.shape)} must agree in B and C")
+    if not 1 <= U1 <= 1024:
+        raise ValueError(f"{who}: U + 1 must be 1 .. 1024")
+    if not (torch.is_tensor(targets) and targets.dtype in (torch.int32, torch.int64)
+            and tuple(targets.shape) == (B, U1 - 1)):
+        raise ValueError(f"{who}: targets must be an int32 or int64 tensor [{B}, {U1 - 1}]")
+    for t, what in ((input_lengths, "input_lengths"), (target_lengths, "target_lengths")):
+        if not (torch.is_tensor(t) and t.dtype in (torch.int32, torch.int64) and tuple(t.shape) == (B,)):
+            raise ValueError(f"{who}: {what} must be an int32 or int64 tensor [{B}]")
+    if not 1 <= T <= 65535:
+        raise ValueError(f"{who}: T must be 1 .. 65535")
+    if not 1 <= C_ <= 1 << 20:
+        raise ValueError(f"{who}: the number of labels must be 1 .. 2^20")
+    if B * T * U1 >= 1 << 31:
+        raise ValueError(f"{who}: B * T * (U + 1) must be below 2^31")
+    if not 0 <= int(blank) < C_:
+        raise ValueError(f"{who}: blank must be one of the {C_} labels")
+    for t, what in ((am, "am"), (lm, "lm"), (targets, "targets"), (input_lengths, "input_lengths"),
+                    (target_lengths, "target_lengths")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {what} must be a CUDA tensor (the scores are computed on the device)")
+        if t.device != am.device:
+            raise ValueError(f"{who}: all tensors must be on one device")
+    tg = targets.detach().to(torch.int32).contiguous()  # (int64 values are converted on the device)
+    fr = input_lengths.detach().to(torch.int32).contiguous()
+    tl = target_lengths.detach().to(torch.int32).contiguous()
+    return _TransducerAddScore.apply(am, lm, tg, fr, tl, int(blank))
+
+
+def transducer_add_loss(am, lm, targets, input_lengths, target_lengths, blank=0, reduction="mean"):
+    """-transducer_add_score(...): float32 [B] with reduction "none", their sum with "sum", their mean over the batch
+    with "mean".  An utterance without a path has loss +inf."""
+    if reduction not in ("none", "sum", "mean"):
+        raise ValueError('transducer_add_loss: reduction must be "none", "sum" or "mean"')
+    loss = -transducer_add_score(am, lm, targets, input_lengths, target_lengths, blank)
     return loss if reduction == "none" else (loss.sum() if reduction == "sum" else loss.mean())
 
 

@@ -421,6 +421,28 @@ inline void transducerScoreGrad(const float* logitsDevice, const int* targetsDev
   detail::check(gtnx_batch_transducer_score_grad(logitsDevice, targetsDevice, framesDevice, targetLengthsDevice, B, T, U,
                                                  C, blank, normalize ? 1 : 0, weightsDevice, gradDevice, rowsDevice));
 }
+/** transducerScore under an additive joint, logits am[b,t,c] + lmDevice[b,u,c] that are never formed: amDevice float32
+ *  [B][T][C], lmDevice float32 [B][U + 1][C]; always normalised; everything else as transducerScore.  The normaliser is
+ *  a float32 matrix product of exponentials: accurate while every live row of am and lm spans at most 40 nats, -inf
+ *  entries allowed; an underflowed node is dead, never NaN -- gtnx_batch_transducer_add_score */
+inline void transducerAddScore(const float* amDevice, const float* lmDevice, const int* targetsDevice,
+                               const int* framesDevice, const int* targetLengthsDevice, int B, int T, int U, int C,
+                               int blank, float* scoresDevice, float* rowsDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_add_score(amDevice, lmDevice, targetsDevice, framesDevice, targetLengthsDevice, B,
+                                                T, U, C, blank, scoresDevice, rowsDevice));
+}
+/** Its gradients under weightsDevice [B]: gradAmDevice float32 [B][T][C] and gradLmDevice float32 [B][U + 1][C], the
+ *  joint's gradient summed over u and over t, every element stored exactly once (rows past the lengths with zeros).
+ *  rowsDevice (or null): the plane transducerAddScore left for the same inputs.  Bit-repeatable, sliced or not (no
+ *  atomics) -- gtnx_batch_transducer_add_score_grad */
+inline void transducerAddScoreGrad(const float* amDevice, const float* lmDevice, const int* targetsDevice,
+                                   const int* framesDevice, const int* targetLengthsDevice, int B, int T, int U, int C,
+                                   int blank, const float* weightsDevice, float* gradAmDevice, float* gradLmDevice,
+                                   const float* rowsDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_add_score_grad(amDevice, lmDevice, targetsDevice, framesDevice,
+                                                     targetLengthsDevice, B, T, U, C, blank, weightsDevice,
+                                                     gradAmDevice, gradLmDevice, rowsDevice));
+}
 /** The exact ASG log score of one device-resident acyclic token lattice per utterance (ctcLatticeScore's lattices) under
  *  the slabs of a Batch::linear and asgScore's table, results left on the device: scoresDevice[b] = log sum over the
  *  lattice's paths p of exp(w(p) + asgScore(emissions_b[0 .. T_b), table, labels(p))), nothing subtracted.  The states

@@ -866,6 +866,36 @@ gtnx_status_t gtnx_batch_transducer_score_grad(const void* logits_device, const 
                                                const void* rows_device);
 /* calls of either kind that have launched so far (process-wide) / utterances they took */
 gtnx_status_t gtnx_batch_transducer_stats(int64_t* calls, int64_t* utterances);
+/* The transducer log score under an ADDITIVE joint, without the joint tensor:
+ *   z[b,t,u,c] = am[b,t,c] + lm[b,u,c]   (never formed),   scores[b] = gtnx_batch_transducer_score's on z, normalised.
+ * am_device: float32 [B][T][C]; lm_device: float32 [B][U+1][C]; both contiguous, read in place; the other arguments, the
+ * -inf cases, the refusals and rows_device are gtnx_batch_transducer_score's.  Rows t >= T_b of am and u > U_b of lm
+ * are never read.  An am or lm row that holds NaN or +inf, or nothing but -inf, makes every node of that row a node no
+ * path leaves.  DOMAIN: the normaliser lse[t,u] = max am[t] + max lm[u] + log sum_c exp(am[t,c] - max) exp(lm[u,c] - max)
+ * is summed in float32 (v_mfma_f32_32x32x2_f32); the accuracy holds while every live row of am and of lm spans at most
+ * 40 nats (maximum minus smallest finite entry), -inf entries (masked labels) allowed; a node whose sum underflows to 0
+ * is a dead node, never NaN.  Launches per slice (transducer_add.hip: max, norm; transducer.hip: sweep); pooled scratch
+ * per utterance 12 bytes per node (none with rows_device) plus 4 (T+U+1), sliced as gtnx_batch_transducer_score's.  The
+ * same bits run to run, sliced or not, whatever an utterance's neighbours are, with or without rows_device. */
+gtnx_status_t gtnx_batch_transducer_add_score(const void* am_device, const void* lm_device, const void* targets_device,
+                                              const void* frames_device, const void* target_lengths_device, int B,
+                                              int T, int U, int C, int blank, void* scores_device, void* rows_device);
+/* Its gradients under weights_device (float32 [B]), g = weights[b] * d scores[b] / d z[b] as
+ * gtnx_batch_transducer_score_grad has it:
+ *   grad_am_device float32 [B][T][C]   = sum over u of g[b,t,u,:]
+ *   grad_lm_device float32 [B][U+1][C] = sum over t of g[b,t,u,:]
+ * as two float32 matrix products plus the blank and label terms.  EVERY element of both is stored exactly once (no
+ * memset): rows t >= T_b / u > U_b and every row of an utterance that scores -inf as zeros.  rows_device (or null): the
+ * plane the score call left for the SAME inputs; with it the norm launch is skipped.  Pooled scratch per utterance: 20
+ * bytes per node (8 with rows_device) plus 4 (T+U+1), sliced over utterances under GTNX_TRANSDUCER_SCRATCH_BYTES' cap
+ * with the same bits.  No floating-point atomics. */
+gtnx_status_t gtnx_batch_transducer_add_score_grad(const void* am_device, const void* lm_device,
+                                                   const void* targets_device, const void* frames_device,
+                                                   const void* target_lengths_device, int B, int T, int U, int C,
+                                                   int blank, const void* weights_device, void* grad_am_device,
+                                                   void* grad_lm_device, const void* rows_device);
+/* calls of either kind that have launched so far (process-wide) / utterances they took */
+gtnx_status_t gtnx_batch_transducer_add_stats(int64_t* calls, int64_t* utterances);
 /* The exact ASG log score of ONE ACYCLIC TOKEN LATTICE PER UTTERANCE -- gtnx_batch_ctc_lattice_score's lattices under
  * gtnx_batch_asg_score's criterion:
  *   scores[b] = log sum over the lattice's paths p of exp(w(p) + asg_score(emissions_b[0 .. T_b), table, labels(p))),
