@@ -81,6 +81,10 @@ debug_transducer_stats = _api.debug_transducer_stats  # (transducer_score / _gra
 transducer_add_score = _api.transducer_add_score  # (the same score under an additive joint am + lm, never formed)
 transducer_add_score_grad = _api.transducer_add_score_grad  # (its gradients for am and lm, every element written)
 debug_transducer_add_stats = _api.debug_transducer_add_stats  # (transducer_add_score / _grad: calls, utterances)
+transducer_pruned_score = _api.transducer_pruned_score  # (the score on a band of S columns per frame, [B, T, S, C])
+transducer_pruned_score_grad = _api.transducer_pruned_score_grad  # (its gradient, every band row written)
+debug_transducer_pruned_stats = _api.debug_transducer_pruned_stats  # (transducer_pruned_score / _grad: calls, utterances)
+transducer_occupancy = _api.transducer_occupancy  # (node occupancies of a full lattice from its kept rows plane)
 ctc_loss_step16 = _api.ctc_loss_step16  # (one CTC criterion step over bfloat16 / float16 emissions, one launch)
 debug_edit_distance_stats = _api.debug_edit_distance_stats  # (edit_distance: calls that launched, pairs computed)
 debug_ctc_score_stats = _api.debug_ctc_score_stats  # (Batch.ctc_score / ctc_score_grad: calls that launched, pairs taken)

@@ -196,6 +196,10 @@ _SIGS = {
                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p],
     "gtnx_batch_transducer_add_stats": [c_i64_p, c_i64_p],
+    "gtnx_batch_transducer_pruned_score": [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p, C.c_void_p],
+    "gtnx_batch_transducer_pruned_score_grad": [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_void_p],
+    "gtnx_batch_transducer_pruned_stats": [c_i64_p, c_i64_p],
+    "gtnx_batch_transducer_occupancy": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "gtnx_batch_asg_lattice_score": [c_graph, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "gtnx_batch_asg_lattice_score_grad": [c_graph, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

@@ -2073,6 +2073,115 @@ def make_api(lib):
                                                        int(blank), _opt_ptr(weights), _opt_ptr(grad_am_out),
                                                        _opt_ptr(grad_lm_out), _opt_ptr(rows)))
 
+    def debug_transducer_pruned_stats():
+        """(calls, utterances): calls of transducer_pruned_score / transducer_pruned_score_grad that have launched so far
+        and the utterances they took (include/gtn_amd.h: gtnx_batch_transducer_pruned_stats)"""
+        return _stats2(lib.gtnx_batch_transducer_pruned_stats)
+
+    def _transducer_pruned_args(who, logits, ranges, targets, frames, target_lengths, blank, dims, outs):
+        """(B, T, S, U, C) of a pruned transducer call: B, T, S, C from `logits` [B, T, S, C] and U from `targets`
+        [B, U] when they are tensors, else from `dims`; the tensors among the arguments are checked against them.
+        `outs`: (tensor or address or None, count function, text) of the float32 arguments."""
+        dims = list(dims)
+        if hasattr(logits, "data_ptr"):
+            if str(logits.dtype) != "torch.float32" or logits.dim() != 4 or not logits.is_contiguous():
+                raise ValueError(f"{who}: logits must be a float32 contiguous tensor [B, T, S, C]")
+            for i, name, want in ((0, "B", logits.shape[0]), (1, "T", logits.shape[1]), (2, "S", logits.shape[2]),
+                                  (4, "C", logits.shape[3])):
+                if dims[i] is not None and int(dims[i]) != want:
+                    raise ValueError(f"{who}: {name} = {dims[i]} is not what logits says ({want})")
+                dims[i] = want
+        if dims[3] is None and hasattr(targets, "data_ptr") and targets.dim() == 2:
+            dims[3] = targets.shape[1]
+        if any(d is None for d in dims):
+            raise ValueError(f"{who}: a device address needs B, T, S, U and C")
+        b, t, s, u, c = (int(d) for d in dims)
+        if not 0 <= int(blank) < max(c, 1):
+            raise ValueError(f"{who}: blank must be one of the {c} labels")
+        checks = [(logits, "torch.float32", None, "logits"),
+                  (ranges, "torch.int32", b * t, "ranges must be an int32 contiguous tensor [B, T]"),
+                  (targets, "torch.int32", b * u, "targets must be an int32 contiguous tensor [B, U]"),
+                  (frames, "torch.int32", b, "frames must be an int32 contiguous tensor [B]"),
+                  (target_lengths, "torch.int32", b, "target_lengths must be an int32 contiguous tensor [B]")]
+        for o, dtype, count, what in checks + [(o, "torch.float32", n(b, t, s, c), w) for o, n, w in outs]:
+            if o is not None and hasattr(o, "data_ptr"):
+                if count is not None and (str(o.dtype) != dtype or not o.is_contiguous() or o.numel() != count):
+                    raise ValueError(f"{who}: {what}")
+                if hasattr(o, "is_cuda") and not o.is_cuda:  # (a host tensor's address means nothing to the kernel)
+                    raise ValueError(f"{who}: {what.split()[0]} must be a CUDA tensor")
+        return b, t, s, u, c
+
+    def transducer_pruned_score(logits, ranges, targets, frames, target_lengths, scores_out, rows_out=None, blank=0,
+                                normalize=True, B=None, T=None, S=None, U=None, C=None):
+        """The pruned (banded) transducer log score of every utterance, left on the device
+        (gtnx_batch_transducer_pruned_score; DESIGN section 44 holds the contract).  `logits`: float32 CUDA tensor
+        [B, T, S, C], contiguous, or a device address with B, T, S, U and C: the joiner's output on the lattice columns
+        ranges[b, t] .. ranges[b, t] + S - 1 of every frame; `ranges`: int32 [B, T], non-decreasing before T_b, steps of
+        at most S - 1; `targets` int32 [B, U], `frames`, `target_lengths` int32 [B], `scores_out` float32 [B] as
+        `transducer_score`.  The score is that call's on the full lattice with every node outside the band removed; -inf,
+        never NaN, also where the band misses (0, 0) or (T_b - 1, U_b), two bands do not overlap, the ranges decrease or
+        a range is outside 0 .. U.  `rows_out` (float32 [B, T, S, 3] or None) keeps the compact plane for
+        `transducer_pruned_score_grad`.  S <= min(64, U + 1), U + 1 <= 1024, B * T * S < 2^31.  No copy back, no wait."""
+        who = "transducer_pruned_score"
+        b, t, s, u, c = _transducer_pruned_args(
+            who, logits, ranges, targets, frames, target_lengths, blank, (B, T, S, U, C),
+            [(scores_out, lambda b, t, s, c: b, "scores_out must be a float32 contiguous tensor [B]"),
+             (rows_out, lambda b, t, s, c: 3 * b * t * s, "rows_out must be a float32 contiguous tensor [B, T, S, 3]")])
+        if b == 0 and hasattr(logits, "data_ptr"):
+            return  # (no utterance, nothing to launch -- and an empty tensor has no address to hand to the engine)
+        check(lib.gtnx_batch_transducer_pruned_score(
+            _opt_ptr(logits), _opt_ptr(ranges), _transducer_targets(targets, b, u), _opt_ptr(frames),
+            _opt_ptr(target_lengths), b, t, s, u, c, int(blank), int(bool(normalize)), _opt_ptr(scores_out),
+            _opt_ptr(rows_out)))
+
+    def transducer_pruned_score_grad(logits, ranges, targets, frames, target_lengths, weights, grad_out, rows=None,
+                                     blank=0, normalize=True, B=None, T=None, S=None, U=None, C=None):
+        """The gradient of the scores of `transducer_pruned_score` under `weights` (float32 [B] on the device), in one
+        stateless call (gtnx_batch_transducer_pruned_score_grad): `grad_out` (float32 [B, T, S, C]), every row stored
+        exactly once -- rows t >= T_b, rows whose u is outside 0 .. U_b, dead rows, nodes nothing passes through and the
+        rows of an utterance that scores -inf with zeros.  `rows`: the plane `transducer_pruned_score` left in
+        `rows_out` for the same inputs, or None.  No atomics, the same bits run to run, sliced or not."""
+        who = "transducer_pruned_score_grad"
+        b, t, s, u, c = _transducer_pruned_args(
+            who, logits, ranges, targets, frames, target_lengths, blank, (B, T, S, U, C),
+            [(weights, lambda b, t, s, c: b, "weights must be a float32 contiguous tensor [B]"),
+             (grad_out, lambda b, t, s, c: b * t * s * c, "grad_out must be a float32 contiguous tensor [B, T, S, C]"),
+             (rows, lambda b, t, s, c: 3 * b * t * s, "rows must be a float32 contiguous tensor [B, T, S, 3]")])
+        if b == 0 and hasattr(logits, "data_ptr"):
+            return
+        check(lib.gtnx_batch_transducer_pruned_score_grad(
+            _opt_ptr(logits), _opt_ptr(ranges), _transducer_targets(targets, b, u), _opt_ptr(frames),
+            _opt_ptr(target_lengths), b, t, s, u, c, int(blank), int(bool(normalize)), _opt_ptr(weights),
+            _opt_ptr(grad_out), _opt_ptr(rows)))
+
+    def transducer_occupancy(rows, frames, target_lengths, out, B=None, T=None, U=None):
+        """The node occupancies of a full transducer lattice (gtnx_batch_transducer_occupancy): `out` float32
+        [B, T, U + 1] = exp(alpha + beta - score) from the compact plane `rows` (float32 CUDA tensor [B, T, U + 1, 3], or a
+        device address with B, T and U) that `transducer_score` or `transducer_add_score` left in `rows_out`; 0 outside
+        t < T_b, u <= U_b and for an utterance that scores -inf; every element stored once."""
+        who = "transducer_occupancy"
+        dims = (B, T, U)
+        if hasattr(rows, "data_ptr"):
+            if (str(rows.dtype) != "torch.float32" or rows.dim() != 4 or rows.shape[3] != 3 or rows.shape[2] < 1
+                    or not rows.is_contiguous()):
+                raise ValueError(f"{who}: rows must be a float32 contiguous tensor [B, T, U + 1, 3]")
+            dims = (rows.shape[0], rows.shape[1], rows.shape[2] - 1)
+        if any(d is None for d in dims):
+            raise ValueError(f"{who}: a device address needs B, T and U")
+        b, t, u = (int(d) for d in dims)
+        for o, dtype, count, what in ((frames, "torch.int32", b, "frames must be an int32 contiguous tensor [B]"),
+                                      (target_lengths, "torch.int32", b,
+                                       "target_lengths must be an int32 contiguous tensor [B]"),
+                                      (out, "torch.float32", b * t * (u + 1),
+                                       "out must be a float32 contiguous tensor [B, T, U + 1]")):
+            if hasattr(o, "data_ptr") and (str(o.dtype) != dtype or not o.is_contiguous() or o.numel() != count
+                                           or not o.is_cuda):
+                raise ValueError(f"{who}: {what} on the device")
+        if b == 0 and hasattr(rows, "data_ptr"):
+            return
+        check(lib.gtnx_batch_transducer_occupancy(_opt_ptr(rows), _opt_ptr(frames), _opt_ptr(target_lengths), b, t, u,
+                                                  _opt_ptr(out)))
+
     def ctc_loss_step16(emissions, targets, loss_out, grad_out, blank=0, input_lengths=None):
         """One CTC criterion step over 16-bit emissions in one launch (gtnx_batch_ctc_loss_step16 has the contract).
         `emissions`: bfloat16 or float16 CUDA tensor [B, T, C], contiguous, read in place; `targets`: B label sequences;
@@ -2162,6 +2271,10 @@ def make_api(lib):
     ns.transducer_add_score = transducer_add_score
     ns.transducer_add_score_grad = transducer_add_score_grad
     ns.debug_transducer_add_stats = debug_transducer_add_stats
+    ns.transducer_pruned_score = transducer_pruned_score
+    ns.transducer_pruned_score_grad = transducer_pruned_score_grad
+    ns.debug_transducer_pruned_stats = debug_transducer_pruned_stats
+    ns.transducer_occupancy = transducer_occupancy
     ns.ctc_loss_step16 = ctc_loss_step16
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties

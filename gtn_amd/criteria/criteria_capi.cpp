@@ -478,6 +478,35 @@ GTN_EXPORT int gtn_transducer_add_score_grad_n(const void* am, const void* lm, c
   });
 }
 
+// Pruned (banded) transducer log scores.  logits: DEVICE float32 [B][T][S][C]; ranges: DEVICE int32 [B][T]; rows: DEVICE
+// float32 [B][T][S][3] or null; the rest as gtn_transducer_score_n.
+GTN_EXPORT int gtn_transducer_pruned_score_n(const void* logits, const void* ranges, const void* targets,
+                                             const void* frames, const void* target_lengths, int B, int T, int S, int U,
+                                             int C, int blank, int normalize, void* scores, void* rows) {
+  return guarded([&] {
+    gtn::criteria::transducerPrunedScoreBatch(logits, ranges, targets, frames, target_lengths, B, T, S, U, C, blank,
+                                              normalize != 0, scores, rows);
+  });
+}
+
+// ... and their gradient under weights: DEVICE float32 [B]: grad (DEVICE float32 [B][T][S][C], every row written).
+GTN_EXPORT int gtn_transducer_pruned_score_grad_n(const void* logits, const void* ranges, const void* targets,
+                                                  const void* frames, const void* target_lengths, int B, int T, int S,
+                                                  int U, int C, int blank, int normalize, const void* weights,
+                                                  void* grad, const void* rows) {
+  return guarded([&] {
+    gtn::criteria::transducerPrunedScoreGradBatch(logits, ranges, targets, frames, target_lengths, B, T, S, U, C, blank,
+                                                  normalize != 0, weights, grad, rows);
+  });
+}
+
+// Node occupancies of a full lattice from its kept compact plane.  rows: DEVICE float32 [B][T][U+1][3]; occ: DEVICE
+// float32 [B][T][U+1].
+GTN_EXPORT int gtn_transducer_occupancy_n(const void* rows, const void* frames, const void* target_lengths, int B, int T,
+                                          int U, void* occ) {
+  return guarded([&] { gtn::criteria::transducerOccupancyBatch(rows, frames, target_lengths, B, T, U, occ); });
+}
+
 // Exact ASG log scores of one device-resident token lattice per utterance.  emissions: DEVICE float32 [B][T][C]; table:
 // DEVICE float32 [C + C*C] as for gtn_asg_score_n; frames: HOST int [B] or null; arcs: DEVICE int32 [B][A][3]; num_arcs /
 // num_nodes: DEVICE int32 [B]; arc_weights: DEVICE float32 [B][A] or null; scores: DEVICE float32 [B].

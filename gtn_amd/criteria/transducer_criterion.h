@@ -112,5 +112,75 @@ inline void transducerAddScoreGradBatch(
                                   static_cast<float*>(gradLmDev), static_cast<const float*>(rowsDev));
 }
 
+/** The pruned (banded) transducer scores: `logitsDev` device float32 [B][T][S][C], the joiner's output on the S lattice
+ *  columns rangesDev[b][t] .. + S - 1 of every frame (`rangesDev` device int32 [B][T]); the rest as
+ *  transducerScoreBatch, `rowsDev` device float32 [B][T][S][3] or null.  gtnx_batch_transducer_pruned_score has the
+ *  contract.  Nothing is copied back. */
+inline void transducerPrunedScoreBatch(
+    const void* logitsDev,
+    const void* rangesDev,
+    const void* targetsDev,
+    const void* framesDev,
+    const void* targetLengthsDev,
+    int B,
+    int T,
+    int S,
+    int U,
+    int C,
+    int blank,
+    bool normalize,
+    void* scoresDev,
+    void* rowsDev = nullptr) {
+  if (!scoresDev) {
+    throw std::invalid_argument("transducerPrunedScoreBatch: null scores");
+  }
+  batched::transducerPrunedScore(static_cast<const float*>(logitsDev), static_cast<const int*>(rangesDev),
+                                 static_cast<const int*>(targetsDev), static_cast<const int*>(framesDev),
+                                 static_cast<const int*>(targetLengthsDev), B, T, S, U, C, blank, normalize,
+                                 static_cast<float*>(scoresDev), static_cast<float*>(rowsDev));
+}
+
+/** Their gradient under `weightsDev` (device float32 [B]): `gradDev` device float32 [B][T][S][C], every row written;
+ *  `rowsDev` the plane transducerPrunedScoreBatch left for the same inputs, or null. */
+inline void transducerPrunedScoreGradBatch(
+    const void* logitsDev,
+    const void* rangesDev,
+    const void* targetsDev,
+    const void* framesDev,
+    const void* targetLengthsDev,
+    int B,
+    int T,
+    int S,
+    int U,
+    int C,
+    int blank,
+    bool normalize,
+    const void* weightsDev,
+    void* gradDev,
+    const void* rowsDev = nullptr) {
+  if (!weightsDev || !gradDev) {
+    throw std::invalid_argument("transducerPrunedScoreGradBatch: null weights or gradient");
+  }
+  batched::transducerPrunedScoreGrad(static_cast<const float*>(logitsDev), static_cast<const int*>(rangesDev),
+                                     static_cast<const int*>(targetsDev), static_cast<const int*>(framesDev),
+                                     static_cast<const int*>(targetLengthsDev), B, T, S, U, C, blank, normalize,
+                                     static_cast<const float*>(weightsDev), static_cast<float*>(gradDev),
+                                     static_cast<const float*>(rowsDev));
+}
+
+/** The node occupancies `occDev` (device float32 [B][T][U + 1]) of the full lattice whose compact plane `rowsDev`
+ *  (device float32 [B][T][U + 1][3]) transducerScoreBatch or transducerAddScoreBatch left. */
+inline void transducerOccupancyBatch(
+    const void* rowsDev,
+    const void* framesDev,
+    const void* targetLengthsDev,
+    int B,
+    int T,
+    int U,
+    void* occDev) {
+  batched::transducerOccupancy(static_cast<const float*>(rowsDev), static_cast<const int*>(framesDev),
+                               static_cast<const int*>(targetLengthsDev), B, T, U, static_cast<float*>(occDev));
+}
+
 } // namespace criteria
 } // namespace gtn

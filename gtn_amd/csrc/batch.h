@@ -491,6 +491,30 @@ void batch_transducer_add_score_grad(const float* am_dev, const float* lm_dev, c
                                      int blank, const float* weights_dev, float* grad_am_dev, float* grad_lm_dev,
                                      const float* rows_dev);
 void batch_transducer_add_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
+// The PRUNED (banded) transducer score (DESIGN section 44 holds the contract): logits_dev float32 [B][T][S][C] holds, per
+// frame, the S lattice columns u = r_t .. r_t + S - 1 with r_t = ranges_dev[b][t] (int32 [B][T], read on the device); the
+// score is batch_transducer_score's on the full lattice with every node outside the band removed.  -inf, never NaN, in
+// that call's cases and where the band misses (0, 0) or (T_b - 1, U_b), two consecutive bands do not overlap, the ranges
+// decrease before T_b, or an r_t is outside 0 .. U.  rows_dev (or null): float32 [B][T][S][3].  Invalid argument before a
+// device is asked for: that call's refusals with S in place of U + 1 in the size limit, and S outside 1 .. min(64, U + 1).
+// Pooled scratch and slicing as batch_transducer_score, per band node.  Two launches per slice, no copy back, no wait.
+void batch_transducer_pruned_score(const float* logits_dev, const int* ranges_dev, const int* targets_dev,
+                                   const int* frames_dev, const int* target_lengths_dev, int B, int T, int S, int U,
+                                   int C, int blank, int normalize, float* scores_dev, float* rows_dev);
+// grad_dev [B][T][S][C] = weights_dev[b] * d score[b] / d logits[b]: every row stored exactly once, the never-read ones
+// (t >= T_b, u outside 0 .. U_b), dead rows and the rows of an utterance that scores -inf with zeros.  rows_dev (or
+// null): the plane batch_transducer_pruned_score left.  No floating-point atomics.
+void batch_transducer_pruned_score_grad(const float* logits_dev, const int* ranges_dev, const int* targets_dev,
+                                        const int* frames_dev, const int* target_lengths_dev, int B, int T, int S, int U,
+                                        int C, int blank, int normalize, const float* weights_dev, float* grad_dev,
+                                        const float* rows_dev);
+void batch_transducer_pruned_stats(int64_t* calls, int64_t* utterances);  // calls of the two above / their utterances
+// occ_dev float32 [B][T][U + 1] = exp(alpha + beta - score) of the full lattice whose compact plane rows_dev
+// [B][T][U + 1][3] batch_transducer_score or batch_transducer_add_score left (beta includes the node's outgoing arcs);
+// 0 outside t < T_b, u <= U_b and for an utterance that scores -inf; every element stored once.  8 bytes of pooled
+// scratch per node, sliced under the same cap.  Two launches per slice (the full sweep, the occupancy kernel).
+void batch_transducer_occupancy(const float* rows_dev, const int* frames_dev, const int* target_lengths_dev, int B,
+                                int T, int U, float* occ_dev);
 // The exact ASG log score of one device-resident acyclic token lattice per utterance (batch_ctc_lattice_score's form)
 // under the n emission slabs of a native linear batch and the [C + C * C] table of batch_asg_score, results on the device
 // (DESIGN section 37 holds the contract): scores_dev[b] = log sum over the lattice's paths p of exp(w(p) +

@@ -1820,6 +1820,143 @@ void batch_transducer_add_score_grad(const float* am_dev, const float* lm_dev, c
                       grad_am_dev, grad_lm_dev);
 }
 
+// ---- pruned (banded) transducer score over logits [B][T][S][C], its gradient, and the occupancy of a full lattice ----
+// (transducer_pruned.hip)
+namespace {
+Counters g_transducer_pruned;  // (calls, utterances)
+static_assert(kTransducerPrunedMaxS == 64, "the texts say 64");
+
+// both entry points, as transducer_impl: scores_dev for the score, weights_dev and grad_dev for the gradient
+void transducer_pruned_impl(const char* who, const float* x, const int* ranges, const int* targets, const int* frames,
+                            const int* tlen, int B, int T, int S, int U, int C, int blank, int normalize,
+                            float* scores_dev, float* rows_dev, const float* weights_dev, float* grad_dev) {
+  const bool want_grad = scores_dev == nullptr;
+  if (!x || !ranges || (!targets && U > 0) || !frames || !tlen)
+    refuse(who, "null input pointer (logits, ranges, targets, frames and target_lengths are all read)");
+  if (want_grad && (!weights_dev || !grad_dev)) refuse(who, "null weights or grad pointer");
+  if (B < 0) refuse(who, "negative B");
+  if (U < 0 || U + 1 > kTransducerMaxU1) refuse(who, "U + 1 outside 1 .. 1024");
+  if (S < 1 || S > kTransducerPrunedMaxS || S > U + 1) refuse(who, "S outside 1 .. min(64, U + 1)");
+  if (T < 1 || T > kTransducerMaxT) refuse(who, "T outside 1 .. 65535");
+  if (C < 1 || C > kTransducerMaxC) refuse(who, "C outside 1 .. 2^20");
+  if (blank < 0 || blank >= C) refuse(who, "blank is not one of the C labels");
+  const int64_t per_utt = int64_t(T) * S;  // band nodes
+  if (int64_t(B) * per_utt > std::numeric_limits<int>::max()) refuse(who, "B * T * S does not fit an int");
+  if (B == 0) return;
+  Runtime& rt = Runtime::get();
+  if (!ptr_device_memory_of(x, rt.device())) refuse(who, "the logits are not memory of the engine's current device");
+  check_outputs_local(who, {scores_dev, grad_dev, want_grad ? nullptr : rows_dev});
+  TransducerPrunedArgs a{};
+  a.x = x;
+  a.ranges = ranges;
+  a.targets = targets;
+  a.frames = frames;
+  a.tlen = tlen;
+  a.weights = weights_dev;
+  a.grad = grad_dev;
+  a.T = T;
+  a.S = S;
+  a.U1 = U + 1;
+  a.C = C;
+  a.blank = blank;
+  a.normalize = normalize ? 1 : 0;
+  DevMemP sc;  // (the gradient's scores: a slice's own, read by its gradient launch)
+  if (want_grad) sc = rt.alloc(sizeof(float) * size_t(B));
+  a.scores = want_grad ? sc->as<float>() : scores_dev;
+  // algorithmic bytes as transducer_impl's, per band node; the sweep also reads r_t once per lane and frame
+  const double row_in = normalize ? 4.0 * C : 8.0;
+  const int64_t own_rows = rows_dev ? 0 : 12;
+  const int64_t per_bytes = per_utt * (own_rows + (want_grad ? 8 : 0));
+  for_pair_slices(B, per_bytes, kTransducerScratch, [&](int64_t b0, int64_t cnt) {
+    const size_t nodes = size_t(per_utt) * size_t(cnt);
+    DevMemP work = rt.alloc(std::max<size_t>(size_t(per_bytes) * size_t(cnt), 16));
+    a.utt0 = int(b0);
+    a.count = int(cnt);
+    a.rows = rows_dev ? const_cast<float*>(rows_dev) + 3 * per_utt * b0 : work->as<float>();
+    a.alpha = want_grad ? work->as<float>(size_t(own_rows) * nodes) : nullptr;
+    a.beta = want_grad ? work->as<float>(size_t(own_rows + 4) * nodes) : nullptr;
+    if (!(want_grad && rows_dev)) {
+      GTNX_PROF("transducer_pruned_rows", double(nodes) * (row_in + 16.0));
+      launch_transducer_pruned_rows(a, rt.stream());
+    }
+    {
+      GTNX_PROF("transducer_pruned_sweep", double(nodes) * (want_grad ? 32.0 : 12.0) + 4.0 * double(cnt));
+      launch_transducer_pruned_sweep(a, rt.stream());
+    }
+    if (want_grad) {
+      GTNX_PROF("transducer_pruned_grad", double(nodes) * ((normalize ? 8.0 : 4.0) * C + 32.0));
+      launch_transducer_pruned_grad(a, rt.stream());
+    }
+  });
+  g_transducer_pruned.add(1, B);
+}
+}  // namespace
+
+void batch_transducer_pruned_stats(int64_t* calls, int64_t* utterances) {
+  g_transducer_pruned.get(calls, utterances);
+}
+
+void batch_transducer_pruned_score(const float* logits_dev, const int* ranges_dev, const int* targets_dev,
+                                   const int* frames_dev, const int* target_lengths_dev, int B, int T, int S, int U,
+                                   int C, int blank, int normalize, float* scores_dev, float* rows_dev) {
+  GTNX_HOST_T("batch.transducer_pruned_score");
+  if (!scores_dev) throw_invalid("[gtnx_batch_transducer_pruned_score] null scores pointer");
+  transducer_pruned_impl("gtnx_batch_transducer_pruned_score", logits_dev, ranges_dev, targets_dev, frames_dev,
+                         target_lengths_dev, B, T, S, U, C, blank, normalize, scores_dev, rows_dev, nullptr, nullptr);
+}
+
+void batch_transducer_pruned_score_grad(const float* logits_dev, const int* ranges_dev, const int* targets_dev,
+                                        const int* frames_dev, const int* target_lengths_dev, int B, int T, int S, int U,
+                                        int C, int blank, int normalize, const float* weights_dev, float* grad_dev,
+                                        const float* rows_dev) {
+  GTNX_HOST_T("batch.transducer_pruned_score_grad");
+  transducer_pruned_impl("gtnx_batch_transducer_pruned_score_grad", logits_dev, ranges_dev, targets_dev, frames_dev,
+                         target_lengths_dev, B, T, S, U, C, blank, normalize, nullptr, const_cast<float*>(rows_dev),
+                         weights_dev, grad_dev);
+}
+
+void batch_transducer_occupancy(const float* rows_dev, const int* frames_dev, const int* target_lengths_dev, int B,
+                                int T, int U, float* occ_dev) {
+  GTNX_HOST_T("batch.transducer_occupancy");
+  const char* who = "gtnx_batch_transducer_occupancy";
+  if (!rows_dev || !frames_dev || !target_lengths_dev) refuse(who, "null input pointer (rows, frames, target_lengths)");
+  if (!occ_dev) refuse(who, "null occupancy pointer");
+  if (B < 0) refuse(who, "negative B");
+  if (U < 0 || U + 1 > kTransducerMaxU1) refuse(who, "U + 1 outside 1 .. 1024");
+  if (T < 1 || T > kTransducerMaxT) refuse(who, "T outside 1 .. 65535");
+  const int64_t per_utt = int64_t(T) * (U + 1);
+  if (int64_t(B) * per_utt > std::numeric_limits<int>::max()) refuse(who, "B * T * (U + 1) does not fit an int");
+  if (B == 0) return;
+  Runtime& rt = Runtime::get();
+  if (!ptr_device_memory_of(rows_dev, rt.device())) refuse(who, "the rows are not memory of the engine's current device");
+  check_outputs_local(who, {occ_dev});
+  TransducerArgs a{};
+  a.frames = frames_dev;
+  a.tlen = target_lengths_dev;
+  a.T = T;
+  a.U1 = U + 1;
+  DevMemP sc = rt.alloc(sizeof(float) * size_t(B));
+  a.scores = sc->as<float>();
+  for_pair_slices(B, per_utt * 8, kTransducerScratch, [&](int64_t b0, int64_t cnt) {
+    const size_t nodes = size_t(per_utt) * size_t(cnt);
+    DevMemP work = rt.alloc(8 * nodes);
+    a.utt0 = int(b0);
+    a.count = int(cnt);
+    a.rows = const_cast<float*>(rows_dev) + 3 * per_utt * b0;  // (only read)
+    a.alpha = work->as<float>();
+    a.beta = work->as<float>(4 * nodes);
+    {
+      GTNX_PROF("transducer_sweep", double(nodes) * 24.0 + 4.0 * double(cnt));
+      launch_transducer_sweep(a, rt.stream());
+    }
+    GTNX_PROF("transducer_occupancy", double(nodes) * 12.0);
+    TransducerOccupancyArgs oa{};
+    oa.a = a;
+    oa.occ = occ_dev;
+    launch_transducer_occupancy(oa, rt.stream());
+  });
+}
+
 // ---- batched ASG score of one device-resident token lattice per utterance, and its gradients (asg_lattice.hip) ----
 namespace {
 Counters g_asg_lattice;  // (calls, utterances)

@@ -1247,6 +1247,43 @@ GTNX_API gtnx_status_t gtnx_batch_transducer_add_score_grad(const void* am_devic
 GTNX_API gtnx_status_t gtnx_batch_transducer_add_stats(int64_t* calls, int64_t* utterances) {
   return guard([&] { batch_transducer_add_stats(calls, utterances); });
 }
+GTNX_API gtnx_status_t gtnx_batch_transducer_pruned_score(const void* logits_device, const void* ranges_device,
+                                                          const void* targets_device, const void* frames_device,
+                                                          const void* target_lengths_device, int B, int T, int S, int U,
+                                                          int C, int blank, int normalize, void* scores_device,
+                                                          void* rows_device) {
+  return guard([&] {
+    batch_transducer_pruned_score(static_cast<const float*>(logits_device), static_cast<const int*>(ranges_device),
+                                  static_cast<const int*>(targets_device), static_cast<const int*>(frames_device),
+                                  static_cast<const int*>(target_lengths_device), B, T, S, U, C, blank, normalize,
+                                  static_cast<float*>(scores_device), static_cast<float*>(rows_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_transducer_pruned_score_grad(const void* logits_device, const void* ranges_device,
+                                                               const void* targets_device, const void* frames_device,
+                                                               const void* target_lengths_device, int B, int T, int S,
+                                                               int U, int C, int blank, int normalize,
+                                                               const void* weights_device, void* grad_device,
+                                                               const void* rows_device) {
+  return guard([&] {
+    batch_transducer_pruned_score_grad(static_cast<const float*>(logits_device), static_cast<const int*>(ranges_device),
+                                       static_cast<const int*>(targets_device), static_cast<const int*>(frames_device),
+                                       static_cast<const int*>(target_lengths_device), B, T, S, U, C, blank, normalize,
+                                       static_cast<const float*>(weights_device), static_cast<float*>(grad_device),
+                                       static_cast<const float*>(rows_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_transducer_pruned_stats(int64_t* calls, int64_t* utterances) {
+  return guard([&] { batch_transducer_pruned_stats(calls, utterances); });
+}
+GTNX_API gtnx_status_t gtnx_batch_transducer_occupancy(const void* rows_device, const void* frames_device,
+                                                       const void* target_lengths_device, int B, int T, int U,
+                                                       void* occ_device) {
+  return guard([&] {
+    batch_transducer_occupancy(static_cast<const float*>(rows_device), static_cast<const int*>(frames_device),
+                               static_cast<const int*>(target_lengths_device), B, T, U, static_cast<float*>(occ_device));
+  });
+}
 GTNX_API gtnx_status_t gtnx_batch_asg_lattice_score(gtnx_batch_t ems, const int* frames, const void* table_device,
                                                     const void* arcs_device, int64_t row_stride,
                                                     const void* num_arcs_device, const void* num_nodes_device,

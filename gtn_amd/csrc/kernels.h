@@ -1247,6 +1247,41 @@ struct TransducerAddArgs {
 void launch_transducer_add_max(const TransducerAddArgs& a, hipStream_t st);
 void launch_transducer_add_norm(const TransducerAddArgs& a, hipStream_t st);
 void launch_transducer_add_grad(const TransducerAddArgs& a, hipStream_t st);
+// transducer_pruned.hip: the same score on a band of S symbol positions per frame, over joint logits x [n][T][S][C] with
+// the band start r_t = ranges[b][t], and the gradient weights[b] * d score[b] / d x[b] (the contract: DESIGN section 44).
+// Band node (b, t, s) is lattice node (t, u = r_t + s); it is live when t < T_b, 0 <= r_t < U1 and u <= U_b.  Planes are
+// indexed by the band node's offset inside the slice, ((b - utt0) * T + t) * S + s.
+//   rows:   per live band node the compact triple of launch_transducer_rows at rows[3 * node].
+//   sweep:  a group of 8, 16, 32 or 64 lanes (the smallest that holds S) per utterance and direction: alpha (always;
+//           writes scores[b], -inf where the ranges decrease) and, with `beta` non-null, beta.  Both planes get every
+//           (t < T_b, s) of an utterance whose counts fit, -inf where the node is not live.  `alpha` null: the score only.
+//   grad:   every row of grad[b] for the slice's utterances, the never-read ones with zeros.
+//   occupancy: occ[b][t][u] = exp(alpha + beta - score) of a FULL lattice's planes as launch_transducer_sweep leaves
+//           them (TransducerArgs: frames, tlen, alpha, beta, scores, T, U1, utt0, count), 0 where the node is not live or
+//           the score is -inf; every element of the slice's utterances stored once.
+constexpr int kTransducerPrunedMaxS = 64;
+struct TransducerPrunedArgs {
+  const GTNX_G float* x;         // [n][T][S][C]
+  const GTNX_G int* ranges;      // [n][T]
+  const GTNX_G int* targets;     // [n][U1 - 1]
+  const GTNX_G int* frames;      // [n]
+  const GTNX_G int* tlen;        // [n]
+  GTNX_G float* rows;            // [count][T][S][3]
+  GTNX_G float* alpha;           // [count][T][S] or null
+  GTNX_G float* beta;            // [count][T][S] or null
+  GTNX_G float* scores;          // [n]
+  const GTNX_G float* weights;   // [n] (grad)
+  GTNX_G float* grad;            // [n][T][S][C] (grad)
+  int T, S, U1, C, blank, normalize, utt0, count;
+};
+void launch_transducer_pruned_rows(const TransducerPrunedArgs& a, hipStream_t st);
+void launch_transducer_pruned_sweep(const TransducerPrunedArgs& a, hipStream_t st);
+void launch_transducer_pruned_grad(const TransducerPrunedArgs& a, hipStream_t st);
+struct TransducerOccupancyArgs {
+  TransducerArgs a;              // (frames, tlen, alpha, beta, scores, T, U1, utt0, count)
+  GTNX_G float* occ;             // [n][T][U1]
+};
+void launch_transducer_occupancy(const TransducerOccupancyArgs& oa, hipStream_t st);
 // asg_lattice.hip: the ASG log score of the utterances utt0 .. utt0 + count - 1, each with one acyclic token lattice of its
 // own in device memory (ctc_lattice.hip's form), under asg_score.hip's [C + C * C] table, and the gradients g[b] * d
 // score[b] / d (emissions_b, table, arc weights of b) (the contract: DESIGN section 37).  The states are the arcs; an

@@ -53,6 +53,9 @@ _ARGTYPES = {
     "gtn_transducer_score_grad_n": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "gtn_transducer_add_score_n": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
     "gtn_transducer_add_score_grad_n": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "gtn_transducer_pruned_score_n": [_P] * 5 + [_I] * 7 + [_P, _P],
+    "gtn_transducer_pruned_score_grad_n": [_P] * 5 + [_I] * 7 + [_P, _P, _P],
+    "gtn_transducer_occupancy_n": [_P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_lattice_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_lattice_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "gtn_asg_lattice_align_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
@@ -1644,6 +1647,189 @@ def transducer_add_loss(am, lm, targets, input_lengths, target_lengths, blank=0,
         raise ValueError('transducer_add_loss: reduction must be "none", "sum" or "mean"')
     loss = -transducer_add_score(am, lm, targets, input_lengths, target_lengths, blank)
     return loss if reduction == "none" else (loss.sum() if reduction == "sum" else loss.mean())
+
+
+class _TransducerPrunedScore(torch.autograd.Function):
+    """_TransducerScore on the band: forward keeps the compact plane [B, T, S, 3] where the logits require grad; backward
+    is the one gradient call with grad_out as the weights."""
+
+    @staticmethod
+    def forward(ctx, logits, ranges, targets, frames, tlen, blank, normalize):
+        x = logits.detach().contiguous()
+        B, T, S, C_ = x.shape
+        U = targets.shape[1]
+        stream = _engine_stream(x.device)
+        scores = torch.empty(B, dtype=torch.float32, device=x.device)
+        rows = torch.empty(B, T, S, 3, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[0] else None
+        if B:
+            args = (x.data_ptr(), ranges.data_ptr(), targets.data_ptr() if targets.numel() else None, frames.data_ptr(),
+                    tlen.data_ptr())
+            if _has_native("transducer_pruned_score", "gtn_transducer_pruned_score_n"):
+                _call("gtn_transducer_pruned_score_n", *args, B, T, S, U, C_, blank, int(normalize), scores.data_ptr(),
+                      _ptr(rows))
+            else:
+                gtn.transducer_pruned_score(*args, scores.data_ptr(), _ptr(rows), blank, normalize, B=B, T=T, S=S, U=U,
+                                            C=C_)
+        _engine_done(stream)
+        ctx.save_for_backward(x, ranges, targets, frames, tlen, rows)
+        ctx.args = (blank, normalize)
+        return scores
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, ranges, targets, frames, tlen, rows = ctx.saved_tensors
+        blank, normalize = ctx.args
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        B, T, S, C_ = x.shape
+        U = targets.shape[1]
+        grad = torch.empty_like(x)
+        if B:
+            g = grad_out.detach().to(torch.float32).contiguous()
+            stream = _engine_stream(x.device)
+            args = (x.data_ptr(), ranges.data_ptr(), targets.data_ptr() if targets.numel() else None, frames.data_ptr(),
+                    tlen.data_ptr())
+            if _native():
+                _call("gtn_transducer_pruned_score_grad_n", *args, B, T, S, U, C_, blank, int(normalize), g.data_ptr(),
+                      grad.data_ptr(), _ptr(rows))
+            else:
+                gtn.transducer_pruned_score_grad(*args, g.data_ptr(), grad.data_ptr(), _ptr(rows), blank, normalize,
+                                                 B=B, T=T, S=S, U=U, C=C_)
+            _engine_done(stream)
+        return (grad,) + (None,) * 6
+
+
+def _transducer_index_args(who, named):
+    """the int32 copies of int32 / int64 index tensors of the given shapes (converted on the device)"""
+    out = []
+    for t, what, shape in named:
+        if not (torch.is_tensor(t) and t.dtype in (torch.int32, torch.int64) and tuple(t.shape) == shape):
+            raise ValueError(f"{who}: {what} must be an int32 or int64 tensor {list(shape)}")
+        out.append(t)
+    return out
+
+
+def transducer_pruned_score(logits, ranges, targets, input_lengths, target_lengths, blank=0, normalize=True):
+    """The pruned (banded) transducer log score of a padded batch, differentiable: the second pass of pruned RNN-T
+    training, where the joiner was evaluated on S symbol positions per frame only.  logits: float32 CUDA tensor
+    [B, T, S, C], band node (t, s) standing for lattice node (t, u = ranges[b, t] + s); ranges: int32 or int64 CUDA
+    tensor [B, T] (`transducer_prune_ranges` makes one); targets [B, U], input_lengths, target_lengths, blank and
+    normalize as transducer_score.  score[b] is transducer_score's on the full lattice with every node outside the band
+    removed.  1 <= S <= min(64, U + 1), U + 1 <= 1024, 1 <= T <= 65535, C <= 2^20, B * T * S < 2^31.  The ranges must not
+    decrease before T_b.  A score is -inf, with a zero gradient and never NaN, in transducer_score's cases and where the
+    band misses (0, 0) or (T_b - 1, U_b), two consecutive bands do not overlap (a step above S - 1), the ranges decrease,
+    or a range is outside 0 .. U.  Band rows with t >= T_b or u outside 0 .. U_b are never read and their gradient rows
+    are exactly 0.  Any grad_out; no atomics, the same bits run to run.  Runs on the caller's stream."""
+    who = "transducer_pruned_score"
+    x = logits
+    if not (torch.is_tensor(x) and x.dim() == 4 and x.dtype == torch.float32):
+        raise ValueError(f"{who}: logits must be a float32 tensor [B, T, S, C]")
+    B, T, S, C_ = x.shape
+    if not (torch.is_tensor(targets) and targets.dim() == 2):
+        raise ValueError(f"{who}: targets must be an int32 or int64 tensor [{B}, U]")
+    U = targets.shape[1]
+    idx = _transducer_index_args(who, ((ranges, "ranges", (B, T)), (targets, "targets", (B, U)),
+                                       (input_lengths, "input_lengths", (B,)), (target_lengths, "target_lengths", (B,))))
+    if U + 1 > 1024:
+        raise ValueError(f"{who}: U + 1 must be 1 .. 1024")
+    if not 1 <= S <= min(64, U + 1):
+        raise ValueError(f"{who}: S must be 1 .. min(64, U + 1)")
+    if not 1 <= T <= 65535:
+        raise ValueError(f"{who}: T must be 1 .. 65535")
+    if not 1 <= C_ <= 1 << 20:
+        raise ValueError(f"{who}: the number of labels must be 1 .. 2^20")
+    if B * T * S >= 1 << 31:
+        raise ValueError(f"{who}: B * T * S must be below 2^31")
+    if not 0 <= int(blank) < C_:
+        raise ValueError(f"{who}: blank must be one of the {C_} labels")
+    for t, what in zip([x] + idx, ("logits", "ranges", "targets", "input_lengths", "target_lengths")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {what} must be a CUDA tensor (the scores are computed on the device)")
+        if t.device != x.device:
+            raise ValueError(f"{who}: all tensors must be on one device")
+    rg, tg, fr, tl = (t.detach().to(torch.int32).contiguous() for t in idx)
+    return _TransducerPrunedScore.apply(x, rg, tg, fr, tl, int(blank), bool(normalize))
+
+
+def transducer_pruned_loss(logits, ranges, targets, input_lengths, target_lengths, blank=0, normalize=True,
+                           reduction="mean"):
+    """-transducer_pruned_score(...): float32 [B] with reduction "none", their sum with "sum", their mean over the batch
+    with "mean".  An utterance without a path in its band has loss +inf."""
+    if reduction not in ("none", "sum", "mean"):
+        raise ValueError('transducer_pruned_loss: reduction must be "none", "sum" or "mean"')
+    loss = -transducer_pruned_score(logits, ranges, targets, input_lengths, target_lengths, blank, normalize)
+    return loss if reduction == "none" else (loss.sum() if reduction == "sum" else loss.mean())
+
+
+def transducer_occupancy(rows, input_lengths, target_lengths):
+    """The occupancy of every node of a full transducer lattice, occ[b, t, u] = exp(alpha + beta - score) (beta with the
+    node's outgoing arcs), float32 [B, T, U + 1], from the compact plane `rows` (float32 CUDA tensor [B, T, U + 1, 3])
+    that gtn_amd.transducer_score or gtn_amd.transducer_add_score left in `rows_out`.  0 outside t < T_b, u <= U_b and for
+    an utterance that scores -inf.  Not differentiable: it chooses the pruning bounds (`transducer_prune_ranges`).  Runs
+    on the caller's stream."""
+    who = "transducer_occupancy"
+    if not (torch.is_tensor(rows) and rows.dim() == 4 and rows.dtype == torch.float32 and rows.shape[3] == 3
+            and rows.shape[2] >= 1):
+        raise ValueError(f"{who}: rows must be a float32 tensor [B, T, U + 1, 3]")
+    B, T, U1, _ = rows.shape
+    idx = _transducer_index_args(who, ((input_lengths, "input_lengths", (B,)), (target_lengths, "target_lengths", (B,))))
+    if U1 > 1024 or not 1 <= T <= 65535 or B * T * U1 >= 1 << 31:
+        raise ValueError(f"{who}: U + 1 <= 1024, 1 <= T <= 65535 and B * T * (U + 1) < 2^31 are required")
+    for t, what in zip([rows] + idx, ("rows", "input_lengths", "target_lengths")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {what} must be a CUDA tensor")
+        if t.device != rows.device:
+            raise ValueError(f"{who}: all tensors must be on one device")
+    r = rows.detach().contiguous()
+    fr, tl = (t.detach().to(torch.int32).contiguous() for t in idx)
+    occ = torch.empty(B, T, U1, dtype=torch.float32, device=r.device)
+    if B:
+        stream = _engine_stream(r.device)
+        if _has_native("transducer_occupancy", "gtn_transducer_occupancy_n"):
+            _call("gtn_transducer_occupancy_n", r.data_ptr(), fr.data_ptr(), tl.data_ptr(), B, T, U1 - 1, occ.data_ptr())
+        else:
+            gtn.transducer_occupancy(r.data_ptr(), fr.data_ptr(), tl.data_ptr(), occ.data_ptr(), B=B, T=T, U=U1 - 1)
+        _engine_done(stream)
+    return occ
+
+
+def transducer_prune_ranges(occ, input_lengths, target_lengths, S):
+    """The band starts int32 [B, T] for `transducer_pruned_score` from node occupancies occ [B, T, U + 1]
+    (`transducer_occupancy`), in plain torch on occ's device (off the hot path: B T (U + 1) floats).  With
+    E = max(0, U_b + 1 - S): per frame a_t is the smallest start in 0 .. E whose window sum_{k < S} occ[t, a + k] is
+    largest; it is clamped to [lo_t, hi_t], hi_t = min(E, t (S - 1)), lo_t = min(hi_t, max(0, E - (T_b - 1 - t)(S - 1)));
+    m_t is the running minimum of the clamped starts from frame T_b - 1 backwards; then r_0 = 0 and
+    r_{t+1} = min(m_{t+1}, r_t + S - 1).  Frames t >= T_b repeat r_{T_b - 1}.  The result is non-decreasing, steps by at
+    most S - 1, starts at 0 and ends at E whenever E <= (T_b - 1)(S - 1) -- what the banded lattice needs to hold the
+    start and the end and to stay connected."""
+    who = "transducer_prune_ranges"
+    if not (torch.is_tensor(occ) and occ.dim() == 3 and occ.is_floating_point()):
+        raise ValueError(f"{who}: occ must be a floating-point tensor [B, T, U + 1]")
+    B, T, U1 = occ.shape
+    S = int(S)
+    if not 1 <= S <= U1:
+        raise ValueError(f"{who}: S must be 1 .. U + 1")
+    fr, tl = _transducer_index_args(who, ((input_lengths, "input_lengths", (B,)),
+                                          (target_lengths, "target_lengths", (B,))))
+    dev = occ.device
+    Tb = fr.to(dev).long().clamp(1, T)[:, None]
+    E = (tl.to(dev).long().clamp(0, U1 - 1)[:, None] + 1 - S).clamp(min=0)
+    t = torch.arange(T, device=dev)[None, :]
+    win = occ.detach().unfold(2, S, 1).sum(dim=3)                       # [B, T, U + 2 - S]
+    starts = torch.arange(win.shape[2], device=dev)[None, None, :]
+    win = win.masked_fill(starts > E[:, :, None], float("-inf"))
+    best = win.max(dim=2, keepdim=True).values
+    a = torch.where(win == best, starts, win.shape[2]).amin(dim=2)    # the smallest start among the largest windows
+    hi = torch.minimum(E, t * (S - 1))
+    lo = torch.minimum(hi, (E - (Tb - 1 - t) * (S - 1)).clamp(min=0))
+    a = torch.minimum(torch.maximum(a, lo), hi)
+    a = torch.where(t < Tb, a, E)                                     # (frames past the end do not bind the minimum)
+    m = torch.flip(torch.cummin(torch.flip(a, [1]), dim=1).values, [1])
+    # r_{t+1} = min(m_{t+1}, r_t + S - 1), r_0 = 0  <=>  r_t = min over j <= t of (m'_j + (t - j)(S - 1)), m'_0 = 0
+    m = torch.cat([torch.zeros_like(m[:, :1]), m[:, 1:]], dim=1)
+    r = torch.cummin(m - t * (S - 1), dim=1).values + t * (S - 1)
+    last = torch.gather(r, 1, Tb - 1)
+    return torch.where(t < Tb, r, last).to(torch.int32)
 
 
 class _ASGLatticeScore(torch.autograd.Function):

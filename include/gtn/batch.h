@@ -443,6 +443,36 @@ inline void transducerAddScoreGrad(const float* amDevice, const float* lmDevice,
                                                      targetLengthsDevice, B, T, U, C, blank, weightsDevice,
                                                      gradAmDevice, gradLmDevice, rowsDevice));
 }
+/** The pruned (banded) transducer score: logitsDevice float32 [B][T][S][C] holds per frame the lattice columns
+ *  r_t .. r_t + S - 1, r_t = rangesDevice[b][t] (int32 [B][T], non-decreasing, steps of at most S - 1); the score is
+ *  transducerScore's on the full lattice with every node outside the band removed.  -inf, never NaN, where the band
+ *  misses the start or the end, two bands do not overlap, the ranges decrease or leave 0 .. U.  rowsDevice (or null):
+ *  float32 [B][T][S][3].  S <= min(64, U + 1), B * T * S < 2^31 -- gtnx_batch_transducer_pruned_score */
+inline void transducerPrunedScore(const float* logitsDevice, const int* rangesDevice, const int* targetsDevice,
+                                  const int* framesDevice, const int* targetLengthsDevice, int B, int T, int S, int U,
+                                  int C, int blank, bool normalize, float* scoresDevice, float* rowsDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_pruned_score(logitsDevice, rangesDevice, targetsDevice, framesDevice,
+                                                   targetLengthsDevice, B, T, S, U, C, blank, normalize ? 1 : 0,
+                                                   scoresDevice, rowsDevice));
+}
+/** Its gradient under weightsDevice [B]: gradDevice float32 [B][T][S][C], every row stored exactly once (the never-read
+ *  ones with zeros); rowsDevice (or null): the plane transducerPrunedScore left.  Bit-repeatable, sliced or not (no
+ *  atomics) -- gtnx_batch_transducer_pruned_score_grad */
+inline void transducerPrunedScoreGrad(const float* logitsDevice, const int* rangesDevice, const int* targetsDevice,
+                                      const int* framesDevice, const int* targetLengthsDevice, int B, int T, int S,
+                                      int U, int C, int blank, bool normalize, const float* weightsDevice,
+                                      float* gradDevice, const float* rowsDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_pruned_score_grad(logitsDevice, rangesDevice, targetsDevice, framesDevice,
+                                                        targetLengthsDevice, B, T, S, U, C, blank, normalize ? 1 : 0,
+                                                        weightsDevice, gradDevice, rowsDevice));
+}
+/** occDevice float32 [B][T][U + 1] = exp(alpha + beta - score) of the full lattice whose compact plane rowsDevice
+ *  [B][T][U + 1][3] transducerScore or transducerAddScore left; 0 past the lengths and for an utterance that scores
+ *  -inf -- gtnx_batch_transducer_occupancy */
+inline void transducerOccupancy(const float* rowsDevice, const int* framesDevice, const int* targetLengthsDevice, int B,
+                                int T, int U, float* occDevice) {
+  detail::check(gtnx_batch_transducer_occupancy(rowsDevice, framesDevice, targetLengthsDevice, B, T, U, occDevice));
+}
 /** The exact ASG log score of one device-resident acyclic token lattice per utterance (ctcLatticeScore's lattices) under
  *  the slabs of a Batch::linear and asgScore's table, results left on the device: scoresDevice[b] = log sum over the
  *  lattice's paths p of exp(w(p) + asgScore(emissions_b[0 .. T_b), table, labels(p))), nothing subtracted.  The states

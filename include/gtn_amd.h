@@ -896,6 +896,46 @@ gtnx_status_t gtnx_batch_transducer_add_score_grad(const void* am_device, const 
                                                    void* grad_lm_device, const void* rows_device);
 /* calls of either kind that have launched so far (process-wide) / utterances they took */
 gtnx_status_t gtnx_batch_transducer_add_stats(int64_t* calls, int64_t* utterances);
+/* The PRUNED (banded) transducer log score: the joiner was evaluated on S symbol positions per frame,
+ *   logits_device float32 [B][T][S][C], band node (t, s) standing for lattice node (t, u = r_t + s),
+ *   ranges_device  int32   [B][T], r_t, read on the device,
+ * and scores[b] is gtnx_batch_transducer_score's on the full T_b x (U_b+1) lattice with every node outside the band
+ * removed: node (t,u) exists iff t < T_b, r_t <= u < r_t + S and 0 <= u <= U_b; an arc exists iff both its ends do; the
+ * start is (0,0), the end the blank arc out of (T_b-1, U_b).  targets_device int32 [B][U], frames_device and
+ * target_lengths_device int32 [B], blank, normalize, rows_device (float32 [B][T][S][3] or null) as that call's.  Band
+ * rows with t >= T_b or u outside 0 .. U_b are never read.  -inf, never NaN: that call's cases; the band does not hold
+ * (0,0) or (T_b-1, U_b); two consecutive bands do not overlap (r_{t+1} > r_t + S - 1); r_{t+1} < r_t for some
+ * t+1 < T_b (NON-DECREASING RANGES ARE REQUIRED; the wave that walks the utterance detects it); an r_t outside 0 .. U
+ * (such a frame has no node; r_t never becomes an address).  GTNX_INVALID_ARGUMENT before a device is asked for: a null
+ * pointer, a negative B, U+1 outside 1 .. 1024, S outside 1 .. min(64, U+1), T outside 1 .. 65535, C outside 1 .. 2^20,
+ * blank outside 0 .. C-1, B*T*S >= 2^31.  B == 0 returns without touching a device.  Launches per slice
+ * (transducer_pruned.hip: rows, sweep); pooled scratch 12 bytes per band node (none with rows_device), sliced under
+ * GTNX_TRANSDUCER_SCRATCH_BYTES' cap.  The same bits run to run, sliced or not, whatever an utterance's neighbours are,
+ * with or without rows_device. */
+gtnx_status_t gtnx_batch_transducer_pruned_score(const void* logits_device, const void* ranges_device,
+                                                 const void* targets_device, const void* frames_device,
+                                                 const void* target_lengths_device, int B, int T, int S, int U, int C,
+                                                 int blank, int normalize, void* scores_device, void* rows_device);
+/* Its gradient under weights_device (float32 [B]): grad_device float32 [B][T][S][C], gtnx_batch_transducer_score_grad's
+ * formula per band node with the band's neighbours beta[t, s+1] and beta[t+1, s - (r_{t+1} - r_t)].  EVERY row is
+ * stored exactly once (no memset): rows t >= T_b, rows whose u is outside 0 .. U_b, dead rows, nodes nothing passes
+ * through and every row of an utterance that scores -inf as zeros.  rows_device (or null): the plane the score call
+ * left for the SAME inputs.  Pooled scratch 20 bytes per band node (8 with rows_device).  No floating-point atomics. */
+gtnx_status_t gtnx_batch_transducer_pruned_score_grad(const void* logits_device, const void* ranges_device,
+                                                      const void* targets_device, const void* frames_device,
+                                                      const void* target_lengths_device, int B, int T, int S, int U,
+                                                      int C, int blank, int normalize, const void* weights_device,
+                                                      void* grad_device, const void* rows_device);
+/* calls of either kind that have launched so far (process-wide) / utterances they took */
+gtnx_status_t gtnx_batch_transducer_pruned_stats(int64_t* calls, int64_t* utterances);
+/* The occupancy of every node of a FULL lattice, from the compact plane rows_device float32 [B][T][U+1][3] that
+ * gtnx_batch_transducer_score or gtnx_batch_transducer_add_score left:
+ *   occ_device float32 [B][T][U+1] = exp(alpha[t,u] + beta[t,u] - scores[b]),  beta including the node's outgoing arcs,
+ * 0 outside t < T_b, u <= U_b and for an utterance that scores -inf; every element stored once.  The pruning bounds of
+ * the banded call are chosen from it (torch_loss.transducer_prune_ranges).  The same refusals about B, T and U.  Pooled
+ * scratch 8 bytes per node, sliced as above; launches per slice: transducer.hip's sweep, the occupancy kernel. */
+gtnx_status_t gtnx_batch_transducer_occupancy(const void* rows_device, const void* frames_device,
+                                              const void* target_lengths_device, int B, int T, int U, void* occ_device);
 /* The exact ASG log score of ONE ACYCLIC TOKEN LATTICE PER UTTERANCE -- gtnx_batch_ctc_lattice_score's lattices under
  * gtnx_batch_asg_score's criterion:
  *   scores[b] = log sum over the lattice's paths p of exp(w(p) + asg_score(emissions_b[0 .. T_b), table, labels(p))),
