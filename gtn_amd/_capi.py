@@ -199,6 +199,11 @@ _SIGS = {
     "gtnx_batch_transducer_pruned_score": [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p, C.c_void_p],
     "gtnx_batch_transducer_pruned_score_grad": [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_void_p],
     "gtnx_batch_transducer_pruned_stats": [c_i64_p, c_i64_p],
+    "gtnx_batch_transducer_score16": [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 2,
+    "gtnx_batch_transducer_score_grad16": [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 3,
+    "gtnx_batch_transducer_pruned_score16": [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p] * 2,
+    "gtnx_batch_transducer_pruned_score_grad16": [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 7
+                                                 + [C.c_void_p] * 3,
     "gtnx_batch_transducer_occupancy": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "gtnx_batch_asg_lattice_score": [c_graph, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],

@@ -1907,23 +1907,38 @@ def make_api(lib):
                                            int(ref_stride), _opt_ptr(ref_lengths), b, n, l, u, _opt_ptr(dist_out),
                                            _opt_ptr(ops_out)))
 
+    _TRANSDUCER_DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2}  # (0: the float32 entry; else gtn_amd.h's code)
+
     def debug_transducer_stats():
         """(calls, utterances): calls of transducer_score / transducer_score_grad that have launched so far and the
         utterances they took (include/gtn_amd.h: gtnx_batch_transducer_stats)"""
         return _stats2(lib.gtnx_batch_transducer_stats)
 
-    def _transducer_args(who, logits, targets, frames, target_lengths, blank, dims, outs):
-        """(B, T, U, C) of a transducer call: from `logits` [B, T, U + 1, C] when it is a tensor, else from `dims`
-        (a device address says nothing); the tensors among the arguments are checked against them.  `outs`: (tensor or
-        address or None, dtype, count function, text) of the other arguments."""
+    def _transducer_dtype(who, logits, dtype):
+        """the logits' element type as a name, from the tensor or, for a device address, from `dtype` (a torch dtype or
+        a name; None: float32).  None where it is none of float32, float16 and bfloat16."""
+        name = str(logits.dtype if hasattr(logits, "data_ptr") else (dtype or "float32")).replace("torch.", "")
+        if hasattr(logits, "data_ptr") and dtype is not None and str(dtype).replace("torch.", "") != name:
+            raise ValueError(f"{who}: dtype = {dtype} is not what logits says ({name})")
+        return name if name in _TRANSDUCER_DTYPES else None
+
+    def _transducer_args(who, logits, targets, frames, target_lengths, blank, dims, outs, dtype=None):
+        """(B, T, U, C, code) of a transducer call: the sizes from `logits` [B, T, U + 1, C] when it is a tensor, else
+        from `dims` (a device address says nothing); code 0 for float32 logits, else the 16-bit entry's dtype code.  The
+        tensors among the arguments are checked against them.  `outs`: (tensor or address or None, count function,
+        text[, True: of the logits' dtype]) of the other arguments, float32 unless marked."""
+        name = _transducer_dtype(who, logits, dtype)
         if hasattr(logits, "data_ptr"):
-            if str(logits.dtype) != "torch.float32" or logits.dim() != 4 or not logits.is_contiguous():
-                raise ValueError(f"{who}: logits must be a float32 contiguous tensor [B, T, U + 1, C]")
+            if name is None or logits.dim() != 4 or not logits.is_contiguous():
+                raise ValueError(f"{who}: logits must be a float32 contiguous tensor [B, T, U + 1, C]"
+                                 " (or a bfloat16 / float16 one)")
             shape = (logits.shape[0], logits.shape[1], logits.shape[2] - 1, logits.shape[3])
-            for name, have, want in zip("BTUC", dims, shape):
+            for dim, have, want in zip("BTUC", dims, shape):
                 if have is not None and int(have) != want:
-                    raise ValueError(f"{who}: {name} = {have} is not what logits says ({want})")
+                    raise ValueError(f"{who}: {dim} = {have} is not what logits says ({want})")
             dims = shape
+        elif name is None:
+            raise ValueError(f"{who}: dtype must be float32, float16 or bfloat16")
         if any(d is None for d in dims):
             raise ValueError(f"{who}: a device address needs B, T, U and C")
         b, t, u, c = (int(d) for d in dims)
@@ -1933,13 +1948,16 @@ def make_api(lib):
                   (targets, "torch.int32", b * u, "targets must be an int32 contiguous tensor [B, U]"),
                   (frames, "torch.int32", b, "frames must be an int32 contiguous tensor [B]"),
                   (target_lengths, "torch.int32", b, "target_lengths must be an int32 contiguous tensor [B]")]
-        for o, dtype, count, what in checks + [(o, "torch.float32", n(b, t, u, c), w) for o, n, w in outs]:
+        for o, n, w, *like in outs:
+            of = "torch." + name if like and name != "float32" else "torch.float32"
+            checks.append((o, of, n(b, t, u, c), w + (f" (the logits are {name}: of that dtype)" if like else "")))
+        for o, dtype, count, what in checks:
             if o is not None and hasattr(o, "data_ptr"):
                 if count is not None and (str(o.dtype) != dtype or not o.is_contiguous() or o.numel() != count):
                     raise ValueError(f"{who}: {what}")
                 if hasattr(o, "is_cuda") and not o.is_cuda:  # (a host tensor's address means nothing to the kernel)
                     raise ValueError(f"{who}: {what.split()[0]} must be a CUDA tensor")
-        return b, t, u, c
+        return b, t, u, c, _TRANSDUCER_DTYPES[name]
 
     def _transducer_targets(targets, b, u):
         """the targets' address; an empty [B, 0] tensor has none and is never read"""
@@ -1948,7 +1966,7 @@ def make_api(lib):
         return _opt_ptr(targets)
 
     def transducer_score(logits, targets, frames, target_lengths, scores_out, rows_out=None, blank=0, normalize=True,
-                         B=None, T=None, U=None, C=None):
+                         B=None, T=None, U=None, C=None, dtype=None):
         """The transducer (RNN-T) log score of every utterance over device-resident joint logits, left on the device
         (gtnx_batch_transducer_score; DESIGN section 42 holds the contract).  `logits`: float32 CUDA tensor [B, T, U + 1,
         C], contiguous, or a device address with B, T, U and C; `targets`: int32 [B, U]; `frames`, `target_lengths`:
@@ -1956,40 +1974,47 @@ def make_api(lib):
         kernel takes the log-softmax of every live row), the path score of the rows as they are without.  -inf, never
         NaN: T_b == 0 or beyond T, U_b beyond U, a token outside 0 .. C - 1 or equal to `blank`, no finite path.
         `rows_out` (float32 [B, T, U + 1, 3] or None) keeps (lp_blank, lp_label, lse) of every live node for
-        `transducer_score_grad`.  U + 1 <= 1024, T <= 65535, C <= 2^20, B * T * (U + 1) < 2^31.  No copy back, no wait."""
+        `transducer_score_grad`.  U + 1 <= 1024, T <= 65535, C <= 2^20, B * T * (U + 1) < 2^31.  No copy back, no wait.
+        A bfloat16 or float16 `logits` tensor is read as it is (gtnx_batch_transducer_score16):
+        exact conversion, float32 arithmetic, float32 `scores_out` and `rows_out`; with a device address, say
+        `dtype="bfloat16"` or `"float16"`."""
         who = "transducer_score"
-        b, t, u, c = _transducer_args(
+        b, t, u, c, code = _transducer_args(
             who, logits, targets, frames, target_lengths, blank, (B, T, U, C),
             [(scores_out, lambda b, t, u, c: b, "scores_out must be a float32 contiguous tensor [B]"),
              (rows_out, lambda b, t, u, c: 3 * b * t * (u + 1),
-              "rows_out must be a float32 contiguous tensor [B, T, U + 1, 3]")])
+              "rows_out must be a float32 contiguous tensor [B, T, U + 1, 3]")], dtype)
         if b == 0 and hasattr(logits, "data_ptr"):
             return  # (no utterance, nothing to launch -- and an empty tensor has no address to hand to the engine)
-        check(lib.gtnx_batch_transducer_score(_opt_ptr(logits), _transducer_targets(targets, b, u), _opt_ptr(frames),
-                                              _opt_ptr(target_lengths), b, t, u, c, int(blank), int(bool(normalize)),
-                                              _opt_ptr(scores_out), _opt_ptr(rows_out)))
+        head = (_opt_ptr(logits),) + ((code,) if code else ())
+        check((lib.gtnx_batch_transducer_score16 if code else lib.gtnx_batch_transducer_score)(
+            *head, _transducer_targets(targets, b, u), _opt_ptr(frames), _opt_ptr(target_lengths), b, t, u, c,
+            int(blank), int(bool(normalize)), _opt_ptr(scores_out), _opt_ptr(rows_out)))
 
     def transducer_score_grad(logits, targets, frames, target_lengths, weights, grad_out, rows=None, blank=0,
-                              normalize=True, B=None, T=None, U=None, C=None):
+                              normalize=True, B=None, T=None, U=None, C=None, dtype=None):
         """The gradient of the scores of `transducer_score` under `weights` (float32 [B] on the device), in one
         stateless call (gtnx_batch_transducer_score_grad): `grad_out` (float32 [B, T, U + 1, C]) = weights[b] * d
         score[b] / d logits[b], every row stored exactly once -- the rows that are never read (t >= T_b, u > U_b), those
         of an utterance that scores -inf and dead rows with zeros.  `rows`: the plane `transducer_score` left in
         `rows_out` for the same inputs, or None (then it is recomputed: one more pass over the logits).  Pooled scratch,
-        sliced beyond 256 MiB with the same bits; no atomics, the same bits run to run."""
+        sliced beyond 256 MiB with the same bits; no atomics, the same bits run to run.  Bfloat16 or float16 `logits`
+        (`dtype=` with a device address): `grad_out` has their dtype, formed in float32 and rounded once to nearest even,
+        the zero rows as +0 bits (gtnx_batch_transducer_score_grad16); `weights` and `rows` stay float32."""
         who = "transducer_score_grad"
-        b, t, u, c = _transducer_args(
+        b, t, u, c, code = _transducer_args(
             who, logits, targets, frames, target_lengths, blank, (B, T, U, C),
             [(weights, lambda b, t, u, c: b, "weights must be a float32 contiguous tensor [B]"),
              (grad_out, lambda b, t, u, c: b * t * (u + 1) * c,
-              "grad_out must be a float32 contiguous tensor [B, T, U + 1, C]"),
-             (rows, lambda b, t, u, c: 3 * b * t * (u + 1), "rows must be a float32 contiguous tensor [B, T, U + 1, 3]")])
+              "grad_out must be a float32 contiguous tensor [B, T, U + 1, C]", True),
+             (rows, lambda b, t, u, c: 3 * b * t * (u + 1), "rows must be a float32 contiguous tensor [B, T, U + 1, 3]")],
+            dtype)
         if b == 0 and hasattr(logits, "data_ptr"):
             return
-        check(lib.gtnx_batch_transducer_score_grad(_opt_ptr(logits), _transducer_targets(targets, b, u),
-                                                   _opt_ptr(frames), _opt_ptr(target_lengths), b, t, u, c, int(blank),
-                                                   int(bool(normalize)), _opt_ptr(weights), _opt_ptr(grad_out),
-                                                   _opt_ptr(rows)))
+        head = (_opt_ptr(logits),) + ((code,) if code else ())
+        check((lib.gtnx_batch_transducer_score_grad16 if code else lib.gtnx_batch_transducer_score_grad)(
+            *head, _transducer_targets(targets, b, u), _opt_ptr(frames), _opt_ptr(target_lengths), b, t, u, c,
+            int(blank), int(bool(normalize)), _opt_ptr(weights), _opt_ptr(grad_out), _opt_ptr(rows)))
 
     def debug_transducer_add_stats():
         """(calls, utterances): calls of transducer_add_score / transducer_add_score_grad that have launched so far and
@@ -2078,18 +2103,22 @@ def make_api(lib):
         and the utterances they took (include/gtn_amd.h: gtnx_batch_transducer_pruned_stats)"""
         return _stats2(lib.gtnx_batch_transducer_pruned_stats)
 
-    def _transducer_pruned_args(who, logits, ranges, targets, frames, target_lengths, blank, dims, outs):
-        """(B, T, S, U, C) of a pruned transducer call: B, T, S, C from `logits` [B, T, S, C] and U from `targets`
-        [B, U] when they are tensors, else from `dims`; the tensors among the arguments are checked against them.
-        `outs`: (tensor or address or None, count function, text) of the float32 arguments."""
+    def _transducer_pruned_args(who, logits, ranges, targets, frames, target_lengths, blank, dims, outs, dtype=None):
+        """(B, T, S, U, C, code) of a pruned transducer call: B, T, S, C from `logits` [B, T, S, C] and U from `targets`
+        [B, U] when they are tensors, else from `dims`; code and `outs` as _transducer_args'.  The tensors among the
+        arguments are checked against them."""
         dims = list(dims)
+        name = _transducer_dtype(who, logits, dtype)
+        if name is None and not hasattr(logits, "data_ptr"):
+            raise ValueError(f"{who}: dtype must be float32, float16 or bfloat16")
         if hasattr(logits, "data_ptr"):
-            if str(logits.dtype) != "torch.float32" or logits.dim() != 4 or not logits.is_contiguous():
-                raise ValueError(f"{who}: logits must be a float32 contiguous tensor [B, T, S, C]")
-            for i, name, want in ((0, "B", logits.shape[0]), (1, "T", logits.shape[1]), (2, "S", logits.shape[2]),
-                                  (4, "C", logits.shape[3])):
+            if name is None or logits.dim() != 4 or not logits.is_contiguous():
+                raise ValueError(f"{who}: logits must be a float32 contiguous tensor [B, T, S, C]"
+                                 " (or a bfloat16 / float16 one)")
+            for i, dim, want in ((0, "B", logits.shape[0]), (1, "T", logits.shape[1]), (2, "S", logits.shape[2]),
+                                 (4, "C", logits.shape[3])):
                 if dims[i] is not None and int(dims[i]) != want:
-                    raise ValueError(f"{who}: {name} = {dims[i]} is not what logits says ({want})")
+                    raise ValueError(f"{who}: {dim} = {dims[i]} is not what logits says ({want})")
                 dims[i] = want
         if dims[3] is None and hasattr(targets, "data_ptr") and targets.dim() == 2:
             dims[3] = targets.shape[1]
@@ -2103,16 +2132,19 @@ def make_api(lib):
                   (targets, "torch.int32", b * u, "targets must be an int32 contiguous tensor [B, U]"),
                   (frames, "torch.int32", b, "frames must be an int32 contiguous tensor [B]"),
                   (target_lengths, "torch.int32", b, "target_lengths must be an int32 contiguous tensor [B]")]
-        for o, dtype, count, what in checks + [(o, "torch.float32", n(b, t, s, c), w) for o, n, w in outs]:
+        for o, n, w, *like in outs:
+            of = "torch." + name if like and name != "float32" else "torch.float32"
+            checks.append((o, of, n(b, t, s, c), w + (f" (the logits are {name}: of that dtype)" if like else "")))
+        for o, dtype, count, what in checks:
             if o is not None and hasattr(o, "data_ptr"):
                 if count is not None and (str(o.dtype) != dtype or not o.is_contiguous() or o.numel() != count):
                     raise ValueError(f"{who}: {what}")
                 if hasattr(o, "is_cuda") and not o.is_cuda:  # (a host tensor's address means nothing to the kernel)
                     raise ValueError(f"{who}: {what.split()[0]} must be a CUDA tensor")
-        return b, t, s, u, c
+        return b, t, s, u, c, _TRANSDUCER_DTYPES[name]
 
     def transducer_pruned_score(logits, ranges, targets, frames, target_lengths, scores_out, rows_out=None, blank=0,
-                                normalize=True, B=None, T=None, S=None, U=None, C=None):
+                                normalize=True, B=None, T=None, S=None, U=None, C=None, dtype=None):
         """The pruned (banded) transducer log score of every utterance, left on the device
         (gtnx_batch_transducer_pruned_score; DESIGN section 44 holds the contract).  `logits`: float32 CUDA tensor
         [B, T, S, C], contiguous, or a device address with B, T, S, U and C: the joiner's output on the lattice columns
@@ -2121,38 +2153,44 @@ def make_api(lib):
         `transducer_score`.  The score is that call's on the full lattice with every node outside the band removed; -inf,
         never NaN, also where the band misses (0, 0) or (T_b - 1, U_b), two bands do not overlap, the ranges decrease or
         a range is outside 0 .. U.  `rows_out` (float32 [B, T, S, 3] or None) keeps the compact plane for
-        `transducer_pruned_score_grad`.  S <= min(64, U + 1), U + 1 <= 1024, B * T * S < 2^31.  No copy back, no wait."""
+        `transducer_pruned_score_grad`.  S <= min(64, U + 1), U + 1 <= 1024, B * T * S < 2^31.  No copy back, no wait.
+        Bfloat16 or float16 `logits` (`dtype=` with a device address) are read as they are, as `transducer_score` reads
+        them (gtnx_batch_transducer_pruned_score16)."""
         who = "transducer_pruned_score"
-        b, t, s, u, c = _transducer_pruned_args(
+        b, t, s, u, c, code = _transducer_pruned_args(
             who, logits, ranges, targets, frames, target_lengths, blank, (B, T, S, U, C),
             [(scores_out, lambda b, t, s, c: b, "scores_out must be a float32 contiguous tensor [B]"),
-             (rows_out, lambda b, t, s, c: 3 * b * t * s, "rows_out must be a float32 contiguous tensor [B, T, S, 3]")])
+             (rows_out, lambda b, t, s, c: 3 * b * t * s, "rows_out must be a float32 contiguous tensor [B, T, S, 3]")],
+            dtype)
         if b == 0 and hasattr(logits, "data_ptr"):
             return  # (no utterance, nothing to launch -- and an empty tensor has no address to hand to the engine)
-        check(lib.gtnx_batch_transducer_pruned_score(
-            _opt_ptr(logits), _opt_ptr(ranges), _transducer_targets(targets, b, u), _opt_ptr(frames),
-            _opt_ptr(target_lengths), b, t, s, u, c, int(blank), int(bool(normalize)), _opt_ptr(scores_out),
-            _opt_ptr(rows_out)))
+        head = (_opt_ptr(logits),) + ((code,) if code else ())
+        check((lib.gtnx_batch_transducer_pruned_score16 if code else lib.gtnx_batch_transducer_pruned_score)(
+            *head, _opt_ptr(ranges), _transducer_targets(targets, b, u), _opt_ptr(frames), _opt_ptr(target_lengths), b,
+            t, s, u, c, int(blank), int(bool(normalize)), _opt_ptr(scores_out), _opt_ptr(rows_out)))
 
     def transducer_pruned_score_grad(logits, ranges, targets, frames, target_lengths, weights, grad_out, rows=None,
-                                     blank=0, normalize=True, B=None, T=None, S=None, U=None, C=None):
+                                     blank=0, normalize=True, B=None, T=None, S=None, U=None, C=None, dtype=None):
         """The gradient of the scores of `transducer_pruned_score` under `weights` (float32 [B] on the device), in one
         stateless call (gtnx_batch_transducer_pruned_score_grad): `grad_out` (float32 [B, T, S, C]), every row stored
         exactly once -- rows t >= T_b, rows whose u is outside 0 .. U_b, dead rows, nodes nothing passes through and the
         rows of an utterance that scores -inf with zeros.  `rows`: the plane `transducer_pruned_score` left in
-        `rows_out` for the same inputs, or None.  No atomics, the same bits run to run, sliced or not."""
+        `rows_out` for the same inputs, or None.  No atomics, the same bits run to run, sliced or not.  Bfloat16 or
+        float16 `logits` (`dtype=` with a device address): `grad_out` has their dtype, as `transducer_score_grad`'s
+        (gtnx_batch_transducer_pruned_score_grad16)."""
         who = "transducer_pruned_score_grad"
-        b, t, s, u, c = _transducer_pruned_args(
+        b, t, s, u, c, code = _transducer_pruned_args(
             who, logits, ranges, targets, frames, target_lengths, blank, (B, T, S, U, C),
             [(weights, lambda b, t, s, c: b, "weights must be a float32 contiguous tensor [B]"),
-             (grad_out, lambda b, t, s, c: b * t * s * c, "grad_out must be a float32 contiguous tensor [B, T, S, C]"),
-             (rows, lambda b, t, s, c: 3 * b * t * s, "rows must be a float32 contiguous tensor [B, T, S, 3]")])
+             (grad_out, lambda b, t, s, c: b * t * s * c, "grad_out must be a float32 contiguous tensor [B, T, S, C]",
+              True),
+             (rows, lambda b, t, s, c: 3 * b * t * s, "rows must be a float32 contiguous tensor [B, T, S, 3]")], dtype)
         if b == 0 and hasattr(logits, "data_ptr"):
             return
-        check(lib.gtnx_batch_transducer_pruned_score_grad(
-            _opt_ptr(logits), _opt_ptr(ranges), _transducer_targets(targets, b, u), _opt_ptr(frames),
-            _opt_ptr(target_lengths), b, t, s, u, c, int(blank), int(bool(normalize)), _opt_ptr(weights),
-            _opt_ptr(grad_out), _opt_ptr(rows)))
+        head = (_opt_ptr(logits),) + ((code,) if code else ())
+        check((lib.gtnx_batch_transducer_pruned_score_grad16 if code else lib.gtnx_batch_transducer_pruned_score_grad)(
+            *head, _opt_ptr(ranges), _transducer_targets(targets, b, u), _opt_ptr(frames), _opt_ptr(target_lengths), b,
+            t, s, u, c, int(blank), int(bool(normalize)), _opt_ptr(weights), _opt_ptr(grad_out), _opt_ptr(rows)))
 
     def transducer_occupancy(rows, frames, target_lengths, out, B=None, T=None, U=None):
         """The node occupancies of a full transducer lattice (gtnx_batch_transducer_occupancy): `out` float32

@@ -500,6 +500,43 @@ GTN_EXPORT int gtn_transducer_pruned_score_grad_n(const void* logits, const void
   });
 }
 
+// The four transducer entries above over bfloat16 / float16 logits: logits and grad hold 2-byte elements of dtype
+// (GTNX_DTYPE_F16 / GTNX_DTYPE_BF16); scores, weights and rows stay float32.
+GTN_EXPORT int gtn_transducer_score16_n(const void* logits, int dtype, const void* targets, const void* frames,
+                                        const void* target_lengths, int B, int T, int U, int C, int blank,
+                                        int normalize, void* scores, void* rows) {
+  return guarded([&] {
+    gtn::criteria::transducerScoreBatch16(logits, dtype, targets, frames, target_lengths, B, T, U, C, blank,
+                                          normalize != 0, scores, rows);
+  });
+}
+GTN_EXPORT int gtn_transducer_score_grad16_n(const void* logits, int dtype, const void* targets, const void* frames,
+                                             const void* target_lengths, int B, int T, int U, int C, int blank,
+                                             int normalize, const void* weights, void* grad, const void* rows) {
+  return guarded([&] {
+    gtn::criteria::transducerScoreGradBatch16(logits, dtype, targets, frames, target_lengths, B, T, U, C, blank,
+                                              normalize != 0, weights, grad, rows);
+  });
+}
+GTN_EXPORT int gtn_transducer_pruned_score16_n(const void* logits, int dtype, const void* ranges, const void* targets,
+                                               const void* frames, const void* target_lengths, int B, int T, int S,
+                                               int U, int C, int blank, int normalize, void* scores, void* rows) {
+  return guarded([&] {
+    gtn::criteria::transducerPrunedScoreBatch16(logits, dtype, ranges, targets, frames, target_lengths, B, T, S, U, C,
+                                                blank, normalize != 0, scores, rows);
+  });
+}
+GTN_EXPORT int gtn_transducer_pruned_score_grad16_n(const void* logits, int dtype, const void* ranges,
+                                                    const void* targets, const void* frames,
+                                                    const void* target_lengths, int B, int T, int S, int U, int C,
+                                                    int blank, int normalize, const void* weights, void* grad,
+                                                    const void* rows) {
+  return guarded([&] {
+    gtn::criteria::transducerPrunedScoreGradBatch16(logits, dtype, ranges, targets, frames, target_lengths, B, T, S, U,
+                                                    C, blank, normalize != 0, weights, grad, rows);
+  });
+}
+
 // Node occupancies of a full lattice from its kept compact plane.  rows: DEVICE float32 [B][T][U+1][3]; occ: DEVICE
 // float32 [B][T][U+1].
 GTN_EXPORT int gtn_transducer_occupancy_n(const void* rows, const void* frames, const void* target_lengths, int B, int T,

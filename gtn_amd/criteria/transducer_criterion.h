@@ -168,6 +168,112 @@ inline void transducerPrunedScoreGradBatch(
                                      static_cast<const float*>(rowsDev));
 }
 
+/** transducerScoreBatch over bfloat16 / float16 logits: `logitsDev` holds 2-byte elements of `dtype` (GTNX_DTYPE_F16 /
+ *  GTNX_DTYPE_BF16), read in place; scores and the rows plane stay float32.  gtnx_batch_transducer_score16 has the
+ *  contract. */
+inline void transducerScoreBatch16(
+    const void* logitsDev,
+    int dtype,
+    const void* targetsDev,
+    const void* framesDev,
+    const void* targetLengthsDev,
+    int B,
+    int T,
+    int U,
+    int C,
+    int blank,
+    bool normalize,
+    void* scoresDev,
+    void* rowsDev = nullptr) {
+  if (!scoresDev) {
+    throw std::invalid_argument("transducerScoreBatch16: null scores");
+  }
+  batched::transducerScore16(logitsDev, dtype, static_cast<const int*>(targetsDev), static_cast<const int*>(framesDev),
+                             static_cast<const int*>(targetLengthsDev), B, T, U, C, blank, normalize,
+                             static_cast<float*>(scoresDev), static_cast<float*>(rowsDev));
+}
+
+/** Their gradient under `weightsDev` (device float32 [B]): `gradDev` device [B][T][U + 1][C] of the logits' dtype, every
+ *  row written; `rowsDev` the plane transducerScoreBatch16 left for the same inputs, or null. */
+inline void transducerScoreGradBatch16(
+    const void* logitsDev,
+    int dtype,
+    const void* targetsDev,
+    const void* framesDev,
+    const void* targetLengthsDev,
+    int B,
+    int T,
+    int U,
+    int C,
+    int blank,
+    bool normalize,
+    const void* weightsDev,
+    void* gradDev,
+    const void* rowsDev = nullptr) {
+  if (!weightsDev || !gradDev) {
+    throw std::invalid_argument("transducerScoreGradBatch16: null weights or gradient");
+  }
+  batched::transducerScoreGrad16(logitsDev, dtype, static_cast<const int*>(targetsDev),
+                                 static_cast<const int*>(framesDev), static_cast<const int*>(targetLengthsDev), B, T, U,
+                                 C, blank, normalize, static_cast<const float*>(weightsDev), gradDev,
+                                 static_cast<const float*>(rowsDev));
+}
+
+/** transducerPrunedScoreBatch over bfloat16 / float16 logits [B][T][S][C] of `dtype`; the rest as
+ *  transducerScoreBatch16.  gtnx_batch_transducer_pruned_score16 has the contract. */
+inline void transducerPrunedScoreBatch16(
+    const void* logitsDev,
+    int dtype,
+    const void* rangesDev,
+    const void* targetsDev,
+    const void* framesDev,
+    const void* targetLengthsDev,
+    int B,
+    int T,
+    int S,
+    int U,
+    int C,
+    int blank,
+    bool normalize,
+    void* scoresDev,
+    void* rowsDev = nullptr) {
+  if (!scoresDev) {
+    throw std::invalid_argument("transducerPrunedScoreBatch16: null scores");
+  }
+  batched::transducerPrunedScore16(logitsDev, dtype, static_cast<const int*>(rangesDev),
+                                   static_cast<const int*>(targetsDev), static_cast<const int*>(framesDev),
+                                   static_cast<const int*>(targetLengthsDev), B, T, S, U, C, blank, normalize,
+                                   static_cast<float*>(scoresDev), static_cast<float*>(rowsDev));
+}
+
+/** Their gradient under `weightsDev`: `gradDev` device [B][T][S][C] of the logits' dtype, every row written. */
+inline void transducerPrunedScoreGradBatch16(
+    const void* logitsDev,
+    int dtype,
+    const void* rangesDev,
+    const void* targetsDev,
+    const void* framesDev,
+    const void* targetLengthsDev,
+    int B,
+    int T,
+    int S,
+    int U,
+    int C,
+    int blank,
+    bool normalize,
+    const void* weightsDev,
+    void* gradDev,
+    const void* rowsDev = nullptr) {
+  if (!weightsDev || !gradDev) {
+    throw std::invalid_argument("transducerPrunedScoreGradBatch16: null weights or gradient");
+  }
+  batched::transducerPrunedScoreGrad16(logitsDev, dtype, static_cast<const int*>(rangesDev),
+                                       static_cast<const int*>(targetsDev), static_cast<const int*>(framesDev),
+                                       static_cast<const int*>(targetLengthsDev), B, T, S, U, C, blank, normalize,
+                                       static_cast<const float*>(weightsDev), gradDev,
+                                       static_cast<const float*>(rowsDev));
+}
+
 /** The node occupancies `occDev` (device float32 [B][T][U + 1]) of the full lattice whose compact plane `rowsDev`
  *  (device float32 [B][T][U + 1][3]) transducerScoreBatch or transducerAddScoreBatch left. */
 inline void transducerOccupancyBatch(

@@ -509,6 +509,26 @@ void batch_transducer_pruned_score_grad(const float* logits_dev, const int* rang
                                         int C, int blank, int normalize, const float* weights_dev, float* grad_dev,
                                         const float* rows_dev);
 void batch_transducer_pruned_stats(int64_t* calls, int64_t* utterances);  // calls of the two above / their utterances
+// The four calls above over bfloat16 / float16 logits (DESIGN section 45 holds what is added to sections 42 and 44):
+// logits_dev and grad_dev hold 2-byte elements of `dtype` (GTNX_DTYPE_F16 / GTNX_DTYPE_BF16, anything else is refused
+// before a device is asked for), read and written in place by transducer16.hip -- converted exactly, float32
+// arithmetic, the gradient rounded once to nearest even, never-read rows as +0 bits.  Scores, weights and the rows
+// plane stay float32, and a plane left by a 16-bit score call serves the 16-bit gradient call and
+// batch_transducer_occupancy.  The same refusals, -inf cases, scratch, slicing and bits; they count in
+// batch_transducer_stats / batch_transducer_pruned_stats.
+void batch_transducer_score16(const void* logits_dev, int dtype, const int* targets_dev, const int* frames_dev,
+                              const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
+                              float* scores_dev, float* rows_dev);
+void batch_transducer_score_grad16(const void* logits_dev, int dtype, const int* targets_dev, const int* frames_dev,
+                                   const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
+                                   const float* weights_dev, void* grad_dev, const float* rows_dev);
+void batch_transducer_pruned_score16(const void* logits_dev, int dtype, const int* ranges_dev, const int* targets_dev,
+                                     const int* frames_dev, const int* target_lengths_dev, int B, int T, int S, int U,
+                                     int C, int blank, int normalize, float* scores_dev, float* rows_dev);
+void batch_transducer_pruned_score_grad16(const void* logits_dev, int dtype, const int* ranges_dev,
+                                          const int* targets_dev, const int* frames_dev, const int* target_lengths_dev,
+                                          int B, int T, int S, int U, int C, int blank, int normalize,
+                                          const float* weights_dev, void* grad_dev, const float* rows_dev);
 // occ_dev float32 [B][T][U + 1] = exp(alpha + beta - score) of the full lattice whose compact plane rows_dev
 // [B][T][U + 1][3] batch_transducer_score or batch_transducer_add_score left (beta includes the node's outgoing arcs);
 // 0 outside t < T_b, u <= U_b and for an utterance that scores -inf; every element stored once.  8 bytes of pooled

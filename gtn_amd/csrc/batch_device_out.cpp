@@ -1615,13 +1615,18 @@ static_assert(kTransducerMaxU1 == 1024 && kTransducerMaxT == 65535 && kTransduce
 
 // both entry points: scores_dev for the score (rows_dev: where the compact plane is left, or null); weights_dev and
 // grad_dev for the gradient (rows_dev: the plane a score call left, or null)
-void transducer_impl(const char* who, const float* x, const int* targets, const int* frames, const int* tlen, int B,
-                     int T, int U, int C, int blank, int normalize, float* scores_dev, float* rows_dev,
-                     const float* weights_dev, float* grad_dev) {
+// (dtype: GTNX_DTYPE_F32, or GTNX_DTYPE_F16 / GTNX_DTYPE_BF16 for the 16-bit entries -- x and grad_dev have that type
+// and transducer16.hip's rows and gradient kernels stand in for transducer.hip's; the sweep is the same)
+void transducer_impl(const char* who, const void* x, int dtype, const int* targets, const int* frames, const int* tlen,
+                     int B, int T, int U, int C, int blank, int normalize, float* scores_dev, float* rows_dev,
+                     const float* weights_dev, void* grad_dev) {
   const bool want_grad = scores_dev == nullptr;
   // what the arguments alone decide comes first: no device is asked for an invalid call
   if (!x || (!targets && U > 0) || !frames || !tlen)
     refuse(who, "null input pointer (logits, targets, frames and target_lengths are all read)");
+  const bool f32 = dtype == GTNX_DTYPE_F32;
+  if (!f32 && dtype != GTNX_DTYPE_F16 && dtype != GTNX_DTYPE_BF16)
+    refuse(who, "the logits must be GTNX_DTYPE_F16 or GTNX_DTYPE_BF16");
   if (want_grad && (!weights_dev || !grad_dev)) refuse(who, "null weights or grad pointer");
   if (B < 0) refuse(who, "negative B");
   if (U < 0 || U + 1 > kTransducerMaxU1) refuse(who, "U + 1 outside 1 .. 1024");
@@ -1636,12 +1641,12 @@ void transducer_impl(const char* who, const float* x, const int* targets, const 
   if (!ptr_device_memory_of(x, rt.device())) refuse(who, "the logits are not memory of the engine's current device");
   check_outputs_local(who, {scores_dev, grad_dev, want_grad ? nullptr : rows_dev});
   TransducerArgs a{};
-  a.x = x;
+  a.x = f32 ? static_cast<const float*>(x) : nullptr;
   a.targets = targets;
   a.frames = frames;
   a.tlen = tlen;
   a.weights = weights_dev;
-  a.grad = grad_dev;
+  a.grad = f32 ? static_cast<float*>(grad_dev) : nullptr;
   a.T = T;
   a.U1 = U1;
   a.C = C;
@@ -1653,7 +1658,8 @@ void transducer_impl(const char* who, const float* x, const int* targets, const 
   // algorithmic bytes, by the widths (the counts are device memory: an upper bound).  rows: every logit once, the
   // triple out (unnormalised: two gathered entries).  sweep: per direction two of the three values in, one plane out.
   // grad: every logit in (normalised) and every gradient out, the triple and three plane values in.
-  const double row_in = normalize ? 4.0 * C : 8.0;
+  const double elem = f32 ? 4.0 : 2.0;
+  const double row_in = normalize ? elem * C : 2.0 * elem;
   const int64_t own_rows = rows_dev ? 0 : 12;
   const int64_t per_bytes = per_utt * (own_rows + (want_grad ? 8 : 0));
   for_pair_slices(B, per_bytes, kTransducerScratch, [&](int64_t b0, int64_t cnt) {
@@ -1664,17 +1670,23 @@ void transducer_impl(const char* who, const float* x, const int* targets, const 
     a.rows = rows_dev ? const_cast<float*>(rows_dev) + 3 * per_utt * b0 : work->as<float>();
     a.alpha = want_grad ? work->as<float>(size_t(own_rows) * nodes) : nullptr;
     a.beta = want_grad ? work->as<float>(size_t(own_rows + 4) * nodes) : nullptr;
+    // (the 16-bit kernels' view of the same slice; ranges null: the full lattice, W == U1)
+    const Transducer16Args h{x, nullptr, targets, frames, tlen, a.rows, a.alpha, a.beta, a.scores, a.weights, grad_dev,
+                             T, U1, U1, C, blank, a.normalize, a.utt0, a.count, dtype == GTNX_DTYPE_BF16 ? 1 : 0};
     if (!(want_grad && rows_dev)) {
-      GTNX_PROF("transducer_rows", double(nodes) * (row_in + 12.0));
-      launch_transducer_rows(a, rt.stream());
+      GTNX_PROF(f32 ? "transducer_rows" : "transducer16_rows", double(nodes) * (row_in + 12.0));
+      if (f32) launch_transducer_rows(a, rt.stream());
+      else launch_transducer16_rows(h, rt.stream());
     }
     {
       GTNX_PROF("transducer_sweep", double(nodes) * (want_grad ? 24.0 : 8.0) + 4.0 * double(cnt));
       launch_transducer_sweep(a, rt.stream());
     }
     if (want_grad) {
-      GTNX_PROF("transducer_grad", double(nodes) * ((normalize ? 8.0 : 4.0) * C + 24.0));
-      launch_transducer_grad(a, rt.stream());
+      GTNX_PROF(f32 ? "transducer_grad" : "transducer16_grad",
+                double(nodes) * ((normalize ? 2.0 : 1.0) * elem * C + 24.0));
+      if (f32) launch_transducer_grad(a, rt.stream());
+      else launch_transducer16_grad(h, rt.stream());
     }
     // (the planes go back to the stream-ordered pool behind the launches)
   });
@@ -1689,16 +1701,40 @@ void batch_transducer_score(const float* logits_dev, const int* targets_dev, con
                             float* scores_dev, float* rows_dev) {
   GTNX_HOST_T("batch.transducer_score");
   if (!scores_dev) throw_invalid("[gtnx_batch_transducer_score] null scores pointer");
-  transducer_impl("gtnx_batch_transducer_score", logits_dev, targets_dev, frames_dev, target_lengths_dev, B, T, U, C,
-                  blank, normalize, scores_dev, rows_dev, nullptr, nullptr);
+  transducer_impl("gtnx_batch_transducer_score", logits_dev, GTNX_DTYPE_F32, targets_dev, frames_dev,
+                  target_lengths_dev, B, T, U, C, blank, normalize, scores_dev, rows_dev, nullptr, nullptr);
 }
 
 void batch_transducer_score_grad(const float* logits_dev, const int* targets_dev, const int* frames_dev,
                                  const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
                                  const float* weights_dev, float* grad_dev, const float* rows_dev) {
   GTNX_HOST_T("batch.transducer_score_grad");
-  transducer_impl("gtnx_batch_transducer_score_grad", logits_dev, targets_dev, frames_dev, target_lengths_dev, B, T, U,
-                  C, blank, normalize, nullptr, const_cast<float*>(rows_dev), weights_dev, grad_dev);
+  transducer_impl("gtnx_batch_transducer_score_grad", logits_dev, GTNX_DTYPE_F32, targets_dev, frames_dev,
+                  target_lengths_dev, B, T, U, C, blank, normalize, nullptr, const_cast<float*>(rows_dev), weights_dev,
+                  grad_dev);
+}
+
+namespace {
+// a 16-bit entry's dtype: the float32 code belongs to the float32 entries and is refused like any other
+int dtype16_only(int dtype) { return dtype == GTNX_DTYPE_F32 ? -1 : dtype; }
+}  // namespace
+
+void batch_transducer_score16(const void* logits_dev, int dtype, const int* targets_dev, const int* frames_dev,
+                              const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
+                              float* scores_dev, float* rows_dev) {
+  GTNX_HOST_T("batch.transducer_score16");
+  if (!scores_dev) throw_invalid("[gtnx_batch_transducer_score16] null scores pointer");
+  transducer_impl("gtnx_batch_transducer_score16", logits_dev, dtype16_only(dtype), targets_dev, frames_dev,
+                  target_lengths_dev, B, T, U, C, blank, normalize, scores_dev, rows_dev, nullptr, nullptr);
+}
+
+void batch_transducer_score_grad16(const void* logits_dev, int dtype, const int* targets_dev, const int* frames_dev,
+                                   const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
+                                   const float* weights_dev, void* grad_dev, const float* rows_dev) {
+  GTNX_HOST_T("batch.transducer_score_grad16");
+  transducer_impl("gtnx_batch_transducer_score_grad16", logits_dev, dtype16_only(dtype), targets_dev, frames_dev,
+                  target_lengths_dev, B, T, U, C, blank, normalize, nullptr, const_cast<float*>(rows_dev), weights_dev,
+                  grad_dev);
 }
 
 // ---- batched transducer score under an additive joint, am + lm never formed, and its gradients (transducer_add.hip) ----
@@ -1827,12 +1863,15 @@ Counters g_transducer_pruned;  // (calls, utterances)
 static_assert(kTransducerPrunedMaxS == 64, "the texts say 64");
 
 // both entry points, as transducer_impl: scores_dev for the score, weights_dev and grad_dev for the gradient
-void transducer_pruned_impl(const char* who, const float* x, const int* ranges, const int* targets, const int* frames,
-                            const int* tlen, int B, int T, int S, int U, int C, int blank, int normalize,
-                            float* scores_dev, float* rows_dev, const float* weights_dev, float* grad_dev) {
+void transducer_pruned_impl(const char* who, const void* x, int dtype, const int* ranges, const int* targets,
+                            const int* frames, const int* tlen, int B, int T, int S, int U, int C, int blank,
+                            int normalize, float* scores_dev, float* rows_dev, const float* weights_dev, void* grad_dev) {
   const bool want_grad = scores_dev == nullptr;
   if (!x || !ranges || (!targets && U > 0) || !frames || !tlen)
     refuse(who, "null input pointer (logits, ranges, targets, frames and target_lengths are all read)");
+  const bool f32 = dtype == GTNX_DTYPE_F32;
+  if (!f32 && dtype != GTNX_DTYPE_F16 && dtype != GTNX_DTYPE_BF16)
+    refuse(who, "the logits must be GTNX_DTYPE_F16 or GTNX_DTYPE_BF16");
   if (want_grad && (!weights_dev || !grad_dev)) refuse(who, "null weights or grad pointer");
   if (B < 0) refuse(who, "negative B");
   if (U < 0 || U + 1 > kTransducerMaxU1) refuse(who, "U + 1 outside 1 .. 1024");
@@ -1847,13 +1886,13 @@ void transducer_pruned_impl(const char* who, const float* x, const int* ranges, 
   if (!ptr_device_memory_of(x, rt.device())) refuse(who, "the logits are not memory of the engine's current device");
   check_outputs_local(who, {scores_dev, grad_dev, want_grad ? nullptr : rows_dev});
   TransducerPrunedArgs a{};
-  a.x = x;
+  a.x = f32 ? static_cast<const float*>(x) : nullptr;
   a.ranges = ranges;
   a.targets = targets;
   a.frames = frames;
   a.tlen = tlen;
   a.weights = weights_dev;
-  a.grad = grad_dev;
+  a.grad = f32 ? static_cast<float*>(grad_dev) : nullptr;
   a.T = T;
   a.S = S;
   a.U1 = U + 1;
@@ -1864,7 +1903,8 @@ void transducer_pruned_impl(const char* who, const float* x, const int* ranges, 
   if (want_grad) sc = rt.alloc(sizeof(float) * size_t(B));
   a.scores = want_grad ? sc->as<float>() : scores_dev;
   // algorithmic bytes as transducer_impl's, per band node; the sweep also reads r_t once per lane and frame
-  const double row_in = normalize ? 4.0 * C : 8.0;
+  const double elem = f32 ? 4.0 : 2.0;
+  const double row_in = normalize ? elem * C : 2.0 * elem;
   const int64_t own_rows = rows_dev ? 0 : 12;
   const int64_t per_bytes = per_utt * (own_rows + (want_grad ? 8 : 0));
   for_pair_slices(B, per_bytes, kTransducerScratch, [&](int64_t b0, int64_t cnt) {
@@ -1875,17 +1915,23 @@ void transducer_pruned_impl(const char* who, const float* x, const int* ranges, 
     a.rows = rows_dev ? const_cast<float*>(rows_dev) + 3 * per_utt * b0 : work->as<float>();
     a.alpha = want_grad ? work->as<float>(size_t(own_rows) * nodes) : nullptr;
     a.beta = want_grad ? work->as<float>(size_t(own_rows + 4) * nodes) : nullptr;
+    // (the 16-bit kernels' view of the same slice: the band, W == S)
+    const Transducer16Args h{x, ranges, targets, frames, tlen, a.rows, a.alpha, a.beta, a.scores, a.weights, grad_dev,
+                             T, S, a.U1, C, blank, a.normalize, a.utt0, a.count, dtype == GTNX_DTYPE_BF16 ? 1 : 0};
     if (!(want_grad && rows_dev)) {
-      GTNX_PROF("transducer_pruned_rows", double(nodes) * (row_in + 16.0));
-      launch_transducer_pruned_rows(a, rt.stream());
+      GTNX_PROF(f32 ? "transducer_pruned_rows" : "transducer16_pruned_rows", double(nodes) * (row_in + 16.0));
+      if (f32) launch_transducer_pruned_rows(a, rt.stream());
+      else launch_transducer16_rows(h, rt.stream());
     }
     {
       GTNX_PROF("transducer_pruned_sweep", double(nodes) * (want_grad ? 32.0 : 12.0) + 4.0 * double(cnt));
       launch_transducer_pruned_sweep(a, rt.stream());
     }
     if (want_grad) {
-      GTNX_PROF("transducer_pruned_grad", double(nodes) * ((normalize ? 8.0 : 4.0) * C + 32.0));
-      launch_transducer_pruned_grad(a, rt.stream());
+      GTNX_PROF(f32 ? "transducer_pruned_grad" : "transducer16_pruned_grad",
+                double(nodes) * ((normalize ? 2.0 : 1.0) * elem * C + 32.0));
+      if (f32) launch_transducer_pruned_grad(a, rt.stream());
+      else launch_transducer16_grad(h, rt.stream());
     }
   });
   g_transducer_pruned.add(1, B);
@@ -1901,8 +1947,9 @@ void batch_transducer_pruned_score(const float* logits_dev, const int* ranges_de
                                    int C, int blank, int normalize, float* scores_dev, float* rows_dev) {
   GTNX_HOST_T("batch.transducer_pruned_score");
   if (!scores_dev) throw_invalid("[gtnx_batch_transducer_pruned_score] null scores pointer");
-  transducer_pruned_impl("gtnx_batch_transducer_pruned_score", logits_dev, ranges_dev, targets_dev, frames_dev,
-                         target_lengths_dev, B, T, S, U, C, blank, normalize, scores_dev, rows_dev, nullptr, nullptr);
+  transducer_pruned_impl("gtnx_batch_transducer_pruned_score", logits_dev, GTNX_DTYPE_F32, ranges_dev, targets_dev,
+                         frames_dev, target_lengths_dev, B, T, S, U, C, blank, normalize, scores_dev, rows_dev, nullptr,
+                         nullptr);
 }
 
 void batch_transducer_pruned_score_grad(const float* logits_dev, const int* ranges_dev, const int* targets_dev,
@@ -1910,9 +1957,29 @@ void batch_transducer_pruned_score_grad(const float* logits_dev, const int* rang
                                         int C, int blank, int normalize, const float* weights_dev, float* grad_dev,
                                         const float* rows_dev) {
   GTNX_HOST_T("batch.transducer_pruned_score_grad");
-  transducer_pruned_impl("gtnx_batch_transducer_pruned_score_grad", logits_dev, ranges_dev, targets_dev, frames_dev,
-                         target_lengths_dev, B, T, S, U, C, blank, normalize, nullptr, const_cast<float*>(rows_dev),
-                         weights_dev, grad_dev);
+  transducer_pruned_impl("gtnx_batch_transducer_pruned_score_grad", logits_dev, GTNX_DTYPE_F32, ranges_dev, targets_dev,
+                         frames_dev, target_lengths_dev, B, T, S, U, C, blank, normalize, nullptr,
+                         const_cast<float*>(rows_dev), weights_dev, grad_dev);
+}
+
+void batch_transducer_pruned_score16(const void* logits_dev, int dtype, const int* ranges_dev, const int* targets_dev,
+                                     const int* frames_dev, const int* target_lengths_dev, int B, int T, int S, int U,
+                                     int C, int blank, int normalize, float* scores_dev, float* rows_dev) {
+  GTNX_HOST_T("batch.transducer_pruned_score16");
+  if (!scores_dev) throw_invalid("[gtnx_batch_transducer_pruned_score16] null scores pointer");
+  transducer_pruned_impl("gtnx_batch_transducer_pruned_score16", logits_dev, dtype16_only(dtype), ranges_dev,
+                         targets_dev, frames_dev, target_lengths_dev, B, T, S, U, C, blank, normalize, scores_dev,
+                         rows_dev, nullptr, nullptr);
+}
+
+void batch_transducer_pruned_score_grad16(const void* logits_dev, int dtype, const int* ranges_dev,
+                                          const int* targets_dev, const int* frames_dev, const int* target_lengths_dev,
+                                          int B, int T, int S, int U, int C, int blank, int normalize,
+                                          const float* weights_dev, void* grad_dev, const float* rows_dev) {
+  GTNX_HOST_T("batch.transducer_pruned_score_grad16");
+  transducer_pruned_impl("gtnx_batch_transducer_pruned_score_grad16", logits_dev, dtype16_only(dtype), ranges_dev,
+                         targets_dev, frames_dev, target_lengths_dev, B, T, S, U, C, blank, normalize, nullptr,
+                         const_cast<float*>(rows_dev), weights_dev, grad_dev);
 }
 
 void batch_transducer_occupancy(const float* rows_dev, const int* frames_dev, const int* target_lengths_dev, int B,

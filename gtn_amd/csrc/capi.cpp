@@ -1276,6 +1276,59 @@ GTNX_API gtnx_status_t gtnx_batch_transducer_pruned_score_grad(const void* logit
 GTNX_API gtnx_status_t gtnx_batch_transducer_pruned_stats(int64_t* calls, int64_t* utterances) {
   return guard([&] { batch_transducer_pruned_stats(calls, utterances); });
 }
+GTNX_API gtnx_status_t gtnx_batch_transducer_score16(const void* logits_device, int dtype, const void* targets_device,
+                                                     const void* frames_device, const void* target_lengths_device,
+                                                     int B, int T, int U, int C, int blank, int normalize,
+                                                     void* scores_device, void* rows_device) {
+  return guard([&] {
+    batch_transducer_score16(logits_device, dtype, static_cast<const int*>(targets_device),
+                             static_cast<const int*>(frames_device), static_cast<const int*>(target_lengths_device), B,
+                             T, U, C, blank, normalize, static_cast<float*>(scores_device),
+                             static_cast<float*>(rows_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_transducer_score_grad16(const void* logits_device, int dtype,
+                                                          const void* targets_device, const void* frames_device,
+                                                          const void* target_lengths_device, int B, int T, int U, int C,
+                                                          int blank, int normalize, const void* weights_device,
+                                                          void* grad_device, const void* rows_device) {
+  return guard([&] {
+    batch_transducer_score_grad16(logits_device, dtype, static_cast<const int*>(targets_device),
+                                  static_cast<const int*>(frames_device),
+                                  static_cast<const int*>(target_lengths_device), B, T, U, C, blank, normalize,
+                                  static_cast<const float*>(weights_device), grad_device,
+                                  static_cast<const float*>(rows_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_transducer_pruned_score16(const void* logits_device, int dtype,
+                                                            const void* ranges_device, const void* targets_device,
+                                                            const void* frames_device,
+                                                            const void* target_lengths_device, int B, int T, int S,
+                                                            int U, int C, int blank, int normalize,
+                                                            void* scores_device, void* rows_device) {
+  return guard([&] {
+    batch_transducer_pruned_score16(logits_device, dtype, static_cast<const int*>(ranges_device),
+                                    static_cast<const int*>(targets_device), static_cast<const int*>(frames_device),
+                                    static_cast<const int*>(target_lengths_device), B, T, S, U, C, blank, normalize,
+                                    static_cast<float*>(scores_device), static_cast<float*>(rows_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_transducer_pruned_score_grad16(const void* logits_device, int dtype,
+                                                                 const void* ranges_device, const void* targets_device,
+                                                                 const void* frames_device,
+                                                                 const void* target_lengths_device, int B, int T, int S,
+                                                                 int U, int C, int blank, int normalize,
+                                                                 const void* weights_device, void* grad_device,
+                                                                 const void* rows_device) {
+  return guard([&] {
+    batch_transducer_pruned_score_grad16(logits_device, dtype, static_cast<const int*>(ranges_device),
+                                         static_cast<const int*>(targets_device),
+                                         static_cast<const int*>(frames_device),
+                                         static_cast<const int*>(target_lengths_device), B, T, S, U, C, blank,
+                                         normalize, static_cast<const float*>(weights_device), grad_device,
+                                         static_cast<const float*>(rows_device));
+  });
+}
 GTNX_API gtnx_status_t gtnx_batch_transducer_occupancy(const void* rows_device, const void* frames_device,
                                                        const void* target_lengths_device, int B, int T, int U,
                                                        void* occ_device) {

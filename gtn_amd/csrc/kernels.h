@@ -1282,6 +1282,29 @@ struct TransducerOccupancyArgs {
   GTNX_G float* occ;             // [n][T][U1]
 };
 void launch_transducer_occupancy(const TransducerOccupancyArgs& oa, hipStream_t st);
+// transducer16.hip: the rows and gradient passes of the two scores above over bfloat16 / float16 logits (the contract:
+// DESIGN section 45).  `ranges` null: the full lattice, x [n][T][U1][C] and W == U1; non-null: the band, x [n][T][S][C] and
+// W == S.  Elements are converted exactly; everything but x and grad is float32 and laid out as TransducerArgs' /
+// TransducerPrunedArgs' planes, so launch_transducer_sweep / launch_transducer_pruned_sweep run between the two.
+//   rows:   the compact triple of every live node, as launch_transducer_rows / launch_transducer_pruned_rows store it.
+//   grad:   every row of grad[b] for the slice's utterances in x's type, rounded once to nearest even; the never-read
+//           ones as +0 bits.
+struct Transducer16Args {
+  const GTNX_G void* x;          // [n][T][W][C], 2-byte elements
+  const GTNX_G int* ranges;      // [n][T] or null
+  const GTNX_G int* targets;     // [n][U1 - 1]
+  const GTNX_G int* frames;      // [n]
+  const GTNX_G int* tlen;        // [n]
+  GTNX_G float* rows;            // [count][T][W][3]
+  const GTNX_G float* alpha;     // [count][T][W] (grad)
+  const GTNX_G float* beta;      // [count][T][W] (grad)
+  const GTNX_G float* scores;    // [n] (grad)
+  const GTNX_G float* weights;   // [n] (grad)
+  GTNX_G void* grad;             // [n][T][W][C], x's type (grad)
+  int T, W, U1, C, blank, normalize, utt0, count, bf16;
+};
+void launch_transducer16_rows(const Transducer16Args& a, hipStream_t st);
+void launch_transducer16_grad(const Transducer16Args& a, hipStream_t st);
 // asg_lattice.hip: the ASG log score of the utterances utt0 .. utt0 + count - 1, each with one acyclic token lattice of its
 // own in device memory (ctc_lattice.hip's form), under asg_score.hip's [C + C * C] table, and the gradients g[b] * d
 // score[b] / d (emissions_b, table, arc weights of b) (the contract: DESIGN section 37).  The states are the arcs; an

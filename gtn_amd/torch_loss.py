@@ -55,6 +55,10 @@ _ARGTYPES = {
     "gtn_transducer_add_score_grad_n": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "gtn_transducer_pruned_score_n": [_P] * 5 + [_I] * 7 + [_P, _P],
     "gtn_transducer_pruned_score_grad_n": [_P] * 5 + [_I] * 7 + [_P, _P, _P],
+    "gtn_transducer_score16_n": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
+    "gtn_transducer_score_grad16_n": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "gtn_transducer_pruned_score16_n": [_P, _I] + [_P] * 4 + [_I] * 7 + [_P, _P],
+    "gtn_transducer_pruned_score_grad16_n": [_P, _I] + [_P] * 4 + [_I] * 7 + [_P, _P, _P],
     "gtn_transducer_occupancy_n": [_P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_lattice_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_lattice_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
@@ -1446,9 +1450,18 @@ def asg_full_score(emissions, transitions, start=None, input_lengths=None):
     return _ASGFullScore.apply(x, transitions, start, frames)
 
 
+def _transducer_route(x, name):
+    """(native symbol, leading arguments, keywords of the gtn_amd entry) for logits x: bfloat16 / float16 logits take the
+    16-bit entries, which read x as it is and write a gradient of its dtype"""
+    if x.dtype in _DTYPE16:
+        return f"gtn_transducer_{name}16_n", (x.data_ptr(), _DTYPE16[x.dtype]), {"dtype": x.dtype}
+    return f"gtn_transducer_{name}_n", (x.data_ptr(),), {}
+
+
 class _TransducerScore(torch.autograd.Function):
     """forward: the rows and alpha launches; where the logits require grad the compact plane `rows` is kept as a saved
-    tensor.  backward: the one gradient call with grad_out as the weights, which then reads the logits once."""
+    tensor.  backward: the one gradient call with grad_out as the weights, which then reads the logits once.  The
+    logits are float32, bfloat16 or float16 and the gradient has their dtype; scores and `rows` are float32."""
 
     @staticmethod
     def forward(ctx, logits, targets, frames, tlen, blank, normalize):
@@ -1458,12 +1471,13 @@ class _TransducerScore(torch.autograd.Function):
         scores = torch.empty(B, dtype=torch.float32, device=x.device)
         rows = torch.empty(B, T, U1, 3, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[0] else None
         if B:
-            args = (x.data_ptr(), targets.data_ptr() if targets.numel() else None, frames.data_ptr(), tlen.data_ptr())
-            if _has_native("transducer_score", "gtn_transducer_score_n"):
-                _call("gtn_transducer_score_n", *args, B, T, U1 - 1, C_, blank, int(normalize), scores.data_ptr(),
-                      _ptr(rows))
+            symbol, head, kw = _transducer_route(x, "score")
+            args = (targets.data_ptr() if targets.numel() else None, frames.data_ptr(), tlen.data_ptr())
+            if _has_native("transducer_score", symbol):
+                _call(symbol, *head, *args, B, T, U1 - 1, C_, blank, int(normalize), scores.data_ptr(), _ptr(rows))
             else:
-                gtn.transducer_score(*args, scores.data_ptr(), _ptr(rows), blank, normalize, B=B, T=T, U=U1 - 1, C=C_)
+                gtn.transducer_score(x.data_ptr(), *args, scores.data_ptr(), _ptr(rows), blank, normalize, B=B, T=T,
+                                     U=U1 - 1, C=C_, **kw)
         _engine_done(stream)
         ctx.save_for_backward(x, targets, frames, tlen, rows)
         ctx.args = (blank, normalize)
@@ -1480,13 +1494,14 @@ class _TransducerScore(torch.autograd.Function):
         if B:
             g = grad_out.detach().to(torch.float32).contiguous()
             stream = _engine_stream(x.device)
-            args = (x.data_ptr(), targets.data_ptr() if targets.numel() else None, frames.data_ptr(), tlen.data_ptr())
+            symbol, head, kw = _transducer_route(x, "score_grad")
+            args = (targets.data_ptr() if targets.numel() else None, frames.data_ptr(), tlen.data_ptr())
             if _native():
-                _call("gtn_transducer_score_grad_n", *args, B, T, U1 - 1, C_, blank, int(normalize), g.data_ptr(),
-                      grad.data_ptr(), _ptr(rows))
+                _call(symbol, *head, *args, B, T, U1 - 1, C_, blank, int(normalize), g.data_ptr(), grad.data_ptr(),
+                      _ptr(rows))
             else:
-                gtn.transducer_score_grad(*args, g.data_ptr(), grad.data_ptr(), _ptr(rows), blank, normalize, B=B, T=T,
-                                          U=U1 - 1, C=C_)
+                gtn.transducer_score_grad(x.data_ptr(), *args, g.data_ptr(), grad.data_ptr(), _ptr(rows), blank,
+                                          normalize, B=B, T=T, U=U1 - 1, C=C_, **kw)
             _engine_done(stream)
         return grad, None, None, None, None, None
 
@@ -1494,7 +1509,10 @@ class _TransducerScore(torch.autograd.Function):
 def transducer_score(logits, targets, input_lengths, target_lengths, blank=0, normalize=True):
     """The transducer (RNN-T) log score of a padded batch over joint logits, differentiable: with `normalize` score[b] =
     log P(targets[b, :U_b] | logits[b, :T_b]), the kernel taking the log-softmax of every live row itself; without it the
-    rows are taken as log-probabilities as they are.  logits: float32 CUDA tensor [B, T, U + 1, C], read in place;
+    rows are taken as log-probabilities as they are.  logits: float32 CUDA tensor [B, T, U + 1, C], read in place -- or
+    a bfloat16 / float16 one, what autocast hands over, read as it is: every element is converted exactly, the arithmetic
+    is float32, the scores are float32 and autograd gets a gradient of the logits' dtype, rounded once; no float32 copy of
+    either tensor is made;
     targets: int32 or int64 CUDA tensor [B, U]; input_lengths (T_b) and target_lengths (U_b): int32 or int64 CUDA tensors
     [B], read on the device -- nothing is downloaded.  U + 1 <= 1024, 1 <= T <= 65535, C <= 2^20, B * T * (U + 1) < 2^31.
     Returns float32 [B].  A score is -inf, with a zero gradient and never NaN, when T_b == 0, T_b > T, U_b > U, a target
@@ -1505,8 +1523,9 @@ def transducer_score(logits, targets, input_lengths, target_lengths, blank=0, no
     forward plus backward read the logits twice and write them once.  Runs on the caller's stream."""
     who = "transducer_score"
     x = logits
-    if not (torch.is_tensor(x) and x.dim() == 4 and x.dtype == torch.float32 and x.shape[2] >= 1):
-        raise ValueError(f"{who}: logits must be a float32 tensor [B, T, U + 1, C]")
+    if not (torch.is_tensor(x) and x.dim() == 4 and (x.dtype == torch.float32 or x.dtype in _DTYPE16)
+            and x.shape[2] >= 1):
+        raise ValueError(f"{who}: logits must be a float32 tensor [B, T, U + 1, C] (or bfloat16 / float16)")
     B, T, U1, C_ = x.shape
     if not (torch.is_tensor(targets) and targets.dtype in (torch.int32, torch.int64)
             and tuple(targets.shape) == (B, U1 - 1)):
@@ -1662,14 +1681,14 @@ class _TransducerPrunedScore(torch.autograd.Function):
         scores = torch.empty(B, dtype=torch.float32, device=x.device)
         rows = torch.empty(B, T, S, 3, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[0] else None
         if B:
-            args = (x.data_ptr(), ranges.data_ptr(), targets.data_ptr() if targets.numel() else None, frames.data_ptr(),
+            symbol, head, kw = _transducer_route(x, "pruned_score")
+            args = (ranges.data_ptr(), targets.data_ptr() if targets.numel() else None, frames.data_ptr(),
                     tlen.data_ptr())
-            if _has_native("transducer_pruned_score", "gtn_transducer_pruned_score_n"):
-                _call("gtn_transducer_pruned_score_n", *args, B, T, S, U, C_, blank, int(normalize), scores.data_ptr(),
-                      _ptr(rows))
+            if _has_native("transducer_pruned_score", symbol):
+                _call(symbol, *head, *args, B, T, S, U, C_, blank, int(normalize), scores.data_ptr(), _ptr(rows))
             else:
-                gtn.transducer_pruned_score(*args, scores.data_ptr(), _ptr(rows), blank, normalize, B=B, T=T, S=S, U=U,
-                                            C=C_)
+                gtn.transducer_pruned_score(x.data_ptr(), *args, scores.data_ptr(), _ptr(rows), blank, normalize, B=B,
+                                            T=T, S=S, U=U, C=C_, **kw)
         _engine_done(stream)
         ctx.save_for_backward(x, ranges, targets, frames, tlen, rows)
         ctx.args = (blank, normalize)
@@ -1687,14 +1706,15 @@ class _TransducerPrunedScore(torch.autograd.Function):
         if B:
             g = grad_out.detach().to(torch.float32).contiguous()
             stream = _engine_stream(x.device)
-            args = (x.data_ptr(), ranges.data_ptr(), targets.data_ptr() if targets.numel() else None, frames.data_ptr(),
+            symbol, head, kw = _transducer_route(x, "pruned_score_grad")
+            args = (ranges.data_ptr(), targets.data_ptr() if targets.numel() else None, frames.data_ptr(),
                     tlen.data_ptr())
             if _native():
-                _call("gtn_transducer_pruned_score_grad_n", *args, B, T, S, U, C_, blank, int(normalize), g.data_ptr(),
-                      grad.data_ptr(), _ptr(rows))
+                _call(symbol, *head, *args, B, T, S, U, C_, blank, int(normalize), g.data_ptr(), grad.data_ptr(),
+                      _ptr(rows))
             else:
-                gtn.transducer_pruned_score_grad(*args, g.data_ptr(), grad.data_ptr(), _ptr(rows), blank, normalize,
-                                                 B=B, T=T, S=S, U=U, C=C_)
+                gtn.transducer_pruned_score_grad(x.data_ptr(), *args, g.data_ptr(), grad.data_ptr(), _ptr(rows), blank,
+                                                 normalize, B=B, T=T, S=S, U=U, C=C_, **kw)
             _engine_done(stream)
         return (grad,) + (None,) * 6
 
@@ -1712,7 +1732,8 @@ def _transducer_index_args(who, named):
 def transducer_pruned_score(logits, ranges, targets, input_lengths, target_lengths, blank=0, normalize=True):
     """The pruned (banded) transducer log score of a padded batch, differentiable: the second pass of pruned RNN-T
     training, where the joiner was evaluated on S symbol positions per frame only.  logits: float32 CUDA tensor
-    [B, T, S, C], band node (t, s) standing for lattice node (t, u = ranges[b, t] + s); ranges: int32 or int64 CUDA
+    [B, T, S, C] -- or a bfloat16 / float16 one, read as it is exactly as transducer_score reads one, the gradient in
+    the logits' dtype --, band node (t, s) standing for lattice node (t, u = ranges[b, t] + s); ranges: int32 or int64 CUDA
     tensor [B, T] (`transducer_prune_ranges` makes one); targets [B, U], input_lengths, target_lengths, blank and
     normalize as transducer_score.  score[b] is transducer_score's on the full lattice with every node outside the band
     removed.  1 <= S <= min(64, U + 1), U + 1 <= 1024, 1 <= T <= 65535, C <= 2^20, B * T * S < 2^31.  The ranges must not
@@ -1722,8 +1743,8 @@ def transducer_pruned_score(logits, ranges, targets, input_lengths, target_lengt
     are exactly 0.  Any grad_out; no atomics, the same bits run to run.  Runs on the caller's stream."""
     who = "transducer_pruned_score"
     x = logits
-    if not (torch.is_tensor(x) and x.dim() == 4 and x.dtype == torch.float32):
-        raise ValueError(f"{who}: logits must be a float32 tensor [B, T, S, C]")
+    if not (torch.is_tensor(x) and x.dim() == 4 and (x.dtype == torch.float32 or x.dtype in _DTYPE16)):
+        raise ValueError(f"{who}: logits must be a float32 tensor [B, T, S, C] (or bfloat16 / float16)")
     B, T, S, C_ = x.shape
     if not (torch.is_tensor(targets) and targets.dim() == 2):
         raise ValueError(f"{who}: targets must be an int32 or int64 tensor [{B}, U]")

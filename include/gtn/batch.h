@@ -466,6 +466,42 @@ inline void transducerPrunedScoreGrad(const float* logitsDevice, const int* rang
                                                         targetLengthsDevice, B, T, S, U, C, blank, normalize ? 1 : 0,
                                                         weightsDevice, gradDevice, rowsDevice));
 }
+/** transducerScore / transducerScoreGrad / transducerPrunedScore / transducerPrunedScoreGrad over bfloat16 / float16
+ *  logits, read as they are: logitsDevice and gradDevice hold 2-byte elements of `dtype` (GTNX_DTYPE_F16 /
+ *  GTNX_DTYPE_BF16); scores, weights and the rows plane stay float32.  Exact conversion, float32 arithmetic, the gradient
+ *  rounded once to nearest even, never-read rows as +0 bits; no float32 copy of either tensor.  Everything else is the
+ *  float32 function's -- gtnx_batch_transducer_score16 and its three siblings */
+inline void transducerScore16(const void* logitsDevice, int dtype, const int* targetsDevice, const int* framesDevice,
+                              const int* targetLengthsDevice, int B, int T, int U, int C, int blank, bool normalize,
+                              float* scoresDevice, float* rowsDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_score16(logitsDevice, dtype, targetsDevice, framesDevice, targetLengthsDevice, B,
+                                              T, U, C, blank, normalize ? 1 : 0, scoresDevice, rowsDevice));
+}
+inline void transducerScoreGrad16(const void* logitsDevice, int dtype, const int* targetsDevice,
+                                  const int* framesDevice, const int* targetLengthsDevice, int B, int T, int U, int C,
+                                  int blank, bool normalize, const float* weightsDevice, void* gradDevice,
+                                  const float* rowsDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_score_grad16(logitsDevice, dtype, targetsDevice, framesDevice,
+                                                   targetLengthsDevice, B, T, U, C, blank, normalize ? 1 : 0,
+                                                   weightsDevice, gradDevice, rowsDevice));
+}
+inline void transducerPrunedScore16(const void* logitsDevice, int dtype, const int* rangesDevice,
+                                    const int* targetsDevice, const int* framesDevice, const int* targetLengthsDevice,
+                                    int B, int T, int S, int U, int C, int blank, bool normalize, float* scoresDevice,
+                                    float* rowsDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_pruned_score16(logitsDevice, dtype, rangesDevice, targetsDevice, framesDevice,
+                                                     targetLengthsDevice, B, T, S, U, C, blank, normalize ? 1 : 0,
+                                                     scoresDevice, rowsDevice));
+}
+inline void transducerPrunedScoreGrad16(const void* logitsDevice, int dtype, const int* rangesDevice,
+                                        const int* targetsDevice, const int* framesDevice,
+                                        const int* targetLengthsDevice, int B, int T, int S, int U, int C, int blank,
+                                        bool normalize, const float* weightsDevice, void* gradDevice,
+                                        const float* rowsDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_pruned_score_grad16(logitsDevice, dtype, rangesDevice, targetsDevice,
+                                                          framesDevice, targetLengthsDevice, B, T, S, U, C, blank,
+                                                          normalize ? 1 : 0, weightsDevice, gradDevice, rowsDevice));
+}
 /** occDevice float32 [B][T][U + 1] = exp(alpha + beta - score) of the full lattice whose compact plane rowsDevice
  *  [B][T][U + 1][3] transducerScore or transducerAddScore left; 0 past the lengths and for an utterance that scores
  *  -inf -- gtnx_batch_transducer_occupancy */

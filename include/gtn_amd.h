@@ -928,6 +928,38 @@ gtnx_status_t gtnx_batch_transducer_pruned_score_grad(const void* logits_device,
                                                       void* grad_device, const void* rows_device);
 /* calls of either kind that have launched so far (process-wide) / utterances they took */
 gtnx_status_t gtnx_batch_transducer_pruned_stats(int64_t* calls, int64_t* utterances);
+/* The four calls above over BFLOAT16 / FLOAT16 joint logits, what autocast hands over, as they are:
+ * logits_device holds 2-byte elements of `dtype` (GTNX_DTYPE_F16: IEEE half, GTNX_DTYPE_BF16: bfloat16) in the same
+ * layout, and grad_device has that dtype too.  An element is converted exactly and all arithmetic is float32 (float16's
+ * own inf and NaN count as inf and NaN); the gradient is formed in float32 and rounded ONCE to nearest even; rows that are
+ * never read, dead rows and the rows of an utterance that scores -inf are stored as +0 bits.  scores_device,
+ * weights_device and rows_device stay float32: a plane left by a 16-bit score call serves the 16-bit gradient call and
+ * gtnx_batch_transducer_occupancy.  No float32 copy of either tensor is made.  Everything else -- the -inf cases, never
+ * NaN, never-read rows, the limits, pooled scratch and slicing, the same bits run to run, sliced or not, whatever the
+ * neighbours, with or without rows_device -- is the float32 call's.  GTNX_INVALID_ARGUMENT before a device is asked for:
+ * the float32 call's refusals and a dtype other than the two.  A base that is only 2-byte aligned is valid (16-byte
+ * loads and stores need C % 8 == 0 and 16-byte aligned bases; anything else moves 2-byte elements).  They count in
+ * gtnx_batch_transducer_stats / gtnx_batch_transducer_pruned_stats.  Launches per slice: transducer16.hip's rows and
+ * gradient kernels around the float32 call's sweep. */
+gtnx_status_t gtnx_batch_transducer_score16(const void* logits_device, int dtype, const void* targets_device,
+                                            const void* frames_device, const void* target_lengths_device, int B, int T,
+                                            int U, int C, int blank, int normalize, void* scores_device,
+                                            void* rows_device);
+gtnx_status_t gtnx_batch_transducer_score_grad16(const void* logits_device, int dtype, const void* targets_device,
+                                                 const void* frames_device, const void* target_lengths_device, int B,
+                                                 int T, int U, int C, int blank, int normalize,
+                                                 const void* weights_device, void* grad_device,
+                                                 const void* rows_device);
+gtnx_status_t gtnx_batch_transducer_pruned_score16(const void* logits_device, int dtype, const void* ranges_device,
+                                                   const void* targets_device, const void* frames_device,
+                                                   const void* target_lengths_device, int B, int T, int S, int U, int C,
+                                                   int blank, int normalize, void* scores_device, void* rows_device);
+gtnx_status_t gtnx_batch_transducer_pruned_score_grad16(const void* logits_device, int dtype,
+                                                        const void* ranges_device, const void* targets_device,
+                                                        const void* frames_device, const void* target_lengths_device,
+                                                        int B, int T, int S, int U, int C, int blank, int normalize,
+                                                        const void* weights_device, void* grad_device,
+                                                        const void* rows_device);
 /* The occupancy of every node of a FULL lattice, from the compact plane rows_device float32 [B][T][U+1][3] that
  * gtnx_batch_transducer_score or gtnx_batch_transducer_add_score left:
  *   occ_device float32 [B][T][U+1] = exp(alpha[t,u] + beta[t,u] - scores[b]),  beta including the node's outgoing arcs,
