@@ -85,6 +85,9 @@ transducer_pruned_score = _api.transducer_pruned_score  # (the score on a band o
 transducer_pruned_score_grad = _api.transducer_pruned_score_grad  # (its gradient, every band row written)
 debug_transducer_pruned_stats = _api.debug_transducer_pruned_stats  # (transducer_pruned_score / _grad: calls, utterances)
 transducer_occupancy = _api.transducer_occupancy  # (node occupancies of a full lattice from its kept rows plane)
+transducer_align = _api.transducer_align  # (best alignment of the transcript on the transducer lattice, on the device)
+transducer_align_rows = _api.transducer_align_rows  # (the same from a kept rows plane alone: no logits, no targets)
+debug_transducer_align_stats = _api.debug_transducer_align_stats  # (transducer_align / _rows: calls, utterances)
 ctc_loss_step16 = _api.ctc_loss_step16  # (one CTC criterion step over bfloat16 / float16 emissions, one launch)
 debug_edit_distance_stats = _api.debug_edit_distance_stats  # (edit_distance: calls that launched, pairs computed)
 debug_ctc_score_stats = _api.debug_ctc_score_stats  # (Batch.ctc_score / ctc_score_grad: calls that launched, pairs taken)

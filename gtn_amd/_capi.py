@@ -205,6 +205,10 @@ _SIGS = {
     "gtnx_batch_transducer_pruned_score_grad16": [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 7
                                                  + [C.c_void_p] * 3,
     "gtnx_batch_transducer_occupancy": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "gtnx_batch_transducer_align": [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p] * 5,
+    "gtnx_batch_transducer_align16": [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p] * 5,
+    "gtnx_batch_transducer_align_rows": [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 4,
+    "gtnx_batch_transducer_align_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_asg_lattice_score": [c_graph, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
     "gtnx_batch_asg_lattice_score_grad": [c_graph, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

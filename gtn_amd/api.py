@@ -2220,6 +2220,80 @@ def make_api(lib):
         check(lib.gtnx_batch_transducer_occupancy(_opt_ptr(rows), _opt_ptr(frames), _opt_ptr(target_lengths), b, t, u,
                                                   _opt_ptr(out)))
 
+    def debug_transducer_align_stats():
+        """(calls, utterances): calls of transducer_align / transducer_align_rows that have launched so far and the
+        utterances they took (include/gtn_amd.h: gtnx_batch_transducer_align_stats)"""
+        return _stats2(lib.gtnx_batch_transducer_align_stats)
+
+    def _transducer_align_outs(who, b, t, u, token_frames_out, token_scores_out, frame_tokens_out):
+        """the alignment's outputs beyond the scores, checked where they are tensors; [B, 0] has no address"""
+        for o, dtype, count, what in (
+                (token_frames_out, "torch.int32", b * u, "token_frames_out must be an int32 contiguous tensor [B, U]"),
+                (token_scores_out, "torch.float32", b * u, "token_scores_out must be a float32 contiguous tensor [B, U]"),
+                (frame_tokens_out, "torch.int32", b * t, "frame_tokens_out must be an int32 contiguous tensor [B, T]")):
+            if hasattr(o, "data_ptr") and (str(o.dtype) != dtype or not o.is_contiguous() or o.numel() != count
+                                           or not o.is_cuda):
+                raise ValueError(f"{who}: {what} on the device")
+        return (_transducer_targets(token_frames_out, b, u), _transducer_targets(token_scores_out, b, u),
+                _opt_ptr(frame_tokens_out))
+
+    def transducer_align(logits, targets, frames, target_lengths, scores_out, token_frames_out, token_scores_out=None,
+                         frame_tokens_out=None, rows=None, blank=0, normalize=True, B=None, T=None, U=None, C=None,
+                         dtype=None):
+        """The best alignment of every transcript on its transducer lattice, left on the device
+        (gtnx_batch_transducer_align; DESIGN section 46 holds the contract).  The inputs, the -inf cases and the limits
+        are `transducer_score`'s; the recurrence is its max-plus twin in float32, the blank arc winning a tie.
+        `scores_out`: float32 [B], the best path's score; `token_frames_out`: int32 [B, U], the frame at which token u is
+        emitted, -1 for u >= U_b and without a path; `token_scores_out` (or None): float32 [B, U], the label's log
+        probability there, -inf where the frame is -1; `frame_tokens_out` (or None): int32 [B, T], the column at which
+        the path leaves frame t by its blank, -1 for t >= T_b and without a path.  Every element is stored exactly once.
+        `rows`: the plane `transducer_score` left in `rows_out` for the same inputs, or None (then it is computed: one
+        pass over the logits).  Bfloat16 or float16 `logits` (`dtype=` with a device address) are read as they are
+        (gtnx_batch_transducer_align16).  No copy back, no wait, no autograd."""
+        who = "transducer_align"
+        b, t, u, c, code = _transducer_args(
+            who, logits, targets, frames, target_lengths, blank, (B, T, U, C),
+            [(scores_out, lambda b, t, u, c: b, "scores_out must be a float32 contiguous tensor [B]"),
+             (rows, lambda b, t, u, c: 3 * b * t * (u + 1), "rows must be a float32 contiguous tensor [B, T, U + 1, 3]")],
+            dtype)
+        outs = _transducer_align_outs(who, b, t, u, token_frames_out, token_scores_out, frame_tokens_out)
+        if b == 0 and hasattr(logits, "data_ptr"):
+            return
+        head = (_opt_ptr(logits),) + ((code,) if code else ())
+        check((lib.gtnx_batch_transducer_align16 if code else lib.gtnx_batch_transducer_align)(
+            *head, _transducer_targets(targets, b, u), _opt_ptr(frames), _opt_ptr(target_lengths), b, t, u, c,
+            int(blank), int(bool(normalize)), _opt_ptr(rows), _opt_ptr(scores_out), *outs))
+
+    def transducer_align_rows(rows, frames, target_lengths, scores_out, token_frames_out, token_scores_out=None,
+                              frame_tokens_out=None, B=None, T=None, U=None):
+        """`transducer_align` from a kept compact plane alone (gtnx_batch_transducer_align_rows): `rows` is the float32
+        CUDA tensor [B, T, U + 1, 3] (or a device address with B, T and U) that `transducer_score`, with logits of any
+        of its dtypes, or `transducer_add_score` left in `rows_out`; no logits and no targets are read.  The outputs are
+        `transducer_align`'s."""
+        who = "transducer_align_rows"
+        dims = (B, T, U)
+        if hasattr(rows, "data_ptr"):
+            if (str(rows.dtype) != "torch.float32" or rows.dim() != 4 or rows.shape[3] != 3 or rows.shape[2] < 1
+                    or not rows.is_contiguous() or not rows.is_cuda):
+                raise ValueError(f"{who}: rows must be a float32 contiguous CUDA tensor [B, T, U + 1, 3]")
+            dims = (rows.shape[0], rows.shape[1], rows.shape[2] - 1)
+        if any(d is None for d in dims):
+            raise ValueError(f"{who}: a device address needs B, T and U")
+        b, t, u = (int(d) for d in dims)
+        for o, dtype, count, what in ((frames, "torch.int32", b, "frames must be an int32 contiguous tensor [B]"),
+                                      (target_lengths, "torch.int32", b,
+                                       "target_lengths must be an int32 contiguous tensor [B]"),
+                                      (scores_out, "torch.float32", b,
+                                       "scores_out must be a float32 contiguous tensor [B]")):
+            if hasattr(o, "data_ptr") and (str(o.dtype) != dtype or not o.is_contiguous() or o.numel() != count
+                                           or not o.is_cuda):
+                raise ValueError(f"{who}: {what} on the device")
+        outs = _transducer_align_outs(who, b, t, u, token_frames_out, token_scores_out, frame_tokens_out)
+        if b == 0 and hasattr(rows, "data_ptr"):
+            return
+        check(lib.gtnx_batch_transducer_align_rows(_opt_ptr(rows), _opt_ptr(frames), _opt_ptr(target_lengths), b, t, u,
+                                                   _opt_ptr(scores_out), *outs))
+
     def ctc_loss_step16(emissions, targets, loss_out, grad_out, blank=0, input_lengths=None):
         """One CTC criterion step over 16-bit emissions in one launch (gtnx_batch_ctc_loss_step16 has the contract).
         `emissions`: bfloat16 or float16 CUDA tensor [B, T, C], contiguous, read in place; `targets`: B label sequences;
@@ -2313,6 +2387,9 @@ def make_api(lib):
     ns.transducer_pruned_score_grad = transducer_pruned_score_grad
     ns.debug_transducer_pruned_stats = debug_transducer_pruned_stats
     ns.transducer_occupancy = transducer_occupancy
+    ns.transducer_align = transducer_align
+    ns.transducer_align_rows = transducer_align_rows
+    ns.debug_transducer_align_stats = debug_transducer_align_stats
     ns.ctc_loss_step16 = ctc_loss_step16
     ns.debug_symbolic_route = debug_symbolic_route
     ns.debug_viterbi_ties = debug_viterbi_ties

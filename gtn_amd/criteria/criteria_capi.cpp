@@ -544,6 +544,20 @@ GTN_EXPORT int gtn_transducer_occupancy_n(const void* rows, const void* frames, 
   return guarded([&] { gtn::criteria::transducerOccupancyBatch(rows, frames, target_lengths, B, T, U, occ); });
 }
 
+// The best alignment of every transcript on its transducer lattice.  logits: DEVICE [B][T][U+1][C] of dtype (0: float32,
+// else GTNX_DTYPE_F16 / GTNX_DTYPE_BF16), or null with rows alone; rows: DEVICE float32 [B][T][U+1][3] or null; scores:
+// DEVICE float32 [B]; token_frames: DEVICE int32 [B][U]; token_scores: DEVICE float32 [B][U] or null; frame_tokens:
+// DEVICE int32 [B][T] or null.
+GTN_EXPORT int gtn_transducer_align_n(const void* logits, int dtype, const void* targets, const void* frames,
+                                      const void* target_lengths, int B, int T, int U, int C, int blank, int normalize,
+                                      const void* rows, void* scores, void* token_frames, void* token_scores,
+                                      void* frame_tokens) {
+  return guarded([&] {
+    gtn::criteria::transducerAlignBatch(logits, dtype, targets, frames, target_lengths, B, T, U, C, blank,
+                                        normalize != 0, rows, scores, token_frames, token_scores, frame_tokens);
+  });
+}
+
 // Exact ASG log scores of one device-resident token lattice per utterance.  emissions: DEVICE float32 [B][T][C]; table:
 // DEVICE float32 [C + C*C] as for gtn_asg_score_n; frames: HOST int [B] or null; arcs: DEVICE int32 [B][A][3]; num_arcs /
 // num_nodes: DEVICE int32 [B]; arc_weights: DEVICE float32 [B][A] or null; scores: DEVICE float32 [B].

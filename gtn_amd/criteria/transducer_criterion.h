@@ -288,5 +288,48 @@ inline void transducerOccupancyBatch(
                                static_cast<const int*>(targetLengthsDev), B, T, U, static_cast<float*>(occDev));
 }
 
+/** The best alignment of every transcript on its lattice (gtnx_batch_transducer_align has the contract): the inputs of
+ *  transducerScoreBatch, or of transducerScoreBatch16 with `dtype` GTNX_DTYPE_F16 / GTNX_DTYPE_BF16 (0: float32);
+ *  `scoresDev` device float32 [B], `tokenFramesDev` device int32 [B][U], `tokenScoresDev` device float32 [B][U] or null,
+ *  `frameTokensDev` device int32 [B][T] or null, `rowsDev` the plane a score call left for the same inputs, or null.
+ *  `logitsDev` null: the alignment from `rowsDev` alone (gtnx_batch_transducer_align_rows).  Nothing is copied back. */
+inline void transducerAlignBatch(
+    const void* logitsDev,
+    int dtype,
+    const void* targetsDev,
+    const void* framesDev,
+    const void* targetLengthsDev,
+    int B,
+    int T,
+    int U,
+    int C,
+    int blank,
+    bool normalize,
+    const void* rowsDev,
+    void* scoresDev,
+    void* tokenFramesDev,
+    void* tokenScoresDev = nullptr,
+    void* frameTokensDev = nullptr) {
+  if (!scoresDev) {
+    throw std::invalid_argument("transducerAlignBatch: null scores");
+  }
+  const int* tg = static_cast<const int*>(targetsDev);
+  const int* fr = static_cast<const int*>(framesDev);
+  const int* tl = static_cast<const int*>(targetLengthsDev);
+  const float* rows = static_cast<const float*>(rowsDev);
+  float* sc = static_cast<float*>(scoresDev);
+  int* tf = static_cast<int*>(tokenFramesDev);
+  float* ts = static_cast<float*>(tokenScoresDev);
+  int* ft = static_cast<int*>(frameTokensDev);
+  if (!logitsDev) {
+    batched::transducerAlignRows(rows, fr, tl, B, T, U, sc, tf, ts, ft);
+  } else if (dtype == 0) {
+    batched::transducerAlign(static_cast<const float*>(logitsDev), tg, fr, tl, B, T, U, C, blank, normalize, sc, tf, ts,
+                             ft, rows);
+  } else {
+    batched::transducerAlign16(logitsDev, dtype, tg, fr, tl, B, T, U, C, blank, normalize, sc, tf, ts, ft, rows);
+  }
+}
+
 } // namespace criteria
 } // namespace gtn

@@ -535,6 +535,33 @@ void batch_transducer_pruned_score_grad16(const void* logits_dev, int dtype, con
 // scratch per node, sliced under the same cap.  Two launches per slice (the full sweep, the occupancy kernel).
 void batch_transducer_occupancy(const float* rows_dev, const int* frames_dev, const int* target_lengths_dev, int B,
                                 int T, int U, float* occ_dev);
+// The best alignment of the transcript on the transducer lattice (DESIGN section 46 holds the contract): max-plus over
+// the compact plane of batch_transducer_score's inputs, v[t,u] = max(v[t-1,u] + lp_blank[t-1,u], v[t,u-1] +
+// lp_label[t,u-1]) in float32 with the blank arc winning a tie.  scores_dev float32 [B] = v[T_b-1,U_b] +
+// lp_blank[T_b-1,U_b], -inf exactly in batch_transducer_score's -inf cases; token_frames_dev int32 [B][U], the frame at
+// which token u is emitted (-1 for u >= U_b and without a path); token_scores_dev (or null) float32 [B][U], lp_label
+// there (-inf where the frame is -1); frame_tokens_dev (or null) int32 [B][T], the column at which the path leaves frame
+// t by its blank (-1 for t >= T_b and without a path).  Every element stored exactly once, no memset, never NaN.
+// rows_dev (or null): the plane a score call left for the same inputs; with it the rows launch is skipped.  The
+// refusals are batch_transducer_score's, plus null scores / token_frames (token_frames may be null when U == 0).
+// Pooled scratch per utterance: 12 bytes per node (none with rows_dev), plus 64 T (128 T when U + 1 > 512) for the
+// decision bits where T is above 960 (480) rows, else they live in LDS; sliced under GTNX_TRANSDUCER_SCRATCH_BYTES' cap
+// with the same bits.  Two launches per slice (rows, align), no copy back, no wait, no atomics.
+void batch_transducer_align(const float* logits_dev, const int* targets_dev, const int* frames_dev,
+                            const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
+                            const float* rows_dev, float* scores_dev, int* token_frames_dev, float* token_scores_dev,
+                            int* frame_tokens_dev);
+// the same over bfloat16 / float16 logits (batch_transducer_score16's dtype rules), through transducer16.hip's rows pass
+void batch_transducer_align16(const void* logits_dev, int dtype, const int* targets_dev, const int* frames_dev,
+                              const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
+                              const float* rows_dev, float* scores_dev, int* token_frames_dev, float* token_scores_dev,
+                              int* frame_tokens_dev);
+// the same from a kept plane rows_dev float32 [B][T][U + 1][3] alone, whichever of batch_transducer_score, the 16-bit
+// call or batch_transducer_add_score left it; NaN and +inf in it close the arc.  One launch per slice.
+void batch_transducer_align_rows(const float* rows_dev, const int* frames_dev, const int* target_lengths_dev, int B,
+                                 int T, int U, float* scores_dev, int* token_frames_dev, float* token_scores_dev,
+                                 int* frame_tokens_dev);
+void batch_transducer_align_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
 // The exact ASG log score of one device-resident acyclic token lattice per utterance (batch_ctc_lattice_score's form)
 // under the n emission slabs of a native linear batch and the [C + C * C] table of batch_asg_score, results on the device
 // (DESIGN section 37 holds the contract): scores_dev[b] = log sum over the lattice's paths p of exp(w(p) +

@@ -2024,6 +2024,125 @@ void batch_transducer_occupancy(const float* rows_dev, const int* frames_dev, co
   });
 }
 
+// ---- batched transducer forced alignment: max-plus over the compact plane, results on the device ----
+// (transducer_align.hip)
+namespace {
+Counters g_transducer_align;  // (calls, utterances)
+
+// the three entry points.  x null: the caller's plane is all there is (align_rows); else transducer_impl's checks of the
+// logits, and the rows pass runs per slice unless rows_dev is given
+void transducer_align_impl(const char* who, const void* x, int dtype, const int* targets, const int* frames,
+                           const int* tlen, int B, int T, int U, int C, int blank, int normalize, const float* rows_dev,
+                           float* scores_dev, int* token_frames_dev, float* token_scores_dev, int* frame_tokens_dev,
+                           bool from_rows) {
+  const bool f32 = dtype == GTNX_DTYPE_F32;
+  if (from_rows) {
+    if (!rows_dev || !frames || !tlen) refuse(who, "null input pointer (rows, frames and target_lengths are all read)");
+  } else {
+    if (!x || (!targets && U > 0) || !frames || !tlen)
+      refuse(who, "null input pointer (logits, targets, frames and target_lengths are all read)");
+    if (!f32 && dtype != GTNX_DTYPE_F16 && dtype != GTNX_DTYPE_BF16)
+      refuse(who, "the logits must be GTNX_DTYPE_F16 or GTNX_DTYPE_BF16");
+  }
+  if (!scores_dev || (!token_frames_dev && U > 0)) refuse(who, "null scores or token_frames pointer");
+  if (B < 0) refuse(who, "negative B");
+  if (U < 0 || U + 1 > kTransducerMaxU1) refuse(who, "U + 1 outside 1 .. 1024");
+  if (T < 1 || T > kTransducerMaxT) refuse(who, "T outside 1 .. 65535");
+  if (!from_rows) {
+    if (C < 1 || C > kTransducerMaxC) refuse(who, "C outside 1 .. 2^20");
+    if (blank < 0 || blank >= C) refuse(who, "blank is not one of the C labels");
+  }
+  const int U1 = U + 1;
+  const int64_t per_utt = int64_t(T) * U1;  // nodes
+  if (int64_t(B) * per_utt > std::numeric_limits<int>::max()) refuse(who, "B * T * (U + 1) does not fit an int");
+  if (B == 0) return;
+  Runtime& rt = Runtime::get();
+  if (!from_rows && !ptr_device_memory_of(x, rt.device()))
+    refuse(who, "the logits are not memory of the engine's current device");
+  if (rows_dev && !ptr_device_memory_of(rows_dev, rt.device()))
+    refuse(who, "the rows are not memory of the engine's current device");
+  check_outputs_local(who, {scores_dev, token_frames_dev, token_scores_dev, frame_tokens_dev});
+  TransducerArgs a{};  // the rows pass
+  a.x = f32 ? static_cast<const float*>(x) : nullptr;
+  a.targets = targets;
+  a.frames = frames;
+  a.tlen = tlen;
+  a.T = T;
+  a.U1 = U1;
+  a.C = C;
+  a.blank = blank;
+  a.normalize = normalize ? 1 : 0;
+  TransducerAlignArgs g{};
+  g.frames = frames;
+  g.tlen = tlen;
+  g.scores = scores_dev;
+  g.token_frames = token_frames_dev;
+  g.token_scores = token_scores_dev;
+  g.frame_tokens = frame_tokens_dev;
+  g.T = T;
+  g.U1 = U1;
+  // pooled scratch per utterance: the bit plane where it does not fit LDS (first: 16-byte aligned), then the compact
+  // plane unless the caller brought one.  Algorithmic bytes of the align launch: two of the three values of a node in,
+  // a bit per node out and in again where the plane is global, the outputs.
+  const int64_t plane = int64_t(transducer_align_plane_bytes(T, U1));
+  const int64_t own_rows = rows_dev ? 0 : 12 * per_utt;
+  const double elem = f32 ? 4.0 : 2.0;
+  const double row_in = normalize ? elem * C : 2.0 * elem;
+  const double out_bytes = 4.0 + 4.0 * U * (token_scores_dev ? 3 : 1) + (frame_tokens_dev ? 4.0 * T : 0.0);
+  for_pair_slices(B, plane + own_rows, kTransducerScratch, [&](int64_t b0, int64_t cnt) {
+    const size_t nodes = size_t(per_utt) * size_t(cnt);
+    DevMemP work = rt.alloc(std::max<size_t>(size_t(plane + own_rows) * size_t(cnt), 16));
+    a.utt0 = g.utt0 = int(b0);
+    a.count = g.count = int(cnt);
+    a.rows = rows_dev ? const_cast<float*>(rows_dev) + 3 * per_utt * b0 : work->as<float>(size_t(plane) * size_t(cnt));
+    a.scores = scores_dev;
+    g.rows = a.rows;
+    g.plane = plane ? work->as<char>() : nullptr;
+    if (!rows_dev) {
+      const Transducer16Args h{x, nullptr, targets, frames, tlen, a.rows, nullptr, nullptr, nullptr, nullptr, nullptr,
+                               T, U1, U1, C, blank, a.normalize, a.utt0, a.count, dtype == GTNX_DTYPE_BF16 ? 1 : 0};
+      GTNX_PROF(f32 ? "transducer_rows" : "transducer16_rows", double(nodes) * (row_in + 12.0));
+      if (f32) launch_transducer_rows(a, rt.stream());
+      else launch_transducer16_rows(h, rt.stream());
+    }
+    GTNX_PROF("transducer_align", double(nodes) * 8.0 + double(cnt) * (double(plane) * 2.0 + out_bytes));
+    launch_transducer_align(g, rt.stream());
+  });
+  g_transducer_align.add(1, B);
+}
+}  // namespace
+
+void batch_transducer_align_stats(int64_t* calls, int64_t* utterances) { g_transducer_align.get(calls, utterances); }
+
+void batch_transducer_align(const float* logits_dev, const int* targets_dev, const int* frames_dev,
+                            const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
+                            const float* rows_dev, float* scores_dev, int* token_frames_dev, float* token_scores_dev,
+                            int* frame_tokens_dev) {
+  GTNX_HOST_T("batch.transducer_align");
+  transducer_align_impl("gtnx_batch_transducer_align", logits_dev, GTNX_DTYPE_F32, targets_dev, frames_dev,
+                        target_lengths_dev, B, T, U, C, blank, normalize, rows_dev, scores_dev, token_frames_dev,
+                        token_scores_dev, frame_tokens_dev, false);
+}
+
+void batch_transducer_align16(const void* logits_dev, int dtype, const int* targets_dev, const int* frames_dev,
+                              const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
+                              const float* rows_dev, float* scores_dev, int* token_frames_dev, float* token_scores_dev,
+                              int* frame_tokens_dev) {
+  GTNX_HOST_T("batch.transducer_align16");
+  transducer_align_impl("gtnx_batch_transducer_align16", logits_dev, dtype16_only(dtype), targets_dev, frames_dev,
+                        target_lengths_dev, B, T, U, C, blank, normalize, rows_dev, scores_dev, token_frames_dev,
+                        token_scores_dev, frame_tokens_dev, false);
+}
+
+void batch_transducer_align_rows(const float* rows_dev, const int* frames_dev, const int* target_lengths_dev, int B,
+                                 int T, int U, float* scores_dev, int* token_frames_dev, float* token_scores_dev,
+                                 int* frame_tokens_dev) {
+  GTNX_HOST_T("batch.transducer_align_rows");
+  transducer_align_impl("gtnx_batch_transducer_align_rows", nullptr, GTNX_DTYPE_F32, nullptr, frames_dev,
+                        target_lengths_dev, B, T, U, 1, 0, 0, rows_dev, scores_dev, token_frames_dev, token_scores_dev,
+                        frame_tokens_dev, true);
+}
+
 // ---- batched ASG score of one device-resident token lattice per utterance, and its gradients (asg_lattice.hip) ----
 namespace {
 Counters g_asg_lattice;  // (calls, utterances)

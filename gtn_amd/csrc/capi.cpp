@@ -1329,6 +1329,48 @@ GTNX_API gtnx_status_t gtnx_batch_transducer_pruned_score_grad16(const void* log
                                          static_cast<const float*>(rows_device));
   });
 }
+GTNX_API gtnx_status_t gtnx_batch_transducer_align(const void* logits_device, const void* targets_device,
+                                                   const void* frames_device, const void* target_lengths_device,
+                                                   int B, int T, int U, int C, int blank, int normalize,
+                                                   const void* rows_device, void* scores_device,
+                                                   void* token_frames_device, void* token_scores_device,
+                                                   void* frame_tokens_device) {
+  return guard([&] {
+    batch_transducer_align(static_cast<const float*>(logits_device), static_cast<const int*>(targets_device),
+                           static_cast<const int*>(frames_device), static_cast<const int*>(target_lengths_device), B, T,
+                           U, C, blank, normalize, static_cast<const float*>(rows_device),
+                           static_cast<float*>(scores_device), static_cast<int*>(token_frames_device),
+                           static_cast<float*>(token_scores_device), static_cast<int*>(frame_tokens_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_transducer_align16(const void* logits_device, int dtype, const void* targets_device,
+                                                     const void* frames_device, const void* target_lengths_device,
+                                                     int B, int T, int U, int C, int blank, int normalize,
+                                                     const void* rows_device, void* scores_device,
+                                                     void* token_frames_device, void* token_scores_device,
+                                                     void* frame_tokens_device) {
+  return guard([&] {
+    batch_transducer_align16(logits_device, dtype, static_cast<const int*>(targets_device),
+                             static_cast<const int*>(frames_device), static_cast<const int*>(target_lengths_device), B,
+                             T, U, C, blank, normalize, static_cast<const float*>(rows_device),
+                             static_cast<float*>(scores_device), static_cast<int*>(token_frames_device),
+                             static_cast<float*>(token_scores_device), static_cast<int*>(frame_tokens_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_transducer_align_rows(const void* rows_device, const void* frames_device,
+                                                        const void* target_lengths_device, int B, int T, int U,
+                                                        void* scores_device, void* token_frames_device,
+                                                        void* token_scores_device, void* frame_tokens_device) {
+  return guard([&] {
+    batch_transducer_align_rows(static_cast<const float*>(rows_device), static_cast<const int*>(frames_device),
+                                static_cast<const int*>(target_lengths_device), B, T, U,
+                                static_cast<float*>(scores_device), static_cast<int*>(token_frames_device),
+                                static_cast<float*>(token_scores_device), static_cast<int*>(frame_tokens_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_transducer_align_stats(int64_t* calls, int64_t* utterances) {
+  return guard([&] { batch_transducer_align_stats(calls, utterances); });
+}
 GTNX_API gtnx_status_t gtnx_batch_transducer_occupancy(const void* rows_device, const void* frames_device,
                                                        const void* target_lengths_device, int B, int T, int U,
                                                        void* occ_device) {

@@ -1305,6 +1305,26 @@ struct Transducer16Args {
 };
 void launch_transducer16_rows(const Transducer16Args& a, hipStream_t st);
 void launch_transducer16_grad(const Transducer16Args& a, hipStream_t st);
+// transducer_align.hip: the best alignment of the transcript on the full lattice, max-plus over the compact plane `rows`
+// that launch_transducer_rows, launch_transducer16_rows or launch_transducer_add_norm left for the slice (the contract:
+// DESIGN section 46).  One wave per utterance and one launch: the sweep keeps one decision bit per node, the walk and
+// the outputs follow in the same wave.  scores / token_frames / token_scores / frame_tokens are indexed by the utterance
+// in the whole batch; every element of the slice's utterances is stored exactly once (-inf, -1 without a path).
+//   plane:  scratch for the bit plane, transducer_align_plane_bytes(T, U1) bytes per utterance of the slice, 16-byte
+//           aligned; that function returns 0 where the plane lives in LDS, and `plane` is then not looked at.
+struct TransducerAlignArgs {
+  const GTNX_G float* rows;      // [count][T][U1][3]
+  const GTNX_G int* frames;      // [n]
+  const GTNX_G int* tlen;        // [n]
+  GTNX_G void* plane;            // [count][T][64] words of 1 or 2 bytes, or unused
+  GTNX_G float* scores;          // [n]
+  GTNX_G int* token_frames;      // [n][U1 - 1]
+  GTNX_G float* token_scores;    // [n][U1 - 1] or null
+  GTNX_G int* frame_tokens;      // [n][T] or null
+  int T, U1, utt0, count;
+};
+size_t transducer_align_plane_bytes(int T, int U1);
+void launch_transducer_align(const TransducerAlignArgs& a, hipStream_t st);
 // asg_lattice.hip: the ASG log score of the utterances utt0 .. utt0 + count - 1, each with one acyclic token lattice of its
 // own in device memory (ctc_lattice.hip's form), under asg_score.hip's [C + C * C] table, and the gradients g[b] * d
 // score[b] / d (emissions_b, table, arc weights of b) (the contract: DESIGN section 37).  The states are the arcs; an

@@ -60,6 +60,7 @@ _ARGTYPES = {
     "gtn_transducer_pruned_score16_n": [_P, _I] + [_P] * 4 + [_I] * 7 + [_P, _P],
     "gtn_transducer_pruned_score_grad16_n": [_P, _I] + [_P] * 4 + [_I] * 7 + [_P, _P, _P],
     "gtn_transducer_occupancy_n": [_P, _P, _P, _I, _I, _I, _P],
+    "gtn_transducer_align_n": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "gtn_asg_lattice_score_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "gtn_asg_lattice_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "gtn_asg_lattice_align_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
@@ -1812,6 +1813,101 @@ def transducer_occupancy(rows, input_lengths, target_lengths):
             gtn.transducer_occupancy(r.data_ptr(), fr.data_ptr(), tl.data_ptr(), occ.data_ptr(), B=B, T=T, U=U1 - 1)
         _engine_done(stream)
     return occ
+
+
+def _transducer_align_run(who, x, rows, tg, fr, tl, shape, blank, normalize, return_token_scores, return_frame_tokens):
+    """the one engine call behind transducer_align (x: the logits) and transducer_align_rows (x None)"""
+    B, T, U, C_ = shape
+    dev = fr.device
+    scores = torch.empty(B, dtype=torch.float32, device=dev)
+    token_frames = torch.empty(B, U, dtype=torch.int32, device=dev)
+    token_scores = torch.empty(B, U, dtype=torch.float32, device=dev) if return_token_scores else None
+    frame_tokens = torch.empty(B, T, dtype=torch.int32, device=dev) if return_frame_tokens else None
+    if B:
+        stream = _engine_stream(dev)
+        code = 0 if x is None or x.dtype == torch.float32 else _DTYPE16[x.dtype]
+        outs = (scores.data_ptr(), token_frames.data_ptr() if U else None,
+                token_scores.data_ptr() if U and token_scores is not None else None, _ptr(frame_tokens))
+        tgp = tg.data_ptr() if tg is not None and tg.numel() else None
+        if _has_native(who, "gtn_transducer_align_n"):
+            _call("gtn_transducer_align_n", _ptr(x), code, tgp, fr.data_ptr(), tl.data_ptr(), B, T, U, C_, blank,
+                  int(normalize), _ptr(rows), *outs)
+        elif x is None:
+            gtn.transducer_align_rows(rows.data_ptr(), fr.data_ptr(), tl.data_ptr(), *outs, B=B, T=T, U=U)
+        else:
+            gtn.transducer_align(x.data_ptr(), tgp, fr.data_ptr(), tl.data_ptr(), *outs, _ptr(rows), blank, normalize,
+                                 B=B, T=T, U=U, C=C_, dtype=x.dtype)
+        _engine_done(stream)
+    out = (scores, token_frames)
+    if return_token_scores:
+        out += (token_scores,)
+    if return_frame_tokens:
+        out += (frame_tokens,)
+    return out
+
+
+def _transducer_align_rows_arg(who, rows, B, T, U1):
+    if not (torch.is_tensor(rows) and rows.dtype == torch.float32 and tuple(rows.shape) == (B, T, U1, 3)):
+        raise ValueError(f"{who}: rows must be a float32 tensor [{B}, {T}, {U1}, 3]")
+    return rows.detach().contiguous()
+
+
+def transducer_align(logits, targets, input_lengths, target_lengths, blank=0, normalize=True, rows=None,
+                     return_token_scores=False, return_frame_tokens=False):
+    """The best alignment of targets[b, :U_b] on the transducer lattice of logits[b, :T_b]: the max-plus twin of
+    transducer_score over the same inputs (float32, bfloat16 or float16 logits [B, T, U + 1, C], read in place), in
+    float32 with the blank arc winning a tie.  Returns (scores, token_frames[, token_scores][, frame_tokens]):
+    scores float32 [B], the best path's score, -inf exactly in transducer_score's -inf cases; token_frames int32 [B, U],
+    the frame at which token u is emitted, non-decreasing, -1 for u >= U_b and without a path; token_scores float32
+    [B, U], the label's log probability there, -inf where the frame is -1; frame_tokens int32 [B, T], the column at
+    which the path leaves frame t by its blank, -1 for t >= T_b and without a path.  `rows`: the float32 [B, T, U + 1, 3]
+    plane gtn_amd.transducer_score left in `rows_out` for the same inputs; with it the logits are not read.  Nothing is
+    downloaded; not differentiable.  Runs on the caller's stream."""
+    who = "transducer_align"
+    x = logits
+    if not (torch.is_tensor(x) and x.dim() == 4 and (x.dtype == torch.float32 or x.dtype in _DTYPE16)
+            and x.shape[2] >= 1):
+        raise ValueError(f"{who}: logits must be a float32 tensor [B, T, U + 1, C] (or bfloat16 / float16)")
+    B, T, U1, C_ = x.shape
+    idx = _transducer_index_args(who, ((targets, "targets", (B, U1 - 1)), (input_lengths, "input_lengths", (B,)),
+                                       (target_lengths, "target_lengths", (B,))))
+    if U1 > 1024 or not 1 <= T <= 65535 or not 1 <= C_ <= 1 << 20 or B * T * U1 >= 1 << 31:
+        raise ValueError(f"{who}: U + 1 <= 1024, 1 <= T <= 65535, C <= 2^20 and B * T * (U + 1) < 2^31 are required")
+    if not 0 <= int(blank) < C_:
+        raise ValueError(f"{who}: blank must be one of the {C_} labels")
+    r = None if rows is None else _transducer_align_rows_arg(who, rows, B, T, U1)
+    for t, what in zip([x] + idx + ([r] if r is not None else []),
+                       ("logits", "targets", "input_lengths", "target_lengths", "rows")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {what} must be a CUDA tensor (the alignment is computed on the device)")
+        if t.device != x.device:
+            raise ValueError(f"{who}: all tensors must be on one device")
+    tg, fr, tl = (t.detach().to(torch.int32).contiguous() for t in idx)
+    return _transducer_align_run(who, x.detach().contiguous(), r, tg, fr, tl, (B, T, U1 - 1, C_), int(blank),
+                                 bool(normalize), return_token_scores, return_frame_tokens)
+
+
+def transducer_align_rows(rows, input_lengths, target_lengths, return_token_scores=False, return_frame_tokens=False):
+    """transducer_align from a kept compact plane alone: `rows` is the float32 CUDA tensor [B, T, U + 1, 3] that
+    gtn_amd.transducer_score (logits of any of its dtypes) or gtn_amd.transducer_add_score left in `rows_out`, so an
+    additive joint is aligned without its joint tensor and a training step's saved plane gives time stamps without
+    another pass over the logits.  No logits and no targets are read.  Returns what transducer_align returns."""
+    who = "transducer_align_rows"
+    if not (torch.is_tensor(rows) and rows.dim() == 4 and rows.shape[2] >= 1):
+        raise ValueError(f"{who}: rows must be a float32 tensor [B, T, U + 1, 3]")
+    B, T, U1, _ = rows.shape
+    r = _transducer_align_rows_arg(who, rows, B, T, U1)
+    idx = _transducer_index_args(who, ((input_lengths, "input_lengths", (B,)), (target_lengths, "target_lengths", (B,))))
+    if U1 > 1024 or not 1 <= T <= 65535 or B * T * U1 >= 1 << 31:
+        raise ValueError(f"{who}: U + 1 <= 1024, 1 <= T <= 65535 and B * T * (U + 1) < 2^31 are required")
+    for t, what in zip([r] + idx, ("rows", "input_lengths", "target_lengths")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {what} must be a CUDA tensor (the alignment is computed on the device)")
+        if t.device != r.device:
+            raise ValueError(f"{who}: all tensors must be on one device")
+    fr, tl = (t.detach().to(torch.int32).contiguous() for t in idx)
+    return _transducer_align_run(who, None, r, None, fr, tl, (B, T, U1 - 1, 1), 0, False, return_token_scores,
+                                 return_frame_tokens)
 
 
 def transducer_prune_ranges(occ, input_lengths, target_lengths, S):

@@ -509,6 +509,38 @@ inline void transducerOccupancy(const float* rowsDevice, const int* framesDevice
                                 int T, int U, float* occDevice) {
   detail::check(gtnx_batch_transducer_occupancy(rowsDevice, framesDevice, targetLengthsDevice, B, T, U, occDevice));
 }
+/** The best alignment of every transcript on its transducer lattice, left on the device: transducerScore's inputs and
+ *  -inf cases, its max-plus twin in float32 with the blank arc winning a tie.  scoresDevice float32 [B], the best path's
+ *  score; tokenFramesDevice int32 [B][U], the frame at which token u is emitted (-1 for u >= U_b and without a path);
+ *  tokenScoresDevice (or null) float32 [B][U], the label's log probability there (-inf where the frame is -1);
+ *  frameTokensDevice (or null) int32 [B][T], the column at which the path leaves frame t by its blank (-1 for t >= T_b
+ *  and without a path).  Every element stored once.  rowsDevice (or null): the plane transducerScore left for the same
+ *  inputs.  No copy back, no wait -- gtnx_batch_transducer_align */
+inline void transducerAlign(const float* logitsDevice, const int* targetsDevice, const int* framesDevice,
+                            const int* targetLengthsDevice, int B, int T, int U, int C, int blank, bool normalize,
+                            float* scoresDevice, int* tokenFramesDevice, float* tokenScoresDevice = nullptr,
+                            int* frameTokensDevice = nullptr, const float* rowsDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_align(logitsDevice, targetsDevice, framesDevice, targetLengthsDevice, B, T, U, C,
+                                            blank, normalize ? 1 : 0, rowsDevice, scoresDevice, tokenFramesDevice,
+                                            tokenScoresDevice, frameTokensDevice));
+}
+/** transducerAlign over bfloat16 / float16 logits (transducerScore16's dtype) -- gtnx_batch_transducer_align16 */
+inline void transducerAlign16(const void* logitsDevice, int dtype, const int* targetsDevice, const int* framesDevice,
+                              const int* targetLengthsDevice, int B, int T, int U, int C, int blank, bool normalize,
+                              float* scoresDevice, int* tokenFramesDevice, float* tokenScoresDevice = nullptr,
+                              int* frameTokensDevice = nullptr, const float* rowsDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_align16(logitsDevice, dtype, targetsDevice, framesDevice, targetLengthsDevice, B,
+                                              T, U, C, blank, normalize ? 1 : 0, rowsDevice, scoresDevice,
+                                              tokenFramesDevice, tokenScoresDevice, frameTokensDevice));
+}
+/** transducerAlign from a kept plane alone: rowsDevice float32 [B][T][U + 1][3] as transducerScore, transducerScore16 or
+ *  transducerAddScore left it; no logits, no targets -- gtnx_batch_transducer_align_rows */
+inline void transducerAlignRows(const float* rowsDevice, const int* framesDevice, const int* targetLengthsDevice, int B,
+                                int T, int U, float* scoresDevice, int* tokenFramesDevice,
+                                float* tokenScoresDevice = nullptr, int* frameTokensDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_align_rows(rowsDevice, framesDevice, targetLengthsDevice, B, T, U, scoresDevice,
+                                                 tokenFramesDevice, tokenScoresDevice, frameTokensDevice));
+}
 /** The exact ASG log score of one device-resident acyclic token lattice per utterance (ctcLatticeScore's lattices) under
  *  the slabs of a Batch::linear and asgScore's table, results left on the device: scoresDevice[b] = log sum over the
  *  lattice's paths p of exp(w(p) + asgScore(emissions_b[0 .. T_b), table, labels(p))), nothing subtracted.  The states

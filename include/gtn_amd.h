@@ -968,6 +968,45 @@ gtnx_status_t gtnx_batch_transducer_pruned_score_grad16(const void* logits_devic
  * scratch 8 bytes per node, sliced as above; launches per slice: transducer.hip's sweep, the occupancy kernel. */
 gtnx_status_t gtnx_batch_transducer_occupancy(const void* rows_device, const void* frames_device,
                                               const void* target_lengths_device, int B, int T, int U, void* occ_device);
+/* The BEST ALIGNMENT of the transcript on the transducer lattice, the max-plus half of gtnx_batch_transducer_score
+ * (DESIGN section 46), with the inputs, lp, -inf cases and refusals of that call:
+ *   v[0,0] = 0;  v[t,u] = max(v[t-1,u] + lp[t-1,u,blank], v[t,u-1] + lp[t,u-1,y[u-1]])   in float32, as written;
+ *   of two equal candidates the blank arc from t-1 wins; a -inf candidate never wins against a finite one;
+ *   scores_device        float32 [B]    = v[T_b-1,U_b] + lp[T_b-1,U_b,blank], -inf exactly where no finite path exists;
+ *   token_frames_device  int32   [B][U]: the frame t at which token u is emitted (the label arc out of (t,u) on the best
+ *                        path), non-decreasing in u; -1 for u >= U_b and for every u of an utterance without a path;
+ *   token_scores_device  float32 [B][U] or null: lp[token_frames[u], u, y[u]]; -inf where token_frames is -1;
+ *   frame_tokens_device  int32   [B][T] or null: the column u at which the path leaves frame t by its blank,
+ *                        non-decreasing, U_b at t = T_b-1; -1 for t >= T_b and without a path.
+ * Every element of every output passed is stored exactly once (no memset); never NaN; rows t >= T_b and columns u > U_b
+ * of the inputs are never read; no atomics; the same bits run to run, sliced or not, whatever an utterance's neighbours
+ * are, with or without rows_device.  rows_device (or null): the float32 [B][T][U+1][3] plane a score call left for the
+ * SAME inputs; with it the rows launch is skipped.  GTNX_INVALID_ARGUMENT before a device is asked for:
+ * gtnx_batch_transducer_score's refusals, a null scores_device, a null token_frames_device with U > 0.  Launches per
+ * slice: the rows kernel of transducer.hip, then transducer_align.hip's one kernel (one wave per utterance: sweep with
+ * one decision bit per node, walk, outputs).  Pooled scratch per utterance: 12 bytes per node (none with rows_device)
+ * and, only where T is above 960 rows (480 with U+1 > 512), 64 T (128 T) bytes of decision bits; below that they live
+ * in LDS.  Sliced under GTNX_TRANSDUCER_SCRATCH_BYTES' cap.  No copy back, no wait. */
+gtnx_status_t gtnx_batch_transducer_align(const void* logits_device, const void* targets_device,
+                                          const void* frames_device, const void* target_lengths_device, int B, int T,
+                                          int U, int C, int blank, int normalize, const void* rows_device,
+                                          void* scores_device, void* token_frames_device, void* token_scores_device,
+                                          void* frame_tokens_device);
+/* The same over bfloat16 / float16 logits (gtnx_batch_transducer_score16's dtype rules and rows kernel). */
+gtnx_status_t gtnx_batch_transducer_align16(const void* logits_device, int dtype, const void* targets_device,
+                                            const void* frames_device, const void* target_lengths_device, int B, int T,
+                                            int U, int C, int blank, int normalize, const void* rows_device,
+                                            void* scores_device, void* token_frames_device, void* token_scores_device,
+                                            void* frame_tokens_device);
+/* The same from a kept plane alone: rows_device float32 [B][T][U+1][3] as gtnx_batch_transducer_score, the 16-bit call
+ * or gtnx_batch_transducer_add_score left it (so the additive joint aligns without its joint tensor).  No logits, no
+ * targets; NaN or +inf in the plane closes the arc.  The refusals about B, T, U and null pointers; one launch per slice. */
+gtnx_status_t gtnx_batch_transducer_align_rows(const void* rows_device, const void* frames_device,
+                                               const void* target_lengths_device, int B, int T, int U,
+                                               void* scores_device, void* token_frames_device,
+                                               void* token_scores_device, void* frame_tokens_device);
+/* calls of the three above that have launched so far (process-wide) / utterances they took */
+gtnx_status_t gtnx_batch_transducer_align_stats(int64_t* calls, int64_t* utterances);
 /* The exact ASG log score of ONE ACYCLIC TOKEN LATTICE PER UTTERANCE -- gtnx_batch_ctc_lattice_score's lattices under
  * gtnx_batch_asg_score's criterion:
  *   scores[b] = log sum over the lattice's paths p of exp(w(p) + asg_score(emissions_b[0 .. T_b), table, labels(p))),
