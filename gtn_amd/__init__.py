@@ -78,6 +78,9 @@ edit_distance = _api.edit_distance  # (batched Levenshtein distance of device-re
 transducer_score = _api.transducer_score  # (batched transducer / RNN-T log score over device-resident joint logits)
 transducer_score_grad = _api.transducer_score_grad  # (its gradient under per-utterance weights, every row written)
 debug_transducer_stats = _api.debug_transducer_stats  # (transducer_score / _grad: calls that launched, utterances)
+transducer_tdt_score = _api.transducer_tdt_score  # (token-and-duration transducer score over [B, T, U + 1, C + D] logits)
+transducer_tdt_score_grad = _api.transducer_tdt_score_grad  # (its gradient, token and duration parts, every row written)
+debug_transducer_tdt_stats = _api.debug_transducer_tdt_stats  # (transducer_tdt_score / _grad: calls, utterances)
 transducer_add_score = _api.transducer_add_score  # (the same score under an additive joint am + lm, never formed)
 transducer_add_score_grad = _api.transducer_add_score_grad  # (its gradients for am and lm, every element written)
 debug_transducer_add_stats = _api.debug_transducer_add_stats  # (transducer_add_score / _grad: calls, utterances)

@@ -190,6 +190,9 @@ _SIGS = {
     "gtnx_batch_transducer_score_grad": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "gtnx_batch_transducer_stats": [c_i64_p, c_i64_p],
+    "gtnx_batch_transducer_tdt_score": [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_float, C.c_void_p, C.c_void_p],
+    "gtnx_batch_transducer_tdt_score_grad": [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_float] + [C.c_void_p] * 3,
+    "gtnx_batch_transducer_tdt_stats": [c_i64_p, c_i64_p],
     "gtnx_batch_transducer_add_score": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                         C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
     "gtnx_batch_transducer_add_score_grad": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

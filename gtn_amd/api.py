@@ -2016,6 +2016,90 @@ def make_api(lib):
             *head, _transducer_targets(targets, b, u), _opt_ptr(frames), _opt_ptr(target_lengths), b, t, u, c,
             int(blank), int(bool(normalize)), _opt_ptr(weights), _opt_ptr(grad_out), _opt_ptr(rows)))
 
+    def debug_transducer_tdt_stats():
+        """(calls, utterances): calls of transducer_tdt_score / transducer_tdt_score_grad that have launched so far and
+        the utterances they took (include/gtn_amd.h: gtnx_batch_transducer_tdt_stats)"""
+        return _stats2(lib.gtnx_batch_transducer_tdt_stats)
+
+    def _transducer_tdt_args(who, logits, targets, frames, target_lengths, blank, sigma, D, dims, outs):
+        """(B, T, U, C) of a TDT call: from `logits` [B, T, U + 1, C + D] and D when it is a tensor, else from `dims`.
+        The tensors among the arguments are checked against them; `outs` as _transducer_args', all float32."""
+        d = int(D)
+        if not 2 <= d <= 8:
+            raise ValueError(f"{who}: D must be in 2 .. 8")
+        if not (float(sigma) >= 0.0 and float(sigma) < float("inf")):
+            raise ValueError(f"{who}: sigma must be finite and >= 0")
+        if hasattr(logits, "data_ptr"):
+            if str(logits.dtype) != "torch.float32" or logits.dim() != 4 or not logits.is_contiguous() \
+                    or logits.shape[3] <= d:
+                raise ValueError(f"{who}: logits must be a float32 contiguous tensor [B, T, U + 1, C + D]")
+            shape = (logits.shape[0], logits.shape[1], logits.shape[2] - 1, logits.shape[3] - d)
+            for dim, have, want in zip("BTUC", dims, shape):
+                if have is not None and int(have) != want:
+                    raise ValueError(f"{who}: {dim} = {have} is not what logits says ({want})")
+            dims = shape
+        if any(x is None for x in dims):
+            raise ValueError(f"{who}: a device address needs B, T, U and C")
+        b, t, u, c = (int(x) for x in dims)
+        if not 0 <= int(blank) < max(c, 1):
+            raise ValueError(f"{who}: blank must be one of the {c} tokens")
+        checks = [(logits, None, "logits"),
+                  (targets, ("torch.int32", b * u), "targets must be an int32 contiguous tensor [B, U]"),
+                  (frames, ("torch.int32", b), "frames must be an int32 contiguous tensor [B]"),
+                  (target_lengths, ("torch.int32", b), "target_lengths must be an int32 contiguous tensor [B]")]
+        checks += [(o, ("torch.float32", n(b, t, u, c, d)), w) for o, n, w in outs]
+        tensors = [(o, want, what) for o, want, what in checks if o is not None and hasattr(o, "data_ptr")]
+        for o, want, what in tensors:
+            if want and (str(o.dtype) != want[0] or not o.is_contiguous() or o.numel() != want[1]):
+                raise ValueError(f"{who}: {what}")
+        for o, want, what in tensors:  # (a host tensor's address means nothing to the kernel)
+            if hasattr(o, "is_cuda") and not o.is_cuda:
+                raise ValueError(f"{who}: {what.split()[0]} must be a CUDA tensor")
+        return b, t, u, c, d
+
+    def transducer_tdt_score(logits, targets, frames, target_lengths, scores_out, D, rows_out=None, blank=0, sigma=0.0,
+                             B=None, T=None, U=None, C=None):
+        """The token-and-duration transducer (TDT) log score of every utterance over device-resident joint logits, left
+        on the device (gtnx_batch_transducer_tdt_score; DESIGN section 47 holds the contract).  `logits`: float32 CUDA
+        tensor [B, T, U + 1, C + D], contiguous -- C token logits (blank included), then the logits of durations
+        0 .. D - 1 -- or a device address with B, T, U and C; `D` (2 .. 8) is always given.  `targets`, `frames`,
+        `target_lengths` and the -inf cases as `transducer_score`.  Every arc jumps its duration's frames (blanks 1 ..
+        D - 1, labels 0 .. D - 1) and weighs log_softmax(tokens) - `sigma` + log_softmax(durations).  `rows_out` (float32
+        [B, T, U + 1, D + 4] or None) keeps (lp_blank, lp_label, lse_tok, lse_dur, lp_dur[0 .. D-1]) of every live node
+        for `transducer_tdt_score_grad`.  No copy back, no wait."""
+        who = "transducer_tdt_score"
+        b, t, u, c, d = _transducer_tdt_args(
+            who, logits, targets, frames, target_lengths, blank, sigma, D, (B, T, U, C),
+            [(scores_out, lambda b, t, u, c, d: b, "scores_out must be a float32 contiguous tensor [B]"),
+             (rows_out, lambda b, t, u, c, d: (d + 4) * b * t * (u + 1),
+              "rows_out must be a float32 contiguous tensor [B, T, U + 1, D + 4]")])
+        if b == 0 and hasattr(logits, "data_ptr"):
+            return  # (no utterance, nothing to launch -- and an empty tensor has no address to hand to the engine)
+        check(lib.gtnx_batch_transducer_tdt_score(
+            _opt_ptr(logits), _transducer_targets(targets, b, u), _opt_ptr(frames), _opt_ptr(target_lengths), b, t, u, c,
+            d, int(blank), float(sigma), _opt_ptr(scores_out), _opt_ptr(rows_out)))
+
+    def transducer_tdt_score_grad(logits, targets, frames, target_lengths, weights, grad_out, D, rows=None, blank=0,
+                                  sigma=0.0, B=None, T=None, U=None, C=None):
+        """The gradient of the scores of `transducer_tdt_score` under `weights` (float32 [B] on the device), in one
+        stateless call (gtnx_batch_transducer_tdt_score_grad): `grad_out` (float32 [B, T, U + 1, C + D]) = weights[b] * d
+        score[b] / d logits[b], token and duration parts, every row stored exactly once -- the never-read rows, those of
+        an utterance that scores -inf and dead rows with zeros.  `rows`: the plane `transducer_tdt_score` left in
+        `rows_out` for the same inputs and sigma, or None (then it is recomputed).  No atomics, the same bits run to run."""
+        who = "transducer_tdt_score_grad"
+        b, t, u, c, d = _transducer_tdt_args(
+            who, logits, targets, frames, target_lengths, blank, sigma, D, (B, T, U, C),
+            [(weights, lambda b, t, u, c, d: b, "weights must be a float32 contiguous tensor [B]"),
+             (grad_out, lambda b, t, u, c, d: b * t * (u + 1) * (c + d),
+              "grad_out must be a float32 contiguous tensor [B, T, U + 1, C + D]"),
+             (rows, lambda b, t, u, c, d: (d + 4) * b * t * (u + 1),
+              "rows must be a float32 contiguous tensor [B, T, U + 1, D + 4]")])
+        if b == 0 and hasattr(logits, "data_ptr"):
+            return
+        check(lib.gtnx_batch_transducer_tdt_score_grad(
+            _opt_ptr(logits), _transducer_targets(targets, b, u), _opt_ptr(frames), _opt_ptr(target_lengths), b, t, u, c,
+            d, int(blank), float(sigma), _opt_ptr(weights), _opt_ptr(grad_out), _opt_ptr(rows)))
+
     def debug_transducer_add_stats():
         """(calls, utterances): calls of transducer_add_score / transducer_add_score_grad that have launched so far and
         the utterances they took (include/gtn_amd.h: gtnx_batch_transducer_add_stats)"""
@@ -2380,6 +2464,9 @@ def make_api(lib):
     ns.transducer_score = transducer_score
     ns.transducer_score_grad = transducer_score_grad
     ns.debug_transducer_stats = debug_transducer_stats
+    ns.transducer_tdt_score = transducer_tdt_score
+    ns.transducer_tdt_score_grad = transducer_tdt_score_grad
+    ns.debug_transducer_tdt_stats = debug_transducer_tdt_stats
     ns.transducer_add_score = transducer_add_score
     ns.transducer_add_score_grad = transducer_add_score_grad
     ns.debug_transducer_add_stats = debug_transducer_add_stats

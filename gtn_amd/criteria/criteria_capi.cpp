@@ -457,6 +457,28 @@ GTN_EXPORT int gtn_transducer_score_grad_n(const void* logits, const void* targe
   });
 }
 
+// Token-and-duration transducer (TDT) log scores.  logits: DEVICE float32 [B][T][U+1][C+D]; rows: DEVICE float32
+// [B][T][U+1][D+4] or null; the rest as gtn_transducer_score_n.
+GTN_EXPORT int gtn_transducer_tdt_score_n(const void* logits, const void* targets, const void* frames,
+                                          const void* target_lengths, int B, int T, int U, int C, int D, int blank,
+                                          float sigma, void* scores, void* rows) {
+  return guarded([&] {
+    gtn::criteria::transducerTdtScoreBatch(logits, targets, frames, target_lengths, B, T, U, C, D, blank, sigma, scores,
+                                           rows);
+  });
+}
+
+// ... and their gradient under weights: DEVICE float32 [B]: grad (DEVICE float32 [B][T][U+1][C+D], every row written);
+// rows: the plane gtn_transducer_tdt_score_n left for the same inputs, or null.
+GTN_EXPORT int gtn_transducer_tdt_score_grad_n(const void* logits, const void* targets, const void* frames,
+                                               const void* target_lengths, int B, int T, int U, int C, int D, int blank,
+                                               float sigma, const void* weights, void* grad, const void* rows) {
+  return guarded([&] {
+    gtn::criteria::transducerTdtScoreGradBatch(logits, targets, frames, target_lengths, B, T, U, C, D, blank, sigma,
+                                               weights, grad, rows);
+  });
+}
+
 // Transducer log scores under an additive joint.  am: DEVICE float32 [B][T][C]; lm: DEVICE float32 [B][U+1][C]; the
 // rest as gtn_transducer_score_n, always normalised.
 GTN_EXPORT int gtn_transducer_add_score_n(const void* am, const void* lm, const void* targets, const void* frames,

@@ -60,6 +60,57 @@ inline void transducerScoreGradBatch(
                                static_cast<const float*>(rowsDev));
 }
 
+/** The token-and-duration transducer (TDT) log scores: `logitsDev` device float32 [B][T][U + 1][C + D] (C token logits,
+ *  then D duration logits); `rowsDev` device float32 [B][T][U + 1][D + 4] or null; the rest as transducerScoreBatch.
+ *  gtnx_batch_transducer_tdt_score has the contract.  Nothing is copied back. */
+inline void transducerTdtScoreBatch(
+    const void* logitsDev,
+    const void* targetsDev,
+    const void* framesDev,
+    const void* targetLengthsDev,
+    int B,
+    int T,
+    int U,
+    int C,
+    int D,
+    int blank,
+    float sigma,
+    void* scoresDev,
+    void* rowsDev = nullptr) {
+  if (!scoresDev) {
+    throw std::invalid_argument("transducerTdtScoreBatch: null scores");
+  }
+  batched::transducerTdtScore(static_cast<const float*>(logitsDev), static_cast<const int*>(targetsDev),
+                              static_cast<const int*>(framesDev), static_cast<const int*>(targetLengthsDev), B, T, U, C,
+                              D, blank, sigma, static_cast<float*>(scoresDev), static_cast<float*>(rowsDev));
+}
+
+/** Their gradient under `weightsDev` (device float32 [B]): `gradDev` device float32 [B][T][U + 1][C + D], every row
+ *  written; `rowsDev` the plane transducerTdtScoreBatch left for the same inputs, or null (then it is recomputed). */
+inline void transducerTdtScoreGradBatch(
+    const void* logitsDev,
+    const void* targetsDev,
+    const void* framesDev,
+    const void* targetLengthsDev,
+    int B,
+    int T,
+    int U,
+    int C,
+    int D,
+    int blank,
+    float sigma,
+    const void* weightsDev,
+    void* gradDev,
+    const void* rowsDev = nullptr) {
+  if (!weightsDev || !gradDev) {
+    throw std::invalid_argument("transducerTdtScoreGradBatch: null weights or gradient");
+  }
+  batched::transducerTdtScoreGrad(static_cast<const float*>(logitsDev), static_cast<const int*>(targetsDev),
+                                  static_cast<const int*>(framesDev), static_cast<const int*>(targetLengthsDev), B, T, U,
+                                  C, D, blank, sigma, static_cast<const float*>(weightsDev),
+                                  static_cast<float*>(gradDev), static_cast<const float*>(rowsDev));
+}
+
 /** The same scores under an additive joint: `amDev` device float32 [B][T][C] and `lmDev` device float32 [B][U + 1][C]
  *  stand for the logits amDev[b][t][c] + lmDev[b][u][c], which are never formed; always normalised.
  *  gtnx_batch_transducer_add_score has the contract and the float32 domain.  Nothing is copied back. */

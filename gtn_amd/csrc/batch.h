@@ -472,6 +472,24 @@ void batch_transducer_score_grad(const float* logits_dev, const int* targets_dev
                                  const int* target_lengths_dev, int B, int T, int U, int C, int blank, int normalize,
                                  const float* weights_dev, float* grad_dev, const float* rows_dev);
 void batch_transducer_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
+// The token-and-duration transducer (TDT) log score (DESIGN section 47 holds the contract): logits_dev float32
+// [B][T][U + 1][C + D], C token logits then the logits of durations 0 .. D - 1; lp_tok = log_softmax(row[:C]) - sigma,
+// lp_dur = log_softmax(row[C:]); a blank arc of duration d = 1 .. D-1 goes to (t + d, u), a label arc of duration
+// d = 0 .. D-1 to (t + d, u + 1), the blank arcs out of column U_b that land on row T_b end the path.  The -inf cases
+// and the index inputs are batch_transducer_score's.  rows_dev (or null): float32 [B][T][U + 1][D + 4], gets
+// (lp_blank, lp_label, lse_tok, lse_dur, lp_dur[0 .. D-1]) of every live node.  Invalid argument before a device is asked
+// for: batch_transducer_score's, D outside 2 .. 8, C + D above 2^20, a sigma that is negative or not finite.  Pooled
+// scratch 4 (D + 4) bytes per node without rows, sliced under GTNX_TRANSDUCER_SCRATCH_BYTES.  Two launches per slice.
+void batch_transducer_tdt_score(const float* logits_dev, const int* targets_dev, const int* frames_dev,
+                                const int* target_lengths_dev, int B, int T, int U, int C, int D, int blank, float sigma,
+                                float* scores_dev, float* rows_dev);
+// The gradient grad_dev [B][T][U + 1][C + D] = weights_dev[b] * d score[b] / d logits[b], both segments of every row
+// stored exactly once, the never-read ones with zeros.  rows_dev (or null): the plane batch_transducer_tdt_score left;
+// with it the rows launch is skipped.  8 more bytes of pooled scratch per node.  No floating-point atomics.
+void batch_transducer_tdt_score_grad(const float* logits_dev, const int* targets_dev, const int* frames_dev,
+                                     const int* target_lengths_dev, int B, int T, int U, int C, int D, int blank,
+                                     float sigma, const float* weights_dev, float* grad_dev, const float* rows_dev);
+void batch_transducer_tdt_stats(int64_t* calls, int64_t* utterances);  // calls that launched / utterances they took
 // The same score under an ADDITIVE joint, logits z[b,t,u,c] = am[b,t,c] + lm[b,u,c] that are never formed (DESIGN section
 // 43 holds the contract): am_dev float32 [B][T][C], lm_dev float32 [B][U + 1][C], the rest as batch_transducer_score;
 // always normalised.  The normaliser is a float32 matrix product of exponentials: the accuracy holds while every live

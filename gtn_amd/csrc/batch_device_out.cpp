@@ -2143,6 +2143,103 @@ void batch_transducer_align_rows(const float* rows_dev, const int* frames_dev, c
                         frame_tokens_dev, true);
 }
 
+// ---- batched token-and-duration transducer (TDT) score over joint logits [B][T][U+1][C+D], and its gradient ----
+// (transducer_tdt.hip)
+namespace {
+Counters g_transducer_tdt;  // (calls, utterances)
+static_assert(kTransducerTdtMinD == 2 && kTransducerTdtMaxD == 8, "the texts say 2 .. 8");
+
+// both entry points, as transducer_impl: scores_dev for the score, weights_dev and grad_dev for the gradient
+void transducer_tdt_impl(const char* who, const float* x, const int* targets, const int* frames, const int* tlen, int B,
+                         int T, int U, int C, int D, int blank, float sigma, float* scores_dev, float* rows_dev,
+                         const float* weights_dev, float* grad_dev) {
+  const bool want_grad = scores_dev == nullptr;
+  // what the arguments alone decide comes first: no device is asked for an invalid call
+  if (!x || (!targets && U > 0) || !frames || !tlen)
+    refuse(who, "null input pointer (logits, targets, frames and target_lengths are all read)");
+  if (want_grad && (!weights_dev || !grad_dev)) refuse(who, "null weights or grad pointer");
+  if (B < 0) refuse(who, "negative B");
+  if (U < 0 || U + 1 > kTransducerMaxU1) refuse(who, "U + 1 outside 1 .. 1024");
+  if (T < 1 || T > kTransducerMaxT) refuse(who, "T outside 1 .. 65535");
+  if (D < kTransducerTdtMinD || D > kTransducerTdtMaxD) refuse(who, "D outside 2 .. 8");
+  if (C < 1 || C > kTransducerMaxC - D) refuse(who, "C < 1 or C + D above 2^20");
+  if (blank < 0 || blank >= C) refuse(who, "blank is not one of the C tokens");
+  if (!(sigma >= 0.0f) || !(sigma < std::numeric_limits<float>::infinity()))
+    refuse(who, "sigma must be finite and >= 0");
+  const int U1 = U + 1;
+  const int64_t per_utt = int64_t(T) * U1;  // nodes
+  if (int64_t(B) * per_utt > std::numeric_limits<int>::max()) refuse(who, "B * T * (U + 1) does not fit an int");
+  if (B == 0) return;
+  Runtime& rt = Runtime::get();
+  if (!ptr_device_memory_of(x, rt.device())) refuse(who, "the logits are not memory of the engine's current device");
+  check_outputs_local(who, {scores_dev, grad_dev, want_grad ? nullptr : rows_dev});
+  TransducerTdtArgs a{};
+  a.x = x;
+  a.targets = targets;
+  a.frames = frames;
+  a.tlen = tlen;
+  a.weights = weights_dev;
+  a.grad = grad_dev;
+  a.sigma = sigma;
+  a.T = T;
+  a.U1 = U1;
+  a.C = C;
+  a.D = D;
+  a.blank = blank;
+  DevMemP sc;  // (the gradient's scores: a slice's own, read by its gradient launch)
+  if (want_grad) sc = rt.alloc(sizeof(float) * size_t(B));
+  a.scores = want_grad ? sc->as<float>() : scores_dev;
+  // algorithmic bytes (the counts are device memory: an upper bound).  rows: every logit once, D + 4 floats out.  sweep:
+  // per direction the D + 2 log-probabilities in, one plane out.  grad: every logit in and every gradient out, the plane
+  // row, alpha and up to 2 D - 1 betas in.
+  const int P = D + 4;
+  const int64_t own_rows = rows_dev ? 0 : 4 * P;
+  const int64_t per_bytes = per_utt * (own_rows + (want_grad ? 8 : 0));
+  for_pair_slices(B, per_bytes, kTransducerScratch, [&](int64_t b0, int64_t cnt) {
+    const size_t nodes = size_t(per_utt) * size_t(cnt);
+    DevMemP work = rt.alloc(std::max<size_t>(size_t(per_bytes) * size_t(cnt), 16));
+    a.utt0 = int(b0);
+    a.count = int(cnt);
+    a.rows = rows_dev ? rows_dev + int64_t(P) * per_utt * b0 : work->as<float>();
+    a.alpha = want_grad ? work->as<float>(size_t(own_rows) * nodes) : nullptr;
+    a.beta = want_grad ? work->as<float>(size_t(own_rows + 4) * nodes) : nullptr;
+    if (!(want_grad && rows_dev)) {
+      GTNX_PROF("transducer_tdt_rows", double(nodes) * 4.0 * (C + D + P));
+      launch_transducer_tdt_rows(a, rt.stream());
+    }
+    {
+      GTNX_PROF("transducer_tdt_sweep", double(nodes) * (want_grad ? 2.0 : 1.0) * 4.0 * (D + 3) + 4.0 * double(cnt));
+      launch_transducer_tdt_sweep(a, rt.stream());
+    }
+    if (want_grad) {
+      GTNX_PROF("transducer_tdt_grad", double(nodes) * 4.0 * (2.0 * (C + D) + P + 2 * D));
+      launch_transducer_tdt_grad(a, rt.stream());
+    }
+    // (the planes go back to the stream-ordered pool behind the launches)
+  });
+  g_transducer_tdt.add(1, B);
+}
+}  // namespace
+
+void batch_transducer_tdt_stats(int64_t* calls, int64_t* utterances) { g_transducer_tdt.get(calls, utterances); }
+
+void batch_transducer_tdt_score(const float* logits_dev, const int* targets_dev, const int* frames_dev,
+                                const int* target_lengths_dev, int B, int T, int U, int C, int D, int blank, float sigma,
+                                float* scores_dev, float* rows_dev) {
+  GTNX_HOST_T("batch.transducer_tdt_score");
+  if (!scores_dev) throw_invalid("[gtnx_batch_transducer_tdt_score] null scores pointer");
+  transducer_tdt_impl("gtnx_batch_transducer_tdt_score", logits_dev, targets_dev, frames_dev, target_lengths_dev, B, T, U,
+                      C, D, blank, sigma, scores_dev, rows_dev, nullptr, nullptr);
+}
+
+void batch_transducer_tdt_score_grad(const float* logits_dev, const int* targets_dev, const int* frames_dev,
+                                     const int* target_lengths_dev, int B, int T, int U, int C, int D, int blank,
+                                     float sigma, const float* weights_dev, float* grad_dev, const float* rows_dev) {
+  GTNX_HOST_T("batch.transducer_tdt_score_grad");
+  transducer_tdt_impl("gtnx_batch_transducer_tdt_score_grad", logits_dev, targets_dev, frames_dev, target_lengths_dev, B,
+                      T, U, C, D, blank, sigma, nullptr, const_cast<float*>(rows_dev), weights_dev, grad_dev);
+}
+
 // ---- batched ASG score of one device-resident token lattice per utterance, and its gradients (asg_lattice.hip) ----
 namespace {
 Counters g_asg_lattice;  // (calls, utterances)

@@ -1219,6 +1219,34 @@ GTNX_API gtnx_status_t gtnx_batch_transducer_score_grad(const void* logits_devic
 GTNX_API gtnx_status_t gtnx_batch_transducer_stats(int64_t* calls, int64_t* utterances) {
   return guard([&] { batch_transducer_stats(calls, utterances); });
 }
+GTNX_API gtnx_status_t gtnx_batch_transducer_tdt_score(const void* logits_device, const void* targets_device,
+                                                       const void* frames_device, const void* target_lengths_device,
+                                                       int B, int T, int U, int C, int D, int blank, float sigma,
+                                                       void* scores_device, void* rows_device) {
+  return guard([&] {
+    batch_transducer_tdt_score(static_cast<const float*>(logits_device), static_cast<const int*>(targets_device),
+                               static_cast<const int*>(frames_device), static_cast<const int*>(target_lengths_device),
+                               B, T, U, C, D, blank, sigma, static_cast<float*>(scores_device),
+                               static_cast<float*>(rows_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_transducer_tdt_score_grad(const void* logits_device, const void* targets_device,
+                                                            const void* frames_device,
+                                                            const void* target_lengths_device, int B, int T, int U,
+                                                            int C, int D, int blank, float sigma,
+                                                            const void* weights_device, void* grad_device,
+                                                            const void* rows_device) {
+  return guard([&] {
+    batch_transducer_tdt_score_grad(static_cast<const float*>(logits_device), static_cast<const int*>(targets_device),
+                                    static_cast<const int*>(frames_device),
+                                    static_cast<const int*>(target_lengths_device), B, T, U, C, D, blank, sigma,
+                                    static_cast<const float*>(weights_device), static_cast<float*>(grad_device),
+                                    static_cast<const float*>(rows_device));
+  });
+}
+GTNX_API gtnx_status_t gtnx_batch_transducer_tdt_stats(int64_t* calls, int64_t* utterances) {
+  return guard([&] { batch_transducer_tdt_stats(calls, utterances); });
+}
 GTNX_API gtnx_status_t gtnx_batch_transducer_add_score(const void* am_device, const void* lm_device,
                                                        const void* targets_device, const void* frames_device,
                                                        const void* target_lengths_device, int B, int T, int U, int C,

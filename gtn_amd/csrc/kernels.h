@@ -1325,6 +1325,34 @@ struct TransducerAlignArgs {
 };
 size_t transducer_align_plane_bytes(int T, int U1);
 void launch_transducer_align(const TransducerAlignArgs& a, hipStream_t st);
+// transducer_tdt.hip: the token-and-duration transducer (TDT) log score over joint logits x [n][T][U1][C + D] -- C token
+// logits, then the logits of durations 0 .. D - 1 -- and the gradient weights[b] * d score[b] / d x[b] (the contract:
+// DESIGN section 47).  Live nodes, slices and plane indexing as TransducerArgs'.
+//   rows:   per live node D + 4 floats at rows[(D + 4) * node]: (lp_blank - sigma, lp_label - sigma, lse_tok, lse_dur,
+//           lp_dur[0 .. D-1]); lp_label is -inf at u == U_b and for a token outside 0 .. C - 1 or equal to blank; a row
+//           with a dead segment (NaN, +inf, nothing finite) gets -inf in every log-probability and 0 in both lse.
+//   sweep:  one wave per utterance and direction: alpha (always; writes scores[b]) and, with `beta` non-null, beta.
+//           `alpha` null: nothing but the score is stored.
+//   grad:   every row of grad[b] for the slice's utterances, the never-read ones with zeros.
+constexpr int kTransducerTdtMinD = 2;
+constexpr int kTransducerTdtMaxD = 8;
+struct TransducerTdtArgs {
+  const GTNX_G float* x;         // [n][T][U1][C + D]
+  const GTNX_G int* targets;     // [n][U1 - 1]
+  const GTNX_G int* frames;      // [n]
+  const GTNX_G int* tlen;        // [n]
+  GTNX_G float* rows;            // [count][T][U1][D + 4]
+  GTNX_G float* alpha;           // [count][T][U1] or null
+  GTNX_G float* beta;            // [count][T][U1] or null
+  GTNX_G float* scores;          // [n]
+  const GTNX_G float* weights;   // [n] (grad)
+  GTNX_G float* grad;            // [n][T][U1][C + D] (grad)
+  float sigma;
+  int T, U1, C, D, blank, utt0, count;
+};
+void launch_transducer_tdt_rows(const TransducerTdtArgs& a, hipStream_t st);
+void launch_transducer_tdt_sweep(const TransducerTdtArgs& a, hipStream_t st);
+void launch_transducer_tdt_grad(const TransducerTdtArgs& a, hipStream_t st);
 // asg_lattice.hip: the ASG log score of the utterances utt0 .. utt0 + count - 1, each with one acyclic token lattice of its
 // own in device memory (ctc_lattice.hip's form), under asg_score.hip's [C + C * C] table, and the gradients g[b] * d
 // score[b] / d (emissions_b, table, arc weights of b) (the contract: DESIGN section 37).  The states are the arcs; an

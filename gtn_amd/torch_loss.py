@@ -51,6 +51,8 @@ _ARGTYPES = {
     "gtn_asg_full_score_grad_n": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
     "gtn_transducer_score_n": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "gtn_transducer_score_grad_n": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "gtn_transducer_tdt_score_n": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P],
+    "gtn_transducer_tdt_score_grad_n": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P],
     "gtn_transducer_add_score_n": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
     "gtn_transducer_add_score_grad_n": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "gtn_transducer_pruned_score_n": [_P] * 5 + [_I] * 7 + [_P, _P],
@@ -1562,6 +1564,110 @@ def transducer_loss(logits, targets, input_lengths, target_lengths, blank=0, nor
     if reduction not in ("none", "sum", "mean"):
         raise ValueError('transducer_loss: reduction must be "none", "sum" or "mean"')
     loss = -transducer_score(logits, targets, input_lengths, target_lengths, blank, normalize)
+    return loss if reduction == "none" else (loss.sum() if reduction == "sum" else loss.mean())
+
+
+class _TransducerTdtScore(torch.autograd.Function):
+    """_TransducerScore for the token-and-duration lattice: forward keeps the plane [B, T, U + 1, D + 4] where the logits
+    require grad; backward is the one gradient call with grad_out as the weights."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, frames, tlen, D, blank, sigma):
+        x = logits.detach().contiguous()
+        B, T, U1, CD = x.shape
+        stream = _engine_stream(x.device)
+        scores = torch.empty(B, dtype=torch.float32, device=x.device)
+        rows = torch.empty(B, T, U1, D + 4, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[0] else None
+        if B:
+            args = (targets.data_ptr() if targets.numel() else None, frames.data_ptr(), tlen.data_ptr())
+            if _has_native("transducer_tdt_score", "gtn_transducer_tdt_score_n"):
+                _call("gtn_transducer_tdt_score_n", x.data_ptr(), *args, B, T, U1 - 1, CD - D, D, blank, sigma,
+                      scores.data_ptr(), _ptr(rows))
+            else:
+                gtn.transducer_tdt_score(x.data_ptr(), *args, scores.data_ptr(), D, _ptr(rows), blank, sigma, B=B, T=T,
+                                         U=U1 - 1, C=CD - D)
+        _engine_done(stream)
+        ctx.save_for_backward(x, targets, frames, tlen, rows)
+        ctx.args = (D, blank, sigma)
+        return scores
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, targets, frames, tlen, rows = ctx.saved_tensors
+        D, blank, sigma = ctx.args
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None, None
+        B, T, U1, CD = x.shape
+        grad = torch.empty_like(x)
+        if B:
+            g = grad_out.detach().to(torch.float32).contiguous()
+            stream = _engine_stream(x.device)
+            args = (targets.data_ptr() if targets.numel() else None, frames.data_ptr(), tlen.data_ptr())
+            if _native():
+                _call("gtn_transducer_tdt_score_grad_n", x.data_ptr(), *args, B, T, U1 - 1, CD - D, D, blank, sigma,
+                      g.data_ptr(), grad.data_ptr(), _ptr(rows))
+            else:
+                gtn.transducer_tdt_score_grad(x.data_ptr(), *args, g.data_ptr(), grad.data_ptr(), D, _ptr(rows), blank,
+                                              sigma, B=B, T=T, U=U1 - 1, C=CD - D)
+            _engine_done(stream)
+        return grad, None, None, None, None, None, None
+
+
+def transducer_tdt_score(logits, targets, input_lengths, target_lengths, num_durations, blank=0, sigma=0.0):
+    """The token-and-duration transducer (TDT) log score of a padded batch over joint logits, differentiable.  logits:
+    float32 CUDA tensor [B, T, U + 1, C + num_durations], read in place: C token logits (blank included), then the logits
+    of durations 0 .. num_durations - 1 (2 <= num_durations <= 8).  The kernel takes one log-softmax over each part of
+    every live row; a blank arc of duration d >= 1 goes from (t, u) to (t + d, u), a label arc of duration d >= 0 to
+    (t + d, u + 1), each weighing lp_tok - sigma + lp_dur[d]; a path ends with a blank arc out of column U_b that lands
+    exactly on frame T_b.  targets, input_lengths, target_lengths, the limits and the -inf cases are transducer_score's.
+    Returns float32 [B].  The backward is one call with grad_out as per-utterance weights and has the same bits run to
+    run (no atomics); where the logits require grad the forward keeps 4 (num_durations + 4) bytes per node.  Runs on the
+    caller's stream."""
+    who = "transducer_tdt_score"
+    x = logits
+    D = int(num_durations)
+    if not 2 <= D <= 8:
+        raise ValueError(f"{who}: num_durations must be 2 .. 8")
+    if not (torch.is_tensor(x) and x.dim() == 4 and x.dtype == torch.float32 and x.shape[2] >= 1 and x.shape[3] > D):
+        raise ValueError(f"{who}: logits must be a float32 tensor [B, T, U + 1, C + num_durations]")
+    B, T, U1, CD = x.shape
+    if not (torch.is_tensor(targets) and targets.dtype in (torch.int32, torch.int64)
+            and tuple(targets.shape) == (B, U1 - 1)):
+        raise ValueError(f"{who}: targets must be an int32 or int64 tensor [{B}, {U1 - 1}]")
+    for t, what in ((input_lengths, "input_lengths"), (target_lengths, "target_lengths")):
+        if not (torch.is_tensor(t) and t.dtype in (torch.int32, torch.int64) and tuple(t.shape) == (B,)):
+            raise ValueError(f"{who}: {what} must be an int32 or int64 tensor [{B}]")
+    if U1 > 1024:
+        raise ValueError(f"{who}: U + 1 must be 1 .. 1024")
+    if not 1 <= T <= 65535:
+        raise ValueError(f"{who}: T must be 1 .. 65535")
+    if CD > 1 << 20:
+        raise ValueError(f"{who}: C + num_durations must be at most 2^20")
+    if B * T * U1 >= 1 << 31:
+        raise ValueError(f"{who}: B * T * (U + 1) must be below 2^31")
+    if not 0 <= int(blank) < CD - D:
+        raise ValueError(f"{who}: blank must be one of the {CD - D} tokens")
+    if not (float(sigma) >= 0.0 and float(sigma) < float("inf")):
+        raise ValueError(f"{who}: sigma must be finite and >= 0")
+    for t, what in ((x, "logits"), (targets, "targets"), (input_lengths, "input_lengths"),
+                    (target_lengths, "target_lengths")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{who}: {what} must be a CUDA tensor (the scores are computed on the device)")
+        if t.device != x.device:
+            raise ValueError(f"{who}: all tensors must be on one device")
+    tg = targets.detach().to(torch.int32).contiguous()  # (int64 values are converted on the device)
+    fr = input_lengths.detach().to(torch.int32).contiguous()
+    tl = target_lengths.detach().to(torch.int32).contiguous()
+    return _TransducerTdtScore.apply(x, tg, fr, tl, D, int(blank), float(sigma))
+
+
+def transducer_tdt_loss(logits, targets, input_lengths, target_lengths, num_durations, blank=0, sigma=0.0,
+                        reduction="mean"):
+    """-transducer_tdt_score(...): float32 [B] with reduction "none", their sum with "sum", their mean over the batch
+    with "mean".  An utterance without a path has loss +inf."""
+    if reduction not in ("none", "sum", "mean"):
+        raise ValueError('transducer_tdt_loss: reduction must be "none", "sum" or "mean"')
+    loss = -transducer_tdt_score(logits, targets, input_lengths, target_lengths, num_durations, blank, sigma)
     return loss if reduction == "none" else (loss.sum() if reduction == "sum" else loss.mean())
 
 

@@ -421,6 +421,26 @@ inline void transducerScoreGrad(const float* logitsDevice, const int* targetsDev
   detail::check(gtnx_batch_transducer_score_grad(logitsDevice, targetsDevice, framesDevice, targetLengthsDevice, B, T, U,
                                                  C, blank, normalize ? 1 : 0, weightsDevice, gradDevice, rowsDevice));
 }
+/** The token-and-duration transducer (TDT) log score: logitsDevice float32 [B][T][U + 1][C + D], C token logits then
+ *  the logits of durations 0 .. D - 1 (2 <= D <= 8); every arc jumps its duration's frames and weighs lp_tok - sigma +
+ *  lp_dur, two softmaxes per row.  Index inputs and -inf cases as transducerScore.  rowsDevice (or null): float32
+ *  [B][T][U + 1][D + 4], keeps the compact plane for transducerTdtScoreGrad -- gtnx_batch_transducer_tdt_score */
+inline void transducerTdtScore(const float* logitsDevice, const int* targetsDevice, const int* framesDevice,
+                               const int* targetLengthsDevice, int B, int T, int U, int C, int D, int blank, float sigma,
+                               float* scoresDevice, float* rowsDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_tdt_score(logitsDevice, targetsDevice, framesDevice, targetLengthsDevice, B, T, U,
+                                                C, D, blank, sigma, scoresDevice, rowsDevice));
+}
+/** The gradient of transducerTdtScore under the weights weightsDevice [B]: gradDevice float32 [B][T][U + 1][C + D], every
+ *  row stored exactly once.  rowsDevice (or null): the plane transducerTdtScore left for the same inputs.  Stateless and
+ *  bit-repeatable, sliced or not (no atomics) -- gtnx_batch_transducer_tdt_score_grad */
+inline void transducerTdtScoreGrad(const float* logitsDevice, const int* targetsDevice, const int* framesDevice,
+                                   const int* targetLengthsDevice, int B, int T, int U, int C, int D, int blank,
+                                   float sigma, const float* weightsDevice, float* gradDevice,
+                                   const float* rowsDevice = nullptr) {
+  detail::check(gtnx_batch_transducer_tdt_score_grad(logitsDevice, targetsDevice, framesDevice, targetLengthsDevice, B, T,
+                                                     U, C, D, blank, sigma, weightsDevice, gradDevice, rowsDevice));
+}
 /** transducerScore under an additive joint, logits am[b,t,c] + lmDevice[b,u,c] that are never formed: amDevice float32
  *  [B][T][C], lmDevice float32 [B][U + 1][C]; always normalised; everything else as transducerScore.  The normaliser is
  *  a float32 matrix product of exponentials: accurate while every live row of am and lm spans at most 40 nats, -inf

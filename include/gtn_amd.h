@@ -866,6 +866,47 @@ gtnx_status_t gtnx_batch_transducer_score_grad(const void* logits_device, const 
                                                const void* rows_device);
 /* calls of either kind that have launched so far (process-wide) / utterances they took */
 gtnx_status_t gtnx_batch_transducer_stats(int64_t* calls, int64_t* utterances);
+/* The token-and-duration transducer (TDT) log score of B utterances over device-resident joint logits (DESIGN section
+ * 47).  logits_device: float32 [B][T][U+1][C+D], contiguous, read in place: entries 0 .. C-1 of a row are token logits
+ * (blank included), entries C .. C+D-1 the logits of durations 0 .. D-1.  Per live node (t < T_b, u <= U_b):
+ *   lp_tok = log_softmax(row[:C]) - sigma,   lp_dur = log_softmax(row[C:])
+ *   blank arc, d = 1 .. D-1: weight lp_tok[blank] + lp_dur[d], to (t+d, u) if t+d < T_b, to the end if u == U_b and
+ *                            t+d == T_b;
+ *   label arc, d = 0 .. D-1, u < U_b: weight lp_tok[y[u]] + lp_dur[d], to (t+d, u+1) if t+d < T_b;
+ *   any other arc overshoots and carries no path.  alpha[0,0] = 0, alpha[t,u] = log-sum over the incoming arcs,
+ *   scores[b] = logadd over d = 1 .. min(D-1, T_b) of alpha[T_b-d, U_b] + lp_tok[blank] + lp_dur[d] at (T_b-d, U_b).
+ * targets_device, frames_device, target_lengths_device and the -inf cases (never NaN) are gtnx_batch_transducer_score's;
+ * a live row either of whose segments holds NaN or +inf, or nothing finite, is a node no path leaves.
+ * rows_device (or null): float32 [B][T][U+1][D+4]; gets (lp_blank, lp_label, lse_tok, lse_dur, lp_dur[0 .. D-1]) of every
+ * live node, the first two with -sigma in them, for gtnx_batch_transducer_tdt_score_grad.
+ * GTNX_INVALID_ARGUMENT before a device is asked for: a null pointer, a negative B, U+1 outside 1 .. 1024, T outside
+ * 1 .. 65535, D outside 2 .. 8, C < 1, C+D above 2^20, blank outside 0 .. C-1, a sigma that is negative or not finite,
+ * B*T*(U+1) >= 2^31.  B == 0 returns without touching a device.  Launches on the engine's stream (transducer_tdt.hip:
+ * rows, sweep), per slice of at most 256 MiB of pooled scratch (4 (D+4) bytes per node; none with rows_device); no copy
+ * back, no wait.  The same bits run to run, sliced or not, whatever an utterance's neighbours are, with or without
+ * rows_device. */
+gtnx_status_t gtnx_batch_transducer_tdt_score(const void* logits_device, const void* targets_device,
+                                              const void* frames_device, const void* target_lengths_device, int B,
+                                              int T, int U, int C, int D, int blank, float sigma, void* scores_device,
+                                              void* rows_device);
+/* The gradient of those scores under caller-supplied weights_device (float32 [B]; grad_out under autograd):
+ *   grad_device float32 [B][T][U+1][C+D] = weights[b] * d scores[b] / d logits[b].  With the arc occupancies ob_d, ol_d
+ *   = exp(alpha + arc weight + beta[target] - score) (beta of the end 0), OB = sum ob_d, OL = sum ol_d:
+ *     token c:    w * ([c == blank] OB + [c == y[u]] OL - exp(row[c] - lse_tok) * (OB + OL))
+ *     duration d: w * (ob_d + ol_d - exp(lp_dur[d]) * (OB + OL))
+ * EVERY row is stored exactly once by the gradient launch itself (there is no memset): the never-read rows, the rows
+ * of an utterance that scores -inf and dead rows with zeros.  rows_device (or null): the plane the score call left in
+ * it for the SAME inputs and sigma; with it the pass that recomputes the plane is skipped.  The same refusals as the
+ * score call.  Pooled scratch: 4 (D+4) + 8 bytes per node (8 with rows_device), sliced over utterances under the 256 MiB
+ * cap with the same bits (GTNX_TRANSDUCER_SCRATCH_BYTES, read per call, lowers the cap: a debug switch).  Launches per
+ * slice: rows, sweep (alpha and beta side by side), gradient.  No floating-point atomics. */
+gtnx_status_t gtnx_batch_transducer_tdt_score_grad(const void* logits_device, const void* targets_device,
+                                                   const void* frames_device, const void* target_lengths_device, int B,
+                                                   int T, int U, int C, int D, int blank, float sigma,
+                                                   const void* weights_device, void* grad_device,
+                                                   const void* rows_device);
+/* calls of either kind that have launched so far (process-wide) / utterances they took */
+gtnx_status_t gtnx_batch_transducer_tdt_stats(int64_t* calls, int64_t* utterances);
 /* The transducer log score under an ADDITIVE joint, without the joint tensor:
  *   z[b,t,u,c] = am[b,t,c] + lm[b,u,c]   (never formed),   scores[b] = gtnx_batch_transducer_score's on z, normalised.
  * am_device: float32 [B][T][C]; lm_device: float32 [B][U+1][C]; both contiguous, read in place; the other arguments, the
